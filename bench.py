@@ -13,11 +13,18 @@ the recording-by-recording shape of round 1.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (HIP events recorded on
-the plan's stream inside the timed region); `pipeline` is the same algorithmic-bytes figure
-over the whole step; `cpu_baseline` is the CPU oracle (the C restatement of the reference's
-scalar loops, 1 thread — the reference decode is single-threaded) timed on this host on the
-same recording, and it doubles as a bit-exact parity check of the GPU output.
+Rank 0 prints ONE JSON line.  A plain run does only what the headline needs: it sets up, runs the untimed
+steps (`--pre-steps`, `--settle-steps`, then W warm-up steps), times exactly K steps and prints `value`,
+`ms_per_step` and the workload.  `--full` adds everything else, as before: the per-kernel measurement
+passes, `roofline` for the dominant kernel (HIP events recorded on the plan's stream inside the timed
+region), `pipeline` (the same algorithmic-bytes figure over the whole step), `power`, the extra legs
+(PCM16 ingest, image stage, host-fed, one-shot), the sustained front end, the fast-mode leg, and
+`cpu_baseline`: the CPU oracle (the C restatement of the reference's scalar loops, 1 thread — the
+reference decode is single-threaded) timed on this host on the same recording, which doubles as a
+bit-exact parity check of the GPU output.
+
+`--dump-outputs DIR` writes what the last timed step handed its caller (rows, result records, sync
+positions of every recording of the call) as .npy files: see dump_last_step().
 """
 import argparse
 import json
@@ -32,6 +39,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md: 8.0 TB/s; ~6.3 achievable)
+DUMP_ROW_BYTES = 48 << 20  # --dump-outputs: rows of the last step beyond this are sampled (64 MB in all at most)
 
 
 class _QuietStdout:
@@ -224,6 +232,43 @@ def run_config4(args):
         dist.destroy_process_group()
 
 
+def synth_inputs(rate, seconds, seeds):
+    """synth_apt() of every seed, on up to 16 host threads (numpy releases the GIL in the large array operations);
+    each recording depends on its own seed only, so the arrays are the same as one after another."""
+    from concurrent.futures import ThreadPoolExecutor
+    from noaa_apt_amd.testing.synth import synth_apt
+    cpus = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    with ThreadPoolExecutor(max(1, min(16, cpus, len(seeds)))) as ex:
+        return list(ex.map(lambda s: synth_apt(rate, seconds, seed=s), seeds))
+
+
+def dump_last_step(out_dir, prefix, plan, results, d_rows, rec_ids, sync):
+    """--dump-outputs: what the last timed step handed its caller, one set of files per recording of the call, named
+    by the recording's input index (<prefix>recNNN_*.npy): the result record (status, reason, n_rows, n_sync, work_len,
+    n_out; float64), the sync positions (float64) and the rows (float32, n_rows x 2080).  When the call's rows exceed
+    DUMP_ROW_BYTES, every recording keeps the same number of rows, chosen by a generator seeded with its input index
+    (their indices: _rows_index.npy)."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    width = 2080
+    per_rec = max(width, DUMP_ROW_BYTES // 4 // max(1, len(results)))  # floats of rows kept per recording
+    for b, (r, rec) in enumerate(zip(results, rec_ids)):
+        stem = os.path.join(out_dir, f"{prefix}rec{rec:03d}")
+        np.save(f"{stem}_result.npy", np.array([r.status, r.reason, r.n_rows, r.n_sync, r.work_len, r.n_out], np.float64))
+        pos = plan.sync_positions(b) if sync else np.zeros(0, np.uint64)
+        np.save(f"{stem}_sync_pos.npy", pos.astype(np.float64))
+        n_out = int(r.n_out)
+        rows = d_rows[b][:n_out]
+        if n_out > per_rec:
+            n_rows = n_out // width
+            idx = np.sort(np.random.default_rng(rec).choice(n_rows, per_rec // width, replace=False))
+            rows = rows[:n_rows * width].view(n_rows, width).index_select(0, torch.from_numpy(idx).to(rows.device))
+            np.save(f"{stem}_rows_index.npy", idx.astype(np.float64))
+        elif n_out % width == 0:
+            rows = rows.view(-1, width)
+        np.save(f"{stem}_rows.npy", rows.cpu().numpy().astype(np.float32))
+
+
 def tuned_settings(apt, args):
     """The profile's Settings with the --set overrides applied."""
     settings = apt.Settings.profile(args.profile)
@@ -280,8 +325,18 @@ def main():
                          "eight, device-resident and host-fed; shares of GPUs that are not there are marked 'not measured'")
     ap.add_argument("--recordings", type=int, default=256)
     ap.add_argument("--node-gpus", type=int, default=8, help="GPUs config 4 shards over (BASELINE.json: 8)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: per-kernel passes, roofline, pipeline and power figures, the "
+                         "extra legs, the sustained front end, the fast-mode leg, the CPU baseline and the parity check "
+                         "(--no-* switch parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the rows, result records and sync positions of the last timed step to DIR/*.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.config4:
+        if args.dump_outputs:
+            ap.error("--dump-outputs is not available with --config4")
         return run_config4(args)
 
     json_out = _QuietStdout()
@@ -330,7 +385,7 @@ def main():
     # ---- synthetic recording (seeded per rank), moved to HBM before any timing
     # recording 0 is the one checked against the oracle; the others differ in seed (noise, image)
     n_inputs = max(1, args.inputs, args.batch)
-    xs = [synth_apt(args.rate, args.seconds, seed=2 + rank + 1000 * j) for j in range(n_inputs)]
+    xs = synth_inputs(args.rate, args.seconds, [2 + rank + 1000 * j for j in range(n_inputs)])
     x = xs[0]
     n = x.size
     stream = torch.cuda.Stream(device=dev)
@@ -345,59 +400,64 @@ def main():
         cap = int(plan.info.max_rows)
         d_rows_all = [torch.empty(cap * 2080, dtype=torch.float32, device=dev) for _ in range(B)]
         d_rows = d_rows_all[0]
+        # the last timed step writes rows of its own: consecutive calls run on different streams, and the earlier calls
+        # still in flight would otherwise overwrite them in the shared buffers
+        d_rows_last = [torch.empty(cap * 2080, dtype=torch.float32, device=dev) for _ in range(B)]
         torch.cuda.synchronize()  # inputs are resident before anything is enqueued on the plan's streams
         # call j decodes the B recordings j, j+1, ... (mod n_inputs); recording 0 of call 0 is checked
         sigs = [[d_xs[(j + b) % n_inputs].data_ptr() for b in range(B)] for j in range(n_inputs)]
         nn, out, caps = [n] * B, [t.data_ptr() for t in d_rows_all], [cap] * B
+        out_last = [t.data_ptr() for t in d_rows_last]
         counter = [0]
 
-        def step(j=None):
+        def step(j=None, rows=None):
             if j is None:
                 j = counter[0] % n_inputs
                 counter[0] += 1
-            plan.decode_device(sigs[j], nn, out, caps)
+            plan.decode_device(sigs[j], nn, out if rows is None else rows, caps)
 
         # (amd-smi is opened here, well before the timed region: its initialisation takes a while, and a pause between
         # the warm-up steps and the timed steps would let the power manager's averages relax)
         smu = None
-        if not args.no_power:  # (every rank watches its own device: the first 8-GPU run should explain itself)
+        if args.full and not args.no_power:  # (every rank watches its own device: the first 8-GPU run should explain itself)
             from noaa_apt_amd.testing.smu import SmuSampler
             smu = SmuSampler(pci_bus_id=getattr(torch.cuda.get_device_properties(dev), "pci_bus_id", None), device_index=local_rank)
 
-        # ---- per-kernel measurement passes, BEFORE the warm-up steps (they are part of every run; placed
+        # ---- untimed pipelined steps, then (--full) the per-kernel measurement passes, BEFORE the warm-up steps (placed
         # here they also bring the GPU out of the idle clocks it fell to while the host generated inputs)
-        # (a) the dominant kernel with nothing else on the GPU — one step at a time, a host
-        # synchronisation after each, HIP events around every launch.  This per-launch duration
-        # is what `roofline` uses (a launch in the timed region below shares the GPU with the
-        # launches of the other calls in flight, so its duration there is not GPU time per launch).
         for _ in range(args.pre_steps):  # (the host spent seconds generating inputs: wake the GPU before timing anything)
             step()
-        torch.cuda.synchronize()
-        plan.enable_timing(2)
-        for _ in range(24):
-            step()
+        iso_times, single_ms, ktimes = {}, None, {}
+        if args.full:
+            # (a) the dominant kernel with nothing else on the GPU — one step at a time, a host
+            # synchronisation after each, HIP events around every launch.  This per-launch duration
+            # is what `roofline` uses (a launch in the timed region below shares the GPU with the
+            # launches of the other calls in flight, so its duration there is not GPU time per launch).
             torch.cuda.synchronize()
-        iso_times = plan.collect_timing()
-        # (b) the same kernel launched over ONE recording (the launch shape of round 1), one launch at a time
-        single_ms = None
-        if B > 1 and not args.no_sync and not args.no_single_launch:
-            plan1 = apt.Plan(settings, rate, True, max_samples=n, max_batch=1, device=local_rank, mode=mode)
-            plan1.enable_timing(2)
-            for j in range(16):
-                plan1.decode_device([d_xs[j % n_inputs].data_ptr()], [n], out[:1], caps[:1])
+            plan.enable_timing(2)
+            for _ in range(24):
+                step()
                 torch.cuda.synchronize()
-            single_ms = plan1.collect_timing().get("fused_front_end", (None, 0))[0]
-            plan1.close()
-        # (c) pipelined, with events around every kernel, for the per-kernel breakdown.  This pass is also what the
-        # power manager sees last before the warm-up steps: passes (a) and (b) leave the package 40 % idle, its power
-        # average relaxes, and a pipelined loop started then runs its first ~5 ms at up to 2.4 GHz, the next ~10 ms
-        # BELOW the settled clock (the controller overshoots) — `--settle-steps` pipelined steps (default 40: ~35 ms)
-        # put the loop into the state a long run is in before W and K are counted
-        plan.enable_timing(2)
-        for _ in range(10):
-            step()
-        ktimes = plan.collect_timing()
-        plan.enable_timing(0)
+            iso_times = plan.collect_timing()
+            # (b) the same kernel launched over ONE recording (the launch shape of round 1), one launch at a time
+            if B > 1 and not args.no_sync and not args.no_single_launch:
+                plan1 = apt.Plan(settings, rate, True, max_samples=n, max_batch=1, device=local_rank, mode=mode)
+                plan1.enable_timing(2)
+                for j in range(16):
+                    plan1.decode_device([d_xs[j % n_inputs].data_ptr()], [n], out[:1], caps[:1])
+                    torch.cuda.synchronize()
+                single_ms = plan1.collect_timing().get("fused_front_end", (None, 0))[0]
+                plan1.close()
+            # (c) pipelined, with events around every kernel, for the per-kernel breakdown.  This pass is also what the
+            # power manager sees last before the warm-up steps: passes (a) and (b) leave the package 40 % idle, its power
+            # average relaxes, and a pipelined loop started then runs its first ~5 ms at up to 2.4 GHz, the next ~10 ms
+            # BELOW the settled clock (the controller overshoots) — `--settle-steps` pipelined steps (default 40: ~35 ms)
+            # put the loop into the state a long run is in before W and K are counted
+            plan.enable_timing(2)
+            for _ in range(10):
+                step()
+            ktimes = plan.collect_timing()
+            plan.enable_timing(0)
         # what the power manager does meanwhile (every rank, its own device): the SMU's accumulators read before and after
         # a window of pipelined steps — no thread beside it — and a sampled loop of the same steps behind it.  The first
         # snapshot is taken HERE, before the settle and warm-up steps, not between the warm-up's synchronize and t0 (round
@@ -413,21 +473,31 @@ def main():
         for _ in range(args.warmup):
             step()
         torch.cuda.synchronize()
-        # timed region: HIP events bracket the dominant kernel of every 8th step (the markers
+        # timed region (--full): HIP events bracket the dominant kernel of every 8th step (the markers
         # serialise the stream for ~6 us each; sampling keeps the measurement live but cheap)
-        plan.enable_timing(0 if args.no_kernel_timing else 1)
+        if args.full:
+            plan.enable_timing(0 if args.no_kernel_timing else 1)
         job_barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
+        for i in range(args.steps):
+            step(rows=out_last if i == args.steps - 1 else None)
         t_enq = time.perf_counter()  # host finished enqueueing (informational)
         torch.cuda.synchronize()
         t_local = time.perf_counter()  # this rank's own K steps (the job's time is taken behind the barrier)
         job_barrier()
         t1 = time.perf_counter()
-        dom_times = plan.collect_timing()
-        plan.enable_timing(0)
+        dom_times = {}
+        if args.full:
+            dom_times = plan.collect_timing()
+            plan.enable_timing(0)
+        # what the last timed step handed its caller: recording b of call j is input (j + b) mod n_inputs
+        last = plan.results(B)
+        last_ids = [(counter[0] - 1 + b) % n_inputs for b in range(B)]
+        if args.dump_outputs:
+            dump_last_step(args.dump_outputs, "" if world == 1 else f"rank{rank}_", plan, last, d_rows_last, last_ids,
+                           not args.no_sync)
+        del d_rows_last
         power = None
         if smu is not None:
             power = {"source": "amd-smi gpu_metrics, per rank (this object: rank 0's device): energy and throttler-residency accumulators read before the settle + "
@@ -452,15 +522,17 @@ def main():
                     power["settled"]["ms_per_step"] = round(1e3 * (b3 - a3) / k3, 5)
             else:
                 power["error"] = smu.error
-        step(0)  # the recording that is compared with the oracle below
-        res = plan.results(1)[0]
-        ref_pos = plan.sync_positions(0) if not args.no_sync else np.zeros(0, np.uint64)
-        torch.cuda.synchronize()
-        ref_rows = d_rows[:res.n_out].clone()
+        res = last[0]
+        if args.full:
+            step(0)  # the recording that is compared with the oracle below
+            res = plan.results(1)[0]
+            ref_pos = plan.sync_positions(0) if not args.no_sync else np.zeros(0, np.uint64)
+            torch.cuda.synchronize()
+            ref_rows = d_rows[:res.n_out].clone()
 
-        # ---- extra legs (not part of `value`): the rows either side of the decode path
+        # ---- extra legs (--full; not part of `value`): the rows either side of the decode path
         extras = {}
-        if not args.no_extras and not args.no_sync and args.mode == "strict" and res.status == 0:
+        if args.full and not args.no_extras and not args.no_sync and args.mode == "strict" and res.status == 0:
             k2 = max(8, min(args.steps, 100))
 
             def timed_loop(fn):
@@ -593,17 +665,17 @@ def main():
                 "ms": round(shots[len(shots) // 2], 3), "ms_min": round(shots[0], 3), "ms_max": round(shots[-1], 3)}
             del host_recs, host_wavs
             apt.cache_clear()
-        pflags = plan.read_internal("picker_flags", np.uint32, 32)
+        pflags = plan.read_internal("picker_flags", np.uint32, 32) if args.full else None
         sustained = None
-        if not args.no_extras and not args.no_sync and world == 1:
+        if args.full and not args.no_extras and not args.no_sync and world == 1:
             torch.cuda.synchronize()
             sustained = sustained_front_end(args, B)
 
-        # ---- the same K steps in APTGPU_MODE_FAST (reported NEXT TO the strict headline, never as `value`):
+        # ---- (--full) the same K steps in APTGPU_MODE_FAST (reported NEXT TO the strict headline, never as `value`):
         # same inputs, same batch, same warm-up / timing protocol, its own isolated kernel timing, and its
         # tolerance check against the oracle further down
         fast_leg = None
-        if args.mode == "strict" and not args.no_extras and not args.no_sync and rank == 0:
+        if args.full and args.mode == "strict" and not args.no_extras and not args.no_sync and rank == 0:
             planf = apt.Plan(settings, rate, True, max_samples=n, max_batch=B, device=local_rank, mode=apt.MODE_FAST)
             if planf.info.fused in (1, 3, 4):
                 def fstep(j):
@@ -638,119 +710,35 @@ def main():
     from noaa_apt_amd import shard
     # whole-job figures: MAX elapsed over ranks, SUM of samples over ranks (no other collective)
     elapsed, total_samples_per_step = shard.reduce_job(t1 - t0, float(n) * max(1, args.batch), device=dev)
-    # what each rank saw (bookkeeping, outside the timed region): its own K steps, its device's power and clocks in the
-    # settled loop, joules per call, and where its process and device sit
-    try:
-        aff = dict(zip(("pci", "numa_node", "cpulist"), apt.host_affinity(local_rank)))
-    except Exception as e:  # noqa: BLE001
-        aff = {"error": str(e)}
-    settled = (power or {}).get("settled") or {}
-    timed = (power or {}).get("window") or {}
-    mine = {"rank": rank, "device": local_rank, "ms_per_step": round(1e3 * (t_local - t0) / args.steps, 5),
+    # what each rank saw (bookkeeping, outside the timed region): its own K steps and (--full) its device's power and
+    # clocks in the settled loop, joules per call, and where its process and device sit
+    mine = {"rank": rank, "device": local_rank, "ms_per_step": round(1e3 * (t_local - t0) / args.steps, 5)}
+    if args.full:
+        try:
+            aff = dict(zip(("pci", "numa_node", "cpulist"), apt.host_affinity(local_rank)))
+        except Exception as e:  # noqa: BLE001
+            aff = {"error": str(e)}
+        settled = (power or {}).get("settled") or {}
+        timed = (power or {}).get("window") or {}
+        mine.update({
             "socket_w": (settled.get("socket_w") or {}).get("mean"),
             "gfxclk_mhz": (settled.get("gfxclk_mhz") or {}).get("mean_over_xcds"),
             "joules_per_call": (round(timed["socket_w_mean"] * timed["window_s"] / timed["steps"], 4)
                                 if timed.get("socket_w_mean") and timed.get("window_s") and timed.get("steps") else None),
             "pci": aff.get("pci"), "numa_node": aff.get("numa_node"),
-            "cpus_allowed": len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else None}
+            "cpus_allowed": len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else None})
     per_rank = [mine]
     if dist is not None and world > 1:
         per_rank = [None] * world
         dist.all_gather_object(per_rank, mine, group=cpu_group) if cpu_group is not None else dist.all_gather_object(per_rank, mine)
 
-    if res.status != 0:
-        raise SystemExit(f"decode failed on rank {rank}: status {res.status} reason {res.reason}")
+    for r in ([res] if args.full else []) + last:
+        if r.status != 0:
+            raise SystemExit(f"decode failed on rank {rank}: status {r.status} reason {r.reason}")
 
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps
         value = total_samples_per_step * args.steps / elapsed / 1e6
-        # algorithmic bytes of one recording: every input f32 read once, every output pixel
-        # written once: 4*N_in + 4*2080*rows
-        b_alg = (4.0 * n + 4.0 * 2080.0 * res.n_rows) * max(1, args.batch)  # per call (= per front-end launch)
-        src = dom_times if dom_times else ktimes
-        dom = max(src.items(), key=lambda kv: kv[1][0]) if src else ("none", (0.0, 0))
-        dom_ms = dom[1][0]                                   # in the timed region: overlapped with other launches
-        alone_ms, alone_n = iso_times.get(dom[0], (0.0, 0))  # one launch at a time: GPU time per launch
-        achieved = b_alg / (alone_ms * 1e-3) / 1e9 if alone_ms > 0 else 0.0
-        kernel_sum_ms = sum(v[0] for v in ktimes.values())
-        pipe_achieved = b_alg / (ms_per_step * 1e-3) / 1e9
-        # HBM bytes per launch of the dominant kernel as measured with rocprofv3 PMC counters
-        # (separate FETCH_SIZE / WRITE_SIZE passes, gfx950 2x read correction applied by
-        # tools/summarize_pmc.py) for THIS workload and mode; null when no matching profile is committed
-        traffic, traffic_src, sq = None, None, None
-        if (args.rate, args.seconds, args.profile, max(1, args.batch)) == (48000, 600.0, "standard", 16) \
-                and dom[0] == "fused_front_end" and args.mode in ("strict", "fast"):
-            # committed counter summaries are only quoted when they were collected on THESE kernel sources
-            # (tools/collect_profiles.sh stamps them with tools/csrc_hash.py's hash of noaa_apt_amd/csrc)
-            sys.path.insert(0, os.path.join(ROOT, "tools"))
-            try:
-                from csrc_hash import csrc_sha16, matches as stamp_matches
-                here = csrc_sha16(ROOT)
-            except Exception:
-                here = None
-                stamp_matches = None
-            import glob
-
-            def newest_profile(stem):
-                """The latest round's profiles/rNN_<stem>.json whose stamp matches the sources here (else the latest one)."""
-                cands = sorted(glob.glob(os.path.join(ROOT, "profiles", f"r[0-9][0-9]_{stem}.json")), reverse=True)
-                first = None
-                for fpath in cands:
-                    try:
-                        d_ = json.load(open(fpath))
-                    except Exception:
-                        continue
-                    first = first or (fpath, d_)
-                    if here and stamp_matches(d_, "front_end", ROOT):
-                        return fpath, d_, True
-                return (first[0], first[1], False) if first else (None, None, False)
-
-            try:
-                f, d_t, ok_t = newest_profile(f"hbm_traffic_{args.mode}")
-                rel = os.path.relpath(f, ROOT) if f else None
-                if ok_t:
-                    traffic = d_t["per_launch"]["k_fused"]["hbm_total_MB"] * 1e6
-                    traffic_src = (f"{rel} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, "
-                                   f"collected on these kernel sources: csrc {d_t.get('csrc_sha16')})")
-                elif f:
-                    traffic_src = (f"{rel} is stamped {d_t.get('csrc_sha16')}, the kernel "
-                                   f"sources here hash to {here}: not quoted")
-            except Exception:
-                traffic = None
-            try:
-                _, d_s, ok_s = newest_profile(f"sq_counters_{args.mode}")
-                sq = d_s if ok_s else None
-            except Exception:
-                sq = None
-        # arithmetic the front end EXECUTES per work-rate sample: two flops per FIR tap, ~8 for the envelope,
-        # 22 for the sync correlation from pulse sums (every mode: the strict front end only bounds the
-        # reference's 114-term chain, which the picker then evaluates for ~3 % of the positions), +3 for the
-        # strict mode's sum of |F| behind those bounds
-        w_len = float(res.work_len)
-        taps1 = plan.info.n_resample_taps / plan.info.l
-        corr_ops = 22.0 if args.mode == "fast" else 25.0
-        flops = w_len * (2.0 * taps1 + 8.0 + 2.0 * plan.info.n_lowpass_taps + corr_ops) * max(1, args.batch)
-        valu = {
-            "note": "the kernel is bound by VALU issue, not HBM (DESIGN.md §5.1): arithmetic the front end executes "
-                    "per launch over the isolated kernel time, against the 157.3 TFLOP/s fp32 vector peak",
-            "algorithmic_flops_per_launch": flops,
-            "achieved_tflops": round(flops / (alone_ms * 1e-3) / 1e12, 3) if alone_ms > 0 else None,
-            "pct_of_fp32_vector_peak": round(100.0 * flops / (alone_ms * 1e-3) / 157.3e12, 2) if alone_ms > 0 else None,
-        }
-        if sq:
-            valu.update({k: sq[k] for k in ("valu_instructions_per_wave", "waves_per_launch", "issue_floor_us",
-                                            "source") if k in sq})
-            if alone_ms > 0 and "issue_floor_us" in sq:
-                # (the counters were collected on single-recording launches: the floor of a launch over
-                # `batch` recordings is that many times as long)
-                valu["issue_floor_us_per_launch"] = round(sq["issue_floor_us"] * max(1, args.batch), 2)
-                valu["achieved_frac_of_issue_floor"] = round(sq["issue_floor_us"] * max(1, args.batch) / (alone_ms * 1e3), 4)
-                # the floor above is priced at 2.4 GHz; in the pipelined loop the package is at its power limit and the
-                # SMU runs the XCDs slower (`power.settled`): the same floor at the clock the pipeline actually gets
-                clk = ((power or {}).get("settled") or {}).get("gfxclk_mhz", {}).get("mean_over_xcds")
-                if clk:
-                    valu["issue_floor_us_per_launch_at_settled_clock"] = round(valu["issue_floor_us_per_launch"] * 2400.0 / clk, 2)
-                    valu["settled_gfxclk_mhz"] = clk
         line = {
             "metric": "Msamples/sec WAV->APT-line decode",
             "value": round(value, 3),
@@ -759,7 +747,10 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 5),
-            "joules_per_call": mine["joules_per_call"],  # socket energy accumulator over `power.window` (settle + W + K pipelined steps) / that many calls: rank 0's device (every rank's: per_rank)
+        }
+        if args.full:
+            line["joules_per_call"] = mine["joules_per_call"]  # socket energy accumulator over `power.window` (settle + W + K pipelined steps) / that many calls: rank 0's device (every rank's: per_rank)
+        line.update({
             "per_rank": per_rank,
             "higher_is_better": True,
             "scaling": "weak",
@@ -779,11 +770,101 @@ def main():
                 "n_sync": int(res.n_sync),
                 "input_resident_in_hbm": True,
                 "distinct_inputs_round_robin": n_inputs,
-                "picker": {"path": {0: "lds", 1: "sequential-walk", 2: "global"}.get(int(pflags[1]), "?"),
-                           "node_capacity": int(pflags[3]), "visited_nodes": int(pflags[4]), "orbit": {1: "direct", 2: "doubling (LDS)", 3: "doubling over all nodes (LDS, no closure)"}.get(int(pflags[6]), "doubling (L2)"),
-                           "cycle_stamps": [int(v) for v in pflags[8:11]]},
             },
-            "roofline": {
+        })
+        if args.full:
+            # algorithmic bytes of one recording: every input f32 read once, every output pixel
+            # written once: 4*N_in + 4*2080*rows
+            b_alg = (4.0 * n + 4.0 * 2080.0 * res.n_rows) * max(1, args.batch)  # per call (= per front-end launch)
+            src = dom_times if dom_times else ktimes
+            dom = max(src.items(), key=lambda kv: kv[1][0]) if src else ("none", (0.0, 0))
+            dom_ms = dom[1][0]                                   # in the timed region: overlapped with other launches
+            alone_ms, alone_n = iso_times.get(dom[0], (0.0, 0))  # one launch at a time: GPU time per launch
+            achieved = b_alg / (alone_ms * 1e-3) / 1e9 if alone_ms > 0 else 0.0
+            kernel_sum_ms = sum(v[0] for v in ktimes.values())
+            pipe_achieved = b_alg / (ms_per_step * 1e-3) / 1e9
+            # HBM bytes per launch of the dominant kernel as measured with rocprofv3 PMC counters
+            # (separate FETCH_SIZE / WRITE_SIZE passes, gfx950 2x read correction applied by
+            # tools/summarize_pmc.py) for THIS workload and mode; null when no matching profile is committed
+            traffic, traffic_src, sq = None, None, None
+            if (args.rate, args.seconds, args.profile, max(1, args.batch)) == (48000, 600.0, "standard", 16) \
+                    and dom[0] == "fused_front_end" and args.mode in ("strict", "fast"):
+                # committed counter summaries are only quoted when they were collected on THESE kernel sources
+                # (tools/collect_profiles.sh stamps them with tools/csrc_hash.py's hash of noaa_apt_amd/csrc)
+                sys.path.insert(0, os.path.join(ROOT, "tools"))
+                try:
+                    from csrc_hash import csrc_sha16, matches as stamp_matches
+                    here = csrc_sha16(ROOT)
+                except Exception:
+                    here = None
+                    stamp_matches = None
+                import glob
+
+                def newest_profile(stem):
+                    """The latest round's profiles/rNN_<stem>.json whose stamp matches the sources here (else the latest one)."""
+                    cands = sorted(glob.glob(os.path.join(ROOT, "profiles", f"r[0-9][0-9]_{stem}.json")), reverse=True)
+                    first = None
+                    for fpath in cands:
+                        try:
+                            d_ = json.load(open(fpath))
+                        except Exception:
+                            continue
+                        first = first or (fpath, d_)
+                        if here and stamp_matches(d_, "front_end", ROOT):
+                            return fpath, d_, True
+                    return (first[0], first[1], False) if first else (None, None, False)
+
+                try:
+                    f, d_t, ok_t = newest_profile(f"hbm_traffic_{args.mode}")
+                    rel = os.path.relpath(f, ROOT) if f else None
+                    if ok_t:
+                        traffic = d_t["per_launch"]["k_fused"]["hbm_total_MB"] * 1e6
+                        traffic_src = (f"{rel} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, "
+                                       f"collected on these kernel sources: csrc {d_t.get('csrc_sha16')})")
+                    elif f:
+                        traffic_src = (f"{rel} is stamped {d_t.get('csrc_sha16')}, the kernel "
+                                       f"sources here hash to {here}: not quoted")
+                except Exception:
+                    traffic = None
+                try:
+                    _, d_s, ok_s = newest_profile(f"sq_counters_{args.mode}")
+                    sq = d_s if ok_s else None
+                except Exception:
+                    sq = None
+            # arithmetic the front end EXECUTES per work-rate sample: two flops per FIR tap, ~8 for the envelope,
+            # 22 for the sync correlation from pulse sums (every mode: the strict front end only bounds the
+            # reference's 114-term chain, which the picker then evaluates for ~3 % of the positions), +3 for the
+            # strict mode's sum of |F| behind those bounds
+            w_len = float(res.work_len)
+            taps1 = plan.info.n_resample_taps / plan.info.l
+            corr_ops = 22.0 if args.mode == "fast" else 25.0
+            flops = w_len * (2.0 * taps1 + 8.0 + 2.0 * plan.info.n_lowpass_taps + corr_ops) * max(1, args.batch)
+            valu = {
+                "note": "the kernel is bound by VALU issue, not HBM (DESIGN.md §5.1): arithmetic the front end executes "
+                        "per launch over the isolated kernel time, against the 157.3 TFLOP/s fp32 vector peak",
+                "algorithmic_flops_per_launch": flops,
+                "achieved_tflops": round(flops / (alone_ms * 1e-3) / 1e12, 3) if alone_ms > 0 else None,
+                "pct_of_fp32_vector_peak": round(100.0 * flops / (alone_ms * 1e-3) / 157.3e12, 2) if alone_ms > 0 else None,
+            }
+            if sq:
+                valu.update({k: sq[k] for k in ("valu_instructions_per_wave", "waves_per_launch", "issue_floor_us",
+                                                "source") if k in sq})
+                if alone_ms > 0 and "issue_floor_us" in sq:
+                    # (the counters were collected on single-recording launches: the floor of a launch over
+                    # `batch` recordings is that many times as long)
+                    valu["issue_floor_us_per_launch"] = round(sq["issue_floor_us"] * max(1, args.batch), 2)
+                    valu["achieved_frac_of_issue_floor"] = round(sq["issue_floor_us"] * max(1, args.batch) / (alone_ms * 1e3), 4)
+                    # the floor above is priced at 2.4 GHz; in the pipelined loop the package is at its power limit and the
+                    # SMU runs the XCDs slower (`power.settled`): the same floor at the clock the pipeline actually gets
+                    clk = ((power or {}).get("settled") or {}).get("gfxclk_mhz", {}).get("mean_over_xcds")
+                    if clk:
+                        valu["issue_floor_us_per_launch_at_settled_clock"] = round(valu["issue_floor_us_per_launch"] * 2400.0 / clk, 2)
+                        valu["settled_gfxclk_mhz"] = clk
+            line["config"]["picker"] = {
+                "path": {0: "lds", 1: "sequential-walk", 2: "global"}.get(int(pflags[1]), "?"),
+                "node_capacity": int(pflags[3]), "visited_nodes": int(pflags[4]), "orbit": {1: "direct", 2: "doubling (LDS)", 3: "doubling over all nodes (LDS, no closure)"}.get(int(pflags[6]), "doubling (L2)"),
+                "cycle_stamps": [int(v) for v in pflags[8:11]]}
+            line["roofline"] = {
                 "bound": "hbm",
                 "kernel": dom[0],
                 # ONE launch at a time (host synchronisation between steps), HIP events on the launch's stream
@@ -821,11 +902,11 @@ def main():
                     "kernel_avg_ms": round(single_ms, 5),
                     "algorithmic_bytes_per_launch": b_alg / max(1, args.batch),
                     "frac": round(b_alg / max(1, args.batch) / (single_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5)},
-            },
+            }
             # the pipelined loop runs at the package power limit: socket power, the gfx clocks the SMU grants, the share
             # of time the power throttler was active (None when amd-smi cannot be read)
-            "power": power,
-            "pipeline": {
+            line["power"] = power
+            line["pipeline"] = {
                 "achieved": round(pipe_achieved, 2),
                 "unit": "GB/s",
                 "frac": round(pipe_achieved / HBM_PEAK_GBS, 5),
@@ -836,8 +917,7 @@ def main():
                 # of the overlap, not GPU time.  The GPU time of a kernel is kernels_alone_ms (one call in flight at a time).
                 "kernels_span_in_pipeline_ms": {k: round(v[0], 5) for k, v in sorted(ktimes.items())},
                 "kernels_alone_ms": {k: round(v[0], 5) for k, v in sorted(iso_times.items())},
-            },
-        }
+            }
         if extras:
             line["extras"] = extras
         if fast_leg:
@@ -853,7 +933,7 @@ def main():
                              "achieved": round(f_frac * HBM_PEAK_GBS, 2) if f_frac else None, "peak": HBM_PEAK_GBS,
                              "unit": "GB/s", "frac": round(f_frac, 5) if f_frac else None},
             }
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             from oracle import binding as oracle
             os_ = {k: getattr(settings, k) for k in ("work_rate", "resample_atten",
                                                       "resample_delta_freq", "resample_cutout",

@@ -38,7 +38,7 @@ def test_config4_under_torchrun_on_every_visible_gpu():
 
 
 def test_default_bench_line_under_torchrun():
-    n, line = _torchrun(["--steps", "6", "--warmup", "2", "--seconds", "60", "--batch", "4", "--no-extras",
+    n, line = _torchrun(["--steps", "6", "--warmup", "2", "--seconds", "60", "--batch", "4", "--full", "--no-extras",
                          "--no-cpu-baseline"], 29543)
     assert line["n_gpus"] == n and line["steps"] == 6 and line["scaling"] == "weak"
     assert line["value"] > 0 and line["roofline"]["frac"] > 0

@@ -15,7 +15,8 @@ from oracle import wav_binding as ow
 from oracle.binding import OracleError
 
 f32 = np.float32
-REF_FIXTURE = "/root/reference/test/noise_48000hz.wav"
+# the reference's test/noise_48000hz.wav (a byte-identical copy: tests/test_reference_fixture.py pins its hash)
+REF_FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_fixture", "noise_48000hz.wav")
 
 
 def _values(bits, n, rng):
@@ -121,7 +122,6 @@ def test_oracle_vs_scipy_float_and_int():
         assert spec.sample_rate == 22050 and spec.channels == channels
 
 
-@pytest.mark.skipif(not os.path.exists(REF_FIXTURE), reason="reference tree not present")
 def test_reference_fixture():
     """test/noise_48000hz.wav of the reference (despite its name: 11025 Hz, mono, 16 bit)."""
     data = open(REF_FIXTURE, "rb").read()

@@ -11,7 +11,7 @@ run() {  # name, env..., -- bench args
   local envs=()
   while [ "$1" != "--" ]; do envs+=("$1"); shift; done
   shift
-  env "${envs[@]}" timeout 300 python bench.py --steps 60 --warmup 10 --no-extras --no-cpu-baseline "$@" > $O/${TAG}_bench_tuned_$name.json 2> $O/${TAG}_bench_tuned_$name.err
+  env "${envs[@]}" timeout 300 python bench.py --full --steps 60 --warmup 10 --no-extras --no-cpu-baseline "$@" > $O/${TAG}_bench_tuned_$name.json 2> $O/${TAG}_bench_tuned_$name.err
   python - $O/${TAG}_bench_tuned_$name.json $name <<'PY'
 import json, sys
 try:

@@ -9,5 +9,5 @@ for l in open("gpurun_out/orbit/sweep.txt"):
     if l.startswith("{") and "config" in l:
         d=json.loads(l); print(d["config"], d["ms_per_recording"], d["rows_checksum"], d["alone_ms_per_call"])
 PY
-for e in 0 1; do APTGPU_ORBIT_ALG=$e python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $O/bench20_$e.json 2>/dev/null; python3 -c "
+for e in 0 1; do APTGPU_ORBIT_ALG=$e python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $O/bench20_$e.json 2>/dev/null; python3 -c "
 import json;d=json.loads(open('$O/bench20_$e.json').read().strip().splitlines()[-1]);print('alg',$e,d['ms_per_step'],d['config']['picker'])"; done
