@@ -2,10 +2,14 @@
  * aptgpu_decode.c — minimal C caller of the drop-in boundary (include/aptgpu.h):
  *
  *     aptgpu_decode in.wav out.pgm [contrast: telemetry|percent|minmax] [--no-sync]
+ *                   [--histogram] [--palette FILE]
  *
- * What `noaa-apt in.wav -o out.png` does up to the grayscale image (main.rs:91-110,
- * noaa_apt.rs:114-192), minus PNG encoding: load -> decode -> contrast limits -> 8-bit image,
- * written as a binary PGM.  Plain C99, links only libaptgpu.so.
+ * What `noaa-apt in.wav -o out.png` does (main.rs:91-110, noaa_apt.rs:114-235) minus PNG
+ * encoding and the map overlay: load -> decode -> contrast limits -> 8-bit image, written as a
+ * binary PGM.  --histogram: Contrast::Histogram (MinMax limits, then each channel's histogram
+ * equalised).  --palette FILE: false colour (`-F`, tune values 0) from a raw 256 x 256 RGB palette
+ * (196 608 bytes, pixel (a, b) at (b*256 + a)*3), written as a binary PPM (the RGBA image without
+ * its alpha).  Plain C99, links only libaptgpu.so.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -22,15 +26,35 @@ static void on_status(float progress, const char *text, void *user)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s in.wav out.pgm [telemetry|percent|minmax] [--no-sync]\n", argv[0]);
+        fprintf(stderr, "usage: %s in.wav out.pgm [telemetry|percent|minmax] [--no-sync] [--histogram] "
+                "[--palette FILE]\n", argv[0]);
         return 2;
     }
     int contrast = APTGPU_CONTRAST_PERCENT, sync = 1;
+    const char *palette_path = NULL;
     for (int i = 3; i < argc; ++i) {
         if (!strcmp(argv[i], "telemetry")) contrast = APTGPU_CONTRAST_TELEMETRY;
         else if (!strcmp(argv[i], "percent")) contrast = APTGPU_CONTRAST_PERCENT;
         else if (!strcmp(argv[i], "minmax")) contrast = APTGPU_CONTRAST_MINMAX;
+        else if (!strcmp(argv[i], "--histogram")) contrast = APTGPU_CONTRAST_HISTOGRAM;
         else if (!strcmp(argv[i], "--no-sync")) sync = 0;
+        else if (!strcmp(argv[i], "--palette") && i + 1 < argc) palette_path = argv[++i];
+    }
+
+    /* the palette, decoded by the caller (the reference: image::open(..).into_rgb8(), processing.rs:115) */
+    static uint8_t palette[256 * 256 * 3];
+    aptgpu_color_settings color;
+    memset(&color, 0, sizeof color);
+    color.struct_size = sizeof color;
+    color.palette_rgb = palette;
+    if (palette_path) {
+        FILE *p = fopen(palette_path, "rb");
+        if (!p || fread(palette, 1, sizeof palette, p) != sizeof palette || fgetc(p) != EOF) {
+            fprintf(stderr, "Invalid palette image dimensions (want %u raw RGB bytes): %s\n", (unsigned)sizeof palette,
+                    palette_path);
+            return 1;
+        }
+        fclose(p);
     }
 
     /* the file image */
@@ -72,15 +96,25 @@ int main(int argc, char **argv)
     uint8_t *image = NULL;
     size_t n_px = 0;
     aptgpu_image_result info;
-    rc = aptgpu_process_gray(&ctx, rows, n_rows_px, contrast, 0.98f, APTGPU_ROTATE_NO, &image, &n_px, &info, err,
-                             sizeof err);
+    if (palette_path || contrast == APTGPU_CONTRAST_HISTOGRAM)
+        rc = aptgpu_process_image(&ctx, rows, n_rows_px, contrast, 0.98f, APTGPU_ROTATE_NO,
+                                  palette_path ? &color : NULL, palette_path ? 4 : 1, &image, &n_px, &info, err,
+                                  sizeof err);
+    else
+        rc = aptgpu_process_gray(&ctx, rows, n_rows_px, contrast, 0.98f, APTGPU_ROTATE_NO, &image, &n_px, &info,
+                                 err, sizeof err);
     aptgpu_free(rows);
     if (rc != APTGPU_OK) { fprintf(stderr, "image stage failed (%d): %s\n", rc, err); return 1; }
 
     FILE *o = fopen(argv[2], "wb");
     if (!o) { perror(argv[2]); return 1; }
-    fprintf(o, "P5\n2080 %u\n255\n", info.height);
-    fwrite(image, 1, (size_t)info.height * 2080u, o);
+    if (palette_path) {
+        fprintf(o, "P6\n2080 %u\n255\n", info.height);
+        for (size_t i = 0; i < (size_t)info.height * 2080u; ++i) fwrite(image + 4 * i, 1, 3, o);  /* drop alpha */
+    } else {
+        fprintf(o, "P5\n2080 %u\n255\n", info.height);
+        fwrite(image, 1, (size_t)info.height * 2080u, o);
+    }
     fclose(o);
     aptgpu_free(image);
     fprintf(stderr, "wrote %s: 2080 x %u, contrast limits %g .. %g\n", argv[2], info.height, info.low, info.high);

@@ -369,14 +369,20 @@ int aptgpu_find_sync(const aptgpu_context *ctx, const float *signal, size_t n,
 /* ====================================================================== */
 /* 4. consumers of the pixel rows                 */
 /* ====================================================================== */
-/* The grayscale part of noaa_apt::process() (src/noaa_apt.rs:132-192): contrast limits   */
-/* -> map_signal_u8, plus telemetry.rs and the 180-degree channel rotation.  False colour, */
-/* histogram equalisation and the map overlay stay on the host (out of scope).            */
+/* noaa_apt::process() (src/noaa_apt.rs:132-235) without the map overlay: contrast limits  */
+/* -> map_signal_u8, plus telemetry.rs, histogram equalisation (imageext.rs:21-45), palette */
+/* false colour (processing.rs:113-165) and the 180-degree channel rotation.  The map      */
+/* overlay, Rotate::Orbit and equalisation of a false-colour image (CIE Lab, imageext.rs:51-64) */
+/* stay out of scope.  aptgpu_process_gray / aptgpu_plan_process_device: the grayscale   */
+/* image of the first three contrasts; aptgpu_process_image / aptgpu_plan_process_device_image: */
+/* every contrast, optional false colour, gray or RGBA output.                             */
 
 #define APTGPU_CONTRAST_TELEMETRY 0 /* Contrast::Telemetry   src/noaa_apt.rs:141-150 */
 #define APTGPU_CONTRAST_PERCENT 1   /* Contrast::Percent(p)  src/noaa_apt.rs:151-157 */
 #define APTGPU_CONTRAST_MINMAX 2    /* Contrast::MinMax      src/noaa_apt.rs:158-164 (Histogram
                                        takes the same limits before its equalisation) */
+#define APTGPU_CONTRAST_HISTOGRAM 3 /* Contrast::Histogram: MinMax limits, then per-channel equalisation
+                                       (aptgpu_process_image / aptgpu_plan_process_device_image only) */
 #define APTGPU_ROTATE_NO 0          /* Rotate::No  */
 #define APTGPU_ROTATE_YES 1         /* Rotate::Yes  src/noaa_apt.rs:228-231, processing.rs:21-37 */
 
@@ -427,6 +433,33 @@ int aptgpu_process_gray(const aptgpu_context *ctx, const float *signal, size_t n
 int aptgpu_plan_process_device(aptgpu_plan *plan, int count, const float *const *d_rows,
                                const size_t *rows_cap, int contrast, float percent, int rotate,
                                uint8_t *const *d_images, char *err, size_t err_cap);
+
+/* noaa_apt::ColorSettings (src/noaa_apt.rs:63-71) with the palette already decoded by the caller
+ * (`image::open(..).into_rgb8()`, 256 x 256, alpha dropped). */
+typedef struct aptgpu_color_settings {
+    uint32_t struct_size;        /* sizeof(aptgpu_color_settings) */
+    uint32_t reserved;
+    const uint8_t *palette_rgb;  /* host, 256*256*3: pixel (a, b) at (b*256 + a)*3 */
+    float ch_a_tune_start, ch_a_tune_end, ch_b_tune_start, ch_b_tune_end;
+} aptgpu_color_settings;
+/* process() for every contrast incl. APTGPU_CONTRAST_HISTOGRAM, with optional false colour (color
+ * nullable).  channels 1 = the gray image (no colour allowed), 4 = the reference's RgbaImage (A = 255).
+ * The image has height = n / 2080 whole rows; *image_out malloc'd, *n_out = height*2080*channels
+ * bytes, info->n_px = height*2080.  Status callbacks as aptgpu_process_gray (Histogram: "Mapping
+ * values").  Refused with APTGPU_ERR_UNSUPPORTED before any callback: Rotate::Orbit, and false
+ * colour together with Histogram (the reference equalises channel A in CIE Lab then). */
+int aptgpu_process_image(const aptgpu_context *ctx, const float *signal, size_t n, int contrast,
+                         float percent, int rotate, const aptgpu_color_settings *color, int channels,
+                         uint8_t **image_out, size_t *n_out, aptgpu_image_result *info, char *err,
+                         size_t err_cap);
+/* Device-resident, chained behind the last aptgpu_plan_decode_device call like
+ * aptgpu_plan_process_device; d_images[i] holds rows_cap[i]*2080*channels bytes (16-byte aligned
+ * for channels 4, 4-byte for channels 1).  The palette is uploaded once per workspace slot and
+ * again only when its bytes change.  Results through aptgpu_plan_image_results. */
+int aptgpu_plan_process_device_image(aptgpu_plan *plan, int count, const float *const *d_rows,
+                                     const size_t *rows_cap, int contrast, float percent, int rotate,
+                                     const aptgpu_color_settings *color, int channels,
+                                     uint8_t *const *d_images, char *err, size_t err_cap);
 /* Waits for the image stage of the last call and copies the records. */
 int aptgpu_plan_image_results(aptgpu_plan *plan, int count, aptgpu_image_result *results);
 

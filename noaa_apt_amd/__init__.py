@@ -15,6 +15,8 @@ Names, argument meaning and error behaviour follow the reference:
     load (WAV ingest), decode_wav                          /root/reference/src/noaa_apt.rs:114-130, wav.rs:11-57
     resample_wav (WAV->WAV tool), write_wav                /root/reference/src/resample.rs:17-71, wav.rs:59-98
     process (grayscale part), Contrast, Rotate             /root/reference/src/noaa_apt.rs:25-60,132-235
+    process: Contrast.HISTOGRAM, ColorSettings (false      the reference's processing.rs:83-165, imageext.rs:21-45,
+    colour); no map overlay                                noaa_apt.rs:63-71
     percent, get_min, get_max, map_signal_u8               /root/reference/src/misc.rs:119, dsp.rs:20-54
     read_telemetry, Telemetry                              /root/reference/src/telemetry.rs:19-243
 
@@ -24,11 +26,11 @@ raise.  (The CPU oracle lives in oracle/ and is test infrastructure only.)
 from .api import (  # noqa: F401
     FINAL_RATE, PX_PER_ROW, CARRIER_FREQ,
     AptError, InternalError, RateOverflowError, HipError, InvalidError, UnsupportedError,
-    WavOpenError, IoError, WavSpec, wav_parse, load, decode_wav, write_wav, resample_wav,
+    InvalidInputError, WavOpenError, IoError, WavSpec, wav_parse, load, decode_wav, write_wav, resample_wav,
     Rate, Freq, Settings, Context, Stats,
     NoFilter, Lowpass, LowpassDcRemoval,
     decode, resample_with_filter, resample, demodulate, filter, find_sync, generate_sync_frame,
-    Contrast, Rotate, Telemetry, ImageResult,
+    Contrast, Rotate, ColorSettings, Telemetry, ImageResult,
     get_min, get_max, percent, map_signal_u8, read_telemetry, process,
     Plan, PlanInfo, Result, KernelTime, decode_batch, BatchStats, host_alloc_f32, host_free,
     lib, lib_path, use_library, build, device_count, version, abi_version, cache_clear, cache_info, host_affinity, host_affinity_from_sysfs,

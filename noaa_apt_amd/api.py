@@ -61,8 +61,12 @@ class UnsupportedError(AptError):
     code = 5
 
 
+class InvalidInputError(AptError):   # err::Error::InvalidInput (a palette that cannot be used)
+    code = 8
+
+
 _ERRORS = {c.code: c for c in (InternalError, RateOverflowError, HipError, InvalidError,
-                               UnsupportedError, WavOpenError, IoError)}
+                               UnsupportedError, WavOpenError, IoError, InvalidInputError)}
 
 
 def _check(rc, err=None):
@@ -119,6 +123,12 @@ class ImageResult(C.Structure):
                 ("telemetry_quality", C.c_float), ("channel_a", C.c_int32), ("channel_b", C.c_int32),
                 ("reserved", C.c_uint32), ("n_px", C.c_uint64), ("values_a", C.c_float * 16),
                 ("values_b", C.c_float * 16)]
+
+
+class _CColorSettings(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("palette_rgb", _u8p),
+                ("ch_a_tune_start", C.c_float), ("ch_a_tune_end", C.c_float),
+                ("ch_b_tune_start", C.c_float), ("ch_b_tune_end", C.c_float)]
 
 
 class WavSpec(C.Structure):
@@ -274,6 +284,11 @@ def lib():
     L.aptgpu_plan_process_device.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz), i32, f, i32,
                                              C.POINTER(vp), C.c_char_p, sz]
     L.aptgpu_plan_image_results.argtypes = [vp, i32, C.POINTER(ImageResult)]
+    ccs = C.POINTER(_CColorSettings)
+    L.aptgpu_process_image.argtypes = [cp, _f32p, sz, i32, f, i32, ccs, i32, C.POINTER(_u8p), C.POINTER(sz),
+                                       C.POINTER(ImageResult), C.c_char_p, sz]
+    L.aptgpu_plan_process_device_image.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz), i32, f, i32, ccs, i32,
+                                                   C.POINTER(vp), C.c_char_p, sz]
     _lib = L
     return L
 
@@ -652,9 +667,9 @@ def resample_wav(context, settings, input_wav, output_filename, output_rate: int
 
 # ------------------------------------------------------------------ consumers of the rows
 class Contrast:
-    """noaa_apt::Contrast (noaa_apt.rs:25-37).  Histogram's equalisation is host-side and out
-    of scope; it takes MinMax limits first (noaa_apt.rs:158)."""
-    TELEMETRY, MINMAX = ("telemetry",), ("minmax",)
+    """noaa_apt::Contrast (noaa_apt.rs:25-37).  HISTOGRAM takes MinMax limits (noaa_apt.rs:158), then
+    equalises the histogram of each channel half (processing.rs:83-101)."""
+    TELEMETRY, MINMAX, HISTOGRAM = ("telemetry",), ("minmax",), ("histogram",)
 
     @staticmethod
     def Percent(p):  # noqa: N802 - the reference's variant name
@@ -663,13 +678,62 @@ class Contrast:
     @staticmethod
     def _c(contrast):
         kind = contrast[0]
-        return ({"telemetry": 0, "percent": 1, "minmax": 2}[kind],
+        return ({"telemetry": 0, "percent": 1, "minmax": 2, "histogram": 3}[kind],
                 contrast[1] if kind == "percent" else 0.0)
 
 
 class Rotate:
     """noaa_apt::Rotate (noaa_apt.rs:52-60); Orbit needs orbit propagation (out of scope)."""
     NO, YES, ORBIT = 0, 1, 2
+
+
+def _rust_debug_str(text):
+    """`{:?}` of a path (Rust's Debug for str): quoted, with backslashes and quotes escaped."""
+    out = []
+    for ch in str(text):
+        if ch in '"\\':
+            out.append("\\" + ch)
+        elif ch == "\n":
+            out.append("\\n")
+        elif ch == "\r":
+            out.append("\\r")
+        elif ch == "\t":
+            out.append("\\t")
+        else:
+            out.append(ch)
+    return '"' + "".join(out) + '"'
+
+
+class ColorSettings:
+    """noaa_apt::ColorSettings (noaa_apt.rs:63-71): the false-colour palette and the tune values of both channels.
+
+    `palette` is a path, decoded here with PIL's convert("RGB") as processing::false_color decodes it with
+    `image::open(..).into_rgb8()` (processing.rs:113-121: alpha dropped), or a (256, 256, 3) or (256, 256, 4) uint8
+    array, indexed [b, a] (alpha dropped).  Errors are the reference's InvalidInput texts."""
+
+    def __init__(self, palette, ch_a_tune_start=0.0, ch_a_tune_end=0.0, ch_b_tune_start=0.0, ch_b_tune_end=0.0):
+        if isinstance(palette, (str, bytes, os.PathLike)):
+            path = os.fsdecode(palette)
+            try:
+                from PIL import Image
+                with Image.open(path) as im:
+                    arr = np.asarray(im.convert("RGB"), dtype=np.uint8)
+            except Exception:
+                raise InvalidInputError(f"Could not load {_rust_debug_str(path)}") from None
+        else:
+            arr = np.asarray(palette)
+            if arr.dtype != np.uint8 or arr.ndim != 3 or arr.shape[2] not in (3, 4):
+                raise InvalidInputError("Invalid palette image dimensions")
+            arr = arr[:, :, :3]
+        if arr.shape[:2] != (256, 256):
+            raise InvalidInputError("Invalid palette image dimensions")
+        self.palette = np.ascontiguousarray(arr)
+        self.ch_a_tune_start, self.ch_a_tune_end = float(ch_a_tune_start), float(ch_a_tune_end)
+        self.ch_b_tune_start, self.ch_b_tune_end = float(ch_b_tune_start), float(ch_b_tune_end)
+
+    def _c(self):
+        return _CColorSettings(C.sizeof(_CColorSettings), 0, self.palette.ctypes.data_as(_u8p),
+                               self.ch_a_tune_start, self.ch_a_tune_end, self.ch_b_tune_start, self.ch_b_tune_end)
 
 
 class Telemetry:
@@ -747,11 +811,17 @@ def read_telemetry(context, signal):  # telemetry.rs:125
 
 def process(context, signal, contrast_adjustment, rotate=Rotate.NO, color=None, orbit=None,
             return_info=False):
-    """noaa_apt::process (noaa_apt.rs:132-235) up to the grayscale image: returns the
-    height x 2080 u8 array.  False colour, histogram equalisation and the map overlay are
-    host-side features of the reference that this path does not offer."""
-    if color is not None or orbit is not None:
-        raise UnsupportedError("false colour / map overlay are not part of the GPU path")
+    """noaa_apt::process (noaa_apt.rs:132-235) without the map overlay.  Returns the height x 2080 u8
+    gray image, or with `color` (a ColorSettings) the height x 2080 x 4 RGBA image of the reference's
+    false colour (A = 255).  Contrast.HISTOGRAM equalises each channel half of the gray image.
+    Unsupported: the map overlay (`orbit`), Rotate.ORBIT, and HISTOGRAM together with false colour
+    (the reference equalises channel A in CIE Lab then)."""
+    if orbit is not None:
+        raise UnsupportedError("the map overlay is not part of the GPU path")
+    if color is not None and not isinstance(color, ColorSettings):
+        raise UnsupportedError("color must be a ColorSettings")
+    if color is not None or contrast_adjustment == Contrast.HISTOGRAM:
+        return _process_image(context, signal, contrast_adjustment, rotate, color, return_info)
     cctx = (context or Context())._c()
     x, xp = _as_f32(signal)
     kind, p = Contrast._c(contrast_adjustment)
@@ -760,6 +830,22 @@ def process(context, signal, contrast_adjustment, rotate=Rotate.NO, color=None, 
     _check(lib().aptgpu_process_gray(C.byref(cctx), xp, x.size, kind, p, int(rotate), C.byref(img),
                                      C.byref(n), C.byref(info), err, _ERRCAP), err)
     out = _take(img, n.value, np.uint8).reshape(-1, PX_PER_ROW)
+    return (out, info) if return_info else out
+
+
+def _process_image(context, signal, contrast_adjustment, rotate, color, return_info):
+    cctx = (context or Context())._c()
+    x, xp = _as_f32(signal)
+    kind, p = Contrast._c(contrast_adjustment)
+    channels = 4 if color is not None else 1
+    ccol = color._c() if color is not None else None
+    img, n, info = _u8p(), C.c_size_t(), ImageResult()
+    err = C.create_string_buffer(_ERRCAP)
+    _check(lib().aptgpu_process_image(C.byref(cctx), xp, x.size, kind, p, int(rotate),
+                                      C.byref(ccol) if ccol is not None else None, channels, C.byref(img),
+                                      C.byref(n), C.byref(info), err, _ERRCAP), err)
+    out = _take(img, n.value, np.uint8)
+    out = out.reshape(-1, PX_PER_ROW, 4) if channels == 4 else out.reshape(-1, PX_PER_ROW)
     return (out, info) if return_info else out
 
 
@@ -903,6 +989,24 @@ class Plan:
         _check(lib().aptgpu_plan_process_device(self._p, k, (C.c_void_p * k)(*d_rows),
                                                 (C.c_size_t * k)(*rows_cap), kind, p, int(rotate),
                                                 (C.c_void_p * k)(*d_images), err, _ERRCAP), err)
+
+    def process_device_image(self, d_rows: Sequence[int], rows_cap: Sequence[int], contrast_adjustment,
+                             d_images: Sequence[int], rotate=Rotate.NO, color=None, channels=None):
+        """process() with every contrast (HISTOGRAM too) and optional false colour (a ColorSettings) for the
+        recordings of the last decode_device call, chained on the device behind their decode.  d_images[i]
+        holds rows_cap[i] * 2080 * channels bytes; channels defaults to 4 (RGBA) with colour, 1 (gray) without."""
+        if color is not None and not isinstance(color, ColorSettings):
+            raise UnsupportedError("color must be a ColorSettings")
+        if channels is None:
+            channels = 4 if color is not None else 1
+        k = len(d_rows)
+        kind, p = Contrast._c(contrast_adjustment)
+        ccol = color._c() if color is not None else None
+        err = C.create_string_buffer(_ERRCAP)
+        _check(lib().aptgpu_plan_process_device_image(self._p, k, (C.c_void_p * k)(*d_rows),
+                                                      (C.c_size_t * k)(*rows_cap), kind, p, int(rotate),
+                                                      C.byref(ccol) if ccol is not None else None, int(channels),
+                                                      (C.c_void_p * k)(*d_images), err, _ERRCAP), err)
 
     def image_results(self, count=1) -> List[ImageResult]:
         arr = (ImageResult * count)()

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "apt_capi_util.hpp"
+#include "apt_kernels_color.hpp"
 
 namespace {
 
@@ -133,6 +134,59 @@ void telemetry_steps(const aptgpu_context *ctx, ImageCall &c, const ImageResult 
     step(ctx, true, "telemetry_quality", 0, q.data(), q.size(), 0);
 }
 
+// process()'s contrast limits (noaa_apt.rs:141-165) with its 0.1 status: every contrast but Telemetry
+// leaves its error (if any) in the record for the caller's c.info() after the image kernels
+void process_limits(const aptgpu_context *ctx, ImageCall &c, int contrast, float percent, aptgpu_image_result *info)
+{
+    hipStream_t s = c.sc.stream;
+    const uint64_t n = c.n;
+    if (contrast == APTGPU_CONTRAST_TELEMETRY) {
+        status(ctx, 0.1f, "Adjusting contrast from telemetry");  // noaa_apt.rs:142
+        apt::gpu::image_telemetry(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, c.d_info.ptr, true);
+        const ImageResult r = c.info();
+        copy_out(info, r);
+        throw_for(r, contrast);
+        telemetry_steps(ctx, c, r);
+    } else if (contrast == APTGPU_CONTRAST_PERCENT) {
+        // noaa_apt.rs:152-155
+        status(ctx, 0.1f, "Adjusting contrast using " + rust_display_f32(percent * 100.f) + " percent");
+        if (percent < 0.f || percent > 1.f) throw Error{ErrorKind::Internal, kBadPercent};
+        if (n == 0) throw Error{ErrorKind::Internal, kZeroMin};
+        apt::gpu::image_percent(s, c.d_x.ptr, nullptr, n, n, percent, c.ws.ptr, c.d_info.ptr);
+    } else {
+        status(ctx, 0.1f, "Mapping values");  // noaa_apt.rs:159 (MinMax and Histogram)
+        if (n == 0) throw Error{ErrorKind::Internal, kZeroMin};
+        apt::gpu::image_minmax(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, c.d_info.ptr);
+    }
+}
+
+// The checks of aptgpu_process_image / aptgpu_plan_process_device_image, all before any status callback.
+// Returns the folded tune values when false colour is on.
+bool color_args(int contrast, int rotate, const aptgpu_color_settings *color, int channels, apt::gpu::ColorTune *tune)
+{
+    if (contrast < APTGPU_CONTRAST_TELEMETRY || contrast > APTGPU_CONTRAST_HISTOGRAM)
+        throw Error{ErrorKind::Invalid, "unknown contrast adjustment"};
+    if (rotate != APTGPU_ROTATE_NO && rotate != APTGPU_ROTATE_YES)
+        throw Error{ErrorKind::Unsupported, "Rotate::Orbit needs orbit propagation (host side, out of scope)"};
+    if (channels != 1 && channels != 4) throw Error{ErrorKind::Invalid, "channels must be 1 (gray) or 4 (RGBA)"};
+    if (!color) return false;
+    if (color->struct_size < sizeof(aptgpu_color_settings) || !color->palette_rgb)
+        throw Error{ErrorKind::Invalid, "aptgpu_color_settings: struct_size or palette_rgb not set"};
+    if (contrast == APTGPU_CONTRAST_HISTOGRAM)
+        throw Error{ErrorKind::Unsupported,
+                    "histogram equalisation of a false-colour image (CIE Lab, imageext.rs:51-64) is out of scope"};
+    if (channels != 4) throw Error{ErrorKind::Invalid, "false colour needs channels = 4 (RGBA)"};
+    // tune_input_values (processing.rs:126-140): the per-call part, f32 as the reference rounds it
+    const float factor = 0.3f;
+    const float s_a = color->ch_a_tune_start * factor, e_a = color->ch_a_tune_end * factor;
+    const float s_b = color->ch_b_tune_start * factor, e_b = color->ch_b_tune_end * factor;
+    tune->k_a = 1.f + e_a - s_a;
+    tune->o_a = s_a * 255.f;
+    tune->k_b = 1.f + e_b - s_b;
+    tune->o_b = s_b * 255.f;
+    return true;
+}
+
 int extreme(const aptgpu_context *ctx, const float *signal, size_t n, float *out, bool want_max, char *err,
             size_t err_cap)
 {
@@ -236,24 +290,7 @@ int aptgpu_process_gray(const aptgpu_context *ctx, const float *signal, size_t n
             throw Error{ErrorKind::Unsupported, "Rotate::Orbit needs orbit propagation (host side, out of scope)"};
         ImageCall c(ctx, signal, n);
         hipStream_t s = c.sc.stream;
-        if (contrast == APTGPU_CONTRAST_TELEMETRY) {
-            status(ctx, 0.1f, "Adjusting contrast from telemetry");  // noaa_apt.rs:142
-            apt::gpu::image_telemetry(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, c.d_info.ptr, true);
-            const ImageResult r = c.info();
-            copy_out(info, r);
-            throw_for(r, contrast);
-            telemetry_steps(ctx, c, r);
-        } else if (contrast == APTGPU_CONTRAST_PERCENT) {
-            // noaa_apt.rs:152-155
-            status(ctx, 0.1f, "Adjusting contrast using " + rust_display_f32(percent * 100.f) + " percent");
-            if (percent < 0.f || percent > 1.f) throw Error{ErrorKind::Internal, kBadPercent};
-            if (n == 0) throw Error{ErrorKind::Internal, kZeroMin};
-            apt::gpu::image_percent(s, c.d_x.ptr, nullptr, n, n, percent, c.ws.ptr, c.d_info.ptr);
-        } else {
-            status(ctx, 0.1f, "Mapping values");  // noaa_apt.rs:159
-            if (n == 0) throw Error{ErrorKind::Internal, kZeroMin};
-            apt::gpu::image_minmax(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, c.d_info.ptr);
-        }
+        process_limits(ctx, c, contrast, percent, info);
         status(ctx, 0.3f, "Generating image");  // noaa_apt.rs:180
         apt::DeviceBuffer<uint8_t> d_img;
         d_img.alloc(n + 16);
@@ -295,6 +332,84 @@ int aptgpu_plan_process_device(aptgpu_plan *plan, int count, const float *const 
             plan->enqueue_image(i, d_rows[i], static_cast<uint64_t>(rows_cap[i]) * 2080u, contrast, percent, rotate == APTGPU_ROTATE_YES,
                                 d_images[i]);
         }
+        return APTGPU_OK;
+    });
+}
+
+int aptgpu_process_image(const aptgpu_context *ctx, const float *signal, size_t n, int contrast, float percent,
+                         int rotate, const aptgpu_color_settings *color, int channels, uint8_t **image_out,
+                         size_t *n_out, aptgpu_image_result *info, char *err, size_t err_cap)
+{
+    if ((!signal && n) || !image_out || !n_out) return APTGPU_ERR_INVALID;
+    *image_out = nullptr;
+    *n_out = 0;
+    return guarded(err, err_cap, [&] {
+        apt::gpu::ColorTune tune{};
+        const bool colored = color_args(contrast, rotate, color, channels, &tune);
+        std::vector<uint32_t> packed;  // (outlives the call's stream: ~ImageCall synchronises it)
+        ImageCall c(ctx, signal, n);
+        hipStream_t s = c.sc.stream;
+        process_limits(ctx, c, contrast, percent, info);
+        status(ctx, 0.3f, "Generating image");  // noaa_apt.rs:180
+        const size_t bytes = n / 2080 * 2080 * static_cast<size_t>(channels);
+        apt::DeviceBuffer<char> cws;
+        cws.alloc(apt::gpu::color_ws_bytes());
+        apt::hip_check(apt::gpu::color_ws_init(s, cws.ptr), "hipMemsetAsync");
+        if (colored) {
+            packed.resize(65536);
+            apt::gpu::color_pack_palette(color->palette_rgb, packed.data());
+            apt::hip_check(hipMemcpyAsync(apt::gpu::color_ws_palette(cws.ptr), packed.data(),
+                                          packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s),
+                           "hipMemcpyAsync H2D (palette)");
+        }
+        apt::DeviceBuffer<uint8_t> d_img;
+        d_img.alloc(bytes + 16);
+        const bool equalize = contrast == APTGPU_CONTRAST_HISTOGRAM;
+        if (equalize) apt::gpu::image_equalize(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, cws.ptr);
+        if (rotate == APTGPU_ROTATE_YES) status(ctx, 0.90f, "Rotating output image");  // noaa_apt.rs:229
+        apt::gpu::image_color(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, cws.ptr, equalize, colored ? &tune : nullptr,
+                              channels, rotate == APTGPU_ROTATE_YES, d_img.ptr, c.d_info.ptr);
+        apt::hip_check(hipGetLastError(), "kernel launch (image stage)");
+        const ImageResult r = c.info();
+        copy_out(info, r);
+        throw_for(r, contrast);
+        uint8_t *h = host_alloc<uint8_t>(bytes);
+        if (bytes && (hipMemcpyAsync(h, d_img.ptr, bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                      hipStreamSynchronize(s) != hipSuccess)) {
+            std::free(h);
+            throw Error{ErrorKind::Hip, "D2H copy failed"};
+        }
+        *image_out = h;
+        *n_out = bytes;
+        return APTGPU_OK;
+    });
+}
+
+int aptgpu_plan_process_device_image(aptgpu_plan *plan, int count, const float *const *d_rows,
+                                     const size_t *rows_cap, int contrast, float percent, int rotate,
+                                     const aptgpu_color_settings *color, int channels,
+                                     uint8_t *const *d_images, char *err, size_t err_cap)
+{
+    if (!plan || count < 0 || !d_rows || !rows_cap || !d_images) return APTGPU_ERR_INVALID;
+    return guarded(err, err_cap, [&] {
+        apt::gpu::ColorTune tune{};
+        const bool colored = color_args(contrast, rotate, color, channels, &tune);
+        if (static_cast<size_t>(count) > plan->last_slots.size())
+            throw Error{ErrorKind::Invalid, "count exceeds the recordings of the last decode call"};
+        if (contrast == APTGPU_CONTRAST_PERCENT && (percent < 0.f || percent > 1.f))
+            throw Error{ErrorKind::Internal, kBadPercent};
+        const uintptr_t align = channels == 4 ? 15u : 3u;
+        for (int i = 0; i < count; ++i) {
+            if (!d_rows[i] || !d_images[i]) throw Error{ErrorKind::Invalid, "null device pointer"};
+            if (reinterpret_cast<uintptr_t>(d_images[i]) & align)
+                throw Error{ErrorKind::Invalid, channels == 4 ? "d_images must be 16-byte aligned for channels = 4"
+                                                              : "d_images must be 4-byte aligned"};
+        }
+        apt::hip_check(hipSetDevice(plan->device), "hipSetDevice");
+        if (colored) plan->set_palette(color->palette_rgb);
+        for (int i = 0; i < count; ++i)
+            plan->enqueue_image_color(i, d_rows[i], static_cast<uint64_t>(rows_cap[i]) * 2080u, contrast, percent,
+                                      rotate == APTGPU_ROTATE_YES, colored ? &tune : nullptr, channels, d_images[i]);
         return APTGPU_OK;
     });
 }

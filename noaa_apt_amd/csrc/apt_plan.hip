@@ -855,8 +855,7 @@ void aptgpu_plan::run_call(int count, const Input *ins, float *const *d_rows, co
 }
 
 // ------------------------------------------------------------------ image stage
-void aptgpu_plan::enqueue_image(int i, const float *d_rows, uint64_t rows_cap_floats, int contrast,
-                                float percent, bool rotate, uint8_t *d_image)
+aptgpu_plan::ImageTarget aptgpu_plan::image_target(int i, uint64_t rows_cap_floats)
 {
     using namespace apt::gpu;
     const size_t slot = static_cast<size_t>(last_slots[static_cast<size_t>(i)]);
@@ -871,22 +870,83 @@ void aptgpu_plan::enqueue_image(int i, const float *d_rows, uint64_t rows_cap_fl
         d_image_results.alloc(slots.size());
     }
     if (!sl.image_ws.ptr) sl.image_ws.alloc(image_ws_bytes(ws_cap));
-    hipStream_t cur = stream_of(i);
-    ImageResult *out = d_image_results.ptr + slot;
-    const Result *res = d_results.ptr + slot;
-    void *ws = sl.image_ws.ptr;
-    auto timed = [&](const char *name, auto &&launch) {
-        timer.begin(cur, name, false);
-        launch();
-        timer.end(cur);
-    };
+    return ImageTarget{sl, stream_of(i), cap, sl.image_ws.ptr, d_image_results.ptr + slot, d_results.ptr + slot};
+}
+
+void aptgpu_plan::enqueue_limits(const ImageTarget &t, const float *d_rows, int contrast, float percent)
+{
+    using namespace apt::gpu;
     // (the first kernel of every variant resets the record)
     if (contrast == APTGPU_CONTRAST_TELEMETRY)
-        timed("image_telemetry", [&] { image_telemetry(cur, d_rows, res, 0, cap, ws, out, true); });
+        timed(t.stream, "image_telemetry", [&] { image_telemetry(t.stream, d_rows, t.res, 0, t.cap, t.ws, t.out, true); });
     else if (contrast == APTGPU_CONTRAST_PERCENT)
-        timed("image_percent", [&] { image_percent(cur, d_rows, res, 0, cap, percent, ws, out); });
-    else
-        timed("image_minmax", [&] { image_minmax(cur, d_rows, res, 0, cap, ws, out); });
-    timed("image_map_u8", [&] { image_map_u8(cur, d_rows, res, 0, cap, ws, rotate, d_image, out); });
+        timed(t.stream, "image_percent", [&] { image_percent(t.stream, d_rows, t.res, 0, t.cap, percent, t.ws, t.out); });
+    else  // MinMax, and Histogram's limits (noaa_apt.rs:158-164)
+        timed(t.stream, "image_minmax", [&] { image_minmax(t.stream, d_rows, t.res, 0, t.cap, t.ws, t.out); });
+}
+
+void aptgpu_plan::enqueue_image(int i, const float *d_rows, uint64_t rows_cap_floats, int contrast,
+                                float percent, bool rotate, uint8_t *d_image)
+{
+    using namespace apt::gpu;
+    const ImageTarget t = image_target(i, rows_cap_floats);
+    enqueue_limits(t, d_rows, contrast, percent);
+    timed(t.stream, "image_map_u8", [&] { image_map_u8(t.stream, d_rows, t.res, 0, t.cap, t.ws, rotate, d_image, t.out); });
+    apt::hip_check(hipGetLastError(), "kernel launch (image stage)");
+}
+
+aptgpu_plan::Palette::~Palette()
+{
+    for (hipEvent_t ev : uploaded)
+        if (ev) (void)hipEventDestroy(ev);
+    if (pinned) (void)hipHostFree(pinned);
+}
+
+void aptgpu_plan::set_palette(const uint8_t *rgb)
+{
+    constexpr size_t kBytes = 256 * 256 * 3;
+    if (palette.gen != 0 && std::memcmp(palette.rgb.data(), rgb, kBytes) == 0) return;
+    if (!palette.pinned) {
+        apt::hip_check(hipHostMalloc(reinterpret_cast<void **>(&palette.pinned), 65536 * sizeof(uint32_t)),
+                       "hipHostMalloc");
+        palette.uploaded.assign(streams.size(), nullptr);
+    }
+    // the slots' uploads of the previous generation read `pinned`: wait for them (only when the palette
+    // changes; a plan that keeps one palette never waits here)
+    for (hipEvent_t ev : palette.uploaded)
+        if (ev) apt::hip_check(hipEventSynchronize(ev), "hipEventSynchronize");
+    palette.rgb.assign(rgb, rgb + kBytes);
+    apt::gpu::color_pack_palette(rgb, palette.pinned);
+    ++palette.gen;
+}
+
+void aptgpu_plan::enqueue_image_color(int i, const float *d_rows, uint64_t rows_cap_floats, int contrast,
+                                      float percent, bool rotate, const apt::gpu::ColorTune *tune, int channels,
+                                      uint8_t *d_image)
+{
+    using namespace apt::gpu;
+    const ImageTarget t = image_target(i, rows_cap_floats);
+    Slot &sl = t.slot;
+    if (!sl.color_ws.ptr) {
+        sl.color_ws.alloc(color_ws_bytes());
+        apt::hip_check(color_ws_init(t.stream, sl.color_ws.ptr), "hipMemsetAsync");
+    }
+    if (tune && sl.palette_gen != palette.gen) {
+        apt::hip_check(hipMemcpyAsync(color_ws_palette(sl.color_ws.ptr), palette.pinned, 65536 * sizeof(uint32_t),
+                                      hipMemcpyHostToDevice, t.stream),
+                       "hipMemcpyAsync H2D (palette)");
+        hipEvent_t &ev = palette.uploaded[static_cast<size_t>(last_stream)];
+        if (!ev) apt::hip_check(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
+        apt::hip_check(hipEventRecord(ev, t.stream), "hipEventRecord");
+        sl.palette_gen = palette.gen;
+    }
+    enqueue_limits(t, d_rows, contrast, percent);
+    const bool equalize = contrast == APTGPU_CONTRAST_HISTOGRAM;
+    if (equalize)
+        timed(t.stream, "image_equalize", [&] { image_equalize(t.stream, d_rows, t.res, 0, t.cap, t.ws, sl.color_ws.ptr); });
+    timed(t.stream, "image_color", [&] {
+        image_color(t.stream, d_rows, t.res, 0, t.cap, t.ws, sl.color_ws.ptr, equalize, tune, channels, rotate, d_image,
+                    t.out);
+    });
     apt::hip_check(hipGetLastError(), "kernel launch (image stage)");
 }

@@ -11,6 +11,7 @@
 #include "../../include/aptgpu.h"
 #include "apt_host.hpp"
 #include "apt_kernels.hpp"
+#include "apt_kernels_color.hpp"
 #include "apt_wav.hpp"
 
 namespace apt {
@@ -174,6 +175,8 @@ struct aptgpu_plan {
         apt::DeviceBuffer<uint64_t> nanw;     // 52-bit words of NaN correlation positions
         apt::DeviceBuffer<uint32_t> slot_nt, slot_cnt, flags, orbit_ws;
         apt::DeviceBuffer<char> image_ws;  // scratch of the image stage, allocated on first use
+        apt::DeviceBuffer<char> color_ws;  // histograms, tables and palette of the colour stage, on first use
+        uint64_t palette_gen = 0;          // generation of the palette color_ws holds (0 = none)
         apt::DeviceBuffer<float> ingest;   // WAV -> f32 staging when the fused PCM16 path does not apply
     };
     std::vector<Slot> slots;
@@ -187,6 +190,40 @@ struct aptgpu_plan {
     void enqueue_image(int i, const float *d_rows, uint64_t rows_cap_floats, int contrast, float percent,
                        bool rotate, uint8_t *d_image);
     hipStream_t stream_of(int) { return streams[static_cast<size_t>(last_stream)]; }
+    struct ImageTarget {
+        Slot &slot;
+        hipStream_t stream;
+        uint64_t cap;  // floats of the rows buffer the image stage may read
+        void *ws;
+        apt::gpu::ImageResult *out;
+        const apt::gpu::Result *res;
+    };
+    ImageTarget image_target(int i, uint64_t rows_cap_floats);  // allocates the slot's scratch on first use
+    void enqueue_limits(const ImageTarget &t, const float *d_rows, int contrast, float percent);
+    template <typename Fn>
+    void timed(hipStream_t s, const char *name, Fn &&launch)
+    {
+        timer.begin(s, name, false);
+        launch();
+        timer.end(s);
+    }
+    // The same with every contrast (APTGPU_CONTRAST_HISTOGRAM too), optional false colour and 1 or 4 bytes per
+    // pixel (aptgpu_plan_process_device_image).  set_palette first when tune is non-null.
+    void enqueue_image_color(int i, const float *d_rows, uint64_t rows_cap_floats, int contrast, float percent,
+                             bool rotate, const apt::gpu::ColorTune *tune, int channels, uint8_t *d_image);
+    // The false-colour palette (256*256*3 RGB).  The plan keeps a host copy; bytes that differ from it start a new
+    // generation, which every slot uploads on its own stream the next time it colours an image.
+    void set_palette(const uint8_t *rgb);
+    struct Palette {
+        std::vector<uint8_t> rgb;   // the host copy the next call compares against
+        uint32_t *pinned = nullptr; // packed RGBA of the current generation, the source of the slots' uploads
+        std::vector<hipEvent_t> uploaded;  // per stream: behind its latest upload from `pinned` (null: none yet)
+        uint64_t gen = 0;
+        Palette() = default;
+        Palette(const Palette &) = delete;
+        Palette &operator=(const Palette &) = delete;
+        ~Palette();
+    } palette;
 
     apt::KernelTimer timer;
 
