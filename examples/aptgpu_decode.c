@@ -2,14 +2,16 @@
  * aptgpu_decode.c — minimal C caller of the drop-in boundary (include/aptgpu.h):
  *
  *     aptgpu_decode in.wav out.pgm [contrast: telemetry|percent|minmax] [--no-sync]
- *                   [--histogram] [--palette FILE]
+ *                   [--histogram] [--palette FILE] [--lab]
  *
  * What `noaa-apt in.wav -o out.png` does (main.rs:91-110, noaa_apt.rs:114-235) minus PNG
  * encoding and the map overlay: load -> decode -> contrast limits -> 8-bit image, written as a
  * binary PGM.  --histogram: Contrast::Histogram (MinMax limits, then each channel's histogram
  * equalised).  --palette FILE: false colour (`-F`, tune values 0) from a raw 256 x 256 RGB palette
  * (196 608 bytes, pixel (a, b) at (b*256 + a)*3), written as a binary PPM (the RGBA image without
- * its alpha).  Plain C99, links only libaptgpu.so.
+ * its alpha).  --lab: with --histogram and --palette, equalise the false-colour image as the
+ * reference does, channel A in CIE Lab (APTGPU_COLOR_EQUALIZE_LAB); without it that combination
+ * is refused.  Plain C99, links only libaptgpu.so.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -27,10 +29,10 @@ int main(int argc, char **argv)
 {
     if (argc < 3) {
         fprintf(stderr, "usage: %s in.wav out.pgm [telemetry|percent|minmax] [--no-sync] [--histogram] "
-                "[--palette FILE]\n", argv[0]);
+                "[--palette FILE] [--lab]\n", argv[0]);
         return 2;
     }
-    int contrast = APTGPU_CONTRAST_PERCENT, sync = 1;
+    int contrast = APTGPU_CONTRAST_PERCENT, sync = 1, lab = 0;
     const char *palette_path = NULL;
     for (int i = 3; i < argc; ++i) {
         if (!strcmp(argv[i], "telemetry")) contrast = APTGPU_CONTRAST_TELEMETRY;
@@ -38,6 +40,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "minmax")) contrast = APTGPU_CONTRAST_MINMAX;
         else if (!strcmp(argv[i], "--histogram")) contrast = APTGPU_CONTRAST_HISTOGRAM;
         else if (!strcmp(argv[i], "--no-sync")) sync = 0;
+        else if (!strcmp(argv[i], "--lab")) lab = 1;
         else if (!strcmp(argv[i], "--palette") && i + 1 < argc) palette_path = argv[++i];
     }
 
@@ -47,6 +50,7 @@ int main(int argc, char **argv)
     memset(&color, 0, sizeof color);
     color.struct_size = sizeof color;
     color.palette_rgb = palette;
+    if (lab) color.flags = APTGPU_COLOR_EQUALIZE_LAB;
     if (palette_path) {
         FILE *p = fopen(palette_path, "rb");
         if (!p || fread(palette, 1, sizeof palette, p) != sizeof palette || fgetc(p) != EOF) {

@@ -360,6 +360,12 @@ int aptgpu_demodulate(const aptgpu_context *ctx, const float *signal, size_t n,
 /* dsp::filter(context, signal, filter)             src/dsp.rs:386-410 */
 int aptgpu_filter_signal(const aptgpu_context *ctx, const float *signal, size_t n,
                          aptgpu_filter filt, float **out, char *err, size_t err_cap);
+/* lab 0.11.0's Lab::from_rgb / Lab::to_rgb (Cargo.lock:991) as the Lab path of aptgpu_process_image
+ * runs them (CPU only): rgb holds n (R, G, B) u8 triples, lab n (L, a, b) f32 triples.  from_rgb calls
+ * the C library's powf; to_rgb is f32 arithmetic plus a threshold quantiser that stands in for the
+ * crate's final powf + round + clamp.  Restated from the crate's published source. */
+int aptgpu_lab_from_rgb(const uint8_t *rgb, size_t n, float *lab);
+int aptgpu_lab_to_rgb(const float *lab, size_t n, uint8_t *rgb);
 /* find_sync(context, signal, work_rate)            src/decode.rs:204-263
  * correlation_out nullable (the "sync_correlation" step). */
 int aptgpu_find_sync(const aptgpu_context *ctx, const float *signal, size_t n,
@@ -371,11 +377,12 @@ int aptgpu_find_sync(const aptgpu_context *ctx, const float *signal, size_t n,
 /* ====================================================================== */
 /* noaa_apt::process() (src/noaa_apt.rs:132-235) without the map overlay: contrast limits  */
 /* -> map_signal_u8, plus telemetry.rs, histogram equalisation (imageext.rs:21-45), palette */
-/* false colour (processing.rs:113-165) and the 180-degree channel rotation.  The map      */
-/* overlay, Rotate::Orbit and equalisation of a false-colour image (CIE Lab, imageext.rs:51-64) */
-/* stay out of scope.  aptgpu_process_gray / aptgpu_plan_process_device: the grayscale   */
-/* image of the first three contrasts; aptgpu_process_image / aptgpu_plan_process_device_image: */
-/* every contrast, optional false colour, gray or RGBA output.                             */
+/* false colour (processing.rs:113-165) and the 180-degree channel rotation.  Equalisation */
+/* of a false-colour image (CIE Lab, imageext.rs:51-64) is opt-in                        */
+/* (APTGPU_COLOR_EQUALIZE_LAB); the map overlay and Rotate::Orbit stay out of scope.       */
+/* aptgpu_process_gray / aptgpu_plan_process_device: the grayscale image of the first     */
+/* three contrasts; aptgpu_process_image / aptgpu_plan_process_device_image: every        */
+/* contrast, optional false colour, gray or RGBA output.                                   */
 
 #define APTGPU_CONTRAST_TELEMETRY 0 /* Contrast::Telemetry   src/noaa_apt.rs:141-150 */
 #define APTGPU_CONTRAST_PERCENT 1   /* Contrast::Percent(p)  src/noaa_apt.rs:151-157 */
@@ -438,16 +445,22 @@ int aptgpu_plan_process_device(aptgpu_plan *plan, int count, const float *const 
  * (`image::open(..).into_rgb8()`, 256 x 256, alpha dropped). */
 typedef struct aptgpu_color_settings {
     uint32_t struct_size;        /* sizeof(aptgpu_color_settings) */
-    uint32_t reserved;
+    uint32_t flags;              /* APTGPU_COLOR_* bits; 0 = the behaviour of ABI 2 before flags */
     const uint8_t *palette_rgb;  /* host, 256*256*3: pixel (a, b) at (b*256 + a)*3 */
     float ch_a_tune_start, ch_a_tune_end, ch_b_tune_start, ch_b_tune_end;
 } aptgpu_color_settings;
+/* With APTGPU_CONTRAST_HISTOGRAM: equalise the false-colour image as the reference does, channel A in
+ * CIE Lab (98 % limits, false colour, then L equalised over 101 bins, imageext.rs:50-64; channel B as
+ * the gray equalisation).  Bit-exact against tests/np_lab_model.py, a restatement of the lab crate
+ * 0.11.0.  No effect with the other contrasts; any other bit is APTGPU_ERR_INVALID. */
+#define APTGPU_COLOR_EQUALIZE_LAB (1u << 0)
 /* process() for every contrast incl. APTGPU_CONTRAST_HISTOGRAM, with optional false colour (color
  * nullable).  channels 1 = the gray image (no colour allowed), 4 = the reference's RgbaImage (A = 255).
  * The image has height = n / 2080 whole rows; *image_out malloc'd, *n_out = height*2080*channels
  * bytes, info->n_px = height*2080.  Status callbacks as aptgpu_process_gray (Histogram: "Mapping
- * values").  Refused with APTGPU_ERR_UNSUPPORTED before any callback: Rotate::Orbit, and false
- * colour together with Histogram (the reference equalises channel A in CIE Lab then). */
+ * values").  Histogram with false colour needs color->flags & APTGPU_COLOR_EQUALIZE_LAB (the reference
+ * equalises channel A in CIE Lab then); without it, and for Rotate::Orbit, the call is refused with
+ * APTGPU_ERR_UNSUPPORTED before any callback. */
 int aptgpu_process_image(const aptgpu_context *ctx, const float *signal, size_t n, int contrast,
                          float percent, int rotate, const aptgpu_color_settings *color, int channels,
                          uint8_t **image_out, size_t *n_out, aptgpu_image_result *info, char *err,

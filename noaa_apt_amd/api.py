@@ -126,7 +126,7 @@ class ImageResult(C.Structure):
 
 
 class _CColorSettings(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("palette_rgb", _u8p),
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("palette_rgb", _u8p),
                 ("ch_a_tune_start", C.c_float), ("ch_a_tune_end", C.c_float),
                 ("ch_b_tune_start", C.c_float), ("ch_b_tune_end", C.c_float)]
 
@@ -231,6 +231,8 @@ def lib():
     L.aptgpu_plan_collect_timing.argtypes = [vp, C.POINTER(KernelTime), sz, C.POINTER(sz)]
     L.aptgpu_filter_design.argtypes = [C.POINTER(_CFilter), C.POINTER(_f32p), C.POINTER(sz)]
     L.aptgpu_filter_resample.argtypes = [C.POINTER(_CFilter), u32, u32]
+    L.aptgpu_lab_from_rgb.argtypes = [_u8p, sz, _f32p]
+    L.aptgpu_lab_to_rgb.argtypes = [_f32p, sz, _u8p]
     L.aptgpu_filter_resample.restype = None
     L.aptgpu_generate_sync_frame.argtypes = [u32, C.POINTER(_i8p), C.POINTER(sz), C.c_char_p, sz]
     L.aptgpu_resample_with_filter.argtypes = [C.POINTER(_CContext), _f32p, sz, u32, u32, _CFilter,
@@ -704,14 +706,43 @@ def _rust_debug_str(text):
     return '"' + "".join(out) + '"'
 
 
+COLOR_EQUALIZE_LAB = 1 << 0  # aptgpu_color_settings.flags
+
+
+def lab_from_rgb(rgb):
+    """Lab::from_rgb of the lab crate 0.11.0 (CPU, aptgpu_lab_from_rgb): (..., 3) uint8 -> (..., 3) float32 L, a, b."""
+    x = np.ascontiguousarray(rgb, np.uint8)
+    if x.shape[-1:] != (3,):
+        raise InvalidError("lab_from_rgb: the last axis must hold R, G, B")
+    out = np.empty(x.shape, np.float32)
+    _check(lib().aptgpu_lab_from_rgb(x.ctypes.data_as(_u8p), x.size // 3, out.ctypes.data_as(_f32p)))
+    return out
+
+
+def lab_to_rgb(lab):
+    """Lab::to_rgb of the lab crate 0.11.0 (CPU, aptgpu_lab_to_rgb) as the GPU's Lab path computes it:
+    (..., 3) float32 L, a, b -> (..., 3) uint8."""
+    x = np.ascontiguousarray(lab, np.float32)
+    if x.shape[-1:] != (3,):
+        raise InvalidError("lab_to_rgb: the last axis must hold L, a, b")
+    out = np.empty(x.shape, np.uint8)
+    _check(lib().aptgpu_lab_to_rgb(x.ctypes.data_as(_f32p), x.size // 3, out.ctypes.data_as(_u8p)))
+    return out
+
+
 class ColorSettings:
     """noaa_apt::ColorSettings (noaa_apt.rs:63-71): the false-colour palette and the tune values of both channels.
 
     `palette` is a path, decoded here with PIL's convert("RGB") as processing::false_color decodes it with
     `image::open(..).into_rgb8()` (processing.rs:113-121: alpha dropped), or a (256, 256, 3) or (256, 256, 4) uint8
-    array, indexed [b, a] (alpha dropped).  Errors are the reference's InvalidInput texts."""
+    array, indexed [b, a] (alpha dropped).  Errors are the reference's InvalidInput texts.
 
-    def __init__(self, palette, ch_a_tune_start=0.0, ch_a_tune_end=0.0, ch_b_tune_start=0.0, ch_b_tune_end=0.0):
+    `equalize_lab` (opt-in) lets Contrast.HISTOGRAM run with this colour: the reference's CIE Lab equalisation of
+    channel A (APTGPU_COLOR_EQUALIZE_LAB; bit-exact against a restatement of the lab crate).
+    Without it that combination raises UnsupportedError; with the other contrasts it changes nothing."""
+
+    def __init__(self, palette, ch_a_tune_start=0.0, ch_a_tune_end=0.0, ch_b_tune_start=0.0, ch_b_tune_end=0.0,
+                 equalize_lab=False):
         if isinstance(palette, (str, bytes, os.PathLike)):
             path = os.fsdecode(palette)
             try:
@@ -730,9 +761,11 @@ class ColorSettings:
         self.palette = np.ascontiguousarray(arr)
         self.ch_a_tune_start, self.ch_a_tune_end = float(ch_a_tune_start), float(ch_a_tune_end)
         self.ch_b_tune_start, self.ch_b_tune_end = float(ch_b_tune_start), float(ch_b_tune_end)
+        self.equalize_lab = bool(equalize_lab)
 
     def _c(self):
-        return _CColorSettings(C.sizeof(_CColorSettings), 0, self.palette.ctypes.data_as(_u8p),
+        flags = COLOR_EQUALIZE_LAB if self.equalize_lab else 0
+        return _CColorSettings(C.sizeof(_CColorSettings), flags, self.palette.ctypes.data_as(_u8p),
                                self.ch_a_tune_start, self.ch_a_tune_end, self.ch_b_tune_start, self.ch_b_tune_end)
 
 
@@ -813,9 +846,9 @@ def process(context, signal, contrast_adjustment, rotate=Rotate.NO, color=None, 
             return_info=False):
     """noaa_apt::process (noaa_apt.rs:132-235) without the map overlay.  Returns the height x 2080 u8
     gray image, or with `color` (a ColorSettings) the height x 2080 x 4 RGBA image of the reference's
-    false colour (A = 255).  Contrast.HISTOGRAM equalises each channel half of the gray image.
-    Unsupported: the map overlay (`orbit`), Rotate.ORBIT, and HISTOGRAM together with false colour
-    (the reference equalises channel A in CIE Lab then)."""
+    false colour (A = 255).  Contrast.HISTOGRAM equalises each channel half of the gray image; together with
+    false colour it needs ColorSettings(equalize_lab=True) (the reference equalises channel A in CIE Lab then).
+    Unsupported: the map overlay (`orbit`), Rotate.ORBIT, and HISTOGRAM with colour without equalize_lab."""
     if orbit is not None:
         raise UnsupportedError("the map overlay is not part of the GPU path")
     if color is not None and not isinstance(color, ColorSettings):

@@ -1,6 +1,7 @@
 // apt_capi_image.hip — extern "C" surface of include/aptgpu.h §4: the consumers of decode()'s
 // pixel rows (contrast limits, u8 mapping, telemetry), host-buffer and device-resident forms.
 #include <cmath>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -134,9 +135,12 @@ void telemetry_steps(const aptgpu_context *ctx, ImageCall &c, const ImageResult 
     step(ctx, true, "telemetry_quality", 0, q.data(), q.size(), 0);
 }
 
-// process()'s contrast limits (noaa_apt.rs:141-165) with its 0.1 status: every contrast but Telemetry
-// leaves its error (if any) in the record for the caller's c.info() after the image kernels
-void process_limits(const aptgpu_context *ctx, ImageCall &c, int contrast, float percent, aptgpu_image_result *info)
+// process()'s contrast limits (noaa_apt.rs:141-175) with its 0.1 status: every contrast but Telemetry
+// leaves its error (if any) in the record for the caller's c.info() after the image kernels.  lab:
+// Histogram with false colour, whose limits are misc::percent(signal, 0.98) once get_min / get_max
+// have passed (noaa_apt.rs:170-175); their only error is the zero length, checked first.
+void process_limits(const aptgpu_context *ctx, ImageCall &c, int contrast, float percent, aptgpu_image_result *info,
+                    bool lab = false)
 {
     hipStream_t s = c.sc.stream;
     const uint64_t n = c.n;
@@ -156,14 +160,19 @@ void process_limits(const aptgpu_context *ctx, ImageCall &c, int contrast, float
     } else {
         status(ctx, 0.1f, "Mapping values");  // noaa_apt.rs:159 (MinMax and Histogram)
         if (n == 0) throw Error{ErrorKind::Internal, kZeroMin};
-        apt::gpu::image_minmax(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, c.d_info.ptr);
+        if (lab)
+            apt::gpu::image_percent(s, c.d_x.ptr, nullptr, n, n, 0.98f, c.ws.ptr, c.d_info.ptr);
+        else
+            apt::gpu::image_minmax(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, c.d_info.ptr);
     }
 }
 
 // The checks of aptgpu_process_image / aptgpu_plan_process_device_image, all before any status callback.
-// Returns the folded tune values when false colour is on.
-bool color_args(int contrast, int rotate, const aptgpu_color_settings *color, int channels, apt::gpu::ColorTune *tune)
+// Returns the folded tune values when false colour is on, and in *lab whether the Lab path runs.
+bool color_args(int contrast, int rotate, const aptgpu_color_settings *color, int channels, apt::gpu::ColorTune *tune,
+                bool *lab)
 {
+    *lab = false;
     if (contrast < APTGPU_CONTRAST_TELEMETRY || contrast > APTGPU_CONTRAST_HISTOGRAM)
         throw Error{ErrorKind::Invalid, "unknown contrast adjustment"};
     if (rotate != APTGPU_ROTATE_NO && rotate != APTGPU_ROTATE_YES)
@@ -172,9 +181,14 @@ bool color_args(int contrast, int rotate, const aptgpu_color_settings *color, in
     if (!color) return false;
     if (color->struct_size < sizeof(aptgpu_color_settings) || !color->palette_rgb)
         throw Error{ErrorKind::Invalid, "aptgpu_color_settings: struct_size or palette_rgb not set"};
-    if (contrast == APTGPU_CONTRAST_HISTOGRAM)
-        throw Error{ErrorKind::Unsupported,
-                    "histogram equalisation of a false-colour image (CIE Lab, imageext.rs:51-64) is out of scope"};
+    if (color->flags & ~APTGPU_COLOR_EQUALIZE_LAB) throw Error{ErrorKind::Invalid, "aptgpu_color_settings: unknown flags"};
+    if (contrast == APTGPU_CONTRAST_HISTOGRAM) {
+        if (!(color->flags & APTGPU_COLOR_EQUALIZE_LAB))
+            throw Error{ErrorKind::Unsupported,
+                        "histogram equalisation of a false-colour image (CIE Lab, imageext.rs:51-64) needs "
+                        "APTGPU_COLOR_EQUALIZE_LAB in aptgpu_color_settings.flags"};
+        *lab = true;
+    }
     if (channels != 4) throw Error{ErrorKind::Invalid, "false colour needs channels = 4 (RGBA)"};
     // tune_input_values (processing.rs:126-140): the per-call part, f32 as the reference rounds it
     const float factor = 0.3f;
@@ -345,17 +359,25 @@ int aptgpu_process_image(const aptgpu_context *ctx, const float *signal, size_t 
     *n_out = 0;
     return guarded(err, err_cap, [&] {
         apt::gpu::ColorTune tune{};
-        const bool colored = color_args(contrast, rotate, color, channels, &tune);
+        bool lab = false;
+        const bool colored = color_args(contrast, rotate, color, channels, &tune, &lab);
         std::vector<uint32_t> packed;  // (outlives the call's stream: ~ImageCall synchronises it)
+        std::shared_ptr<const apt::lab::Tables> lab_tables;  // (likewise)
         ImageCall c(ctx, signal, n);
         hipStream_t s = c.sc.stream;
-        process_limits(ctx, c, contrast, percent, info);
+        process_limits(ctx, c, contrast, percent, info, lab);
         status(ctx, 0.3f, "Generating image");  // noaa_apt.rs:180
         const size_t bytes = n / 2080 * 2080 * static_cast<size_t>(channels);
         apt::DeviceBuffer<char> cws;
         cws.alloc(apt::gpu::color_ws_bytes());
         apt::hip_check(apt::gpu::color_ws_init(s, cws.ptr), "hipMemsetAsync");
-        if (colored) {
+        apt::DeviceBuffer<char> lws;
+        if (lab) {
+            lab_tables = apt::lab::tables_for(color->palette_rgb);
+            lws.alloc(apt::gpu::lab_ws_bytes());
+            apt::hip_check(hipMemcpyAsync(lws.ptr, lab_tables.get(), sizeof(apt::lab::Tables), hipMemcpyHostToDevice, s),
+                           "hipMemcpyAsync H2D (Lab tables)");
+        } else if (colored) {
             packed.resize(65536);
             apt::gpu::color_pack_palette(color->palette_rgb, packed.data());
             apt::hip_check(hipMemcpyAsync(apt::gpu::color_ws_palette(cws.ptr), packed.data(),
@@ -365,10 +387,11 @@ int aptgpu_process_image(const aptgpu_context *ctx, const float *signal, size_t 
         apt::DeviceBuffer<uint8_t> d_img;
         d_img.alloc(bytes + 16);
         const bool equalize = contrast == APTGPU_CONTRAST_HISTOGRAM;
-        if (equalize) apt::gpu::image_equalize(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, cws.ptr);
+        if (lab) apt::gpu::image_equalize_lab(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, cws.ptr, lws.ptr, tune);
+        else if (equalize) apt::gpu::image_equalize(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, cws.ptr);
         if (rotate == APTGPU_ROTATE_YES) status(ctx, 0.90f, "Rotating output image");  // noaa_apt.rs:229
         apt::gpu::image_color(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, cws.ptr, equalize, colored ? &tune : nullptr,
-                              channels, rotate == APTGPU_ROTATE_YES, d_img.ptr, c.d_info.ptr);
+                              channels, rotate == APTGPU_ROTATE_YES, d_img.ptr, c.d_info.ptr, lab ? lws.ptr : nullptr);
         apt::hip_check(hipGetLastError(), "kernel launch (image stage)");
         const ImageResult r = c.info();
         copy_out(info, r);
@@ -393,7 +416,8 @@ int aptgpu_plan_process_device_image(aptgpu_plan *plan, int count, const float *
     if (!plan || count < 0 || !d_rows || !rows_cap || !d_images) return APTGPU_ERR_INVALID;
     return guarded(err, err_cap, [&] {
         apt::gpu::ColorTune tune{};
-        const bool colored = color_args(contrast, rotate, color, channels, &tune);
+        bool lab = false;
+        const bool colored = color_args(contrast, rotate, color, channels, &tune, &lab);
         if (static_cast<size_t>(count) > plan->last_slots.size())
             throw Error{ErrorKind::Invalid, "count exceeds the recordings of the last decode call"};
         if (contrast == APTGPU_CONTRAST_PERCENT && (percent < 0.f || percent > 1.f))
@@ -406,10 +430,11 @@ int aptgpu_plan_process_device_image(aptgpu_plan *plan, int count, const float *
                                                               : "d_images must be 4-byte aligned"};
         }
         apt::hip_check(hipSetDevice(plan->device), "hipSetDevice");
-        if (colored) plan->set_palette(color->palette_rgb);
+        if (colored) plan->set_palette(color->palette_rgb, lab);
         for (int i = 0; i < count; ++i)
             plan->enqueue_image_color(i, d_rows[i], static_cast<uint64_t>(rows_cap[i]) * 2080u, contrast, percent,
-                                      rotate == APTGPU_ROTATE_YES, colored ? &tune : nullptr, channels, d_images[i]);
+                                      rotate == APTGPU_ROTATE_YES, colored ? &tune : nullptr, channels, d_images[i],
+                                      lab);
         return APTGPU_OK;
     });
 }

@@ -8,6 +8,7 @@
 #pragma once
 
 #include "apt_kernels.hpp"
+#include "apt_lab.hpp"
 
 namespace apt::gpu {
 
@@ -33,13 +34,25 @@ uint32_t *color_ws_palette(void *color_ws);
 void image_equalize(hipStream_t s, const float *x, const Result *res, uint64_t n, uint64_t cap,
                     void *image_ws, void *color_ws);
 
+// Scratch of the Lab path (equalisation of a false-colour image), allocated only when that path runs:
+// the host's lab::Tables of the palette at offset 0 (the caller uploads them), then the 101 equalised
+// L values and the RGBA of every table index, both rewritten by each call.
+size_t lab_ws_bytes();
+
+// Histogram + false colour (processing.rs:87-101 with has_color): channel A (the false-colour image
+// incl. its gray columns) equalised in CIE Lab, channel B as image_equalize.  Leaves the RGBA of every
+// Lab table index in lab_ws and channel B's table in color_ws for image_color.  tune: as image_color's.
+void image_equalize_lab(hipStream_t s, const float *x, const Result *res, uint64_t n, uint64_t cap,
+                        void *image_ws, void *color_ws, void *lab_ws, const ColorTune &tune);
+
 // The output pass: map_signal_u8, then the equalisation tables (equalize) or the palette over
 // channel A's image columns (tune != nullptr), then the optional 180-degree rotation, written as
 // `channels` bytes per pixel (1 = gray, 4 = RGBA, A = 255) for the height = n / 2080 whole rows.
-// Fills info's limits, height and n_px (= height * 2080) like image_map_u8.  out: 4-byte aligned
-// for channels 1, 16-byte aligned for channels 4.
+// lab_ws (after image_equalize_lab, with tune, equalize and channels 4): channel A comes from its RGBA
+// table instead.  Fills info's limits, height and n_px (= height * 2080) like image_map_u8.  out:
+// 4-byte aligned for channels 1, 16-byte aligned for channels 4.
 void image_color(hipStream_t s, const float *x, const Result *res, uint64_t n, uint64_t cap,
                  void *image_ws, const void *color_ws, bool equalize, const ColorTune *tune, int channels,
-                 bool rotate, uint8_t *out, ImageResult *info);
+                 bool rotate, uint8_t *out, ImageResult *info, const void *lab_ws = nullptr);
 
 }  // namespace apt::gpu

@@ -899,13 +899,31 @@ aptgpu_plan::Palette::~Palette()
 {
     for (hipEvent_t ev : uploaded)
         if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : lab_uploaded)
+        if (ev) (void)hipEventDestroy(ev);
     if (pinned) (void)hipHostFree(pinned);
+    if (lab_pinned) (void)hipHostFree(lab_pinned);
 }
 
-void aptgpu_plan::set_palette(const uint8_t *rgb)
+void aptgpu_plan::set_palette(const uint8_t *rgb, bool lab)
 {
     constexpr size_t kBytes = 256 * 256 * 3;
-    if (palette.gen != 0 && std::memcmp(palette.rgb.data(), rgb, kBytes) == 0) return;
+    if (palette.gen == 0 || std::memcmp(palette.rgb.data(), rgb, kBytes) != 0) new_palette(rgb);
+    if (!lab || palette.lab_gen == palette.gen) return;
+    if (!palette.lab_pinned) {
+        apt::hip_check(hipHostMalloc(reinterpret_cast<void **>(&palette.lab_pinned), sizeof(apt::lab::Tables)),
+                       "hipHostMalloc");
+        palette.lab_uploaded.assign(streams.size(), nullptr);
+    }
+    for (hipEvent_t ev : palette.lab_uploaded)  // as for `pinned` below
+        if (ev) apt::hip_check(hipEventSynchronize(ev), "hipEventSynchronize");
+    std::memcpy(palette.lab_pinned, apt::lab::tables_for(rgb).get(), sizeof(apt::lab::Tables));
+    palette.lab_gen = palette.gen;
+}
+
+void aptgpu_plan::new_palette(const uint8_t *rgb)
+{
+    constexpr size_t kBytes = 256 * 256 * 3;
     if (!palette.pinned) {
         apt::hip_check(hipHostMalloc(reinterpret_cast<void **>(&palette.pinned), 65536 * sizeof(uint32_t)),
                        "hipHostMalloc");
@@ -922,7 +940,7 @@ void aptgpu_plan::set_palette(const uint8_t *rgb)
 
 void aptgpu_plan::enqueue_image_color(int i, const float *d_rows, uint64_t rows_cap_floats, int contrast,
                                       float percent, bool rotate, const apt::gpu::ColorTune *tune, int channels,
-                                      uint8_t *d_image)
+                                      uint8_t *d_image, bool lab)
 {
     using namespace apt::gpu;
     const ImageTarget t = image_target(i, rows_cap_floats);
@@ -940,13 +958,33 @@ void aptgpu_plan::enqueue_image_color(int i, const float *d_rows, uint64_t rows_
         apt::hip_check(hipEventRecord(ev, t.stream), "hipEventRecord");
         sl.palette_gen = palette.gen;
     }
-    enqueue_limits(t, d_rows, contrast, percent);
+    if (lab) {
+        if (!sl.lab_ws.ptr) sl.lab_ws.alloc(lab_ws_bytes());
+        if (sl.lab_gen != palette.lab_gen) {
+            apt::hip_check(hipMemcpyAsync(sl.lab_ws.ptr, palette.lab_pinned, sizeof(apt::lab::Tables),
+                                          hipMemcpyHostToDevice, t.stream),
+                           "hipMemcpyAsync H2D (Lab tables)");
+            hipEvent_t &ev = palette.lab_uploaded[static_cast<size_t>(last_stream)];
+            if (!ev) apt::hip_check(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
+            apt::hip_check(hipEventRecord(ev, t.stream), "hipEventRecord");
+            sl.lab_gen = palette.lab_gen;
+        }
+        // Histogram with colour takes the 98 % limits; the zero-length error of get_min / get_max is the same
+        // record (reason 1) as percent's (noaa_apt.rs:158-175)
+        enqueue_limits(t, d_rows, APTGPU_CONTRAST_PERCENT, 0.98f);
+    } else {
+        enqueue_limits(t, d_rows, contrast, percent);
+    }
     const bool equalize = contrast == APTGPU_CONTRAST_HISTOGRAM;
-    if (equalize)
+    if (lab)
+        timed(t.stream, "image_equalize_lab", [&] {
+            image_equalize_lab(t.stream, d_rows, t.res, 0, t.cap, t.ws, sl.color_ws.ptr, sl.lab_ws.ptr, *tune);
+        });
+    else if (equalize)
         timed(t.stream, "image_equalize", [&] { image_equalize(t.stream, d_rows, t.res, 0, t.cap, t.ws, sl.color_ws.ptr); });
     timed(t.stream, "image_color", [&] {
         image_color(t.stream, d_rows, t.res, 0, t.cap, t.ws, sl.color_ws.ptr, equalize, tune, channels, rotate, d_image,
-                    t.out);
+                    t.out, lab ? sl.lab_ws.ptr : nullptr);
     });
     apt::hip_check(hipGetLastError(), "kernel launch (image stage)");
 }

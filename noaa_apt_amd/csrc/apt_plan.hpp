@@ -177,6 +177,8 @@ struct aptgpu_plan {
         apt::DeviceBuffer<char> image_ws;  // scratch of the image stage, allocated on first use
         apt::DeviceBuffer<char> color_ws;  // histograms, tables and palette of the colour stage, on first use
         uint64_t palette_gen = 0;          // generation of the palette color_ws holds (0 = none)
+        apt::DeviceBuffer<char> lab_ws;    // Lab tables + per-call RGBA table, on first use of the Lab path
+        uint64_t lab_gen = 0;              // generation of the palette whose Lab tables lab_ws holds (0 = none)
         apt::DeviceBuffer<float> ingest;   // WAV -> f32 staging when the fused PCM16 path does not apply
     };
     std::vector<Slot> slots;
@@ -208,17 +210,24 @@ struct aptgpu_plan {
         timer.end(s);
     }
     // The same with every contrast (APTGPU_CONTRAST_HISTOGRAM too), optional false colour and 1 or 4 bytes per
-    // pixel (aptgpu_plan_process_device_image).  set_palette first when tune is non-null.
+    // pixel (aptgpu_plan_process_device_image).  set_palette first when tune is non-null (with lab: Histogram
+    // with false colour, equalised in CIE Lab).
     void enqueue_image_color(int i, const float *d_rows, uint64_t rows_cap_floats, int contrast, float percent,
-                             bool rotate, const apt::gpu::ColorTune *tune, int channels, uint8_t *d_image);
+                             bool rotate, const apt::gpu::ColorTune *tune, int channels, uint8_t *d_image,
+                             bool lab = false);
     // The false-colour palette (256*256*3 RGB).  The plan keeps a host copy; bytes that differ from it start a new
-    // generation, which every slot uploads on its own stream the next time it colours an image.
-    void set_palette(const uint8_t *rgb);
+    // generation, which every slot uploads on its own stream the next time it colours an image.  lab: also the
+    // palette's Lab tables (apt_lab.hpp), computed once per generation and uploaded per slot likewise.
+    void set_palette(const uint8_t *rgb, bool lab = false);
+    void new_palette(const uint8_t *rgb);  // (set_palette: the bytes differ)
     struct Palette {
         std::vector<uint8_t> rgb;   // the host copy the next call compares against
         uint32_t *pinned = nullptr; // packed RGBA of the current generation, the source of the slots' uploads
         std::vector<hipEvent_t> uploaded;  // per stream: behind its latest upload from `pinned` (null: none yet)
         uint64_t gen = 0;
+        apt::lab::Tables *lab_pinned = nullptr;  // Lab tables of generation lab_gen
+        std::vector<hipEvent_t> lab_uploaded;    // per stream: behind its latest upload from `lab_pinned`
+        uint64_t lab_gen = 0;
         Palette() = default;
         Palette(const Palette &) = delete;
         Palette &operator=(const Palette &) = delete;
