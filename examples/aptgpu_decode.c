@@ -2,7 +2,7 @@
  * aptgpu_decode.c — minimal C caller of the drop-in boundary (include/aptgpu.h):
  *
  *     aptgpu_decode in.wav out.pgm [contrast: telemetry|percent|minmax] [--no-sync]
- *                   [--histogram] [--palette FILE] [--lab]
+ *                   [--histogram] [--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE]
  *
  * What `noaa-apt in.wav -o out.png` does (main.rs:91-110, noaa_apt.rs:114-235) minus PNG
  * encoding and the map overlay: load -> decode -> contrast limits -> 8-bit image, written as a
@@ -11,7 +11,10 @@
  * (196 608 bytes, pixel (a, b) at (b*256 + a)*3), written as a binary PPM (the RGBA image without
  * its alpha).  --lab: with --histogram and --palette, equalise the false-colour image as the
  * reference does, channel A in CIE Lab (APTGPU_COLOR_EQUALIZE_LAB); without it that combination
- * is refused.  Plain C99, links only libaptgpu.so.
+ * is refused.  --map DIR --track FILE: the map overlay (`--map`) of DIR/states.shp, countries.shp and
+ * lakes.shp with the default settings and colours; FILE holds the satellite's raw f64 (lat, lon)
+ * pairs in radians, one per image row (SGP4 is the caller's job); written as a PPM.  Plain C99,
+ * links only libaptgpu.so.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -29,11 +32,11 @@ int main(int argc, char **argv)
 {
     if (argc < 3) {
         fprintf(stderr, "usage: %s in.wav out.pgm [telemetry|percent|minmax] [--no-sync] [--histogram] "
-                "[--palette FILE] [--lab]\n", argv[0]);
+                "[--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE]\n", argv[0]);
         return 2;
     }
     int contrast = APTGPU_CONTRAST_PERCENT, sync = 1, lab = 0;
-    const char *palette_path = NULL;
+    const char *palette_path = NULL, *map_dir = NULL, *track_path = NULL;
     for (int i = 3; i < argc; ++i) {
         if (!strcmp(argv[i], "telemetry")) contrast = APTGPU_CONTRAST_TELEMETRY;
         else if (!strcmp(argv[i], "percent")) contrast = APTGPU_CONTRAST_PERCENT;
@@ -42,6 +45,8 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--no-sync")) sync = 0;
         else if (!strcmp(argv[i], "--lab")) lab = 1;
         else if (!strcmp(argv[i], "--palette") && i + 1 < argc) palette_path = argv[++i];
+        else if (!strcmp(argv[i], "--map") && i + 1 < argc) map_dir = argv[++i];
+        else if (!strcmp(argv[i], "--track") && i + 1 < argc) track_path = argv[++i];
     }
 
     /* the palette, decoded by the caller (the reference: image::open(..).into_rgb8(), processing.rs:115) */
@@ -100,7 +105,28 @@ int main(int argc, char **argv)
     uint8_t *image = NULL;
     size_t n_px = 0;
     aptgpu_image_result info;
-    if (palette_path || contrast == APTGPU_CONTRAST_HISTOGRAM)
+    const int rgba = palette_path || map_dir;
+    if (map_dir) {
+        /* the track: one (lat, lon) per image row, as map.rs:41-58 computes it with SGP4 */
+        const size_t height = n_rows_px / 2080;
+        double *track = malloc((height ? height : 1) * 2 * sizeof(double));
+        FILE *t = track_path ? fopen(track_path, "rb") : NULL;
+        if (!track || !t || fread(track, sizeof(double), 2 * height, t) != 2 * height || fgetc(t) != EOF) {
+            fprintf(stderr, "--map needs --track FILE with exactly %zu (lat, lon) f64 pairs\n", height);
+            return 1;
+        }
+        fclose(t);
+        aptgpu_map_layers *layers = NULL;
+        aptgpu_map_settings ms = {sizeof(aptgpu_map_settings), 0, 0.0, 1.0, 1.0};  /* config.rs:646-648 */
+        rc = aptgpu_map_layers_create(&layers);
+        if (rc == APTGPU_OK) rc = aptgpu_map_layers_load_dir(layers, map_dir, err, sizeof err);
+        if (rc == APTGPU_OK)
+            rc = aptgpu_process_image_map(&ctx, rows, n_rows_px, contrast, 0.98f, APTGPU_ROTATE_NO,
+                                          palette_path ? &color : NULL, 4, &ms, layers, track, &image, &n_px, &info,
+                                          err, sizeof err);
+        aptgpu_map_layers_destroy(layers);
+        free(track);
+    } else if (palette_path || contrast == APTGPU_CONTRAST_HISTOGRAM)
         rc = aptgpu_process_image(&ctx, rows, n_rows_px, contrast, 0.98f, APTGPU_ROTATE_NO,
                                   palette_path ? &color : NULL, palette_path ? 4 : 1, &image, &n_px, &info, err,
                                   sizeof err);
@@ -112,7 +138,7 @@ int main(int argc, char **argv)
 
     FILE *o = fopen(argv[2], "wb");
     if (!o) { perror(argv[2]); return 1; }
-    if (palette_path) {
+    if (rgba) {
         fprintf(o, "P6\n2080 %u\n255\n", info.height);
         for (size_t i = 0; i < (size_t)info.height * 2080u; ++i) fwrite(image + 4 * i, 1, 3, o);  /* drop alpha */
     } else {

@@ -375,11 +375,11 @@ int aptgpu_find_sync(const aptgpu_context *ctx, const float *signal, size_t n,
 /* ====================================================================== */
 /* 4. consumers of the pixel rows                 */
 /* ====================================================================== */
-/* noaa_apt::process() (src/noaa_apt.rs:132-235) without the map overlay: contrast limits  */
+/* noaa_apt::process() (src/noaa_apt.rs:132-235): contrast limits                           */
 /* -> map_signal_u8, plus telemetry.rs, histogram equalisation (imageext.rs:21-45), palette */
 /* false colour (processing.rs:113-165) and the 180-degree channel rotation.  Equalisation */
 /* of a false-colour image (CIE Lab, imageext.rs:51-64) is opt-in                        */
-/* (APTGPU_COLOR_EQUALIZE_LAB); the map overlay and Rotate::Orbit stay out of scope.       */
+/* (APTGPU_COLOR_EQUALIZE_LAB); the map overlay from a caller-computed track (below).       */
 /* aptgpu_process_gray / aptgpu_plan_process_device: the grayscale image of the first     */
 /* three contrasts; aptgpu_process_image / aptgpu_plan_process_device_image: every        */
 /* contrast, optional false colour, gray or RGBA output.                                   */
@@ -475,6 +475,72 @@ int aptgpu_plan_process_device_image(aptgpu_plan *plan, int count, const float *
                                      uint8_t *const *d_images, char *err, size_t err_cap);
 /* Waits for the image stage of the last call and copies the records. */
 int aptgpu_plan_image_results(aptgpu_plan *plan, int count, aptgpu_image_result *results);
+
+/* ---- the map overlay (map.rs:14-200) ----
+ * SGP4 stays with the caller: it passes the satellite's (lat, lon) for every image row, in radians, as map.rs:41-58
+ * computes them.  The overlay draws over the RGBA image before the rotation, as the reference does.  Errors found on
+ * the device land in aptgpu_image_result (status APTGPU_ERR_INTERNAL) with these reasons; the image is then left
+ * without the overlay: */
+#define APTGPU_MAP_REASON_OVERFLOW 5  /* more than APTGPU_MAP_MAX_FRAGMENTS fragments in one image */
+#define APTGPU_MAP_REASON_WALK 6      /* a segment's walk is longer than APTGPU_MAP_MAX_WALK steps or has a
+                                         non-finite end (the reference loops for ages or panics there) */
+#define APTGPU_MAP_REASON_COUNT 7     /* the position count differs from the image height */
+#define APTGPU_MAP_REASON_PIXEL 8     /* more than APTGPU_MAP_MAX_PIXEL_FRAGMENTS fragments on one pixel (tiny
+                                         hscale / vscale squeeze the whole map into a few pixels) */
+#define APTGPU_MAP_MAX_FRAGMENTS (1u << 21)
+#define APTGPU_MAP_MAX_PIXEL_FRAGMENTS (1u << 16)
+#define APTGPU_MAP_MAX_WALK (1u << 20)
+
+/* noaa_apt::MapSettings minus the colours (src/noaa_apt.rs:84-91); the CLI's defaults are yaw 0, hscale 1, vscale 1
+ * (config.rs:646-648). */
+typedef struct aptgpu_map_settings {
+    uint32_t struct_size; /* sizeof(aptgpu_map_settings) */
+    uint32_t reserved;    /* 0 */
+    double yaw, hscale, vscale;
+} aptgpu_map_settings;
+
+/* The shapefile layers in the reference's draw order, with their RGBA colours.  Parsed once; uploaded once per
+ * device workspace and again only after the layer set changes. */
+typedef struct aptgpu_map_layers aptgpu_map_layers;
+#define APTGPU_MAP_STATES 0    /* states.shp, read as Polyline; default colour (255, 255, 0, 150)  */
+#define APTGPU_MAP_COUNTRIES 1 /* countries.shp, Polygon; (255, 255, 0, 255)                       */
+#define APTGPU_MAP_LAKES 2     /* lakes.shp, Polygon; (50, 200, 200, 255)  (default_settings.toml:72-74) */
+/* An empty layer set with the default colours. */
+int aptgpu_map_layers_create(aptgpu_map_layers **out);
+void aptgpu_map_layers_destroy(aptgpu_map_layers *layers);
+/* Reads <dir>/states.shp, countries.shp and lakes.shp (all three must exist: "Could not load {:?}",
+ * APTGPU_ERR_INTERNAL, as map.rs:136-137).  Shapefile errors: a record of another type than its layer's is
+ * APTGPU_ERR_INTERNAL, a layer type other than Polyline / Polygon APTGPU_ERR_UNSUPPORTED, an empty part
+ * APTGPU_ERR_INVALID.  On error the set is unchanged. */
+int aptgpu_map_layers_load_dir(aptgpu_map_layers *layers, const char *dir, char *err, size_t err_cap);
+/* Sets one layer from arrays: xy holds n_points (x = lon°, y = lat°) pairs, part k is points
+ * [part_offsets[k], part_offsets[k + 1]) with part_offsets[0] = 0 and part_offsets[n_parts] = n_points, no part
+ * empty.  n_parts = 0 removes the layer (it is then not drawn). */
+int aptgpu_map_layers_set(aptgpu_map_layers *layers, int layer, const double *xy, size_t n_points,
+                          const uint32_t *part_offsets, size_t n_parts, char *err, size_t err_cap);
+int aptgpu_map_layers_set_color(aptgpu_map_layers *layers, int layer, const uint8_t rgba[4]);
+/* The reader alone (CPU): the parts of one .shp file read as shape_type 3 (Polyline) or 5 (Polygon).  *xy and
+ * *part_offsets malloc'd (free with aptgpu_free), *n_parts + 1 offsets. */
+int aptgpu_map_read_shapefile(const char *path, int shape_type, double **xy, size_t *n_points,
+                              uint32_t **part_offsets, size_t *n_parts, char *err, size_t err_cap);
+
+/* aptgpu_process_image followed by the map overlay.  channels must be 4 (APTGPU_ERR_INVALID otherwise);
+ * Rotate::Orbit stays APTGPU_ERR_UNSUPPORTED.  sat_positions: height = n / 2080 pairs (lat, lon) in
+ * radians.  Status callback 0.5 "Drawing map" (noaa_apt.rs:205). */
+int aptgpu_process_image_map(const aptgpu_context *ctx, const float *signal, size_t n, int contrast,
+                             float percent, int rotate, const aptgpu_color_settings *color, int channels,
+                             const aptgpu_map_settings *map, const aptgpu_map_layers *layers,
+                             const double *sat_positions, uint8_t **image_out, size_t *n_out,
+                             aptgpu_image_result *info, char *err, size_t err_cap);
+/* aptgpu_plan_process_device_image followed by the map overlay, on each recording's stream without a host round
+ * trip.  sat_positions[i] holds n_positions[i] pairs; the height is known only on the device, so a count that
+ * differs from it is reported through aptgpu_plan_image_results (APTGPU_MAP_REASON_COUNT). */
+int aptgpu_plan_process_device_image_map(aptgpu_plan *plan, int count, const float *const *d_rows,
+                                         const size_t *rows_cap, int contrast, float percent, int rotate,
+                                         const aptgpu_color_settings *color, int channels,
+                                         const aptgpu_map_settings *map, const aptgpu_map_layers *layers,
+                                         const double *const *sat_positions, const size_t *n_positions,
+                                         uint8_t *const *d_images, char *err, size_t err_cap);
 
 /* ====================================================================== */
 /* 5. WAV ingest in front of decode()                 */

@@ -16,9 +16,11 @@ Names, argument meaning and error behaviour follow the reference:
     resample_wav (WAV->WAV tool), write_wav                /root/reference/src/resample.rs:17-71, wav.rs:59-98
     process (grayscale part), Contrast, Rotate             /root/reference/src/noaa_apt.rs:25-60,132-235
     process: Contrast.HISTOGRAM, ColorSettings (false      the reference's processing.rs:83-165, imageext.rs:21-45,
-    colour); no map overlay                                noaa_apt.rs:63-71
+    colour)                                                noaa_apt.rs:63-71
     ColorSettings(equalize_lab=True), lab_from_rgb,        imageext.rs:50-143, the lab crate 0.11.0
     lab_to_rgb (Histogram + colour in CIE Lab)
+    process(orbit=MapOverlay(...)): the map overlay,       map.rs:14-200 (SGP4 stays with the caller: it passes
+    MapSettings, MapLayers, read_shapefile                 the per-row track), noaa_apt.rs:84-91
     percent, get_min, get_max, map_signal_u8               /root/reference/src/misc.rs:119, dsp.rs:20-54
     read_telemetry, Telemetry                              /root/reference/src/telemetry.rs:19-243
 
@@ -32,7 +34,8 @@ from .api import (  # noqa: F401
     Rate, Freq, Settings, Context, Stats,
     NoFilter, Lowpass, LowpassDcRemoval,
     decode, resample_with_filter, resample, demodulate, filter, find_sync, generate_sync_frame,
-    Contrast, Rotate, ColorSettings, Telemetry, ImageResult,
+    Contrast, Rotate, ColorSettings, Telemetry, ImageResult, MapSettings, MapLayers, MapOverlay, read_shapefile,
+    MAP_STATES, MAP_COUNTRIES, MAP_LAKES,
     get_min, get_max, percent, map_signal_u8, read_telemetry, process, lab_from_rgb, lab_to_rgb,
     Plan, PlanInfo, Result, KernelTime, decode_batch, BatchStats, host_alloc_f32, host_free,
     lib, lib_path, use_library, build, device_count, version, abi_version, cache_clear, cache_info, host_affinity, host_affinity_from_sysfs,

@@ -25,6 +25,8 @@ _f32p = C.POINTER(C.c_float)
 _u64p = C.POINTER(C.c_uint64)
 _i8p = C.POINTER(C.c_int8)
 _u8p = C.POINTER(C.c_uint8)
+_f64p = C.POINTER(C.c_double)
+_u32p = C.POINTER(C.c_uint32)
 _ERRCAP = 1024
 
 
@@ -129,6 +131,11 @@ class _CColorSettings(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("palette_rgb", _u8p),
                 ("ch_a_tune_start", C.c_float), ("ch_a_tune_end", C.c_float),
                 ("ch_b_tune_start", C.c_float), ("ch_b_tune_end", C.c_float)]
+
+
+class _CMapSettings(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("yaw", C.c_double),
+                ("hscale", C.c_double), ("vscale", C.c_double)]
 
 
 class WavSpec(C.Structure):
@@ -291,6 +298,20 @@ def lib():
                                        C.POINTER(ImageResult), C.c_char_p, sz]
     L.aptgpu_plan_process_device_image.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz), i32, f, i32, ccs, i32,
                                                    C.POINTER(vp), C.c_char_p, sz]
+    cms = C.POINTER(_CMapSettings)
+    L.aptgpu_map_layers_create.argtypes = [C.POINTER(vp)]
+    L.aptgpu_map_layers_destroy.argtypes = [vp]
+    L.aptgpu_map_layers_destroy.restype = None
+    L.aptgpu_map_layers_load_dir.argtypes = [vp, C.c_char_p, C.c_char_p, sz]
+    L.aptgpu_map_layers_set.argtypes = [vp, i32, _f64p, sz, _u32p, sz, C.c_char_p, sz]
+    L.aptgpu_map_layers_set_color.argtypes = [vp, i32, _u8p]
+    L.aptgpu_map_read_shapefile.argtypes = [C.c_char_p, i32, C.POINTER(_f64p), C.POINTER(sz), C.POINTER(_u32p),
+                                            C.POINTER(sz), C.c_char_p, sz]
+    L.aptgpu_process_image_map.argtypes = [cp, _f32p, sz, i32, f, i32, ccs, i32, cms, vp, _f64p, C.POINTER(_u8p),
+                                           C.POINTER(sz), C.POINTER(ImageResult), C.c_char_p, sz]
+    L.aptgpu_plan_process_device_image_map.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz), i32, f, i32, ccs, i32,
+                                                       cms, vp, C.POINTER(_f64p), C.POINTER(sz), C.POINTER(vp),
+                                                       C.c_char_p, sz]
     _lib = L
     return L
 
@@ -769,6 +790,97 @@ class ColorSettings:
                                self.ch_a_tune_start, self.ch_a_tune_end, self.ch_b_tune_start, self.ch_b_tune_end)
 
 
+MAP_STATES, MAP_COUNTRIES, MAP_LAKES = 0, 1, 2  # aptgpu_map_layers layer indices (the reference's draw order)
+
+
+def read_shapefile(path, shape_type):
+    """The layer set's ESRI shapefile reader alone (aptgpu_map_read_shapefile, CPU): the parts of `path` read as
+    shape_type 3 (Polyline) or 5 (Polygon), as a list of (n, 2) float64 arrays of (lon°, lat°)."""
+    xy, n, parts, k = _f64p(), C.c_size_t(), _u32p(), C.c_size_t()
+    err = C.create_string_buffer(_ERRCAP)
+    _check(lib().aptgpu_map_read_shapefile(os.fsencode(os.fspath(path)), int(shape_type), C.byref(xy), C.byref(n),
+                                           C.byref(parts), C.byref(k), err, _ERRCAP), err)
+    pts = _take(xy, 2 * n.value, np.float64).reshape(-1, 2)
+    off = _take(parts, k.value + 1, np.uint32)
+    return [pts[off[i]:off[i + 1]].copy() for i in range(k.value)]
+
+
+class MapLayers:
+    """The shapefile layers of the map overlay (aptgpu_map_layers): states (drawn as polylines), countries and lakes
+    (polygons), in the reference's draw order (map.rs:133-198).  Each argument is None (layer left out) or a list of
+    parts, each an (n, 2) array of (lon°, lat°).  Parsed and flattened once; a plan uploads it once per slot."""
+
+    def __init__(self, states=None, countries=None, lakes=None):
+        self._p = C.c_void_p()
+        _check(lib().aptgpu_map_layers_create(C.byref(self._p)))
+        for k, parts in ((MAP_STATES, states), (MAP_COUNTRIES, countries), (MAP_LAKES, lakes)):
+            if parts is not None:
+                self._set(k, parts)
+
+    @staticmethod
+    def load(directory):
+        """map.rs's res/shapefiles: <directory>/states.shp, countries.shp and lakes.shp."""
+        m = MapLayers()
+        err = C.create_string_buffer(_ERRCAP)
+        _check(lib().aptgpu_map_layers_load_dir(m._p, os.fsencode(os.fspath(directory)), err, _ERRCAP), err)
+        return m
+
+    def _set(self, k, parts):
+        arrs = [np.ascontiguousarray(np.asarray(p, dtype=np.float64).reshape(-1, 2)) for p in parts]
+        xy = np.ascontiguousarray(np.concatenate(arrs) if arrs else np.zeros((0, 2)), dtype=np.float64)
+        off = np.zeros(len(arrs) + 1, np.uint32)
+        off[1:] = np.cumsum([len(a) for a in arrs]) if arrs else []
+        err = C.create_string_buffer(_ERRCAP)
+        _check(lib().aptgpu_map_layers_set(self._p, k, xy.ctypes.data_as(_f64p), len(xy), off.ctypes.data_as(_u32p),
+                                           len(arrs), err, _ERRCAP), err)
+
+    def _colors(self, settings):
+        for k, c in ((MAP_STATES, settings.states_color), (MAP_COUNTRIES, settings.countries_color),
+                     (MAP_LAKES, settings.lakes_color)):
+            rgba = (C.c_uint8 * 4)(*[int(v) for v in c])
+            _check(lib().aptgpu_map_layers_set_color(self._p, k, rgba))
+
+    def close(self):
+        if self._p:
+            lib().aptgpu_map_layers_destroy(self._p)
+            self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class MapSettings:
+    """noaa_apt::MapSettings (noaa_apt.rs:84-91) with the CLI's defaults (config.rs:646-648) and the colours of
+    default_settings.toml:72-74."""
+
+    def __init__(self, yaw=0.0, hscale=1.0, vscale=1.0, countries_color=(255, 255, 0, 255),
+                 states_color=(255, 255, 0, 150), lakes_color=(50, 200, 200, 255)):
+        self.yaw, self.hscale, self.vscale = float(yaw), float(hscale), float(vscale)
+        self.countries_color, self.states_color, self.lakes_color = (tuple(countries_color), tuple(states_color),
+                                                                     tuple(lakes_color))
+        for c in (self.countries_color, self.states_color, self.lakes_color):
+            if len(c) != 4 or not all(0 <= int(v) <= 255 for v in c):
+                raise InvalidError("map colours are (r, g, b, a) tuples of u8")
+
+    def _c(self):
+        return _CMapSettings(C.sizeof(_CMapSettings), 0, self.yaw, self.hscale, self.vscale)
+
+
+class MapOverlay:
+    """What process() needs to draw the map (the `orbit` argument): the satellite's (lat, lon) in radians for every
+    image row, as map.rs:41-58 computes them with SGP4 (the caller's job), the settings and the layers."""
+
+    def __init__(self, sat_positions, settings=None, layers=None):
+        self.sat_positions = np.ascontiguousarray(np.asarray(sat_positions, dtype=np.float64).reshape(-1, 2))
+        self.settings = settings if settings is not None else MapSettings()
+        if not isinstance(layers, MapLayers):
+            raise InvalidError("MapOverlay needs a MapLayers")
+        self.layers = layers
+
+
 class Telemetry:
     """telemetry::Telemetry (telemetry.rs:19-121): wedge values of both bands."""
 
@@ -844,13 +956,16 @@ def read_telemetry(context, signal):  # telemetry.rs:125
 
 def process(context, signal, contrast_adjustment, rotate=Rotate.NO, color=None, orbit=None,
             return_info=False):
-    """noaa_apt::process (noaa_apt.rs:132-235) without the map overlay.  Returns the height x 2080 u8
+    """noaa_apt::process (noaa_apt.rs:132-235).  Returns the height x 2080 u8
     gray image, or with `color` (a ColorSettings) the height x 2080 x 4 RGBA image of the reference's
     false colour (A = 255).  Contrast.HISTOGRAM equalises each channel half of the gray image; together with
     false colour it needs ColorSettings(equalize_lab=True) (the reference equalises channel A in CIE Lab then).
-    Unsupported: the map overlay (`orbit`), Rotate.ORBIT, and HISTOGRAM with colour without equalize_lab."""
+    `orbit` may be a MapOverlay: the map is drawn over the RGBA image (height x 2080 x 4, also without colour).
+    Unsupported: any other `orbit`, Rotate.ORBIT, and HISTOGRAM with colour without equalize_lab."""
+    if isinstance(orbit, MapOverlay):
+        return _process_image(context, signal, contrast_adjustment, rotate, color, return_info, orbit)
     if orbit is not None:
-        raise UnsupportedError("the map overlay is not part of the GPU path")
+        raise UnsupportedError("orbit: only a MapOverlay (the map overlay) is served on the GPU path")
     if color is not None and not isinstance(color, ColorSettings):
         raise UnsupportedError("color must be a ColorSettings")
     if color is not None or contrast_adjustment == Contrast.HISTOGRAM:
@@ -866,17 +981,31 @@ def process(context, signal, contrast_adjustment, rotate=Rotate.NO, color=None, 
     return (out, info) if return_info else out
 
 
-def _process_image(context, signal, contrast_adjustment, rotate, color, return_info):
+def _process_image(context, signal, contrast_adjustment, rotate, color, return_info, overlay=None, channels=None):
+    if color is not None and not isinstance(color, ColorSettings):
+        raise UnsupportedError("color must be a ColorSettings")
     cctx = (context or Context())._c()
     x, xp = _as_f32(signal)
     kind, p = Contrast._c(contrast_adjustment)
-    channels = 4 if color is not None else 1
+    if channels is None:
+        channels = 4 if color is not None or overlay is not None else 1
     ccol = color._c() if color is not None else None
     img, n, info = _u8p(), C.c_size_t(), ImageResult()
     err = C.create_string_buffer(_ERRCAP)
-    _check(lib().aptgpu_process_image(C.byref(cctx), xp, x.size, kind, p, int(rotate),
-                                      C.byref(ccol) if ccol is not None else None, channels, C.byref(img),
-                                      C.byref(n), C.byref(info), err, _ERRCAP), err)
+    if overlay is not None:
+        if len(overlay.sat_positions) != x.size // PX_PER_ROW:
+            raise InvalidError(f"MapOverlay: {len(overlay.sat_positions)} positions for {x.size // PX_PER_ROW} rows")
+        overlay.layers._colors(overlay.settings)
+        cms = overlay.settings._c()
+        _check(lib().aptgpu_process_image_map(C.byref(cctx), xp, x.size, kind, p, int(rotate),
+                                              C.byref(ccol) if ccol is not None else None, int(channels),
+                                              C.byref(cms), overlay.layers._p,
+                                              overlay.sat_positions.ctypes.data_as(_f64p), C.byref(img), C.byref(n),
+                                              C.byref(info), err, _ERRCAP), err)
+    else:
+        _check(lib().aptgpu_process_image(C.byref(cctx), xp, x.size, kind, p, int(rotate),
+                                          C.byref(ccol) if ccol is not None else None, channels, C.byref(img),
+                                          C.byref(n), C.byref(info), err, _ERRCAP), err)
     out = _take(img, n.value, np.uint8)
     out = out.reshape(-1, PX_PER_ROW, 4) if channels == 4 else out.reshape(-1, PX_PER_ROW)
     return (out, info) if return_info else out
@@ -1024,18 +1153,35 @@ class Plan:
                                                 (C.c_void_p * k)(*d_images), err, _ERRCAP), err)
 
     def process_device_image(self, d_rows: Sequence[int], rows_cap: Sequence[int], contrast_adjustment,
-                             d_images: Sequence[int], rotate=Rotate.NO, color=None, channels=None):
+                             d_images: Sequence[int], rotate=Rotate.NO, color=None, channels=None, map=None):  # noqa: A002
         """process() with every contrast (HISTOGRAM too) and optional false colour (a ColorSettings) for the
         recordings of the last decode_device call, chained on the device behind their decode.  d_images[i]
-        holds rows_cap[i] * 2080 * channels bytes; channels defaults to 4 (RGBA) with colour, 1 (gray) without."""
+        holds rows_cap[i] * 2080 * channels bytes; channels defaults to 4 (RGBA) with colour or map, 1 (gray)
+        without.  map: a MapOverlay, or one per recording (all with the same settings and layers); a position count
+        that differs from a recording's height is reported in image_results() (reason 7)."""
         if color is not None and not isinstance(color, ColorSettings):
             raise UnsupportedError("color must be a ColorSettings")
         if channels is None:
-            channels = 4 if color is not None else 1
+            channels = 4 if color is not None or map is not None else 1
         k = len(d_rows)
         kind, p = Contrast._c(contrast_adjustment)
         ccol = color._c() if color is not None else None
         err = C.create_string_buffer(_ERRCAP)
+        if map is not None:
+            maps = [map] * k if isinstance(map, MapOverlay) else list(map)
+            if len(maps) != k or not all(isinstance(m, MapOverlay) for m in maps):
+                raise InvalidError("map: a MapOverlay or one per recording")
+            if any(m.layers is not maps[0].layers or vars(m.settings) != vars(maps[0].settings) for m in maps):
+                raise InvalidError("map: every recording's MapOverlay must share settings and layers")
+            maps[0].layers._colors(maps[0].settings)
+            cms = maps[0].settings._c()
+            pos = (_f64p * k)(*[m.sat_positions.ctypes.data_as(_f64p) for m in maps])
+            npos = (C.c_size_t * k)(*[len(m.sat_positions) for m in maps])
+            _check(lib().aptgpu_plan_process_device_image_map(
+                self._p, k, (C.c_void_p * k)(*d_rows), (C.c_size_t * k)(*rows_cap), kind, p, int(rotate),
+                C.byref(ccol) if ccol is not None else None, int(channels), C.byref(cms), maps[0].layers._p, pos, npos,
+                (C.c_void_p * k)(*d_images), err, _ERRCAP), err)
+            return
         _check(lib().aptgpu_plan_process_device_image(self._p, k, (C.c_void_p * k)(*d_rows),
                                                       (C.c_size_t * k)(*rows_cap), kind, p, int(rotate),
                                                       C.byref(ccol) if ccol is not None else None, int(channels),

@@ -7,6 +7,12 @@
 
 #include "apt_capi_util.hpp"
 #include "apt_kernels_color.hpp"
+#include "apt_map.hpp"
+
+// the opaque handle of include/aptgpu.h
+struct aptgpu_map_layers {
+    apt::map::Layers layers;
+};
 
 namespace {
 
@@ -20,6 +26,10 @@ const char *kZeroMax = "Can't get maximum of a zero length vector";
 const char *kTelemetryShort = "Recording too short for telemetry decoding";
 const char *kBadPercent = "Percent given should be between 0 and 1";
 const char *kNoLowBucket = "percent: no bucket reaches the low threshold (the reference panics here)";
+const char *kMapOverflow = "map overlay: more than APTGPU_MAP_MAX_FRAGMENTS (2^21) fragments in one image";
+const char *kMapWalk = "map overlay: a segment's walk is longer than APTGPU_MAP_MAX_WALK (2^20) steps or has a non-finite end";
+const char *kMapPixel = "map overlay: more than APTGPU_MAP_MAX_PIXEL_FRAGMENTS (2^16) fragments on one pixel";
+const char *kMapCount = "map overlay: the number of satellite positions differs from the image height";
 const char *kChannelNames[9] = {"1", "2", "3a", "4", "5", "3b", "Unknown", "Unknown", "Unknown"};
 
 // Rust's `{}` for an f32: shortest decimal that round-trips, never in exponent form.
@@ -64,6 +74,10 @@ void throw_for(const ImageResult &r, int contrast)
     case 1: throw Error{ErrorKind::Internal, kZeroMin};
     case 2: throw Error{ErrorKind::Internal, kTelemetryShort};
     case 3: throw Error{ErrorKind::Internal, kNoLowBucket};
+    case apt::map::kReasonOverflow: throw Error{ErrorKind::Internal, kMapOverflow};
+    case apt::map::kReasonWalk: throw Error{ErrorKind::Internal, kMapWalk};
+    case apt::map::kReasonCount: throw Error{ErrorKind::Internal, kMapCount};
+    case apt::map::kReasonPixel: throw Error{ErrorKind::Internal, kMapPixel};
     default: throw Error{ErrorKind::Internal, "image stage failed"};
     }
     (void)contrast;
@@ -216,6 +230,144 @@ int extreme(const aptgpu_context *ctx, const float *signal, size_t n, float *out
     });
 }
 
+// The map overlay of one call (aptgpu_process_image_map / aptgpu_plan_process_device_image_map).
+struct MapCall {
+    const aptgpu_map_settings *settings;
+    const apt::map::Layers *layers;
+};
+
+// The checks of the map entry points, after color_args (so Rotate::Orbit stays Unsupported first).
+void map_args(int channels, const aptgpu_map_settings *map, const aptgpu_map_layers *layers)
+{
+    if (!map || map->struct_size < sizeof(aptgpu_map_settings) || !layers)
+        throw Error{ErrorKind::Invalid, "aptgpu_map_settings: struct_size not set, or no layer set"};
+    if (channels != 4) throw Error{ErrorKind::Invalid, "the map overlay needs channels = 4 (RGBA)"};
+}
+
+int layer_index(int layer)
+{
+    if (layer < APTGPU_MAP_STATES || layer > APTGPU_MAP_LAKES) throw Error{ErrorKind::Invalid, "unknown map layer"};
+    return layer;
+}
+
+apt::map::Scalars map_scalars(const MapCall &m, const double *positions, size_t count)
+{
+    return apt::map::scalars(positions, count, m.settings->yaw, m.settings->hscale, m.settings->vscale);
+}
+
+apt::map::Colors map_colors(const apt::map::Layers &l)
+{
+    return apt::map::Colors{{l.color[0], l.color[1], l.color[2]}};
+}
+
+int process_image(const aptgpu_context *ctx, const float *signal, size_t n, int contrast, float percent, int rotate,
+                  const aptgpu_color_settings *color, int channels, const MapCall *map, const double *positions,
+                  uint8_t **image_out, size_t *n_out, aptgpu_image_result *info, char *err, size_t err_cap)
+{
+    if ((!signal && n) || !image_out || !n_out) return APTGPU_ERR_INVALID;
+    *image_out = nullptr;
+    *n_out = 0;
+    return guarded(err, err_cap, [&] {
+        apt::gpu::ColorTune tune{};
+        bool lab = false;
+        const bool colored = color_args(contrast, rotate, color, channels, &tune, &lab);
+        if (map && n / 2080 == 0 && n != 0)
+            throw Error{ErrorKind::Internal, "map overlay: the image has no row to draw on"};
+        std::vector<uint32_t> packed;  // (outlives the call's stream: ~ImageCall synchronises it)
+        std::shared_ptr<const apt::lab::Tables> lab_tables;  // (likewise)
+        apt::map::Device map_dev;  // (likewise)
+        ImageCall c(ctx, signal, n);
+        hipStream_t s = c.sc.stream;
+        process_limits(ctx, c, contrast, percent, info, lab);
+        status(ctx, 0.3f, "Generating image");  // noaa_apt.rs:180
+        const size_t bytes = n / 2080 * 2080 * static_cast<size_t>(channels);
+        apt::DeviceBuffer<char> cws;
+        cws.alloc(apt::gpu::color_ws_bytes());
+        apt::hip_check(apt::gpu::color_ws_init(s, cws.ptr), "hipMemsetAsync");
+        apt::DeviceBuffer<char> lws;
+        if (lab) {
+            lab_tables = apt::lab::tables_for(color->palette_rgb);
+            lws.alloc(apt::gpu::lab_ws_bytes());
+            apt::hip_check(hipMemcpyAsync(lws.ptr, lab_tables.get(), sizeof(apt::lab::Tables), hipMemcpyHostToDevice, s),
+                           "hipMemcpyAsync H2D (Lab tables)");
+        } else if (colored) {
+            packed.resize(65536);
+            apt::gpu::color_pack_palette(color->palette_rgb, packed.data());
+            apt::hip_check(hipMemcpyAsync(apt::gpu::color_ws_palette(cws.ptr), packed.data(),
+                                          packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s),
+                           "hipMemcpyAsync H2D (palette)");
+        }
+        apt::DeviceBuffer<uint8_t> d_img;
+        d_img.alloc(bytes + 16);
+        const bool equalize = contrast == APTGPU_CONTRAST_HISTOGRAM;
+        if (lab) apt::gpu::image_equalize_lab(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, cws.ptr, lws.ptr, tune);
+        else if (equalize) apt::gpu::image_equalize(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, cws.ptr);
+        if (map) status(ctx, 0.5f, "Drawing map");                                    // noaa_apt.rs:205
+        if (rotate == APTGPU_ROTATE_YES) status(ctx, 0.90f, "Rotating output image");  // noaa_apt.rs:229
+        apt::gpu::image_color(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, cws.ptr, equalize, colored ? &tune : nullptr,
+                              channels, rotate == APTGPU_ROTATE_YES, d_img.ptr, c.d_info.ptr, lab ? lws.ptr : nullptr);
+        if (map) {
+            const size_t height = n / 2080;
+            map_dev.prepare(s, *map->layers, height);
+            map_dev.upload_track(s, positions, height);
+            apt::map::image_map_overlay(s, map_dev, map_scalars(*map, positions, height), map_colors(*map->layers),
+                                        static_cast<uint32_t>(height), rotate == APTGPU_ROTATE_YES, d_img.ptr,
+                                        c.d_info.ptr);
+        }
+        apt::hip_check(hipGetLastError(), "kernel launch (image stage)");
+        const ImageResult r = c.info();
+        copy_out(info, r);
+        throw_for(r, contrast);
+        uint8_t *h = host_alloc<uint8_t>(bytes);
+        if (bytes && (hipMemcpyAsync(h, d_img.ptr, bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                      hipStreamSynchronize(s) != hipSuccess)) {
+            std::free(h);
+            throw Error{ErrorKind::Hip, "D2H copy failed"};
+        }
+        *image_out = h;
+        *n_out = bytes;
+        return APTGPU_OK;
+    });
+}
+
+int plan_process_image(aptgpu_plan *plan, int count, const float *const *d_rows, const size_t *rows_cap, int contrast,
+                       float percent, int rotate, const aptgpu_color_settings *color, int channels, const MapCall *map,
+                       const double *const *positions, const size_t *n_positions, uint8_t *const *d_images, char *err,
+                       size_t err_cap)
+{
+    if (!plan || count < 0 || !d_rows || !rows_cap || !d_images) return APTGPU_ERR_INVALID;
+    if (map && count > 0 && (!positions || !n_positions)) return APTGPU_ERR_INVALID;
+    return guarded(err, err_cap, [&] {
+        apt::gpu::ColorTune tune{};
+        bool lab = false;
+        const bool colored = color_args(contrast, rotate, color, channels, &tune, &lab);
+        if (static_cast<size_t>(count) > plan->last_slots.size())
+            throw Error{ErrorKind::Invalid, "count exceeds the recordings of the last decode call"};
+        if (contrast == APTGPU_CONTRAST_PERCENT && (percent < 0.f || percent > 1.f))
+            throw Error{ErrorKind::Internal, kBadPercent};
+        const uintptr_t align = channels == 4 ? 15u : 3u;
+        for (int i = 0; i < count; ++i) {
+            if (!d_rows[i] || !d_images[i]) throw Error{ErrorKind::Invalid, "null device pointer"};
+            if (map && !positions[i] && n_positions[i]) throw Error{ErrorKind::Invalid, "null sat_positions"};
+            if (reinterpret_cast<uintptr_t>(d_images[i]) & align)
+                throw Error{ErrorKind::Invalid, channels == 4 ? "d_images must be 16-byte aligned for channels = 4"
+                                                              : "d_images must be 4-byte aligned"};
+        }
+        apt::hip_check(hipSetDevice(plan->device), "hipSetDevice");
+        if (colored) plan->set_palette(color->palette_rgb, lab);
+        for (int i = 0; i < count; ++i)
+            plan->enqueue_image_color(i, d_rows[i], static_cast<uint64_t>(rows_cap[i]) * 2080u, contrast, percent,
+                                      rotate == APTGPU_ROTATE_YES, colored ? &tune : nullptr, channels, d_images[i],
+                                      lab);
+        if (map)
+            for (int i = 0; i < count; ++i)
+                plan->enqueue_image_map(i, static_cast<uint64_t>(rows_cap[i]) * 2080u, *map->layers,
+                                        map_scalars(*map, positions[i], n_positions[i]), map_colors(*map->layers),
+                                        positions[i], n_positions[i], rotate == APTGPU_ROTATE_YES, d_images[i]);
+        return APTGPU_OK;
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -354,58 +506,8 @@ int aptgpu_process_image(const aptgpu_context *ctx, const float *signal, size_t 
                          int rotate, const aptgpu_color_settings *color, int channels, uint8_t **image_out,
                          size_t *n_out, aptgpu_image_result *info, char *err, size_t err_cap)
 {
-    if ((!signal && n) || !image_out || !n_out) return APTGPU_ERR_INVALID;
-    *image_out = nullptr;
-    *n_out = 0;
-    return guarded(err, err_cap, [&] {
-        apt::gpu::ColorTune tune{};
-        bool lab = false;
-        const bool colored = color_args(contrast, rotate, color, channels, &tune, &lab);
-        std::vector<uint32_t> packed;  // (outlives the call's stream: ~ImageCall synchronises it)
-        std::shared_ptr<const apt::lab::Tables> lab_tables;  // (likewise)
-        ImageCall c(ctx, signal, n);
-        hipStream_t s = c.sc.stream;
-        process_limits(ctx, c, contrast, percent, info, lab);
-        status(ctx, 0.3f, "Generating image");  // noaa_apt.rs:180
-        const size_t bytes = n / 2080 * 2080 * static_cast<size_t>(channels);
-        apt::DeviceBuffer<char> cws;
-        cws.alloc(apt::gpu::color_ws_bytes());
-        apt::hip_check(apt::gpu::color_ws_init(s, cws.ptr), "hipMemsetAsync");
-        apt::DeviceBuffer<char> lws;
-        if (lab) {
-            lab_tables = apt::lab::tables_for(color->palette_rgb);
-            lws.alloc(apt::gpu::lab_ws_bytes());
-            apt::hip_check(hipMemcpyAsync(lws.ptr, lab_tables.get(), sizeof(apt::lab::Tables), hipMemcpyHostToDevice, s),
-                           "hipMemcpyAsync H2D (Lab tables)");
-        } else if (colored) {
-            packed.resize(65536);
-            apt::gpu::color_pack_palette(color->palette_rgb, packed.data());
-            apt::hip_check(hipMemcpyAsync(apt::gpu::color_ws_palette(cws.ptr), packed.data(),
-                                          packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s),
-                           "hipMemcpyAsync H2D (palette)");
-        }
-        apt::DeviceBuffer<uint8_t> d_img;
-        d_img.alloc(bytes + 16);
-        const bool equalize = contrast == APTGPU_CONTRAST_HISTOGRAM;
-        if (lab) apt::gpu::image_equalize_lab(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, cws.ptr, lws.ptr, tune);
-        else if (equalize) apt::gpu::image_equalize(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, cws.ptr);
-        if (rotate == APTGPU_ROTATE_YES) status(ctx, 0.90f, "Rotating output image");  // noaa_apt.rs:229
-        apt::gpu::image_color(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, cws.ptr, equalize, colored ? &tune : nullptr,
-                              channels, rotate == APTGPU_ROTATE_YES, d_img.ptr, c.d_info.ptr, lab ? lws.ptr : nullptr);
-        apt::hip_check(hipGetLastError(), "kernel launch (image stage)");
-        const ImageResult r = c.info();
-        copy_out(info, r);
-        throw_for(r, contrast);
-        uint8_t *h = host_alloc<uint8_t>(bytes);
-        if (bytes && (hipMemcpyAsync(h, d_img.ptr, bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
-                      hipStreamSynchronize(s) != hipSuccess)) {
-            std::free(h);
-            throw Error{ErrorKind::Hip, "D2H copy failed"};
-        }
-        *image_out = h;
-        *n_out = bytes;
-        return APTGPU_OK;
-    });
+    return process_image(ctx, signal, n, contrast, percent, rotate, color, channels, nullptr, nullptr, image_out, n_out,
+                         info, err, err_cap);
 }
 
 int aptgpu_plan_process_device_image(aptgpu_plan *plan, int count, const float *const *d_rows,
@@ -413,28 +515,135 @@ int aptgpu_plan_process_device_image(aptgpu_plan *plan, int count, const float *
                                      const aptgpu_color_settings *color, int channels,
                                      uint8_t *const *d_images, char *err, size_t err_cap)
 {
-    if (!plan || count < 0 || !d_rows || !rows_cap || !d_images) return APTGPU_ERR_INVALID;
-    return guarded(err, err_cap, [&] {
+    return plan_process_image(plan, count, d_rows, rows_cap, contrast, percent, rotate, color, channels, nullptr,
+                              nullptr, nullptr, d_images, err, err_cap);
+}
+
+int aptgpu_process_image_map(const aptgpu_context *ctx, const float *signal, size_t n, int contrast,
+                             float percent, int rotate, const aptgpu_color_settings *color, int channels,
+                             const aptgpu_map_settings *map, const aptgpu_map_layers *layers,
+                             const double *sat_positions, uint8_t **image_out, size_t *n_out,
+                             aptgpu_image_result *info, char *err, size_t err_cap)
+{
+    if (!sat_positions && n >= 2080) return APTGPU_ERR_INVALID;
+    int rc = guarded(err, err_cap, [&] {
         apt::gpu::ColorTune tune{};
         bool lab = false;
-        const bool colored = color_args(contrast, rotate, color, channels, &tune, &lab);
-        if (static_cast<size_t>(count) > plan->last_slots.size())
-            throw Error{ErrorKind::Invalid, "count exceeds the recordings of the last decode call"};
-        if (contrast == APTGPU_CONTRAST_PERCENT && (percent < 0.f || percent > 1.f))
-            throw Error{ErrorKind::Internal, kBadPercent};
-        const uintptr_t align = channels == 4 ? 15u : 3u;
-        for (int i = 0; i < count; ++i) {
-            if (!d_rows[i] || !d_images[i]) throw Error{ErrorKind::Invalid, "null device pointer"};
-            if (reinterpret_cast<uintptr_t>(d_images[i]) & align)
-                throw Error{ErrorKind::Invalid, channels == 4 ? "d_images must be 16-byte aligned for channels = 4"
-                                                              : "d_images must be 4-byte aligned"};
+        color_args(contrast, rotate, color, channels, &tune, &lab);
+        map_args(channels, map, layers);
+        return APTGPU_OK;
+    });
+    if (rc != APTGPU_OK) return rc;
+    const MapCall m{map, &layers->layers};
+    return process_image(ctx, signal, n, contrast, percent, rotate, color, channels, &m, sat_positions, image_out,
+                         n_out, info, err, err_cap);
+}
+
+int aptgpu_plan_process_device_image_map(aptgpu_plan *plan, int count, const float *const *d_rows,
+                                         const size_t *rows_cap, int contrast, float percent, int rotate,
+                                         const aptgpu_color_settings *color, int channels,
+                                         const aptgpu_map_settings *map, const aptgpu_map_layers *layers,
+                                         const double *const *sat_positions, const size_t *n_positions,
+                                         uint8_t *const *d_images, char *err, size_t err_cap)
+{
+    int rc = guarded(err, err_cap, [&] {
+        apt::gpu::ColorTune tune{};
+        bool lab = false;
+        color_args(contrast, rotate, color, channels, &tune, &lab);
+        map_args(channels, map, layers);
+        return APTGPU_OK;
+    });
+    if (rc != APTGPU_OK) return rc;
+    const MapCall m{map, &layers->layers};
+    return plan_process_image(plan, count, d_rows, rows_cap, contrast, percent, rotate, color, channels, &m,
+                              sat_positions, n_positions, d_images, err, err_cap);
+}
+
+int aptgpu_map_layers_create(aptgpu_map_layers **out)
+{
+    if (!out) return APTGPU_ERR_INVALID;
+    *out = nullptr;
+    try {
+        *out = new aptgpu_map_layers();
+    } catch (const std::bad_alloc &) {
+        return APTGPU_ERR_INVALID;
+    }
+    return APTGPU_OK;
+}
+
+void aptgpu_map_layers_destroy(aptgpu_map_layers *layers)
+{
+    delete layers;
+}
+
+int aptgpu_map_layers_load_dir(aptgpu_map_layers *layers, const char *dir, char *err, size_t err_cap)
+{
+    if (!layers || !dir) return APTGPU_ERR_INVALID;
+    return guarded(err, err_cap, [&] {
+        // res_path!("shapefiles", name): the directory joined with the file name
+        std::string base(dir);
+        if (!base.empty() && base.back() != '/') base += '/';
+        apt::map::Layer st = apt::map::read_shp(base + "states.shp", apt::map::kShpPolyline);
+        apt::map::Layer co = apt::map::read_shp(base + "countries.shp", apt::map::kShpPolygon);
+        apt::map::Layer la = apt::map::read_shp(base + "lakes.shp", apt::map::kShpPolygon);
+        apt::map::Layers &l = layers->layers;
+        l.layer[0] = std::move(st);
+        l.layer[1] = std::move(co);
+        l.layer[2] = std::move(la);
+        l.present[0] = l.present[1] = l.present[2] = true;
+        l.flatten();
+        return APTGPU_OK;
+    });
+}
+
+int aptgpu_map_layers_set(aptgpu_map_layers *layers, int layer, const double *xy, size_t n_points,
+                          const uint32_t *part_offsets, size_t n_parts, char *err, size_t err_cap)
+{
+    if (!layers || (!xy && n_points) || (!part_offsets && n_parts)) return APTGPU_ERR_INVALID;
+    return guarded(err, err_cap, [&] {
+        const int k = layer_index(layer);
+        if (n_parts == 0) {
+            if (n_points) throw Error{ErrorKind::Invalid, "layer: points without parts"};
+            layers->layers.clear(k);
+            return APTGPU_OK;
         }
-        apt::hip_check(hipSetDevice(plan->device), "hipSetDevice");
-        if (colored) plan->set_palette(color->palette_rgb, lab);
-        for (int i = 0; i < count; ++i)
-            plan->enqueue_image_color(i, d_rows[i], static_cast<uint64_t>(rows_cap[i]) * 2080u, contrast, percent,
-                                      rotate == APTGPU_ROTATE_YES, colored ? &tune : nullptr, channels, d_images[i],
-                                      lab);
+        apt::map::Layer l;
+        l.xy.assign(xy, xy + 2 * n_points);
+        l.parts.assign(part_offsets, part_offsets + n_parts + 1);
+        layers->layers.set(k, std::move(l));
+        return APTGPU_OK;
+    });
+}
+
+int aptgpu_map_layers_set_color(aptgpu_map_layers *layers, int layer, const uint8_t rgba[4])
+{
+    if (!layers || !rgba || layer < APTGPU_MAP_STATES || layer > APTGPU_MAP_LAKES) return APTGPU_ERR_INVALID;
+    layers->layers.color[layer] = uint32_t(rgba[0]) | (uint32_t(rgba[1]) << 8) | (uint32_t(rgba[2]) << 16) |
+                                  (uint32_t(rgba[3]) << 24);
+    return APTGPU_OK;
+}
+
+int aptgpu_map_read_shapefile(const char *path, int shape_type, double **xy, size_t *n_points,
+                              uint32_t **part_offsets, size_t *n_parts, char *err, size_t err_cap)
+{
+    if (!path || !xy || !n_points || !part_offsets || !n_parts) return APTGPU_ERR_INVALID;
+    *xy = nullptr;
+    *part_offsets = nullptr;
+    *n_points = *n_parts = 0;
+    return guarded(err, err_cap, [&] {
+        const apt::map::Layer l = apt::map::read_shp(path, shape_type);
+        double *h = host_alloc<double>(l.xy.size());
+        uint32_t *o = static_cast<uint32_t *>(std::malloc(l.parts.size() * sizeof(uint32_t)));
+        if (!o) {
+            std::free(h);
+            throw std::bad_alloc();
+        }
+        std::memcpy(h, l.xy.data(), l.xy.size() * sizeof(double));
+        std::memcpy(o, l.parts.data(), l.parts.size() * sizeof(uint32_t));
+        *xy = h;
+        *part_offsets = o;
+        *n_points = l.points();
+        *n_parts = l.parts.size() - 1;
         return APTGPU_OK;
     });
 }

@@ -1,0 +1,57 @@
+// apt_kernels_map.hpp — the gfx950 side of the map overlay (apt_kernels_map.hip): device state of one overlay
+// target and the launch sequence that draws a layer set (apt_map.hpp) over process()'s RGBA image.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "apt_kernels.hpp"
+#include "apt_map.hpp"
+
+namespace apt {
+void hip_check(hipError_t e, const char *what);
+}
+
+namespace apt::map {
+
+// Device-side state of one overlay target (a one-shot call or a plan slot): the uploaded layer set, the per-vertex
+// projection and segment scan, the track, the fragments and their per-pixel runs.  Grows, never shrinks.
+struct Device {
+    double *verts = nullptr;    // 2 per vertex (lon°, lat°)
+    int32_t *meta = nullptr;    // 2 per vertex
+    double *proj = nullptr;     // 2 per vertex (x, y) relative pixels
+    uint64_t *seg = nullptr;    // fragments per segment, then their exclusive scan (n_vert + 1)
+    uint64_t *sums = nullptr;   // scan block sums
+    double *track = nullptr;    // 2 per row (lat, lon) rad
+    double *xoff = nullptr;     // per row
+    uint64_t *frags = nullptr;  // kMaxFragments packed fragments, in draw order
+    uint32_t *slot = nullptr;   // 2 * kMaxFragments: each copy's arrival slot at its pixel
+    uint32_t *runs = nullptr;   // 2 * kMaxFragments: the copies grouped into one contiguous run per pixel
+    uint32_t *cnt = nullptr;    // per pixel of rows_cap rows: copies landing there (zero between calls)
+    uint32_t *base = nullptr;   // per pixel: start of its run in `runs` (valid where cnt != 0)
+    uint32_t *ctl = nullptr;    // [0] fragment total, [1] error / skip, [2] run allocator
+    static constexpr int kTrackRing = 8;
+    double *track_host[kTrackRing] = {};  // pinned staging of the track (rows_cap rows each), used in turn
+    hipEvent_t track_ev[kTrackRing] = {}; // behind the latest upload from track_host[k]
+    int track_next = 0;
+    size_t n_vert = 0, vert_cap = 0, rows_cap = 0;
+    uint64_t gen = 0;           // layer-set generation held in verts/meta
+    bool frag_ready = false;
+    Device() = default;
+    Device(const Device &) = delete;
+    Device &operator=(const Device &) = delete;
+    ~Device();
+    // (re)allocates for rows_cap rows and uploads the layer set when its generation differs, on stream s
+    void prepare(hipStream_t s, const Layers &layers, size_t rows_cap);
+    // copies min(count, rows_cap) positions to the device through the next staging buffer of the ring; waits on the
+    // host only while that buffer's upload of kTrackRing calls ago is still queued
+    void upload_track(hipStream_t s, const double *positions, size_t count);
+};
+
+// The overlay on the RGBA image `img` (height rows of 2080 px, from info->height on the device), which image_color
+// wrote, with the rotation folded in when `rotate` (each fragment goes through the same permutation).  d_track holds
+// min(count, rows_cap) positions; count != height is an error in info (reason kReasonCount), as are the bounds
+// above.  An info record whose status is already set is left alone and nothing is drawn.
+void image_map_overlay(hipStream_t s, Device &dev, const Scalars &sc, const Colors &colors, uint32_t count,
+                       bool rotate, uint8_t *img, apt::gpu::ImageResult *info);
+
+}  // namespace apt::map

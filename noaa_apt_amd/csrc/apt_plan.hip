@@ -988,3 +988,19 @@ void aptgpu_plan::enqueue_image_color(int i, const float *d_rows, uint64_t rows_
     });
     apt::hip_check(hipGetLastError(), "kernel launch (image stage)");
 }
+
+void aptgpu_plan::enqueue_image_map(int i, uint64_t rows_cap_floats, const apt::map::Layers &layers,
+                                    const apt::map::Scalars &sc, const apt::map::Colors &colors,
+                                    const double *positions, size_t count, bool rotate, uint8_t *d_image)
+{
+    const ImageTarget t = image_target(i, rows_cap_floats);
+    Slot &sl = t.slot;
+    if (!sl.map) sl.map = std::make_unique<apt::map::Device>();
+    sl.map->prepare(t.stream, layers, t.cap / 2080u);
+    sl.map->upload_track(t.stream, positions, count);
+    const uint32_t n = count < 0xffffffffu ? static_cast<uint32_t>(count) : 0xffffffffu;
+    timed(t.stream, "image_map_overlay", [&] {
+        apt::map::image_map_overlay(t.stream, *sl.map, sc, colors, n, rotate, d_image, t.out);
+    });
+    apt::hip_check(hipGetLastError(), "kernel launch (map overlay)");
+}

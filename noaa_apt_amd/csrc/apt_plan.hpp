@@ -5,6 +5,7 @@
 
 #include <cstdint>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -12,6 +13,7 @@
 #include "apt_host.hpp"
 #include "apt_kernels.hpp"
 #include "apt_kernels_color.hpp"
+#include "apt_kernels_map.hpp"
 #include "apt_wav.hpp"
 
 namespace apt {
@@ -179,6 +181,7 @@ struct aptgpu_plan {
         uint64_t palette_gen = 0;          // generation of the palette color_ws holds (0 = none)
         apt::DeviceBuffer<char> lab_ws;    // Lab tables + per-call RGBA table, on first use of the Lab path
         uint64_t lab_gen = 0;              // generation of the palette whose Lab tables lab_ws holds (0 = none)
+        std::unique_ptr<apt::map::Device> map;  // the map overlay's layer set, lists and track, on first use
         apt::DeviceBuffer<float> ingest;   // WAV -> f32 staging when the fused PCM16 path does not apply
     };
     std::vector<Slot> slots;
@@ -215,6 +218,11 @@ struct aptgpu_plan {
     void enqueue_image_color(int i, const float *d_rows, uint64_t rows_cap_floats, int contrast, float percent,
                              bool rotate, const apt::gpu::ColorTune *tune, int channels, uint8_t *d_image,
                              bool lab = false);
+    // The map overlay (apt_kernels_map.hpp) over recording i's RGBA image, behind enqueue_image_color on the same
+    // stream.  The slot uploads the layer set once per generation; positions: `count` (lat, lon) pairs.
+    void enqueue_image_map(int i, uint64_t rows_cap_floats, const apt::map::Layers &layers,
+                           const apt::map::Scalars &sc, const apt::map::Colors &colors, const double *positions,
+                           size_t count, bool rotate, uint8_t *d_image);
     // The false-colour palette (256*256*3 RGB).  The plan keeps a host copy; bytes that differ from it start a new
     // generation, which every slot uploads on its own stream the next time it colours an image.  lab: also the
     // palette's Lab tables (apt_lab.hpp), computed once per generation and uploaded per slot likewise.
