@@ -2,11 +2,12 @@
  * aptgpu_decode.c — minimal C caller of the drop-in boundary (include/aptgpu.h):
  *
  *     aptgpu_decode in.wav out.pgm [contrast: telemetry|percent|minmax] [--no-sync]
- *                   [--histogram] [--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE]
+ *                   [--histogram] [--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE] [--png]
  *
- * What `noaa-apt in.wav -o out.png` does (main.rs:91-110, noaa_apt.rs:114-235) minus PNG
- * encoding and the map overlay: load -> decode -> contrast limits -> 8-bit image, written as a
- * binary PGM.  --histogram: Contrast::Histogram (MinMax limits, then each channel's histogram
+ * What `noaa-apt in.wav -o out.png` does (main.rs:91-110, noaa_apt.rs:114-235): load -> decode ->
+ * contrast limits -> 8-bit image, written as a binary PGM, or with --png as the PNG file the GPU
+ * encodes (aptgpu_process_image_png: gray, or RGBA with --palette / --map; only the file's bytes
+ * cross to the host).  --histogram: Contrast::Histogram (MinMax limits, then each channel's histogram
  * equalised).  --palette FILE: false colour (`-F`, tune values 0) from a raw 256 x 256 RGB palette
  * (196 608 bytes, pixel (a, b) at (b*256 + a)*3), written as a binary PPM (the RGBA image without
  * its alpha).  --lab: with --histogram and --palette, equalise the false-colour image as the
@@ -32,10 +33,10 @@ int main(int argc, char **argv)
 {
     if (argc < 3) {
         fprintf(stderr, "usage: %s in.wav out.pgm [telemetry|percent|minmax] [--no-sync] [--histogram] "
-                "[--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE]\n", argv[0]);
+                "[--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE] [--png]\n", argv[0]);
         return 2;
     }
-    int contrast = APTGPU_CONTRAST_PERCENT, sync = 1, lab = 0;
+    int contrast = APTGPU_CONTRAST_PERCENT, sync = 1, lab = 0, png = 0;
     const char *palette_path = NULL, *map_dir = NULL, *track_path = NULL;
     for (int i = 3; i < argc; ++i) {
         if (!strcmp(argv[i], "telemetry")) contrast = APTGPU_CONTRAST_TELEMETRY;
@@ -44,6 +45,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--histogram")) contrast = APTGPU_CONTRAST_HISTOGRAM;
         else if (!strcmp(argv[i], "--no-sync")) sync = 0;
         else if (!strcmp(argv[i], "--lab")) lab = 1;
+        else if (!strcmp(argv[i], "--png")) png = 1;
         else if (!strcmp(argv[i], "--palette") && i + 1 < argc) palette_path = argv[++i];
         else if (!strcmp(argv[i], "--map") && i + 1 < argc) map_dir = argv[++i];
         else if (!strcmp(argv[i], "--track") && i + 1 < argc) track_path = argv[++i];
@@ -106,6 +108,7 @@ int main(int argc, char **argv)
     size_t n_px = 0;
     aptgpu_image_result info;
     const int rgba = palette_path || map_dir;
+    aptgpu_png_settings ps = {sizeof(aptgpu_png_settings), 0};
     if (map_dir) {
         /* the track: one (lat, lon) per image row, as map.rs:41-58 computes it with SGP4 */
         const size_t height = n_rows_px / 2080;
@@ -120,13 +123,21 @@ int main(int argc, char **argv)
         aptgpu_map_settings ms = {sizeof(aptgpu_map_settings), 0, 0.0, 1.0, 1.0};  /* config.rs:646-648 */
         rc = aptgpu_map_layers_create(&layers);
         if (rc == APTGPU_OK) rc = aptgpu_map_layers_load_dir(layers, map_dir, err, sizeof err);
-        if (rc == APTGPU_OK)
+        if (rc == APTGPU_OK && png)
+            rc = aptgpu_process_image_png(&ctx, rows, n_rows_px, contrast, 0.98f, APTGPU_ROTATE_NO,
+                                          palette_path ? &color : NULL, 4, &ms, layers, track, &ps, &image, &n_px,
+                                          &info, err, sizeof err);
+        else if (rc == APTGPU_OK)
             rc = aptgpu_process_image_map(&ctx, rows, n_rows_px, contrast, 0.98f, APTGPU_ROTATE_NO,
                                           palette_path ? &color : NULL, 4, &ms, layers, track, &image, &n_px, &info,
                                           err, sizeof err);
         aptgpu_map_layers_destroy(layers);
         free(track);
-    } else if (palette_path || contrast == APTGPU_CONTRAST_HISTOGRAM)
+    } else if (png)
+        rc = aptgpu_process_image_png(&ctx, rows, n_rows_px, contrast, 0.98f, APTGPU_ROTATE_NO,
+                                      palette_path ? &color : NULL, palette_path ? 4 : 1, NULL, NULL, NULL, &ps, &image,
+                                      &n_px, &info, err, sizeof err);
+    else if (palette_path || contrast == APTGPU_CONTRAST_HISTOGRAM)
         rc = aptgpu_process_image(&ctx, rows, n_rows_px, contrast, 0.98f, APTGPU_ROTATE_NO,
                                   palette_path ? &color : NULL, palette_path ? 4 : 1, &image, &n_px, &info, err,
                                   sizeof err);
@@ -138,7 +149,9 @@ int main(int argc, char **argv)
 
     FILE *o = fopen(argv[2], "wb");
     if (!o) { perror(argv[2]); return 1; }
-    if (rgba) {
+    if (png) {
+        fwrite(image, 1, n_px, o);  /* the file as it is: img.save(&output_filename), main.rs */
+    } else if (rgba) {
         fprintf(o, "P6\n2080 %u\n255\n", info.height);
         for (size_t i = 0; i < (size_t)info.height * 2080u; ++i) fwrite(image + 4 * i, 1, 3, o);  /* drop alpha */
     } else {

@@ -398,13 +398,15 @@ typedef struct aptgpu_image_result {
     int32_t status;          /* APTGPU_OK or APTGPU_ERR_INTERNAL */
     int32_t reason;          /* 1 zero-length signal (dsp.rs:40-44), 2 too short for telemetry
                                 (telemetry.rs:199-203), 3 no low bucket (misc.rs:172 panics),
-                                4 the decode before it failed */
+                                4 the decode before it failed, 5-8 the map overlay's limits
+                                (APTGPU_MAP_REASON_*), 9 APTGPU_PNG_REASON_CAPACITY */
     uint32_t height;         /* rows of 2080 px */
     uint32_t telemetry_row;  /* best frame start, telemetry.rs:196,228-230 */
     float low, high;         /* the contrast limits used by map_signal_u8 */
     float telemetry_quality;
     int32_t channel_a, channel_b; /* index for aptgpu_channel_name(), -1 = not computed */
-    uint32_t reserved;
+    uint32_t png_bytes;      /* the *_png entry points: length of the PNG file (with APTGPU_PNG_REASON_CAPACITY
+                                the length it needs); 0 from every other call (this was `reserved`) */
     uint64_t n_px;           /* u8 pixels written */
     float values_a[16], values_b[16]; /* wedges 1-16 of each band */
 } aptgpu_image_result;
@@ -541,6 +543,49 @@ int aptgpu_plan_process_device_image_map(aptgpu_plan *plan, int count, const flo
                                          const aptgpu_map_settings *map, const aptgpu_map_layers *layers,
                                          const double *const *sat_positions, const size_t *n_positions,
                                          uint8_t *const *d_images, char *err, size_t err_cap);
+
+/* ---- PNG encoding (main.rs, the Decode arm: `img.save(&output_filename)`) ----
+ * The file is the signature, IHDR, one IDAT and IEND: 8 bits per sample, no interlace, colour type 0 (gray) for
+ * channels 1 and 6 (RGBA, what the reference's RgbaImage saves as) for channels 4.  Decoding it gives the input bytes
+ * exactly; its bytes are a function of the pixels and the settings alone (not of the batch, the slot or the run) but
+ * are not those of the `png` crate.  Filter, deflate (matches, Huffman codes, bit packing), Adler-32 and CRC-32 all
+ * run on the GPU; only the encoded bytes cross to the host. */
+#define APTGPU_PNG_REASON_CAPACITY 9 /* aptgpu_image_result.reason: png_cap[i] is below the file's length, which
+                                        png_bytes then holds; nothing was written to d_png[i] */
+typedef struct aptgpu_png_settings {
+    uint32_t struct_size; /* sizeof(aptgpu_png_settings) */
+    uint32_t flags;       /* 0; any set bit is APTGPU_ERR_INVALID */
+} aptgpu_png_settings;
+/* The largest file the encoder can emit for such an image (every deflate chunk stored): pure host arithmetic.  0 for
+ * a zero width or height, channels other than 1 or 4, or an image past 2^31 filtered bytes. */
+size_t aptgpu_png_bound(uint32_t width, uint32_t height, int channels);
+/* Any host u8 image (height rows of width pixels of `channels` bytes) through the GPU encoder; settings nullable
+ * (= flags 0).  *png_out malloc'd, *n_out bytes.  A zero width or height and channels other than 1 or 4 are
+ * APTGPU_ERR_INVALID. */
+int aptgpu_encode_png(const aptgpu_context *ctx, const uint8_t *image, uint32_t width, uint32_t height, int channels,
+                      const aptgpu_png_settings *settings, uint8_t **png_out, size_t *n_out, char *err,
+                      size_t err_cap);
+/* aptgpu_process_image_map returning the PNG file instead of the pixels.  map, layers and sat_positions are nullable
+ * together (then no overlay, and channels may be 1).  info->png_bytes = *n_out.  A signal shorter than one row has
+ * no image to encode: APTGPU_ERR_INVALID. */
+int aptgpu_process_image_png(const aptgpu_context *ctx, const float *signal, size_t n, int contrast, float percent,
+                             int rotate, const aptgpu_color_settings *color, int channels,
+                             const aptgpu_map_settings *map, const aptgpu_map_layers *layers,
+                             const double *sat_positions, const aptgpu_png_settings *png, uint8_t **png_out,
+                             size_t *n_out, aptgpu_image_result *info, char *err, size_t err_cap);
+/* aptgpu_plan_process_device_image_map (map, layers, sat_positions and n_positions nullable together) followed by the
+ * encoder on each recording's stream: d_images[i] receives the pixels as before, d_png[i] (png_cap[i] bytes;
+ * aptgpu_png_bound(2080, rows_cap[i], channels) always suffices) the file.  Its length arrives in
+ * aptgpu_plan_image_results' png_bytes.  A capacity below the file's length is reported there (status
+ * APTGPU_ERR_INTERNAL, reason APTGPU_PNG_REASON_CAPACITY, png_bytes = the length needed) and d_png[i] is left
+ * untouched: nothing is truncated. */
+int aptgpu_plan_process_device_image_png(aptgpu_plan *plan, int count, const float *const *d_rows,
+                                         const size_t *rows_cap, int contrast, float percent, int rotate,
+                                         const aptgpu_color_settings *color, int channels,
+                                         const aptgpu_map_settings *map, const aptgpu_map_layers *layers,
+                                         const double *const *sat_positions, const size_t *n_positions,
+                                         uint8_t *const *d_images, const aptgpu_png_settings *png,
+                                         uint8_t *const *d_png, const size_t *png_cap, char *err, size_t err_cap);
 
 /* ====================================================================== */
 /* 5. WAV ingest in front of decode()                 */

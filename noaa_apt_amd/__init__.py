@@ -21,6 +21,8 @@ Names, argument meaning and error behaviour follow the reference:
     lab_to_rgb (Histogram + colour in CIE Lab)
     process(orbit=MapOverlay(...)): the map overlay,       map.rs:14-200 (SGP4 stays with the caller: it passes
     MapSettings, MapLayers, read_shapefile                 the per-row track), noaa_apt.rs:84-91
+    process(png=True), encode_png, png_bound: the PNG      main.rs, the Decode arm: img.save(&output_filename)
+    file of the image, encoded on the GPU
     percent, get_min, get_max, map_signal_u8               /root/reference/src/misc.rs:119, dsp.rs:20-54
     read_telemetry, Telemetry                              /root/reference/src/telemetry.rs:19-243
 
@@ -37,6 +39,7 @@ from .api import (  # noqa: F401
     Contrast, Rotate, ColorSettings, Telemetry, ImageResult, MapSettings, MapLayers, MapOverlay, read_shapefile,
     MAP_STATES, MAP_COUNTRIES, MAP_LAKES,
     get_min, get_max, percent, map_signal_u8, read_telemetry, process, lab_from_rgb, lab_to_rgb,
+    encode_png, png_bound, PNG_REASON_CAPACITY,
     Plan, PlanInfo, Result, KernelTime, decode_batch, BatchStats, host_alloc_f32, host_free,
     lib, lib_path, use_library, build, device_count, version, abi_version, cache_clear, cache_info, host_affinity, host_affinity_from_sysfs,
     MODE_STRICT, MODE_GENERIC, MODE_FP16_TAPS, MODE_FAST,

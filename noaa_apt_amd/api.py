@@ -123,14 +123,23 @@ class ImageResult(C.Structure):
     _fields_ = [("status", C.c_int32), ("reason", C.c_int32), ("height", C.c_uint32),
                 ("telemetry_row", C.c_uint32), ("low", C.c_float), ("high", C.c_float),
                 ("telemetry_quality", C.c_float), ("channel_a", C.c_int32), ("channel_b", C.c_int32),
-                ("reserved", C.c_uint32), ("n_px", C.c_uint64), ("values_a", C.c_float * 16),
+                ("png_bytes", C.c_uint32), ("n_px", C.c_uint64), ("values_a", C.c_float * 16),
                 ("values_b", C.c_float * 16)]
+
+    @property
+    def reserved(self):  # the field's name before the PNG entry points used it
+        return self.png_bytes
 
 
 class _CColorSettings(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("palette_rgb", _u8p),
                 ("ch_a_tune_start", C.c_float), ("ch_a_tune_end", C.c_float),
                 ("ch_b_tune_start", C.c_float), ("ch_b_tune_end", C.c_float)]
+
+
+class _CPngSettings(C.Structure):
+    """aptgpu_png_settings"""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class _CMapSettings(C.Structure):
@@ -312,6 +321,15 @@ def lib():
     L.aptgpu_plan_process_device_image_map.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz), i32, f, i32, ccs, i32,
                                                        cms, vp, C.POINTER(_f64p), C.POINTER(sz), C.POINTER(vp),
                                                        C.c_char_p, sz]
+    cps = C.POINTER(_CPngSettings)
+    L.aptgpu_png_bound.argtypes = [u32, u32, i32]
+    L.aptgpu_png_bound.restype = sz
+    L.aptgpu_encode_png.argtypes = [cp, _u8p, u32, u32, i32, cps, C.POINTER(_u8p), C.POINTER(sz), C.c_char_p, sz]
+    L.aptgpu_process_image_png.argtypes = [cp, _f32p, sz, i32, f, i32, ccs, i32, cms, vp, _f64p, cps, C.POINTER(_u8p),
+                                           C.POINTER(sz), C.POINTER(ImageResult), C.c_char_p, sz]
+    L.aptgpu_plan_process_device_image_png.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz), i32, f, i32, ccs, i32,
+                                                       cms, vp, C.POINTER(_f64p), C.POINTER(sz), C.POINTER(vp), cps,
+                                                       C.POINTER(vp), C.POINTER(sz), C.c_char_p, sz]
     _lib = L
     return L
 
@@ -954,14 +972,48 @@ def read_telemetry(context, signal):  # telemetry.rs:125
     return Telemetry._from(r)
 
 
+PNG_REASON_CAPACITY = 9  # ImageResult.reason: the PNG buffer is smaller than the file (png_bytes = its length)
+
+
+def png_bound(width, height, channels):
+    """aptgpu_png_bound: the largest file the encoder can emit for such an image (host arithmetic)."""
+    n = lib().aptgpu_png_bound(int(width), int(height), int(channels))
+    if n == 0:
+        raise InvalidError("png_bound: width and height >= 1, channels 1 or 4, below 2^31 bytes")
+    return int(n)
+
+
+def encode_png(image, context=None) -> bytes:
+    """aptgpu_encode_png: a (height, width) or (height, width, 1) uint8 image as a gray PNG, a (height, width, 4) one
+    as RGBA, encoded on the GPU.  Decoding the file gives the array back exactly."""
+    x = np.ascontiguousarray(image)
+    if x.dtype != np.uint8 or x.ndim not in (2, 3):
+        raise InvalidError("encode_png: a uint8 array of (height, width) or (height, width, channels)")
+    height, width = x.shape[:2]
+    channels = x.shape[2] if x.ndim == 3 else 1
+    cctx = (context or Context())._c()
+    cps = _CPngSettings(C.sizeof(_CPngSettings), 0)
+    out, n = _u8p(), C.c_size_t()
+    err = C.create_string_buffer(_ERRCAP)
+    _check(lib().aptgpu_encode_png(C.byref(cctx), x.ctypes.data_as(_u8p), width, height, channels, C.byref(cps),
+                                   C.byref(out), C.byref(n), err, _ERRCAP), err)
+    return _take(out, n.value, np.uint8).tobytes()
+
+
 def process(context, signal, contrast_adjustment, rotate=Rotate.NO, color=None, orbit=None,
-            return_info=False):
+            return_info=False, png=False):
     """noaa_apt::process (noaa_apt.rs:132-235).  Returns the height x 2080 u8
     gray image, or with `color` (a ColorSettings) the height x 2080 x 4 RGBA image of the reference's
     false colour (A = 255).  Contrast.HISTOGRAM equalises each channel half of the gray image; together with
     false colour it needs ColorSettings(equalize_lab=True) (the reference equalises channel A in CIE Lab then).
     `orbit` may be a MapOverlay: the map is drawn over the RGBA image (height x 2080 x 4, also without colour).
+    png=True: the image is also encoded on the GPU and the PNG file's bytes are returned instead of the pixels
+    (what `img.save()` writes in main.rs; gray without colour and map, RGBA with).
     Unsupported: any other `orbit`, Rotate.ORBIT, and HISTOGRAM with colour without equalize_lab."""
+    if png:
+        if orbit is not None and not isinstance(orbit, MapOverlay):
+            raise UnsupportedError("orbit: only a MapOverlay (the map overlay) is served on the GPU path")
+        return _process_image(context, signal, contrast_adjustment, rotate, color, return_info, orbit, png=True)
     if isinstance(orbit, MapOverlay):
         return _process_image(context, signal, contrast_adjustment, rotate, color, return_info, orbit)
     if orbit is not None:
@@ -981,7 +1033,8 @@ def process(context, signal, contrast_adjustment, rotate=Rotate.NO, color=None, 
     return (out, info) if return_info else out
 
 
-def _process_image(context, signal, contrast_adjustment, rotate, color, return_info, overlay=None, channels=None):
+def _process_image(context, signal, contrast_adjustment, rotate, color, return_info, overlay=None, channels=None,
+                   png=False):
     if color is not None and not isinstance(color, ColorSettings):
         raise UnsupportedError("color must be a ColorSettings")
     cctx = (context or Context())._c()
@@ -996,6 +1049,17 @@ def _process_image(context, signal, contrast_adjustment, rotate, color, return_i
         if len(overlay.sat_positions) != x.size // PX_PER_ROW:
             raise InvalidError(f"MapOverlay: {len(overlay.sat_positions)} positions for {x.size // PX_PER_ROW} rows")
         overlay.layers._colors(overlay.settings)
+    if png:
+        cms = overlay.settings._c() if overlay is not None else None
+        cps = _CPngSettings(C.sizeof(_CPngSettings), 0)
+        _check(lib().aptgpu_process_image_png(
+            C.byref(cctx), xp, x.size, kind, p, int(rotate), C.byref(ccol) if ccol is not None else None,
+            int(channels), C.byref(cms) if cms is not None else None, overlay.layers._p if overlay is not None else None,
+            overlay.sat_positions.ctypes.data_as(_f64p) if overlay is not None else None, C.byref(cps), C.byref(img),
+            C.byref(n), C.byref(info), err, _ERRCAP), err)
+        data = _take(img, n.value, np.uint8).tobytes()
+        return (data, info) if return_info else data
+    if overlay is not None:
         cms = overlay.settings._c()
         _check(lib().aptgpu_process_image_map(C.byref(cctx), xp, x.size, kind, p, int(rotate),
                                               C.byref(ccol) if ccol is not None else None, int(channels),
@@ -1153,12 +1217,17 @@ class Plan:
                                                 (C.c_void_p * k)(*d_images), err, _ERRCAP), err)
 
     def process_device_image(self, d_rows: Sequence[int], rows_cap: Sequence[int], contrast_adjustment,
-                             d_images: Sequence[int], rotate=Rotate.NO, color=None, channels=None, map=None):  # noqa: A002
+                             d_images: Sequence[int], rotate=Rotate.NO, color=None, channels=None, map=None,  # noqa: A002
+                             png=None):
         """process() with every contrast (HISTOGRAM too) and optional false colour (a ColorSettings) for the
         recordings of the last decode_device call, chained on the device behind their decode.  d_images[i]
         holds rows_cap[i] * 2080 * channels bytes; channels defaults to 4 (RGBA) with colour or map, 1 (gray)
         without.  map: a MapOverlay, or one per recording (all with the same settings and layers); a position count
-        that differs from a recording's height is reported in image_results() (reason 7)."""
+        that differs from a recording's height is reported in image_results() (reason 7).
+        png: (d_png, png_cap), device pointers and their capacities in bytes, one per recording: each image is then
+        also encoded as a PNG file on its stream (png_bound(2080, rows_cap[i], channels) bytes always suffice); the
+        lengths arrive through png_sizes().  A capacity below the file's length is reported in image_results()
+        (reason PNG_REASON_CAPACITY, png_bytes = the length needed) and nothing is written."""
         if color is not None and not isinstance(color, ColorSettings):
             raise UnsupportedError("color must be a ColorSettings")
         if channels is None:
@@ -1167,6 +1236,23 @@ class Plan:
         kind, p = Contrast._c(contrast_adjustment)
         ccol = color._c() if color is not None else None
         err = C.create_string_buffer(_ERRCAP)
+        if png is not None:
+            d_png, png_cap = png
+            if len(d_png) != k or len(png_cap) != k:
+                raise InvalidError("png: (d_png, png_cap) with one entry per recording")
+            cms, layers, pos, npos = None, None, None, None
+            if map is not None:
+                maps = self._maps(map, k)
+                cms, layers = maps[0].settings._c(), maps[0].layers._p
+                pos = (_f64p * k)(*[m.sat_positions.ctypes.data_as(_f64p) for m in maps])
+                npos = (C.c_size_t * k)(*[len(m.sat_positions) for m in maps])
+            cps = _CPngSettings(C.sizeof(_CPngSettings), 0)
+            _check(lib().aptgpu_plan_process_device_image_png(
+                self._p, k, (C.c_void_p * k)(*d_rows), (C.c_size_t * k)(*rows_cap), kind, p, int(rotate),
+                C.byref(ccol) if ccol is not None else None, int(channels), C.byref(cms) if cms is not None else None,
+                layers, pos, npos, (C.c_void_p * k)(*d_images), C.byref(cps), (C.c_void_p * k)(*d_png),
+                (C.c_size_t * k)(*[int(c) for c in png_cap]), err, _ERRCAP), err)
+            return
         if map is not None:
             maps = [map] * k if isinstance(map, MapOverlay) else list(map)
             if len(maps) != k or not all(isinstance(m, MapOverlay) for m in maps):
@@ -1186,6 +1272,27 @@ class Plan:
                                                       (C.c_size_t * k)(*rows_cap), kind, p, int(rotate),
                                                       C.byref(ccol) if ccol is not None else None, int(channels),
                                                       (C.c_void_p * k)(*d_images), err, _ERRCAP), err)
+
+    @staticmethod
+    def _maps(map, k):  # noqa: A002
+        maps = [map] * k if isinstance(map, MapOverlay) else list(map)
+        if len(maps) != k or not all(isinstance(m, MapOverlay) for m in maps):
+            raise InvalidError("map: a MapOverlay or one per recording")
+        if any(m.layers is not maps[0].layers or vars(m.settings) != vars(maps[0].settings) for m in maps):
+            raise InvalidError("map: every recording's MapOverlay must share settings and layers")
+        maps[0].layers._colors(maps[0].settings)
+        return maps
+
+    def png_sizes(self, count=1) -> List[int]:
+        """Lengths of the PNG files of the last process_device_image(..., png=...) call (waits for it).  Raises for a
+        recording whose image stage or encoding failed; image_results() has the records."""
+        out = []
+        for i, r in enumerate(self.image_results(count)):
+            if r.status != 0:
+                raise InternalError(f"recording {i}: image stage failed (reason {r.reason}"
+                                    + (f", the PNG needs {r.png_bytes} bytes)" if r.reason == PNG_REASON_CAPACITY else ")"))
+            out.append(int(r.png_bytes))
+        return out
 
     def image_results(self, count=1) -> List[ImageResult]:
         arr = (ImageResult * count)()

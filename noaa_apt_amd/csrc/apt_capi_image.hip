@@ -7,6 +7,7 @@
 
 #include "apt_capi_util.hpp"
 #include "apt_kernels_color.hpp"
+#include "apt_kernels_png.hpp"
 #include "apt_map.hpp"
 
 // the opaque handle of include/aptgpu.h
@@ -30,6 +31,7 @@ const char *kMapOverflow = "map overlay: more than APTGPU_MAP_MAX_FRAGMENTS (2^2
 const char *kMapWalk = "map overlay: a segment's walk is longer than APTGPU_MAP_MAX_WALK (2^20) steps or has a non-finite end";
 const char *kMapPixel = "map overlay: more than APTGPU_MAP_MAX_PIXEL_FRAGMENTS (2^16) fragments on one pixel";
 const char *kMapCount = "map overlay: the number of satellite positions differs from the image height";
+const char *kPngCapacity = "PNG encoding: the output buffer is smaller than the file (APTGPU_PNG_REASON_CAPACITY)";
 const char *kChannelNames[9] = {"1", "2", "3a", "4", "5", "3b", "Unknown", "Unknown", "Unknown"};
 
 // Rust's `{}` for an f32: shortest decimal that round-trips, never in exponent form.
@@ -78,6 +80,7 @@ void throw_for(const ImageResult &r, int contrast)
     case apt::map::kReasonWalk: throw Error{ErrorKind::Internal, kMapWalk};
     case apt::map::kReasonCount: throw Error{ErrorKind::Internal, kMapCount};
     case apt::map::kReasonPixel: throw Error{ErrorKind::Internal, kMapPixel};
+    case apt::png::kReasonCapacity: throw Error{ErrorKind::Internal, kPngCapacity};
     default: throw Error{ErrorKind::Internal, "image stage failed"};
     }
     (void)contrast;
@@ -260,9 +263,43 @@ apt::map::Colors map_colors(const apt::map::Layers &l)
     return apt::map::Colors{{l.color[0], l.color[1], l.color[2]}};
 }
 
+// The checks of the PNG entry points' settings (nullable: flags 0).
+void png_args(const aptgpu_png_settings *png)
+{
+    if (!png) return;
+    if (png->struct_size < sizeof(aptgpu_png_settings))
+        throw Error{ErrorKind::Invalid, "aptgpu_png_settings: struct_size not set"};
+    if (png->flags) throw Error{ErrorKind::Invalid, "aptgpu_png_settings: unknown flags"};
+}
+
+// width, height, channels of an image the encoder takes; returns the filtered stream's bytes
+uint64_t png_shape(uint32_t width, uint32_t height, int channels)
+{
+    if (width == 0 || height == 0) throw Error{ErrorKind::Invalid, "a PNG needs a width and a height of at least 1"};
+    if (channels != 1 && channels != 4) throw Error{ErrorKind::Invalid, "channels must be 1 (gray) or 4 (RGBA)"};
+    const uint64_t stream = apt::png::stream_bytes(width, height, channels);
+    if (stream >= apt::png::kMaxStream) throw Error{ErrorKind::Invalid, "image too large for the PNG encoder (2^31 bytes)"};
+    return stream;
+}
+
+// Copies the encoded file behind the call's stream to a malloc'd host buffer.
+void png_to_host(hipStream_t s, const uint8_t *d_png, size_t len, uint8_t **png_out, size_t *n_out)
+{
+    uint8_t *h = host_alloc<uint8_t>(len);
+    if (len && (hipMemcpyAsync(h, d_png, len, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                hipStreamSynchronize(s) != hipSuccess)) {
+        std::free(h);
+        throw Error{ErrorKind::Hip, "D2H copy failed"};
+    }
+    *png_out = h;
+    *n_out = len;
+}
+
+// png: encode the image on the device and return the file instead of the pixels
 int process_image(const aptgpu_context *ctx, const float *signal, size_t n, int contrast, float percent, int rotate,
                   const aptgpu_color_settings *color, int channels, const MapCall *map, const double *positions,
-                  uint8_t **image_out, size_t *n_out, aptgpu_image_result *info, char *err, size_t err_cap)
+                  uint8_t **image_out, size_t *n_out, aptgpu_image_result *info, char *err, size_t err_cap,
+                  bool png = false)
 {
     if ((!signal && n) || !image_out || !n_out) return APTGPU_ERR_INVALID;
     *image_out = nullptr;
@@ -273,6 +310,7 @@ int process_image(const aptgpu_context *ctx, const float *signal, size_t n, int 
         const bool colored = color_args(contrast, rotate, color, channels, &tune, &lab);
         if (map && n / 2080 == 0 && n != 0)
             throw Error{ErrorKind::Internal, "map overlay: the image has no row to draw on"};
+        if (png && n / 2080 == 0 && n != 0) throw Error{ErrorKind::Invalid, "PNG encoding: the image has no row"};
         std::vector<uint32_t> packed;  // (outlives the call's stream: ~ImageCall synchronises it)
         std::shared_ptr<const apt::lab::Tables> lab_tables;  // (likewise)
         apt::map::Device map_dev;  // (likewise)
@@ -314,10 +352,24 @@ int process_image(const aptgpu_context *ctx, const float *signal, size_t n, int 
                                         static_cast<uint32_t>(height), rotate == APTGPU_ROTATE_YES, d_img.ptr,
                                         c.d_info.ptr);
         }
+        apt::DeviceBuffer<char> pws;
+        apt::DeviceBuffer<uint8_t> d_png;
+        if (png) {
+            const uint32_t height = static_cast<uint32_t>(n / 2080);
+            const uint64_t stream = png_shape(2080, height, channels);
+            const uint64_t cap = apt::png::bound(2080, height, channels);
+            pws.alloc(apt::png::ws_bytes(stream));
+            d_png.alloc(cap);
+            apt::png::encode(s, d_img.ptr, 2080, height, channels, pws.ptr, stream, d_png.ptr, cap, c.d_info.ptr, nullptr);
+        }
         apt::hip_check(hipGetLastError(), "kernel launch (image stage)");
         const ImageResult r = c.info();
         copy_out(info, r);
         throw_for(r, contrast);
+        if (png) {
+            png_to_host(s, d_png.ptr, r.reserved, image_out, n_out);
+            return APTGPU_OK;
+        }
         uint8_t *h = host_alloc<uint8_t>(bytes);
         if (bytes && (hipMemcpyAsync(h, d_img.ptr, bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
                       hipStreamSynchronize(s) != hipSuccess)) {
@@ -333,7 +385,7 @@ int process_image(const aptgpu_context *ctx, const float *signal, size_t n, int 
 int plan_process_image(aptgpu_plan *plan, int count, const float *const *d_rows, const size_t *rows_cap, int contrast,
                        float percent, int rotate, const aptgpu_color_settings *color, int channels, const MapCall *map,
                        const double *const *positions, const size_t *n_positions, uint8_t *const *d_images, char *err,
-                       size_t err_cap)
+                       size_t err_cap, uint8_t *const *d_png = nullptr, const size_t *png_cap = nullptr)
 {
     if (!plan || count < 0 || !d_rows || !rows_cap || !d_images) return APTGPU_ERR_INVALID;
     if (map && count > 0 && (!positions || !n_positions)) return APTGPU_ERR_INVALID;
@@ -349,6 +401,7 @@ int plan_process_image(aptgpu_plan *plan, int count, const float *const *d_rows,
         for (int i = 0; i < count; ++i) {
             if (!d_rows[i] || !d_images[i]) throw Error{ErrorKind::Invalid, "null device pointer"};
             if (map && !positions[i] && n_positions[i]) throw Error{ErrorKind::Invalid, "null sat_positions"};
+            if (d_png && !d_png[i]) throw Error{ErrorKind::Invalid, "null device pointer (d_png)"};
             if (reinterpret_cast<uintptr_t>(d_images[i]) & align)
                 throw Error{ErrorKind::Invalid, channels == 4 ? "d_images must be 16-byte aligned for channels = 4"
                                                               : "d_images must be 4-byte aligned"};
@@ -364,6 +417,10 @@ int plan_process_image(aptgpu_plan *plan, int count, const float *const *d_rows,
                 plan->enqueue_image_map(i, static_cast<uint64_t>(rows_cap[i]) * 2080u, *map->layers,
                                         map_scalars(*map, positions[i], n_positions[i]), map_colors(*map->layers),
                                         positions[i], n_positions[i], rotate == APTGPU_ROTATE_YES, d_images[i]);
+        if (d_png)
+            for (int i = 0; i < count; ++i)
+                plan->enqueue_image_png(i, static_cast<uint64_t>(rows_cap[i]) * 2080u, channels, d_images[i], d_png[i],
+                                        png_cap[i]);
         return APTGPU_OK;
     });
 }
@@ -557,6 +614,104 @@ int aptgpu_plan_process_device_image_map(aptgpu_plan *plan, int count, const flo
     const MapCall m{map, &layers->layers};
     return plan_process_image(plan, count, d_rows, rows_cap, contrast, percent, rotate, color, channels, &m,
                               sat_positions, n_positions, d_images, err, err_cap);
+}
+
+size_t aptgpu_png_bound(uint32_t width, uint32_t height, int channels)
+{
+    if (width == 0 || height == 0 || (channels != 1 && channels != 4)) return 0;
+    if (apt::png::stream_bytes(width, height, channels) >= apt::png::kMaxStream) return 0;
+    return static_cast<size_t>(apt::png::bound(width, height, channels));
+}
+
+int aptgpu_encode_png(const aptgpu_context *ctx, const uint8_t *image, uint32_t width, uint32_t height, int channels,
+                      const aptgpu_png_settings *settings, uint8_t **png_out, size_t *n_out, char *err,
+                      size_t err_cap)
+{
+    if (!png_out || !n_out) return APTGPU_ERR_INVALID;
+    *png_out = nullptr;
+    *n_out = 0;
+    return guarded(err, err_cap, [&] {
+        // (every check before the device is touched)
+        png_args(settings);
+        const uint64_t stream = png_shape(width, height, channels);
+        if (!image) throw Error{ErrorKind::Invalid, "null image"};
+        const size_t bytes = static_cast<size_t>(width) * height * static_cast<size_t>(channels);
+        const uint64_t cap = apt::png::bound(width, height, channels);
+        Scratch sc(ctx);
+        hipStream_t s = sc.stream;
+        apt::DeviceBuffer<uint8_t> d_img, d_png;
+        apt::DeviceBuffer<char> ws;
+        apt::DeviceBuffer<uint64_t> d_len;
+        d_img.alloc(bytes + 16);
+        d_png.alloc(cap);
+        ws.alloc(apt::png::ws_bytes(stream));
+        d_len.alloc(1);
+        apt::hip_check(hipMemcpyAsync(d_img.ptr, image, bytes, hipMemcpyHostToDevice, s), "hipMemcpyAsync H2D");
+        apt::png::encode(s, d_img.ptr, width, height, channels, ws.ptr, stream, d_png.ptr, cap, nullptr, d_len.ptr);
+        apt::hip_check(hipGetLastError(), "kernel launch (PNG encoder)");
+        uint64_t len = 0;
+        apt::hip_check(hipMemcpyAsync(&len, d_len.ptr, sizeof len, hipMemcpyDeviceToHost, s), "hipMemcpyAsync D2H");
+        apt::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
+        if (len == 0 || len > cap) throw Error{ErrorKind::Internal, "PNG encoder: the file exceeds aptgpu_png_bound"};
+        png_to_host(s, d_png.ptr, static_cast<size_t>(len), png_out, n_out);
+        return APTGPU_OK;
+    });
+}
+
+// map, layers and sat_positions of the PNG entry points: all given or none
+bool png_map_given(const void *map, const void *layers, const void *positions, bool need_positions)
+{
+    if (!map && !layers && !positions) return false;
+    if (!map || !layers || (!positions && need_positions))
+        throw Error{ErrorKind::Invalid, "map, layers and sat_positions must be given together"};
+    return true;
+}
+
+int aptgpu_process_image_png(const aptgpu_context *ctx, const float *signal, size_t n, int contrast, float percent,
+                             int rotate, const aptgpu_color_settings *color, int channels,
+                             const aptgpu_map_settings *map, const aptgpu_map_layers *layers,
+                             const double *sat_positions, const aptgpu_png_settings *png, uint8_t **png_out,
+                             size_t *n_out, aptgpu_image_result *info, char *err, size_t err_cap)
+{
+    bool with_map = false;
+    int rc = guarded(err, err_cap, [&] {
+        apt::gpu::ColorTune tune{};
+        bool lab = false;
+        color_args(contrast, rotate, color, channels, &tune, &lab);
+        png_args(png);
+        with_map = png_map_given(map, layers, sat_positions, n >= 2080);
+        if (with_map) map_args(channels, map, layers);
+        return APTGPU_OK;
+    });
+    if (rc != APTGPU_OK) return rc;
+    MapCall m{map, with_map ? &layers->layers : nullptr};
+    return process_image(ctx, signal, n, contrast, percent, rotate, color, channels, with_map ? &m : nullptr,
+                         sat_positions, png_out, n_out, info, err, err_cap, true);
+}
+
+int aptgpu_plan_process_device_image_png(aptgpu_plan *plan, int count, const float *const *d_rows,
+                                         const size_t *rows_cap, int contrast, float percent, int rotate,
+                                         const aptgpu_color_settings *color, int channels,
+                                         const aptgpu_map_settings *map, const aptgpu_map_layers *layers,
+                                         const double *const *sat_positions, const size_t *n_positions,
+                                         uint8_t *const *d_images, const aptgpu_png_settings *png,
+                                         uint8_t *const *d_png, const size_t *png_cap, char *err, size_t err_cap)
+{
+    if (!d_png || !png_cap) return APTGPU_ERR_INVALID;
+    bool with_map = false;
+    int rc = guarded(err, err_cap, [&] {
+        apt::gpu::ColorTune tune{};
+        bool lab = false;
+        color_args(contrast, rotate, color, channels, &tune, &lab);
+        png_args(png);
+        with_map = png_map_given(map, layers, sat_positions, true);
+        if (with_map) map_args(channels, map, layers);
+        return APTGPU_OK;
+    });
+    if (rc != APTGPU_OK) return rc;
+    MapCall m{map, with_map ? &layers->layers : nullptr};
+    return plan_process_image(plan, count, d_rows, rows_cap, contrast, percent, rotate, color, channels,
+                              with_map ? &m : nullptr, sat_positions, n_positions, d_images, err, err_cap, d_png, png_cap);
 }
 
 int aptgpu_map_layers_create(aptgpu_map_layers **out)

@@ -1004,3 +1004,26 @@ void aptgpu_plan::enqueue_image_map(int i, uint64_t rows_cap_floats, const apt::
     });
     apt::hip_check(hipGetLastError(), "kernel launch (map overlay)");
 }
+
+void aptgpu_plan::enqueue_image_png(int i, uint64_t rows_cap_floats, int channels, const uint8_t *d_image,
+                                    uint8_t *d_png, uint64_t png_cap)
+{
+    const ImageTarget t = image_target(i, rows_cap_floats);
+    Slot &sl = t.slot;
+    const uint32_t rows = static_cast<uint32_t>(t.cap / 2080u);  // the launch grids cover the capacity
+    if (rows == 0) return;
+    // (sized for the plan's largest image with 4 bytes per pixel, so one allocation serves every call)
+    const uint64_t ws_rows = std::max<uint64_t>(max_rows, out_len_nosync(work_len_for(max_samples)) / 2080u + 1);
+    const uint64_t stream_cap = apt::png::stream_bytes(2080, ws_rows, 4);
+    if (!sl.png_ws.ptr) sl.png_ws.alloc(apt::png::ws_bytes(stream_cap));
+    timed(t.stream, "image_png_filter", [&] {
+        apt::png::encode_filter(t.stream, d_image, 2080, rows, channels, sl.png_ws.ptr, stream_cap, t.out);
+    });
+    timed(t.stream, "image_png_deflate", [&] {
+        apt::png::encode_deflate(t.stream, 2080, rows, channels, sl.png_ws.ptr, stream_cap, t.out);
+    });
+    timed(t.stream, "image_png_place", [&] {
+        apt::png::encode_place(t.stream, 2080, rows, channels, sl.png_ws.ptr, stream_cap, d_png, png_cap, t.out, nullptr);
+    });
+    apt::hip_check(hipGetLastError(), "kernel launch (PNG encoder)");
+}

@@ -14,6 +14,7 @@
 #include "apt_kernels.hpp"
 #include "apt_kernels_color.hpp"
 #include "apt_kernels_map.hpp"
+#include "apt_kernels_png.hpp"
 #include "apt_wav.hpp"
 
 namespace apt {
@@ -182,6 +183,7 @@ struct aptgpu_plan {
         apt::DeviceBuffer<char> lab_ws;    // Lab tables + per-call RGBA table, on first use of the Lab path
         uint64_t lab_gen = 0;              // generation of the palette whose Lab tables lab_ws holds (0 = none)
         std::unique_ptr<apt::map::Device> map;  // the map overlay's layer set, lists and track, on first use
+        apt::DeviceBuffer<char> png_ws;    // the PNG encoder's filtered stream, staging and chunk records, on first use
         apt::DeviceBuffer<float> ingest;   // WAV -> f32 staging when the fused PCM16 path does not apply
     };
     std::vector<Slot> slots;
@@ -223,6 +225,10 @@ struct aptgpu_plan {
     void enqueue_image_map(int i, uint64_t rows_cap_floats, const apt::map::Layers &layers,
                            const apt::map::Scalars &sc, const apt::map::Colors &colors, const double *positions,
                            size_t count, bool rotate, uint8_t *d_image);
+    // The PNG encoder (apt_kernels_png.hpp) over recording i's finished image, behind everything above on the same
+    // stream: the file goes to d_png (png_cap bytes), its length to the image record.
+    void enqueue_image_png(int i, uint64_t rows_cap_floats, int channels, const uint8_t *d_image, uint8_t *d_png,
+                           uint64_t png_cap);
     // The false-colour palette (256*256*3 RGB).  The plan keeps a host copy; bytes that differ from it start a new
     // generation, which every slot uploads on its own stream the next time it colours an image.  lab: also the
     // palette's Lab tables (apt_lab.hpp), computed once per generation and uploaded per slot likewise.

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """tools/image_stage_timing.py [--calls N] — device time of process()'s image stage per recording, at the config 2
-shape (16 recordings x 600 s at 48 kHz, 1198 rows each, one decode_device call), in six variants:
+shape (16 recordings x 600 s at 48 kHz, 1198 rows each, one decode_device call), in these variants:
 
     minmax_gray       aptgpu_plan_process_device, MinMax (the path before the colour stage: image_minmax + image_map_u8)
     minmax_gray_new   aptgpu_plan_process_device_image, MinMax, 1 byte per pixel (its output pass instead of image_map_u8)
@@ -12,13 +12,21 @@ shape (16 recordings x 600 s at 48 kHz, 1198 rows each, one decode_device call),
     map_fixture       color_rgba + the map overlay of the clipped South America shapefiles (tests/golden/shapefiles)
                       over a northbound track through them
     map_world         color_rgba + the map overlay of world-scale synthetic layers (~250 000 vertices)
+    png_gray          minmax_gray_new + the PNG encoder (colour type 0), the file left in HBM
+    png_rgba          the same image as RGBA (colour type 6: what the reference's RgbaImage saves as)
+    png_color         color_rgba + the PNG encoder
 
 Per kernel: the plan's event timing (every launch bracketed, one call in flight), ms per recording.  Per variant also
 the wall time of one call of 16 recordings with timing off (host clock around enqueue + synchronise).  Last, the host
 cost of the Lab tables when the palette changes: one call with a new palette each time against one with the same, and
 the host cost of building a world-scale layer set and of its first upload.  --variants a,b runs only those.
+For the png_* variants the wall time includes the copy of the encoded bytes to the host, and beside it stands the path
+without the encoder, on the same host in the same run: copy the raw image to the host and save() it with Pillow at its
+default level and at compress_level=1, single-threaded.  Then the file sizes against Pillow's for the committed rows
+of the reference's example image and one full-size false-colour image.
 GPU box."""
 import argparse
+import io
 import os
 import sys
 import time
@@ -55,6 +63,40 @@ def world_layers(seed=3, parts=2500, per_part=100):
     return {"states": out[:parts // 3], "countries": out[parts // 3:2 * parts // 3], "lakes": out[2 * parts // 3:]}
 
 
+def cpu_name():
+    try:
+        with open("/proc/cpuinfo") as f:
+            for line in f:
+                if line.startswith("model name"):
+                    return line.split(":", 1)[1].strip()
+    except OSError:
+        pass
+    return "unknown CPU"
+
+
+def pillow_save(px, **kw):
+    """(seconds, bytes) of Pillow's PNG save() of a (h, w) or (h, w, 4) u8 image."""
+    from PIL import Image
+    buf = io.BytesIO()
+    t0 = time.perf_counter()
+    Image.fromarray(px, "RGBA" if px.ndim == 3 else "L").save(buf, format="PNG", **kw)
+    return time.perf_counter() - t0, buf.tell()
+
+
+def png_sizes_report(full_px):
+    """File sizes of the encoder against Pillow's default save() (zlib level 6) and compress_level=1."""
+    rows = np.load(os.path.join(ROOT, "tests", "golden", "reference_image", "argentina_rows.npy"))
+    rgba = np.ascontiguousarray(np.stack([rows, rows, rows, np.full_like(rows, 255)], axis=-1))
+    print("PNG file sizes: encoder / Pillow default (level 6) / Pillow compress_level=1, bytes and ratios")
+    for name, px in (("argentina_rows gray", rows), ("argentina_rows RGBA", rgba),
+                     (f"synthetic false colour {full_px.shape[0]} rows", full_px)):
+        ours = len(apt.encode_png(px))
+        _, p6 = pillow_save(px)
+        _, p1 = pillow_save(px, compress_level=1)
+        print(f"  {name:34s} {ours:9d} {p6:9d} {p1:9d}   x{ours / p6:.3f} of level 6, x{ours / p1:.3f} of level 1, "
+              f"level 1 is x{p1 / p6:.3f} of level 6")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=20)
@@ -85,7 +127,16 @@ def main():
     pos = track(-52.0, -68.0, 8.0, rows)
     map_fixture = apt.MapOverlay(pos, apt.MapSettings(), fixture)
     map_world = apt.MapOverlay(pos, apt.MapSettings(), world)
+    png_cap = [apt.png_bound(2080, cap, 4)] * RECORDINGS
+    d_png = [torch.empty(png_cap[0], dtype=torch.uint8, device=dev) for _ in range(RECORDINGS)]
+    png = (ptr(d_png), png_cap)
+    png_channels = {"png_gray": 1, "png_rgba": 4, "png_color": 4}
     variants = {
+        "png_gray": lambda: plan.process_device_image(ptr(d_rows), caps, apt.Contrast.MINMAX, ptr(d_img), png=png),
+        "png_rgba": lambda: plan.process_device_image(ptr(d_rows), caps, apt.Contrast.MINMAX, ptr(d_img), channels=4,
+                                                      png=png),
+        "png_color": lambda: plan.process_device_image(ptr(d_rows), caps, apt.Contrast.MINMAX, ptr(d_img), color=color,
+                                                       png=png),
         "minmax_gray": lambda: plan.process_device(ptr(d_rows), caps, apt.Contrast.MINMAX, ptr(d_img)),
         "minmax_gray_new": lambda: plan.process_device_image(ptr(d_rows), caps, apt.Contrast.MINMAX, ptr(d_img)),
         "histogram_gray": lambda: plan.process_device_image(ptr(d_rows), caps, apt.Contrast.HISTOGRAM, ptr(d_img)),
@@ -131,6 +182,34 @@ def main():
             call()
         plan.synchronize()
         wall = (time.perf_counter() - t0) / args.calls
+        if name in png_channels:
+            # the whole product: the call, the lengths, and the encoded bytes on the host
+            t0 = time.perf_counter()
+            for _ in range(args.calls):
+                call()
+                sizes = plan.png_sizes(RECORDINGS)
+                files = [d_png[i][:sizes[i]].cpu() for i in range(RECORDINGS)]
+            wall_png = (time.perf_counter() - t0) / args.calls
+            # the path without the encoder: the raw image to the host, Pillow's save() there (one thread)
+            ch = png_channels[name]
+            shape = (rows, 2080, 4) if ch == 4 else (rows, 2080)
+            host = {"default": [], "level1": []}
+            copy = []
+            for i in range(3):
+                t0 = time.perf_counter()
+                px = d_img[i][:rows * 2080 * ch].cpu().numpy().reshape(shape)
+                copy.append(time.perf_counter() - t0)
+                host["default"].append(pillow_save(px)[0])
+                host["level1"].append(pillow_save(px, compress_level=1)[0])
+            t_copy, t6, t1 = np.median(copy), np.median(host["default"]), np.median(host["level1"])
+            per_rec = wall_png / RECORDINGS
+            print(f"{name:18s} {'wall+copy / rec':16s} {per_rec * 1e3:8.4f}   (one call of {RECORDINGS}, png_sizes and "
+                  f"{sum(len(f) for f in files) / RECORDINGS / 1e6:.2f} MB of file per recording copied to the host)")
+            print(f"{name:18s} {'host path / rec':16s} {(t_copy + t6) * 1e3:8.2f}   (raw copy {t_copy * 1e3:.2f} ms + "
+                  f"Pillow save() {t6 * 1e3:.1f} ms; compress_level=1: {t1 * 1e3:.1f} ms; medians of 3, one thread, "
+                  f"{cpu_name()})")
+            print(f"{name:18s} {'host / GPU':16s} {(t_copy + t6) / per_rec:8.1f}   (default level; level 1: "
+                  f"{(t_copy + t1) / per_rec:.1f})")
         plan.enable_timing(2)
         for _ in range(args.calls):
             call()
@@ -145,6 +224,10 @@ def main():
             print(f"{name:18s} {kname:16s} {ms:8.4f}   ({launches})")
         print(f"{name:18s} {'sum (events)':16s} {total:8.4f}")
         print(f"{name:18s} {'wall / rec':16s} {wall * 1e3 / RECORDINGS:8.4f}   (one call of {RECORDINGS}, timing off)")
+    if any(k in png_channels for k in variants):
+        plan.process_device_image(ptr(d_rows), caps, apt.Contrast.MINMAX, ptr(d_img), color=color)
+        plan.synchronize()
+        png_sizes_report(d_img[0][:rows * 2080 * 4].cpu().numpy().reshape(rows, 2080, 4))
     if "histogram_color_lab" not in variants:
         plan.close()
         return
