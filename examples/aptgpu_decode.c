@@ -3,6 +3,7 @@
  *
  *     aptgpu_decode in.wav out.pgm [contrast: telemetry|percent|minmax] [--no-sync]
  *                   [--histogram] [--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE] [--png]
+ *                   [--tle FILE --sat NAME (--start-ms N | --end-ms N)] [--rotate no|yes|orbit]
  *
  * What `noaa-apt in.wav -o out.png` does (main.rs:91-110, noaa_apt.rs:114-235): load -> decode ->
  * contrast limits -> 8-bit image, written as a binary PGM, or with --png as the PNG file the GPU
@@ -33,11 +34,14 @@ int main(int argc, char **argv)
 {
     if (argc < 3) {
         fprintf(stderr, "usage: %s in.wav out.pgm [telemetry|percent|minmax] [--no-sync] [--histogram] "
-                "[--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE] [--png]\n", argv[0]);
+                "[--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE] [--png]\n"
+                "       [--tle FILE --sat NAME (--start-ms N | --end-ms N)] [--rotate no|yes|orbit]\n", argv[0]);
         return 2;
     }
     int contrast = APTGPU_CONTRAST_PERCENT, sync = 1, lab = 0, png = 0;
-    const char *palette_path = NULL, *map_dir = NULL, *track_path = NULL;
+    const char *palette_path = NULL, *map_dir = NULL, *track_path = NULL, *tle_path = NULL, *sat = NULL;
+    int rotate = APTGPU_ROTATE_NO, ref_kind = -1;
+    long long ref_ms = 0;
     for (int i = 3; i < argc; ++i) {
         if (!strcmp(argv[i], "telemetry")) contrast = APTGPU_CONTRAST_TELEMETRY;
         else if (!strcmp(argv[i], "percent")) contrast = APTGPU_CONTRAST_PERCENT;
@@ -49,6 +53,14 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--palette") && i + 1 < argc) palette_path = argv[++i];
         else if (!strcmp(argv[i], "--map") && i + 1 < argc) map_dir = argv[++i];
         else if (!strcmp(argv[i], "--track") && i + 1 < argc) track_path = argv[++i];
+        else if (!strcmp(argv[i], "--tle") && i + 1 < argc) tle_path = argv[++i];
+        else if (!strcmp(argv[i], "--sat") && i + 1 < argc) sat = argv[++i];
+        else if (!strcmp(argv[i], "--start-ms") && i + 1 < argc) ref_kind = APTGPU_REF_TIME_START, ref_ms = atoll(argv[++i]);
+        else if (!strcmp(argv[i], "--end-ms") && i + 1 < argc) ref_kind = APTGPU_REF_TIME_END, ref_ms = atoll(argv[++i]);
+        else if (!strcmp(argv[i], "--rotate") && i + 1 < argc) {
+            const char *r = argv[++i];
+            rotate = !strcmp(r, "orbit") ? APTGPU_ROTATE_ORBIT : !strcmp(r, "yes") ? APTGPU_ROTATE_YES : APTGPU_ROTATE_NO;
+        }
     }
 
     /* the palette, decoded by the caller (the reference: image::open(..).into_rgb8(), processing.rs:115) */
@@ -109,7 +121,44 @@ int main(int argc, char **argv)
     aptgpu_image_result info;
     const int rgba = palette_path || map_dir;
     aptgpu_png_settings ps = {sizeof(aptgpu_png_settings), 0};
-    if (map_dir) {
+    if (tle_path) {
+        /* OrbitSettings: the track (and Rotate::Orbit) from the TLE, computed by the library; no track file */
+        char *tle = NULL;
+        FILE *t = fopen(tle_path, "rb");
+        long tn = 0;
+        if (t) { fseek(t, 0, SEEK_END); tn = ftell(t); fseek(t, 0, SEEK_SET); tle = malloc((size_t)tn + 1); }
+        if (!t || !tle || fread(tle, 1, (size_t)tn, t) != (size_t)tn || !sat || ref_kind < 0) {
+            fprintf(stderr, "--tle FILE needs a readable file, --sat NAME and --start-ms N or --end-ms N\n");
+            return 1;
+        }
+        tle[tn] = 0;
+        fclose(t);
+        aptgpu_map_layers *layers = NULL;
+        aptgpu_map_settings ms = {sizeof(aptgpu_map_settings), 0, 0.0, 1.0, 1.0};  /* config.rs:646-648 */
+        aptgpu_orbit_settings os;
+        memset(&os, 0, sizeof os);
+        os.struct_size = sizeof os;
+        os.sat_name = sat;
+        os.tle = tle;
+        os.ref_kind = ref_kind;
+        os.ref_unix_ms = ref_ms;
+        os.draw_map = map_dir ? &ms : NULL;
+        rc = APTGPU_OK;
+        if (map_dir) {
+            rc = aptgpu_map_layers_create(&layers);
+            if (rc == APTGPU_OK) rc = aptgpu_map_layers_load_dir(layers, map_dir, err, sizeof err);
+        }
+        if (rc == APTGPU_OK)
+            rc = aptgpu_process_image_orbit(&ctx, rows, n_rows_px, contrast, 0.98f, rotate,
+                                            palette_path ? &color : NULL, rgba ? 4 : 1, &os, layers,
+                                            png ? APTGPU_OUTPUT_PNG : APTGPU_OUTPUT_PIXELS, &ps, &image, &n_px, &info,
+                                            err, sizeof err);
+        aptgpu_map_layers_destroy(layers);
+        free(tle);
+    } else if (rotate == APTGPU_ROTATE_ORBIT) {
+        fprintf(stderr, "--rotate orbit needs --tle FILE --sat NAME and a time\n");
+        return 1;
+    } else if (map_dir) {
         /* the track: one (lat, lon) per image row, as map.rs:41-58 computes it with SGP4 */
         const size_t height = n_rows_px / 2080;
         double *track = malloc((height ? height : 1) * 2 * sizeof(double));
@@ -124,25 +173,25 @@ int main(int argc, char **argv)
         rc = aptgpu_map_layers_create(&layers);
         if (rc == APTGPU_OK) rc = aptgpu_map_layers_load_dir(layers, map_dir, err, sizeof err);
         if (rc == APTGPU_OK && png)
-            rc = aptgpu_process_image_png(&ctx, rows, n_rows_px, contrast, 0.98f, APTGPU_ROTATE_NO,
+            rc = aptgpu_process_image_png(&ctx, rows, n_rows_px, contrast, 0.98f, rotate,
                                           palette_path ? &color : NULL, 4, &ms, layers, track, &ps, &image, &n_px,
                                           &info, err, sizeof err);
         else if (rc == APTGPU_OK)
-            rc = aptgpu_process_image_map(&ctx, rows, n_rows_px, contrast, 0.98f, APTGPU_ROTATE_NO,
+            rc = aptgpu_process_image_map(&ctx, rows, n_rows_px, contrast, 0.98f, rotate,
                                           palette_path ? &color : NULL, 4, &ms, layers, track, &image, &n_px, &info,
                                           err, sizeof err);
         aptgpu_map_layers_destroy(layers);
         free(track);
     } else if (png)
-        rc = aptgpu_process_image_png(&ctx, rows, n_rows_px, contrast, 0.98f, APTGPU_ROTATE_NO,
+        rc = aptgpu_process_image_png(&ctx, rows, n_rows_px, contrast, 0.98f, rotate,
                                       palette_path ? &color : NULL, palette_path ? 4 : 1, NULL, NULL, NULL, &ps, &image,
                                       &n_px, &info, err, sizeof err);
     else if (palette_path || contrast == APTGPU_CONTRAST_HISTOGRAM)
-        rc = aptgpu_process_image(&ctx, rows, n_rows_px, contrast, 0.98f, APTGPU_ROTATE_NO,
+        rc = aptgpu_process_image(&ctx, rows, n_rows_px, contrast, 0.98f, rotate,
                                   palette_path ? &color : NULL, palette_path ? 4 : 1, &image, &n_px, &info, err,
                                   sizeof err);
     else
-        rc = aptgpu_process_gray(&ctx, rows, n_rows_px, contrast, 0.98f, APTGPU_ROTATE_NO, &image, &n_px, &info,
+        rc = aptgpu_process_gray(&ctx, rows, n_rows_px, contrast, 0.98f, rotate, &image, &n_px, &info,
                                  err, sizeof err);
     aptgpu_free(rows);
     if (rc != APTGPU_OK) { fprintf(stderr, "image stage failed (%d): %s\n", rc, err); return 1; }

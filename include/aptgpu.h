@@ -379,7 +379,8 @@ int aptgpu_find_sync(const aptgpu_context *ctx, const float *signal, size_t n,
 /* -> map_signal_u8, plus telemetry.rs, histogram equalisation (imageext.rs:21-45), palette */
 /* false colour (processing.rs:113-165) and the 180-degree channel rotation.  Equalisation */
 /* of a false-colour image (CIE Lab, imageext.rs:51-64) is opt-in                        */
-/* (APTGPU_COLOR_EQUALIZE_LAB); the map overlay from a caller-computed track (below).       */
+/* (APTGPU_COLOR_EQUALIZE_LAB); the map overlay from a caller-computed track or from a TLE  */
+/* (below).                                                                                  */
 /* aptgpu_process_gray / aptgpu_plan_process_device: the grayscale image of the first     */
 /* three contrasts; aptgpu_process_image / aptgpu_plan_process_device_image: every        */
 /* contrast, optional false colour, gray or RGBA output.                                   */
@@ -392,6 +393,8 @@ int aptgpu_find_sync(const aptgpu_context *ctx, const float *signal, size_t n,
                                        (aptgpu_process_image / aptgpu_plan_process_device_image only) */
 #define APTGPU_ROTATE_NO 0          /* Rotate::No  */
 #define APTGPU_ROTATE_YES 1         /* Rotate::Yes  src/noaa_apt.rs:228-231, processing.rs:21-37 */
+#define APTGPU_ROTATE_ORBIT 2       /* Rotate::Orbit: the *_orbit entry points only (they decide from the satellite's
+                                       pass, processing.rs:40-81); everywhere else APTGPU_ERR_UNSUPPORTED */
 
 /* What the image stage found; also the telemetry::Telemetry values (src/telemetry.rs:19-23). */
 typedef struct aptgpu_image_result {
@@ -399,7 +402,7 @@ typedef struct aptgpu_image_result {
     int32_t reason;          /* 1 zero-length signal (dsp.rs:40-44), 2 too short for telemetry
                                 (telemetry.rs:199-203), 3 no low bucket (misc.rs:172 panics),
                                 4 the decode before it failed, 5-8 the map overlay's limits
-                                (APTGPU_MAP_REASON_*), 9 APTGPU_PNG_REASON_CAPACITY */
+                                (APTGPU_MAP_REASON_*), 9 APTGPU_PNG_REASON_CAPACITY, 10 APTGPU_SAT_REASON_SGP4 */
     uint32_t height;         /* rows of 2080 px */
     uint32_t telemetry_row;  /* best frame start, telemetry.rs:196,228-230 */
     float low, high;         /* the contrast limits used by map_signal_u8 */
@@ -479,8 +482,8 @@ int aptgpu_plan_process_device_image(aptgpu_plan *plan, int count, const float *
 int aptgpu_plan_image_results(aptgpu_plan *plan, int count, aptgpu_image_result *results);
 
 /* ---- the map overlay (map.rs:14-200) ----
- * SGP4 stays with the caller: it passes the satellite's (lat, lon) for every image row, in radians, as map.rs:41-58
- * computes them.  The overlay draws over the RGBA image before the rotation, as the reference does.  Errors found on
+ * The caller passes the satellite's (lat, lon) for every image row, in radians, as map.rs:41-58 computes them; or
+ * it passes the TLE and the time and the track is computed on the GPU ("the satellite track" below).  The overlay draws over the RGBA image before the rotation, as the reference does.  Errors found on
  * the device land in aptgpu_image_result (status APTGPU_ERR_INTERNAL) with these reasons; the image is then left
  * without the overlay: */
 #define APTGPU_MAP_REASON_OVERFLOW 5  /* more than APTGPU_MAP_MAX_FRAGMENTS fragments in one image */
@@ -586,6 +589,67 @@ int aptgpu_plan_process_device_image_png(aptgpu_plan *plan, int count, const flo
                                          const double *const *sat_positions, const size_t *n_positions,
                                          uint8_t *const *d_images, const aptgpu_png_settings *png,
                                          uint8_t *const *d_png, const size_t *png_cap, char *err, size_t err_cap);
+
+/* ---- the satellite track (map.rs:28-58, processing.rs:40-81) ----
+ * noaa_apt::OrbitSettings: the satellite's name, the TLE text and the reference time.  SGP4 (near earth, WGS-72), the
+ * sidereal time and the geodetic sub-point of every image row, t = start + 500 ms * row, are computed in f64: by a
+ * kernel, one thread per row, where the image height is known, and by the same source text on the CPU.  The
+ * algorithm is Vallado's 2006 SGP4 as the `satellite` crate ports it; the parity statement is the reference's own
+ * known-answer test (geo.rs:225-233), not bit equality with the crate. */
+#define APTGPU_REF_TIME_START 0 /* RefTime::Start(t): row 0 is at t */
+#define APTGPU_REF_TIME_END 1   /* RefTime::End(t): row 0 is at t - 500 ms * height (map.rs:45) */
+#define APTGPU_SAT_REASON_SGP4 10 /* aptgpu_image_result.reason: SGP4 returned an error for a row of the image (the
+                                     satellite decayed, eccentricity out of range: the reference panics there); the
+                                     image is left without the overlay */
+typedef struct aptgpu_orbit_settings {
+    uint32_t struct_size;  /* sizeof(aptgpu_orbit_settings) */
+    uint32_t flags;        /* 0; any set bit is APTGPU_ERR_INVALID */
+    const char *sat_name;  /* SatName::to_string(): "NOAA 15", "NOAA 18", "NOAA 19" (any title line of the text) */
+    const char *tle;       /* custom_tle: title / line 1 / line 2 per satellite.  NULL is APTGPU_ERR_UNSUPPORTED: the
+                              reference then downloads the current TLE, which this library does not do */
+    int32_t ref_kind;      /* APTGPU_REF_TIME_START / APTGPU_REF_TIME_END */
+    int32_t reserved;      /* 0 */
+    int64_t ref_unix_ms;   /* the DateTime<Utc> as milliseconds since 1970-01-01T00:00:00Z */
+    const aptgpu_map_settings *draw_map; /* nullable: then no map, only the rotation decision */
+} aptgpu_orbit_settings;
+/* Errors of every entry point that takes the struct: a name that is not in the text is APTGPU_ERR_INTERNAL with the
+ * reference's `Satellite "NAME" not found in TLE` (a malformed record is skipped, as the reference ignores
+ * parse_multiple's errors); an orbit with a period of 225 minutes or more needs the deep-space branch:
+ * APTGPU_ERR_UNSUPPORTED; an SGP4 error return is APTGPU_ERR_INTERNAL with its number and meaning. */
+/* The track of an image of `height` rows, computed by the kernel and copied back: latlon_out receives height pairs
+ * (lat, lon) in radians, longitude in [-pi, pi]. */
+int aptgpu_sat_track(const aptgpu_context *ctx, const aptgpu_orbit_settings *orbit, uint32_t height,
+                     double *latlon_out, char *err, size_t err_cap);
+/* The same on the CPU (no GPU needed): the values a caller of aptgpu_process_image_map would compute itself. */
+int aptgpu_sat_track_host(const aptgpu_orbit_settings *orbit, uint32_t height, double *latlon_out, char *err,
+                          size_t err_cap);
+/* processing::south_to_north_pass (CPU): the sub-points at the reference time as given (Start and End alike, as the
+ * reference) and 2 s later, geo::azimuth between them, *out = |azimuth| < pi/2: the satellite is heading north.  (The
+ * reference compares `azimuth < PI/4 || azimuth > 3*PI/4`, which an atan2 result meets on the northbound and the
+ * southbound stretches of a retrograde orbit alike; this returns what that function documents.  DESIGN.md §14.) */
+int aptgpu_south_to_north_pass(const aptgpu_orbit_settings *orbit, int *out, char *err, size_t err_cap);
+
+#define APTGPU_OUTPUT_PIXELS 0 /* *out: the image, height*2080*channels bytes */
+#define APTGPU_OUTPUT_PNG 1    /* *out: the PNG file (png nullable = flags 0) */
+/* process() with the reference's OrbitSettings: aptgpu_process_image, then the map overlay when orbit->draw_map is set
+ * (layers required then, channels 4; status 0.5 "Drawing map"), then optionally the PNG encoder.  rotate may be
+ * APTGPU_ROTATE_ORBIT: decided by aptgpu_south_to_north_pass before anything is launched (status 0.90 "Rotating
+ * output image" only when it rotates). */
+int aptgpu_process_image_orbit(const aptgpu_context *ctx, const float *signal, size_t n, int contrast, float percent,
+                               int rotate, const aptgpu_color_settings *color, int channels,
+                               const aptgpu_orbit_settings *orbit, const aptgpu_map_layers *layers, int output,
+                               const aptgpu_png_settings *png, uint8_t **out, size_t *n_out,
+                               aptgpu_image_result *info, char *err, size_t err_cap);
+/* aptgpu_plan_process_device_image_png with the track computed on each recording's stream: orbit[i] is recording i's
+ * satellite and time (RefTime::End is resolved on the device, where the height is known).  draw_map must be set for
+ * every recording or for none; layers is shared.  d_png (with png and png_cap) is nullable: then no PNG.  A
+ * propagation error in any row is reported through aptgpu_plan_image_results (APTGPU_SAT_REASON_SGP4). */
+int aptgpu_plan_process_device_image_orbit(aptgpu_plan *plan, int count, const float *const *d_rows,
+                                           const size_t *rows_cap, int contrast, float percent, int rotate,
+                                           const aptgpu_color_settings *color, int channels,
+                                           const aptgpu_orbit_settings *const *orbit, const aptgpu_map_layers *layers,
+                                           uint8_t *const *d_images, const aptgpu_png_settings *png,
+                                           uint8_t *const *d_png, const size_t *png_cap, char *err, size_t err_cap);
 
 /* ====================================================================== */
 /* 5. WAV ingest in front of decode()                 */

@@ -19,8 +19,11 @@ Names, argument meaning and error behaviour follow the reference:
     colour)                                                noaa_apt.rs:63-71
     ColorSettings(equalize_lab=True), lab_from_rgb,        imageext.rs:50-143, the lab crate 0.11.0
     lab_to_rgb (Histogram + colour in CIE Lab)
-    process(orbit=MapOverlay(...)): the map overlay,       map.rs:14-200 (SGP4 stays with the caller: it passes
-    MapSettings, MapLayers, read_shapefile                 the per-row track), noaa_apt.rs:84-91
+    process(orbit=MapOverlay(...)): the map overlay,       map.rs:14-200 (from a track the caller passes),
+    MapSettings, MapLayers, read_shapefile                 noaa_apt.rs:84-91
+    process(orbit=OrbitSettings(...)), Rotate.ORBIT,       noaa_apt.rs:58-108, map.rs:28-58, processing.rs:40-81
+    SatName, RefTime, sat_track, sat_track_host,           (SGP4 on the GPU, one thread per image row)
+    south_to_north_pass
     process(png=True), encode_png, png_bound: the PNG      main.rs, the Decode arm: img.save(&output_filename)
     file of the image, encoded on the GPU
     percent, get_min, get_max, map_signal_u8               /root/reference/src/misc.rs:119, dsp.rs:20-54
@@ -40,6 +43,7 @@ from .api import (  # noqa: F401
     MAP_STATES, MAP_COUNTRIES, MAP_LAKES,
     get_min, get_max, percent, map_signal_u8, read_telemetry, process, lab_from_rgb, lab_to_rgb,
     encode_png, png_bound, PNG_REASON_CAPACITY,
+    SatName, RefTime, OrbitSettings, sat_track, sat_track_host, south_to_north_pass, SAT_REASON_SGP4,
     Plan, PlanInfo, Result, KernelTime, decode_batch, BatchStats, host_alloc_f32, host_free,
     lib, lib_path, use_library, build, device_count, version, abi_version, cache_clear, cache_info, host_affinity, host_affinity_from_sysfs,
     MODE_STRICT, MODE_GENERIC, MODE_FP16_TAPS, MODE_FAST,

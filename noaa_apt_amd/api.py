@@ -142,6 +142,12 @@ class _CPngSettings(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class _COrbitSettings(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("sat_name", C.c_char_p), ("tle", C.c_char_p),
+                ("ref_kind", C.c_int32), ("reserved", C.c_int32), ("ref_unix_ms", C.c_int64),
+                ("draw_map", C.c_void_p)]
+
+
 class _CMapSettings(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("yaw", C.c_double),
                 ("hscale", C.c_double), ("vscale", C.c_double)]
@@ -322,6 +328,15 @@ def lib():
                                                        cms, vp, C.POINTER(_f64p), C.POINTER(sz), C.POINTER(vp),
                                                        C.c_char_p, sz]
     cps = C.POINTER(_CPngSettings)
+    cos = C.POINTER(_COrbitSettings)
+    L.aptgpu_sat_track.argtypes = [cp, cos, u32, _f64p, C.c_char_p, sz]
+    L.aptgpu_sat_track_host.argtypes = [cos, u32, _f64p, C.c_char_p, sz]
+    L.aptgpu_south_to_north_pass.argtypes = [cos, C.POINTER(C.c_int), C.c_char_p, sz]
+    L.aptgpu_process_image_orbit.argtypes = [cp, _f32p, sz, i32, f, i32, ccs, i32, cos, vp, i32, cps,
+                                             C.POINTER(_u8p), C.POINTER(sz), C.POINTER(ImageResult), C.c_char_p, sz]
+    L.aptgpu_plan_process_device_image_orbit.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz), i32, f, i32, ccs, i32,
+                                                         C.POINTER(cos), vp, C.POINTER(vp), cps, C.POINTER(vp),
+                                                         C.POINTER(sz), C.c_char_p, sz]
     L.aptgpu_png_bound.argtypes = [u32, u32, i32]
     L.aptgpu_png_bound.restype = sz
     L.aptgpu_encode_png.argtypes = [cp, _u8p, u32, u32, i32, cps, C.POINTER(_u8p), C.POINTER(sz), C.c_char_p, sz]
@@ -724,7 +739,8 @@ class Contrast:
 
 
 class Rotate:
-    """noaa_apt::Rotate (noaa_apt.rs:52-60); Orbit needs orbit propagation (out of scope)."""
+    """noaa_apt::Rotate (noaa_apt.rs:52-60).  ORBIT decides from the satellite's pass (south_to_north_pass) and
+    needs process(orbit=OrbitSettings(...))."""
     NO, YES, ORBIT = 0, 1, 2
 
 
@@ -888,8 +904,9 @@ class MapSettings:
 
 
 class MapOverlay:
-    """What process() needs to draw the map (the `orbit` argument): the satellite's (lat, lon) in radians for every
-    image row, as map.rs:41-58 computes them with SGP4 (the caller's job), the settings and the layers."""
+    """What process() needs to draw the map from a track the caller has (the `orbit` argument): the satellite's
+    (lat, lon) in radians for every image row, as map.rs:41-58 computes them with SGP4 (sat_track_host() does; an
+    OrbitSettings leaves it to the GPU), the settings and the layers."""
 
     def __init__(self, sat_positions, settings=None, layers=None):
         self.sat_positions = np.ascontiguousarray(np.asarray(sat_positions, dtype=np.float64).reshape(-1, 2))
@@ -897,6 +914,91 @@ class MapOverlay:
         if not isinstance(layers, MapLayers):
             raise InvalidError("MapOverlay needs a MapLayers")
         self.layers = layers
+
+
+class SatName:
+    """noaa_apt::SatName with its to_string() (noaa_apt.rs:95-108)."""
+    NOAA15, NOAA18, NOAA19 = "NOAA 15", "NOAA 18", "NOAA 19"
+
+
+class RefTime:
+    """noaa_apt::RefTime (noaa_apt.rs:58-61): the time of the image's first row (Start) or of the row after its last
+    (End: the start is 500 ms * height earlier, map.rs:45).  `t`: a timezone-aware datetime (truncated to
+    milliseconds) or integer Unix milliseconds."""
+    START, END = 0, 1
+
+    def __init__(self, kind, t):
+        if kind not in (RefTime.START, RefTime.END):
+            raise InvalidError("RefTime: kind is RefTime.START or RefTime.END")
+        if hasattr(t, "utcoffset"):
+            import datetime as _dt
+            if t.utcoffset() is None:
+                raise InvalidError("RefTime: the datetime must be timezone-aware")
+            d = t - _dt.datetime(1970, 1, 1, tzinfo=_dt.timezone.utc)
+            t = (d.days * 86400 + d.seconds) * 1000 + d.microseconds // 1000
+        elif not isinstance(t, (int, np.integer)):
+            raise InvalidError("RefTime: a timezone-aware datetime or integer Unix milliseconds")
+        self.kind, self.unix_ms = kind, int(t)
+
+    @staticmethod
+    def Start(t):  # noqa: N802 - the reference's variant name
+        return RefTime(RefTime.START, t)
+
+    @staticmethod
+    def End(t):  # noqa: N802
+        return RefTime(RefTime.END, t)
+
+
+class OrbitSettings:
+    """noaa_apt::OrbitSettings (noaa_apt.rs:75-82): satellite, TLE text, reference time and, to draw the map, a
+    MapSettings.  custom_tle=None raises UnsupportedError (the reference downloads the current TLE then)."""
+
+    def __init__(self, sat_name, custom_tle, ref_time, draw_map=None):
+        if not isinstance(ref_time, RefTime):
+            raise InvalidError("OrbitSettings: ref_time is RefTime.Start(t) or RefTime.End(t)")
+        if draw_map is not None and not isinstance(draw_map, MapSettings):
+            raise InvalidError("OrbitSettings: draw_map is a MapSettings or None")
+        self.sat_name, self.custom_tle, self.ref_time, self.draw_map = str(sat_name), custom_tle, ref_time, draw_map
+
+    def _c(self):
+        """(struct, keepalive): the struct points into the keepalive objects"""
+        name = self.sat_name.encode()
+        tle = self.custom_tle.encode() if isinstance(self.custom_tle, str) else self.custom_tle
+        cms = self.draw_map._c() if self.draw_map is not None else None
+        c = _COrbitSettings(C.sizeof(_COrbitSettings), 0, name, tle, self.ref_time.kind, 0, self.ref_time.unix_ms,
+                            C.cast(C.pointer(cms), C.c_void_p) if cms is not None else None)
+        return c, (name, tle, cms)
+
+
+def sat_track(orbit: OrbitSettings, height, context=None):
+    """The (lat, lon) in radians of the satellite for each of `height` image rows (map.rs:41-58), computed by the
+    GPU kernel: a height x 2 f64 array."""
+    out = np.empty((int(height), 2), np.float64)
+    c, _keep = orbit._c()
+    cctx = (context or Context())._c()
+    err = C.create_string_buffer(_ERRCAP)
+    _check(lib().aptgpu_sat_track(C.byref(cctx), C.byref(c), int(height), out.ctypes.data_as(_f64p), err, _ERRCAP), err)
+    return out
+
+
+def sat_track_host(orbit: OrbitSettings, height):
+    """sat_track on the CPU, with the same source text (no GPU needed)."""
+    out = np.empty((int(height), 2), np.float64)
+    c, _keep = orbit._c()
+    err = C.create_string_buffer(_ERRCAP)
+    _check(lib().aptgpu_sat_track_host(C.byref(c), int(height), out.ctypes.data_as(_f64p), err, _ERRCAP), err)
+    return out
+
+
+def south_to_north_pass(orbit: OrbitSettings) -> bool:
+    """processing::south_to_north_pass (processing.rs:40-81), CPU: whether Rotate.ORBIT rotates the image.  True when
+    the sub-point's heading over the 2 s after the reference time is northward (|azimuth| < pi/2); the reference's
+    own comparison is true for southbound NOAA passes too."""
+    c, _keep = orbit._c()
+    out = C.c_int(0)
+    err = C.create_string_buffer(_ERRCAP)
+    _check(lib().aptgpu_south_to_north_pass(C.byref(c), C.byref(out), err, _ERRCAP), err)
+    return bool(out.value)
 
 
 class Telemetry:
@@ -972,6 +1074,7 @@ def read_telemetry(context, signal):  # telemetry.rs:125
     return Telemetry._from(r)
 
 
+SAT_REASON_SGP4 = 10  # ImageResult.reason: SGP4 failed for a row of the image; no overlay was drawn
 PNG_REASON_CAPACITY = 9  # ImageResult.reason: the PNG buffer is smaller than the file (png_bytes = its length)
 
 
@@ -1001,7 +1104,7 @@ def encode_png(image, context=None) -> bytes:
 
 
 def process(context, signal, contrast_adjustment, rotate=Rotate.NO, color=None, orbit=None,
-            return_info=False, png=False):
+            return_info=False, png=False, layers=None):
     """noaa_apt::process (noaa_apt.rs:132-235).  Returns the height x 2080 u8
     gray image, or with `color` (a ColorSettings) the height x 2080 x 4 RGBA image of the reference's
     false colour (A = 255).  Contrast.HISTOGRAM equalises each channel half of the gray image; together with
@@ -1009,7 +1112,14 @@ def process(context, signal, contrast_adjustment, rotate=Rotate.NO, color=None, 
     `orbit` may be a MapOverlay: the map is drawn over the RGBA image (height x 2080 x 4, also without colour).
     png=True: the image is also encoded on the GPU and the PNG file's bytes are returned instead of the pixels
     (what `img.save()` writes in main.rs; gray without colour and map, RGBA with).
-    Unsupported: any other `orbit`, Rotate.ORBIT, and HISTOGRAM with colour without equalize_lab."""
+    `orbit` may also be the reference's OrbitSettings: the track is then computed on the GPU with SGP4; with
+    draw_map set the map is drawn (`layers`, a MapLayers, is required then: the reference finds its shapefiles
+    itself), and Rotate.ORBIT rotates south-to-north passes.
+    Unsupported: any other `orbit`, Rotate.ORBIT without an OrbitSettings (the reference only warns and does not
+    rotate; with a MapOverlay too: a bare track carries no time to decide with), and HISTOGRAM with colour without
+    equalize_lab."""
+    if isinstance(orbit, OrbitSettings):
+        return _process_image_orbit(context, signal, contrast_adjustment, rotate, color, return_info, orbit, layers, png)
     if png:
         if orbit is not None and not isinstance(orbit, MapOverlay):
             raise UnsupportedError("orbit: only a MapOverlay (the map overlay) is served on the GPU path")
@@ -1072,6 +1182,34 @@ def _process_image(context, signal, contrast_adjustment, rotate, color, return_i
                                           C.byref(n), C.byref(info), err, _ERRCAP), err)
     out = _take(img, n.value, np.uint8)
     out = out.reshape(-1, PX_PER_ROW, 4) if channels == 4 else out.reshape(-1, PX_PER_ROW)
+    return (out, info) if return_info else out
+
+
+def _process_image_orbit(context, signal, contrast_adjustment, rotate, color, return_info, orbit, layers, png):
+    if color is not None and not isinstance(color, ColorSettings):
+        raise UnsupportedError("color must be a ColorSettings")
+    if orbit.draw_map is not None:
+        if not isinstance(layers, MapLayers):
+            raise InvalidError("OrbitSettings.draw_map needs layers=MapLayers")
+        layers._colors(orbit.draw_map)
+    cctx = (context or Context())._c()
+    x, xp = _as_f32(signal)
+    kind, p = Contrast._c(contrast_adjustment)
+    channels = 4 if color is not None or orbit.draw_map is not None else 1
+    ccol = color._c() if color is not None else None
+    corb, _keep = orbit._c()
+    cps = _CPngSettings(C.sizeof(_CPngSettings), 0)
+    img, n, info = _u8p(), C.c_size_t(), ImageResult()
+    err = C.create_string_buffer(_ERRCAP)
+    _check(lib().aptgpu_process_image_orbit(
+        C.byref(cctx), xp, x.size, kind, p, int(rotate), C.byref(ccol) if ccol is not None else None, channels,
+        C.byref(corb), layers._p if orbit.draw_map is not None else None, 1 if png else 0, C.byref(cps), C.byref(img),
+        C.byref(n), C.byref(info), err, _ERRCAP), err)
+    out = _take(img, n.value, np.uint8)
+    if png:
+        out = out.tobytes()
+    else:
+        out = out.reshape(-1, PX_PER_ROW, 4) if channels == 4 else out.reshape(-1, PX_PER_ROW)
     return (out, info) if return_info else out
 
 
@@ -1218,7 +1356,7 @@ class Plan:
 
     def process_device_image(self, d_rows: Sequence[int], rows_cap: Sequence[int], contrast_adjustment,
                              d_images: Sequence[int], rotate=Rotate.NO, color=None, channels=None, map=None,  # noqa: A002
-                             png=None):
+                             png=None, orbit=None, layers=None):
         """process() with every contrast (HISTOGRAM too) and optional false colour (a ColorSettings) for the
         recordings of the last decode_device call, chained on the device behind their decode.  d_images[i]
         holds rows_cap[i] * 2080 * channels bytes; channels defaults to 4 (RGBA) with colour or map, 1 (gray)
@@ -1227,15 +1365,44 @@ class Plan:
         png: (d_png, png_cap), device pointers and their capacities in bytes, one per recording: each image is then
         also encoded as a PNG file on its stream (png_bound(2080, rows_cap[i], channels) bytes always suffice); the
         lengths arrive through png_sizes().  A capacity below the file's length is reported in image_results()
-        (reason PNG_REASON_CAPACITY, png_bytes = the length needed) and nothing is written."""
+        (reason PNG_REASON_CAPACITY, png_bytes = the length needed) and nothing is written.
+        orbit (instead of map): an OrbitSettings, or one per recording; each recording's track is computed on its
+        stream (RefTime.End from the height the device found) and Rotate.ORBIT is decided per recording.  draw_map
+        must be set for all or none (`layers` required then); an SGP4 error in a row is reported in image_results()
+        (reason SAT_REASON_SGP4) and that image comes back without the overlay."""
         if color is not None and not isinstance(color, ColorSettings):
             raise UnsupportedError("color must be a ColorSettings")
-        if channels is None:
-            channels = 4 if color is not None or map is not None else 1
         k = len(d_rows)
+        orbits = None
+        if orbit is not None:
+            if map is not None:
+                raise InvalidError("map and orbit exclude each other")
+            orbits = [orbit] * k if isinstance(orbit, OrbitSettings) else list(orbit)
+            if len(orbits) != k or not all(isinstance(o, OrbitSettings) for o in orbits):
+                raise InvalidError("orbit: an OrbitSettings or one per recording")
+        drawn = bool(orbits) and orbits[0].draw_map is not None
+        if channels is None:
+            channels = 4 if color is not None or map is not None or drawn else 1
         kind, p = Contrast._c(contrast_adjustment)
         ccol = color._c() if color is not None else None
         err = C.create_string_buffer(_ERRCAP)
+        if orbits is not None:
+            if drawn:
+                if not isinstance(layers, MapLayers):
+                    raise InvalidError("OrbitSettings.draw_map needs layers=MapLayers")
+                layers._colors(orbits[0].draw_map)
+            cs = [o._c() for o in orbits]
+            ptrs = (C.POINTER(_COrbitSettings) * k)(*[C.pointer(c) for c, _ in cs])
+            cps = _CPngSettings(C.sizeof(_CPngSettings), 0)
+            d_png, png_cap = png if png is not None else (None, None)
+            if png is not None and (len(d_png) != k or len(png_cap) != k):
+                raise InvalidError("png: (d_png, png_cap) with one entry per recording")
+            _check(lib().aptgpu_plan_process_device_image_orbit(
+                self._p, k, (C.c_void_p * k)(*d_rows), (C.c_size_t * k)(*rows_cap), kind, p, int(rotate),
+                C.byref(ccol) if ccol is not None else None, int(channels), ptrs, layers._p if drawn else None,
+                (C.c_void_p * k)(*d_images), C.byref(cps), (C.c_void_p * k)(*d_png) if png is not None else None,
+                (C.c_size_t * k)(*[int(c) for c in png_cap]) if png is not None else None, err, _ERRCAP), err)
+            return
         if png is not None:
             d_png, png_cap = png
             if len(d_png) != k or len(png_cap) != k:

@@ -8,7 +8,9 @@
 #include "apt_capi_util.hpp"
 #include "apt_kernels_color.hpp"
 #include "apt_kernels_png.hpp"
+#include "apt_kernels_track.hpp"
 #include "apt_map.hpp"
+#include "apt_sat.hpp"
 
 // the opaque handle of include/aptgpu.h
 struct aptgpu_map_layers {
@@ -31,6 +33,7 @@ const char *kMapOverflow = "map overlay: more than APTGPU_MAP_MAX_FRAGMENTS (2^2
 const char *kMapWalk = "map overlay: a segment's walk is longer than APTGPU_MAP_MAX_WALK (2^20) steps or has a non-finite end";
 const char *kMapPixel = "map overlay: more than APTGPU_MAP_MAX_PIXEL_FRAGMENTS (2^16) fragments on one pixel";
 const char *kMapCount = "map overlay: the number of satellite positions differs from the image height";
+const char *kSatSgp4 = "satellite track: SGP4 failed for a row of the image (APTGPU_SAT_REASON_SGP4)";
 const char *kPngCapacity = "PNG encoding: the output buffer is smaller than the file (APTGPU_PNG_REASON_CAPACITY)";
 const char *kChannelNames[9] = {"1", "2", "3a", "4", "5", "3b", "Unknown", "Unknown", "Unknown"};
 
@@ -80,6 +83,7 @@ void throw_for(const ImageResult &r, int contrast)
     case apt::map::kReasonWalk: throw Error{ErrorKind::Internal, kMapWalk};
     case apt::map::kReasonCount: throw Error{ErrorKind::Internal, kMapCount};
     case apt::map::kReasonPixel: throw Error{ErrorKind::Internal, kMapPixel};
+    case apt::sat::kReasonSgp4: throw Error{ErrorKind::Internal, kSatSgp4};
     case apt::png::kReasonCapacity: throw Error{ErrorKind::Internal, kPngCapacity};
     default: throw Error{ErrorKind::Internal, "image stage failed"};
     }
@@ -193,7 +197,7 @@ bool color_args(int contrast, int rotate, const aptgpu_color_settings *color, in
     if (contrast < APTGPU_CONTRAST_TELEMETRY || contrast > APTGPU_CONTRAST_HISTOGRAM)
         throw Error{ErrorKind::Invalid, "unknown contrast adjustment"};
     if (rotate != APTGPU_ROTATE_NO && rotate != APTGPU_ROTATE_YES)
-        throw Error{ErrorKind::Unsupported, "Rotate::Orbit needs orbit propagation (host side, out of scope)"};
+        throw Error{ErrorKind::Unsupported, "Rotate::Orbit needs the satellite and the time: aptgpu_orbit_settings, the *_orbit entry points"};
     if (channels != 1 && channels != 4) throw Error{ErrorKind::Invalid, "channels must be 1 (gray) or 4 (RGBA)"};
     if (!color) return false;
     if (color->struct_size < sizeof(aptgpu_color_settings) || !color->palette_rgb)
@@ -263,6 +267,43 @@ apt::map::Colors map_colors(const apt::map::Layers &l)
     return apt::map::Colors{{l.color[0], l.color[1], l.color[2]}};
 }
 
+// One recording's aptgpu_orbit_settings after its checks: the initialised satellite and the reference time for the
+// kernels, the map settings (null: no overlay) and Rotate::Orbit's outcome.
+struct SatCall {
+    apt::sat::TrackCall call;
+    const aptgpu_map_settings *draw_map;
+};
+
+// The checks of aptgpu_orbit_settings, then parse + sgp4init (cached for the last TLE and name).
+SatCall orbit_args(const aptgpu_orbit_settings *orbit)
+{
+    if (!orbit || orbit->struct_size < sizeof(aptgpu_orbit_settings))
+        throw Error{ErrorKind::Invalid, "aptgpu_orbit_settings: struct_size not set"};
+    if (orbit->flags) throw Error{ErrorKind::Invalid, "aptgpu_orbit_settings: unknown flags"};
+    if (!orbit->sat_name) throw Error{ErrorKind::Invalid, "aptgpu_orbit_settings: sat_name not set"};
+    if (orbit->ref_kind != APTGPU_REF_TIME_START && orbit->ref_kind != APTGPU_REF_TIME_END)
+        throw Error{ErrorKind::Invalid, "aptgpu_orbit_settings: unknown ref_kind"};
+    if (!orbit->tle)
+        throw Error{ErrorKind::Unsupported,
+                    "aptgpu_orbit_settings: tle is NULL (the reference then downloads the current TLE, "
+                    "misc::get_current_tle; pass the text)"};
+    if (orbit->draw_map && orbit->draw_map->struct_size < sizeof(aptgpu_map_settings))
+        throw Error{ErrorKind::Invalid, "aptgpu_map_settings: struct_size not set"};
+    SatCall c{};
+    c.call.rec = apt::sat::satrec_for(orbit->tle, orbit->sat_name);
+    c.call.ref_ms = orbit->ref_unix_ms;
+    c.call.ref_is_end = orbit->ref_kind == APTGPU_REF_TIME_END;
+    c.draw_map = orbit->draw_map;
+    return c;
+}
+
+// Rotate::Orbit -> Yes / No (noaa_apt.rs:229-234), before anything is launched
+int resolve_rotate(int rotate, const SatCall &c)
+{
+    if (rotate != APTGPU_ROTATE_ORBIT) return rotate;
+    return apt::sat::south_to_north_pass(c.call.rec, c.call.ref_ms) ? APTGPU_ROTATE_YES : APTGPU_ROTATE_NO;
+}
+
 // The checks of the PNG entry points' settings (nullable: flags 0).
 void png_args(const aptgpu_png_settings *png)
 {
@@ -299,7 +340,7 @@ void png_to_host(hipStream_t s, const uint8_t *d_png, size_t len, uint8_t **png_
 int process_image(const aptgpu_context *ctx, const float *signal, size_t n, int contrast, float percent, int rotate,
                   const aptgpu_color_settings *color, int channels, const MapCall *map, const double *positions,
                   uint8_t **image_out, size_t *n_out, aptgpu_image_result *info, char *err, size_t err_cap,
-                  bool png = false)
+                  bool png = false, const apt::sat::TrackCall *sat = nullptr)
 {
     if ((!signal && n) || !image_out || !n_out) return APTGPU_ERR_INVALID;
     *image_out = nullptr;
@@ -347,10 +388,16 @@ int process_image(const aptgpu_context *ctx, const float *signal, size_t n, int 
         if (map) {
             const size_t height = n / 2080;
             map_dev.prepare(s, *map->layers, height);
-            map_dev.upload_track(s, positions, height);
-            apt::map::image_map_overlay(s, map_dev, map_scalars(*map, positions, height), map_colors(*map->layers),
-                                        static_cast<uint32_t>(height), rotate == APTGPU_ROTATE_YES, d_img.ptr,
-                                        c.d_info.ptr);
+            if (sat) {
+                apt::map::image_map_overlay_sat(s, map_dev, *sat, map->settings->yaw, map->settings->hscale,
+                                                map->settings->vscale, map_colors(*map->layers),
+                                                rotate == APTGPU_ROTATE_YES, d_img.ptr, c.d_info.ptr);
+            } else {
+                map_dev.upload_track(s, positions, height);
+                apt::map::image_map_overlay(s, map_dev, map_scalars(*map, positions, height),
+                                            map_colors(*map->layers), static_cast<uint32_t>(height),
+                                            rotate == APTGPU_ROTATE_YES, d_img.ptr, c.d_info.ptr);
+            }
         }
         apt::DeviceBuffer<char> pws;
         apt::DeviceBuffer<uint8_t> d_png;
@@ -385,13 +432,30 @@ int process_image(const aptgpu_context *ctx, const float *signal, size_t n, int 
 int plan_process_image(aptgpu_plan *plan, int count, const float *const *d_rows, const size_t *rows_cap, int contrast,
                        float percent, int rotate, const aptgpu_color_settings *color, int channels, const MapCall *map,
                        const double *const *positions, const size_t *n_positions, uint8_t *const *d_images, char *err,
-                       size_t err_cap, uint8_t *const *d_png = nullptr, const size_t *png_cap = nullptr)
+                       size_t err_cap, uint8_t *const *d_png = nullptr, const size_t *png_cap = nullptr,
+                       const aptgpu_orbit_settings *const *orbit = nullptr, const apt::map::Layers *orbit_layers = nullptr)
 {
     if (!plan || count < 0 || !d_rows || !rows_cap || !d_images) return APTGPU_ERR_INVALID;
     if (map && count > 0 && (!positions || !n_positions)) return APTGPU_ERR_INVALID;
     return guarded(err, err_cap, [&] {
         apt::gpu::ColorTune tune{};
         bool lab = false;
+        // the orbit form: every recording's satellite, time, map settings and Rotate::Orbit outcome, before any launch
+        std::vector<SatCall> sats;
+        std::vector<int> rotates(static_cast<size_t>(count), rotate);
+        if (orbit) {
+            for (int i = 0; i < count; ++i) {
+                sats.push_back(orbit_args(orbit[i]));
+                rotates[static_cast<size_t>(i)] = resolve_rotate(rotate, sats.back());
+                if ((sats.back().draw_map != nullptr) != (sats.front().draw_map != nullptr))
+                    throw Error{ErrorKind::Invalid, "draw_map must be set for every recording of the call or for none"};
+            }
+            if (!sats.empty() && sats.front().draw_map) {
+                if (!orbit_layers) throw Error{ErrorKind::Invalid, "draw_map needs a layer set"};
+                if (channels != 4) throw Error{ErrorKind::Invalid, "the map overlay needs channels = 4 (RGBA)"};
+            }
+            if (rotate == APTGPU_ROTATE_ORBIT) rotate = APTGPU_ROTATE_NO;  // (resolved per recording above)
+        }
         const bool colored = color_args(contrast, rotate, color, channels, &tune, &lab);
         if (static_cast<size_t>(count) > plan->last_slots.size())
             throw Error{ErrorKind::Invalid, "count exceeds the recordings of the last decode call"};
@@ -410,8 +474,14 @@ int plan_process_image(aptgpu_plan *plan, int count, const float *const *d_rows,
         if (colored) plan->set_palette(color->palette_rgb, lab);
         for (int i = 0; i < count; ++i)
             plan->enqueue_image_color(i, d_rows[i], static_cast<uint64_t>(rows_cap[i]) * 2080u, contrast, percent,
-                                      rotate == APTGPU_ROTATE_YES, colored ? &tune : nullptr, channels, d_images[i],
-                                      lab);
+                                      rotates[static_cast<size_t>(i)] == APTGPU_ROTATE_YES, colored ? &tune : nullptr,
+                                      channels, d_images[i], lab);
+        if (!sats.empty() && sats.front().draw_map)
+            for (int i = 0; i < count; ++i)
+                plan->enqueue_image_map_sat(i, static_cast<uint64_t>(rows_cap[i]) * 2080u, *orbit_layers,
+                                            sats[static_cast<size_t>(i)].call, *sats[static_cast<size_t>(i)].draw_map,
+                                            map_colors(*orbit_layers),
+                                            rotates[static_cast<size_t>(i)] == APTGPU_ROTATE_YES, d_images[i]);
         if (map)
             for (int i = 0; i < count; ++i)
                 plan->enqueue_image_map(i, static_cast<uint64_t>(rows_cap[i]) * 2080u, *map->layers,
@@ -510,7 +580,7 @@ int aptgpu_process_gray(const aptgpu_context *ctx, const float *signal, size_t n
             contrast != APTGPU_CONTRAST_MINMAX)
             throw Error{ErrorKind::Invalid, "unknown contrast adjustment"};
         if (rotate != APTGPU_ROTATE_NO && rotate != APTGPU_ROTATE_YES)
-            throw Error{ErrorKind::Unsupported, "Rotate::Orbit needs orbit propagation (host side, out of scope)"};
+            throw Error{ErrorKind::Unsupported, "Rotate::Orbit needs the satellite and the time: aptgpu_orbit_settings, the *_orbit entry points"};
         ImageCall c(ctx, signal, n);
         hipStream_t s = c.sc.stream;
         process_limits(ctx, c, contrast, percent, info);
@@ -546,7 +616,7 @@ int aptgpu_plan_process_device(aptgpu_plan *plan, int count, const float *const 
         if (contrast < APTGPU_CONTRAST_TELEMETRY || contrast > APTGPU_CONTRAST_MINMAX)
             throw Error{ErrorKind::Invalid, "unknown contrast adjustment"};
         if (rotate != APTGPU_ROTATE_NO && rotate != APTGPU_ROTATE_YES)
-            throw Error{ErrorKind::Unsupported, "Rotate::Orbit needs orbit propagation (host side, out of scope)"};
+            throw Error{ErrorKind::Unsupported, "Rotate::Orbit needs the satellite and the time: aptgpu_orbit_settings, the *_orbit entry points"};
         if (contrast == APTGPU_CONTRAST_PERCENT && (percent < 0.f || percent > 1.f))
             throw Error{ErrorKind::Internal, kBadPercent};
         apt::hip_check(hipSetDevice(plan->device), "hipSetDevice");
@@ -712,6 +782,95 @@ int aptgpu_plan_process_device_image_png(aptgpu_plan *plan, int count, const flo
     MapCall m{map, with_map ? &layers->layers : nullptr};
     return plan_process_image(plan, count, d_rows, rows_cap, contrast, percent, rotate, color, channels,
                               with_map ? &m : nullptr, sat_positions, n_positions, d_images, err, err_cap, d_png, png_cap);
+}
+
+int aptgpu_sat_track_host(const aptgpu_orbit_settings *orbit, uint32_t height, double *latlon_out, char *err,
+                          size_t err_cap)
+{
+    if (!latlon_out && height) return APTGPU_ERR_INVALID;
+    return guarded(err, err_cap, [&] {
+        const SatCall c = orbit_args(orbit);
+        apt::sat::track_host(c.call.rec, c.call.ref_is_end != 0, c.call.ref_ms, height, latlon_out);
+        return APTGPU_OK;
+    });
+}
+
+int aptgpu_sat_track(const aptgpu_context *ctx, const aptgpu_orbit_settings *orbit, uint32_t height,
+                     double *latlon_out, char *err, size_t err_cap)
+{
+    if (!latlon_out && height) return APTGPU_ERR_INVALID;
+    return guarded(err, err_cap, [&] {
+        const SatCall c = orbit_args(orbit);
+        if (height == 0) return APTGPU_OK;
+        Scratch sc(ctx);
+        apt::DeviceBuffer<double> d_track;
+        apt::DeviceBuffer<uint32_t> d_err;
+        d_track.alloc(2 * static_cast<size_t>(height));
+        d_err.alloc(1);
+        apt::hip_check(hipMemsetAsync(d_err.ptr, 0, sizeof(uint32_t), sc.stream), "hipMemsetAsync");
+        apt::sat::track(sc.stream, c.call, nullptr, height, height, d_track.ptr, d_err.ptr);
+        apt::hip_check(hipGetLastError(), "kernel launch (satellite track)");
+        uint32_t e = 0;
+        apt::hip_check(hipMemcpyAsync(&e, d_err.ptr, sizeof e, hipMemcpyDeviceToHost, sc.stream), "hipMemcpyAsync D2H");
+        apt::hip_check(hipMemcpyAsync(latlon_out, d_track.ptr, 2 * static_cast<size_t>(height) * sizeof(double),
+                                      hipMemcpyDeviceToHost, sc.stream),
+                       "hipMemcpyAsync D2H");
+        apt::hip_check(hipStreamSynchronize(sc.stream), "hipStreamSynchronize");
+        if (e) throw Error{ErrorKind::Internal, apt::sat::error_text(static_cast<int32_t>(e))};
+        return APTGPU_OK;
+    });
+}
+
+int aptgpu_south_to_north_pass(const aptgpu_orbit_settings *orbit, int *out, char *err, size_t err_cap)
+{
+    if (!out) return APTGPU_ERR_INVALID;
+    return guarded(err, err_cap, [&] {
+        const SatCall c = orbit_args(orbit);
+        *out = apt::sat::south_to_north_pass(c.call.rec, c.call.ref_ms) ? 1 : 0;
+        return APTGPU_OK;
+    });
+}
+
+int aptgpu_process_image_orbit(const aptgpu_context *ctx, const float *signal, size_t n, int contrast, float percent,
+                               int rotate, const aptgpu_color_settings *color, int channels,
+                               const aptgpu_orbit_settings *orbit, const aptgpu_map_layers *layers, int output,
+                               const aptgpu_png_settings *png, uint8_t **out, size_t *n_out,
+                               aptgpu_image_result *info, char *err, size_t err_cap)
+{
+    SatCall c{};
+    const int rc = guarded(err, err_cap, [&] {
+        if (output != APTGPU_OUTPUT_PIXELS && output != APTGPU_OUTPUT_PNG)
+            throw Error{ErrorKind::Invalid, "unknown output kind"};
+        c = orbit_args(orbit);
+        rotate = resolve_rotate(rotate, c);
+        if (output == APTGPU_OUTPUT_PNG) png_args(png);
+        if (c.draw_map) map_args(channels, c.draw_map, layers);
+        return APTGPU_OK;
+    });
+    if (rc != APTGPU_OK) return rc;
+    MapCall m{c.draw_map, c.draw_map ? &layers->layers : nullptr};
+    return process_image(ctx, signal, n, contrast, percent, rotate, color, channels, c.draw_map ? &m : nullptr,
+                         nullptr, out, n_out, info, err, err_cap, output == APTGPU_OUTPUT_PNG, &c.call);
+}
+
+int aptgpu_plan_process_device_image_orbit(aptgpu_plan *plan, int count, const float *const *d_rows,
+                                           const size_t *rows_cap, int contrast, float percent, int rotate,
+                                           const aptgpu_color_settings *color, int channels,
+                                           const aptgpu_orbit_settings *const *orbit, const aptgpu_map_layers *layers,
+                                           uint8_t *const *d_images, const aptgpu_png_settings *png,
+                                           uint8_t *const *d_png, const size_t *png_cap, char *err, size_t err_cap)
+{
+    if (!orbit || (d_png && !png_cap)) return APTGPU_ERR_INVALID;
+    if (d_png) {
+        const int rc = guarded(err, err_cap, [&] {
+            png_args(png);
+            return APTGPU_OK;
+        });
+        if (rc != APTGPU_OK) return rc;
+    }
+    return plan_process_image(plan, count, d_rows, rows_cap, contrast, percent, rotate, color, channels, nullptr,
+                              nullptr, nullptr, d_images, err, err_cap, d_png, png_cap, orbit,
+                              layers ? &layers->layers : nullptr);
 }
 
 int aptgpu_map_layers_create(aptgpu_map_layers **out)

@@ -1,6 +1,7 @@
 // apt_kernels_map.hip — gfx950 kernels of the map overlay (apt_kernels_map.hpp; map.rs:14-200).
 //
-// One call is eleven launches on the image's stream, none of them waiting on the host:
+// One call is eleven launches on the image's stream, none of them waiting on the host (with the track computed on the
+// device, apt_kernels_track.hpp, two more in front, and the first two below read their scalars from device memory):
 //   k_map_track    x offset of every track row (map.rs:110-114), and the call's checks (count == height)
 //   k_map_project  latlon_to_rel_px of every vertex, once (map.rs:71-100); both segments that share a vertex
 //                  read the same value, as the reference's two evaluations of one input give
@@ -22,6 +23,8 @@
 // device library's, which may differ from glibc by an ulp (the parity contract of DESIGN.md §12).  The blend is
 // f32, one rounding per operation, as the crate's.
 #include "apt_kernels_map.hpp"
+
+#include "apt_kernels_track.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -175,6 +178,41 @@ __global__ __launch_bounds__(kThreads) void k_map_project(const double *verts, u
     const uint32_t v = blockIdx.x * kThreads + threadIdx.x;
     if (v >= n) return;
     // (pt.y / 180. * PI, pt.x / 180. * PI), map.rs:142-143
+    const double lat = verts[2 * v + 1] / 180. * kPi, lon = verts[2 * v] / 180. * kPi;
+    double x, y;
+    rel_px(sc, lat, lon, x, y);
+    proj[2 * v] = x;
+    proj[2 * v + 1] = y;
+}
+
+// The two kernels above fed from the device: the scalars and the row count are k_sat_scalars' (the height itself, so
+// the count check can only fail on the capacity), ctl[3] holds k_sat_track's SGP4 error.
+__global__ __launch_bounds__(kThreads) void k_map_track_dev(const double *track, uint32_t rows_cap, const Scalars *scp,
+                                                            double *xoff, const ImageResult *info, uint32_t *ctl)
+{
+    const uint32_t r = blockIdx.x * kThreads + threadIdx.x;
+    const uint32_t count = ctl[4];
+    if (r == 0) {
+        ctl[0] = 0;
+        ctl[2] = 0;
+        ctl[1] = info->status != 0 ? kSkip
+                 : ctl[3] != 0     ? static_cast<uint32_t>(apt::sat::kReasonSgp4)
+                                   : (count == 0 || count > rows_cap ? kReasonCount : 0u);
+        ctl[3] = 0;  // (zero between calls, as k_sat_track expects it)
+    }
+    if (r >= rows_cap || r >= count) return;
+    const Scalars sc = *scp;
+    double x, y;
+    rel_px(sc, track[2 * r], track[2 * r + 1], x, y);
+    xoff[r] = x;
+}
+
+__global__ __launch_bounds__(kThreads) void k_map_project_dev(const double *verts, uint32_t n, const Scalars *scp,
+                                                              double *proj)
+{
+    const uint32_t v = blockIdx.x * kThreads + threadIdx.x;
+    if (v >= n) return;
+    const Scalars sc = *scp;
     const double lat = verts[2 * v + 1] / 180. * kPi, lon = verts[2 * v] / 180. * kPi;
     double x, y;
     rel_px(sc, lat, lon, x, y);
@@ -478,7 +516,7 @@ Device::~Device()
                     static_cast<void *>(seg), static_cast<void *>(sums), static_cast<void *>(track),
                     static_cast<void *>(xoff), static_cast<void *>(frags), static_cast<void *>(slot),
                     static_cast<void *>(runs), static_cast<void *>(cnt), static_cast<void *>(base),
-                    static_cast<void *>(ctl)})
+                    static_cast<void *>(ctl), static_cast<void *>(scalars)})
         if (p) (void)hipFree(p);
     for (int k = 0; k < kTrackRing; ++k) {
         if (track_ev[k]) (void)hipEventDestroy(track_ev[k]);
@@ -493,7 +531,9 @@ void Device::prepare(hipStream_t s, const Layers &layers, size_t rows)
         dev_alloc(frags, kMaxFragments, "hipMalloc (map fragments)");
         dev_alloc(slot, 2 * static_cast<size_t>(kMaxFragments), "hipMalloc (map runs)");
         dev_alloc(runs, 2 * static_cast<size_t>(kMaxFragments), "hipMalloc (map runs)");
-        dev_alloc(ctl, 3, "hipMalloc (map control)");
+        dev_alloc(ctl, kCtlWords, "hipMalloc (map control)");
+        dev_alloc(scalars, 1, "hipMalloc (map control)");
+        apt::hip_check(hipMemsetAsync(ctl, 0, kCtlWords * sizeof(uint32_t), s), "hipMemsetAsync");
         frag_ready = true;
     }
     if (vert_cap < n + 1 || !verts) {
@@ -549,6 +589,14 @@ void Device::upload_track(hipStream_t s, const double *positions, size_t count)
     apt::hip_check(hipEventRecord(track_ev[k], s), "hipEventRecord");
 }
 
+namespace {
+
+// the nine launches behind the projection, shared by both forms
+void overlay_tail(hipStream_t s, Device &d, uint32_t n, const Colors &colors, bool rotate, uint8_t *img,
+                  ImageResult *info);
+
+}  // namespace
+
 void image_map_overlay(hipStream_t s, Device &d, const Scalars &sc, const Colors &colors, uint32_t count,
                        bool rotate, uint8_t *img, ImageResult *info)
 {
@@ -556,6 +604,26 @@ void image_map_overlay(hipStream_t s, Device &d, const Scalars &sc, const Colors
     const uint32_t rows = static_cast<uint32_t>(d.rows_cap < count ? d.rows_cap : count);
     k_map_track<<<blocks(rows, kThreads), kThreads, 0, s>>>(d.track, count, rows, sc, d.xoff, info, d.ctl);
     k_map_project<<<blocks(n, kThreads), kThreads, 0, s>>>(d.verts, n, sc, d.proj);
+    overlay_tail(s, d, n, colors, rotate, img, info);
+}
+
+void image_map_overlay_sat(hipStream_t s, Device &d, const apt::sat::TrackCall &call, double yaw, double hscale,
+                           double vscale, const Colors &colors, bool rotate, uint8_t *img, ImageResult *info)
+{
+    const uint32_t n = static_cast<uint32_t>(d.n_vert);
+    const uint32_t rows = static_cast<uint32_t>(d.rows_cap < 0xffffffffu ? d.rows_cap : 0xffffffffu);
+    apt::sat::track(s, call, info, 0, rows, d.track, d.ctl + 3);
+    apt::sat::scalars(s, d.track, info, rows, yaw, hscale, vscale, d.scalars, d.ctl + 4);
+    k_map_track_dev<<<blocks(rows, kThreads), kThreads, 0, s>>>(d.track, rows, d.scalars, d.xoff, info, d.ctl);
+    k_map_project_dev<<<blocks(n, kThreads), kThreads, 0, s>>>(d.verts, n, d.scalars, d.proj);
+    overlay_tail(s, d, n, colors, rotate, img, info);
+}
+
+namespace {
+
+void overlay_tail(hipStream_t s, Device &d, uint32_t n, const Colors &colors, bool rotate, uint8_t *img,
+                  ImageResult *info)
+{
     k_map_count<<<blocks(n + 1, kThreads), kThreads, 0, s>>>(d.proj, d.meta, n, d.xoff, info, d.ctl, d.seg);
     const uint32_t nb = blocks(n + 1, kScanBlock);
     k_scan_local<<<nb, kThreads, 0, s>>>(d.seg, n + 1, d.sums);
@@ -569,5 +637,7 @@ void image_map_overlay(hipStream_t s, Device &d, const Scalars &sc, const Colors
     k_map_blend<<<kListBlocks, kThreads, 0, s>>>(d.frags, d.ctl, info, rotate, colors, d.cnt, d.slot, d.base, d.runs,
                                                  reinterpret_cast<uint32_t *>(img));
 }
+
+}  // namespace
 
 }  // namespace apt::map

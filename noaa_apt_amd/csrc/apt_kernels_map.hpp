@@ -11,6 +11,10 @@ namespace apt {
 void hip_check(hipError_t e, const char *what);
 }
 
+namespace apt::sat {
+struct TrackCall;
+}
+
 namespace apt::map {
 
 // Device-side state of one overlay target (a one-shot call or a plan slot): the uploaded layer set, the per-vertex
@@ -28,7 +32,10 @@ struct Device {
     uint32_t *runs = nullptr;   // 2 * kMaxFragments: the copies grouped into one contiguous run per pixel
     uint32_t *cnt = nullptr;    // per pixel of rows_cap rows: copies landing there (zero between calls)
     uint32_t *base = nullptr;   // per pixel: start of its run in `runs` (valid where cnt != 0)
-    uint32_t *ctl = nullptr;    // [0] fragment total, [1] error / skip, [2] run allocator
+    uint32_t *ctl = nullptr;    // [0] fragment total, [1] error / skip, [2] run allocator; the device-fed form:
+                                // [3] SGP4 error of the track, [4] row count
+    Scalars *scalars = nullptr; // the device-fed form's per-call scalars (k_sat_scalars)
+    static constexpr size_t kCtlWords = 8;
     static constexpr int kTrackRing = 8;
     double *track_host[kTrackRing] = {};  // pinned staging of the track (rows_cap rows each), used in turn
     hipEvent_t track_ev[kTrackRing] = {}; // behind the latest upload from track_host[k]
@@ -53,5 +60,13 @@ struct Device {
 // above.  An info record whose status is already set is left alone and nothing is drawn.
 void image_map_overlay(hipStream_t s, Device &dev, const Scalars &sc, const Colors &colors, uint32_t count,
                        bool rotate, uint8_t *img, apt::gpu::ImageResult *info);
+
+// The same with the track computed on the device (apt_kernels_track.hpp): SGP4 for info->height rows into dev.track,
+// the scalars of map.rs:59-69 from its two ends into device memory, then the overlay reading both from there.  No
+// upload and no host wait.  A propagation error in any row is reported in info (apt::sat::kReasonSgp4) and nothing
+// is drawn.
+void image_map_overlay_sat(hipStream_t s, Device &dev, const apt::sat::TrackCall &call, double yaw, double hscale,
+                           double vscale, const Colors &colors, bool rotate, uint8_t *img,
+                           apt::gpu::ImageResult *info);
 
 }  // namespace apt::map

@@ -1005,6 +1005,21 @@ void aptgpu_plan::enqueue_image_map(int i, uint64_t rows_cap_floats, const apt::
     apt::hip_check(hipGetLastError(), "kernel launch (map overlay)");
 }
 
+void aptgpu_plan::enqueue_image_map_sat(int i, uint64_t rows_cap_floats, const apt::map::Layers &layers,
+                                        const apt::sat::TrackCall &call, const aptgpu_map_settings &settings,
+                                        const apt::map::Colors &colors, bool rotate, uint8_t *d_image)
+{
+    const ImageTarget t = image_target(i, rows_cap_floats);
+    Slot &sl = t.slot;
+    if (!sl.map) sl.map = std::make_unique<apt::map::Device>();
+    sl.map->prepare(t.stream, layers, t.cap / 2080u);
+    timed(t.stream, "image_map_overlay_sat", [&] {
+        apt::map::image_map_overlay_sat(t.stream, *sl.map, call, settings.yaw, settings.hscale, settings.vscale, colors,
+                                        rotate, d_image, t.out);
+    });
+    apt::hip_check(hipGetLastError(), "kernel launch (map overlay)");
+}
+
 void aptgpu_plan::enqueue_image_png(int i, uint64_t rows_cap_floats, int channels, const uint8_t *d_image,
                                     uint8_t *d_png, uint64_t png_cap)
 {

@@ -225,6 +225,11 @@ struct aptgpu_plan {
     void enqueue_image_map(int i, uint64_t rows_cap_floats, const apt::map::Layers &layers,
                            const apt::map::Scalars &sc, const apt::map::Colors &colors, const double *positions,
                            size_t count, bool rotate, uint8_t *d_image);
+    // The same with the track computed on the device from the satellite and the reference time (apt_kernels_track.hpp):
+    // nothing is staged or uploaded per call.
+    void enqueue_image_map_sat(int i, uint64_t rows_cap_floats, const apt::map::Layers &layers,
+                               const apt::sat::TrackCall &call, const aptgpu_map_settings &settings,
+                               const apt::map::Colors &colors, bool rotate, uint8_t *d_image);
     // The PNG encoder (apt_kernels_png.hpp) over recording i's finished image, behind everything above on the same
     // stream: the file goes to d_png (png_cap bytes), its length to the image record.
     void enqueue_image_png(int i, uint64_t rows_cap_floats, int channels, const uint8_t *d_image, uint8_t *d_png,
