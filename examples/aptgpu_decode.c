@@ -4,6 +4,7 @@
  *     aptgpu_decode in.wav out.pgm [contrast: telemetry|percent|minmax] [--no-sync]
  *                   [--histogram] [--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE] [--png]
  *                   [--tle FILE --sat NAME (--start-ms N | --end-ms N)] [--rotate no|yes|orbit]
+ *                   [--project equirect|mercator[:step_deg] [--grid DEG]]
  *
  * What `noaa-apt in.wav -o out.png` does (main.rs:91-110, noaa_apt.rs:114-235): load -> decode ->
  * contrast limits -> 8-bit image, written as a binary PGM, or with --png as the PNG file the GPU
@@ -15,8 +16,12 @@
  * reference does, channel A in CIE Lab (APTGPU_COLOR_EQUALIZE_LAB); without it that combination
  * is refused.  --map DIR --track FILE: the map overlay (`--map`) of DIR/states.shp, countries.shp and
  * lakes.shp with the default settings and colours; FILE holds the satellite's raw f64 (lat, lon)
- * pairs in radians, one per image row (SGP4 is the caller's job); written as a PPM.  Plain C99,
- * links only libaptgpu.so.
+ * pairs in radians, one per image row (SGP4 is the caller's job); written as a PPM.
+ * --project KIND[:STEP]: the finished image (channel A) reprojected onto a north-up equirectangular or
+ * Mercator grid of STEP degrees per pixel (default 0.04) that aptgpu_projection_fit sizes from the track
+ * (--track FILE, or --tle: aptgpu_sat_track_host), bilinear; --grid DEG adds a graticule.  Written as a
+ * PPM of the grid's size, or with --png as the RGBA PNG (transparent off the swath).  Plain C99, links
+ * only libaptgpu.so.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -35,13 +40,16 @@ int main(int argc, char **argv)
     if (argc < 3) {
         fprintf(stderr, "usage: %s in.wav out.pgm [telemetry|percent|minmax] [--no-sync] [--histogram] "
                 "[--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE] [--png]\n"
-                "       [--tle FILE --sat NAME (--start-ms N | --end-ms N)] [--rotate no|yes|orbit]\n", argv[0]);
+                "       [--tle FILE --sat NAME (--start-ms N | --end-ms N)] [--rotate no|yes|orbit]\n"
+                "       [--project equirect|mercator[:step_deg] [--grid DEG]]\n", argv[0]);
         return 2;
     }
     int contrast = APTGPU_CONTRAST_PERCENT, sync = 1, lab = 0, png = 0;
     const char *palette_path = NULL, *map_dir = NULL, *track_path = NULL, *tle_path = NULL, *sat = NULL;
     int rotate = APTGPU_ROTATE_NO, ref_kind = -1;
     long long ref_ms = 0;
+    const char *project = NULL;
+    double grid_deg = 0.0;
     for (int i = 3; i < argc; ++i) {
         if (!strcmp(argv[i], "telemetry")) contrast = APTGPU_CONTRAST_TELEMETRY;
         else if (!strcmp(argv[i], "percent")) contrast = APTGPU_CONTRAST_PERCENT;
@@ -57,6 +65,8 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--sat") && i + 1 < argc) sat = argv[++i];
         else if (!strcmp(argv[i], "--start-ms") && i + 1 < argc) ref_kind = APTGPU_REF_TIME_START, ref_ms = atoll(argv[++i]);
         else if (!strcmp(argv[i], "--end-ms") && i + 1 < argc) ref_kind = APTGPU_REF_TIME_END, ref_ms = atoll(argv[++i]);
+        else if (!strcmp(argv[i], "--project") && i + 1 < argc) project = argv[++i];
+        else if (!strcmp(argv[i], "--grid") && i + 1 < argc) grid_deg = atof(argv[++i]);
         else if (!strcmp(argv[i], "--rotate") && i + 1 < argc) {
             const char *r = argv[++i];
             rotate = !strcmp(r, "orbit") ? APTGPU_ROTATE_ORBIT : !strcmp(r, "yes") ? APTGPU_ROTATE_YES : APTGPU_ROTATE_NO;
@@ -121,7 +131,64 @@ int main(int argc, char **argv)
     aptgpu_image_result info;
     const int rgba = palette_path || map_dir;
     aptgpu_png_settings ps = {sizeof(aptgpu_png_settings), 0};
-    if (tle_path) {
+    aptgpu_projection_settings proj;
+    memset(&proj, 0, sizeof proj);
+    if (project) {
+        /* the georeferenced image: the grid is fitted to the track, which comes from --track or from the TLE */
+        const size_t height = n_rows_px / 2080;
+        const int kind = !strncmp(project, "mercator", 8) ? APTGPU_PROJECTION_MERCATOR : APTGPU_PROJECTION_EQUIRECTANGULAR;
+        const char *colon = strchr(project, ':');
+        const double step = colon ? atof(colon + 1) : 0.04;
+        double *track = malloc((height ? height : 1) * 2 * sizeof(double));
+        char *tle = NULL;
+        aptgpu_orbit_settings os;
+        memset(&os, 0, sizeof os);
+        rc = APTGPU_OK;
+        if (tle_path) {
+            FILE *t = fopen(tle_path, "rb");
+            long tn = 0;
+            if (t) { fseek(t, 0, SEEK_END); tn = ftell(t); fseek(t, 0, SEEK_SET); tle = malloc((size_t)tn + 1); }
+            if (!t || !tle || fread(tle, 1, (size_t)tn, t) != (size_t)tn || !sat || ref_kind < 0) {
+                fprintf(stderr, "--tle FILE needs a readable file, --sat NAME and --start-ms N or --end-ms N\n");
+                return 1;
+            }
+            tle[tn] = 0;
+            fclose(t);
+            os.struct_size = sizeof os;
+            os.sat_name = sat;
+            os.tle = tle;
+            os.ref_kind = ref_kind;
+            os.ref_unix_ms = ref_ms;
+            rc = aptgpu_sat_track_host(&os, (uint32_t)height, track, err, sizeof err);  /* for the fit alone */
+        } else {
+            FILE *t = track_path ? fopen(track_path, "rb") : NULL;
+            if (!track || !t || fread(track, sizeof(double), 2 * height, t) != 2 * height || fgetc(t) != EOF) {
+                fprintf(stderr, "--project needs --track FILE with exactly %zu (lat, lon) f64 pairs, or --tle\n", height);
+                return 1;
+            }
+            fclose(t);
+        }
+        aptgpu_map_layers *layers = NULL;
+        aptgpu_map_settings ms = {sizeof(aptgpu_map_settings), 0, 0.0, 1.0, 1.0};  /* config.rs:646-648 */
+        if (rc == APTGPU_OK) rc = aptgpu_projection_fit(track, height, ms.hscale, kind, step, 0, &proj, err, sizeof err);
+        proj.sampling = APTGPU_SAMPLING_BILINEAR;
+        proj.grid_deg = grid_deg;
+        proj.grid_color[0] = proj.grid_color[1] = proj.grid_color[2] = 255;
+        proj.grid_color[3] = 160;
+        if (rc == APTGPU_OK && map_dir) {
+            rc = aptgpu_map_layers_create(&layers);
+            if (rc == APTGPU_OK) rc = aptgpu_map_layers_load_dir(layers, map_dir, err, sizeof err);
+        }
+        if (rc == APTGPU_OK)
+            rc = aptgpu_process_image_project(&ctx, rows, n_rows_px, contrast, 0.98f, rotate,
+                                              palette_path ? &color : NULL, rgba ? 4 : 1, &ms, layers,
+                                              tle_path ? NULL : track, tle_path ? &os : NULL, &proj,
+                                              png ? APTGPU_OUTPUT_PNG : APTGPU_OUTPUT_PIXELS, &ps, &image, &n_px, &info,
+                                              err, sizeof err);
+        aptgpu_map_layers_destroy(layers);
+        free(track);
+        free(tle);
+    } else if (tle_path) {
         /* OrbitSettings: the track (and Rotate::Orbit) from the TLE, computed by the library; no track file */
         char *tle = NULL;
         FILE *t = fopen(tle_path, "rb");
@@ -200,6 +267,9 @@ int main(int argc, char **argv)
     if (!o) { perror(argv[2]); return 1; }
     if (png) {
         fwrite(image, 1, n_px, o);  /* the file as it is: img.save(&output_filename), main.rs */
+    } else if (project) {
+        fprintf(o, "P6\n%u %u\n255\n", proj.width, proj.height);
+        for (size_t i = 0; i < (size_t)proj.width * proj.height; ++i) fwrite(image + 4 * i, 1, 3, o);  /* drop alpha */
     } else if (rgba) {
         fprintf(o, "P6\n2080 %u\n255\n", info.height);
         for (size_t i = 0; i < (size_t)info.height * 2080u; ++i) fwrite(image + 4 * i, 1, 3, o);  /* drop alpha */
@@ -209,6 +279,10 @@ int main(int argc, char **argv)
     }
     fclose(o);
     aptgpu_free(image);
-    fprintf(stderr, "wrote %s: 2080 x %u, contrast limits %g .. %g\n", argv[2], info.height, info.low, info.high);
+    if (project)
+        fprintf(stderr, "wrote %s: %u x %u, north %g, west %g, %g degrees per pixel\n", argv[2], proj.width, proj.height,
+                proj.lat_north, proj.lon_west, proj.step);
+    else
+        fprintf(stderr, "wrote %s: 2080 x %u, contrast limits %g .. %g\n", argv[2], info.height, info.low, info.high);
     return 0;
 }

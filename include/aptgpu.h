@@ -402,7 +402,8 @@ typedef struct aptgpu_image_result {
     int32_t reason;          /* 1 zero-length signal (dsp.rs:40-44), 2 too short for telemetry
                                 (telemetry.rs:199-203), 3 no low bucket (misc.rs:172 panics),
                                 4 the decode before it failed, 5-8 the map overlay's limits
-                                (APTGPU_MAP_REASON_*), 9 APTGPU_PNG_REASON_CAPACITY, 10 APTGPU_SAT_REASON_SGP4 */
+                                (APTGPU_MAP_REASON_*), 9 APTGPU_PNG_REASON_CAPACITY, 10 APTGPU_SAT_REASON_SGP4,
+                                11 APTGPU_PROJECT_REASON_CAPACITY */
     uint32_t height;         /* rows of 2080 px */
     uint32_t telemetry_row;  /* best frame start, telemetry.rs:196,228-230 */
     float low, high;         /* the contrast limits used by map_signal_u8 */
@@ -650,6 +651,85 @@ int aptgpu_plan_process_device_image_orbit(aptgpu_plan *plan, int count, const f
                                            const aptgpu_orbit_settings *const *orbit, const aptgpu_map_layers *layers,
                                            uint8_t *const *d_images, const aptgpu_png_settings *png,
                                            uint8_t *const *d_png, const size_t *png_cap, char *err, size_t err_cap);
+
+/* ---- reprojection onto a north-up map grid ----
+ * The reference's image is the raw swath; its to-do list names the next step (docs/development.md:112 "Draw image over
+ * mercator (or at least equirectangular) projection", :99 "Add latitude longitude grid").  Every output pixel goes
+ * backwards through the reference's own latlon_to_rel_px (map.rs:71-100) and the x-offset correction of map.rs:105-111
+ * into one channel of the unrotated swath image, so the projected coastlines agree with the overlay's by construction.
+ * The settings struct is the georeference of the output: the centre of pixel (i, j) lies at
+ *   longitude lon_west + j * step                                   (degrees; may pass 180, never wrapped)
+ *   latitude  lat_north - i * step                                  (equirectangular)
+ *             atan(sinh(asinh(tan(lat_north)) - i * step in rad))   (Mercator: step is the longitude step)
+ * A pixel is painted only where the swath covers it: the band of map.rs:116-121 (-456 < x < 456, 0 < y < height) and
+ * less than 60 degrees of arc from the track's first point (latlon_to_rel_px clamps its distance there; beyond it every
+ * point would alias onto one image row).  Every other pixel is (0, 0, 0, 0).  The output is always RGBA; a gray source
+ * reads as (g, g, g, 255). */
+#define APTGPU_PROJECTION_EQUIRECTANGULAR 0
+#define APTGPU_PROJECTION_MERCATOR 1
+#define APTGPU_PROJECTION_CHANNEL_A 0 /* columns x + 539 of the swath  */
+#define APTGPU_PROJECTION_CHANNEL_B 1 /* columns x + 1579              */
+#define APTGPU_SAMPLING_NEAREST 0     /* the pixel at floor(x + 0.5), floor(y + 0.5) */
+#define APTGPU_SAMPLING_BILINEAR 1    /* the four neighbours in f64, every channel, rounded half up */
+#define APTGPU_PROJECT_REASON_CAPACITY 11 /* aptgpu_image_result.reason: out_cap[i] is below width * height * 4 bytes;
+                                             nothing was written to d_out[i] */
+#define APTGPU_PROJECTION_MAX_PIXELS (1u << 26)
+typedef struct aptgpu_projection_settings {
+    uint32_t struct_size; /* sizeof(aptgpu_projection_settings) */
+    int32_t kind;         /* APTGPU_PROJECTION_* */
+    uint32_t width, height;      /* >= 1, width * height <= APTGPU_PROJECTION_MAX_PIXELS */
+    double lat_north, lon_west;  /* degrees: the centre of pixel (0, 0); |lat_north| <= 90 (and the last row's for
+                                    the equirectangular grid) */
+    double step;          /* degrees per pixel, finite and > 0 */
+    int32_t channel;      /* APTGPU_PROJECTION_CHANNEL_* */
+    int32_t sampling;     /* APTGPU_SAMPLING_* */
+    double grid_deg;      /* 0: no graticule; otherwise >= step: the rows and columns nearest to every multiple of it are
+                             blended with grid_color (image 0.24.7's blend, once where they cross), over painted and
+                             empty pixels alike */
+    uint8_t grid_color[4]; /* RGBA */
+    uint32_t reserved;    /* 0 */
+} aptgpu_projection_settings;
+/* Host only (no GPU): a grid of `kind` that covers the swath of a track of `count` (lat, lon) pairs in radians: the
+ * track's bounding box (longitudes unwrapped so that consecutive rows differ by less than pi), grown by the swath's
+ * half angle 456 * 0.0005 / hscale in latitude and by that / cos(max |lat|) in longitude, latitudes clamped to +-85
+ * degrees for Mercator and +-90 otherwise, the longitude span to 360.  Conservative, not tight.  step_deg > 0 is the
+ * step; otherwise max_width >= 2 columns span the box.  channel A, nearest sampling and no graticule are filled in. */
+int aptgpu_projection_fit(const double *track, size_t count, double hscale, int kind, double step_deg,
+                          uint32_t max_width, aptgpu_projection_settings *out, char *err, size_t err_cap);
+/* Reprojects a host image: height rows of 2080 px of `channels` (1 or 4) bytes, unrotated, with its track (n_positions
+ * = height pairs).  map gives yaw / hscale / vscale (nullable: 0, 1, 1).  output APTGPU_OUTPUT_PIXELS: *out is the
+ * RGBA grid, proj->width * proj->height * 4 bytes; APTGPU_OUTPUT_PNG: the PNG file of it (png nullable). */
+int aptgpu_project_image(const aptgpu_context *ctx, const uint8_t *image, uint32_t height, int channels,
+                         const double *sat_positions, size_t n_positions, const aptgpu_map_settings *map,
+                         const aptgpu_projection_settings *proj, int output, const aptgpu_png_settings *png,
+                         uint8_t **out, size_t *n_out, char *err, size_t err_cap);
+/* process() with the reprojection at its end: the image stage, the map overlay when `layers` is given (drawn on the
+ * swath by the overlay's own launches; channels 4 then), the reprojection, optionally the PNG encoder, all on one
+ * stream.  Exactly one of sat_positions (height pairs) and orbit (the track is then computed on the GPU) must be
+ * given.  map gives yaw / hscale / vscale (nullable: orbit->draw_map when that is set, else 0, 1, 1).  The projection
+ * reads the unrotated image and north is up by construction: any rotate but APTGPU_ROTATE_NO is APTGPU_ERR_INVALID.
+ * info->height stays the swath's height; info->n_px its pixels. */
+int aptgpu_process_image_project(const aptgpu_context *ctx, const float *signal, size_t n, int contrast, float percent,
+                                 int rotate, const aptgpu_color_settings *color, int channels,
+                                 const aptgpu_map_settings *map, const aptgpu_map_layers *layers,
+                                 const double *sat_positions, const aptgpu_orbit_settings *orbit,
+                                 const aptgpu_projection_settings *proj, int output, const aptgpu_png_settings *png,
+                                 uint8_t **out, size_t *n_out, aptgpu_image_result *info, char *err, size_t err_cap);
+/* Device-resident: aptgpu_plan_process_device_image (+ overlay with `layers`) followed by the reprojection of
+ * recording i onto proj[i] into d_out[i] (out_cap[i] bytes, 4-byte aligned), on the recording's stream without a host
+ * round trip.  Exactly one of sat_positions / n_positions and orbit is given (arrays of count).  d_png (with png_cap)
+ * is nullable: then no PNG; aptgpu_png_bound(proj[i].width, proj[i].height, 4) always suffices.  Through
+ * aptgpu_plan_image_results: an out_cap[i] that is too small (APTGPU_PROJECT_REASON_CAPACITY; never truncated), a
+ * position count that differs from the height (APTGPU_MAP_REASON_COUNT), an SGP4 error (APTGPU_SAT_REASON_SGP4). */
+int aptgpu_plan_process_device_image_project(aptgpu_plan *plan, int count, const float *const *d_rows,
+                                             const size_t *rows_cap, int contrast, float percent, int rotate,
+                                             const aptgpu_color_settings *color, int channels,
+                                             const aptgpu_map_settings *map, const aptgpu_map_layers *layers,
+                                             const double *const *sat_positions, const size_t *n_positions,
+                                             const aptgpu_orbit_settings *const *orbit, uint8_t *const *d_images,
+                                             const aptgpu_projection_settings *proj, uint8_t *const *d_out,
+                                             const size_t *out_cap, const aptgpu_png_settings *png,
+                                             uint8_t *const *d_png, const size_t *png_cap, char *err, size_t err_cap);
 
 /* ====================================================================== */
 /* 5. WAV ingest in front of decode()                 */

@@ -153,6 +153,14 @@ class _CMapSettings(C.Structure):
                 ("hscale", C.c_double), ("vscale", C.c_double)]
 
 
+class _CProjectionSettings(C.Structure):
+    """aptgpu_projection_settings"""
+    _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_int32), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("lat_north", C.c_double), ("lon_west", C.c_double), ("step", C.c_double), ("channel", C.c_int32),
+                ("sampling", C.c_int32), ("grid_deg", C.c_double), ("grid_color", C.c_uint8 * 4),
+                ("reserved", C.c_uint32)]
+
+
 class WavSpec(C.Structure):
     """aptgpu_wav_spec: hound::WavSpec plus where the samples are."""
     _fields_ = [("channels", C.c_uint16), ("bits_per_sample", C.c_uint16),
@@ -345,6 +353,16 @@ def lib():
     L.aptgpu_plan_process_device_image_png.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz), i32, f, i32, ccs, i32,
                                                        cms, vp, C.POINTER(_f64p), C.POINTER(sz), C.POINTER(vp), cps,
                                                        C.POINTER(vp), C.POINTER(sz), C.c_char_p, sz]
+    cpr = C.POINTER(_CProjectionSettings)
+    L.aptgpu_projection_fit.argtypes = [_f64p, sz, C.c_double, i32, C.c_double, u32, cpr, C.c_char_p, sz]
+    L.aptgpu_project_image.argtypes = [cp, _u8p, u32, i32, _f64p, sz, cms, cpr, i32, cps, C.POINTER(_u8p),
+                                       C.POINTER(sz), C.c_char_p, sz]
+    L.aptgpu_process_image_project.argtypes = [cp, _f32p, sz, i32, f, i32, ccs, i32, cms, vp, _f64p, cos, cpr, i32, cps,
+                                               C.POINTER(_u8p), C.POINTER(sz), C.POINTER(ImageResult), C.c_char_p, sz]
+    L.aptgpu_plan_process_device_image_project.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz), i32, f, i32, ccs, i32,
+                                                           cms, vp, C.POINTER(_f64p), C.POINTER(sz), C.POINTER(cos),
+                                                           C.POINTER(vp), cpr, C.POINTER(vp), C.POINTER(sz), cps,
+                                                           C.POINTER(vp), C.POINTER(sz), C.c_char_p, sz]
     _lib = L
     return L
 
@@ -1103,8 +1121,129 @@ def encode_png(image, context=None) -> bytes:
     return _take(out, n.value, np.uint8).tobytes()
 
 
+PROJECT_REASON_CAPACITY = 11  # ImageResult.reason: the projection's output buffer is below width * height * 4 bytes
+
+
+class Projection:
+    """The map grids of the reprojection (aptgpu_projection_settings.kind), its source channel and its sampling."""
+    EQUIRECTANGULAR, MERCATOR = 0, 1
+    CHANNEL_A, CHANNEL_B = 0, 1
+    NEAREST, BILINEAR = 0, 1
+
+
+class ProjectionSettings:
+    """aptgpu_projection_settings: a north-up grid of width x height pixels whose pixel (i, j) has its centre at
+    longitude lon_west + j * step and latitude lat_north - i * step (equirectangular) or
+    atan(sinh(asinh(tan(lat_north)) - i * step)) (Mercator), all in degrees; this is the georeference of the output.
+    channel: the half of the swath that is sampled; sampling: NEAREST or BILINEAR; grid_deg > 0 draws a graticule
+    in grid_color over every multiple of it.  geometry: the MapSettings whose yaw / hscale / vscale place the swath
+    when no overlay is drawn (with an overlay, the overlay's settings do)."""
+
+    def __init__(self, kind, width, height, lat_north, lon_west, step, channel=Projection.CHANNEL_A,
+                 sampling=Projection.NEAREST, grid_deg=0.0, grid_color=(255, 255, 255, 255), geometry=None):
+        self.kind, self.width, self.height = int(kind), int(width), int(height)
+        self.lat_north, self.lon_west, self.step = float(lat_north), float(lon_west), float(step)
+        self.channel, self.sampling, self.grid_deg = int(channel), int(sampling), float(grid_deg)
+        self.grid_color = tuple(int(v) for v in grid_color)
+        if len(self.grid_color) != 4 or not all(0 <= v <= 255 for v in self.grid_color):
+            raise InvalidError("grid_color is an (r, g, b, a) tuple of u8")
+        if geometry is not None and not isinstance(geometry, MapSettings):
+            raise InvalidError("geometry is a MapSettings or None")
+        self.geometry = geometry
+        if not (0 <= self.width < 1 << 32 and 0 <= self.height < 1 << 32):
+            raise InvalidError("aptgpu_projection_settings: width and height must be at least 1")
+
+    def _c(self):
+        return _CProjectionSettings(C.sizeof(_CProjectionSettings), self.kind, self.width, self.height, self.lat_north,
+                                    self.lon_west, self.step, self.channel, self.sampling, self.grid_deg,
+                                    (C.c_uint8 * 4)(*self.grid_color), 0)
+
+    @property
+    def shape(self):
+        return (self.height, self.width, 4)
+
+
+def projection_fit(sat_positions, kind=Projection.EQUIRECTANGULAR, step=None, max_width=None, hscale=1.0):
+    """aptgpu_projection_fit (host only): a ProjectionSettings whose grid covers the swath of a track of (lat, lon)
+    rows in radians, with `step` degrees per pixel or, without it, `max_width` columns.  Conservative, not tight:
+    the track's bounding box grown by the swath's half angle."""
+    pos = np.ascontiguousarray(np.asarray(sat_positions, dtype=np.float64).reshape(-1, 2))
+    out = _CProjectionSettings()
+    err = C.create_string_buffer(_ERRCAP)
+    _check(lib().aptgpu_projection_fit(pos.ctypes.data_as(_f64p), len(pos), float(hscale), int(kind),
+                                       float(step) if step is not None else 0.0,
+                                       int(max_width) if max_width is not None else 0, C.byref(out), err, _ERRCAP), err)
+    return ProjectionSettings(out.kind, out.width, out.height, out.lat_north, out.lon_west, out.step, out.channel,
+                              out.sampling, out.grid_deg)
+
+
+def project_image(image, sat_positions, projection, settings=None, png=False, context=None):
+    """aptgpu_project_image: an unrotated (height, 2080) gray or (height, 2080, 4) RGBA uint8 image with its track
+    (height rows of lat, lon in radians) onto the grid of `projection`: the (grid height, grid width, 4) RGBA array,
+    or with png=True the PNG file's bytes.  settings: the MapSettings of the geometry (yaw, hscale, vscale)."""
+    x = np.ascontiguousarray(image)
+    if x.dtype != np.uint8 or x.ndim not in (2, 3) or x.shape[1] != PX_PER_ROW or (x.ndim == 3 and x.shape[2] != 4):
+        raise InvalidError("project_image: a uint8 array of (height, 2080) or (height, 2080, 4)")
+    if not isinstance(projection, ProjectionSettings):
+        raise InvalidError("projection must be a ProjectionSettings")
+    pos = np.ascontiguousarray(np.asarray(sat_positions, dtype=np.float64).reshape(-1, 2))
+    cctx = (context or Context())._c()
+    cms = (settings or projection.geometry or MapSettings())._c()
+    cpr, cps = projection._c(), _CPngSettings(C.sizeof(_CPngSettings), 0)
+    out, n = _u8p(), C.c_size_t()
+    err = C.create_string_buffer(_ERRCAP)
+    _check(lib().aptgpu_project_image(C.byref(cctx), x.ctypes.data_as(_u8p), x.shape[0], 4 if x.ndim == 3 else 1,
+                                      pos.ctypes.data_as(_f64p), len(pos), C.byref(cms), C.byref(cpr), 1 if png else 0,
+                                      C.byref(cps), C.byref(out), C.byref(n), err, _ERRCAP), err)
+    data = _take(out, n.value, np.uint8)
+    return data.tobytes() if png else data.reshape(projection.shape)
+
+
+def _process_image_project(context, signal, contrast_adjustment, rotate, color, return_info, orbit, layers, png,
+                           projection):
+    if not isinstance(projection, ProjectionSettings):
+        raise InvalidError("projection must be a ProjectionSettings")
+    if color is not None and not isinstance(color, ColorSettings):
+        raise UnsupportedError("color must be a ColorSettings")
+    if orbit is None:
+        raise InvalidError("a projection needs the track: orbit = a MapOverlay, an OrbitSettings or the sat_positions")
+    cctx = (context or Context())._c()
+    x, xp = _as_f32(signal)
+    kind, p = Contrast._c(contrast_adjustment)
+    ccol = color._c() if color is not None else None
+    corb, keep, pos, lay, ms = None, None, None, None, projection.geometry
+    if isinstance(orbit, OrbitSettings):
+        corb, keep = orbit._c()
+        if orbit.draw_map is not None:
+            if not isinstance(layers, MapLayers):
+                raise InvalidError("OrbitSettings.draw_map needs layers=MapLayers")
+            layers._colors(orbit.draw_map)
+            lay, ms = layers, orbit.draw_map
+    elif isinstance(orbit, MapOverlay):
+        orbit.layers._colors(orbit.settings)
+        pos, lay, ms = orbit.sat_positions, orbit.layers, orbit.settings
+    else:
+        pos = np.ascontiguousarray(np.asarray(orbit, dtype=np.float64).reshape(-1, 2))
+    if pos is not None and len(pos) != x.size // PX_PER_ROW:
+        raise InvalidError(f"projection: {len(pos)} positions for {x.size // PX_PER_ROW} rows")
+    channels = 4 if color is not None or lay is not None else 1
+    cms = (ms or MapSettings())._c()
+    cpr, cps = projection._c(), _CPngSettings(C.sizeof(_CPngSettings), 0)
+    img, n, info = _u8p(), C.c_size_t(), ImageResult()
+    err = C.create_string_buffer(_ERRCAP)
+    _check(lib().aptgpu_process_image_project(
+        C.byref(cctx), xp, x.size, kind, p, int(rotate), C.byref(ccol) if ccol is not None else None, channels,
+        C.byref(cms), lay._p if lay is not None else None, pos.ctypes.data_as(_f64p) if pos is not None else None,
+        C.byref(corb) if corb is not None else None, C.byref(cpr), 1 if png else 0, C.byref(cps), C.byref(img),
+        C.byref(n), C.byref(info), err, _ERRCAP), err)
+    del keep
+    out = _take(img, n.value, np.uint8)
+    out = out.tobytes() if png else out.reshape(projection.shape)
+    return (out, info) if return_info else out
+
+
 def process(context, signal, contrast_adjustment, rotate=Rotate.NO, color=None, orbit=None,
-            return_info=False, png=False, layers=None):
+            return_info=False, png=False, layers=None, projection=None):
     """noaa_apt::process (noaa_apt.rs:132-235).  Returns the height x 2080 u8
     gray image, or with `color` (a ColorSettings) the height x 2080 x 4 RGBA image of the reference's
     false colour (A = 255).  Contrast.HISTOGRAM equalises each channel half of the gray image; together with
@@ -1117,7 +1256,15 @@ def process(context, signal, contrast_adjustment, rotate=Rotate.NO, color=None, 
     itself), and Rotate.ORBIT rotates south-to-north passes.
     Unsupported: any other `orbit`, Rotate.ORBIT without an OrbitSettings (the reference only warns and does not
     rotate; with a MapOverlay too: a bare track carries no time to decide with), and HISTOGRAM with colour without
-    equalize_lab."""
+    equalize_lab.
+    projection (a ProjectionSettings): the finished image is reprojected on the GPU onto a north-up map grid and the
+    (grid height, grid width, 4) RGBA array is returned (or its PNG file).  The track comes from `orbit`: a
+    MapOverlay or an OrbitSettings with draw_map (the map is drawn on the swath first), an OrbitSettings without, or
+    plain sat_positions (no map).  It reads the unrotated image and north is up by construction: any rotate but
+    Rotate.NO raises InvalidError."""
+    if projection is not None:
+        return _process_image_project(context, signal, contrast_adjustment, rotate, color, return_info, orbit, layers,
+                                      png, projection)
     if isinstance(orbit, OrbitSettings):
         return _process_image_orbit(context, signal, contrast_adjustment, rotate, color, return_info, orbit, layers, png)
     if png:
@@ -1356,7 +1503,7 @@ class Plan:
 
     def process_device_image(self, d_rows: Sequence[int], rows_cap: Sequence[int], contrast_adjustment,
                              d_images: Sequence[int], rotate=Rotate.NO, color=None, channels=None, map=None,  # noqa: A002
-                             png=None, orbit=None, layers=None):
+                             png=None, orbit=None, layers=None, projection=None):
         """process() with every contrast (HISTOGRAM too) and optional false colour (a ColorSettings) for the
         recordings of the last decode_device call, chained on the device behind their decode.  d_images[i]
         holds rows_cap[i] * 2080 * channels bytes; channels defaults to 4 (RGBA) with colour or map, 1 (gray)
@@ -1369,10 +1516,19 @@ class Plan:
         orbit (instead of map): an OrbitSettings, or one per recording; each recording's track is computed on its
         stream (RefTime.End from the height the device found) and Rotate.ORBIT is decided per recording.  draw_map
         must be set for all or none (`layers` required then); an SGP4 error in a row is reported in image_results()
-        (reason SAT_REASON_SGP4) and that image comes back without the overlay."""
+        (reason SAT_REASON_SGP4) and that image comes back without the overlay.
+        projection: (settings, d_out, out_cap): a ProjectionSettings, a device pointer and its capacity in bytes per
+        recording.  Behind everything above, recording i's unrotated image is reprojected onto settings[i] into
+        d_out[i] (width * height * 4 bytes of RGBA); `png` then holds the projected image's file.  The track is
+        `map`'s (a MapOverlay: the map is drawn first), `orbit`'s, or map = a list of plain sat_positions arrays
+        (no map).  A capacity that is too small is reported in image_results() (reason PROJECT_REASON_CAPACITY) and
+        nothing is written; a position count that differs from the height as reason 7."""
         if color is not None and not isinstance(color, ColorSettings):
             raise UnsupportedError("color must be a ColorSettings")
         k = len(d_rows)
+        if projection is not None:
+            return self._process_device_image_project(d_rows, rows_cap, contrast_adjustment, d_images, rotate, color,
+                                                      channels, map, png, orbit, layers, projection)
         orbits = None
         if orbit is not None:
             if map is not None:
@@ -1439,6 +1595,60 @@ class Plan:
                                                       (C.c_size_t * k)(*rows_cap), kind, p, int(rotate),
                                                       C.byref(ccol) if ccol is not None else None, int(channels),
                                                       (C.c_void_p * k)(*d_images), err, _ERRCAP), err)
+
+    def _process_device_image_project(self, d_rows, rows_cap, contrast_adjustment, d_images, rotate, color, channels,
+                                      map, png, orbit, layers, projection):  # noqa: A002
+        k = len(d_rows)
+        settings, d_out, out_cap = projection
+        settings = [settings] * k if isinstance(settings, ProjectionSettings) else list(settings)
+        if len(settings) != k or len(d_out) != k or len(out_cap) != k or \
+                not all(isinstance(q, ProjectionSettings) for q in settings):
+            raise InvalidError("projection: (settings, d_out, out_cap) with one entry per recording")
+        if (map is None) == (orbit is None):
+            raise InvalidError("a projection needs the track: exactly one of map and orbit")
+        ms, lay, pos, npos, ptrs, keep = settings[0].geometry, None, None, None, None, None
+        if orbit is not None:
+            orbits = [orbit] * k if isinstance(orbit, OrbitSettings) else list(orbit)
+            if len(orbits) != k or not all(isinstance(o, OrbitSettings) for o in orbits):
+                raise InvalidError("orbit: an OrbitSettings or one per recording")
+            if orbits[0].draw_map is not None:
+                if not isinstance(layers, MapLayers):
+                    raise InvalidError("OrbitSettings.draw_map needs layers=MapLayers")
+                layers._colors(orbits[0].draw_map)
+                lay, ms = layers, orbits[0].draw_map
+            keep = [o._c() for o in orbits]
+            ptrs = (C.POINTER(_COrbitSettings) * k)(*[C.pointer(c) for c, _ in keep])
+        else:
+            if isinstance(map, MapOverlay) or all(isinstance(m, MapOverlay) for m in map):
+                maps = self._maps(map, k)
+                lay, ms = maps[0].layers, maps[0].settings
+                tracks = [m.sat_positions for m in maps]
+            else:
+                tracks = [np.ascontiguousarray(np.asarray(t, dtype=np.float64).reshape(-1, 2)) for t in map]
+                if len(tracks) != k:
+                    raise InvalidError("map: one sat_positions array per recording")
+            pos = (_f64p * k)(*[t.ctypes.data_as(_f64p) for t in tracks])
+            npos = (C.c_size_t * k)(*[len(t) for t in tracks])
+            keep = tracks
+        if channels is None:
+            channels = 4 if color is not None or lay is not None else 1
+        kind, p = Contrast._c(contrast_adjustment)
+        ccol = color._c() if color is not None else None
+        cms = (ms or MapSettings())._c()
+        cpr = (_CProjectionSettings * k)(*[q._c() for q in settings])
+        cps = _CPngSettings(C.sizeof(_CPngSettings), 0)
+        d_png, png_cap = png if png is not None else (None, None)
+        if png is not None and (len(d_png) != k or len(png_cap) != k):
+            raise InvalidError("png: (d_png, png_cap) with one entry per recording")
+        err = C.create_string_buffer(_ERRCAP)
+        _check(lib().aptgpu_plan_process_device_image_project(
+            self._p, k, (C.c_void_p * k)(*d_rows), (C.c_size_t * k)(*rows_cap), kind, p, int(rotate),
+            C.byref(ccol) if ccol is not None else None, int(channels), C.byref(cms),
+            lay._p if lay is not None else None, pos, npos, ptrs, (C.c_void_p * k)(*d_images), cpr,
+            (C.c_void_p * k)(*d_out), (C.c_size_t * k)(*[int(c) for c in out_cap]), C.byref(cps),
+            (C.c_void_p * k)(*d_png) if png is not None else None,
+            (C.c_size_t * k)(*[int(c) for c in png_cap]) if png is not None else None, err, _ERRCAP), err)
+        del keep
 
     @staticmethod
     def _maps(map, k):  # noqa: A002

@@ -8,6 +8,7 @@
 #include "apt_capi_util.hpp"
 #include "apt_kernels_color.hpp"
 #include "apt_kernels_png.hpp"
+#include "apt_kernels_project.hpp"
 #include "apt_kernels_track.hpp"
 #include "apt_map.hpp"
 #include "apt_sat.hpp"
@@ -35,6 +36,7 @@ const char *kMapPixel = "map overlay: more than APTGPU_MAP_MAX_PIXEL_FRAGMENTS (
 const char *kMapCount = "map overlay: the number of satellite positions differs from the image height";
 const char *kSatSgp4 = "satellite track: SGP4 failed for a row of the image (APTGPU_SAT_REASON_SGP4)";
 const char *kPngCapacity = "PNG encoding: the output buffer is smaller than the file (APTGPU_PNG_REASON_CAPACITY)";
+const char *kProjectCapacity = "reprojection: the output buffer is smaller than width * height * 4 bytes (APTGPU_PROJECT_REASON_CAPACITY)";
 const char *kChannelNames[9] = {"1", "2", "3a", "4", "5", "3b", "Unknown", "Unknown", "Unknown"};
 
 // Rust's `{}` for an f32: shortest decimal that round-trips, never in exponent form.
@@ -85,6 +87,7 @@ void throw_for(const ImageResult &r, int contrast)
     case apt::map::kReasonPixel: throw Error{ErrorKind::Internal, kMapPixel};
     case apt::sat::kReasonSgp4: throw Error{ErrorKind::Internal, kSatSgp4};
     case apt::png::kReasonCapacity: throw Error{ErrorKind::Internal, kPngCapacity};
+    case apt::project::kReasonCapacity: throw Error{ErrorKind::Internal, kProjectCapacity};
     default: throw Error{ErrorKind::Internal, "image stage failed"};
     }
     (void)contrast;
@@ -243,6 +246,36 @@ struct MapCall {
     const apt::map::Layers *layers;
 };
 
+// The reprojection of one call or recording (the *_project entry points) after its checks: the grid, its graticule
+// and the yaw / hscale / vscale of the geometry (the overlay's settings when one is drawn).
+struct ProjectCall {
+    apt::project::Grid grid;
+    std::vector<uint8_t> flags;
+    aptgpu_map_settings ms;
+    uint64_t bytes() const { return static_cast<uint64_t>(grid.width) * grid.height * 4u; }
+};
+
+ProjectCall project_args(const aptgpu_projection_settings *proj, const aptgpu_map_settings *map)
+{
+    ProjectCall c;
+    c.grid = apt::project::checked(proj);
+    c.flags = apt::project::graticule(c.grid, proj->grid_deg);
+    c.ms = aptgpu_map_settings{sizeof(aptgpu_map_settings), 0, 0., 1., 1.};
+    if (map) {
+        if (map->struct_size < sizeof(aptgpu_map_settings))
+            throw Error{ErrorKind::Invalid, "aptgpu_map_settings: struct_size not set"};
+        c.ms = *map;
+    }
+    return c;
+}
+
+// The projection reads the unrotated image and north is up by construction.
+void project_rotate(int rotate)
+{
+    if (rotate != APTGPU_ROTATE_NO)
+        throw Error{ErrorKind::Invalid, "a projection takes rotate = APTGPU_ROTATE_NO only: it reads the unrotated image and north is up by construction"};
+}
+
 // The checks of the map entry points, after color_args (so Rotate::Orbit stays Unsupported first).
 void map_args(int channels, const aptgpu_map_settings *map, const aptgpu_map_layers *layers)
 {
@@ -340,7 +373,7 @@ void png_to_host(hipStream_t s, const uint8_t *d_png, size_t len, uint8_t **png_
 int process_image(const aptgpu_context *ctx, const float *signal, size_t n, int contrast, float percent, int rotate,
                   const aptgpu_color_settings *color, int channels, const MapCall *map, const double *positions,
                   uint8_t **image_out, size_t *n_out, aptgpu_image_result *info, char *err, size_t err_cap,
-                  bool png = false, const apt::sat::TrackCall *sat = nullptr)
+                  bool png = false, const apt::sat::TrackCall *sat = nullptr, const ProjectCall *pj = nullptr)
 {
     if ((!signal && n) || !image_out || !n_out) return APTGPU_ERR_INVALID;
     *image_out = nullptr;
@@ -352,9 +385,11 @@ int process_image(const aptgpu_context *ctx, const float *signal, size_t n, int 
         if (map && n / 2080 == 0 && n != 0)
             throw Error{ErrorKind::Internal, "map overlay: the image has no row to draw on"};
         if (png && n / 2080 == 0 && n != 0) throw Error{ErrorKind::Invalid, "PNG encoding: the image has no row"};
+        if (pj && n / 2080 == 0 && n != 0) throw Error{ErrorKind::Internal, "reprojection: the image has no row to read"};
         std::vector<uint32_t> packed;  // (outlives the call's stream: ~ImageCall synchronises it)
         std::shared_ptr<const apt::lab::Tables> lab_tables;  // (likewise)
         apt::map::Device map_dev;  // (likewise)
+        apt::project::Device project_dev;  // (likewise)
         ImageCall c(ctx, signal, n);
         hipStream_t s = c.sc.stream;
         process_limits(ctx, c, contrast, percent, info, lab);
@@ -398,10 +433,34 @@ int process_image(const aptgpu_context *ctx, const float *signal, size_t n, int 
                                             map_colors(*map->layers), static_cast<uint32_t>(height),
                                             rotate == APTGPU_ROTATE_YES, d_img.ptr, c.d_info.ptr);
             }
+        } else if (pj) {  // no overlay: the track's x offsets and the call's checks alone
+            const size_t height = n / 2080;
+            map_dev.prepare_track(s, height);
+            if (sat) {
+                apt::map::image_map_track_sat(s, map_dev, *sat, pj->ms.yaw, pj->ms.hscale, pj->ms.vscale, c.d_info.ptr);
+            } else {
+                map_dev.upload_track(s, positions, height);
+                apt::map::image_map_track(s, map_dev,
+                                          apt::map::scalars(positions, height, pj->ms.yaw, pj->ms.hscale, pj->ms.vscale),
+                                          static_cast<uint32_t>(height), c.d_info.ptr);
+            }
         }
         apt::DeviceBuffer<char> pws;
-        apt::DeviceBuffer<uint8_t> d_png;
-        if (png) {
+        apt::DeviceBuffer<uint8_t> d_png, d_grid;
+        if (pj) {
+            d_grid.alloc(pj->bytes() + 16);
+            project_dev.upload_flags(s, pj->flags);
+            apt::map::Scalars host_sc{};
+            if (!sat) host_sc = apt::map::scalars(positions, n / 2080, pj->ms.yaw, pj->ms.hscale, pj->ms.vscale);
+            apt::project::image_project(s, project_dev, map_dev, sat ? nullptr : &host_sc, pj->grid, d_img.ptr, channels,
+                                        d_grid.ptr, pj->bytes(), c.d_info.ptr);
+            if (png) {
+                png_shape(pj->grid.width, pj->grid.height, 4);
+                const uint64_t cap = apt::png::bound(pj->grid.width, pj->grid.height, 4);
+                d_png.alloc(cap);
+                apt::project::image_project_png(s, project_dev, pj->grid, d_grid.ptr, d_png.ptr, cap, c.d_info.ptr);
+            }
+        } else if (png) {
             const uint32_t height = static_cast<uint32_t>(n / 2080);
             const uint64_t stream = png_shape(2080, height, channels);
             const uint64_t cap = apt::png::bound(2080, height, channels);
@@ -417,14 +476,15 @@ int process_image(const aptgpu_context *ctx, const float *signal, size_t n, int 
             png_to_host(s, d_png.ptr, r.reserved, image_out, n_out);
             return APTGPU_OK;
         }
-        uint8_t *h = host_alloc<uint8_t>(bytes);
-        if (bytes && (hipMemcpyAsync(h, d_img.ptr, bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
-                      hipStreamSynchronize(s) != hipSuccess)) {
+        const size_t out_bytes = pj ? static_cast<size_t>(pj->bytes()) : bytes;
+        uint8_t *h = host_alloc<uint8_t>(out_bytes);
+        if (out_bytes && (hipMemcpyAsync(h, pj ? d_grid.ptr : d_img.ptr, out_bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                          hipStreamSynchronize(s) != hipSuccess)) {
             std::free(h);
             throw Error{ErrorKind::Hip, "D2H copy failed"};
         }
         *image_out = h;
-        *n_out = bytes;
+        *n_out = out_bytes;
         return APTGPU_OK;
     });
 }
@@ -433,7 +493,9 @@ int plan_process_image(aptgpu_plan *plan, int count, const float *const *d_rows,
                        float percent, int rotate, const aptgpu_color_settings *color, int channels, const MapCall *map,
                        const double *const *positions, const size_t *n_positions, uint8_t *const *d_images, char *err,
                        size_t err_cap, uint8_t *const *d_png = nullptr, const size_t *png_cap = nullptr,
-                       const aptgpu_orbit_settings *const *orbit = nullptr, const apt::map::Layers *orbit_layers = nullptr)
+                       const aptgpu_orbit_settings *const *orbit = nullptr, const apt::map::Layers *orbit_layers = nullptr,
+                       const std::vector<ProjectCall> *pj = nullptr, uint8_t *const *d_out = nullptr,
+                       const size_t *out_cap = nullptr)
 {
     if (!plan || count < 0 || !d_rows || !rows_cap || !d_images) return APTGPU_ERR_INVALID;
     if (map && count > 0 && (!positions || !n_positions)) return APTGPU_ERR_INVALID;
@@ -450,7 +512,8 @@ int plan_process_image(aptgpu_plan *plan, int count, const float *const *d_rows,
                 if ((sats.back().draw_map != nullptr) != (sats.front().draw_map != nullptr))
                     throw Error{ErrorKind::Invalid, "draw_map must be set for every recording of the call or for none"};
             }
-            if (!sats.empty() && sats.front().draw_map) {
+            // (with a projection the layer set alone asks for the overlay; its settings are the projection's)
+            if (!sats.empty() && (pj ? orbit_layers != nullptr : sats.front().draw_map != nullptr)) {
                 if (!orbit_layers) throw Error{ErrorKind::Invalid, "draw_map needs a layer set"};
                 if (channels != 4) throw Error{ErrorKind::Invalid, "the map overlay needs channels = 4 (RGBA)"};
             }
@@ -466,6 +529,10 @@ int plan_process_image(aptgpu_plan *plan, int count, const float *const *d_rows,
             if (!d_rows[i] || !d_images[i]) throw Error{ErrorKind::Invalid, "null device pointer"};
             if (map && !positions[i] && n_positions[i]) throw Error{ErrorKind::Invalid, "null sat_positions"};
             if (d_png && !d_png[i]) throw Error{ErrorKind::Invalid, "null device pointer (d_png)"};
+            if (pj && !orbit && (!positions || !n_positions || (!positions[i] && n_positions[i])))
+                throw Error{ErrorKind::Invalid, "null sat_positions"};
+            if (pj && (!d_out[i] || (reinterpret_cast<uintptr_t>(d_out[i]) & 3u)))
+                throw Error{ErrorKind::Invalid, "d_out must be non-null and 4-byte aligned"};
             if (reinterpret_cast<uintptr_t>(d_images[i]) & align)
                 throw Error{ErrorKind::Invalid, channels == 4 ? "d_images must be 16-byte aligned for channels = 4"
                                                               : "d_images must be 4-byte aligned"};
@@ -476,10 +543,12 @@ int plan_process_image(aptgpu_plan *plan, int count, const float *const *d_rows,
             plan->enqueue_image_color(i, d_rows[i], static_cast<uint64_t>(rows_cap[i]) * 2080u, contrast, percent,
                                       rotates[static_cast<size_t>(i)] == APTGPU_ROTATE_YES, colored ? &tune : nullptr,
                                       channels, d_images[i], lab);
-        if (!sats.empty() && sats.front().draw_map)
+        const bool orbit_overlay = !sats.empty() && (pj ? orbit_layers != nullptr : sats.front().draw_map != nullptr);
+        if (orbit_overlay)
             for (int i = 0; i < count; ++i)
                 plan->enqueue_image_map_sat(i, static_cast<uint64_t>(rows_cap[i]) * 2080u, *orbit_layers,
-                                            sats[static_cast<size_t>(i)].call, *sats[static_cast<size_t>(i)].draw_map,
+                                            sats[static_cast<size_t>(i)].call,
+                                            pj ? (*pj)[static_cast<size_t>(i)].ms : *sats[static_cast<size_t>(i)].draw_map,
                                             map_colors(*orbit_layers),
                                             rotates[static_cast<size_t>(i)] == APTGPU_ROTATE_YES, d_images[i]);
         if (map)
@@ -487,6 +556,17 @@ int plan_process_image(aptgpu_plan *plan, int count, const float *const *d_rows,
                 plan->enqueue_image_map(i, static_cast<uint64_t>(rows_cap[i]) * 2080u, *map->layers,
                                         map_scalars(*map, positions[i], n_positions[i]), map_colors(*map->layers),
                                         positions[i], n_positions[i], rotate == APTGPU_ROTATE_YES, d_images[i]);
+        if (pj) {
+            for (int i = 0; i < count; ++i) {
+                const ProjectCall &c = (*pj)[static_cast<size_t>(i)];
+                plan->enqueue_image_project(i, static_cast<uint64_t>(rows_cap[i]) * 2080u, channels, d_images[i], c.grid,
+                                            c.flags, c.ms, map != nullptr || orbit_overlay,
+                                            positions ? positions[i] : nullptr, n_positions ? n_positions[i] : 0,
+                                            orbit ? &sats[static_cast<size_t>(i)].call : nullptr, d_out[i], out_cap[i],
+                                            d_png ? d_png[i] : nullptr, d_png ? png_cap[i] : 0);
+            }
+            return APTGPU_OK;
+        }
         if (d_png)
             for (int i = 0; i < count; ++i)
                 plan->enqueue_image_png(i, static_cast<uint64_t>(rows_cap[i]) * 2080u, channels, d_images[i], d_png[i],
@@ -871,6 +951,147 @@ int aptgpu_plan_process_device_image_orbit(aptgpu_plan *plan, int count, const f
     return plan_process_image(plan, count, d_rows, rows_cap, contrast, percent, rotate, color, channels, nullptr,
                               nullptr, nullptr, d_images, err, err_cap, d_png, png_cap, orbit,
                               layers ? &layers->layers : nullptr);
+}
+
+int aptgpu_projection_fit(const double *track, size_t count, double hscale, int kind, double step_deg,
+                          uint32_t max_width, aptgpu_projection_settings *out, char *err, size_t err_cap)
+{
+    if ((!track && count) || !out) return APTGPU_ERR_INVALID;
+    return guarded(err, err_cap, [&] {
+        apt::project::fit(track, count, hscale, kind, step_deg, max_width, out);
+        return APTGPU_OK;
+    });
+}
+
+int aptgpu_project_image(const aptgpu_context *ctx, const uint8_t *image, uint32_t height, int channels,
+                         const double *sat_positions, size_t n_positions, const aptgpu_map_settings *map,
+                         const aptgpu_projection_settings *proj, int output, const aptgpu_png_settings *png,
+                         uint8_t **out, size_t *n_out, char *err, size_t err_cap)
+{
+    if (!out || !n_out) return APTGPU_ERR_INVALID;
+    *out = nullptr;
+    *n_out = 0;
+    return guarded(err, err_cap, [&] {
+        // (every check before the device is touched)
+        if (output != APTGPU_OUTPUT_PIXELS && output != APTGPU_OUTPUT_PNG)
+            throw Error{ErrorKind::Invalid, "unknown output kind"};
+        if (output == APTGPU_OUTPUT_PNG) png_args(png);
+        if (channels != 1 && channels != 4) throw Error{ErrorKind::Invalid, "channels must be 1 (gray) or 4 (RGBA)"};
+        const ProjectCall pj = project_args(proj, map);
+        if (!image || height == 0) throw Error{ErrorKind::Invalid, "reprojection: the image has no row to read"};
+        if (!sat_positions) throw Error{ErrorKind::Invalid, "null sat_positions"};
+        if (output == APTGPU_OUTPUT_PNG) png_shape(pj.grid.width, pj.grid.height, 4);
+        const size_t bytes = static_cast<size_t>(height) * 2080u * static_cast<size_t>(channels);
+        apt::map::Device map_dev;  // (outlive the call's stream: ~Scratch synchronises it)
+        apt::project::Device project_dev;
+        ImageResult rec{};
+        rec.height = height;
+        rec.channel_a = rec.channel_b = -1;
+        rec.n_px = static_cast<uint64_t>(height) * 2080u;
+        Scratch sc(ctx);
+        hipStream_t s = sc.stream;
+        apt::DeviceBuffer<uint8_t> d_img, d_grid, d_png;
+        apt::DeviceBuffer<ImageResult> d_info;
+        d_img.alloc(bytes + 16);
+        d_grid.alloc(pj.bytes() + 16);
+        d_info.alloc(1);
+        apt::hip_check(hipMemcpyAsync(d_img.ptr, image, bytes, hipMemcpyHostToDevice, s), "hipMemcpyAsync H2D");
+        apt::hip_check(hipMemcpyAsync(d_info.ptr, &rec, sizeof rec, hipMemcpyHostToDevice, s), "hipMemcpyAsync H2D");
+        map_dev.prepare_track(s, height);
+        map_dev.upload_track(s, sat_positions, n_positions);
+        const apt::map::Scalars msc = apt::map::scalars(sat_positions, n_positions, pj.ms.yaw, pj.ms.hscale, pj.ms.vscale);
+        apt::map::image_map_track(s, map_dev, msc,
+                                  n_positions < 0xffffffffu ? static_cast<uint32_t>(n_positions) : 0xffffffffu, d_info.ptr);
+        project_dev.upload_flags(s, pj.flags);
+        apt::project::image_project(s, project_dev, map_dev, &msc, pj.grid, d_img.ptr, channels, d_grid.ptr, pj.bytes(),
+                                    d_info.ptr);
+        if (output == APTGPU_OUTPUT_PNG) {
+            const uint64_t cap = apt::png::bound(pj.grid.width, pj.grid.height, 4);
+            d_png.alloc(cap);
+            apt::project::image_project_png(s, project_dev, pj.grid, d_grid.ptr, d_png.ptr, cap, d_info.ptr);
+        }
+        apt::hip_check(hipGetLastError(), "kernel launch (reprojection)");
+        ImageResult r{};
+        apt::hip_check(hipMemcpyAsync(&r, d_info.ptr, sizeof r, hipMemcpyDeviceToHost, s), "hipMemcpyAsync D2H");
+        apt::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
+        throw_for(r, APTGPU_CONTRAST_MINMAX);
+        if (output == APTGPU_OUTPUT_PNG) {
+            png_to_host(s, d_png.ptr, r.reserved, out, n_out);
+            return APTGPU_OK;
+        }
+        png_to_host(s, d_grid.ptr, static_cast<size_t>(pj.bytes()), out, n_out);
+        return APTGPU_OK;
+    });
+}
+
+int aptgpu_process_image_project(const aptgpu_context *ctx, const float *signal, size_t n, int contrast, float percent,
+                                 int rotate, const aptgpu_color_settings *color, int channels,
+                                 const aptgpu_map_settings *map, const aptgpu_map_layers *layers,
+                                 const double *sat_positions, const aptgpu_orbit_settings *orbit,
+                                 const aptgpu_projection_settings *proj, int output, const aptgpu_png_settings *png,
+                                 uint8_t **out, size_t *n_out, aptgpu_image_result *info, char *err, size_t err_cap)
+{
+    SatCall c{};
+    ProjectCall pj{};
+    const int rc = guarded(err, err_cap, [&] {
+        if (output != APTGPU_OUTPUT_PIXELS && output != APTGPU_OUTPUT_PNG)
+            throw Error{ErrorKind::Invalid, "unknown output kind"};
+        project_rotate(rotate);
+        if ((sat_positions != nullptr) == (orbit != nullptr))
+            throw Error{ErrorKind::Invalid, "a projection needs exactly one of sat_positions and aptgpu_orbit_settings"};
+        apt::gpu::ColorTune tune{};
+        bool lab = false;
+        color_args(contrast, rotate, color, channels, &tune, &lab);
+        if (orbit) c = orbit_args(orbit);
+        if (output == APTGPU_OUTPUT_PNG) png_args(png);
+        pj = project_args(proj, map ? map : c.draw_map);
+        if (layers) map_args(channels, &pj.ms, layers);
+        if (output == APTGPU_OUTPUT_PNG) png_shape(pj.grid.width, pj.grid.height, 4);
+        return APTGPU_OK;
+    });
+    if (rc != APTGPU_OK) return rc;
+    MapCall m{&pj.ms, layers ? &layers->layers : nullptr};
+    return process_image(ctx, signal, n, contrast, percent, rotate, color, channels, layers ? &m : nullptr, sat_positions,
+                         out, n_out, info, err, err_cap, output == APTGPU_OUTPUT_PNG, orbit ? &c.call : nullptr, &pj);
+}
+
+int aptgpu_plan_process_device_image_project(aptgpu_plan *plan, int count, const float *const *d_rows,
+                                             const size_t *rows_cap, int contrast, float percent, int rotate,
+                                             const aptgpu_color_settings *color, int channels,
+                                             const aptgpu_map_settings *map, const aptgpu_map_layers *layers,
+                                             const double *const *sat_positions, const size_t *n_positions,
+                                             const aptgpu_orbit_settings *const *orbit, uint8_t *const *d_images,
+                                             const aptgpu_projection_settings *proj, uint8_t *const *d_out,
+                                             const size_t *out_cap, const aptgpu_png_settings *png,
+                                             uint8_t *const *d_png, const size_t *png_cap, char *err, size_t err_cap)
+{
+    if (count < 0 || (count > 0 && (!proj || !d_out || !out_cap)) || (d_png && !png_cap)) return APTGPU_ERR_INVALID;
+    std::vector<ProjectCall> pj;
+    const int rc = guarded(err, err_cap, [&] {
+        project_rotate(rotate);
+        if ((sat_positions != nullptr) == (orbit != nullptr) || (sat_positions && !n_positions))
+            throw Error{ErrorKind::Invalid, "a projection needs exactly one of sat_positions and aptgpu_orbit_settings"};
+        apt::gpu::ColorTune tune{};
+        bool lab = false;
+        color_args(contrast, rotate, color, channels, &tune, &lab);
+        if (d_png) png_args(png);
+        for (int i = 0; i < count; ++i) {
+            if (orbit && !orbit[i]) throw Error{ErrorKind::Invalid, "aptgpu_orbit_settings: struct_size not set"};
+            pj.push_back(project_args(proj + i, map ? map : (orbit ? orbit[i]->draw_map : nullptr)));
+            if (d_png) png_shape(pj.back().grid.width, pj.back().grid.height, 4);
+        }
+        if (layers && count > 0) map_args(channels, &pj.front().ms, layers);
+        return APTGPU_OK;
+    });
+    if (rc != APTGPU_OK) return rc;
+    if (orbit)
+        return plan_process_image(plan, count, d_rows, rows_cap, contrast, percent, rotate, color, channels, nullptr,
+                                  nullptr, nullptr, d_images, err, err_cap, d_png, png_cap, orbit,
+                                  layers ? &layers->layers : nullptr, &pj, d_out, out_cap);
+    MapCall m{count > 0 ? &pj.front().ms : nullptr, layers ? &layers->layers : nullptr};
+    return plan_process_image(plan, count, d_rows, rows_cap, contrast, percent, rotate, color, channels,
+                              layers && count > 0 ? &m : nullptr, sat_positions, n_positions, d_images, err, err_cap, d_png,
+                              png_cap, nullptr, nullptr, &pj, d_out, out_cap);
 }
 
 int aptgpu_map_layers_create(aptgpu_map_layers **out)

@@ -24,6 +24,7 @@
 // f32, one rounding per operation, as the crate's.
 #include "apt_kernels_map.hpp"
 
+#include "apt_kernels_map_dev.hpp"
 #include "apt_kernels_track.hpp"
 
 #include <cmath>
@@ -37,37 +38,11 @@ namespace {
 
 using apt::gpu::ImageResult;
 
-constexpr double kPi = 3.14159265358979323846;  // std::f64::consts::PI
 constexpr int kPx = 2080;
 constexpr int kThreads = 256;
 constexpr int kScanItems = 8;
 constexpr int kScanBlock = kThreads * kScanItems;
 constexpr int kListBlocks = 1024;
-constexpr uint32_t kSkip = 1;  // ctl[1]: the image stage failed before the overlay; nothing to draw or report
-
-// latlon_to_rel_px, map.rs:71-100 (geo::azimuth and geo::distance inlined, geo.rs:34-62)
-__device__ inline void rel_px(const Scalars &s, double lat, double lon, double &x, double &y)
-{
-    const double dl = lon - s.start_lon;
-    const double az = atan2(sin(dl), cos(s.start_lat) * tan(lat) - sin(s.start_lat) * cos(dl));
-    const double B = az - s.ref_az;
-    const double dl2 = s.start_lon - lon;
-    double cc = sin(lat) * sin(s.start_lat) + cos(lat) * cos(s.start_lat) * cos(dl2);
-    cc = fmin(fmax(cc, -1.), 1.);
-    // f64::max / min ignore NaN, as fmax / fmin do
-    const double c = fmin(fmax(acos(cc), -kPi / 3.), kPi / 3.);
-    const double a = atan(cos(B) * tan(c));
-    const double b = asin(sin(B) * sin(c));
-    x = -b / s.x_res;
-    y = a / s.y_res + s.yaw * x;
-}
-
-// (y.max(0.) as usize).min(height - 1): the cast saturates (inf -> usize::MAX), NaN -> 0
-__device__ inline uint32_t est_row(double y, uint32_t h)
-{
-    const double m = fmax(y, 0.);
-    return m >= static_cast<double>(h - 1) ? h - 1 : static_cast<uint32_t>(m);
-}
 
 // line_drawing 1.0.0's XiaolinWu<f64, i32> from (sx, sy) to (ex, ey), calling emit(x, y, value) for the points
 // that pass map.rs's band test x in (-456, 456), y in (0, h).  Stops once the major axis has left the band (nothing
@@ -404,28 +379,6 @@ __global__ __launch_bounds__(kThreads) void k_map_scatter(const uint64_t *frags,
     }
 }
 
-// image 0.24.7's Rgba<u8>::blend (src-over in f32, truncating casts), with its alpha 0 / 255 fast paths
-__device__ inline uint32_t blend(uint32_t bg, uint32_t fg)
-{
-    const uint32_t fa8 = fg >> 24;
-    if (fa8 == 0) return bg;
-    if (fa8 == 255) return fg;
-    const float m = 255.f;
-    const float br = static_cast<float>(bg & 255u) / m, bgc = static_cast<float>((bg >> 8) & 255u) / m;
-    const float bb = static_cast<float>((bg >> 16) & 255u) / m, ba = static_cast<float>(bg >> 24) / m;
-    const float fr = static_cast<float>(fg & 255u) / m, fgc = static_cast<float>((fg >> 8) & 255u) / m;
-    const float fb = static_cast<float>((fg >> 16) & 255u) / m, fa = static_cast<float>(fa8) / m;
-    const float af = ba + fa - ba * fa;
-    if (af == 0.f) return bg;
-    const float k = 1.f - fa;
-    const float orr = (fr * fa + (br * ba) * k) / af;
-    const float og = (fgc * fa + (bgc * ba) * k) / af;
-    const float ob = (fb * fa + (bb * ba) * k) / af;
-    const uint32_t r = static_cast<uint32_t>(m * orr), g = static_cast<uint32_t>(m * og);
-    const uint32_t b = static_cast<uint32_t>(m * ob), a = static_cast<uint32_t>(m * af);
-    return (r & 255u) | ((g & 255u) << 8) | ((b & 255u) << 16) | ((a & 255u) << 24);
-}
-
 __device__ inline void sift_down(uint32_t *a, uint32_t root, uint32_t n)
 {
     const uint32_t v = a[root];
@@ -524,6 +477,32 @@ Device::~Device()
     }
 }
 
+void Device::prepare_control(hipStream_t s)
+{
+    if (ctl) return;
+    dev_alloc(ctl, kCtlWords, "hipMalloc (map control)");
+    dev_alloc(scalars, 1, "hipMalloc (map control)");
+    apt::hip_check(hipMemsetAsync(ctl, 0, kCtlWords * sizeof(uint32_t), s), "hipMemsetAsync");
+}
+
+void Device::prepare_track(hipStream_t s, size_t rows)
+{
+    prepare_control(s);
+    if (rows_cap >= rows && track) return;
+    // (the overlay's per-pixel lists are sized by rows_cap too: prepare() makes them anew when it finds them gone)
+    for (void *p : {static_cast<void *>(cnt), static_cast<void *>(base)})
+        if (p) (void)hipFree(p);
+    cnt = base = nullptr;
+    rows_cap = rows > rows_cap ? rows : rows_cap;
+    dev_alloc(track, 2 * rows_cap, "hipMalloc (map track)");
+    dev_alloc(xoff, rows_cap, "hipMalloc (map track)");
+    for (int k = 0; k < kTrackRing; ++k) {
+        if (track_ev[k]) apt::hip_check(hipEventSynchronize(track_ev[k]), "hipEventSynchronize");
+        if (track_host[k]) (void)hipHostFree(track_host[k]);
+        track_host[k] = nullptr;
+    }
+}
+
 void Device::prepare(hipStream_t s, const Layers &layers, size_t rows)
 {
     const size_t n = layers.xy.size() / 2;
@@ -531,9 +510,7 @@ void Device::prepare(hipStream_t s, const Layers &layers, size_t rows)
         dev_alloc(frags, kMaxFragments, "hipMalloc (map fragments)");
         dev_alloc(slot, 2 * static_cast<size_t>(kMaxFragments), "hipMalloc (map runs)");
         dev_alloc(runs, 2 * static_cast<size_t>(kMaxFragments), "hipMalloc (map runs)");
-        dev_alloc(ctl, kCtlWords, "hipMalloc (map control)");
-        dev_alloc(scalars, 1, "hipMalloc (map control)");
-        apt::hip_check(hipMemsetAsync(ctl, 0, kCtlWords * sizeof(uint32_t), s), "hipMemsetAsync");
+        prepare_control(s);
         frag_ready = true;
     }
     if (vert_cap < n + 1 || !verts) {
@@ -605,6 +582,21 @@ void image_map_overlay(hipStream_t s, Device &d, const Scalars &sc, const Colors
     k_map_track<<<blocks(rows, kThreads), kThreads, 0, s>>>(d.track, count, rows, sc, d.xoff, info, d.ctl);
     k_map_project<<<blocks(n, kThreads), kThreads, 0, s>>>(d.verts, n, sc, d.proj);
     overlay_tail(s, d, n, colors, rotate, img, info);
+}
+
+void image_map_track(hipStream_t s, Device &d, const Scalars &sc, uint32_t count, ImageResult *info)
+{
+    const uint32_t rows = static_cast<uint32_t>(d.rows_cap < count ? d.rows_cap : count);
+    k_map_track<<<blocks(rows, kThreads), kThreads, 0, s>>>(d.track, count, rows, sc, d.xoff, info, d.ctl);
+}
+
+void image_map_track_sat(hipStream_t s, Device &d, const apt::sat::TrackCall &call, double yaw, double hscale,
+                         double vscale, ImageResult *info)
+{
+    const uint32_t rows = static_cast<uint32_t>(d.rows_cap < 0xffffffffu ? d.rows_cap : 0xffffffffu);
+    apt::sat::track(s, call, info, 0, rows, d.track, d.ctl + 3);
+    apt::sat::scalars(s, d.track, info, rows, yaw, hscale, vscale, d.scalars, d.ctl + 4);
+    k_map_track_dev<<<blocks(rows, kThreads), kThreads, 0, s>>>(d.track, rows, d.scalars, d.xoff, info, d.ctl);
 }
 
 void image_map_overlay_sat(hipStream_t s, Device &d, const apt::sat::TrackCall &call, double yaw, double hscale,

@@ -49,6 +49,10 @@ struct Device {
     ~Device();
     // (re)allocates for rows_cap rows and uploads the layer set when its generation differs, on stream s
     void prepare(hipStream_t s, const Layers &layers, size_t rows_cap);
+    // the control words and the scalars alone (both prepare forms call it)
+    void prepare_control(hipStream_t s);
+    // the part of prepare() the reprojection needs when no overlay is drawn: control words, track and x offsets
+    void prepare_track(hipStream_t s, size_t rows_cap);
     // copies min(count, rows_cap) positions to the device through the next staging buffer of the ring; waits on the
     // host only while that buffer's upload of kTrackRing calls ago is still queued
     void upload_track(hipStream_t s, const double *positions, size_t count);
@@ -68,5 +72,12 @@ void image_map_overlay(hipStream_t s, Device &dev, const Scalars &sc, const Colo
 void image_map_overlay_sat(hipStream_t s, Device &dev, const apt::sat::TrackCall &call, double yaw, double hscale,
                            double vscale, const Colors &colors, bool rotate, uint8_t *img,
                            apt::gpu::ImageResult *info);
+
+// The first launch of either form alone, for a consumer that needs the track's x offsets but no overlay (the
+// reprojection, apt_kernels_project.hpp): dev.xoff for every row and the call's checks in dev.ctl[1] (kReasonCount,
+// apt::sat::kReasonSgp4, or 1 when info already carries a status).  The record itself is not written.
+void image_map_track(hipStream_t s, Device &dev, const Scalars &sc, uint32_t count, apt::gpu::ImageResult *info);
+void image_map_track_sat(hipStream_t s, Device &dev, const apt::sat::TrackCall &call, double yaw, double hscale,
+                         double vscale, apt::gpu::ImageResult *info);
 
 }  // namespace apt::map

@@ -1020,6 +1020,42 @@ void aptgpu_plan::enqueue_image_map_sat(int i, uint64_t rows_cap_floats, const a
     apt::hip_check(hipGetLastError(), "kernel launch (map overlay)");
 }
 
+void aptgpu_plan::enqueue_image_project(int i, uint64_t rows_cap_floats, int channels, const uint8_t *d_image,
+                                        const apt::project::Grid &grid, const std::vector<uint8_t> &flags,
+                                        const aptgpu_map_settings &ms, bool overlay_done, const double *positions,
+                                        size_t count, const apt::sat::TrackCall *sat, uint8_t *d_out, uint64_t out_cap,
+                                        uint8_t *d_png, uint64_t png_cap)
+{
+    const ImageTarget t = image_target(i, rows_cap_floats);
+    Slot &sl = t.slot;
+    if (!sl.map) sl.map = std::make_unique<apt::map::Device>();
+    if (!sl.project) sl.project = std::make_unique<apt::project::Device>();
+    apt::map::Scalars sc{};
+    if (!sat) sc = apt::map::scalars(positions, count, ms.yaw, ms.hscale, ms.vscale);
+    if (!overlay_done) {
+        sl.map->prepare_track(t.stream, t.cap / 2080u);
+        timed(t.stream, "image_project_track", [&] {
+            if (sat) {
+                apt::map::image_map_track_sat(t.stream, *sl.map, *sat, ms.yaw, ms.hscale, ms.vscale, t.out);
+            } else {
+                sl.map->upload_track(t.stream, positions, count);
+                apt::map::image_map_track(t.stream, *sl.map, sc,
+                                          count < 0xffffffffu ? static_cast<uint32_t>(count) : 0xffffffffu, t.out);
+            }
+        });
+    }
+    sl.project->upload_flags(t.stream, flags);
+    timed(t.stream, "image_project", [&] {
+        apt::project::image_project(t.stream, *sl.project, *sl.map, sat ? nullptr : &sc, grid, d_image, channels, d_out,
+                                    out_cap, t.out);
+    });
+    if (d_png)
+        timed(t.stream, "image_project_png", [&] {
+            apt::project::image_project_png(t.stream, *sl.project, grid, d_out, d_png, png_cap, t.out);
+        });
+    apt::hip_check(hipGetLastError(), "kernel launch (reprojection)");
+}
+
 void aptgpu_plan::enqueue_image_png(int i, uint64_t rows_cap_floats, int channels, const uint8_t *d_image,
                                     uint8_t *d_png, uint64_t png_cap)
 {

@@ -15,6 +15,7 @@
 #include "apt_kernels_color.hpp"
 #include "apt_kernels_map.hpp"
 #include "apt_kernels_png.hpp"
+#include "apt_kernels_project.hpp"
 #include "apt_wav.hpp"
 
 namespace apt {
@@ -183,6 +184,7 @@ struct aptgpu_plan {
         apt::DeviceBuffer<char> lab_ws;    // Lab tables + per-call RGBA table, on first use of the Lab path
         uint64_t lab_gen = 0;              // generation of the palette whose Lab tables lab_ws holds (0 = none)
         std::unique_ptr<apt::map::Device> map;  // the map overlay's layer set, lists and track, on first use
+        std::unique_ptr<apt::project::Device> project;  // the reprojection's graticule, record and PNG scratch, on first use
         apt::DeviceBuffer<char> png_ws;    // the PNG encoder's filtered stream, staging and chunk records, on first use
         apt::DeviceBuffer<float> ingest;   // WAV -> f32 staging when the fused PCM16 path does not apply
     };
@@ -234,6 +236,15 @@ struct aptgpu_plan {
     // stream: the file goes to d_png (png_cap bytes), its length to the image record.
     void enqueue_image_png(int i, uint64_t rows_cap_floats, int channels, const uint8_t *d_image, uint8_t *d_png,
                            uint64_t png_cap);
+    // The reprojection (apt_kernels_project.hpp) of recording i's finished, unrotated image onto `grid` into d_out
+    // (out_cap bytes), behind everything above on the same stream, then optionally its PNG file into d_png.  With
+    // overlay_done the overlay's launches left the track's x offsets and scalars in the slot; otherwise they are
+    // computed here first, from `positions` (count pairs, scalars on the host) or from `sat` (on the device).
+    void enqueue_image_project(int i, uint64_t rows_cap_floats, int channels, const uint8_t *d_image,
+                               const apt::project::Grid &grid, const std::vector<uint8_t> &flags,
+                               const aptgpu_map_settings &ms, bool overlay_done, const double *positions, size_t count,
+                               const apt::sat::TrackCall *sat, uint8_t *d_out, uint64_t out_cap, uint8_t *d_png,
+                               uint64_t png_cap);
     // The false-colour palette (256*256*3 RGB).  The plan keeps a host copy; bytes that differ from it start a new
     // generation, which every slot uploads on its own stream the next time it colours an image.  lab: also the
     // palette's Lab tables (apt_lab.hpp), computed once per generation and uploaded per slot likewise.

@@ -15,6 +15,10 @@ shape (16 recordings x 600 s at 48 kHz, 1198 rows each, one decode_device call),
     png_gray          minmax_gray_new + the PNG encoder (colour type 0), the file left in HBM
     png_rgba          the same image as RGBA (colour type 6: what the reference's RgbaImage saves as)
     png_color         color_rgba + the PNG encoder
+    project_nearest   color_rgba + the reprojection onto the equirectangular grid that projection_fit
+                      sizes for the track at 0.04 degrees per pixel, nearest sampling
+    project_bilinear  the same, bilinear
+    project_nearest_png, project_bilinear_png   the same + the PNG encoder on the projected grid
 
 Per kernel: the plan's event timing (every launch bracketed, one call in flight), ms per recording.  Per variant also
 the wall time of one call of 16 recordings with timing off (host clock around enqueue + synchronise).  Last, the host
@@ -131,7 +135,25 @@ def main():
     d_png = [torch.empty(png_cap[0], dtype=torch.uint8, device=dev) for _ in range(RECORDINGS)]
     png = (ptr(d_png), png_cap)
     png_channels = {"png_gray": 1, "png_rgba": 4, "png_color": 4}
+    fit = apt.projection_fit(pos, apt.Projection.EQUIRECTANGULAR, step=0.04)
+    grids = {s: apt.ProjectionSettings(fit.kind, fit.width, fit.height, fit.lat_north, fit.lon_west, fit.step, sampling=s)
+             for s in (apt.Projection.NEAREST, apt.Projection.BILINEAR)}
+    grid_bytes = fit.width * fit.height * 4
+    d_grid = [torch.empty(grid_bytes, dtype=torch.uint8, device=dev) for _ in range(RECORDINGS)]
+    grid_png_cap = [apt.png_bound(fit.width, fit.height, 4)] * RECORDINGS
+    d_grid_png = [torch.empty(grid_png_cap[0], dtype=torch.uint8, device=dev) for _ in range(RECORDINGS)]
+
+    def project(sampling, with_png):
+        return lambda: plan.process_device_image(
+            ptr(d_rows), caps, apt.Contrast.MINMAX, ptr(d_img), color=color, map=[pos] * RECORDINGS,
+            projection=(grids[sampling], ptr(d_grid), [grid_bytes] * RECORDINGS),
+            png=(ptr(d_grid_png), grid_png_cap) if with_png else None)
+
     variants = {
+        "project_nearest": project(apt.Projection.NEAREST, False),
+        "project_bilinear": project(apt.Projection.BILINEAR, False),
+        "project_nearest_png": project(apt.Projection.NEAREST, True),
+        "project_bilinear_png": project(apt.Projection.BILINEAR, True),
         "png_gray": lambda: plan.process_device_image(ptr(d_rows), caps, apt.Contrast.MINMAX, ptr(d_img), png=png),
         "png_rgba": lambda: plan.process_device_image(ptr(d_rows), caps, apt.Contrast.MINMAX, ptr(d_img), channels=4,
                                                       png=png),
@@ -172,6 +194,8 @@ def main():
               f"{RECORDINGS} with a new set {t_first * 1e3:.3f} ms, next call {t_next * 1e3:.3f} ms")
     print(f"image stage, {RECORDINGS} x {SECONDS} s at {RATE} Hz ({rows} rows = {rows * 2080 / 1e6:.2f} Mpx per "
           f"recording), {args.calls} calls per variant; ms per recording")
+    if any(k.startswith("project_") for k in variants):
+        print(f"project_*: grid {fit.width} x {fit.height} = {fit.width * fit.height / 1e6:.2f} Mpx per recording")
     print(f"{'variant':18s} {'kernel':16s} {'ms/rec':>8s}   (launches)")
     for name, call in variants.items():
         for _ in range(3):  # warm-up: code objects, first-use allocations, palette upload
