@@ -2,7 +2,7 @@
  * aptgpu_decode.c — minimal C caller of the drop-in boundary (include/aptgpu.h):
  *
  *     aptgpu_decode in.wav out.pgm [contrast: telemetry|percent|minmax] [--no-sync]
- *                   [--histogram] [--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE] [--png]
+ *                   [--histogram | --histogram-float] [--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE] [--png]
  *                   [--tle FILE --sat NAME (--start-ms N | --end-ms N)] [--rotate no|yes|orbit]
  *                   [--project equirect|mercator[:step_deg] [--grid DEG]]
  *
@@ -10,7 +10,8 @@
  * contrast limits -> 8-bit image, written as a binary PGM, or with --png as the PNG file the GPU
  * encodes (aptgpu_process_image_png: gray, or RGBA with --palette / --map; only the file's bytes
  * cross to the host).  --histogram: Contrast::Histogram (MinMax limits, then each channel's histogram
- * equalised).  --palette FILE: false colour (`-F`, tune values 0) from a raw 256 x 256 RGB palette
+ * equalised).  --histogram-float: APTGPU_CONTRAST_HISTOGRAM_FLOAT, the equalisation on the f32 samples before they
+ * become 8-bit pixels (gray only: refused with --palette).  --palette FILE: false colour (`-F`, tune values 0) from a raw 256 x 256 RGB palette
  * (196 608 bytes, pixel (a, b) at (b*256 + a)*3), written as a binary PPM (the RGBA image without
  * its alpha).  --lab: with --histogram and --palette, equalise the false-colour image as the
  * reference does, channel A in CIE Lab (APTGPU_COLOR_EQUALIZE_LAB); without it that combination
@@ -38,7 +39,7 @@ static void on_status(float progress, const char *text, void *user)
 int main(int argc, char **argv)
 {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s in.wav out.pgm [telemetry|percent|minmax] [--no-sync] [--histogram] "
+        fprintf(stderr, "usage: %s in.wav out.pgm [telemetry|percent|minmax] [--no-sync] [--histogram | --histogram-float] "
                 "[--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE] [--png]\n"
                 "       [--tle FILE --sat NAME (--start-ms N | --end-ms N)] [--rotate no|yes|orbit]\n"
                 "       [--project equirect|mercator[:step_deg] [--grid DEG]]\n", argv[0]);
@@ -55,6 +56,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "percent")) contrast = APTGPU_CONTRAST_PERCENT;
         else if (!strcmp(argv[i], "minmax")) contrast = APTGPU_CONTRAST_MINMAX;
         else if (!strcmp(argv[i], "--histogram")) contrast = APTGPU_CONTRAST_HISTOGRAM;
+        else if (!strcmp(argv[i], "--histogram-float")) contrast = APTGPU_CONTRAST_HISTOGRAM_FLOAT;
         else if (!strcmp(argv[i], "--no-sync")) sync = 0;
         else if (!strcmp(argv[i], "--lab")) lab = 1;
         else if (!strcmp(argv[i], "--png")) png = 1;
@@ -253,7 +255,7 @@ int main(int argc, char **argv)
         rc = aptgpu_process_image_png(&ctx, rows, n_rows_px, contrast, 0.98f, rotate,
                                       palette_path ? &color : NULL, palette_path ? 4 : 1, NULL, NULL, NULL, &ps, &image,
                                       &n_px, &info, err, sizeof err);
-    else if (palette_path || contrast == APTGPU_CONTRAST_HISTOGRAM)
+    else if (palette_path || contrast == APTGPU_CONTRAST_HISTOGRAM || contrast == APTGPU_CONTRAST_HISTOGRAM_FLOAT)
         rc = aptgpu_process_image(&ctx, rows, n_rows_px, contrast, 0.98f, rotate,
                                   palette_path ? &color : NULL, palette_path ? 4 : 1, &image, &n_px, &info, err,
                                   sizeof err);

@@ -256,7 +256,9 @@ int aptgpu_plan_collect_timing(aptgpu_plan *plan, aptgpu_kernel_time *out, size_
  * (f32, "filter_result"), "correlation" (f32, "sync_correlation"), "group_max" (f32, maxima
  * of the correlation over groups of 52 positions), "terminal_words" (u64), "peaks" (u32,
  * find_sync positions), "picker_flags" (u32[32]: [0] list overflow, [1] 1 = sequential
- * fallback ran, [8..] cycle stamps of the picker kernels).  Writes min(bytes, size) bytes
+ * fallback ran, [8..] cycle stamps of the picker kernels), "eqfloat_thresholds" (u32[2][255]: the
+ * sorted threshold keys T_1..T_255 of half A, then of half B, of the slot's last
+ * APTGPU_CONTRAST_HISTOGRAM_FLOAT image; size 0 before the first one).  Writes min(bytes, size) bytes
  * and returns the buffer's size in *size_out. */
 int aptgpu_plan_read_internal(aptgpu_plan *plan, int i, const char *name, void *host_out,
                               size_t bytes, size_t *size_out);
@@ -382,8 +384,10 @@ int aptgpu_find_sync(const aptgpu_context *ctx, const float *signal, size_t n,
 /* (APTGPU_COLOR_EQUALIZE_LAB); the map overlay from a caller-computed track or from a TLE  */
 /* (below).                                                                                  */
 /* aptgpu_process_gray / aptgpu_plan_process_device: the grayscale image of the first     */
-/* three contrasts; aptgpu_process_image / aptgpu_plan_process_device_image: every        */
-/* contrast, optional false colour, gray or RGBA output.                                   */
+/* three contrasts; aptgpu_process_image / aptgpu_plan_process_device_image and their     */
+/* *_map / *_png / *_orbit / *_project forms: every contrast (APTGPU_CONTRAST_HISTOGRAM   */
+/* and APTGPU_CONTRAST_HISTOGRAM_FLOAT too), optional false colour (not with               */
+/* HISTOGRAM_FLOAT), gray or RGBA output.                                                   */
 
 #define APTGPU_CONTRAST_TELEMETRY 0 /* Contrast::Telemetry   src/noaa_apt.rs:141-150 */
 #define APTGPU_CONTRAST_PERCENT 1   /* Contrast::Percent(p)  src/noaa_apt.rs:151-157 */
@@ -391,6 +395,17 @@ int aptgpu_find_sync(const aptgpu_context *ctx, const float *signal, size_t n,
                                        takes the same limits before its equalisation) */
 #define APTGPU_CONTRAST_HISTOGRAM 3 /* Contrast::Histogram: MinMax limits, then per-channel equalisation
                                        (aptgpu_process_image / aptgpu_plan_process_device_image only) */
+/* Histogram equalisation on the f32 signal, before the pixel values become integers (the reference's to-do list,
+ * docs/development.md:105-106; not a reference Contrast).  The image's two halves (columns [0, 1040) and [1040, 2080)
+ * of the n / 2080 whole rows, N = 1040 * height samples each) are equalised on their own.  Samples are ordered by
+ * IEEE totalOrder on their bits: key = bits ^ (bits >> 31 ? 0xFFFFFFFF : 0x80000000) as u32, so -NaN < -Inf < ... <
+ * -0 < +0 < ... < +Inf < +NaN and every input has a place.  cum(p) = samples of p's half with key <= key(p), and
+ * out(p) = (255f32 * (cum as f32 / N as f32)) as u8 (imageext.rs:33,38 with one bin per representable value).  low /
+ * high of aptgpu_image_result and the zero-length error are Histogram's (MinMax limits); they do not enter the
+ * pixels.  Gray or RGBA (R = G = B, A = 255); with a palette (color != NULL) APTGPU_ERR_UNSUPPORTED before any
+ * callback.  aptgpu_process_image / aptgpu_plan_process_device_image and their *_map / *_png / *_orbit / *_project
+ * forms only; aptgpu_process_gray / aptgpu_plan_process_device refuse it.  DESIGN.md §16. */
+#define APTGPU_CONTRAST_HISTOGRAM_FLOAT 4
 #define APTGPU_ROTATE_NO 0          /* Rotate::No  */
 #define APTGPU_ROTATE_YES 1         /* Rotate::Yes  src/noaa_apt.rs:228-231, processing.rs:21-37 */
 #define APTGPU_ROTATE_ORBIT 2       /* Rotate::Orbit: the *_orbit entry points only (they decide from the satellite's

@@ -742,8 +742,12 @@ def resample_wav(context, settings, input_wav, output_filename, output_rate: int
 # ------------------------------------------------------------------ consumers of the rows
 class Contrast:
     """noaa_apt::Contrast (noaa_apt.rs:25-37).  HISTOGRAM takes MinMax limits (noaa_apt.rs:158), then
-    equalises the histogram of each channel half (processing.rs:83-101)."""
+    equalises the histogram of each channel half (processing.rs:83-101).  HISTOGRAM_FLOAT is not a reference
+    variant: the equalisation on the f32 signal, before the pixel values become integers (the reference's
+    docs/development.md:105-106; APTGPU_CONTRAST_HISTOGRAM_FLOAT in include/aptgpu.h has the definition).  Gray
+    images only: with a ColorSettings it raises UnsupportedError."""
     TELEMETRY, MINMAX, HISTOGRAM = ("telemetry",), ("minmax",), ("histogram",)
+    HISTOGRAM_FLOAT = ("histogram_float",)
 
     @staticmethod
     def Percent(p):  # noqa: N802 - the reference's variant name
@@ -752,7 +756,7 @@ class Contrast:
     @staticmethod
     def _c(contrast):
         kind = contrast[0]
-        return ({"telemetry": 0, "percent": 1, "minmax": 2, "histogram": 3}[kind],
+        return ({"telemetry": 0, "percent": 1, "minmax": 2, "histogram": 3, "histogram_float": 4}[kind],
                 contrast[1] if kind == "percent" else 0.0)
 
 
@@ -1248,6 +1252,8 @@ def process(context, signal, contrast_adjustment, rotate=Rotate.NO, color=None, 
     gray image, or with `color` (a ColorSettings) the height x 2080 x 4 RGBA image of the reference's
     false colour (A = 255).  Contrast.HISTOGRAM equalises each channel half of the gray image; together with
     false colour it needs ColorSettings(equalize_lab=True) (the reference equalises channel A in CIE Lab then).
+    Contrast.HISTOGRAM_FLOAT equalises each half on the f32 samples themselves (exact ranks, all 256 levels in use);
+    it takes no colour (UnsupportedError) and chains into the overlay, PNG, orbit and projection like HISTOGRAM.
     `orbit` may be a MapOverlay: the map is drawn over the RGBA image (height x 2080 x 4, also without colour).
     png=True: the image is also encoded on the GPU and the PNG file's bytes are returned instead of the pixels
     (what `img.save()` writes in main.rs; gray without colour and map, RGBA with).
@@ -1277,7 +1283,7 @@ def process(context, signal, contrast_adjustment, rotate=Rotate.NO, color=None, 
         raise UnsupportedError("orbit: only a MapOverlay (the map overlay) is served on the GPU path")
     if color is not None and not isinstance(color, ColorSettings):
         raise UnsupportedError("color must be a ColorSettings")
-    if color is not None or contrast_adjustment == Contrast.HISTOGRAM:
+    if color is not None or contrast_adjustment in (Contrast.HISTOGRAM, Contrast.HISTOGRAM_FLOAT):
         return _process_image(context, signal, contrast_adjustment, rotate, color, return_info)
     cctx = (context or Context())._c()
     x, xp = _as_f32(signal)
@@ -1504,7 +1510,8 @@ class Plan:
     def process_device_image(self, d_rows: Sequence[int], rows_cap: Sequence[int], contrast_adjustment,
                              d_images: Sequence[int], rotate=Rotate.NO, color=None, channels=None, map=None,  # noqa: A002
                              png=None, orbit=None, layers=None, projection=None):
-        """process() with every contrast (HISTOGRAM too) and optional false colour (a ColorSettings) for the
+        """process() with every contrast (HISTOGRAM and, without colour, HISTOGRAM_FLOAT too) and optional false
+        colour (a ColorSettings) for the
         recordings of the last decode_device call, chained on the device behind their decode.  d_images[i]
         holds rows_cap[i] * 2080 * channels bytes; channels defaults to 4 (RGBA) with colour or map, 1 (gray)
         without.  map: a MapOverlay, or one per recording (all with the same settings and layers); a position count

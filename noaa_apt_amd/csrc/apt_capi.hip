@@ -248,6 +248,10 @@ int aptgpu_plan_read_internal(aptgpu_plan *plan, int i, const char *name, void *
     else if (n == "terminal_words") { src = sl.words.ptr; size = sl.words.count * sizeof(uint64_t); }
     else if (n == "peaks") { src = sl.peaks.ptr; size = sl.peaks.count * sizeof(uint32_t); }
     else if (n == "picker_flags") { src = sl.flags.ptr; size = sl.flags.count * sizeof(uint32_t); }
+    else if (n == "eqfloat_thresholds") {  // T_1..T_255 of half A, then of half B (apt_kernels_eqfloat.hpp)
+        src = sl.eqfloat_ws.ptr ? apt::gpu::eqfloat_ws_thresholds(sl.eqfloat_ws.ptr) : nullptr;
+        size = sl.eqfloat_ws.ptr ? 2 * 255 * sizeof(uint32_t) : 0;
+    }
     else return APTGPU_ERR_INVALID;
     if (size_out) *size_out = size;
     (void)hipSetDevice(plan->device);

@@ -7,6 +7,7 @@
 
 #include "apt_capi_util.hpp"
 #include "apt_kernels_color.hpp"
+#include "apt_kernels_eqfloat.hpp"
 #include "apt_kernels_png.hpp"
 #include "apt_kernels_project.hpp"
 #include "apt_kernels_track.hpp"
@@ -197,7 +198,7 @@ bool color_args(int contrast, int rotate, const aptgpu_color_settings *color, in
                 bool *lab)
 {
     *lab = false;
-    if (contrast < APTGPU_CONTRAST_TELEMETRY || contrast > APTGPU_CONTRAST_HISTOGRAM)
+    if (contrast < APTGPU_CONTRAST_TELEMETRY || contrast > APTGPU_CONTRAST_HISTOGRAM_FLOAT)
         throw Error{ErrorKind::Invalid, "unknown contrast adjustment"};
     if (rotate != APTGPU_ROTATE_NO && rotate != APTGPU_ROTATE_YES)
         throw Error{ErrorKind::Unsupported, "Rotate::Orbit needs the satellite and the time: aptgpu_orbit_settings, the *_orbit entry points"};
@@ -206,6 +207,10 @@ bool color_args(int contrast, int rotate, const aptgpu_color_settings *color, in
     if (color->struct_size < sizeof(aptgpu_color_settings) || !color->palette_rgb)
         throw Error{ErrorKind::Invalid, "aptgpu_color_settings: struct_size or palette_rgb not set"};
     if (color->flags & ~APTGPU_COLOR_EQUALIZE_LAB) throw Error{ErrorKind::Invalid, "aptgpu_color_settings: unknown flags"};
+    if (contrast == APTGPU_CONTRAST_HISTOGRAM_FLOAT)
+        throw Error{ErrorKind::Unsupported,
+                    "APTGPU_CONTRAST_HISTOGRAM_FLOAT equalises the gray image only: the reference has no float-domain "
+                    "equalisation of a false-colour image (pass color = NULL)"};
     if (contrast == APTGPU_CONTRAST_HISTOGRAM) {
         if (!(color->flags & APTGPU_COLOR_EQUALIZE_LAB))
             throw Error{ErrorKind::Unsupported,
@@ -414,12 +419,21 @@ int process_image(const aptgpu_context *ctx, const float *signal, size_t n, int 
         apt::DeviceBuffer<uint8_t> d_img;
         d_img.alloc(bytes + 16);
         const bool equalize = contrast == APTGPU_CONTRAST_HISTOGRAM;
-        if (lab) apt::gpu::image_equalize_lab(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, cws.ptr, lws.ptr, tune);
+        const bool eqfloat = contrast == APTGPU_CONTRAST_HISTOGRAM_FLOAT;
+        apt::DeviceBuffer<char> fws;
+        if (eqfloat) {
+            fws.alloc(apt::gpu::eqfloat_ws_bytes());
+            apt::gpu::image_equalize_float(s, c.d_x.ptr, nullptr, n, n, fws.ptr);
+        } else if (lab) apt::gpu::image_equalize_lab(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, cws.ptr, lws.ptr, tune);
         else if (equalize) apt::gpu::image_equalize(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, cws.ptr);
         if (map) status(ctx, 0.5f, "Drawing map");                                    // noaa_apt.rs:205
         if (rotate == APTGPU_ROTATE_YES) status(ctx, 0.90f, "Rotating output image");  // noaa_apt.rs:229
-        apt::gpu::image_color(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, cws.ptr, equalize, colored ? &tune : nullptr,
-                              channels, rotate == APTGPU_ROTATE_YES, d_img.ptr, c.d_info.ptr, lab ? lws.ptr : nullptr);
+        if (eqfloat)
+            apt::gpu::image_color_float(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, fws.ptr, channels,
+                                        rotate == APTGPU_ROTATE_YES, d_img.ptr, c.d_info.ptr);
+        else
+            apt::gpu::image_color(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, cws.ptr, equalize, colored ? &tune : nullptr,
+                                  channels, rotate == APTGPU_ROTATE_YES, d_img.ptr, c.d_info.ptr, lab ? lws.ptr : nullptr);
         if (map) {
             const size_t height = n / 2080;
             map_dev.prepare(s, *map->layers, height);

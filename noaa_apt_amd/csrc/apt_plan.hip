@@ -975,6 +975,16 @@ void aptgpu_plan::enqueue_image_color(int i, const float *d_rows, uint64_t rows_
     } else {
         enqueue_limits(t, d_rows, contrast, percent);
     }
+    if (contrast == APTGPU_CONTRAST_HISTOGRAM_FLOAT) {  // (no palette: color_args refuses it)
+        if (!sl.eqfloat_ws.ptr) sl.eqfloat_ws.alloc(eqfloat_ws_bytes());
+        timed(t.stream, "image_equalize_float",
+              [&] { image_equalize_float(t.stream, d_rows, t.res, 0, t.cap, sl.eqfloat_ws.ptr); });
+        timed(t.stream, "image_color_float", [&] {
+            image_color_float(t.stream, d_rows, t.res, 0, t.cap, t.ws, sl.eqfloat_ws.ptr, channels, rotate, d_image, t.out);
+        });
+        apt::hip_check(hipGetLastError(), "kernel launch (image stage)");
+        return;
+    }
     const bool equalize = contrast == APTGPU_CONTRAST_HISTOGRAM;
     if (lab)
         timed(t.stream, "image_equalize_lab", [&] {

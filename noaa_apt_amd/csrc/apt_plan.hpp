@@ -13,6 +13,7 @@
 #include "apt_host.hpp"
 #include "apt_kernels.hpp"
 #include "apt_kernels_color.hpp"
+#include "apt_kernels_eqfloat.hpp"
 #include "apt_kernels_map.hpp"
 #include "apt_kernels_png.hpp"
 #include "apt_kernels_project.hpp"
@@ -183,6 +184,7 @@ struct aptgpu_plan {
         uint64_t palette_gen = 0;          // generation of the palette color_ws holds (0 = none)
         apt::DeviceBuffer<char> lab_ws;    // Lab tables + per-call RGBA table, on first use of the Lab path
         uint64_t lab_gen = 0;              // generation of the palette whose Lab tables lab_ws holds (0 = none)
+        apt::DeviceBuffer<char> eqfloat_ws;  // counters, select records and thresholds of HISTOGRAM_FLOAT, on first use
         std::unique_ptr<apt::map::Device> map;  // the map overlay's layer set, lists and track, on first use
         std::unique_ptr<apt::project::Device> project;  // the reprojection's graticule, record and PNG scratch, on first use
         apt::DeviceBuffer<char> png_ws;    // the PNG encoder's filtered stream, staging and chunk records, on first use
@@ -216,7 +218,7 @@ struct aptgpu_plan {
         launch();
         timer.end(s);
     }
-    // The same with every contrast (APTGPU_CONTRAST_HISTOGRAM too), optional false colour and 1 or 4 bytes per
+    // The same with every contrast (APTGPU_CONTRAST_HISTOGRAM and _HISTOGRAM_FLOAT too), optional false colour and 1 or 4 bytes per
     // pixel (aptgpu_plan_process_device_image).  set_palette first when tune is non-null (with lab: Histogram
     // with false colour, equalised in CIE Lab).
     void enqueue_image_color(int i, const float *d_rows, uint64_t rows_cap_floats, int contrast, float percent,

@@ -5,6 +5,8 @@ shape (16 recordings x 600 s at 48 kHz, 1198 rows each, one decode_device call),
     minmax_gray       aptgpu_plan_process_device, MinMax (the path before the colour stage: image_minmax + image_map_u8)
     minmax_gray_new   aptgpu_plan_process_device_image, MinMax, 1 byte per pixel (its output pass instead of image_map_u8)
     histogram_gray    ... Histogram, 1 byte per pixel (+ image_equalize)
+    histogram_float   ... HISTOGRAM_FLOAT, 1 byte per pixel (image_equalize_float: the three count / select levels;
+                      image_color_float: its output pass)
     color_rgba        ... MinMax with false colour (the default palette), 4 bytes per pixel
     histogram_rotate  ... Histogram, 1 byte per pixel, Rotate::Yes
     histogram_color_lab ... Histogram with false colour (the default palette), channel A equalised in CIE Lab
@@ -162,6 +164,8 @@ def main():
         "minmax_gray": lambda: plan.process_device(ptr(d_rows), caps, apt.Contrast.MINMAX, ptr(d_img)),
         "minmax_gray_new": lambda: plan.process_device_image(ptr(d_rows), caps, apt.Contrast.MINMAX, ptr(d_img)),
         "histogram_gray": lambda: plan.process_device_image(ptr(d_rows), caps, apt.Contrast.HISTOGRAM, ptr(d_img)),
+        "histogram_float": lambda: plan.process_device_image(ptr(d_rows), caps, apt.Contrast.HISTOGRAM_FLOAT,
+                                                             ptr(d_img)),
         "color_rgba": lambda: plan.process_device_image(ptr(d_rows), caps, apt.Contrast.MINMAX, ptr(d_img),
                                                         color=color),
         "histogram_rotate": lambda: plan.process_device_image(ptr(d_rows), caps, apt.Contrast.HISTOGRAM, ptr(d_img),
@@ -196,7 +200,7 @@ def main():
           f"recording), {args.calls} calls per variant; ms per recording")
     if any(k.startswith("project_") for k in variants):
         print(f"project_*: grid {fit.width} x {fit.height} = {fit.width * fit.height / 1e6:.2f} Mpx per recording")
-    print(f"{'variant':18s} {'kernel':16s} {'ms/rec':>8s}   (launches)")
+    print(f"{'variant':18s} {'kernel':20s} {'ms/rec':>8s}   (launches)")
     for name, call in variants.items():
         for _ in range(3):  # warm-up: code objects, first-use allocations, palette upload
             call()
@@ -245,7 +249,7 @@ def main():
             if not kname.startswith("image_"):
                 continue
             total += ms
-            print(f"{name:18s} {kname:16s} {ms:8.4f}   ({launches})")
+            print(f"{name:18s} {kname:20s} {ms:8.4f}   ({launches})")
         print(f"{name:18s} {'sum (events)':16s} {total:8.4f}")
         print(f"{name:18s} {'wall / rec':16s} {wall * 1e3 / RECORDINGS:8.4f}   (one call of {RECORDINGS}, timing off)")
     if any(k in png_channels for k in variants):
