@@ -4,7 +4,7 @@
  *     aptgpu_decode in.wav out.pgm [contrast: telemetry|percent|minmax] [--no-sync]
  *                   [--histogram | --histogram-float] [--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE] [--png]
  *                   [--tle FILE --sat NAME (--start-ms N | --end-ms N)] [--rotate no|yes|orbit]
- *                   [--project equirect|mercator[:step_deg] [--grid DEG]]
+ *                   [--project equirect|mercator[:step_deg] [--grid DEG]] [--despeckle R[:T]]
  *
  * What `noaa-apt in.wav -o out.png` does (main.rs:91-110, noaa_apt.rs:114-235): load -> decode ->
  * contrast limits -> 8-bit image, written as a binary PGM, or with --png as the PNG file the GPU
@@ -21,8 +21,10 @@
  * --project KIND[:STEP]: the finished image (channel A) reprojected onto a north-up equirectangular or
  * Mercator grid of STEP degrees per pixel (default 0.04) that aptgpu_projection_fit sizes from the track
  * (--track FILE, or --tle: aptgpu_sat_track_host), bilinear; --grid DEG adds a graticule.  Written as a
- * PPM of the grid's size, or with --png as the RGBA PNG (transparent off the swath).  Plain C99, links
- * only libaptgpu.so.
+ * PPM of the grid's size, or with --png as the RGBA PNG (transparent off the swath).
+ * --despeckle R[:T]: the decoded rows go through aptgpu_despeckle first, a (2R+1) x (2R+1) median (R = 1 or 2) that
+ * never leaves a pixel's column band; T (default 0) is the fraction of the 98 % range a sample must differ from the
+ * median by to be replaced.  Plain C99, links only libaptgpu.so.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -42,14 +44,14 @@ int main(int argc, char **argv)
         fprintf(stderr, "usage: %s in.wav out.pgm [telemetry|percent|minmax] [--no-sync] [--histogram | --histogram-float] "
                 "[--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE] [--png]\n"
                 "       [--tle FILE --sat NAME (--start-ms N | --end-ms N)] [--rotate no|yes|orbit]\n"
-                "       [--project equirect|mercator[:step_deg] [--grid DEG]]\n", argv[0]);
+                "       [--project equirect|mercator[:step_deg] [--grid DEG]] [--despeckle R[:T]]\n", argv[0]);
         return 2;
     }
     int contrast = APTGPU_CONTRAST_PERCENT, sync = 1, lab = 0, png = 0;
     const char *palette_path = NULL, *map_dir = NULL, *track_path = NULL, *tle_path = NULL, *sat = NULL;
     int rotate = APTGPU_ROTATE_NO, ref_kind = -1;
     long long ref_ms = 0;
-    const char *project = NULL;
+    const char *project = NULL, *despeckle = NULL;
     double grid_deg = 0.0;
     for (int i = 3; i < argc; ++i) {
         if (!strcmp(argv[i], "telemetry")) contrast = APTGPU_CONTRAST_TELEMETRY;
@@ -69,6 +71,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--end-ms") && i + 1 < argc) ref_kind = APTGPU_REF_TIME_END, ref_ms = atoll(argv[++i]);
         else if (!strcmp(argv[i], "--project") && i + 1 < argc) project = argv[++i];
         else if (!strcmp(argv[i], "--grid") && i + 1 < argc) grid_deg = atof(argv[++i]);
+        else if (!strcmp(argv[i], "--despeckle") && i + 1 < argc) despeckle = argv[++i];
         else if (!strcmp(argv[i], "--rotate") && i + 1 < argc) {
             const char *r = argv[++i];
             rotate = !strcmp(r, "orbit") ? APTGPU_ROTATE_ORBIT : !strcmp(r, "yes") ? APTGPU_ROTATE_YES : APTGPU_ROTATE_NO;
@@ -127,6 +130,21 @@ int main(int argc, char **argv)
     if (rc != APTGPU_OK) { fprintf(stderr, "decode failed (%d): %s\n", rc, err); return 1; }
     fprintf(stderr, "%u Hz, %llu sync frames, %llu rows\n", rate, (unsigned long long)stats.n_sync,
             (unsigned long long)(n_rows_px / 2080));
+
+    if (despeckle) {
+        /* on the f32 rows, before any contrast limit is taken from them */
+        aptgpu_despeckle_settings ds = {sizeof(aptgpu_despeckle_settings), atoi(despeckle), 0.f};
+        const char *colon = strchr(despeckle, ':');
+        if (colon) ds.threshold = (float)atof(colon + 1);
+        aptgpu_despeckle_result dr;
+        float *filtered = NULL;
+        rc = aptgpu_despeckle(&ctx, rows, n_rows_px, &ds, &filtered, &dr, err, sizeof err);
+        if (rc != APTGPU_OK) { fprintf(stderr, "despeckle failed (%d): %s\n", rc, err); return 1; }
+        fprintf(stderr, "despeckle: radius %d, %llu of %llu samples replaced (t = %g)\n", ds.radius,
+                (unsigned long long)dr.replaced, (unsigned long long)dr.height * 2080ull, dr.t);
+        aptgpu_free(rows);
+        rows = filtered;
+    }
 
     uint8_t *image = NULL;
     size_t n_px = 0;

@@ -746,6 +746,59 @@ int aptgpu_plan_process_device_image_project(aptgpu_plan *plan, int count, const
                                              const size_t *out_cap, const aptgpu_png_settings *png,
                                              uint8_t *const *d_png, const size_t *png_cap, char *err, size_t err_cap);
 
+/* ---- despeckle: a band-aware median of the rows, in front of process() ----
+ * The reference's to-do list names it (docs/development.md:139 "Investigate about despeckle") and has no code for it,
+ * so the definition is this library's; tests/np_despeckle_model.py states it in numpy.  Signal to signal: n floats in,
+ * n floats out, opt-in; nothing else changes when it is not called.
+ *  - h = n / 2080 whole rows are filtered; the samples past h * 2080 are copied bit for bit.  h == 0: the output is
+ *    the input, replaced = 0, status OK, no limits are computed.
+ *  - Every row is eight column bands, [0,39) [39,86) [86,995) [995,1040) and the same + 1040 (sync, space, video and
+ *    telemetry of channels A and B).  The window of pixel (y, x) in band [b0, b1) is the (2r+1)^2 samples at rows
+ *    clamp(y + dy, 0, h - 1) and columns clamp(x + dx, b0, b1 - 1): it never leaves the band, edges are replicated.
+ *  - med = the window's element of rank (2r+1)^2 / 2 (0-based) in IEEE totalOrder on the bits (the key of
+ *    APTGPU_CONTRAST_HISTOGRAM_FLOAT), with its own bits.  out = med if med is not NaN and !(fabsf(x - med) <= t),
+ *    else x: a NaN x among finite neighbours is replaced, a sample in a mostly-NaN window is kept; with t = 0 this
+ *    is the plain median except that +-0 are left alone.
+ *  - threshold == 0: t = 0.  Otherwise (low, high) = aptgpu_percent(signal, 0.98) of the unfiltered signal, exactly
+ *    what APTGPU_CONTRAST_PERCENT with 0.98 reports for it, and t = threshold * (high - low) in f32 (a NaN t makes
+ *    every sample with a non-NaN med take med).  A limits failure (aptgpu_image_result reason 3) fails the host-array
+ *    forms with aptgpu_percent's status and message; the plan form records it and writes the unfiltered rows.
+ *  - replaced counts the samples for which the rule picked med (also where med's bits equal x's). */
+typedef struct aptgpu_despeckle_settings {
+    uint32_t struct_size; /* sizeof(aptgpu_despeckle_settings) */
+    int32_t radius;       /* 1 (3 x 3) or 2 (5 x 5); anything else is APTGPU_ERR_INVALID */
+    float threshold;      /* >= 0 and not NaN (else APTGPU_ERR_INVALID): a fraction of the 98 % range */
+} aptgpu_despeckle_settings;
+typedef struct aptgpu_despeckle_result {
+    int32_t status;    /* APTGPU_OK or APTGPU_ERR_INTERNAL */
+    int32_t reason;    /* 0; 3 the limits found no low bucket; 4 the decode before it failed (plan form) */
+    uint32_t height;   /* whole rows filtered */
+    uint32_t reserved;
+    uint64_t replaced; /* samples that took their window's median */
+    float low, high;   /* the 98 % limits (0 when threshold == 0 or height == 0) */
+    float t;           /* threshold * (high - low) */
+    uint32_t reserved2;
+} aptgpu_despeckle_result;
+/* settings nullable (= radius 1, threshold 0) in every entry point below.  *out malloc'd, n floats (aptgpu_free);
+ * info nullable. */
+int aptgpu_despeckle(const aptgpu_context *ctx, const float *signal, size_t n,
+                     const aptgpu_despeckle_settings *settings, float **out, aptgpu_despeckle_result *info, char *err,
+                     size_t err_cap);
+/* The same on the CPU, in plain C++ (no GPU needed): what the kernel is tested against besides the numpy model. */
+int aptgpu_despeckle_host(const float *signal, size_t n, const aptgpu_despeckle_settings *settings, float **out,
+                          aptgpu_despeckle_result *info, char *err, size_t err_cap);
+/* Device-resident, chained behind the last aptgpu_plan_decode_device call on each recording's stream without a host
+ * round trip (the row count comes from the decode record on the device; with a rows_cap below the decoded height the
+ * rows the decode wrote, as the image stage).  d_rows[i] is the rows buffer given to the decode call (same
+ * rows_cap[i]); d_out[i] has the same capacity, rows_cap[i] * 2080 floats, and must not overlap any d_rows[j]
+ * (APTGPU_ERR_INVALID).  d_out may then be passed as d_rows to any aptgpu_plan_process_device* call.  16-byte
+ * aligned buffers take the vector path.  Timer names: image_percent (threshold > 0), image_despeckle. */
+int aptgpu_plan_despeckle_device(aptgpu_plan *plan, int count, const float *const *d_rows, const size_t *rows_cap,
+                                 const aptgpu_despeckle_settings *settings, float *const *d_out, char *err,
+                                 size_t err_cap);
+/* Waits for the despeckle stage of the last call and copies the records. */
+int aptgpu_plan_despeckle_results(aptgpu_plan *plan, int count, aptgpu_despeckle_result *results);
+
 /* ====================================================================== */
 /* 5. WAV ingest in front of decode()                 */
 /* ====================================================================== */

@@ -28,6 +28,8 @@ Names, argument meaning and error behaviour follow the reference:
     file of the image, encoded on the GPU
     process(projection=ProjectionSettings(...)),           the reference's to-do list, docs/development.md:112,99:
     project_image, projection_fit, Projection              the image on an equirectangular or Mercator grid
+    despeckle, despeckle_host, DespeckleSettings,          the reference's to-do list, docs/development.md:139: a
+    process(despeckle=...), Plan.despeckle_device          band-aware median of the f32 rows in front of process()
     percent, get_min, get_max, map_signal_u8               /root/reference/src/misc.rs:119, dsp.rs:20-54
     read_telemetry, Telemetry                              /root/reference/src/telemetry.rs:19-243
 
@@ -45,6 +47,7 @@ from .api import (  # noqa: F401
     MAP_STATES, MAP_COUNTRIES, MAP_LAKES,
     get_min, get_max, percent, map_signal_u8, read_telemetry, process, lab_from_rgb, lab_to_rgb,
     encode_png, png_bound, PNG_REASON_CAPACITY,
+    DespeckleSettings, DespeckleResult, despeckle, despeckle_host,
     Projection, ProjectionSettings, projection_fit, project_image, PROJECT_REASON_CAPACITY,
     SatName, RefTime, OrbitSettings, sat_track, sat_track_host, south_to_north_pass, SAT_REASON_SGP4,
     Plan, PlanInfo, Result, KernelTime, decode_batch, BatchStats, host_alloc_f32, host_free,

@@ -161,6 +161,18 @@ class _CProjectionSettings(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class _CDespeckleSettings(C.Structure):
+    """aptgpu_despeckle_settings"""
+    _fields_ = [("struct_size", C.c_uint32), ("radius", C.c_int32), ("threshold", C.c_float)]
+
+
+class DespeckleResult(C.Structure):
+    """aptgpu_despeckle_result: rows filtered, samples replaced, the 98 % limits and t = threshold * (high - low)."""
+    _fields_ = [("status", C.c_int32), ("reason", C.c_int32), ("height", C.c_uint32), ("reserved", C.c_uint32),
+                ("replaced", C.c_uint64), ("low", C.c_float), ("high", C.c_float), ("t", C.c_float),
+                ("reserved2", C.c_uint32)]
+
+
 class WavSpec(C.Structure):
     """aptgpu_wav_spec: hound::WavSpec plus where the samples are."""
     _fields_ = [("channels", C.c_uint16), ("bits_per_sample", C.c_uint16),
@@ -363,6 +375,11 @@ def lib():
                                                            cms, vp, C.POINTER(_f64p), C.POINTER(sz), C.POINTER(cos),
                                                            C.POINTER(vp), cpr, C.POINTER(vp), C.POINTER(sz), cps,
                                                            C.POINTER(vp), C.POINTER(sz), C.c_char_p, sz]
+    cds = C.POINTER(_CDespeckleSettings)
+    L.aptgpu_despeckle.argtypes = [cp, _f32p, sz, cds, C.POINTER(_f32p), C.POINTER(DespeckleResult), C.c_char_p, sz]
+    L.aptgpu_despeckle_host.argtypes = [_f32p, sz, cds, C.POINTER(_f32p), C.POINTER(DespeckleResult), C.c_char_p, sz]
+    L.aptgpu_plan_despeckle_device.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz), cds, C.POINTER(vp), C.c_char_p, sz]
+    L.aptgpu_plan_despeckle_results.argtypes = [vp, i32, C.POINTER(DespeckleResult)]
     _lib = L
     return L
 
@@ -1246,8 +1263,63 @@ def _process_image_project(context, signal, contrast_adjustment, rotate, color, 
     return (out, info) if return_info else out
 
 
+class DespeckleSettings:
+    """aptgpu_despeckle_settings: the band-aware median in front of process().  radius 1 (3 x 3) or 2
+    (5 x 5); threshold >= 0 is a fraction of the signal's 98 % range: a sample is replaced by its window's median only
+    where it differs from it by more than that (0: the plain median)."""
+
+    def __init__(self, radius=1, threshold=0.0):
+        self.radius, self.threshold = radius, threshold
+
+    def _c(self, struct_size=None):
+        return _CDespeckleSettings(C.sizeof(_CDespeckleSettings) if struct_size is None else int(struct_size),
+                                   int(self.radius), float(self.threshold))
+
+
+def _despeckle_c(settings):
+    if settings is None:
+        return None
+    if not isinstance(settings, DespeckleSettings):
+        raise InvalidError("despeckle: settings must be a DespeckleSettings")
+    try:
+        return settings._c()
+    except (TypeError, ValueError, OverflowError) as e:
+        raise InvalidError(f"despeckle: {e}") from None
+
+
+def despeckle(signal, settings=None, context=None, return_info=False):
+    """The despeckle stage on the GPU: f32 samples in, as many f32 samples out.  Every whole row of 2080 samples is
+    filtered with a (2 * radius + 1)^2 median that never leaves the pixel's column band (sync, space, video,
+    telemetry of either channel); a partial last row is copied.  With return_info also the DespeckleResult (height,
+    replaced, low, high, t)."""
+    cs = _despeckle_c(settings)
+    cctx = (context or Context())._c()
+    x, xp = _as_f32(signal)
+    out, info = _f32p(), DespeckleResult()
+    err = C.create_string_buffer(_ERRCAP)
+    _check(lib().aptgpu_despeckle(C.byref(cctx), xp, x.size, C.byref(cs) if cs is not None else None, C.byref(out),
+                                  C.byref(info), err, _ERRCAP), err)
+    y = _take(out, x.size)
+    return (y, info) if return_info else y
+
+
+_despeckle = despeckle  # (process() has a parameter of that name)
+
+
+def despeckle_host(signal, settings=None, return_info=False):
+    """despeckle() on the CPU, in plain C++ (no GPU needed): the same bits."""
+    cs = _despeckle_c(settings)
+    x, xp = _as_f32(signal)
+    out, info = _f32p(), DespeckleResult()
+    err = C.create_string_buffer(_ERRCAP)
+    _check(lib().aptgpu_despeckle_host(xp, x.size, C.byref(cs) if cs is not None else None, C.byref(out),
+                                       C.byref(info), err, _ERRCAP), err)
+    y = _take(out, x.size)
+    return (y, info) if return_info else y
+
+
 def process(context, signal, contrast_adjustment, rotate=Rotate.NO, color=None, orbit=None,
-            return_info=False, png=False, layers=None, projection=None):
+            return_info=False, png=False, layers=None, projection=None, despeckle=None):  # noqa: A002
     """noaa_apt::process (noaa_apt.rs:132-235).  Returns the height x 2080 u8
     gray image, or with `color` (a ColorSettings) the height x 2080 x 4 RGBA image of the reference's
     false colour (A = 255).  Contrast.HISTOGRAM equalises each channel half of the gray image; together with
@@ -1267,7 +1339,15 @@ def process(context, signal, contrast_adjustment, rotate=Rotate.NO, color=None, 
     (grid height, grid width, 4) RGBA array is returned (or its PNG file).  The track comes from `orbit`: a
     MapOverlay or an OrbitSettings with draw_map (the map is drawn on the swath first), an OrbitSettings without, or
     plain sat_positions (no map).  It reads the unrotated image and north is up by construction: any rotate but
-    Rotate.NO raises InvalidError."""
+    Rotate.NO raises InvalidError.
+    despeckle (a DespeckleSettings): the signal goes through despeckle() first and the filtered rows are handed to
+    whichever path the other arguments select.  These are two library calls (the rows cross to the host in between);
+    the device-resident composition is Plan.despeckle_device followed by Plan.process_device_image."""
+    if despeckle is not None:
+        if not isinstance(despeckle, DespeckleSettings):
+            raise InvalidError("despeckle must be a DespeckleSettings")
+        signal = _despeckle(signal, despeckle, context)
+        return process(context, signal, contrast_adjustment, rotate, color, orbit, return_info, png, layers, projection)
     if projection is not None:
         return _process_image_project(context, signal, contrast_adjustment, rotate, color, return_info, orbit, layers,
                                       png, projection)
@@ -1506,6 +1586,22 @@ class Plan:
         _check(lib().aptgpu_plan_process_device(self._p, k, (C.c_void_p * k)(*d_rows),
                                                 (C.c_size_t * k)(*rows_cap), kind, p, int(rotate),
                                                 (C.c_void_p * k)(*d_images), err, _ERRCAP), err)
+
+    def despeckle_device(self, d_rows: Sequence[int], rows_cap: Sequence[int], d_out: Sequence[int], settings=None):
+        """The despeckle stage of the recordings of the last decode_device call, chained on the device behind their
+        decode.  d_out[i] holds rows_cap[i] * 2080 floats and must not overlap d_rows; it can then be passed as d_rows
+        to process_device / process_device_image.  Records through despeckle_results()."""
+        k = len(d_rows)
+        cs = _despeckle_c(settings)
+        err = C.create_string_buffer(_ERRCAP)
+        _check(lib().aptgpu_plan_despeckle_device(self._p, k, (C.c_void_p * k)(*d_rows), (C.c_size_t * k)(*rows_cap),
+                                                  C.byref(cs) if cs is not None else None, (C.c_void_p * k)(*d_out),
+                                                  err, _ERRCAP), err)
+
+    def despeckle_results(self, count=1) -> List["DespeckleResult"]:
+        arr = (DespeckleResult * count)()
+        _check(lib().aptgpu_plan_despeckle_results(self._p, count, arr))
+        return list(arr)
 
     def process_device_image(self, d_rows: Sequence[int], rows_cap: Sequence[int], contrast_adjustment,
                              d_images: Sequence[int], rotate=Rotate.NO, color=None, channels=None, map=None,  # noqa: A002

@@ -7,6 +7,7 @@
 
 #include "apt_capi_util.hpp"
 #include "apt_kernels_color.hpp"
+#include "apt_kernels_despeckle.hpp"
 #include "apt_kernels_eqfloat.hpp"
 #include "apt_kernels_png.hpp"
 #include "apt_kernels_project.hpp"
@@ -1195,6 +1196,102 @@ int aptgpu_map_read_shapefile(const char *path, int shape_type, double **xy, siz
         *n_parts = l.parts.size() - 1;
         return APTGPU_OK;
     });
+}
+
+int aptgpu_despeckle(const aptgpu_context *ctx, const float *signal, size_t n,
+                     const aptgpu_despeckle_settings *settings, float **out, aptgpu_despeckle_result *info, char *err,
+                     size_t err_cap)
+{
+    static_assert(sizeof(apt::gpu::DespeckleResult) == sizeof(aptgpu_despeckle_result),
+                  "DespeckleResult must mirror aptgpu_despeckle_result");
+    if ((!signal && n) || !out) return APTGPU_ERR_INVALID;
+    *out = nullptr;
+    return guarded(err, err_cap, [&] {
+        const apt::despeckle::Settings st = apt::despeckle::check_settings(settings);
+        ImageCall c(ctx, signal, n);
+        hipStream_t s = c.sc.stream;
+        apt::DeviceBuffer<float> d_out;
+        apt::DeviceBuffer<apt::gpu::DespeckleResult> d_rec;
+        d_out.alloc(n + 16);
+        d_rec.alloc(1);
+        if (st.threshold != 0.f && n >= 2080)  // (the limits of the unfiltered signal, as Percent(0.98) reports them)
+            apt::gpu::image_percent(s, c.d_x.ptr, nullptr, n, n, 0.98f, c.ws.ptr, c.d_info.ptr);
+        apt::gpu::despeckle(s, c.d_x.ptr, nullptr, n, n, st.radius, st.threshold,
+                            apt::gpu::image_ws_pointers(c.ws.ptr, n).limits, c.d_info.ptr, d_out.ptr, d_rec.ptr);
+        apt::hip_check(hipGetLastError(), "kernel launch (despeckle stage)");
+        apt::gpu::DespeckleResult r{};
+        apt::hip_check(hipMemcpyAsync(&r, d_rec.ptr, sizeof r, hipMemcpyDeviceToHost, s), "hipMemcpyAsync D2H");
+        apt::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
+        if (info) std::memcpy(info, &r, sizeof r);
+        if (r.status != 0) throw Error{ErrorKind::Internal, apt::despeckle::reason_text(r.reason)};
+        *out = c.sc.download_malloc(d_out.ptr, n);
+        return APTGPU_OK;
+    });
+}
+
+int aptgpu_despeckle_host(const float *signal, size_t n, const aptgpu_despeckle_settings *settings, float **out,
+                          aptgpu_despeckle_result *info, char *err, size_t err_cap)
+{
+    if ((!signal && n) || !out) return APTGPU_ERR_INVALID;
+    *out = nullptr;
+    return guarded(err, err_cap, [&] {
+        const apt::despeckle::Settings st = apt::despeckle::check_settings(settings);
+        float *h = host_alloc<float>(n);
+        try {
+            apt::despeckle::run_host(signal, n, st, h, info);
+        } catch (...) {
+            std::free(h);
+            throw;
+        }
+        *out = h;
+        return APTGPU_OK;
+    });
+}
+
+int aptgpu_plan_despeckle_device(aptgpu_plan *plan, int count, const float *const *d_rows, const size_t *rows_cap,
+                                 const aptgpu_despeckle_settings *settings, float *const *d_out, char *err,
+                                 size_t err_cap)
+{
+    if (!plan || count < 0 || !d_rows || !rows_cap || !d_out) return APTGPU_ERR_INVALID;
+    return guarded(err, err_cap, [&] {
+        const apt::despeckle::Settings st = apt::despeckle::check_settings(settings);
+        if (static_cast<size_t>(count) > plan->last_slots.size())
+            throw Error{ErrorKind::Invalid, "count exceeds the recordings of the last decode call"};
+        for (int i = 0; i < count; ++i) {
+            if (!d_rows[i] || !d_out[i]) throw Error{ErrorKind::Invalid, "null device pointer"};
+            const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out[i]);
+            const uintptr_t o1 = o0 + rows_cap[i] * 2080u * sizeof(float);
+            for (int j = 0; j < count; ++j) {
+                const uintptr_t r0 = reinterpret_cast<uintptr_t>(d_rows[j]);
+                const uintptr_t r1 = r0 + rows_cap[j] * 2080u * sizeof(float);
+                if (r0 && ((o0 < r1 && r0 < o1) || o0 == r0)) throw Error{ErrorKind::Invalid, "d_out overlaps d_rows"};
+            }
+        }
+        apt::hip_check(hipSetDevice(plan->device), "hipSetDevice");
+        for (int i = 0; i < count; ++i)
+            plan->enqueue_despeckle(i, d_rows[i], static_cast<uint64_t>(rows_cap[i]) * 2080u, st.radius, st.threshold,
+                                    d_out[i]);
+        return APTGPU_OK;
+    });
+}
+
+int aptgpu_plan_despeckle_results(aptgpu_plan *plan, int count, aptgpu_despeckle_result *results)
+{
+    if (!plan || count < 0 || (!results && count)) return APTGPU_ERR_INVALID;
+    if (static_cast<size_t>(count) > plan->last_slots.size()) return APTGPU_ERR_INVALID;
+    for (int i = 0; i < count; ++i)
+        if (!plan->slot_of(i).despeckle_ws.ptr) return APTGPU_ERR_INVALID;
+    try {
+        apt::hip_check(hipSetDevice(plan->device), "hipSetDevice");
+        plan->sync_all();
+        for (int i = 0; i < count; ++i)
+            apt::hip_check(hipMemcpy(results + i, apt::gpu::despeckle_ws_record(plan->slot_of(i).despeckle_ws.ptr),
+                                     sizeof(aptgpu_despeckle_result), hipMemcpyDeviceToHost),
+                           "hipMemcpy");
+    } catch (const apt::Error &) {
+        return APTGPU_ERR_HIP;
+    }
+    return APTGPU_OK;
 }
 
 int aptgpu_plan_image_results(aptgpu_plan *plan, int count, aptgpu_image_result *results)

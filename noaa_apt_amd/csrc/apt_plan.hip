@@ -895,6 +895,24 @@ void aptgpu_plan::enqueue_image(int i, const float *d_rows, uint64_t rows_cap_fl
     apt::hip_check(hipGetLastError(), "kernel launch (image stage)");
 }
 
+void aptgpu_plan::enqueue_despeckle(int i, const float *d_rows, uint64_t rows_cap_floats, int radius, float threshold,
+                                    float *d_out)
+{
+    using namespace apt::gpu;
+    const ImageTarget t = image_target(i, rows_cap_floats);
+    Slot &sl = t.slot;
+    if (!sl.despeckle_ws.ptr) sl.despeckle_ws.alloc(despeckle_ws_bytes());
+    ImageResult *lim_info = despeckle_ws_limits_info(sl.despeckle_ws.ptr);
+    const float *limits = image_ws_pointers(t.ws, t.cap).limits;
+    if (threshold != 0.f)
+        timed(t.stream, "image_percent", [&] { image_percent(t.stream, d_rows, t.res, 0, t.cap, 0.98f, t.ws, lim_info); });
+    timed(t.stream, "image_despeckle", [&] {
+        despeckle(t.stream, d_rows, t.res, 0, t.cap, radius, threshold, limits, lim_info, d_out,
+                  despeckle_ws_record(sl.despeckle_ws.ptr));
+    });
+    apt::hip_check(hipGetLastError(), "kernel launch (despeckle stage)");
+}
+
 aptgpu_plan::Palette::~Palette()
 {
     for (hipEvent_t ev : uploaded)

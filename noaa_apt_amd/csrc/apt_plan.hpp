@@ -13,6 +13,7 @@
 #include "apt_host.hpp"
 #include "apt_kernels.hpp"
 #include "apt_kernels_color.hpp"
+#include "apt_kernels_despeckle.hpp"
 #include "apt_kernels_eqfloat.hpp"
 #include "apt_kernels_map.hpp"
 #include "apt_kernels_png.hpp"
@@ -185,6 +186,7 @@ struct aptgpu_plan {
         apt::DeviceBuffer<char> lab_ws;    // Lab tables + per-call RGBA table, on first use of the Lab path
         uint64_t lab_gen = 0;              // generation of the palette whose Lab tables lab_ws holds (0 = none)
         apt::DeviceBuffer<char> eqfloat_ws;  // counters, select records and thresholds of HISTOGRAM_FLOAT, on first use
+        apt::DeviceBuffer<char> despeckle_ws;  // record + limits record of the despeckle stage, on first use
         std::unique_ptr<apt::map::Device> map;  // the map overlay's layer set, lists and track, on first use
         std::unique_ptr<apt::project::Device> project;  // the reprojection's graticule, record and PNG scratch, on first use
         apt::DeviceBuffer<char> png_ws;    // the PNG encoder's filtered stream, staging and chunk records, on first use
@@ -224,6 +226,11 @@ struct aptgpu_plan {
     void enqueue_image_color(int i, const float *d_rows, uint64_t rows_cap_floats, int contrast, float percent,
                              bool rotate, const apt::gpu::ColorTune *tune, int channels, uint8_t *d_image,
                              bool lab = false);
+    // The despeckle stage (apt_kernels_despeckle.hpp) of recording i, behind its decode on the same stream: the 98 %
+    // limits of d_rows when threshold != 0 (into the slot's image scratch, which the image stage behind it rewrites),
+    // then one k_despeckle launch into d_out (same capacity, no overlap).  The record stays in the slot.
+    void enqueue_despeckle(int i, const float *d_rows, uint64_t rows_cap_floats, int radius, float threshold,
+                           float *d_out);
     // The map overlay (apt_kernels_map.hpp) over recording i's RGBA image, behind enqueue_image_color on the same
     // stream.  The slot uploads the layer set once per generation; positions: `count` (lat, lon) pairs.
     void enqueue_image_map(int i, uint64_t rows_cap_floats, const apt::map::Layers &layers,

@@ -21,6 +21,10 @@ shape (16 recordings x 600 s at 48 kHz, 1198 rows each, one decode_device call),
                       sizes for the track at 0.04 degrees per pixel, nearest sampling
     project_bilinear  the same, bilinear
     project_nearest_png, project_bilinear_png   the same + the PNG encoder on the projected grid
+    despeckle_r1_t0, despeckle_r1_t01, despeckle_r2_t0, despeckle_r2_t01
+                      the despeckle stage (radius 1 / 2, threshold 0 / 0.1: image_despeckle, and
+                      image_percent when the threshold needs the 98 % limits) into a second rows buffer, then
+                      minmax_gray on the filtered rows: image_minmax, one pass over the same samples, stands beside it
 
 Per kernel: the plan's event timing (every launch bracketed, one call in flight), ms per recording.  Per variant also
 the wall time of one call of 16 recordings with timing off (host clock around enqueue + synchronise).  Last, the host
@@ -151,7 +155,19 @@ def main():
             projection=(grids[sampling], ptr(d_grid), [grid_bytes] * RECORDINGS),
             png=(ptr(d_grid_png), grid_png_cap) if with_png else None)
 
+    d_dsp = [torch.empty(cap * 2080, dtype=torch.float32, device=dev) for _ in range(RECORDINGS)]
+
+    def despeckle(radius, threshold):
+        def call():
+            plan.despeckle_device(ptr(d_rows), caps, ptr(d_dsp), apt.DespeckleSettings(radius, threshold))
+            plan.process_device(ptr(d_dsp), caps, apt.Contrast.MINMAX, ptr(d_img))
+        return call
+
     variants = {
+        "despeckle_r1_t0": despeckle(1, 0.0),
+        "despeckle_r1_t01": despeckle(1, 0.1),
+        "despeckle_r2_t0": despeckle(2, 0.0),
+        "despeckle_r2_t01": despeckle(2, 0.1),
         "project_nearest": project(apt.Projection.NEAREST, False),
         "project_bilinear": project(apt.Projection.BILINEAR, False),
         "project_nearest_png": project(apt.Projection.NEAREST, True),
