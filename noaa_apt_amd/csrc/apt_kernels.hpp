@@ -55,6 +55,7 @@ struct GroupMax {
 struct LaunchSwitches {
     int gather_iters = 1;        // APTGPU_GATHER_ITERS: quads per thread of k_gather_rows_flat (0: the eight-rows form)
     bool words_dpp = true;       // APTGPU_WORDS_DPP=0: k_sync_words without the DPP scans
+    int words_form = 1;          // APTGPU_WORDS_FORM=0: k_sync_words / k_sync_slots in their earlier form (A/B)
     bool orbit_lds = true;       // APTGPU_ORBIT_LDS=0: the orbit kernel's tables in global memory
     int orbit_threads = 0;       // APTGPU_ORBIT_THREADS=256: the 256-thread orbit kernel
     int orbit_alg = 1;           // APTGPU_ORBIT_ALG=0: the breadth-first closure form

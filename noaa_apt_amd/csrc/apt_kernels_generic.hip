@@ -581,6 +581,7 @@ LaunchSwitches read_launch_switches()
     LaunchSwitches sw;
     if (const char *e = std::getenv("APTGPU_GATHER_ITERS")) sw.gather_iters = std::atoi(e);
     if (const char *e = std::getenv("APTGPU_WORDS_DPP")) sw.words_dpp = e[0] != '0';
+    if (const char *e = std::getenv("APTGPU_WORDS_FORM")) sw.words_form = e[0] == '0' ? 0 : 1;
     if (const char *e = std::getenv("APTGPU_ORBIT_LDS")) sw.orbit_lds = e[0] != '0';
     if (const char *e = std::getenv("APTGPU_ORBIT_THREADS")) sw.orbit_threads = std::atoi(e);
     if (const char *e = std::getenv("APTGPU_ORBIT_ALG")) sw.orbit_alg = e[0] == '0' ? 0 : 1;

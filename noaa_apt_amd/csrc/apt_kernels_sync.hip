@@ -65,6 +65,14 @@ namespace apt::gpu {
 namespace {
 
 constexpr int GS = 52;
+
+// -DAPT_WORDS_MARKS=1 (listings only): comments that split k_sync_words' listing into its phases for
+// tools/isa_budget.py --marks (profiles/r14_chain_passes.txt)
+#ifdef APT_WORDS_MARKS
+#define APT_WMARK(what) asm volatile("; APTMARK " what)
+#else
+#define APT_WMARK(what) ((void)0)
+#endif
 constexpr uint64_t kGroupMask = (1ull << GS) - 1;
 constexpr float kNegInf = -__builtin_huge_valf();
 
@@ -143,6 +151,13 @@ __device__ __forceinline__ float wave_suffix_max_excl_dpp(float x, int lane)
     return fmaxf(y, tail);
 }
 
+// maximum over the wave, in every lane (values never NaN; all 64 lanes active)
+__device__ __forceinline__ float wave_max_all_dpp(float x)
+{
+    x = wave_prefix_max_dpp(x);
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 63));
+}
+
 // bytes of dynamic LDS of k_sync_words for r = md/GS groups of look-ahead: terminal and NaN words of the own
 // groups | hi, lo bounds and two buffers of running maxima over own + look-ahead groups | window maxima |
 // candidate list | one F window per wave
@@ -213,7 +228,17 @@ __device__ __forceinline__ float nodes_eval_window(float *win, bool on, int lane
 // the words back — a kernel boundary instead of an inter-workgroup hand-over inside one launch.)
 // DPP: the two scans of a candidate's terminal test with DPP row operations (the default; APTGPU_WORDS_DPP=0 keeps
 // the ds_bpermute form for A/B).
-template <int NL, int PWC, bool DPP>
+// LEAN (the default where PWC > 0 and R = 32 pw; APTGPU_WORDS_FORM=0 keeps the earlier form for A/B): the same predicate
+// and the same words with fewer instructions around the chains —
+//   coarse    prefix and suffix maxima of lo inside blocks of 64 entries, two DPP scans per block and ONE barrier (the
+//             window q+1 .. q+R-1 is a block's suffix, the whole blocks in between and a block's prefix), instead of
+//             six doubling rounds through LDS with a barrier each;
+//   hand-out  the candidates are split evenly between the two waves;
+//   interior  a chunk whose windows all lie inside [0, w) and whose positions all lie inside [0, n_corr) — every chunk
+//             but a recording's last two — loads its windows unpredicated with 32-bit offsets on a scalar base and drops
+//             the per-lane 64-bit position compares;
+//   settle    the three wave-wide reductions of the open-bounds branch with the DPP scan instead of shuffles.
+template <int NL, int PWC, bool DPP, bool LEAN>
 __global__ void __launch_bounds__(kNodesThreads, 4)  // <= 128 VGPRs: must fit beside the front end's waves
 k_sync_words(const CallArgs call, const SlotPtrs *__restrict__ slots, uint32_t pw_arg, uint32_t r_groups /* md/GS */,
              int fast, int use_corr)
@@ -261,40 +286,82 @@ k_sync_words(const CallArgs call, const SlotPtrs *__restrict__ slots, uint32_t p
         sp.res->status = -1;
         sp.res->reason = -1;
     }
-    for (int q = tid; q < N; q += kNodesThreads) {
-        const int64_t g = g0 + q;
-        const GroupMax v = g < static_cast<int64_t>(ng) ? gm[g] : GroupMax{kNegInf, kNegInf};
-        s_hi[q] = v.hi;
-        s_lo[q] = v.lo;
-        s_ma[q] = v.lo;
-    }
-    s_words[tid] = 0ull;  // (kNodesThreads == kChunkGroups)
-    s_nanw[tid] = 0ull;
-    __syncthreads();
-
-    // coarse: WM[q] = max(lo[q+1 .. q+W]), W = R-1 — the full groups inside every window of group q's
-    // positions — from running maxima over power-of-two spans (doubling, log2 W steps of one max per
-    // entry): a window is the union of the two spans of K = 2^floor(log2 W) entries at its two ends.
-    {
-        const int W = R - 1;  // >= 1 for every legal md
-        float *a = s_ma, *bq = s_mb;
-        int K = 1;
-        for (; 2 * K <= W; K *= 2) {
-            for (int q = tid; q < N; q += kNodesThreads) bq[q] = (q + K < N) ? fmaxf(a[q], a[q + K]) : a[q];
-            __syncthreads();
-            float *t = a; a = bq; bq = t;
+    APT_WMARK("BEGIN coarse");
+    static_assert(!LEAN || (DPP && NL > 0 && PWC > 0), "the lean form builds on the DPP scans and the register-held windows");
+    if constexpr (LEAN) {
+        // coarse: WM[q] = max(lo[q+1 .. q+W]), W = R-1, by the two-block method over blocks of 64 entries: P[i] =
+        // max(lo[block start .. i]) and S[i] = max(lo[i .. block end]), each one DPP prefix scan of a wave (S: of the
+        // block read back to front).  R = 32 pw here (the launcher checks it), so every bound below is a constant.
+        // P and S take the place of s_lo, s_ma and s_mb (3 N >= 128 ceil(N / 64) floats for every N >= 126).
+        // Maxima of non-NaN floats do not depend on the order: the same WM as the doubling form.
+        constexpr int RC = 32 * PWC, NC = kChunkGroups + RC + 1, NB = (NC + 63) / 64;
+        static_assert(RC - 2 >= 64 && 2 * NB * 64 <= 3 * NC, "a window spans two blocks or more; P and S fit");
+        float *s_p = s_lo, *s_s = s_lo + NB * 64;
+        const GroupMax *__restrict__ gmb = gm + g0;  // (scalar base, 32-bit offsets)
+        const uint32_t n_left = ng - static_cast<uint32_t>(g0);  // >= 1: groups from g0 on
+#pragma unroll
+        for (int k = 0; k < (NB + kNodesWaves - 1) / kNodesWaves; ++k) {
+            const int b = wave + k * kNodesWaves;  // (wave-uniform: all 64 lanes are active in the scans)
+            if (b < NB) {
+                const uint32_t q = b * 64u + lane, qr = b * 64u + 63u - lane;
+                const GroupMax v = (q < NC && q < n_left) ? gmb[q] : GroupMax{kNegInf, kNegInf};
+                const float lo_r = (qr < NC && qr < n_left) ? gmb[qr].lo : kNegInf;
+                if (q < NC) s_hi[q] = v.hi;
+                s_p[q] = wave_prefix_max_dpp(v.lo);
+                s_s[qr] = wave_prefix_max_dpp(lo_r);
+            }
         }
-        // a[q] = max(lo[q .. q+K-1]) (clipped at N)
-        const int q = tid;
-        const int64_t g = g0 + q;
-        const float wm = fmaxf(a[q + 1], a[q + 1 + W - K]);  // q + W <= CG - 1 + R - 1 < N
-        s_wm[q] = wm;
-        // pruned only when a later group certainly holds more than this one possibly does (a group
-        // that holds a NaN has hi = +inf: its NaN positions may be starts, see the top)
-        if (g < static_cast<int64_t>(ng) && !(wm > s_hi[q])) s_cand[atomicAdd(&s_ncand, 1u)] = static_cast<uint16_t>(q);
+        s_words[tid] = 0ull;  // (kNodesThreads == kChunkGroups)
+        s_nanw[tid] = 0ull;
         __syncthreads();
+        const int q = tid;
+        const int a = q + 1, e = q + RC - 1;  // e - a >= 64: never in the same block; e < NC <= NB * 64
+        float wm = fmaxf(s_s[a], s_p[e]);
+#pragma unroll
+        for (int b = 1; b < NB - 1; ++b) {  // the whole blocks in between
+            const float whole = s_s[b * 64];
+            wm = (b > (a >> 6) && b < (e >> 6)) ? fmaxf(wm, whole) : wm;
+        }
+        s_wm[q] = wm;
+        if (static_cast<uint32_t>(q) < n_left && !(wm > s_hi[q])) s_cand[atomicAdd(&s_ncand, 1u)] = static_cast<uint16_t>(q);
+        __syncthreads();
+    } else {
+        for (int q = tid; q < N; q += kNodesThreads) {
+            const int64_t g = g0 + q;
+            const GroupMax v = g < static_cast<int64_t>(ng) ? gm[g] : GroupMax{kNegInf, kNegInf};
+            s_hi[q] = v.hi;
+            s_lo[q] = v.lo;
+            s_ma[q] = v.lo;
+        }
+        s_words[tid] = 0ull;  // (kNodesThreads == kChunkGroups)
+        s_nanw[tid] = 0ull;
+        __syncthreads();
+
+        // coarse: WM[q] = max(lo[q+1 .. q+W]), W = R-1 — the full groups inside every window of group q's
+        // positions — from running maxima over power-of-two spans (doubling, log2 W steps of one max per
+        // entry): a window is the union of the two spans of K = 2^floor(log2 W) entries at its two ends.
+        {
+            const int W = R - 1;  // >= 1 for every legal md
+            float *a = s_ma, *bq = s_mb;
+            int K = 1;
+            for (; 2 * K <= W; K *= 2) {
+                for (int q = tid; q < N; q += kNodesThreads) bq[q] = (q + K < N) ? fmaxf(a[q], a[q + K]) : a[q];
+                __syncthreads();
+                float *t = a; a = bq; bq = t;
+            }
+            // a[q] = max(lo[q .. q+K-1]) (clipped at N)
+            const int q = tid;
+            const int64_t g = g0 + q;
+            const float wm = fmaxf(a[q + 1], a[q + 1 + W - K]);  // q + W <= CG - 1 + R - 1 < N
+            s_wm[q] = wm;
+            // pruned only when a later group certainly holds more than this one possibly does (a group
+            // that holds a NaN has hi = +inf: its NaN positions may be starts, see the top)
+            if (g < static_cast<int64_t>(ng) && !(wm > s_hi[q])) s_cand[atomicAdd(&s_ncand, 1u)] = static_cast<uint16_t>(q);
+            __syncthreads();
+        }
     }
 
+    APT_WMARK("END coarse");
     // fine: exact terminal test for the candidate groups; each wave takes four candidates at
     // a time so their loads are in flight together.  The group md ahead (whose first positions close
     // the window of this group's positions) is only evaluated when its maximum could matter.
@@ -305,10 +372,16 @@ k_sync_words(const CallArgs call, const SlotPtrs *__restrict__ slots, uint32_t p
     float *wa = s_win + static_cast<size_t>(wave) * wlen;  // this wave's F window
     const uint32_t wneed = GS + 38u * pw - 1u;  // samples of a window
     // F window of the group at `base` -> wa -> its correlation values
-    auto eval_group = [&](uint64_t base, bool on) -> float {
-        for (uint32_t t = lane; t < wlen; t += 64) {
-            const uint64_t j = base + t;
-            wa[t] = (t < wneed && j < w) ? fsig[j] : 0.f;
+    // (INT: an interior chunk, `base` wave-uniform in a scalar register — the whole padded window lies inside F)
+    auto eval_group = [&](auto int_tag, uint64_t base, bool on) -> float {
+        if constexpr (decltype(int_tag)::value) {
+            const float *__restrict__ fb = fsig + base;
+            for (uint32_t t = lane; t < wlen; t += 64) wa[t] = fb[t];
+        } else {
+            for (uint32_t t = lane; t < wlen; t += 64) {
+                const uint64_t j = base + t;
+                wa[t] = (t < wneed && j < w) ? fsig[j] : 0.f;
+            }
         }
         __builtin_amdgcn_wave_barrier();
         const float v = nodes_eval_window<NL, PWC>(wa, on, lane, pw, fast);
@@ -321,10 +394,12 @@ k_sync_words(const CallArgs call, const SlotPtrs *__restrict__ slots, uint32_t p
     // when none of their upper bounds does; what the bounds leave open is settled by evaluating every
     // group in between that could matter — with EXACT; without, the candidate is handed back (false) for
     // the second pass, so that the four-candidates-in-flight loop stays free of that (rare) code.
-    auto settle = [&](auto exact_tag, int q, float cv, float c2v, bool in_v) -> bool {
+    auto settle = [&](auto exact_tag, auto int_tag, int q, float cv, float c2v, bool in_v) -> bool {
         constexpr bool EXACT = decltype(exact_tag)::value;
+        constexpr bool INT = decltype(int_tag)::value;
+        APT_WMARK("BEGIN settle");
         const uint64_t base = static_cast<uint64_t>(gw0 + q) * GS;
-        const bool in2 = in_v && base + lane + md < n_corr;
+        const bool in2 = INT ? in_v : (in_v && base + lane + md < n_corr);
         if (in_v && gw0 + q == 0 && lane == 0 && !(cv > 0.f)) cv = 0.f;  // the peak (0, 0.)
         // NaN: remembered for the start test, -inf for every comparison
         const unsigned long long nanword = __ballot(in_v && cv != cv) & kGroupMask;
@@ -347,7 +422,11 @@ k_sync_words(const CallArgs call, const SlotPtrs *__restrict__ slots, uint32_t p
         if (__ballot(open_lo) != 0ull) {
             float wm_hi = kNegInf;
             for (int h = q + 1 + lane; h < q + R; h += 64) wm_hi = fmaxf(wm_hi, s_hi[h]);
-            for (int d = 32; d >= 1; d >>= 1) wm_hi = fmaxf(wm_hi, __shfl_xor(wm_hi, d, 64));
+            if constexpr (LEAN) {
+                wm_hi = wave_max_all_dpp(wm_hi);
+            } else {
+                for (int d = 32; d >= 1; d >>= 1) wm_hi = fmaxf(wm_hi, __shfl_xor(wm_hi, d, 64));
+            }
             const bool open = open_lo && wm_hi > cv;
             if (__ballot(open) != 0ull) {
                 if constexpr (!EXACT) {
@@ -356,7 +435,11 @@ k_sync_words(const CallArgs call, const SlotPtrs *__restrict__ slots, uint32_t p
                     // exact maximum (NaNs left out) over the groups in between whose upper bound exceeds the
                     // smallest open value: the others cannot exceed any open position
                     float thr = open ? cv : -kNegInf;
-                    for (int d = 32; d >= 1; d >>= 1) thr = fminf(thr, __shfl_xor(thr, d, 64));
+                    if constexpr (LEAN) {
+                        thr = -wave_max_all_dpp(-thr);  // (negation is exact: the same minimum)
+                    } else {
+                        for (int d = 32; d >= 1; d >>= 1) thr = fminf(thr, __shfl_xor(thr, d, 64));
+                    }
                     float ex = kNegInf;
 #pragma unroll 1
                     for (int h0 = q + 1; h0 < q + R; h0 += 64) {
@@ -368,18 +451,22 @@ k_sync_words(const CallArgs call, const SlotPtrs *__restrict__ slots, uint32_t p
                             const int64_t gh = gw0 + h;  // >= 1
                             if (gh >= static_cast<int64_t>(ng)) break;
                             const uint64_t hb = static_cast<uint64_t>(gh) * GS;
-                            const bool on = lane < GS && hb + lane < n_corr;
+                            const bool on = lane < GS && (INT || hb + lane < n_corr);
                             float v = kNegInf;
                             if (corr != nullptr) {
                                 if (on) v = corr[hb + lane];
                             } else {
-                                v = eval_group(hb, on);
+                                v = eval_group(int_tag, hb, on);
                             }
                             if (v != v) v = kNegInf;
                             ex = fmaxf(ex, v);
                         }
                     }
-                    for (int d = 32; d >= 1; d >>= 1) ex = fmaxf(ex, __shfl_xor(ex, d, 64));
+                    if constexpr (LEAN) {
+                        ex = wave_max_all_dpp(ex);
+                    } else {
+                        for (int d = 32; d >= 1; d >>= 1) ex = fmaxf(ex, __shfl_xor(ex, d, 64));
+                    }
                     if (open) wm = ex;
                     if (lane == 0) atomicAdd(&flags[7], 1u);  // how often the bounds were not enough (tests, tuning)
                 }
@@ -391,7 +478,7 @@ k_sync_words(const CallArgs call, const SlotPtrs *__restrict__ slots, uint32_t p
         // that is still a terminal so far is below the upper bound of that maximum (on APT data: almost
         // never).
         const float gm_ahead = s_hi[q + R];
-        if (corr == nullptr && __ballot(in2 && !(wmax > cv) && gm_ahead > cv) != 0ull) c2v = eval_group(base + md, in2);
+        if (corr == nullptr && __ballot(in2 && !(wmax > cv) && gm_ahead > cv) != 0ull) c2v = eval_group(int_tag, base + md, in2);
         if (c2v != c2v) c2v = kNegInf;
         // prefix max over lanes <= lane of the group md positions ahead
         float pfx = c2v;
@@ -411,86 +498,118 @@ k_sync_words(const CallArgs call, const SlotPtrs *__restrict__ slots, uint32_t p
             s_nanw[q] = nanword;
         }
         __builtin_amdgcn_wave_barrier();
+        APT_WMARK("END settle");
         return true;
     };
-    bool any_deferred = false;
-    for (uint32_t c0 = wave * kBatch; c0 < ncand; c0 += kBatch * kNodesWaves) {
-        int qv[kBatch];
-        float cv[kBatch], c2v[kBatch];
-        bool inv[kBatch];
-        float fa[kBatch][NLR];
+    // LEAN: each wave its half of the candidate list (so that neither idles while the other has a batch of four),
+    // else batches of four dealt in turn
+    const uint32_t per_wave = (ncand + kNodesWaves - 1) / kNodesWaves;
+    const uint32_t c_lo = LEAN ? wave * per_wave : wave * kBatch;
+    const uint32_t c_hi = LEAN ? (c_lo + per_wave < ncand ? c_lo + per_wave : ncand) : ncand;
+    const uint32_t c_step = LEAN ? kBatch : kBatch * kNodesWaves;
+    auto fine_passes = [&](auto int_tag) {
+        constexpr bool INT = decltype(int_tag)::value;
+        bool any_deferred = false;
+        for (uint32_t c0 = c_lo; c0 < c_hi; c0 += c_step) {
+            int qv[kBatch];
+            float cv[kBatch], c2v[kBatch];
+            bool inv[kBatch];
+            float fa[kBatch][NLR];
+            APT_WMARK("BEGIN window-load");
 #pragma unroll
-        for (int e = 0; e < kBatch; ++e) {
-            const uint32_t ci = c0 + e;
-            qv[e] = (ci < ncand) ? s_cand[ci] : -1;
-            const int64_t g = gw0 + (qv[e] < 0 ? 0 : qv[e]);
-            const uint64_t i = static_cast<uint64_t>(g) * GS + lane;
-            inv[e] = qv[e] >= 0 && lane < GS && i < n_corr;
-            cv[e] = kNegInf;
-            c2v[e] = kNegInf;
-            if (corr != nullptr) {
-                if (inv[e]) {
-                    cv[e] = corr[i];
-                    if (i + md < n_corr) c2v[e] = corr[i + md];
-                }
-            } else if constexpr (NL > 0) {
+            for (int e = 0; e < kBatch; ++e) {
+                const uint32_t ci = c0 + e;
+                qv[e] = (ci < c_hi) ? s_cand[ci] : -1;
+                if constexpr (LEAN) qv[e] = __builtin_amdgcn_readfirstlane(qv[e]);  // wave-uniform: scalar from here on
+                const int64_t g = gw0 + (qv[e] < 0 ? 0 : qv[e]);
+                const uint64_t i = static_cast<uint64_t>(g) * GS + lane;
+                inv[e] = qv[e] >= 0 && lane < GS && (INT || i < n_corr);
+                cv[e] = kNegInf;
+                c2v[e] = kNegInf;
+                if constexpr (INT) {
+                    // (corr == nullptr) unpredicated: 64 NL samples from the group's first lie inside F, and what lies
+                    // past the window is never read back; an empty entry loads group 0's window and drops it
+                    const float *__restrict__ fb = fsig + static_cast<uint64_t>(g) * GS;
 #pragma unroll
-                for (int t = 0; t < NL; ++t) {
-                    const uint64_t j = static_cast<uint64_t>(g) * GS + lane + 64u * t;
-                    fa[e][t] = (qv[e] >= 0 && lane + 64u * t < wneed && j < w) ? fsig[j] : 0.f;
-                }
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < kBatch; ++e) {
-            if (qv[e] < 0) continue;  // wave-uniform
-            if (corr == nullptr) {
-                // F window of the candidate group -> LDS -> its 52 correlation values
-                if constexpr (NL > 0) {
-#pragma unroll
-                    for (int t = 0; t < NL; ++t)
-                        if (lane + 64u * t < wlen) wa[lane + 64 * t] = fa[e][t];
-                    __builtin_amdgcn_wave_barrier();
-                    cv[e] = nodes_eval_window<NL, PWC>(wa, inv[e], lane, pw, fast);
-                    __builtin_amdgcn_wave_barrier();  // the window is dead from here on: wa is reused
-                } else {
-                    cv[e] = eval_group(static_cast<uint64_t>(gw0 + qv[e]) * GS, inv[e]);
-                }
-            }
-            if (!settle(std::false_type{}, qv[e], cv[e], c2v[e], inv[e])) {
-                if (lane == 0) s_cand[c0 + e] = static_cast<uint16_t>(qv[e]) | kDeferred;
-                any_deferred = true;
-            }
-        }
-    }
-    // second pass: the candidates whose comparison with the groups in between the bounds left open (each
-    // wave its own; one at a time, from scratch)
-    if (any_deferred) {
-#pragma unroll 1
-        for (uint32_t c0 = wave * kBatch; c0 < ncand; c0 += kBatch * kNodesWaves) {
-#pragma unroll 1
-            for (uint32_t ci = c0; ci < c0 + kBatch && ci < ncand; ++ci) {
-                const uint16_t ent = s_cand[ci];
-                if (!(ent & kDeferred)) continue;  // wave-uniform
-                const int q = ent & (kDeferred - 1);
-                const uint64_t base = static_cast<uint64_t>(gw0 + q) * GS;
-                const bool in_v = lane < GS && base + lane < n_corr;
-                float cv = kNegInf, c2v = kNegInf;
-                if (corr != nullptr) {
-                    if (in_v) {
-                        cv = corr[base + lane];
-                        if (base + lane + md < n_corr) c2v = corr[base + lane + md];
+                    for (int t = 0; t < NL; ++t) fa[e][t] = fb[static_cast<uint32_t>(lane) + 64u * t];
+                } else if (corr != nullptr) {
+                    if (inv[e]) {
+                        cv[e] = corr[i];
+                        if (i + md < n_corr) c2v[e] = corr[i + md];
                     }
-                } else {
-                    cv = eval_group(base, in_v);
+                } else if constexpr (NL > 0) {
+#pragma unroll
+                    for (int t = 0; t < NL; ++t) {
+                        const uint64_t j = static_cast<uint64_t>(g) * GS + lane + 64u * t;
+                        fa[e][t] = (qv[e] >= 0 && lane + 64u * t < wneed && j < w) ? fsig[j] : 0.f;
+                    }
                 }
-                (void)settle(std::true_type{}, q, cv, c2v, in_v);
+            }
+            APT_WMARK("END window-load");
+#pragma unroll
+            for (int e = 0; e < kBatch; ++e) {
+                if (qv[e] < 0) continue;  // wave-uniform
+                APT_WMARK("BEGIN stage+chain");
+                if (corr == nullptr) {
+                    // F window of the candidate group -> LDS -> its 52 correlation values
+                    if constexpr (NL > 0) {
+#pragma unroll
+                        for (int t = 0; t < NL; ++t)
+                            if (lane + 64u * t < wlen) wa[lane + 64 * t] = fa[e][t];
+                        __builtin_amdgcn_wave_barrier();
+                        cv[e] = nodes_eval_window<NL, PWC>(wa, inv[e], lane, pw, fast);
+                        __builtin_amdgcn_wave_barrier();  // the window is dead from here on: wa is reused
+                    } else {
+                        cv[e] = eval_group(int_tag, static_cast<uint64_t>(gw0 + qv[e]) * GS, inv[e]);
+                    }
+                }
+                APT_WMARK("END stage+chain");
+                if (!settle(std::false_type{}, int_tag, qv[e], cv[e], c2v[e], inv[e])) {
+                    if (lane == 0) s_cand[c0 + e] = static_cast<uint16_t>(qv[e]) | kDeferred;
+                    any_deferred = true;
+                }
             }
         }
+        // second pass: the candidates whose comparison with the groups in between the bounds left open (each
+        // wave its own; one at a time, from scratch)
+        if (any_deferred) {
+#pragma unroll 1
+            for (uint32_t c0 = c_lo; c0 < c_hi; c0 += c_step) {
+#pragma unroll 1
+                for (uint32_t ci = c0; ci < c0 + kBatch && ci < c_hi; ++ci) {
+                    const uint16_t ent = s_cand[ci];
+                    if (!(ent & kDeferred)) continue;  // wave-uniform
+                    int q = ent & (kDeferred - 1);
+                    if constexpr (LEAN) q = __builtin_amdgcn_readfirstlane(q);
+                    const uint64_t base = static_cast<uint64_t>(gw0 + q) * GS;
+                    const bool in_v = lane < GS && (INT || base + lane < n_corr);
+                    float cv = kNegInf, c2v = kNegInf;
+                    if (corr != nullptr) {
+                        if (in_v) {
+                            cv = corr[base + lane];
+                            if (base + lane + md < n_corr) c2v = corr[base + lane + md];
+                        }
+                    } else {
+                        cv = eval_group(int_tag, base, in_v);
+                    }
+                    (void)settle(std::true_type{}, int_tag, q, cv, c2v, in_v);
+                }
+            }
+        }
+    };
+    // interior: every window this chunk can load — its own groups', and those of the groups up to R ahead — lies inside
+    // [0, w), and every position of those groups inside [0, n_corr) (w = n_corr + 38 pw; a padded window is at most
+    // GS + 38 pw + 2 samples long, and 64 NL <= R GS).  Wave-uniform.
+    if (LEAN && corr == nullptr &&
+        static_cast<uint64_t>(g0 + kChunkGroups + R + 1) * GS <= n_corr) {
+        if constexpr (LEAN) fine_passes(std::true_type{});
+    } else {
+        fine_passes(std::false_type{});
     }
     __syncthreads();
 
     // own groups' words -> HBM (every group of the chunk: zero where nothing was evaluated)
+    APT_WMARK("BEGIN write-out");
     {
         const int64_t g = g0 + tid;
         if (g < static_cast<int64_t>(ng)) {
@@ -498,11 +617,16 @@ k_sync_words(const CallArgs call, const SlotPtrs *__restrict__ slots, uint32_t p
             sp.nanw[g] = s_nanw[tid];
         }
     }
+    APT_WMARK("END write-out");
 }
 
 // k_sync_slots: the ordered node-terminal list of every chunk of 128 groups from the terminal / NaN words:
 // heads of runs of terminals, terminals whose (t - md - 1) is a terminal or a NaN position, terminals on the
 // grid, and the NaN positions a phase can start on (tagged with bit 31).  One thread per group.
+// SKIP (the default; APTGPU_WORDS_FORM=0: without): a wave whose 64 own groups hold no terminal and no NaN bit has
+// nothing to list whatever the groups behind it hold (every entry is a bit of an own word): it leaves out the
+// look-back loads, the scan and the bit loop, and contributes 0 to s_scan — about half the waves on APT data.
+template <bool SKIP>
 __global__ void __launch_bounds__(kNodesThreads)
 k_sync_slots(const CallArgs call, const SlotPtrs *__restrict__ slots, uint32_t pw, uint32_t r_groups /* md/GS */,
              uint32_t grid_groups /* spr/GS */)
@@ -525,9 +649,11 @@ k_sync_slots(const CallArgs call, const SlotPtrs *__restrict__ slots, uint32_t p
         return (gi >= 0 && gi < static_cast<int64_t>(ng)) ? p[gi] : 0ull;
     };
     uint64_t nw = 0, ns = 0;
-    if (g < static_cast<int64_t>(ng)) {
-        const uint64_t wd = words[g];
-        const uint64_t nb = nanw[g];
+    const bool own = g < static_cast<int64_t>(ng);
+    const uint64_t wd = own ? words[g] : 0ull;
+    const uint64_t nb = own ? nanw[g] : 0ull;
+    const bool busy = !SKIP || __ballot((wd | nb) != 0ull) != 0ull;  // (wave-uniform)
+    if (own && busy) {
         const uint64_t prev_bit = word_at(words, g - 1) >> (GS - 1);
         const uint64_t heads = wd & ~(((wd << 1) | prev_bit) & kGroupMask);
         // positions md+1 behind a terminal or behind a NaN position, and the grid: where a phase can start
@@ -541,9 +667,11 @@ k_sync_slots(const CallArgs call, const SlotPtrs *__restrict__ slots, uint32_t p
     // ordered compaction of the node-terminal positions of this chunk (NaN starts tagged with bit 31)
     const uint32_t cnt = static_cast<uint32_t>(__popcll(nw | ns));
     uint32_t inc = cnt;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
+    if (busy) {
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t o = __shfl_up(inc, d, 64);
+            if (lane >= d) inc += o;
+        }
     }
     if (lane == 63) s_scan[wave] = inc;
     __syncthreads();
@@ -1396,23 +1524,39 @@ void sync_nodes(hipStream_t s, const CallArgs &call, const SlotPtrs *d_slots, ui
     const dim3 grid(chunks, call.count);
     const uint32_t wneed = GS + 38u * pw - 1u;
     const bool dpp = sw.words_dpp;  // (APTGPU_WORDS_DPP, read at plan creation)
+    // the lean form (APTGPU_WORDS_FORM, read at plan creation): the compile-time pixel widths with the DPP scans and the
+    // reference's look-ahead, md = 0.8 rows = 32 pw groups
+    const bool lean = sw.words_form != 0 && dpp && r == 32u * pw;
+#define APT_WORDS_LAUNCH_(NL, PWC, DPP, LEAN)                                                                           \
+    hipLaunchKernelGGL((k_sync_words<NL, PWC, DPP, LEAN>), grid, dim3(kNodesThreads), lds, s, call, d_slots, pw, r,     \
+                       fast ? 1 : 0, use_corr ? 1 : 0)
 #define APT_WORDS_LAUNCH(NL, PWC)                                                                                       \
     do {                                                                                                                \
         if (dpp)                                                                                                        \
-            hipLaunchKernelGGL((k_sync_words<NL, PWC, true>), grid, dim3(kNodesThreads), lds, s, call, d_slots, pw, r,  \
-                               fast ? 1 : 0, use_corr ? 1 : 0);                                                         \
+            APT_WORDS_LAUNCH_(NL, PWC, true, false);                                                                    \
         else                                                                                                            \
-            hipLaunchKernelGGL((k_sync_words<NL, PWC, false>), grid, dim3(kNodesThreads), lds, s, call, d_slots, pw, r, \
-                               fast ? 1 : 0, use_corr ? 1 : 0);                                                         \
+            APT_WORDS_LAUNCH_(NL, PWC, false, false);                                                                   \
     } while (0)
-    if (pw == 3) APT_WORDS_LAUNCH(3, 3);        // standard profile
-    else if (pw == 4) APT_WORDS_LAUNCH(4, 4);   // fast profile
-    else if (pw == 5) APT_WORDS_LAUNCH(4, 5);   // slow profile
+#define APT_WORDS_LAUNCH_PW(NL, PWC)                                                                                    \
+    do {                                                                                                                \
+        if (lean)                                                                                                       \
+            APT_WORDS_LAUNCH_(NL, PWC, true, true);                                                                     \
+        else                                                                                                            \
+            APT_WORDS_LAUNCH(NL, PWC);                                                                                  \
+    } while (0)
+    if (pw == 3) APT_WORDS_LAUNCH_PW(3, 3);        // standard profile
+    else if (pw == 4) APT_WORDS_LAUNCH_PW(4, 4);   // fast profile
+    else if (pw == 5) APT_WORDS_LAUNCH_PW(4, 5);   // slow profile
     else if (wneed <= 192) APT_WORDS_LAUNCH(3, 0);
     else if (wneed <= 256) APT_WORDS_LAUNCH(4, 0);
     else APT_WORDS_LAUNCH(0, 0);
+#undef APT_WORDS_LAUNCH_PW
 #undef APT_WORDS_LAUNCH
-    hipLaunchKernelGGL(k_sync_slots, grid, dim3(kNodesThreads), 0, s, call, d_slots, pw, r, spr / GS);
+#undef APT_WORDS_LAUNCH_
+    if (sw.words_form != 0)
+        hipLaunchKernelGGL(k_sync_slots<true>, grid, dim3(kNodesThreads), 0, s, call, d_slots, pw, r, spr / GS);
+    else
+        hipLaunchKernelGGL(k_sync_slots<false>, grid, dim3(kNodesThreads), 0, s, call, d_slots, pw, r, spr / GS);
 }
 
 // node-terminal capacity and uint32 words of scratch k_sync_orbit needs for a work signal of w samples
