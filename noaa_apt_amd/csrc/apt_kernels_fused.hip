@@ -16,8 +16,9 @@
 //   PHASE (M < 0: every other rate a sound card records at)   taps thread-resident, samples paired in LDS;
 //   TABLE (M == 0: fallback)     taps and samples from LDS.
 // Every product and sum is a separate multiplication / addition in the reference's order: bit-identical to the scalar
-// Rust loop (no FMA; #pragma fp contract(off)).  This file: the host side — which kernel serves which geometry, the
-// tap tables in the layouts the kernels read, the launch dispatch.
+// Rust loop (no FMA; #pragma fp contract(off)).  This file: the host side — the tap tables in the layouts the kernels
+// read and the launch dispatch; which kernel serves which geometry: the list and the selection functions of
+// apt_kernels_fused_variants.hpp.
 #include "apt_kernels_fused_launch.hpp"
 
 #include <hip/hip_runtime.h>
@@ -34,15 +35,27 @@
 
 namespace apt::gpu {
 
+namespace {
+// the launch functions of the list's rows, [variant][pcm16]; launches variant v, false where there is none
+using LaunchFn = void (*)(const FusedLaunch &);
+#define APT_FUSED_FN_BOTH(name, ...) {&fused_launch<kFused_##name, float>, &fused_launch<kFused_##name, int16_t>},
+#define APT_FUSED_FN_F32(name, ...) {&fused_launch<kFused_##name, float>, nullptr},
+constexpr LaunchFn kFusedLaunch[kFusedVariantCount][2] = {APT_FUSED_VARIANTS(APT_FUSED_FN_BOTH, APT_FUSED_FN_F32)};
+#undef APT_FUSED_FN_BOTH
+#undef APT_FUSED_FN_F32
+bool launch_variant(FusedVariant v, bool pcm16, const FusedLaunch &a)
+{
+    const LaunchFn fn = v == kFusedNone ? nullptr : kFusedLaunch[v][pcm16 ? 1 : 0];
+    if (fn) fn(a);
+    return fn != nullptr;
+}
+}  // namespace
 
+// the stock geometries: a strict SPLIT kernel compiled for exactly these tap counts (48 / 96 kHz at the standard and slow
+// profiles, 96 kHz at the fast profile)
 bool fused_supported(uint32_t l, uint32_t m, uint32_t t1, uint32_t t2, uint32_t pw)
 {
-    if (l == 13 && m == 50 && t1 == 959 && t2 == 37 && pw == 3) return true;    // 48 kHz, standard
-    if (l == 13 && m == 100 && t1 == 1915 && t2 == 37 && pw == 3) return true;  // 96 kHz, standard
-    if (l == 13 && m == 30 && t1 == 2783 && t2 == 61 && pw == 5) return true;    // 48 kHz, slow profile
-    if (l == 13 && m == 60 && t1 == 5565 && t2 == 61 && pw == 5) return true;    // 96 kHz, slow profile (strict instantiations only)
-    if (l == 13 && m == 75 && t1 == 639 && t2 == 43 && pw == 4) return true;     // 96 kHz, fast profile (strict, f32 input only: odd m)
-    return false;
+    return fused_exact_variant(l, m, t1, t2, pw, kModeStrict) != kFusedNone;
 }
 
 uint32_t fused_group_size(uint32_t l) { return 4 * l; }
@@ -156,7 +169,7 @@ float fused_f16_branch_taps(uint32_t l, uint32_t m, const float *coeff, uint32_t
 
 bool fused_f16_supported(uint32_t l, uint32_t m, uint32_t t1, uint32_t t2, uint32_t pw)
 {
-    return l == 13 && m == 50 && t1 == 959 && t2 == 37 && pw == 3;
+    return fused_exact_variant(l, m, t1, t2, pw, kModeF16Taps) != kFusedNone;
 }
 
 // Bound on |a - c| / sum|F| for a = the pulse-sum evaluation and c = the reference's sequential chain of
@@ -169,40 +182,19 @@ float fused_gm_slack(uint32_t pw, float scale)
     return static_cast<float>(38u * pw - 1u + pw + 18u) * 1.03f * 0x1p-24f * 1.0001f * (scale >= 1.f ? scale : 1.f);
 }
 
+// (not 96 kHz at the slow profile — 100 KB of unrolled taps per instantiation — nor at the fast profile: their strict
+// kernels serve fast mode)
 bool fused_fast_supported(uint32_t l, uint32_t m, uint32_t t1, uint32_t t2, uint32_t pw)
 {
-    if (l == 13 && m == 60 && t1 == 5565) return false;  // (100 KB of unrolled taps per instantiation: the strict kernel serves fast mode)
-    if (l == 13 && m == 75) return false;
-    return fused_supported(l, m, t1, t2, pw);
+    return fused_exact_variant(l, m, t1, t2, pw, kModeFast) != kFusedNone;
 }
 
-// ---- kModeStrictPad: the strict SPLIT kernels compiled for a tap-count bound (apt_kernels_fused_launch.hpp)
-// kModeStrictPad2: the low-pass bound of the instantiation that serves a low-pass of t2 taps other than the profile's
-// (a tuned demodulation_atten), or 0 — the standard profile's work-rate stages at 48 / 96 kHz
-uint32_t fused_pad_t2(uint32_t l, uint32_t m, uint32_t t2, uint32_t pw)
-{
-    if (l != 13 || pw != 3 || (m != 50 && m != 100)) return 0;
-    if ((t2 & 1u) == 0 || t2 == 37 || t2 > static_cast<uint32_t>(kPadT2Max)) return 0;
-    return static_cast<uint32_t>(kPadT2Max);
-}
-uint32_t fused_pad_t1(uint32_t l, uint32_t m, uint32_t t1, uint32_t t2, uint32_t pw)
-{
-    if (l != 13 || (t1 & 1u) == 0) return 0;  // (Kaiser lengths are odd: filters.rs:164-167)
-    uint32_t bound = 0;
-    if ((t2 == 37 || fused_pad_t2(l, m, t2, pw) != 0) && pw == 3) bound = m == 50 ? kPadT1Max48k : m == 100 ? kPadT1Max96k : 0;  // standard profile
-    else if (t2 == 61 && pw == 5) bound = m == 30 ? kPadT1Max48kSlow : m == 60 ? kPadT1Max96kSlow : 0;  // slow profile
-    else if (t2 == 43 && pw == 4) bound = m == 75 ? kPadT1Max96kFastp : 0;                            // fast profile, 96 kHz
-    return t1 <= bound ? bound : 0;
-}
+// ---- kModeStrictPad / kModeStrictPad2: the strict SPLIT kernels compiled for bounds (apt_kernels_fused_variants.hpp)
+uint32_t fused_pad_t2(uint32_t l, uint32_t m, uint32_t t2, uint32_t pw) { return fused_pad_t2_bound(l, m, t2, pw); }
+uint32_t fused_pad_t1(uint32_t l, uint32_t m, uint32_t t1, uint32_t t2, uint32_t pw) { return fused_pad_t1_bound(l, m, t1, t2, pw); }
 
-// ---- kModeMfma: the FIRs as banded Toeplitz products on the matrix cores (apt_kernels_fused_launch.hpp)
-bool fused_mfma_supported(uint32_t l, uint32_t m, uint32_t t1, uint32_t t2, uint32_t pw)
-{
-    if (l != 13 || t2 != 37 || pw != 3 || (t1 & 1u) == 0) return false;  // (Kaiser lengths are odd: filters.rs:164-167)
-    if (m == 50) return t1 <= static_cast<uint32_t>(kMfmaT1Max48k);
-    if (m == 100) return t1 <= static_cast<uint32_t>(kMfmaT1Max96k);
-    return false;
-}
+// ---- kModeMfma: the FIRs as banded Toeplitz products on the matrix cores (apt_kernels_fused_variants.hpp)
+bool fused_mfma_supported(uint32_t l, uint32_t m, uint32_t t1, uint32_t t2, uint32_t pw) { return fused_mfma_fits(l, m, t1, t2, pw); }
 
 namespace {
 uint32_t mfma_kpad(uint32_t l, uint32_t m)
@@ -273,88 +265,28 @@ bool fused_front_end(hipStream_t s, uint32_t l, uint32_t m, uint32_t t1, uint32_
         for (uint32_t i = 0; i < call.count; ++i)
             if (reinterpret_cast<uintptr_t>(call.rec[i].x) & 3u) return false;
     const FusedLaunch a{s, &call, d_prm, max_w, 0, lds_pad};
-    if (mode == kModeStrictPad) {
-        if (fused_pad_t1(l, m, t1, t2, pw) == 0) return false;
-        if (fused_pad_t2(l, m, t2, pw) != 0) {  // the low-pass length a bound too (kModeStrictPad2)
-            if (m == 50) pcm16 ? fused_launch_48k_pad2_i16(a) : fused_launch_48k_pad2_f32(a);
-            else pcm16 ? fused_launch_96k_pad2_i16(a) : fused_launch_96k_pad2_f32(a);
-        } else
-        if (m == 50) pcm16 ? fused_launch_48k_pad_i16(a) : fused_launch_48k_pad_f32(a);
-        else if (m == 100) pcm16 ? fused_launch_96k_pad_i16(a) : fused_launch_96k_pad_f32(a);
-        else if (m == 30) pcm16 ? fused_launch_48k_slow_pad_i16(a) : fused_launch_48k_slow_pad_f32(a);
-        else if (m == 60) pcm16 ? fused_launch_96k_slow_pad_i16(a) : fused_launch_96k_slow_pad_f32(a);
-        else if (m == 75 && !pcm16) fused_launch_96k_fastp_pad_f32(a);
-        else return false;
-        return true;
-    }
-    if (mode == kModeMfma) {
-        if (!fused_mfma_supported(l, m, t1, t2, pw)) return false;
-        if (m == 50) pcm16 ? fused_launch_48k_mfma_i16(a) : fused_launch_48k_mfma_f32(a);
-        else pcm16 ? fused_launch_96k_mfma_i16(a) : fused_launch_96k_mfma_f32(a);
-        return true;
-    }
-    if (l == 13 && m == 50 && t1 == 959 && t2 == 37 && pw == 3) {
-        if (mode == kModeF16Taps)  // fp16-tap stage 1: hb is the half2 table of fused_f16_branch_taps
-            pcm16 ? fused_launch_48k_f16taps_i16(a) : fused_launch_48k_f16taps_f32(a);
-        else if (mode == kModeFast) {
+    const FusedVariant v = fused_split_variant(l, m, t1, t2, pw, mode, pcm16);
 #ifdef APT_WITH_PROBES
-            static const int probe = [] {
-                const char *e = std::getenv("APTGPU_PROBE_STOP");
-                return e ? std::atoi(e) : 0;
-            }();
-            if (!pcm16 && probe >= 1 && probe <= 9 && probe != 6 && probe != 7) {  // (6, 7: the 128 / 192-thread forms, gone with the unsplit stage 1)
-                void (*const fn[9])(const FusedLaunch &) = {fused_launch_probe1, fused_launch_probe2, fused_launch_probe3,
-                                                            fused_launch_probe4, fused_launch_probe5, nullptr,
-                                                            nullptr, fused_launch_probe8, fused_launch_probe9};
-                fn[probe - 1](a);
-            } else
+    // APTGPU_PROBE_STOP: the timing probes stand in for the stock 48 kHz f32 kernels (fast: 1..5, 8, 9; strict: 11..17)
+    static const int probe = [] {
+        const char *e = std::getenv("APTGPU_PROBE_STOP");
+        return e ? std::atoi(e) : 0;
+    }();
+    if (v == kFused_48k_fast && !pcm16 && probe >= 1 && probe <= 9 && probe != 6 && probe != 7) {  // (6, 7: the 128 / 192-thread forms, gone with the unsplit stage 1)
+        void (*const fn[9])(const FusedLaunch &) = {fused_launch_probe1, fused_launch_probe2, fused_launch_probe3,
+                                                    fused_launch_probe4, fused_launch_probe5, nullptr,
+                                                    nullptr, fused_launch_probe8, fused_launch_probe9};
+        fn[probe - 1](a);
+        return true;
+    }
+    if (v == kFused_48k && !pcm16 && probe >= 11 && probe <= 17) {
+        void (*const fn[7])(const FusedLaunch &) = {fused_launch_probe11, fused_launch_probe12, fused_launch_probe13,
+                                                    fused_launch_probe14, fused_launch_probe15, fused_launch_probe16, fused_launch_probe17};
+        fn[probe - 11](a);
+        return true;
+    }
 #endif
-            {
-                pcm16 ? fused_launch_48k_fast_i16(a) : fused_launch_48k_fast_f32(a);
-            }
-        }
-        else {
-#ifdef APT_WITH_PROBES
-            static const int sprobe = [] {
-                const char *e = std::getenv("APTGPU_PROBE_STOP");
-                return e ? std::atoi(e) : 0;
-            }();
-            if (!pcm16 && sprobe >= 11 && sprobe <= 17) {
-                void (*const fn[7])(const FusedLaunch &) = {fused_launch_probe11, fused_launch_probe12, fused_launch_probe13,
-                                                            fused_launch_probe14, fused_launch_probe15, fused_launch_probe16, fused_launch_probe17};
-                fn[sprobe - 11](a);
-            } else
-#endif
-            {
-                pcm16 ? fused_launch_48k_i16(a) : fused_launch_48k_f32(a);
-            }
-        }
-        return true;
-    }
-    if (l == 13 && m == 30 && t1 == 2783 && t2 == 61 && pw == 5 && mode != kModeF16Taps) {
-        if (mode == kModeFast)
-            pcm16 ? fused_launch_48k_slow_fast_i16(a) : fused_launch_48k_slow_fast_f32(a);
-        else
-            pcm16 ? fused_launch_48k_slow_i16(a) : fused_launch_48k_slow_f32(a);
-        return true;
-    }
-    if (l == 13 && m == 75 && t1 == 639 && t2 == 43 && pw == 4 && mode == kModeStrict && !pcm16) {
-        fused_launch_96k_fastp_f32(a);
-        return true;
-    }
-    if (l == 13 && m == 60 && t1 == 5565 && t2 == 61 && pw == 5 && mode == kModeStrict) {
-        pcm16 ? fused_launch_96k_slow_i16(a) : fused_launch_96k_slow_f32(a);
-        return true;
-    }
-    if (l == 13 && m == 100 && t1 == 1915 && t2 == 37 && pw == 3 && mode != kModeF16Taps) {
-        // twice the input per work sample: 128-thread workgroups keep the x tile at 51.8 KB
-        if (mode == kModeFast)
-            pcm16 ? fused_launch_96k_fast_i16(a) : fused_launch_96k_fast_f32(a);
-        else
-            pcm16 ? fused_launch_96k_i16(a) : fused_launch_96k_f32(a);
-        return true;
-    }
-    return false;
+    return launch_variant(v, pcm16, a);
 }
 
 
@@ -396,13 +328,7 @@ bool fused_table_front_end(hipStream_t s, const TableGeom &geom, int mode, bool 
         for (uint32_t i = 0; i < call.count; ++i)
             if (reinterpret_cast<uintptr_t>(call.rec[i].x) & 1u) return false;
     const FusedLaunch a{s, &call, d_prm, max_w, static_cast<size_t>(geom.off_x) + geom.xt};
-    if (mode == kModeFast)
-        pcm16 ? fused_launch_tab_std_fast_i16(a) : fused_launch_tab_std_fast_f32(a);
-    else if (mode == kModeStrict)
-        pcm16 ? fused_launch_tab_std_i16(a) : fused_launch_tab_std_f32(a);
-    else
-        return false;
-    return true;
+    return launch_variant(fused_table_variant(mode), pcm16, a);
 }
 
 
@@ -513,18 +439,11 @@ bool phase_geom(uint32_t threads, uint32_t nq, uint32_t l, uint32_t m, uint32_t 
 
 // kModeStrictPad2 on the PHASE kernels: the low-pass bound of the instantiation that serves a low-pass of t2 taps other than
 // the standard profile's 37 (a tuned demodulation_atten at a sound-card rate), or 0
-namespace {
-uint32_t phase_pad_t2_bound(uint32_t t2, uint32_t pw)
-{
-    if (pw != 3 || (t2 & 1u) == 0 || t2 == 37 || t2 > static_cast<uint32_t>(kPadT2Max)) return 0;
-    return static_cast<uint32_t>(kPadT2Max);
-}
-}  // namespace
 uint32_t fused_phase_pad_t2(uint32_t t2, uint32_t pw)  // (plan creation: reads the A/B switch)
 {
     const char *off = std::getenv("APTGPU_FUSED_PAD");  // (tests: 0 = as until round 6, k_fused_any)
     if (off && off[0] == '0') return 0;
-    return phase_pad_t2_bound(t2, pw);
+    return fused_phase_pad_t2_bound(t2, pw);
 }
 
 bool fused_phase_supported(uint32_t l, uint32_t m, uint32_t t1, uint32_t t2, uint32_t pw, TableGeom *geom)
@@ -738,64 +657,7 @@ bool fused_phase_front_end(hipStream_t s, const TableGeom &geom, uint32_t t2, ui
     const bool halves = phase_halves(static_cast<int>(geom.nq ? geom.nq : 1u), geom.stream != 0, static_cast<int>(geom.nthr),
                                      static_cast<int>(t2), fast_kernel);
     const FusedLaunch a{s, &call, d_prm, max_w, static_cast<size_t>(halves ? geom.xt / 2 : geom.xt)};
-    const bool wide = geom.nthr == 512, huge = geom.nthr == 1024;
-    if (t2 == 61 && pw == 5) {  // the slow profile's work-rate stages, streamed taps (strict instantiations only: they serve fast mode too)
-        if (wide || huge || !geom.stream) return false;
-        if (geom.nq == 1) pcm16 ? fused_launch_phase_slowp_i16(a) : fused_launch_phase_slowp_f32(a);
-        else if (geom.nq == 2) pcm16 ? fused_launch_phase2_slowp_i16(a) : fused_launch_phase2_slowp_f32(a);
-        else if (geom.nq == 4) pcm16 ? fused_launch_phase4_slowp_i16(a) : fused_launch_phase4_slowp_f32(a);
-        else return false;
-        return true;
-    }
-    if (t2 == 43 && pw == 4 && geom.nq > 1) {  // the fast profile's, four / eight branches per thread (strict instantiations only)
-        if (wide || huge) return false;
-        if (geom.nq == 4) pcm16 ? fused_launch_phase4_fastp_i16(a) : fused_launch_phase4_fastp_f32(a);
-        else if (geom.nq == 8) pcm16 ? fused_launch_phase8_fastp_i16(a) : fused_launch_phase8_fastp_f32(a);
-        else if (geom.nq == 16) pcm16 ? fused_launch_phase16_fastp_i16(a) : fused_launch_phase16_fastp_f32(a);
-        else return false;
-        return true;
-    }
-    if (t2 == 43 && pw == 4) {  // the fast profile's work-rate stages
-        if (wide || huge) return false;
-        if (mode == kModeFast) pcm16 ? fused_launch_phase_fastp_fast_i16(a) : fused_launch_phase_fastp_fast_f32(a);
-        else if (mode == kModeStrict) pcm16 ? fused_launch_phase_fastp_i16(a) : fused_launch_phase_fastp_f32(a);
-        else return false;
-        return true;
-    }
-    if (pw == 3 && t2 != 37) {  // a tuned low-pass: kModeStrictPad2 (strict arithmetic: it serves APTGPU_MODE_FAST too)
-        if (wide || huge || phase_pad_t2_bound(t2, pw) == 0) return false;
-        if (geom.nq == 1 || geom.nq == 0) pcm16 ? fused_launch_phase_std_pad2_i16(a) : fused_launch_phase_std_pad2_f32(a);
-        else if (geom.nq == 2) pcm16 ? fused_launch_phase2_std_pad2_i16(a) : fused_launch_phase2_std_pad2_f32(a);
-        else if (geom.nq == 4) pcm16 ? fused_launch_phase4_std_pad2_i16(a) : fused_launch_phase4_std_pad2_f32(a);
-        else return false;
-        return true;
-    }
-    if (geom.nq == 2 || geom.nq == 4) {
-        if (wide || huge) return false;
-        const bool four = geom.nq == 4;
-        if (mode == kModeFast) {
-            if (four) pcm16 ? fused_launch_phase4_std_fast_i16(a) : fused_launch_phase4_std_fast_f32(a);
-            else pcm16 ? fused_launch_phase2_std_fast_i16(a) : fused_launch_phase2_std_fast_f32(a);
-        } else if (mode == kModeStrict) {
-            if (four) pcm16 ? fused_launch_phase4_std_i16(a) : fused_launch_phase4_std_f32(a);
-            else pcm16 ? fused_launch_phase2_std_i16(a) : fused_launch_phase2_std_f32(a);
-        } else {
-            return false;
-        }
-        return true;
-    }
-    if (mode == kModeFast) {
-        if (huge) pcm16 ? fused_launch_phase1024_std_fast_i16(a) : fused_launch_phase1024_std_fast_f32(a);
-        else if (wide) pcm16 ? fused_launch_phase512_std_fast_i16(a) : fused_launch_phase512_std_fast_f32(a);
-        else pcm16 ? fused_launch_phase_std_fast_i16(a) : fused_launch_phase_std_fast_f32(a);
-    } else if (mode == kModeStrict) {
-        if (huge) pcm16 ? fused_launch_phase1024_std_i16(a) : fused_launch_phase1024_std_f32(a);
-        else if (wide) pcm16 ? fused_launch_phase512_std_i16(a) : fused_launch_phase512_std_f32(a);
-        else pcm16 ? fused_launch_phase_std_i16(a) : fused_launch_phase_std_f32(a);
-    }
-    else
-        return false;
-    return true;
+    return launch_variant(fused_phase_variant(geom.nq, geom.nthr, geom.stream != 0, t2, pw, mode), pcm16, a);
 }
 
 }  // namespace apt::gpu

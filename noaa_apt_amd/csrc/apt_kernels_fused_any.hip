@@ -182,13 +182,13 @@ bool fused_any_front_end(hipStream_t s, uint32_t l, uint32_t m, uint32_t t1, uin
             if (reinterpret_cast<uintptr_t>(call.rec[i].x) & 1u) return false;
     const int prof = (t2 == 37 && pw == 3) ? 1 : (t2 == 43 && pw == 4) ? 2 : (t2 == 61 && pw == 5) ? 3 : 0;
     if (c.nthr == 256 && c.kpt == 8)
-        fused_any_launch_256x8(s, call, d_slots, max_w, pcm16, table, h2, h2p, cosphi2, sinphi, inv_sinphi, want_gm, g, lds, prof);
+        fused_any_launch<256, 8>(s, call, d_slots, max_w, pcm16, table, h2, h2p, cosphi2, sinphi, inv_sinphi, want_gm, g, lds, prof);
     else if (c.nthr == 1024 && c.kpt == 8)
-        fused_any_launch_1024x8(s, call, d_slots, max_w, pcm16, table, h2, h2p, cosphi2, sinphi, inv_sinphi, want_gm, g, lds, prof);
+        fused_any_launch<1024, 8>(s, call, d_slots, max_w, pcm16, table, h2, h2p, cosphi2, sinphi, inv_sinphi, want_gm, g, lds, prof);
     else if (c.nthr == 1024 && c.kpt == 4)
-        fused_any_launch_1024x4(s, call, d_slots, max_w, pcm16, table, h2, h2p, cosphi2, sinphi, inv_sinphi, want_gm, g, lds, prof);
+        fused_any_launch<1024, 4>(s, call, d_slots, max_w, pcm16, table, h2, h2p, cosphi2, sinphi, inv_sinphi, want_gm, g, lds, prof);
     else if (c.nthr == 256 && c.kpt == 4)
-        fused_any_launch_256x4(s, call, d_slots, max_w, pcm16, table, h2, h2p, cosphi2, sinphi, inv_sinphi, want_gm, g, lds, prof);
+        fused_any_launch<256, 4>(s, call, d_slots, max_w, pcm16, table, h2, h2p, cosphi2, sinphi, inv_sinphi, want_gm, g, lds, prof);
     else
         return false;
     return true;

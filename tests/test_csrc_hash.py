@@ -13,7 +13,8 @@ def _tree(tmp_path):
     d.mkdir(parents=True)
     src = os.path.join(ROOT, "noaa_apt_amd", "csrc")
     for n in ("apt_kernels.hpp", "apt_sync_corr.hpp", "apt_envelope.hpp", "Makefile", "apt_kernels_sync.hip",
-              "apt_kernels_generic.hip", "apt_kernels_fused_impl.hpp", "apt_kernels_fused_48k_f32.hip",
+              "apt_kernels_generic.hip", "apt_kernels_fused_impl.hpp", "apt_kernels_fused_variant.hip",
+              "apt_kernels_fused_variants.hpp",
               "apt_kernels_fused_any_impl.hpp", "apt_plan.hip"):
         shutil.copy(os.path.join(src, n), d / n)
     return str(tmp_path), d

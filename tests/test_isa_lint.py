@@ -2,7 +2,7 @@
 tuples, waited for one chunk later): tools/isa_lint.py checks the generated code for the one thing that would break it —
 an instruction that touches a tuple between its load and its wait.  Here: the check itself on hand-made listings, and
 on the freshly compiled listing of two of the kernels (hipcc cross-compiles without a GPU; `make -C noaa_apt_amd/csrc lint`
-does all eight)."""
+does every SPLIT one)."""
 import os
 import subprocess
 import sys
@@ -52,8 +52,9 @@ def test_compiled_kernels_keep_their_hands_off_taps_in_flight(tmp_path):
     csrc = os.path.join(ROOT, "noaa_apt_amd", "csrc")
     flags = ("--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math "
              "-fhip-fp32-correctly-rounded-divide-sqrt -fno-slp-vectorize --cuda-device-only -S").split()
-    tus = ["fused_48k_f32", "fused_96k_fast_f32"]
-    procs = [subprocess.Popen(["/opt/rocm/bin/hipcc", *flags, "-o", str(tmp_path / f"{k}.s"), f"apt_kernels_{k}.hip"],
+    tus = ["48k_f32", "96k_fast_f32"]  # (rows 48k and 96k_fast of apt_kernels_fused_variants.hpp, f32 input)
+    procs = [subprocess.Popen(["/opt/rocm/bin/hipcc", *flags, f"-DAPT_FUSED_VARIANT=kFused_{k[:-4]}", "-DAPT_FUSED_XT=float",
+                               "-o", str(tmp_path / f"{k}.s"), "apt_kernels_fused_variant.hip"],
                               cwd=csrc, stderr=subprocess.PIPE) for k in tus]
     for p in procs:
         _, err = p.communicate(timeout=600)

@@ -19,7 +19,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # headers every kernel translation unit includes, and the build flags
 _COMMON = ("apt_kernels.hpp", "apt_sync_corr.hpp", "apt_envelope.hpp", "Makefile")
 _GROUPS = {
-    # k_fused<...>: the specialised front ends (SPLIT / TABLE / PHASE), one instantiation per file
+    # k_fused<...>: the specialised front ends (SPLIT / TABLE / PHASE): one source compiled once per row of the list in
+    # apt_kernels_fused_variants.hpp
     "front_end": lambda n: n.startswith("apt_kernels_fused") and "fused_any" not in n,
     # k_fused_any: the run-time front end
     "front_end_any": lambda n: n.startswith("apt_kernels_fused_any"),
@@ -30,7 +31,7 @@ _GROUPS = {
 
 def _makefile_flags(path):
     """What of the Makefile decides how a kernel is compiled: the compiler, the architecture and the flags — not the list of
-    translation units (round 6: adding an instantiation file used to invalidate every group's profiles)."""
+    translation units (round 6: adding an instantiation used to invalidate every group's profiles)."""
     keep = []
     with open(path, "rb") as f:
         for line in f.read().splitlines():
