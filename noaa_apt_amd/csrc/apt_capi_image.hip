@@ -24,6 +24,10 @@ namespace {
 
 using namespace apt::capi;
 using apt::gpu::ImageResult;
+using apt::ImageJob;
+using apt::ImageRequest;
+using Recording = apt::ImageRequest::Recording;
+using Track = apt::ImageRequest::Track;
 
 static_assert(sizeof(ImageResult) == sizeof(aptgpu_image_result), "ImageResult must mirror aptgpu_image_result");
 
@@ -109,14 +113,19 @@ struct ImageCall {
         d_info.alloc(1);
         apt::gpu::image_begin(sc.stream, d_info.ptr);
     }
-    ImageResult info()
+    // the call as one job of the image stages: (res, n, cap) = (null, n, n)
+    ImageJob job()
+    {
+        return ImageJob{sc.stream, d_x.ptr, nullptr, n, n, ws.ptr, d_info.ptr};
+    }
+    static ImageResult read(hipStream_t s, const ImageResult *d)
     {
         ImageResult r{};
-        apt::hip_check(hipMemcpyAsync(&r, d_info.ptr, sizeof r, hipMemcpyDeviceToHost, sc.stream),
-                       "hipMemcpyAsync D2H");
-        apt::hip_check(hipStreamSynchronize(sc.stream), "hipStreamSynchronize");
+        apt::hip_check(hipMemcpyAsync(&r, d, sizeof r, hipMemcpyDeviceToHost, s), "hipMemcpyAsync D2H");
+        apt::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
         return r;
     }
+    ImageResult info() { return read(sc.stream, d_info.ptr); }
     void limits(float *low, float *high)
     {
         float lim[2] = {0.f, 0.f};
@@ -166,45 +175,56 @@ void telemetry_steps(const aptgpu_context *ctx, ImageCall &c, const ImageResult 
 // Histogram with false colour, whose limits are misc::percent(signal, 0.98) once get_min / get_max
 // have passed (noaa_apt.rs:170-175); their only error is the zero length, checked first.
 void process_limits(const aptgpu_context *ctx, ImageCall &c, int contrast, float percent, aptgpu_image_result *info,
-                    bool lab = false)
+                    bool lab)
 {
-    hipStream_t s = c.sc.stream;
-    const uint64_t n = c.n;
     if (contrast == APTGPU_CONTRAST_TELEMETRY) {
         status(ctx, 0.1f, "Adjusting contrast from telemetry");  // noaa_apt.rs:142
-        apt::gpu::image_telemetry(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, c.d_info.ptr, true);
-        const ImageResult r = c.info();
-        copy_out(info, r);
-        throw_for(r, contrast);
-        telemetry_steps(ctx, c, r);
     } else if (contrast == APTGPU_CONTRAST_PERCENT) {
         // noaa_apt.rs:152-155
         status(ctx, 0.1f, "Adjusting contrast using " + rust_display_f32(percent * 100.f) + " percent");
         if (percent < 0.f || percent > 1.f) throw Error{ErrorKind::Internal, kBadPercent};
-        if (n == 0) throw Error{ErrorKind::Internal, kZeroMin};
-        apt::gpu::image_percent(s, c.d_x.ptr, nullptr, n, n, percent, c.ws.ptr, c.d_info.ptr);
+        if (c.n == 0) throw Error{ErrorKind::Internal, kZeroMin};
     } else {
         status(ctx, 0.1f, "Mapping values");  // noaa_apt.rs:159 (MinMax and Histogram)
-        if (n == 0) throw Error{ErrorKind::Internal, kZeroMin};
-        if (lab)
-            apt::gpu::image_percent(s, c.d_x.ptr, nullptr, n, n, 0.98f, c.ws.ptr, c.d_info.ptr);
-        else
-            apt::gpu::image_minmax(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, c.d_info.ptr);
+        if (c.n == 0) throw Error{ErrorKind::Internal, kZeroMin};
+    }
+    apt::enqueue_image_limits(nullptr, c.job(), lab ? APTGPU_CONTRAST_PERCENT : contrast, lab ? 0.98f : percent);
+    if (contrast == APTGPU_CONTRAST_TELEMETRY) {
+        const ImageResult r = c.info();
+        copy_out(info, r);
+        throw_for(r, contrast);
+        telemetry_steps(ctx, c, r);
     }
 }
 
-// The checks of aptgpu_process_image / aptgpu_plan_process_device_image, all before any status callback.
-// Returns the folded tune values when false colour is on, and in *lab whether the Lab path runs.
-bool color_args(int contrast, int rotate, const aptgpu_color_settings *color, int channels, apt::gpu::ColorTune *tune,
-                bool *lab)
+void contrast_arg(int contrast, int last)
 {
-    *lab = false;
-    if (contrast < APTGPU_CONTRAST_TELEMETRY || contrast > APTGPU_CONTRAST_HISTOGRAM_FLOAT)
-        throw Error{ErrorKind::Invalid, "unknown contrast adjustment"};
+    if (contrast < APTGPU_CONTRAST_TELEMETRY || contrast > last) throw Error{ErrorKind::Invalid, "unknown contrast adjustment"};
+}
+
+void rotate_arg(int rotate)
+{
     if (rotate != APTGPU_ROTATE_NO && rotate != APTGPU_ROTATE_YES)
         throw Error{ErrorKind::Unsupported, "Rotate::Orbit needs the satellite and the time: aptgpu_orbit_settings, the *_orbit entry points"};
+}
+
+void channels_arg(int channels)
+{
     if (channels != 1 && channels != 4) throw Error{ErrorKind::Invalid, "channels must be 1 (gray) or 4 (RGBA)"};
-    if (!color) return false;
+}
+
+// The checks of aptgpu_process_image / aptgpu_plan_process_device_image, all before any status callback.
+// Fills the request's per-call part: the contrast, the channels and, with false colour, the folded tune values and
+// whether the Lab path runs.
+void color_args(ImageRequest &q, int contrast, float percent, int rotate, const aptgpu_color_settings *color, int channels)
+{
+    contrast_arg(contrast, APTGPU_CONTRAST_HISTOGRAM_FLOAT);
+    rotate_arg(rotate);
+    channels_arg(channels);
+    q.contrast = contrast;
+    q.percent = percent;
+    q.channels = channels;
+    if (!color) return;
     if (color->struct_size < sizeof(aptgpu_color_settings) || !color->palette_rgb)
         throw Error{ErrorKind::Invalid, "aptgpu_color_settings: struct_size or palette_rgb not set"};
     if (color->flags & ~APTGPU_COLOR_EQUALIZE_LAB) throw Error{ErrorKind::Invalid, "aptgpu_color_settings: unknown flags"};
@@ -217,18 +237,19 @@ bool color_args(int contrast, int rotate, const aptgpu_color_settings *color, in
             throw Error{ErrorKind::Unsupported,
                         "histogram equalisation of a false-colour image (CIE Lab, imageext.rs:51-64) needs "
                         "APTGPU_COLOR_EQUALIZE_LAB in aptgpu_color_settings.flags"};
-        *lab = true;
+        q.lab = true;
     }
     if (channels != 4) throw Error{ErrorKind::Invalid, "false colour needs channels = 4 (RGBA)"};
     // tune_input_values (processing.rs:126-140): the per-call part, f32 as the reference rounds it
     const float factor = 0.3f;
     const float s_a = color->ch_a_tune_start * factor, e_a = color->ch_a_tune_end * factor;
     const float s_b = color->ch_b_tune_start * factor, e_b = color->ch_b_tune_end * factor;
-    tune->k_a = 1.f + e_a - s_a;
-    tune->o_a = s_a * 255.f;
-    tune->k_b = 1.f + e_b - s_b;
-    tune->o_b = s_b * 255.f;
-    return true;
+    q.tune.k_a = 1.f + e_a - s_a;
+    q.tune.o_a = s_a * 255.f;
+    q.tune.k_b = 1.f + e_b - s_b;
+    q.tune.o_b = s_b * 255.f;
+    q.colored = true;
+    q.palette = color->palette_rgb;
 }
 
 int extreme(const aptgpu_context *ctx, const float *signal, size_t n, float *out, bool want_max, char *err,
@@ -246,33 +267,17 @@ int extreme(const aptgpu_context *ctx, const float *signal, size_t n, float *out
     });
 }
 
-// The map overlay of one call (aptgpu_process_image_map / aptgpu_plan_process_device_image_map).
-struct MapCall {
-    const aptgpu_map_settings *settings;
-    const apt::map::Layers *layers;
-};
-
-// The reprojection of one call or recording (the *_project entry points) after its checks: the grid, its graticule
-// and the yaw / hscale / vscale of the geometry (the overlay's settings when one is drawn).
-struct ProjectCall {
-    apt::project::Grid grid;
-    std::vector<uint8_t> flags;
-    aptgpu_map_settings ms;
-    uint64_t bytes() const { return static_cast<uint64_t>(grid.width) * grid.height * 4u; }
-};
-
-ProjectCall project_args(const aptgpu_projection_settings *proj, const aptgpu_map_settings *map)
+// The reprojection of one recording (the *_project entry points): the grid, its graticule and the yaw / hscale / vscale
+// of the geometry (`map`: the overlay's settings when one is drawn, nullable).
+void project_args(Recording &r, const aptgpu_projection_settings *proj, const aptgpu_map_settings *map)
 {
-    ProjectCall c;
-    c.grid = apt::project::checked(proj);
-    c.flags = apt::project::graticule(c.grid, proj->grid_deg);
-    c.ms = aptgpu_map_settings{sizeof(aptgpu_map_settings), 0, 0., 1., 1.};
+    r.grid = apt::project::checked(proj);
+    r.flags = apt::project::graticule(r.grid, proj->grid_deg);
     if (map) {
         if (map->struct_size < sizeof(aptgpu_map_settings))
             throw Error{ErrorKind::Invalid, "aptgpu_map_settings: struct_size not set"};
-        c.ms = *map;
+        r.geom = *map;
     }
-    return c;
 }
 
 // The projection reads the unrotated image and north is up by construction.
@@ -294,16 +299,6 @@ int layer_index(int layer)
 {
     if (layer < APTGPU_MAP_STATES || layer > APTGPU_MAP_LAKES) throw Error{ErrorKind::Invalid, "unknown map layer"};
     return layer;
-}
-
-apt::map::Scalars map_scalars(const MapCall &m, const double *positions, size_t count)
-{
-    return apt::map::scalars(positions, count, m.settings->yaw, m.settings->hscale, m.settings->vscale);
-}
-
-apt::map::Colors map_colors(const apt::map::Layers &l)
-{
-    return apt::map::Colors{{l.color[0], l.color[1], l.color[2]}};
 }
 
 // One recording's aptgpu_orbit_settings after its checks: the initialised satellite and the reference time for the
@@ -356,238 +351,219 @@ void png_args(const aptgpu_png_settings *png)
 uint64_t png_shape(uint32_t width, uint32_t height, int channels)
 {
     if (width == 0 || height == 0) throw Error{ErrorKind::Invalid, "a PNG needs a width and a height of at least 1"};
-    if (channels != 1 && channels != 4) throw Error{ErrorKind::Invalid, "channels must be 1 (gray) or 4 (RGBA)"};
+    channels_arg(channels);
     const uint64_t stream = apt::png::stream_bytes(width, height, channels);
     if (stream >= apt::png::kMaxStream) throw Error{ErrorKind::Invalid, "image too large for the PNG encoder (2^31 bytes)"};
     return stream;
 }
 
-// Copies the encoded file behind the call's stream to a malloc'd host buffer.
-void png_to_host(hipStream_t s, const uint8_t *d_png, size_t len, uint8_t **png_out, size_t *n_out)
+// Copies `len` bytes of an output behind the call's stream to a malloc'd host buffer.
+void to_host(hipStream_t s, const uint8_t *d, size_t len, uint8_t **out, size_t *n_out)
 {
     uint8_t *h = host_alloc<uint8_t>(len);
-    if (len && (hipMemcpyAsync(h, d_png, len, hipMemcpyDeviceToHost, s) != hipSuccess ||
+    if (len && (hipMemcpyAsync(h, d, len, hipMemcpyDeviceToHost, s) != hipSuccess ||
                 hipStreamSynchronize(s) != hipSuccess)) {
         std::free(h);
         throw Error{ErrorKind::Hip, "D2H copy failed"};
     }
-    *png_out = h;
+    *out = h;
     *n_out = len;
 }
 
-// png: encode the image on the device and return the file instead of the pixels
-int process_image(const aptgpu_context *ctx, const float *signal, size_t n, int contrast, float percent, int rotate,
-                  const aptgpu_color_settings *color, int channels, const MapCall *map, const double *positions,
-                  uint8_t **image_out, size_t *n_out, aptgpu_image_result *info, char *err, size_t err_cap,
-                  bool png = false, const apt::sat::TrackCall *sat = nullptr, const ProjectCall *pj = nullptr)
+// APTGPU_OUTPUT_*: whether the PNG file is asked for
+bool output_arg(int output)
 {
-    if ((!signal && n) || !image_out || !n_out) return APTGPU_ERR_INVALID;
-    *image_out = nullptr;
-    *n_out = 0;
-    return guarded(err, err_cap, [&] {
-        apt::gpu::ColorTune tune{};
-        bool lab = false;
-        const bool colored = color_args(contrast, rotate, color, channels, &tune, &lab);
-        if (map && n / 2080 == 0 && n != 0)
-            throw Error{ErrorKind::Internal, "map overlay: the image has no row to draw on"};
-        if (png && n / 2080 == 0 && n != 0) throw Error{ErrorKind::Invalid, "PNG encoding: the image has no row"};
-        if (pj && n / 2080 == 0 && n != 0) throw Error{ErrorKind::Internal, "reprojection: the image has no row to read"};
-        std::vector<uint32_t> packed;  // (outlives the call's stream: ~ImageCall synchronises it)
-        std::shared_ptr<const apt::lab::Tables> lab_tables;  // (likewise)
-        apt::map::Device map_dev;  // (likewise)
-        apt::project::Device project_dev;  // (likewise)
-        ImageCall c(ctx, signal, n);
-        hipStream_t s = c.sc.stream;
-        process_limits(ctx, c, contrast, percent, info, lab);
-        status(ctx, 0.3f, "Generating image");  // noaa_apt.rs:180
-        const size_t bytes = n / 2080 * 2080 * static_cast<size_t>(channels);
-        apt::DeviceBuffer<char> cws;
-        cws.alloc(apt::gpu::color_ws_bytes());
-        apt::hip_check(apt::gpu::color_ws_init(s, cws.ptr), "hipMemsetAsync");
-        apt::DeviceBuffer<char> lws;
-        if (lab) {
-            lab_tables = apt::lab::tables_for(color->palette_rgb);
-            lws.alloc(apt::gpu::lab_ws_bytes());
-            apt::hip_check(hipMemcpyAsync(lws.ptr, lab_tables.get(), sizeof(apt::lab::Tables), hipMemcpyHostToDevice, s),
-                           "hipMemcpyAsync H2D (Lab tables)");
-        } else if (colored) {
-            packed.resize(65536);
-            apt::gpu::color_pack_palette(color->palette_rgb, packed.data());
-            apt::hip_check(hipMemcpyAsync(apt::gpu::color_ws_palette(cws.ptr), packed.data(),
-                                          packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s),
-                           "hipMemcpyAsync H2D (palette)");
-        }
-        apt::DeviceBuffer<uint8_t> d_img;
-        d_img.alloc(bytes + 16);
-        const bool equalize = contrast == APTGPU_CONTRAST_HISTOGRAM;
-        const bool eqfloat = contrast == APTGPU_CONTRAST_HISTOGRAM_FLOAT;
-        apt::DeviceBuffer<char> fws;
-        if (eqfloat) {
-            fws.alloc(apt::gpu::eqfloat_ws_bytes());
-            apt::gpu::image_equalize_float(s, c.d_x.ptr, nullptr, n, n, fws.ptr);
-        } else if (lab) apt::gpu::image_equalize_lab(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, cws.ptr, lws.ptr, tune);
-        else if (equalize) apt::gpu::image_equalize(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, cws.ptr);
-        if (map) status(ctx, 0.5f, "Drawing map");                                    // noaa_apt.rs:205
-        if (rotate == APTGPU_ROTATE_YES) status(ctx, 0.90f, "Rotating output image");  // noaa_apt.rs:229
-        if (eqfloat)
-            apt::gpu::image_color_float(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, fws.ptr, channels,
-                                        rotate == APTGPU_ROTATE_YES, d_img.ptr, c.d_info.ptr);
-        else
-            apt::gpu::image_color(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, cws.ptr, equalize, colored ? &tune : nullptr,
-                                  channels, rotate == APTGPU_ROTATE_YES, d_img.ptr, c.d_info.ptr, lab ? lws.ptr : nullptr);
-        if (map) {
-            const size_t height = n / 2080;
-            map_dev.prepare(s, *map->layers, height);
-            if (sat) {
-                apt::map::image_map_overlay_sat(s, map_dev, *sat, map->settings->yaw, map->settings->hscale,
-                                                map->settings->vscale, map_colors(*map->layers),
-                                                rotate == APTGPU_ROTATE_YES, d_img.ptr, c.d_info.ptr);
-            } else {
-                map_dev.upload_track(s, positions, height);
-                apt::map::image_map_overlay(s, map_dev, map_scalars(*map, positions, height),
-                                            map_colors(*map->layers), static_cast<uint32_t>(height),
-                                            rotate == APTGPU_ROTATE_YES, d_img.ptr, c.d_info.ptr);
-            }
-        } else if (pj) {  // no overlay: the track's x offsets and the call's checks alone
-            const size_t height = n / 2080;
-            map_dev.prepare_track(s, height);
-            if (sat) {
-                apt::map::image_map_track_sat(s, map_dev, *sat, pj->ms.yaw, pj->ms.hscale, pj->ms.vscale, c.d_info.ptr);
-            } else {
-                map_dev.upload_track(s, positions, height);
-                apt::map::image_map_track(s, map_dev,
-                                          apt::map::scalars(positions, height, pj->ms.yaw, pj->ms.hscale, pj->ms.vscale),
-                                          static_cast<uint32_t>(height), c.d_info.ptr);
-            }
-        }
-        apt::DeviceBuffer<char> pws;
-        apt::DeviceBuffer<uint8_t> d_png, d_grid;
-        if (pj) {
-            d_grid.alloc(pj->bytes() + 16);
-            project_dev.upload_flags(s, pj->flags);
-            apt::map::Scalars host_sc{};
-            if (!sat) host_sc = apt::map::scalars(positions, n / 2080, pj->ms.yaw, pj->ms.hscale, pj->ms.vscale);
-            apt::project::image_project(s, project_dev, map_dev, sat ? nullptr : &host_sc, pj->grid, d_img.ptr, channels,
-                                        d_grid.ptr, pj->bytes(), c.d_info.ptr);
-            if (png) {
-                png_shape(pj->grid.width, pj->grid.height, 4);
-                const uint64_t cap = apt::png::bound(pj->grid.width, pj->grid.height, 4);
-                d_png.alloc(cap);
-                apt::project::image_project_png(s, project_dev, pj->grid, d_grid.ptr, d_png.ptr, cap, c.d_info.ptr);
-            }
-        } else if (png) {
-            const uint32_t height = static_cast<uint32_t>(n / 2080);
-            const uint64_t stream = png_shape(2080, height, channels);
-            const uint64_t cap = apt::png::bound(2080, height, channels);
-            pws.alloc(apt::png::ws_bytes(stream));
-            d_png.alloc(cap);
-            apt::png::encode(s, d_img.ptr, 2080, height, channels, pws.ptr, stream, d_png.ptr, cap, c.d_info.ptr, nullptr);
-        }
-        apt::hip_check(hipGetLastError(), "kernel launch (image stage)");
-        const ImageResult r = c.info();
-        copy_out(info, r);
-        throw_for(r, contrast);
-        if (png) {
-            png_to_host(s, d_png.ptr, r.reserved, image_out, n_out);
-            return APTGPU_OK;
-        }
-        const size_t out_bytes = pj ? static_cast<size_t>(pj->bytes()) : bytes;
-        uint8_t *h = host_alloc<uint8_t>(out_bytes);
-        if (out_bytes && (hipMemcpyAsync(h, pj ? d_grid.ptr : d_img.ptr, out_bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
-                          hipStreamSynchronize(s) != hipSuccess)) {
-            std::free(h);
-            throw Error{ErrorKind::Hip, "D2H copy failed"};
-        }
-        *image_out = h;
-        *n_out = out_bytes;
-        return APTGPU_OK;
-    });
+    if (output != APTGPU_OUTPUT_PIXELS && output != APTGPU_OUTPUT_PNG)
+        throw Error{ErrorKind::Invalid, "unknown output kind"};
+    return output == APTGPU_OUTPUT_PNG;
 }
 
-int plan_process_image(aptgpu_plan *plan, int count, const float *const *d_rows, const size_t *rows_cap, int contrast,
-                       float percent, int rotate, const aptgpu_color_settings *color, int channels, const MapCall *map,
-                       const double *const *positions, const size_t *n_positions, uint8_t *const *d_images, char *err,
-                       size_t err_cap, uint8_t *const *d_png = nullptr, const size_t *png_cap = nullptr,
-                       const aptgpu_orbit_settings *const *orbit = nullptr, const apt::map::Layers *orbit_layers = nullptr,
-                       const std::vector<ProjectCall> *pj = nullptr, uint8_t *const *d_out = nullptr,
-                       const size_t *out_cap = nullptr)
+// map, layers and sat_positions of the PNG entry points: all given or none
+bool png_map_given(const void *map, const void *layers, const void *positions, bool need_positions)
 {
-    if (!plan || count < 0 || !d_rows || !rows_cap || !d_images) return APTGPU_ERR_INVALID;
-    if (map && count > 0 && (!positions || !n_positions)) return APTGPU_ERR_INVALID;
-    return guarded(err, err_cap, [&] {
-        apt::gpu::ColorTune tune{};
-        bool lab = false;
-        // the orbit form: every recording's satellite, time, map settings and Rotate::Orbit outcome, before any launch
-        std::vector<SatCall> sats;
-        std::vector<int> rotates(static_cast<size_t>(count), rotate);
-        if (orbit) {
-            for (int i = 0; i < count; ++i) {
-                sats.push_back(orbit_args(orbit[i]));
-                rotates[static_cast<size_t>(i)] = resolve_rotate(rotate, sats.back());
-                if ((sats.back().draw_map != nullptr) != (sats.front().draw_map != nullptr))
-                    throw Error{ErrorKind::Invalid, "draw_map must be set for every recording of the call or for none"};
-            }
-            // (with a projection the layer set alone asks for the overlay; its settings are the projection's)
-            if (!sats.empty() && (pj ? orbit_layers != nullptr : sats.front().draw_map != nullptr)) {
-                if (!orbit_layers) throw Error{ErrorKind::Invalid, "draw_map needs a layer set"};
-                if (channels != 4) throw Error{ErrorKind::Invalid, "the map overlay needs channels = 4 (RGBA)"};
-            }
-            if (rotate == APTGPU_ROTATE_ORBIT) rotate = APTGPU_ROTATE_NO;  // (resolved per recording above)
-        }
-        const bool colored = color_args(contrast, rotate, color, channels, &tune, &lab);
-        if (static_cast<size_t>(count) > plan->last_slots.size())
-            throw Error{ErrorKind::Invalid, "count exceeds the recordings of the last decode call"};
-        if (contrast == APTGPU_CONTRAST_PERCENT && (percent < 0.f || percent > 1.f))
-            throw Error{ErrorKind::Internal, kBadPercent};
-        const uintptr_t align = channels == 4 ? 15u : 3u;
-        for (int i = 0; i < count; ++i) {
-            if (!d_rows[i] || !d_images[i]) throw Error{ErrorKind::Invalid, "null device pointer"};
-            if (map && !positions[i] && n_positions[i]) throw Error{ErrorKind::Invalid, "null sat_positions"};
-            if (d_png && !d_png[i]) throw Error{ErrorKind::Invalid, "null device pointer (d_png)"};
-            if (pj && !orbit && (!positions || !n_positions || (!positions[i] && n_positions[i])))
-                throw Error{ErrorKind::Invalid, "null sat_positions"};
-            if (pj && (!d_out[i] || (reinterpret_cast<uintptr_t>(d_out[i]) & 3u)))
-                throw Error{ErrorKind::Invalid, "d_out must be non-null and 4-byte aligned"};
-            if (reinterpret_cast<uintptr_t>(d_images[i]) & align)
-                throw Error{ErrorKind::Invalid, channels == 4 ? "d_images must be 16-byte aligned for channels = 4"
-                                                              : "d_images must be 4-byte aligned"};
-        }
-        apt::hip_check(hipSetDevice(plan->device), "hipSetDevice");
-        if (colored) plan->set_palette(color->palette_rgb, lab);
-        for (int i = 0; i < count; ++i)
-            plan->enqueue_image_color(i, d_rows[i], static_cast<uint64_t>(rows_cap[i]) * 2080u, contrast, percent,
-                                      rotates[static_cast<size_t>(i)] == APTGPU_ROTATE_YES, colored ? &tune : nullptr,
-                                      channels, d_images[i], lab);
-        const bool orbit_overlay = !sats.empty() && (pj ? orbit_layers != nullptr : sats.front().draw_map != nullptr);
-        if (orbit_overlay)
-            for (int i = 0; i < count; ++i)
-                plan->enqueue_image_map_sat(i, static_cast<uint64_t>(rows_cap[i]) * 2080u, *orbit_layers,
-                                            sats[static_cast<size_t>(i)].call,
-                                            pj ? (*pj)[static_cast<size_t>(i)].ms : *sats[static_cast<size_t>(i)].draw_map,
-                                            map_colors(*orbit_layers),
-                                            rotates[static_cast<size_t>(i)] == APTGPU_ROTATE_YES, d_images[i]);
-        if (map)
-            for (int i = 0; i < count; ++i)
-                plan->enqueue_image_map(i, static_cast<uint64_t>(rows_cap[i]) * 2080u, *map->layers,
-                                        map_scalars(*map, positions[i], n_positions[i]), map_colors(*map->layers),
-                                        positions[i], n_positions[i], rotate == APTGPU_ROTATE_YES, d_images[i]);
-        if (pj) {
-            for (int i = 0; i < count; ++i) {
-                const ProjectCall &c = (*pj)[static_cast<size_t>(i)];
-                plan->enqueue_image_project(i, static_cast<uint64_t>(rows_cap[i]) * 2080u, channels, d_images[i], c.grid,
-                                            c.flags, c.ms, map != nullptr || orbit_overlay,
-                                            positions ? positions[i] : nullptr, n_positions ? n_positions[i] : 0,
-                                            orbit ? &sats[static_cast<size_t>(i)].call : nullptr, d_out[i], out_cap[i],
-                                            d_png ? d_png[i] : nullptr, d_png ? png_cap[i] : 0);
-            }
-            return APTGPU_OK;
-        }
-        if (d_png)
-            for (int i = 0; i < count; ++i)
-                plan->enqueue_image_png(i, static_cast<uint64_t>(rows_cap[i]) * 2080u, channels, d_images[i], d_png[i],
-                                        png_cap[i]);
-        return APTGPU_OK;
-    });
+    if (!map && !layers && !positions) return false;
+    if (!map || !layers || (!positions && need_positions))
+        throw Error{ErrorKind::Invalid, "map, layers and sat_positions must be given together"};
+    return true;
+}
+
+// The overlay is drawn over every recording of the request, with `map`'s yaw / hscale / vscale where given (a
+// projection's or an orbit's settings are in the recordings already).
+void set_overlay(ImageRequest &q, const aptgpu_map_layers *layers, const aptgpu_map_settings *map)
+{
+    q.overlay = true;
+    q.layers = &layers->layers;
+    if (map)
+        for (Recording &r : q.rec) r.geom = *map;
+}
+
+// The bare checks of a one-shot entry point's buffers.
+bool host_call_ok(const float *signal, size_t n, uint8_t **out, size_t *n_out)
+{
+    return !((!signal && n) || !out || !n_out);
+}
+
+// ... and its outputs before anything is computed (a call that lacks one of them touches neither)
+void clear_outputs(uint8_t **out, size_t *n_out)
+{
+    if (!out || !n_out) return;
+    *out = nullptr;
+    *n_out = 0;
+}
+
+// One host-buffer call under its checked request (one recording): the limits with their status callbacks and host-side
+// errors, Telemetry's step export, the stages on call-local buffers, then the record and the download.  The runner
+// finishes the recording the entry point built: n_positions (the height), the destinations and their capacities.
+int process_image(const aptgpu_context *ctx, const float *signal, size_t n, ImageRequest &q, uint8_t **image_out,
+                  size_t *n_out, aptgpu_image_result *info)
+{
+    Recording &r = q.rec.front();
+    const size_t height = n / 2080;
+    if (height == 0 && n != 0) {
+        if (q.overlay) throw Error{ErrorKind::Internal, "map overlay: the image has no row to draw on"};
+        if (q.png) throw Error{ErrorKind::Invalid, "PNG encoding: the image has no row"};
+        if (q.project) throw Error{ErrorKind::Internal, "reprojection: the image has no row to read"};
+    }
+    r.n_positions = height;  // (host positions: one pair per row)
+    std::vector<uint32_t> packed;  // (outlives the call's stream: ~ImageCall synchronises it)
+    std::shared_ptr<const apt::lab::Tables> lab_tables;  // (likewise)
+    apt::map::Device map_dev;  // (likewise)
+    apt::project::Device project_dev;  // (likewise)
+    ImageCall c(ctx, signal, n);
+    hipStream_t s = c.sc.stream;
+    process_limits(ctx, c, q.contrast, q.percent, info, q.lab);
+    status(ctx, 0.3f, "Generating image");  // noaa_apt.rs:180
+    const size_t bytes = height * 2080 * static_cast<size_t>(q.channels);
+    apt::DeviceBuffer<char> cws, lws, fws, pws;
+    apt::DeviceBuffer<uint8_t> d_img, d_grid, d_png;
+    cws.alloc(apt::gpu::color_ws_bytes());
+    apt::hip_check(apt::gpu::color_ws_init(s, cws.ptr), "hipMemsetAsync");
+    if (q.lab) {
+        lab_tables = apt::lab::tables_for(q.palette);
+        lws.alloc(apt::gpu::lab_ws_bytes());
+        apt::hip_check(hipMemcpyAsync(lws.ptr, lab_tables.get(), sizeof(apt::lab::Tables), hipMemcpyHostToDevice, s),
+                       "hipMemcpyAsync H2D (Lab tables)");
+    } else if (q.colored) {
+        packed.resize(65536);
+        apt::gpu::color_pack_palette(q.palette, packed.data());
+        apt::hip_check(hipMemcpyAsync(apt::gpu::color_ws_palette(cws.ptr), packed.data(),
+                                      packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s),
+                       "hipMemcpyAsync H2D (palette)");
+    }
+    d_img.alloc(bytes + 16);
+    if (q.contrast == APTGPU_CONTRAST_HISTOGRAM_FLOAT) fws.alloc(apt::gpu::eqfloat_ws_bytes());
+    ImageJob j = c.job();
+    if (q.project) {
+        r.out_cap = r.grid_bytes();
+        d_grid.alloc(r.out_cap + 16);
+        if (q.png) r.png_cap = apt::png::bound(r.grid.width, r.grid.height, 4);
+    } else if (q.png) {  // (the scratch sized by the exact stream)
+        j.stream_cap = png_shape(2080, static_cast<uint32_t>(height), q.channels);
+        r.png_cap = apt::png::bound(2080, height, q.channels);
+        pws.alloc(apt::png::ws_bytes(j.stream_cap));
+    }
+    d_png.alloc(r.png_cap);
+    j.color_ws = cws.ptr;
+    j.lab_ws = lws.ptr;
+    j.eqfloat_ws = fws.ptr;
+    j.png_ws = pws.ptr;
+    j.map = &map_dev;
+    j.project = &project_dev;
+    r.d_image = d_img.ptr;
+    r.d_out = d_grid.ptr;
+    r.d_png = d_png.ptr;
+    if (q.overlay) status(ctx, 0.5f, "Drawing map");           // noaa_apt.rs:205
+    if (r.rotate) status(ctx, 0.90f, "Rotating output image");  // noaa_apt.rs:229
+    apt::enqueue_image_color(nullptr, q, r, j);
+    apt::enqueue_image_outputs(nullptr, q, &j, 1);
+    apt::hip_check(hipGetLastError(), "kernel launch (image stage)");
+    const ImageResult res = c.info();
+    copy_out(info, res);
+    throw_for(res, q.contrast);
+    if (q.png)
+        to_host(s, d_png.ptr, res.reserved, image_out, n_out);
+    else if (q.project)
+        to_host(s, d_grid.ptr, r.out_cap, image_out, n_out);
+    else
+        to_host(s, d_img.ptr, bytes, image_out, n_out);
+    return APTGPU_OK;
+}
+
+// The bare checks every plan form shares.
+bool plan_call_ok(const aptgpu_plan *plan, int count, const float *const *d_rows, const size_t *rows_cap,
+                  uint8_t *const *d_images)
+{
+    return plan && count >= 0 && d_rows && rows_cap && d_images;
+}
+
+// The fillers of a plan call's recordings.  Each writes its own fields of the q.rec the entry point has sized and reads
+// nothing of the request, so their order among themselves does not matter.
+// `rotate` (the orbit forms resolve their own after), the image destinations and, when d_png is given, the PNG files':
+void plan_recordings(ImageRequest &q, int rotate, uint8_t *const *d_images, uint8_t *const *d_png, const size_t *png_cap)
+{
+    q.png = d_png != nullptr;
+    for (size_t i = 0; i < q.rec.size(); ++i) {
+        q.rec[i].rotate = rotate == APTGPU_ROTATE_YES;
+        q.rec[i].d_image = d_images[i];
+        q.rec[i].d_png = q.png ? d_png[i] : nullptr;
+        q.rec[i].png_cap = q.png ? png_cap[i] : 0;
+    }
+}
+
+// their tracks on the host:
+void plan_positions(ImageRequest &q, const double *const *positions, const size_t *n_positions)
+{
+    for (size_t i = 0; i < q.rec.size(); ++i) {
+        q.rec[i].track = Track::Positions;
+        q.rec[i].positions = positions[i];
+        q.rec[i].n_positions = n_positions[i];
+    }
+}
+
+// or every recording's satellite, time and Rotate::Orbit outcome (the orbit forms), before any launch.  Returns the
+// first recording's draw_map: set for every recording of the call or for none.
+const aptgpu_map_settings *plan_orbits(ImageRequest &q, const aptgpu_orbit_settings *const *orbit, int rotate)
+{
+    const aptgpu_map_settings *first = nullptr;
+    for (size_t i = 0; i < q.rec.size(); ++i) {
+        const SatCall c = orbit_args(orbit[i]);
+        Recording &r = q.rec[i];
+        r.track = Track::Sat;
+        r.sat = c.call;
+        r.rotate = resolve_rotate(rotate, c) == APTGPU_ROTATE_YES;
+        if (i == 0) first = c.draw_map;
+        if ((c.draw_map != nullptr) != (first != nullptr))
+            throw Error{ErrorKind::Invalid, "draw_map must be set for every recording of the call or for none"};
+    }
+    return first;
+}
+
+// The rest of a plan call under its checked request: the checks that need the live plan, then the stages.
+int plan_process_image(aptgpu_plan *plan, int count, const float *const *d_rows, const size_t *rows_cap,
+                       const ImageRequest &q)
+{
+    if (static_cast<size_t>(count) > plan->last_slots.size())
+        throw Error{ErrorKind::Invalid, "count exceeds the recordings of the last decode call"};
+    if (q.contrast == APTGPU_CONTRAST_PERCENT && (q.percent < 0.f || q.percent > 1.f))
+        throw Error{ErrorKind::Internal, kBadPercent};
+    const uintptr_t align = q.channels == 4 ? 15u : 3u;
+    for (int i = 0; i < count; ++i) {
+        const Recording &r = q.rec[static_cast<size_t>(i)];
+        const bool no_positions = r.track == Track::Positions && !r.positions && r.n_positions;
+        if (!d_rows[i] || !r.d_image) throw Error{ErrorKind::Invalid, "null device pointer"};
+        if (q.overlay && no_positions) throw Error{ErrorKind::Invalid, "null sat_positions"};
+        if (q.png && !r.d_png) throw Error{ErrorKind::Invalid, "null device pointer (d_png)"};
+        if (q.project && no_positions) throw Error{ErrorKind::Invalid, "null sat_positions"};
+        if (q.project && (!r.d_out || (reinterpret_cast<uintptr_t>(r.d_out) & 3u)))
+            throw Error{ErrorKind::Invalid, "d_out must be non-null and 4-byte aligned"};
+        if (reinterpret_cast<uintptr_t>(r.d_image) & align)
+            throw Error{ErrorKind::Invalid, q.channels == 4 ? "d_images must be 16-byte aligned for channels = 4"
+                                                            : "d_images must be 4-byte aligned"};
+    }
+    apt::hip_check(hipSetDevice(plan->device), "hipSetDevice");
+    if (q.colored) plan->set_palette(q.palette, q.lab);
+    plan->enqueue_images(q, count, d_rows, rows_cap);
+    return APTGPU_OK;
 }
 
 }  // namespace
@@ -637,13 +613,8 @@ int aptgpu_map_signal_u8(const aptgpu_context *ctx, const float *signal, size_t 
         d_img.alloc(n + 16);
         apt::gpu::image_set_limits(c.sc.stream, c.ws.ptr, n, low, high);
         apt::gpu::image_map_u8(c.sc.stream, c.d_x.ptr, nullptr, n, n, c.ws.ptr, false, d_img.ptr, c.d_info.ptr);
-        uint8_t *h = host_alloc<uint8_t>(n);
-        if (n && (hipMemcpyAsync(h, d_img.ptr, n, hipMemcpyDeviceToHost, c.sc.stream) != hipSuccess ||
-                  hipStreamSynchronize(c.sc.stream) != hipSuccess)) {
-            std::free(h);
-            throw Error{ErrorKind::Hip, "D2H copy failed"};
-        }
-        *out = h;
+        size_t n_out = 0;
+        to_host(c.sc.stream, d_img.ptr, n, out, &n_out);
         return APTGPU_OK;
     });
 }
@@ -671,14 +642,11 @@ int aptgpu_process_gray(const aptgpu_context *ctx, const float *signal, size_t n
     *image_out = nullptr;
     *n_out = 0;
     return guarded(err, err_cap, [&] {
-        if (contrast != APTGPU_CONTRAST_TELEMETRY && contrast != APTGPU_CONTRAST_PERCENT &&
-            contrast != APTGPU_CONTRAST_MINMAX)
-            throw Error{ErrorKind::Invalid, "unknown contrast adjustment"};
-        if (rotate != APTGPU_ROTATE_NO && rotate != APTGPU_ROTATE_YES)
-            throw Error{ErrorKind::Unsupported, "Rotate::Orbit needs the satellite and the time: aptgpu_orbit_settings, the *_orbit entry points"};
+        contrast_arg(contrast, APTGPU_CONTRAST_MINMAX);
+        rotate_arg(rotate);
         ImageCall c(ctx, signal, n);
         hipStream_t s = c.sc.stream;
-        process_limits(ctx, c, contrast, percent, info);
+        process_limits(ctx, c, contrast, percent, info, false);
         status(ctx, 0.3f, "Generating image");  // noaa_apt.rs:180
         apt::DeviceBuffer<uint8_t> d_img;
         d_img.alloc(n + 16);
@@ -688,14 +656,7 @@ int aptgpu_process_gray(const aptgpu_context *ctx, const float *signal, size_t n
         const ImageResult r = c.info();
         copy_out(info, r);
         throw_for(r, contrast);
-        uint8_t *h = host_alloc<uint8_t>(n);
-        if (n && (hipMemcpyAsync(h, d_img.ptr, n, hipMemcpyDeviceToHost, s) != hipSuccess ||
-                  hipStreamSynchronize(s) != hipSuccess)) {
-            std::free(h);
-            throw Error{ErrorKind::Hip, "D2H copy failed"};
-        }
-        *image_out = h;
-        *n_out = n;
+        to_host(s, d_img.ptr, n, image_out, n_out);
         return APTGPU_OK;
     });
 }
@@ -708,10 +669,8 @@ int aptgpu_plan_process_device(aptgpu_plan *plan, int count, const float *const 
     return guarded(err, err_cap, [&] {
         if (static_cast<size_t>(count) > plan->last_slots.size())
             throw Error{ErrorKind::Invalid, "count exceeds the recordings of the last decode call"};
-        if (contrast < APTGPU_CONTRAST_TELEMETRY || contrast > APTGPU_CONTRAST_MINMAX)
-            throw Error{ErrorKind::Invalid, "unknown contrast adjustment"};
-        if (rotate != APTGPU_ROTATE_NO && rotate != APTGPU_ROTATE_YES)
-            throw Error{ErrorKind::Unsupported, "Rotate::Orbit needs the satellite and the time: aptgpu_orbit_settings, the *_orbit entry points"};
+        contrast_arg(contrast, APTGPU_CONTRAST_MINMAX);
+        rotate_arg(rotate);
         if (contrast == APTGPU_CONTRAST_PERCENT && (percent < 0.f || percent > 1.f))
             throw Error{ErrorKind::Internal, kBadPercent};
         apt::hip_check(hipSetDevice(plan->device), "hipSetDevice");
@@ -728,8 +687,14 @@ int aptgpu_process_image(const aptgpu_context *ctx, const float *signal, size_t 
                          int rotate, const aptgpu_color_settings *color, int channels, uint8_t **image_out,
                          size_t *n_out, aptgpu_image_result *info, char *err, size_t err_cap)
 {
-    return process_image(ctx, signal, n, contrast, percent, rotate, color, channels, nullptr, nullptr, image_out, n_out,
-                         info, err, err_cap);
+    if (!host_call_ok(signal, n, image_out, n_out)) return APTGPU_ERR_INVALID;
+    clear_outputs(image_out, n_out);
+    return guarded(err, err_cap, [&] {
+        ImageRequest q(1);
+        color_args(q, contrast, percent, rotate, color, channels);
+        q.rec[0].rotate = rotate == APTGPU_ROTATE_YES;
+        return process_image(ctx, signal, n, q, image_out, n_out, info);
+    });
 }
 
 int aptgpu_plan_process_device_image(aptgpu_plan *plan, int count, const float *const *d_rows,
@@ -737,8 +702,14 @@ int aptgpu_plan_process_device_image(aptgpu_plan *plan, int count, const float *
                                      const aptgpu_color_settings *color, int channels,
                                      uint8_t *const *d_images, char *err, size_t err_cap)
 {
-    return plan_process_image(plan, count, d_rows, rows_cap, contrast, percent, rotate, color, channels, nullptr,
-                              nullptr, nullptr, d_images, err, err_cap);
+    if (!plan_call_ok(plan, count, d_rows, rows_cap, d_images)) return APTGPU_ERR_INVALID;
+    return guarded(err, err_cap, [&] {
+        ImageRequest q;
+        color_args(q, contrast, percent, rotate, color, channels);
+        q.rec.resize(static_cast<size_t>(count));
+        plan_recordings(q, rotate, d_images, nullptr, nullptr);
+        return plan_process_image(plan, count, d_rows, rows_cap, q);
+    });
 }
 
 int aptgpu_process_image_map(const aptgpu_context *ctx, const float *signal, size_t n, int contrast,
@@ -748,17 +719,18 @@ int aptgpu_process_image_map(const aptgpu_context *ctx, const float *signal, siz
                              aptgpu_image_result *info, char *err, size_t err_cap)
 {
     if (!sat_positions && n >= 2080) return APTGPU_ERR_INVALID;
-    int rc = guarded(err, err_cap, [&] {
-        apt::gpu::ColorTune tune{};
-        bool lab = false;
-        color_args(contrast, rotate, color, channels, &tune, &lab);
+    clear_outputs(image_out, n_out);
+    return guarded(err, err_cap, [&] {
+        ImageRequest q(1);
+        color_args(q, contrast, percent, rotate, color, channels);
         map_args(channels, map, layers);
-        return APTGPU_OK;
+        if (!host_call_ok(signal, n, image_out, n_out)) return APTGPU_ERR_INVALID;
+        q.rec[0].rotate = rotate == APTGPU_ROTATE_YES;
+        q.rec[0].track = Track::Positions;
+        q.rec[0].positions = sat_positions;
+        set_overlay(q, layers, map);
+        return process_image(ctx, signal, n, q, image_out, n_out, info);
     });
-    if (rc != APTGPU_OK) return rc;
-    const MapCall m{map, &layers->layers};
-    return process_image(ctx, signal, n, contrast, percent, rotate, color, channels, &m, sat_positions, image_out,
-                         n_out, info, err, err_cap);
 }
 
 int aptgpu_plan_process_device_image_map(aptgpu_plan *plan, int count, const float *const *d_rows,
@@ -768,17 +740,18 @@ int aptgpu_plan_process_device_image_map(aptgpu_plan *plan, int count, const flo
                                          const double *const *sat_positions, const size_t *n_positions,
                                          uint8_t *const *d_images, char *err, size_t err_cap)
 {
-    int rc = guarded(err, err_cap, [&] {
-        apt::gpu::ColorTune tune{};
-        bool lab = false;
-        color_args(contrast, rotate, color, channels, &tune, &lab);
+    return guarded(err, err_cap, [&] {
+        ImageRequest q;
+        color_args(q, contrast, percent, rotate, color, channels);
         map_args(channels, map, layers);
-        return APTGPU_OK;
+        if (!plan_call_ok(plan, count, d_rows, rows_cap, d_images)) return APTGPU_ERR_INVALID;
+        if (count > 0 && (!sat_positions || !n_positions)) return APTGPU_ERR_INVALID;
+        q.rec.resize(static_cast<size_t>(count));
+        plan_recordings(q, rotate, d_images, nullptr, nullptr);
+        plan_positions(q, sat_positions, n_positions);
+        set_overlay(q, layers, map);
+        return plan_process_image(plan, count, d_rows, rows_cap, q);
     });
-    if (rc != APTGPU_OK) return rc;
-    const MapCall m{map, &layers->layers};
-    return plan_process_image(plan, count, d_rows, rows_cap, contrast, percent, rotate, color, channels, &m,
-                              sat_positions, n_positions, d_images, err, err_cap);
 }
 
 size_t aptgpu_png_bound(uint32_t width, uint32_t height, int channels)
@@ -818,18 +791,9 @@ int aptgpu_encode_png(const aptgpu_context *ctx, const uint8_t *image, uint32_t 
         apt::hip_check(hipMemcpyAsync(&len, d_len.ptr, sizeof len, hipMemcpyDeviceToHost, s), "hipMemcpyAsync D2H");
         apt::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
         if (len == 0 || len > cap) throw Error{ErrorKind::Internal, "PNG encoder: the file exceeds aptgpu_png_bound"};
-        png_to_host(s, d_png.ptr, static_cast<size_t>(len), png_out, n_out);
+        to_host(s, d_png.ptr, static_cast<size_t>(len), png_out, n_out);
         return APTGPU_OK;
     });
-}
-
-// map, layers and sat_positions of the PNG entry points: all given or none
-bool png_map_given(const void *map, const void *layers, const void *positions, bool need_positions)
-{
-    if (!map && !layers && !positions) return false;
-    if (!map || !layers || (!positions && need_positions))
-        throw Error{ErrorKind::Invalid, "map, layers and sat_positions must be given together"};
-    return true;
 }
 
 int aptgpu_process_image_png(const aptgpu_context *ctx, const float *signal, size_t n, int contrast, float percent,
@@ -838,20 +802,23 @@ int aptgpu_process_image_png(const aptgpu_context *ctx, const float *signal, siz
                              const double *sat_positions, const aptgpu_png_settings *png, uint8_t **png_out,
                              size_t *n_out, aptgpu_image_result *info, char *err, size_t err_cap)
 {
-    bool with_map = false;
-    int rc = guarded(err, err_cap, [&] {
-        apt::gpu::ColorTune tune{};
-        bool lab = false;
-        color_args(contrast, rotate, color, channels, &tune, &lab);
+    clear_outputs(png_out, n_out);
+    return guarded(err, err_cap, [&] {
+        ImageRequest q(1);
+        color_args(q, contrast, percent, rotate, color, channels);
         png_args(png);
-        with_map = png_map_given(map, layers, sat_positions, n >= 2080);
+        const bool with_map = png_map_given(map, layers, sat_positions, n >= 2080);
         if (with_map) map_args(channels, map, layers);
-        return APTGPU_OK;
+        if (!host_call_ok(signal, n, png_out, n_out)) return APTGPU_ERR_INVALID;
+        q.png = true;
+        q.rec[0].rotate = rotate == APTGPU_ROTATE_YES;
+        if (with_map) {
+            q.rec[0].track = Track::Positions;
+            q.rec[0].positions = sat_positions;
+            set_overlay(q, layers, map);
+        }
+        return process_image(ctx, signal, n, q, png_out, n_out, info);
     });
-    if (rc != APTGPU_OK) return rc;
-    MapCall m{map, with_map ? &layers->layers : nullptr};
-    return process_image(ctx, signal, n, contrast, percent, rotate, color, channels, with_map ? &m : nullptr,
-                         sat_positions, png_out, n_out, info, err, err_cap, true);
 }
 
 int aptgpu_plan_process_device_image_png(aptgpu_plan *plan, int count, const float *const *d_rows,
@@ -863,20 +830,22 @@ int aptgpu_plan_process_device_image_png(aptgpu_plan *plan, int count, const flo
                                          uint8_t *const *d_png, const size_t *png_cap, char *err, size_t err_cap)
 {
     if (!d_png || !png_cap) return APTGPU_ERR_INVALID;
-    bool with_map = false;
-    int rc = guarded(err, err_cap, [&] {
-        apt::gpu::ColorTune tune{};
-        bool lab = false;
-        color_args(contrast, rotate, color, channels, &tune, &lab);
+    return guarded(err, err_cap, [&] {
+        ImageRequest q;
+        color_args(q, contrast, percent, rotate, color, channels);
         png_args(png);
-        with_map = png_map_given(map, layers, sat_positions, true);
+        const bool with_map = png_map_given(map, layers, sat_positions, true);
         if (with_map) map_args(channels, map, layers);
-        return APTGPU_OK;
+        if (!plan_call_ok(plan, count, d_rows, rows_cap, d_images)) return APTGPU_ERR_INVALID;
+        if (with_map && count > 0 && !n_positions) return APTGPU_ERR_INVALID;
+        q.rec.resize(static_cast<size_t>(count));
+        plan_recordings(q, rotate, d_images, d_png, png_cap);
+        if (with_map) {
+            plan_positions(q, sat_positions, n_positions);
+            set_overlay(q, layers, map);
+        }
+        return plan_process_image(plan, count, d_rows, rows_cap, q);
     });
-    if (rc != APTGPU_OK) return rc;
-    MapCall m{map, with_map ? &layers->layers : nullptr};
-    return plan_process_image(plan, count, d_rows, rows_cap, contrast, percent, rotate, color, channels,
-                              with_map ? &m : nullptr, sat_positions, n_positions, d_images, err, err_cap, d_png, png_cap);
 }
 
 int aptgpu_sat_track_host(const aptgpu_orbit_settings *orbit, uint32_t height, double *latlon_out, char *err,
@@ -932,20 +901,23 @@ int aptgpu_process_image_orbit(const aptgpu_context *ctx, const float *signal, s
                                const aptgpu_png_settings *png, uint8_t **out, size_t *n_out,
                                aptgpu_image_result *info, char *err, size_t err_cap)
 {
-    SatCall c{};
-    const int rc = guarded(err, err_cap, [&] {
-        if (output != APTGPU_OUTPUT_PIXELS && output != APTGPU_OUTPUT_PNG)
-            throw Error{ErrorKind::Invalid, "unknown output kind"};
-        c = orbit_args(orbit);
+    clear_outputs(out, n_out);
+    return guarded(err, err_cap, [&] {
+        ImageRequest q(1);
+        Recording &r = q.rec[0];
+        q.png = output_arg(output);
+        const SatCall c = orbit_args(orbit);
         rotate = resolve_rotate(rotate, c);
-        if (output == APTGPU_OUTPUT_PNG) png_args(png);
+        if (q.png) png_args(png);
         if (c.draw_map) map_args(channels, c.draw_map, layers);
-        return APTGPU_OK;
+        if (!host_call_ok(signal, n, out, n_out)) return APTGPU_ERR_INVALID;
+        color_args(q, contrast, percent, rotate, color, channels);
+        r.rotate = rotate == APTGPU_ROTATE_YES;
+        r.track = Track::Sat;
+        r.sat = c.call;
+        if (c.draw_map) set_overlay(q, layers, c.draw_map);
+        return process_image(ctx, signal, n, q, out, n_out, info);
     });
-    if (rc != APTGPU_OK) return rc;
-    MapCall m{c.draw_map, c.draw_map ? &layers->layers : nullptr};
-    return process_image(ctx, signal, n, contrast, percent, rotate, color, channels, c.draw_map ? &m : nullptr,
-                         nullptr, out, n_out, info, err, err_cap, output == APTGPU_OUTPUT_PNG, &c.call);
 }
 
 int aptgpu_plan_process_device_image_orbit(aptgpu_plan *plan, int count, const float *const *d_rows,
@@ -956,16 +928,22 @@ int aptgpu_plan_process_device_image_orbit(aptgpu_plan *plan, int count, const f
                                            uint8_t *const *d_png, const size_t *png_cap, char *err, size_t err_cap)
 {
     if (!orbit || (d_png && !png_cap)) return APTGPU_ERR_INVALID;
-    if (d_png) {
-        const int rc = guarded(err, err_cap, [&] {
-            png_args(png);
-            return APTGPU_OK;
-        });
-        if (rc != APTGPU_OK) return rc;
-    }
-    return plan_process_image(plan, count, d_rows, rows_cap, contrast, percent, rotate, color, channels, nullptr,
-                              nullptr, nullptr, d_images, err, err_cap, d_png, png_cap, orbit,
-                              layers ? &layers->layers : nullptr);
+    return guarded(err, err_cap, [&] {
+        ImageRequest q;
+        if (d_png) png_args(png);
+        if (!plan_call_ok(plan, count, d_rows, rows_cap, d_images)) return APTGPU_ERR_INVALID;
+        q.rec.resize(static_cast<size_t>(count));
+        plan_recordings(q, rotate, d_images, d_png, png_cap);
+        if (plan_orbits(q, orbit, rotate)) {
+            if (!layers) throw Error{ErrorKind::Invalid, "draw_map needs a layer set"};
+            if (channels != 4) throw Error{ErrorKind::Invalid, "the map overlay needs channels = 4 (RGBA)"};
+            for (int i = 0; i < count; ++i) q.rec[static_cast<size_t>(i)].geom = *orbit[i]->draw_map;
+            set_overlay(q, layers, nullptr);
+        }
+        // (Rotate::Orbit is resolved per recording above)
+        color_args(q, contrast, percent, rotate == APTGPU_ROTATE_ORBIT ? APTGPU_ROTATE_NO : rotate, color, channels);
+        return plan_process_image(plan, count, d_rows, rows_cap, q);
+    });
 }
 
 int aptgpu_projection_fit(const double *track, size_t count, double hscale, int kind, double step_deg,
@@ -988,14 +966,20 @@ int aptgpu_project_image(const aptgpu_context *ctx, const uint8_t *image, uint32
     *n_out = 0;
     return guarded(err, err_cap, [&] {
         // (every check before the device is touched)
-        if (output != APTGPU_OUTPUT_PIXELS && output != APTGPU_OUTPUT_PNG)
-            throw Error{ErrorKind::Invalid, "unknown output kind"};
-        if (output == APTGPU_OUTPUT_PNG) png_args(png);
-        if (channels != 1 && channels != 4) throw Error{ErrorKind::Invalid, "channels must be 1 (gray) or 4 (RGBA)"};
-        const ProjectCall pj = project_args(proj, map);
+        ImageRequest q(1);
+        Recording &r = q.rec[0];
+        q.png = output_arg(output);
+        if (q.png) png_args(png);
+        channels_arg(channels);
+        project_args(r, proj, map);
         if (!image || height == 0) throw Error{ErrorKind::Invalid, "reprojection: the image has no row to read"};
         if (!sat_positions) throw Error{ErrorKind::Invalid, "null sat_positions"};
-        if (output == APTGPU_OUTPUT_PNG) png_shape(pj.grid.width, pj.grid.height, 4);
+        if (q.png) png_shape(r.grid.width, r.grid.height, 4);
+        q.project = true;
+        q.channels = channels;
+        r.track = Track::Positions;
+        r.positions = sat_positions;
+        r.n_positions = n_positions;
         const size_t bytes = static_cast<size_t>(height) * 2080u * static_cast<size_t>(channels);
         apt::map::Device map_dev;  // (outlive the call's stream: ~Scratch synchronises it)
         apt::project::Device project_dev;
@@ -1007,34 +991,32 @@ int aptgpu_project_image(const aptgpu_context *ctx, const uint8_t *image, uint32
         hipStream_t s = sc.stream;
         apt::DeviceBuffer<uint8_t> d_img, d_grid, d_png;
         apt::DeviceBuffer<ImageResult> d_info;
+        r.out_cap = r.grid_bytes();
+        if (q.png) r.png_cap = apt::png::bound(r.grid.width, r.grid.height, 4);
         d_img.alloc(bytes + 16);
-        d_grid.alloc(pj.bytes() + 16);
+        d_grid.alloc(r.out_cap + 16);
+        d_png.alloc(r.png_cap);
         d_info.alloc(1);
+        r.d_image = d_img.ptr;
+        r.d_out = d_grid.ptr;
+        r.d_png = d_png.ptr;
+        // the finished image as a job behind its colour stage, with a hand-made record
+        ImageJob j{};
+        j.stream = s;
+        j.cap = rec.n_px;
+        j.info = d_info.ptr;
+        j.map = &map_dev;
+        j.project = &project_dev;
         apt::hip_check(hipMemcpyAsync(d_img.ptr, image, bytes, hipMemcpyHostToDevice, s), "hipMemcpyAsync H2D");
         apt::hip_check(hipMemcpyAsync(d_info.ptr, &rec, sizeof rec, hipMemcpyHostToDevice, s), "hipMemcpyAsync H2D");
-        map_dev.prepare_track(s, height);
-        map_dev.upload_track(s, sat_positions, n_positions);
-        const apt::map::Scalars msc = apt::map::scalars(sat_positions, n_positions, pj.ms.yaw, pj.ms.hscale, pj.ms.vscale);
-        apt::map::image_map_track(s, map_dev, msc,
-                                  n_positions < 0xffffffffu ? static_cast<uint32_t>(n_positions) : 0xffffffffu, d_info.ptr);
-        project_dev.upload_flags(s, pj.flags);
-        apt::project::image_project(s, project_dev, map_dev, &msc, pj.grid, d_img.ptr, channels, d_grid.ptr, pj.bytes(),
-                                    d_info.ptr);
-        if (output == APTGPU_OUTPUT_PNG) {
-            const uint64_t cap = apt::png::bound(pj.grid.width, pj.grid.height, 4);
-            d_png.alloc(cap);
-            apt::project::image_project_png(s, project_dev, pj.grid, d_grid.ptr, d_png.ptr, cap, d_info.ptr);
-        }
+        apt::enqueue_image_outputs(nullptr, q, &j, 1);
         apt::hip_check(hipGetLastError(), "kernel launch (reprojection)");
-        ImageResult r{};
-        apt::hip_check(hipMemcpyAsync(&r, d_info.ptr, sizeof r, hipMemcpyDeviceToHost, s), "hipMemcpyAsync D2H");
-        apt::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
-        throw_for(r, APTGPU_CONTRAST_MINMAX);
-        if (output == APTGPU_OUTPUT_PNG) {
-            png_to_host(s, d_png.ptr, r.reserved, out, n_out);
-            return APTGPU_OK;
-        }
-        png_to_host(s, d_grid.ptr, static_cast<size_t>(pj.bytes()), out, n_out);
+        const ImageResult res = ImageCall::read(s, d_info.ptr);
+        throw_for(res, APTGPU_CONTRAST_MINMAX);
+        if (q.png)
+            to_host(s, d_png.ptr, res.reserved, out, n_out);
+        else
+            to_host(s, d_grid.ptr, r.out_cap, out, n_out);
         return APTGPU_OK;
     });
 }
@@ -1046,28 +1028,29 @@ int aptgpu_process_image_project(const aptgpu_context *ctx, const float *signal,
                                  const aptgpu_projection_settings *proj, int output, const aptgpu_png_settings *png,
                                  uint8_t **out, size_t *n_out, aptgpu_image_result *info, char *err, size_t err_cap)
 {
-    SatCall c{};
-    ProjectCall pj{};
-    const int rc = guarded(err, err_cap, [&] {
-        if (output != APTGPU_OUTPUT_PIXELS && output != APTGPU_OUTPUT_PNG)
-            throw Error{ErrorKind::Invalid, "unknown output kind"};
+    clear_outputs(out, n_out);
+    return guarded(err, err_cap, [&] {
+        ImageRequest q(1);
+        Recording &r = q.rec[0];
+        q.png = output_arg(output);
         project_rotate(rotate);
         if ((sat_positions != nullptr) == (orbit != nullptr))
             throw Error{ErrorKind::Invalid, "a projection needs exactly one of sat_positions and aptgpu_orbit_settings"};
-        apt::gpu::ColorTune tune{};
-        bool lab = false;
-        color_args(contrast, rotate, color, channels, &tune, &lab);
+        color_args(q, contrast, percent, rotate, color, channels);
+        SatCall c{};
         if (orbit) c = orbit_args(orbit);
-        if (output == APTGPU_OUTPUT_PNG) png_args(png);
-        pj = project_args(proj, map ? map : c.draw_map);
-        if (layers) map_args(channels, &pj.ms, layers);
-        if (output == APTGPU_OUTPUT_PNG) png_shape(pj.grid.width, pj.grid.height, 4);
-        return APTGPU_OK;
+        if (q.png) png_args(png);
+        project_args(r, proj, map ? map : c.draw_map);
+        if (layers) map_args(channels, &r.geom, layers);
+        if (q.png) png_shape(r.grid.width, r.grid.height, 4);
+        if (!host_call_ok(signal, n, out, n_out)) return APTGPU_ERR_INVALID;
+        q.project = true;
+        r.track = orbit ? Track::Sat : Track::Positions;
+        r.sat = c.call;
+        r.positions = sat_positions;
+        if (layers) set_overlay(q, layers, nullptr);
+        return process_image(ctx, signal, n, q, out, n_out, info);
     });
-    if (rc != APTGPU_OK) return rc;
-    MapCall m{&pj.ms, layers ? &layers->layers : nullptr};
-    return process_image(ctx, signal, n, contrast, percent, rotate, color, channels, layers ? &m : nullptr, sat_positions,
-                         out, n_out, info, err, err_cap, output == APTGPU_OUTPUT_PNG, orbit ? &c.call : nullptr, &pj);
 }
 
 int aptgpu_plan_process_device_image_project(aptgpu_plan *plan, int count, const float *const *d_rows,
@@ -1081,32 +1064,33 @@ int aptgpu_plan_process_device_image_project(aptgpu_plan *plan, int count, const
                                              uint8_t *const *d_png, const size_t *png_cap, char *err, size_t err_cap)
 {
     if (count < 0 || (count > 0 && (!proj || !d_out || !out_cap)) || (d_png && !png_cap)) return APTGPU_ERR_INVALID;
-    std::vector<ProjectCall> pj;
-    const int rc = guarded(err, err_cap, [&] {
+    return guarded(err, err_cap, [&] {
+        ImageRequest q;
         project_rotate(rotate);
         if ((sat_positions != nullptr) == (orbit != nullptr) || (sat_positions && !n_positions))
             throw Error{ErrorKind::Invalid, "a projection needs exactly one of sat_positions and aptgpu_orbit_settings"};
-        apt::gpu::ColorTune tune{};
-        bool lab = false;
-        color_args(contrast, rotate, color, channels, &tune, &lab);
+        color_args(q, contrast, percent, rotate, color, channels);
         if (d_png) png_args(png);
+        q.project = true;
+        q.rec.resize(static_cast<size_t>(count));
         for (int i = 0; i < count; ++i) {
+            Recording &r = q.rec[static_cast<size_t>(i)];
             if (orbit && !orbit[i]) throw Error{ErrorKind::Invalid, "aptgpu_orbit_settings: struct_size not set"};
-            pj.push_back(project_args(proj + i, map ? map : (orbit ? orbit[i]->draw_map : nullptr)));
-            if (d_png) png_shape(pj.back().grid.width, pj.back().grid.height, 4);
+            project_args(r, proj + i, map ? map : (orbit ? orbit[i]->draw_map : nullptr));
+            if (d_png) png_shape(r.grid.width, r.grid.height, 4);
+            r.d_out = d_out[i];
+            r.out_cap = out_cap[i];
         }
-        if (layers && count > 0) map_args(channels, &pj.front().ms, layers);
-        return APTGPU_OK;
+        if (layers && count > 0) map_args(channels, &q.rec[0].geom, layers);
+        if (!plan_call_ok(plan, count, d_rows, rows_cap, d_images)) return APTGPU_ERR_INVALID;
+        plan_recordings(q, rotate, d_images, d_png, png_cap);
+        if (orbit)
+            plan_orbits(q, orbit, rotate);
+        else
+            plan_positions(q, sat_positions, n_positions);
+        if (layers && count > 0) set_overlay(q, layers, nullptr);
+        return plan_process_image(plan, count, d_rows, rows_cap, q);
     });
-    if (rc != APTGPU_OK) return rc;
-    if (orbit)
-        return plan_process_image(plan, count, d_rows, rows_cap, contrast, percent, rotate, color, channels, nullptr,
-                                  nullptr, nullptr, d_images, err, err_cap, d_png, png_cap, orbit,
-                                  layers ? &layers->layers : nullptr, &pj, d_out, out_cap);
-    MapCall m{count > 0 ? &pj.front().ms : nullptr, layers ? &layers->layers : nullptr};
-    return plan_process_image(plan, count, d_rows, rows_cap, contrast, percent, rotate, color, channels,
-                              layers && count > 0 ? &m : nullptr, sat_positions, n_positions, d_images, err, err_cap, d_png,
-                              png_cap, nullptr, nullptr, &pj, d_out, out_cap);
 }
 
 int aptgpu_map_layers_create(aptgpu_map_layers **out)

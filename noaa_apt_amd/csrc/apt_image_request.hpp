@@ -1,0 +1,78 @@
+// apt_image_request.hpp — one checked image call (ImageRequest), where a recording's stages run (ImageJob), and the
+// one sequence of launches both the one-shot entry points and the plan go through (apt_plan.hip).
+#pragma once
+
+#include <vector>
+
+#include "apt_kernels_color.hpp"
+#include "apt_kernels_map.hpp"
+#include "apt_kernels_project.hpp"
+#include "apt_kernels_track.hpp"
+
+struct aptgpu_plan;
+
+namespace apt {
+
+// What the aptgpu_process_image* / aptgpu_plan_process_device_image* entry points ask for, after their argument
+// checks.  Which stages run follows from the flags here and nowhere else.  The entry points fill it in their own
+// check order: color_args writes the per-call block down to `palette` and nothing else; everything per recording is
+// written after `rec` has its final size.
+struct ImageRequest {
+    int contrast = APTGPU_CONTRAST_MINMAX;
+    float percent = 0.f;
+    int channels = 1;
+    bool colored = false, lab = false;  // false colour; Histogram with it (equalised in CIE Lab)
+    apt::gpu::ColorTune tune{};
+    const uint8_t *palette = nullptr;
+    // The overlay is drawn: with a projection a layer set is given (its settings are the projection's), without one
+    // the map settings are (draw_map in the orbit forms).  `layers` is then the set.
+    bool overlay = false;
+    const apt::map::Layers *layers = nullptr;
+    bool project = false;  // the image goes through the reprojection onto every recording's grid
+    bool png = false;      // the output is the PNG file of the image (of the grid with a projection)
+    enum class Track { None, Positions, Sat };
+    struct Recording {
+        bool rotate = false;  // (Rotate::Orbit resolved)
+        Track track = Track::None;
+        const double *positions = nullptr;  // Track::Positions: n_positions (lat, lon) pairs on the host
+        size_t n_positions = 0;
+        apt::sat::TrackCall sat{};          // Track::Sat: the track is computed on the device
+        aptgpu_map_settings geom{sizeof(aptgpu_map_settings), 0, 0., 1., 1.};  // yaw / hscale / vscale
+        apt::project::Grid grid{};          // with `project`, and its graticule
+        std::vector<uint8_t> flags;
+        uint64_t grid_bytes() const { return static_cast<uint64_t>(grid.width) * grid.height * 4u; }
+        // the destinations in HBM: the caller's for a plan, call-local buffers for a one-shot call
+        uint8_t *d_image = nullptr, *d_png = nullptr, *d_out = nullptr;
+        size_t png_cap = 0, out_cap = 0;
+    };
+    std::vector<Recording> rec;
+    explicit ImageRequest(size_t recordings = 0) : rec(recordings) {}
+};
+
+// Where one recording's stages run: a plan slot, or the buffers of a one-shot call.  The launches read
+// (res, n, cap) as given: (null, n, n) for a one-shot call, (the decode's record, 0, capacity) for a plan.
+struct ImageJob {
+    hipStream_t stream;
+    const float *rows;
+    const apt::gpu::Result *res;
+    uint64_t n, cap;
+    void *ws;                     // image_ws_bytes scratch
+    apt::gpu::ImageResult *info;  // the record
+    void *color_ws, *lab_ws, *eqfloat_ws, *png_ws;  // (each null unless the request runs its stage)
+    apt::map::Device *map;
+    apt::project::Device *project;
+    uint64_t stream_cap;          // the filtered stream png_ws is sized for
+};
+
+// The launches, in `plan` (null: a one-shot call).  A plan brackets every launch with its timer under the launch's
+// name and checks each stage's launches under a label of their own; a one-shot call does neither and checks once
+// behind everything.
+// The contrast limits of one job (noaa_apt.rs:141-175): the first kernel of every variant, which resets the record.
+void enqueue_image_limits(aptgpu_plan *plan, const ImageJob &j, int contrast, float percent);
+// Equalisation and colour of one job, behind its limits.
+void enqueue_image_color(aptgpu_plan *plan, const ImageRequest &q, const ImageRequest::Recording &r, const ImageJob &j);
+// What follows the colour, stage by stage and job by job within a stage: the overlay, then the reprojection (behind
+// its track when no overlay left one) or the PNG.
+void enqueue_image_outputs(aptgpu_plan *plan, const ImageRequest &q, const ImageJob *jobs, int count);
+
+}  // namespace apt

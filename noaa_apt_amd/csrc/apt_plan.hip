@@ -873,16 +873,28 @@ aptgpu_plan::ImageTarget aptgpu_plan::image_target(int i, uint64_t rows_cap_floa
     return ImageTarget{sl, stream_of(i), cap, sl.image_ws.ptr, d_image_results.ptr + slot, d_results.ptr + slot};
 }
 
-void aptgpu_plan::enqueue_limits(const ImageTarget &t, const float *d_rows, int contrast, float percent)
+// A plan brackets the launch with its timer and checks each stage's launches under the stage's own label; a one-shot
+// call (plan == null) does neither.
+template <typename Fn>
+static void launch_timed(aptgpu_plan *plan, hipStream_t s, const char *name, Fn &&launch)
+{
+    plan ? plan->timed(s, name, launch) : launch();
+}
+static void stage_done(aptgpu_plan *plan, const char *label)
+{
+    if (plan) apt::hip_check(hipGetLastError(), label);
+}
+
+void apt::enqueue_image_limits(aptgpu_plan *plan, const ImageJob &j, int contrast, float percent)
 {
     using namespace apt::gpu;
-    // (the first kernel of every variant resets the record)
+    hipStream_t s = j.stream;
     if (contrast == APTGPU_CONTRAST_TELEMETRY)
-        timed(t.stream, "image_telemetry", [&] { image_telemetry(t.stream, d_rows, t.res, 0, t.cap, t.ws, t.out, true); });
+        launch_timed(plan, s, "image_telemetry", [&] { image_telemetry(s, j.rows, j.res, j.n, j.cap, j.ws, j.info, true); });
     else if (contrast == APTGPU_CONTRAST_PERCENT)
-        timed(t.stream, "image_percent", [&] { image_percent(t.stream, d_rows, t.res, 0, t.cap, percent, t.ws, t.out); });
+        launch_timed(plan, s, "image_percent", [&] { image_percent(s, j.rows, j.res, j.n, j.cap, percent, j.ws, j.info); });
     else  // MinMax, and Histogram's limits (noaa_apt.rs:158-164)
-        timed(t.stream, "image_minmax", [&] { image_minmax(t.stream, d_rows, t.res, 0, t.cap, t.ws, t.out); });
+        launch_timed(plan, s, "image_minmax", [&] { image_minmax(s, j.rows, j.res, j.n, j.cap, j.ws, j.info); });
 }
 
 void aptgpu_plan::enqueue_image(int i, const float *d_rows, uint64_t rows_cap_floats, int contrast,
@@ -890,7 +902,7 @@ void aptgpu_plan::enqueue_image(int i, const float *d_rows, uint64_t rows_cap_fl
 {
     using namespace apt::gpu;
     const ImageTarget t = image_target(i, rows_cap_floats);
-    enqueue_limits(t, d_rows, contrast, percent);
+    apt::enqueue_image_limits(this, image_job(t, d_rows), contrast, percent);
     timed(t.stream, "image_map_u8", [&] { image_map_u8(t.stream, d_rows, t.res, 0, t.cap, t.ws, rotate, d_image, t.out); });
     apt::hip_check(hipGetLastError(), "kernel launch (image stage)");
 }
@@ -956,153 +968,168 @@ void aptgpu_plan::new_palette(const uint8_t *rgb)
     ++palette.gen;
 }
 
-void aptgpu_plan::enqueue_image_color(int i, const float *d_rows, uint64_t rows_cap_floats, int contrast,
-                                      float percent, bool rotate, const apt::gpu::ColorTune *tune, int channels,
-                                      uint8_t *d_image, bool lab)
+void aptgpu_plan::enqueue_images(const apt::ImageRequest &q, int count, const float *const *d_rows,
+                                 const size_t *rows_cap)
 {
     using namespace apt::gpu;
-    const ImageTarget t = image_target(i, rows_cap_floats);
-    Slot &sl = t.slot;
-    if (!sl.color_ws.ptr) {
-        sl.color_ws.alloc(color_ws_bytes());
-        apt::hip_check(color_ws_init(t.stream, sl.color_ws.ptr), "hipMemsetAsync");
-    }
-    if (tune && sl.palette_gen != palette.gen) {
-        apt::hip_check(hipMemcpyAsync(color_ws_palette(sl.color_ws.ptr), palette.pinned, 65536 * sizeof(uint32_t),
-                                      hipMemcpyHostToDevice, t.stream),
-                       "hipMemcpyAsync H2D (palette)");
-        hipEvent_t &ev = palette.uploaded[static_cast<size_t>(last_stream)];
+    // (sized for the plan's largest image with 4 bytes per pixel, so one allocation serves every call)
+    uint64_t stream_cap = 0;
+    if (q.png && !q.project)
+        stream_cap = apt::png::stream_bytes(
+            2080, std::max<uint64_t>(max_rows, out_len_nosync(work_len_for(max_samples)) / 2080u + 1), 4);
+    auto upload = [&](void *dst, const void *pinned, size_t bytes, hipEvent_t &ev, hipStream_t s, const char *what) {
+        apt::hip_check(hipMemcpyAsync(dst, pinned, bytes, hipMemcpyHostToDevice, s), what);
         if (!ev) apt::hip_check(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
-        apt::hip_check(hipEventRecord(ev, t.stream), "hipEventRecord");
-        sl.palette_gen = palette.gen;
-    }
-    if (lab) {
-        if (!sl.lab_ws.ptr) sl.lab_ws.alloc(lab_ws_bytes());
-        if (sl.lab_gen != palette.lab_gen) {
-            apt::hip_check(hipMemcpyAsync(sl.lab_ws.ptr, palette.lab_pinned, sizeof(apt::lab::Tables),
-                                          hipMemcpyHostToDevice, t.stream),
-                           "hipMemcpyAsync H2D (Lab tables)");
-            hipEvent_t &ev = palette.lab_uploaded[static_cast<size_t>(last_stream)];
-            if (!ev) apt::hip_check(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
-            apt::hip_check(hipEventRecord(ev, t.stream), "hipEventRecord");
-            sl.lab_gen = palette.lab_gen;
+        apt::hip_check(hipEventRecord(ev, s), "hipEventRecord");
+    };
+    std::vector<apt::ImageJob> jobs(static_cast<size_t>(count));
+    for (int i = 0; i < count; ++i) {
+        const ImageTarget t = image_target(i, static_cast<uint64_t>(rows_cap[i]) * 2080u);
+        Slot &sl = t.slot;
+        if (!sl.color_ws.ptr) {
+            sl.color_ws.alloc(color_ws_bytes());
+            apt::hip_check(color_ws_init(t.stream, sl.color_ws.ptr), "hipMemsetAsync");
         }
+        if (q.colored && sl.palette_gen != palette.gen) {
+            upload(color_ws_palette(sl.color_ws.ptr), palette.pinned, 65536 * sizeof(uint32_t),
+                   palette.uploaded[static_cast<size_t>(last_stream)], t.stream, "hipMemcpyAsync H2D (palette)");
+            sl.palette_gen = palette.gen;
+        }
+        if (q.lab) {
+            if (!sl.lab_ws.ptr) sl.lab_ws.alloc(lab_ws_bytes());
+            if (sl.lab_gen != palette.lab_gen) {
+                upload(sl.lab_ws.ptr, palette.lab_pinned, sizeof(apt::lab::Tables),
+                       palette.lab_uploaded[static_cast<size_t>(last_stream)], t.stream, "hipMemcpyAsync H2D (Lab tables)");
+                sl.lab_gen = palette.lab_gen;
+            }
+        }
+        if (q.contrast == APTGPU_CONTRAST_HISTOGRAM_FLOAT && !sl.eqfloat_ws.ptr) sl.eqfloat_ws.alloc(eqfloat_ws_bytes());
+        if ((q.overlay || q.project) && !sl.map) sl.map = std::make_unique<apt::map::Device>();
+        if (q.project && !sl.project) sl.project = std::make_unique<apt::project::Device>();
+        if (q.png && !q.project && t.cap >= 2080u && !sl.png_ws.ptr) sl.png_ws.alloc(apt::png::ws_bytes(stream_cap));
+        apt::ImageJob &j = jobs[static_cast<size_t>(i)];
+        j = image_job(t, d_rows[i]);
+        j.color_ws = sl.color_ws.ptr;
+        j.lab_ws = sl.lab_ws.ptr;
+        j.eqfloat_ws = sl.eqfloat_ws.ptr;
+        j.png_ws = sl.png_ws.ptr;
+        j.map = sl.map.get();
+        j.project = sl.project.get();
+        j.stream_cap = stream_cap;
         // Histogram with colour takes the 98 % limits; the zero-length error of get_min / get_max is the same
         // record (reason 1) as percent's (noaa_apt.rs:158-175)
-        enqueue_limits(t, d_rows, APTGPU_CONTRAST_PERCENT, 0.98f);
+        apt::enqueue_image_limits(this, j, q.lab ? APTGPU_CONTRAST_PERCENT : q.contrast, q.lab ? 0.98f : q.percent);
+        apt::enqueue_image_color(this, q, q.rec[static_cast<size_t>(i)], j);
+    }
+    apt::enqueue_image_outputs(this, q, jobs.data(), count);
+}
+
+namespace apt {
+
+using Recording = ImageRequest::Recording;
+
+static uint32_t count32(size_t count) { return count < 0xffffffffu ? static_cast<uint32_t>(count) : 0xffffffffu; }
+
+void enqueue_image_color(aptgpu_plan *plan, const ImageRequest &q, const Recording &r, const ImageJob &j)
+{
+    using namespace apt::gpu;
+    hipStream_t s = j.stream;
+    if (q.contrast == APTGPU_CONTRAST_HISTOGRAM_FLOAT) {  // (no palette: the entry points refuse it)
+        launch_timed(plan, s, "image_equalize_float",
+                     [&] { image_equalize_float(s, j.rows, j.res, j.n, j.cap, j.eqfloat_ws); });
+        launch_timed(plan, s, "image_color_float", [&] {
+            image_color_float(s, j.rows, j.res, j.n, j.cap, j.ws, j.eqfloat_ws, q.channels, r.rotate, r.d_image, j.info);
+        });
     } else {
-        enqueue_limits(t, d_rows, contrast, percent);
-    }
-    if (contrast == APTGPU_CONTRAST_HISTOGRAM_FLOAT) {  // (no palette: color_args refuses it)
-        if (!sl.eqfloat_ws.ptr) sl.eqfloat_ws.alloc(eqfloat_ws_bytes());
-        timed(t.stream, "image_equalize_float",
-              [&] { image_equalize_float(t.stream, d_rows, t.res, 0, t.cap, sl.eqfloat_ws.ptr); });
-        timed(t.stream, "image_color_float", [&] {
-            image_color_float(t.stream, d_rows, t.res, 0, t.cap, t.ws, sl.eqfloat_ws.ptr, channels, rotate, d_image, t.out);
+        const bool equalize = q.contrast == APTGPU_CONTRAST_HISTOGRAM;
+        if (q.lab)
+            launch_timed(plan, s, "image_equalize_lab", [&] {
+                image_equalize_lab(s, j.rows, j.res, j.n, j.cap, j.ws, j.color_ws, j.lab_ws, q.tune);
+            });
+        else if (equalize)
+            launch_timed(plan, s, "image_equalize", [&] { image_equalize(s, j.rows, j.res, j.n, j.cap, j.ws, j.color_ws); });
+        launch_timed(plan, s, "image_color", [&] {
+            image_color(s, j.rows, j.res, j.n, j.cap, j.ws, j.color_ws, equalize, q.colored ? &q.tune : nullptr,
+                        q.channels, r.rotate, r.d_image, j.info, q.lab ? j.lab_ws : nullptr);
         });
-        apt::hip_check(hipGetLastError(), "kernel launch (image stage)");
-        return;
     }
-    const bool equalize = contrast == APTGPU_CONTRAST_HISTOGRAM;
-    if (lab)
-        timed(t.stream, "image_equalize_lab", [&] {
-            image_equalize_lab(t.stream, d_rows, t.res, 0, t.cap, t.ws, sl.color_ws.ptr, sl.lab_ws.ptr, *tune);
+    stage_done(plan, "kernel launch (image stage)");
+}
+
+static void enqueue_image_overlay(aptgpu_plan *plan, const ImageRequest &q, const Recording &r, const ImageJob &j)
+{
+    const apt::map::Colors colors{{q.layers->color[0], q.layers->color[1], q.layers->color[2]}};
+    j.map->prepare(j.stream, *q.layers, j.cap / 2080u);
+    if (r.track == ImageRequest::Track::Sat) {
+        launch_timed(plan, j.stream, "image_map_overlay_sat", [&] {
+            apt::map::image_map_overlay_sat(j.stream, *j.map, r.sat, r.geom.yaw, r.geom.hscale, r.geom.vscale, colors,
+                                            r.rotate, r.d_image, j.info);
         });
-    else if (equalize)
-        timed(t.stream, "image_equalize", [&] { image_equalize(t.stream, d_rows, t.res, 0, t.cap, t.ws, sl.color_ws.ptr); });
-    timed(t.stream, "image_color", [&] {
-        image_color(t.stream, d_rows, t.res, 0, t.cap, t.ws, sl.color_ws.ptr, equalize, tune, channels, rotate, d_image,
-                    t.out, lab ? sl.lab_ws.ptr : nullptr);
-    });
-    apt::hip_check(hipGetLastError(), "kernel launch (image stage)");
+    } else {
+        j.map->upload_track(j.stream, r.positions, r.n_positions);
+        const apt::map::Scalars sc = apt::map::scalars(r.positions, r.n_positions, r.geom.yaw, r.geom.hscale, r.geom.vscale);
+        launch_timed(plan, j.stream, "image_map_overlay", [&] {
+            apt::map::image_map_overlay(j.stream, *j.map, sc, colors, count32(r.n_positions), r.rotate, r.d_image, j.info);
+        });
+    }
+    stage_done(plan, "kernel launch (map overlay)");
 }
 
-void aptgpu_plan::enqueue_image_map(int i, uint64_t rows_cap_floats, const apt::map::Layers &layers,
-                                    const apt::map::Scalars &sc, const apt::map::Colors &colors,
-                                    const double *positions, size_t count, bool rotate, uint8_t *d_image)
+// (an overlay left the track's x offsets and scalars in the job's map device; without one they are computed first)
+static void enqueue_image_project(aptgpu_plan *plan, const ImageRequest &q, const Recording &r, const ImageJob &j)
 {
-    const ImageTarget t = image_target(i, rows_cap_floats);
-    Slot &sl = t.slot;
-    if (!sl.map) sl.map = std::make_unique<apt::map::Device>();
-    sl.map->prepare(t.stream, layers, t.cap / 2080u);
-    sl.map->upload_track(t.stream, positions, count);
-    const uint32_t n = count < 0xffffffffu ? static_cast<uint32_t>(count) : 0xffffffffu;
-    timed(t.stream, "image_map_overlay", [&] {
-        apt::map::image_map_overlay(t.stream, *sl.map, sc, colors, n, rotate, d_image, t.out);
-    });
-    apt::hip_check(hipGetLastError(), "kernel launch (map overlay)");
-}
-
-void aptgpu_plan::enqueue_image_map_sat(int i, uint64_t rows_cap_floats, const apt::map::Layers &layers,
-                                        const apt::sat::TrackCall &call, const aptgpu_map_settings &settings,
-                                        const apt::map::Colors &colors, bool rotate, uint8_t *d_image)
-{
-    const ImageTarget t = image_target(i, rows_cap_floats);
-    Slot &sl = t.slot;
-    if (!sl.map) sl.map = std::make_unique<apt::map::Device>();
-    sl.map->prepare(t.stream, layers, t.cap / 2080u);
-    timed(t.stream, "image_map_overlay_sat", [&] {
-        apt::map::image_map_overlay_sat(t.stream, *sl.map, call, settings.yaw, settings.hscale, settings.vscale, colors,
-                                        rotate, d_image, t.out);
-    });
-    apt::hip_check(hipGetLastError(), "kernel launch (map overlay)");
-}
-
-void aptgpu_plan::enqueue_image_project(int i, uint64_t rows_cap_floats, int channels, const uint8_t *d_image,
-                                        const apt::project::Grid &grid, const std::vector<uint8_t> &flags,
-                                        const aptgpu_map_settings &ms, bool overlay_done, const double *positions,
-                                        size_t count, const apt::sat::TrackCall *sat, uint8_t *d_out, uint64_t out_cap,
-                                        uint8_t *d_png, uint64_t png_cap)
-{
-    const ImageTarget t = image_target(i, rows_cap_floats);
-    Slot &sl = t.slot;
-    if (!sl.map) sl.map = std::make_unique<apt::map::Device>();
-    if (!sl.project) sl.project = std::make_unique<apt::project::Device>();
+    const bool sat = r.track == ImageRequest::Track::Sat;
     apt::map::Scalars sc{};
-    if (!sat) sc = apt::map::scalars(positions, count, ms.yaw, ms.hscale, ms.vscale);
-    if (!overlay_done) {
-        sl.map->prepare_track(t.stream, t.cap / 2080u);
-        timed(t.stream, "image_project_track", [&] {
+    if (!sat) sc = apt::map::scalars(r.positions, r.n_positions, r.geom.yaw, r.geom.hscale, r.geom.vscale);
+    if (!q.overlay) {
+        j.map->prepare_track(j.stream, j.cap / 2080u);
+        launch_timed(plan, j.stream, "image_project_track", [&] {
             if (sat) {
-                apt::map::image_map_track_sat(t.stream, *sl.map, *sat, ms.yaw, ms.hscale, ms.vscale, t.out);
+                apt::map::image_map_track_sat(j.stream, *j.map, r.sat, r.geom.yaw, r.geom.hscale, r.geom.vscale, j.info);
             } else {
-                sl.map->upload_track(t.stream, positions, count);
-                apt::map::image_map_track(t.stream, *sl.map, sc,
-                                          count < 0xffffffffu ? static_cast<uint32_t>(count) : 0xffffffffu, t.out);
+                j.map->upload_track(j.stream, r.positions, r.n_positions);
+                apt::map::image_map_track(j.stream, *j.map, sc, count32(r.n_positions), j.info);
             }
         });
     }
-    sl.project->upload_flags(t.stream, flags);
-    timed(t.stream, "image_project", [&] {
-        apt::project::image_project(t.stream, *sl.project, *sl.map, sat ? nullptr : &sc, grid, d_image, channels, d_out,
-                                    out_cap, t.out);
+    j.project->upload_flags(j.stream, r.flags);
+    launch_timed(plan, j.stream, "image_project", [&] {
+        apt::project::image_project(j.stream, *j.project, *j.map, sat ? nullptr : &sc, r.grid, r.d_image, q.channels,
+                                    r.d_out, r.out_cap, j.info);
     });
-    if (d_png)
-        timed(t.stream, "image_project_png", [&] {
-            apt::project::image_project_png(t.stream, *sl.project, grid, d_out, d_png, png_cap, t.out);
+    if (q.png)
+        launch_timed(plan, j.stream, "image_project_png", [&] {
+            apt::project::image_project_png(j.stream, *j.project, r.grid, r.d_out, r.d_png, r.png_cap, j.info);
         });
-    apt::hip_check(hipGetLastError(), "kernel launch (reprojection)");
+    stage_done(plan, "kernel launch (reprojection)");
 }
 
-void aptgpu_plan::enqueue_image_png(int i, uint64_t rows_cap_floats, int channels, const uint8_t *d_image,
-                                    uint8_t *d_png, uint64_t png_cap)
+static void enqueue_image_png(aptgpu_plan *plan, const ImageRequest &q, const Recording &r, const ImageJob &j)
 {
-    const ImageTarget t = image_target(i, rows_cap_floats);
-    Slot &sl = t.slot;
-    const uint32_t rows = static_cast<uint32_t>(t.cap / 2080u);  // the launch grids cover the capacity
+    const uint32_t rows = static_cast<uint32_t>(j.cap / 2080u);  // the launch grids cover the capacity
     if (rows == 0) return;
-    // (sized for the plan's largest image with 4 bytes per pixel, so one allocation serves every call)
-    const uint64_t ws_rows = std::max<uint64_t>(max_rows, out_len_nosync(work_len_for(max_samples)) / 2080u + 1);
-    const uint64_t stream_cap = apt::png::stream_bytes(2080, ws_rows, 4);
-    if (!sl.png_ws.ptr) sl.png_ws.alloc(apt::png::ws_bytes(stream_cap));
-    timed(t.stream, "image_png_filter", [&] {
-        apt::png::encode_filter(t.stream, d_image, 2080, rows, channels, sl.png_ws.ptr, stream_cap, t.out);
+    launch_timed(plan, j.stream, "image_png_filter", [&] {
+        apt::png::encode_filter(j.stream, r.d_image, 2080, rows, q.channels, j.png_ws, j.stream_cap, j.info);
     });
-    timed(t.stream, "image_png_deflate", [&] {
-        apt::png::encode_deflate(t.stream, 2080, rows, channels, sl.png_ws.ptr, stream_cap, t.out);
+    launch_timed(plan, j.stream, "image_png_deflate", [&] {
+        apt::png::encode_deflate(j.stream, 2080, rows, q.channels, j.png_ws, j.stream_cap, j.info);
     });
-    timed(t.stream, "image_png_place", [&] {
-        apt::png::encode_place(t.stream, 2080, rows, channels, sl.png_ws.ptr, stream_cap, d_png, png_cap, t.out, nullptr);
+    launch_timed(plan, j.stream, "image_png_place", [&] {
+        apt::png::encode_place(j.stream, 2080, rows, q.channels, j.png_ws, j.stream_cap, r.d_png, r.png_cap, j.info, nullptr);
     });
-    apt::hip_check(hipGetLastError(), "kernel launch (PNG encoder)");
+    stage_done(plan, "kernel launch (PNG encoder)");
 }
+
+void enqueue_image_outputs(aptgpu_plan *plan, const ImageRequest &q, const ImageJob *jobs, int count)
+{
+    auto each = [&](auto stage) {
+        for (int i = 0; i < count; ++i) stage(plan, q, q.rec[static_cast<size_t>(i)], jobs[i]);
+    };
+    if (q.overlay) each(enqueue_image_overlay);
+    if (q.project)
+        each(enqueue_image_project);
+    else if (q.png)
+        each(enqueue_image_png);
+}
+
+}  // namespace apt

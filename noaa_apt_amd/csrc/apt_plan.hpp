@@ -11,6 +11,7 @@
 
 #include "../../include/aptgpu.h"
 #include "apt_host.hpp"
+#include "apt_image_request.hpp"
 #include "apt_kernels.hpp"
 #include "apt_kernels_color.hpp"
 #include "apt_kernels_despeckle.hpp"
@@ -212,7 +213,10 @@ struct aptgpu_plan {
         const apt::gpu::Result *res;
     };
     ImageTarget image_target(int i, uint64_t rows_cap_floats);  // allocates the slot's scratch on first use
-    void enqueue_limits(const ImageTarget &t, const float *d_rows, int contrast, float percent);
+    static apt::ImageJob image_job(const ImageTarget &t, const float *d_rows)  // (the scratch pointers stay null)
+    {
+        return apt::ImageJob{t.stream, d_rows, t.res, 0, t.cap, t.ws, t.out};
+    }
     template <typename Fn>
     void timed(hipStream_t s, const char *name, Fn &&launch)
     {
@@ -220,40 +224,16 @@ struct aptgpu_plan {
         launch();
         timer.end(s);
     }
-    // The same with every contrast (APTGPU_CONTRAST_HISTOGRAM and _HISTOGRAM_FLOAT too), optional false colour and 1 or 4 bytes per
-    // pixel (aptgpu_plan_process_device_image).  set_palette first when tune is non-null (with lab: Histogram
-    // with false colour, equalised in CIE Lab).
-    void enqueue_image_color(int i, const float *d_rows, uint64_t rows_cap_floats, int contrast, float percent,
-                             bool rotate, const apt::gpu::ColorTune *tune, int channels, uint8_t *d_image,
-                             bool lab = false);
+    // The image stage under a request (the aptgpu_plan_process_device_image* entry points) of the first `count`
+    // recordings of the last call, behind their decode on the same stream: one ImageJob per recording from its slot,
+    // whose scratch is allocated on first use and whose palette / Lab tables are uploaded once per generation
+    // (set_palette first), then the launches of apt_image_request.hpp.
+    void enqueue_images(const apt::ImageRequest &q, int count, const float *const *d_rows, const size_t *rows_cap);
     // The despeckle stage (apt_kernels_despeckle.hpp) of recording i, behind its decode on the same stream: the 98 %
     // limits of d_rows when threshold != 0 (into the slot's image scratch, which the image stage behind it rewrites),
     // then one k_despeckle launch into d_out (same capacity, no overlap).  The record stays in the slot.
     void enqueue_despeckle(int i, const float *d_rows, uint64_t rows_cap_floats, int radius, float threshold,
                            float *d_out);
-    // The map overlay (apt_kernels_map.hpp) over recording i's RGBA image, behind enqueue_image_color on the same
-    // stream.  The slot uploads the layer set once per generation; positions: `count` (lat, lon) pairs.
-    void enqueue_image_map(int i, uint64_t rows_cap_floats, const apt::map::Layers &layers,
-                           const apt::map::Scalars &sc, const apt::map::Colors &colors, const double *positions,
-                           size_t count, bool rotate, uint8_t *d_image);
-    // The same with the track computed on the device from the satellite and the reference time (apt_kernels_track.hpp):
-    // nothing is staged or uploaded per call.
-    void enqueue_image_map_sat(int i, uint64_t rows_cap_floats, const apt::map::Layers &layers,
-                               const apt::sat::TrackCall &call, const aptgpu_map_settings &settings,
-                               const apt::map::Colors &colors, bool rotate, uint8_t *d_image);
-    // The PNG encoder (apt_kernels_png.hpp) over recording i's finished image, behind everything above on the same
-    // stream: the file goes to d_png (png_cap bytes), its length to the image record.
-    void enqueue_image_png(int i, uint64_t rows_cap_floats, int channels, const uint8_t *d_image, uint8_t *d_png,
-                           uint64_t png_cap);
-    // The reprojection (apt_kernels_project.hpp) of recording i's finished, unrotated image onto `grid` into d_out
-    // (out_cap bytes), behind everything above on the same stream, then optionally its PNG file into d_png.  With
-    // overlay_done the overlay's launches left the track's x offsets and scalars in the slot; otherwise they are
-    // computed here first, from `positions` (count pairs, scalars on the host) or from `sat` (on the device).
-    void enqueue_image_project(int i, uint64_t rows_cap_floats, int channels, const uint8_t *d_image,
-                               const apt::project::Grid &grid, const std::vector<uint8_t> &flags,
-                               const aptgpu_map_settings &ms, bool overlay_done, const double *positions, size_t count,
-                               const apt::sat::TrackCall *sat, uint8_t *d_out, uint64_t out_cap, uint8_t *d_png,
-                               uint64_t png_cap);
     // The false-colour palette (256*256*3 RGB).  The plan keeps a host copy; bytes that differ from it start a new
     // generation, which every slot uploads on its own stream the next time it colours an image.  lab: also the
     // palette's Lab tables (apt_lab.hpp), computed once per generation and uploaded per slot likewise.
