@@ -98,8 +98,14 @@ typedef struct aptgpu_context {
 #define APTGPU_MODE_GENERIC 1 /* force the unfused generic kernels (any rate combination)   */
 #define APTGPU_MODE_FP16_TAPS 2 /* first resample with fp16 taps + fp16 samples through
                                    v_dot2_f32_f16, f32 accumulate (BASELINE.json config 5).  NOT
-                                   bit-exact: pixels within ~2e-3 of the row peak, sync positions
-                                   unchanged on APT data; every other stage as in STRICT        */
+                                   bit-exact: pixels within ~2e-3 of the row peak (of the peak, not
+                                   of the pixel: the error does not shrink with the pixel's own
+                                   value; measured 2.2e-4 max / 3.9e-5 rms of the signal's peak), sync positions unchanged on
+                                   APT data; every other stage as in STRICT.  Input domain: the
+                                   samples are converted to fp16 UNSCALED (only the taps are
+                                   prescaled) — 16-bit PCM and +-1 float data fit, a sample beyond
+                                   +-65504 becomes an infinity, and samples below 6.1e-5 in
+                                   magnitude fall into fp16's subnormals and lose precision      */
 #define APTGPU_MODE_FAST 3 /* f32 throughout with the same taps in the same order, but fused
                               multiply-adds in the two FIR stages, the native square root and a
                               reciprocal multiplication in the envelope, and the +-1 sync correlation
@@ -111,8 +117,10 @@ typedef struct aptgpu_context {
                               are served by the strict kernels.  With a user-tuned resample filter (a
                               tap count other than the stock profiles') at 48 / 96 kHz the resampler
                               runs on the matrix cores from bf16 pieces of the f32 taps (three: exact)
-                              and samples (two: exact for 16-bit data), f32 accumulation: the same
-                              tolerance (measured 5e-7 of full scale). */
+                              and samples (two truncated planes: exact for samples of at most 16
+                              significant bits, the remainder of any other sample is dropped), f32
+                              accumulation: the same tolerance (measured 5e-7 of full scale on 16-bit
+                              data, 1.3e-5 max / 3.7e-6 rms on full-mantissa f32 samples). */
 
 /* What find_sync()/decode() learned; the reference only logs it
  * (`info!("Found {} sync frames")` src/decode.rs:260). */
@@ -259,7 +267,10 @@ int aptgpu_plan_collect_timing(aptgpu_plan *plan, aptgpu_kernel_time *out, size_
  * fallback ran, [8..] cycle stamps of the picker kernels), "eqfloat_thresholds" (u32[2][255]: the
  * sorted threshold keys T_1..T_255 of half A, then of half B, of the slot's last
  * APTGPU_CONTRAST_HISTOGRAM_FLOAT image; size 0 before the first one).  Writes min(bytes, size) bytes
- * and returns the buffer's size in *size_out. */
+ * and returns the buffer's size in *size_out.  Two names are host-side constants with no device copy:
+ * "inv_sinphi" (f32) and "fused_variant" (chars, not NUL-terminated: the row name in
+ * csrc/apt_kernels_fused_variants.hpp of the front-end kernel the slot's last decode launched, with "_f32" or
+ * "_i16" appended for its input type; size 0 where k_fused_any or the unfused kernels ran). */
 int aptgpu_plan_read_internal(aptgpu_plan *plan, int i, const char *name, void *host_out,
                               size_t bytes, size_t *size_out);
 

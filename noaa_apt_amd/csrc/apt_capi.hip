@@ -7,6 +7,7 @@
 #include <string>
 
 #include "apt_capi_util.hpp"
+#include "apt_kernels_fused_variants.hpp"
 #include "apt_session.hpp"
 
 namespace {
@@ -240,6 +241,14 @@ int aptgpu_plan_read_internal(aptgpu_plan *plan, int i, const char *name, void *
     if (n == "inv_sinphi") {  // host-side constant: RN(1/sin(phi)) when the fast exact divide is on, else 0
         if (size_out) *size_out = sizeof(float);
         if (host_out && bytes >= sizeof(float)) std::memcpy(host_out, &plan->inv_sinphi, sizeof(float));
+        return APTGPU_OK;
+    }
+    if (n == "fused_variant") {  // host-side: "<row of apt_kernels_fused_variants.hpp>_f32" / "..._i16", "" where none ran
+        std::string v;
+        if (sl.fused_variant >= 0 && sl.fused_variant < apt::gpu::kFusedVariantCount)
+            v = std::string(apt::gpu::kFusedVariants[sl.fused_variant].name) + (sl.fused_variant_i16 ? "_i16" : "_f32");
+        if (size_out) *size_out = v.size();
+        if (host_out && bytes) std::memcpy(host_out, v.data(), bytes < v.size() ? bytes : v.size());
         return APTGPU_OK;
     }
     if (n == "filtered") { src = sl.filtered.ptr; size = sl.filtered.count * sizeof(float); }

@@ -219,8 +219,11 @@ struct FusedParams {
 // per-group maxima of the sync cross-correlation.  Returns false if no specialisation matches.
 // Inputs are f32 Signals, or (pcm16) mono int16 samples at 4-byte aligned addresses.
 // mode: 0 strict, 1 fp16 taps, 2 fast.
+// variant_out (this and the two front ends below): receives the row of apt_kernels_fused_variants.hpp whose kernel the
+// call launched (a FusedVariant; -1 where none was) — introspection, aptgpu_plan_read_internal("fused_variant").
 bool fused_front_end(hipStream_t s, uint32_t l, uint32_t m, uint32_t t1, uint32_t t2, uint32_t pw, int mode,
-                     bool pcm16, const CallArgs &call, const FusedParams *d_prm, uint64_t max_w, int lds_pad = 0);
+                     bool pcm16, const CallArgs &call, const FusedParams *d_prm, uint64_t max_w, int lds_pad = 0,
+                     int *variant_out = nullptr);
 // kModeMfma (mode 3 of fused_front_end): which geometries have a matrix-core instantiation, and its table —
 // [3 pieces][K / 32][64 lanes][4 dwords] bf16 fragments of the banded Toeplitz matrix of the resampler (h = h0 + h1 + h2
 // exactly)
@@ -232,7 +235,7 @@ void fused_mfma_table(uint32_t l, uint32_t m, const float *coeff, uint32_t t1, u
 // stages (37-tap low-pass, pw = 3).  11 025 Hz (l = 832) is the rate this exists for.
 bool fused_table_supported(uint32_t l, uint32_t m, uint32_t t1, uint32_t t2, uint32_t pw, TableGeom *geom);
 bool fused_table_front_end(hipStream_t s, const TableGeom &geom, int mode, bool pcm16, const CallArgs &call,
-                           const FusedParams *d_prm, uint64_t max_w);
+                           const FusedParams *d_prm, uint64_t max_w, int *variant_out = nullptr);
 
 // Phase-resident stage 1 + the specialised work-rate stages (k_fused in PHASE mode): a thread holds nq slots u + q S'
 // (S' = step_r / nq <= threads) of the step_r outputs after which the polyphase branches repeat, and computes the
@@ -247,7 +250,7 @@ uint32_t fused_phase_table_floats(const TableGeom &geom);
 // host: [l][tpp] taps, rows 16-byte aligned, then the thread assignment lists (geom.perm_off)
 void fused_phase_table(const TableGeom &geom, uint32_t t2, uint32_t pw, const float *coeff, uint32_t t1, float *table);
 bool fused_phase_front_end(hipStream_t s, const TableGeom &geom, uint32_t t2, uint32_t pw, int mode, bool pcm16,
-                           const CallArgs &call, const FusedParams *d_prm, uint64_t max_w);
+                           const CallArgs &call, const FusedParams *d_prm, uint64_t max_w, int *variant_out = nullptr);
 
 // ---- fused front end for any rate / profile (apt_kernels_fused_any.hip) -------------
 // run-time parameters, taps phase-major in LDS; same outputs as fused_front_end

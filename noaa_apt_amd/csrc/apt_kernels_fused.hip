@@ -43,10 +43,11 @@ using LaunchFn = void (*)(const FusedLaunch &);
 constexpr LaunchFn kFusedLaunch[kFusedVariantCount][2] = {APT_FUSED_VARIANTS(APT_FUSED_FN_BOTH, APT_FUSED_FN_F32)};
 #undef APT_FUSED_FN_BOTH
 #undef APT_FUSED_FN_F32
-bool launch_variant(FusedVariant v, bool pcm16, const FusedLaunch &a)
+bool launch_variant(FusedVariant v, bool pcm16, const FusedLaunch &a, int *variant_out)
 {
     const LaunchFn fn = v == kFusedNone ? nullptr : kFusedLaunch[v][pcm16 ? 1 : 0];
     if (fn) fn(a);
+    if (variant_out) *variant_out = fn ? static_cast<int>(v) : static_cast<int>(kFusedNone);
     return fn != nullptr;
 }
 }  // namespace
@@ -258,8 +259,9 @@ void fused_mfma_table(uint32_t l, uint32_t m, const float *coeff, uint32_t t1, u
 }
 
 bool fused_front_end(hipStream_t s, uint32_t l, uint32_t m, uint32_t t1, uint32_t t2, uint32_t pw, int mode,
-                     bool pcm16, const CallArgs &call, const FusedParams *d_prm, uint64_t max_w, int lds_pad)
+                     bool pcm16, const CallArgs &call, const FusedParams *d_prm, uint64_t max_w, int lds_pad, int *variant_out)
 {
+    if (variant_out) *variant_out = static_cast<int>(kFusedNone);
     if (call.count == 0 || call.count > static_cast<uint32_t>(kMaxCall)) return false;
     if (pcm16)  // dword loads of sample pairs
         for (uint32_t i = 0; i < call.count; ++i)
@@ -286,7 +288,7 @@ bool fused_front_end(hipStream_t s, uint32_t l, uint32_t m, uint32_t t1, uint32_
         return true;
     }
 #endif
-    return launch_variant(v, pcm16, a);
+    return launch_variant(v, pcm16, a, variant_out);
 }
 
 
@@ -321,14 +323,15 @@ bool fused_table_supported(uint32_t l, uint32_t m, uint32_t t1, uint32_t t2, uin
 }
 
 bool fused_table_front_end(hipStream_t s, const TableGeom &geom, int mode, bool pcm16, const CallArgs &call,
-                           const FusedParams *d_prm, uint64_t max_w)
+                           const FusedParams *d_prm, uint64_t max_w, int *variant_out)
 {
+    if (variant_out) *variant_out = static_cast<int>(kFusedNone);
     if (call.count == 0 || call.count > static_cast<uint32_t>(kMaxCall)) return false;
     if (pcm16)
         for (uint32_t i = 0; i < call.count; ++i)
             if (reinterpret_cast<uintptr_t>(call.rec[i].x) & 1u) return false;
     const FusedLaunch a{s, &call, d_prm, max_w, static_cast<size_t>(geom.off_x) + geom.xt};
-    return launch_variant(fused_table_variant(mode), pcm16, a);
+    return launch_variant(fused_table_variant(mode), pcm16, a, variant_out);
 }
 
 
@@ -645,8 +648,9 @@ void fused_phase_table(const TableGeom &g, uint32_t t2, uint32_t pw, const float
 }
 
 bool fused_phase_front_end(hipStream_t s, const TableGeom &geom, uint32_t t2, uint32_t pw, int mode, bool pcm16,
-                           const CallArgs &call, const FusedParams *d_prm, uint64_t max_w)
+                           const CallArgs &call, const FusedParams *d_prm, uint64_t max_w, int *variant_out)
 {
+    if (variant_out) *variant_out = static_cast<int>(kFusedNone);
     if (call.count == 0 || call.count > static_cast<uint32_t>(kMaxCall)) return false;
     if (pcm16)
         for (uint32_t i = 0; i < call.count; ++i)
@@ -657,7 +661,7 @@ bool fused_phase_front_end(hipStream_t s, const TableGeom &geom, uint32_t t2, ui
     const bool halves = phase_halves(static_cast<int>(geom.nq ? geom.nq : 1u), geom.stream != 0, static_cast<int>(geom.nthr),
                                      static_cast<int>(t2), fast_kernel);
     const FusedLaunch a{s, &call, d_prm, max_w, static_cast<size_t>(halves ? geom.xt / 2 : geom.xt)};
-    return launch_variant(fused_phase_variant(geom.nq, geom.nthr, geom.stream != 0, t2, pw, mode), pcm16, a);
+    return launch_variant(fused_phase_variant(geom.nq, geom.nthr, geom.stream != 0, t2, pw, mode), pcm16, a, variant_out);
 }
 
 }  // namespace apt::gpu

@@ -600,6 +600,7 @@ void aptgpu_plan::run_call(int count, const Input *ins, float *const *d_rows, co
         const Input &in = ins[i];
         Slot &sl = slots[static_cast<size_t>(slot0 + i)];
         Result *res = d_results.ptr + slot0 + i;
+        sl.fused_variant = -1;  // (until a k_fused instantiation serves this call)
         const uint64_t w = work_len_for(in.n);
         wlen[static_cast<size_t>(i)] = w;
         // decode.rs:79-83 — fewer than 10 rows of samples
@@ -682,12 +683,17 @@ void aptgpu_plan::run_call(int count, const Input *ins, float *const *d_rows, co
             for_chunks(idx, [&](const CallArgs &c, uint64_t max_w, uint32_t) {
                 timed_on(fs, "fused_front_end", [&] {
                     const int kmode = fused_f16 ? 1 : (fused_mfma ? 3 : (fused_pad_t1 ? 4 : (fused_fast ? 2 : 0)));
+                    int variant = -1;
                     const bool ok = fused == 4 ? fused_phase_front_end(fs, table_geom, t2, pw, kmode, kind == 1, c,
-                                                                       d_fused_params.ptr, max_w)
+                                                                       d_fused_params.ptr, max_w, &variant)
                                   : fused == 3 ? fused_table_front_end(fs, table_geom, kmode, kind == 1, c,
-                                                                       d_fused_params.ptr, max_w)
+                                                                       d_fused_params.ptr, max_w, &variant)
                                                : fused_front_end(fs, l, m, t1, t2, pw, kmode, kind == 1, c,
-                                                                 d_fused_params.ptr, max_w, sw.fused_lds_pad);
+                                                                 d_fused_params.ptr, max_w, sw.fused_lds_pad, &variant);
+                    for (uint32_t k = 0; k < c.count; ++k) {
+                        slots[c.rec[k].slot].fused_variant = variant;
+                        slots[c.rec[k].slot].fused_variant_i16 = kind == 1;
+                    }
                     if (!ok)
                         throw apt::Error{apt::ErrorKind::Internal, "fused front end: no kernel for this geometry"};
                 });

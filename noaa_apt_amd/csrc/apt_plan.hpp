@@ -192,6 +192,10 @@ struct aptgpu_plan {
         std::unique_ptr<apt::project::Device> project;  // the reprojection's graticule, record and PNG scratch, on first use
         apt::DeviceBuffer<char> png_ws;    // the PNG encoder's filtered stream, staging and chunk records, on first use
         apt::DeviceBuffer<float> ingest;   // WAV -> f32 staging when the fused PCM16 path does not apply
+        // the k_fused instantiation the slot's last front-end launch ran: row of apt_kernels_fused_variants.hpp (-1:
+        // k_fused_any or the unfused kernels) and whether it was the 16-bit PCM one (read_internal "fused_variant")
+        int fused_variant = -1;
+        bool fused_variant_i16 = false;
     };
     std::vector<Slot> slots;
     apt::DeviceBuffer<apt::gpu::SlotPtrs> d_slots;  // the slots' pointers, for the per-call launches
