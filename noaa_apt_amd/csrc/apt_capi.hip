@@ -5,6 +5,7 @@
 #include <cstring>
 #include <memory>
 #include <string>
+#include <vector>
 
 #include "apt_capi_util.hpp"
 #include "apt_kernels_fused_variants.hpp"
@@ -270,6 +271,30 @@ int aptgpu_plan_read_internal(aptgpu_plan *plan, int i, const char *name, void *
         return APTGPU_ERR_HIP;
     }
     const size_t take = bytes < size ? bytes : size;
+    if (n == "filtered" && sl.f_stride != 0 && plan->pw != 0) {
+        // F in pixel-phase planes (apt::gpu::f_index): returned in natural order all the same — of every plane the
+        // floats the caller's `bytes` reach, interleaved on the host
+        if (!take || !host_out || !src) return APTGPU_OK;
+        try {
+            const uint32_t pw = plan->pw;
+            const uint64_t want = take / sizeof(float);
+            const uint64_t limit = static_cast<uint64_t>(pw) * sl.f_stride;  // samples the planes hold
+            const uint64_t have = want < limit ? want : limit;
+            const uint64_t per = (have + pw - 1) / pw;  // <= f_stride
+            std::vector<float> plane(per);
+            float *out = static_cast<float *>(host_out);
+            for (uint32_t p = 0; p < pw && per; ++p) {
+                if (hipMemcpy(plane.data(), static_cast<const float *>(src) + static_cast<uint64_t>(p) * sl.f_stride,
+                              per * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+                    return APTGPU_ERR_HIP;
+                for (uint64_t k = p, j = 0; k < have; k += pw, ++j) out[k] = plane[j];
+            }
+            for (uint64_t k = have; k < want; ++k) out[k] = 0.f;
+        } catch (const std::exception &) {
+            return APTGPU_ERR_INTERNAL;
+        }
+        return APTGPU_OK;
+    }
     if (take && host_out && src &&
         hipMemcpy(host_out, src, take, hipMemcpyDeviceToHost) != hipSuccess)
         return APTGPU_ERR_HIP;
@@ -381,6 +406,8 @@ int decode_host(const aptgpu_context *ctx_in, const aptgpu_settings *settings, c
         plan->run_call(1, &in, &rows_ptr, &cap64, steps);
         aptgpu_plan::Slot &sl = plan->slot_of(0);
         if (steps) plan->sync_all();  // the step exports below read the slot's buffers
+        // (... F among them, as one contiguous signal: run_call's unfused kernels leave it so, never a k_fused launch)
+        if (steps && sl.f_stride != 0) throw Error{ErrorKind::Internal, "step export: F is in pixel-phase planes"};
         if (wav && steps) {
             apt::Signal x = download(sl.ingest.ptr, n, s);
             step(&ctx, steps, "input", 0, x.data(), x.size(), input_rate_hz);

@@ -84,7 +84,7 @@ struct CallArgs {
     RecArgs rec[kMaxCall];
 };
 struct SlotPtrs {
-    float *f;               // filtered work-rate signal F
+    float *f;               // filtered work-rate signal F (see f_stride)
     GroupMax *gm;           // per-group correlation maxima
     const float *corr;      // full correlation (unfused path / step export only), else nullptr
     uint64_t *words;        // 52-bit terminal words
@@ -92,8 +92,21 @@ struct SlotPtrs {
     uint32_t *slot_nt, *slot_cnt, *flags, *orbit_ws, *peaks;
     Result *res;
     uint32_t peaks_cap;
-    uint32_t reserved;
+    uint32_t f_stride;      // 0: F contiguous; else F in pixel-phase planes of f_stride floats (f_index)
 };
+
+// Where F[i] lies in a slot's filtered buffer.  The k_fused instantiations write F in pw pixel-phase planes —
+// F[i] at f[(i % pw) * stride + i / pw] — so that a pixel row (every pw-th sample from a sync position) is one
+// contiguous run of a plane; stride == 0 is the contiguous layout of k_fused_any and the unfused kernels.
+__host__ __device__ inline uint64_t f_index(uint64_t i, uint32_t pw, uint32_t stride)
+{
+    return stride ? (i % pw) * stride + i / pw : i;
+}
+// plane length of a plan whose longest work signal has max_w samples: a multiple of 4 floats, one quad of padding
+__host__ __device__ inline uint32_t f_plane_stride(uint64_t max_w, uint32_t pw)
+{
+    return static_cast<uint32_t>(((max_w + pw - 1) / pw + 4 + 3) & ~3ull);
+}
 
 // ---- generic kernels (any l, m, tap count) --------------------------------------
 // fast_resampling, dsp.rs:186-289: out[k], k < w

@@ -1786,41 +1786,77 @@ k_fused(const CallArgs call_by_value, const FusedParams *__restrict__ prm)
     }
     APT_MARK("END f_to_lds");
     if constexpr (APT_FUSED_STOP == 4) return;
-    // owned F -> HBM, coalesced 16-byte stores
+    // owned F -> HBM in pixel-phase planes (f_index, apt_kernels.hpp): F[i] at plane i % PW, index i / PW, so that the
+    // row gather reads contiguous runs.  The samples o0 + d + PW k of the tile (d < PW: the offset from the tile's first
+    // sample) are consecutive in ONE plane — which one rotates from tile to tile, OWN_K being no multiple of PW.
     uint32_t slot_late = call.rec[ri].slot;
     asm volatile("" : "+s"(slot_late));  // keeps the loads below from being hoisted above stage 1
     float *__restrict__ f_out = slots[slot_late].f;
+    const uint32_t f_stride = slots[slot_late].f_stride;  // (never 0 here: run_call sets the slot's layout per call)
     if (interior) {
-        // every owned sample exists: whole 16-byte stores at a scalar base advanced in scalar registers plus the
-        // lane's 32-bit offset (as the tile loads), no per-lane 64-bit address arithmetic
+        // every owned sample exists: per run 16-byte stores at a scalar base advanced in scalar registers plus the
+        // lane's 32-bit offset (as the tile loads), no per-lane 64-bit address arithmetic.  A run starts wherever the
+        // tile's first sample falls in its plane: the stores are 4-byte aligned only (measured: the
+        // kernel's HBM writes grow by 0.5 %, and 16-byte ALIGNED stores with a head and a tail are no faster —
+        // profiles/r15_f_planes.txt, tools/probes/patches/f_store_aligned.patch).  The LDS side is the same two two-address reads per store as a contiguous copy takes,
+        // their offsets PW words apart instead of one.
         APT_MARK("BEGIN f_store");
         typedef char __attribute__((address_space(1))) *gchar_wptr;
-        typedef f4 __attribute__((address_space(1))) *gfloat4_wptr;
-        gchar_wptr sb = (gchar_wptr)(f_out + o0);
+        typedef f4 __attribute__((aligned(4))) f4u;
+        typedef f4u __attribute__((address_space(1))) *gfloat4_wptr;
+        typedef float __attribute__((address_space(1))) *gfloat_wptr;
+        // o0 = tile OWN_K as PW q0 + r0, in 32-bit scalar arithmetic (a 64-bit division would go through the vector ALU):
+        // OWN_K = PW A + B and tile = PW tq + tm give q0 = tile A + tq B + (tm B) / PW, r0 = (tm B) % PW
+        constexpr uint32_t A = Gm::OWN_K / PW, B = Gm::OWN_K % PW;
+        const uint32_t tile32 = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(tile));  // (< 2^32 tiles: w < 2^43)
+        const uint32_t tq = tile32 / PW, tm = tile32 - tq * PW;
+        const uint64_t q0 = static_cast<uint64_t>(tile32) * A + static_cast<uint64_t>(tq) * B + (tm * B) / PW;
+        uint32_t r0 = (tm * B) % PW;
+        // (opaque: knowing r0 < PW the compiler turns (r0 + d) / PW below into a compare whose 0 / 1 it materialises in a
+        // vector register, and the runs' bases with it)
+        asm volatile("" : "+s"(r0));
         const uint32_t voff = static_cast<uint32_t>(tid) * 16u;
+        // the runs' bases (scalar) and their whole-workgroup passes, then what is left of each run in the first waves
+        gchar_wptr sbase[PW];
+        static_for<0, PW>([&](auto dd) {
+            constexpr int d = decltype(dd)::value;
+            constexpr int NQ = (Gm::OWN_K - d + PW - 1) / PW / 4;  // whole 16-byte stores of this run
+            const uint32_t rd = r0 + d, wq = rd / PW;  // (the run that wraps to plane 0 starts one index further on)
+            sbase[d] = (gchar_wptr)(f_out + static_cast<uint64_t>(rd - wq * PW) * f_stride + (q0 + wq));
+            asm volatile("" : "+s"(sbase[d]));
 #pragma unroll
-        for (int e = 0; e * kFusedThreads * 4 < Gm::OWN_K; ++e) {
-            const int q = (tid + e * kFusedThreads) * 4;
-            // (PRE_K is odd: the LDS side is four 4-byte-aligned words, read as two two-address reads)
-            if (q < Gm::OWN_K) {
-                const float *src = P + Gm::PRE_K + q;
-                *(gfloat4_wptr)(sb + voff) = (f4){src[0], src[1], src[2], src[3]};
+            for (int e = 0; e < NQ / kFusedThreads; ++e) {
+                const float *src = P + Gm::PRE_K + d + 4 * PW * (tid + e * kFusedThreads);
+                *(gfloat4_wptr)(sbase[d] + voff) = (f4){src[0], src[PW], src[2 * PW], src[3 * PW]};
+                sbase[d] += kFusedThreads * 16;
+                asm volatile("" : "+s"(sbase[d]));
             }
-            sb += kFusedThreads * 16;
-            asm volatile("" : "+s"(sb));
-        }
+        });
+        static_for<0, PW>([&](auto dd) {
+            constexpr int d = decltype(dd)::value;
+            constexpr int N = (Gm::OWN_K - d + PW - 1) / PW;  // samples of this run
+            constexpr int NQ = N / 4, TAIL = N % 4;           // whole 16-byte stores, and what one more thread stores singly
+            constexpr int FULL = NQ / kFusedThreads;          // passes done above
+            constexpr int LEFT = NQ % kFusedThreads + (TAIL ? 1 : 0), WAVES = (LEFT + 63) / 64;
+            if constexpr (LEFT > 0) {
+                // (wave-uniform: a scalar branch for the waves that have nothing left to store)
+                if (WAVES * 64 >= kFusedThreads || __builtin_amdgcn_readfirstlane(tid) < WAVES * 64) {
+                    const int t = tid + FULL * kFusedThreads;
+                    const float *src = P + Gm::PRE_K + d + 4 * PW * t;
+                    if (t < NQ) {
+                        *(gfloat4_wptr)(sbase[d] + voff) = (f4){src[0], src[PW], src[2 * PW], src[3 * PW]};
+                    } else if (TAIL != 0 && t == NQ) {
+#pragma unroll
+                        for (int c = 0; c < TAIL; ++c) ((gfloat_wptr)(sbase[d] + voff))[c] = src[c * PW];
+                    }
+                }
+            }
+        });
         APT_MARK("END f_store");
     } else {
-        float *ft = f_out + o0;
-        for (int q = tid * 4; q < Gm::OWN_K; q += kFusedThreads * 4) {
-            if (Gm::PRE_K + q + 3 < k_hi) {
-                const float *src = P + Gm::PRE_K + q;
-                *reinterpret_cast<float4 *>(ft + q) = make_float4(src[0], src[1], src[2], src[3]);
-            } else {
-                for (int e = 0; e < 4; ++e)
-                    if (Gm::PRE_K + q + e < k_hi) ft[q + e] = P[Gm::PRE_K + q + e];
-            }
-        }
+        // first and last tiles: sample by sample through the index map
+        for (int q = tid; q < Gm::OWN_K; q += kFusedThreads)
+            if (Gm::PRE_K + q < k_hi) f_out[f_index(static_cast<uint64_t>(o0) + q, PW, f_stride)] = P[Gm::PRE_K + q];
     }
     if constexpr (APT_FUSED_STOP == 5) return;
     // ---- stage 4: sync cross-correlation (decode.rs:225-233) -> per-group bounds of its maximum.

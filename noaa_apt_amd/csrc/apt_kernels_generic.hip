@@ -347,7 +347,10 @@ k_orbit_walk(const uint64_t *__restrict__ bits, const float *__restrict__ corr, 
 // to 4160 Hz (decode.rs:158-159 -> filter([1.]) + decimate(pw), dsp.rs:106-116):
 //   px[r*2080 + c] = 0.0 + F[peaks[r] + pw*c] * 1.0,  and px[0] = 0 (the `i > j` guard).
 // ---------------------------------------------------------------------------------
-__device__ __forceinline__ void gather_rows_body(const float *__restrict__ f, const uint32_t *__restrict__ peaks,
+// f_stride: the layout of F (f_index): in pixel-phase planes the pixels of a row are consecutive floats of the plane
+// peaks[r] % pw, from index peaks[r] / pw on — a quad is one 16-byte load, 4-byte aligned only.
+typedef float f4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+__device__ __forceinline__ void gather_rows_body(const float *__restrict__ f, uint32_t f_stride, const uint32_t *__restrict__ peaks,
                                                  Result *__restrict__ res, uint32_t spr, uint32_t pw, int raw,
                                                  float *__restrict__ rows, uint32_t rows_cap)
 {
@@ -370,12 +373,20 @@ __device__ __forceinline__ void gather_rows_body(const float *__restrict__ f, co
     // pixel in the one-pixel-per-thread form this replaces, 5 now.
     const bool quads = (px_per_row & 3u) == 0 && (reinterpret_cast<uintptr_t>(rows) & 15u) == 0;
     for (uint32_t r = blockIdx.y; r < n_rows; r += gridDim.y) {
-        const float *src = f + peaks[r];
+        // (planes: the row's run; contiguous: its first sample, the pixels pw apart)
+        const float *src = f + f_index(peaks[r], pw, f_stride);
+        const uint32_t step = f_stride ? 1u : pw;
         float *dst = rows + static_cast<uint64_t>(r) * px_per_row;
         if (quads) {
             for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < px_per_row / 4u; k += gridDim.x * blockDim.x) {
-                const float *p4 = src + static_cast<uint64_t>(4u * k) * pw;
-                float4 v = make_float4(p4[0], p4[pw], p4[2u * pw], p4[3u * pw]);
+                const float *p4 = src + static_cast<uint64_t>(4u * k) * step;
+                float4 v;
+                if (f_stride) {
+                    const f4_a4 u = *reinterpret_cast<const f4_a4 *>(p4);
+                    v = make_float4(u.x, u.y, u.z, u.w);
+                } else {
+                    v = make_float4(p4[0], p4[pw], p4[2u * pw], p4[3u * pw]);
+                }
                 if (!raw) {  // filter([1.]): sum = 0.0 + x*1.0, and nothing at all for i == 0
                     v.x = __fadd_rn(0.f, __fmul_rn(v.x, 1.f));
                     v.y = __fadd_rn(0.f, __fmul_rn(v.y, 1.f));
@@ -389,7 +400,7 @@ __device__ __forceinline__ void gather_rows_body(const float *__restrict__ f, co
         }
         for (uint32_t c = blockIdx.x * blockDim.x + threadIdx.x; c < px_per_row;
              c += gridDim.x * blockDim.x) {
-            float v = src[static_cast<uint64_t>(c) * pw];
+            float v = src[static_cast<uint64_t>(c) * step];
             if (!raw) {  // filter([1.]): sum = 0.0 + x*1.0, and nothing at all for i == 0
                 v = __fadd_rn(0.f, __fmul_rn(v, 1.f));
                 if (r == 0 && c == 0) v = 0.f;
@@ -404,7 +415,7 @@ k_gather_rows(const float *__restrict__ f, const uint32_t *__restrict__ peaks,
               Result *__restrict__ res, uint32_t spr, uint32_t pw, int raw,
               float *__restrict__ rows, uint32_t rows_cap)
 {
-    gather_rows_body(f, peaks, res, spr, pw, raw, rows, rows_cap);
+    gather_rows_body(f, 0u, peaks, res, spr, pw, raw, rows, rows_cap);  // (the step exports: contiguous F)
 }
 
 // the recordings of one call: blockIdx.z picks the recording
@@ -413,7 +424,7 @@ k_gather_rows_call(const CallArgs call, const SlotPtrs *__restrict__ slots, uint
 {
     const RecArgs rec = call.rec[blockIdx.z];
     const SlotPtrs sp = slots[rec.slot];
-    gather_rows_body(sp.f, sp.peaks, sp.res, spr, pw, 0, rec.rows, rec.rows_cap);
+    gather_rows_body(sp.f, sp.f_stride, sp.peaks, sp.res, spr, pw, 0, rec.rows, rec.rows_cap);
 }
 
 // The same rows with the (row, pixel quad) pairs of a recording as ONE flat index walked by a fixed number of
@@ -438,13 +449,22 @@ k_gather_rows_flat(const CallArgs call, const SlotPtrs *__restrict__ slots, uint
         }
     }
     const float *__restrict__ f = sp.f;
+    const uint32_t f_stride = sp.f_stride;  // (workgroup-uniform: one of the two loads below per launch and recording)
     const uint32_t *__restrict__ peaks = sp.peaks;
     float *__restrict__ rows = rec.rows;
     const uint32_t total = n_rows * QPR;  // < 2^32: rows_cap <= 32768 rows of 520 quads
     for (uint32_t q = blockIdx.x * kBlock + threadIdx.x; q < total; q += gridDim.x * kBlock) {
         const uint32_t r = q / QPR, k = q - r * QPR;
-        const float *p4 = f + peaks[r] + static_cast<uint64_t>(4u * k) * pw;
-        float4 v = make_float4(p4[0], p4[pw], p4[2u * pw], p4[3u * pw]);
+        float4 v;
+        if (f_stride) {
+            // planes: the quad is four consecutive floats of the row's plane (one 16-byte load, 4-byte aligned only)
+            const uint32_t pk = peaks[r], pq = pk / pw;
+            const f4_a4 u = *reinterpret_cast<const f4_a4 *>(f + static_cast<uint64_t>(pk - pq * pw) * f_stride + pq + 4u * k);
+            v = make_float4(u.x, u.y, u.z, u.w);
+        } else {
+            const float *p4 = f + peaks[r] + static_cast<uint64_t>(4u * k) * pw;
+            v = make_float4(p4[0], p4[pw], p4[2u * pw], p4[3u * pw]);
+        }
         // filter([1.]): sum = 0.0 + x*1.0 (x*1.0 is x; the addition turns -0.0 into +0.0), and nothing at all for i == 0
         v.x = __fadd_rn(0.f, __fmul_rn(v.x, 1.f));
         v.y = __fadd_rn(0.f, __fmul_rn(v.y, 1.f));
@@ -466,13 +486,16 @@ k_nosync_rows_call(const CallArgs call, const SlotPtrs *__restrict__ slots, uint
 {
     const RecArgs rec = call.rec[blockIdx.y];
     const float *__restrict__ f = slots[rec.slot].f;
+    const uint32_t f_stride = slots[rec.slot].f_stride;
+    const uint32_t pw = spr / 2080u;  // F's planes (f_index): every m2-th sample is plane 0's run where m2 == pw
     const uint64_t aligned = rec.w / spr * spr;
     uint64_t n_out = aligned / m2;
     if (n_out > rec.rows_cap) n_out = rec.rows_cap;
     const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
     for (uint64_t k = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; k < n_out; k += stride) {
         const uint64_t i = k * m2;
-        rec.rows[k] = i < 1 ? 0.f : __fadd_rn(0.f, __fmul_rn(f[i], 1.f));
+        const uint64_t at = !f_stride ? i : (m2 == pw ? k : f_index(i, pw, f_stride));
+        rec.rows[k] = i < 1 ? 0.f : __fadd_rn(0.f, __fmul_rn(f[at], 1.f));
     }
     if (blockIdx.x == 0 && threadIdx.x == 0)
         *slots[rec.slot].res = Result{0 /* APTGPU_OK */, 0, static_cast<uint32_t>(n_out / 2080u), 0, rec.w, n_out};

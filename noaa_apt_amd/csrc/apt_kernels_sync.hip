@@ -253,6 +253,7 @@ k_sync_words(const CallArgs call, const SlotPtrs *__restrict__ slots, uint32_t p
     const GroupMax *__restrict__ gm = sp.gm;
     const float *__restrict__ corr = use_corr ? sp.corr : nullptr;  // nullptr: re-evaluate from F
     const float *__restrict__ fsig = sp.f;
+    const uint32_t f_stride = sp.f_stride;  // F's layout (f_index): 0 contiguous, else pixel-phase planes of this length
     uint32_t *__restrict__ flags = sp.flags;
 
     // groups [g0, g0 + CG) are the workgroup's own; bounds are needed up to R groups ahead.  LDS is sized
@@ -288,6 +289,8 @@ k_sync_words(const CallArgs call, const SlotPtrs *__restrict__ slots, uint32_t p
     }
     APT_WMARK("BEGIN coarse");
     static_assert(!LEAN || (DPP && NL > 0 && PWC > 0), "the lean form builds on the DPP scans and the register-held windows");
+    static_assert(PWC == 0 || NL == 0 || 64u * NL >= nodes_window(PWC) + PWC - 1,
+                  "an interior window loaded from up to PWC - 1 samples early (F in planes) still covers the window");
     if constexpr (LEAN) {
         // coarse: WM[q] = max(lo[q+1 .. q+W]), W = R-1, by the two-block method over blocks of 64 entries: P[i] =
         // max(lo[block start .. i]) and S[i] = max(lo[i .. block end]), each one DPP prefix scan of a wave (S: of the
@@ -371,16 +374,48 @@ k_sync_words(const CallArgs call, const SlotPtrs *__restrict__ slots, uint32_t p
     constexpr uint16_t kDeferred = 0x8000u;  // s_cand entry: to be settled in the second pass
     float *wa = s_win + static_cast<size_t>(wave) * wlen;  // this wave's F window
     const uint32_t wneed = GS + 38u * pw - 1u;  // samples of a window
+    // word offsets of the samples lane + 64 t behind a window base that is a multiple of pw (interior window loads)
+    [[maybe_unused]] uint32_t plane_ofs[NLR];
+#pragma unroll
+    for (int t = 0; t < NLR; ++t) {
+        const uint32_t tw = static_cast<uint32_t>(lane) + 64u * t;
+        plane_ofs[t] = f_stride ? (tw % pw) * f_stride + tw / pw : tw;
+    }
     // F window of the group at `base` -> wa -> its correlation values
     // (INT: an interior chunk, `base` wave-uniform in a scalar register — the whole padded window lies inside F)
     auto eval_group = [&](auto int_tag, uint64_t base, bool on) -> float {
         if constexpr (decltype(int_tag)::value) {
-            const float *__restrict__ fb = fsig + base;
-            for (uint32_t t = lane; t < wlen; t += 64) wa[t] = fb[t];
+            if constexpr (NL > 0) {
+                // the fine pass's load: 64 NL unpredicated samples from the multiple of pw at or below the window's first
+                // sample (planes; b0 samples early, dropped here) or from the window's first sample (contiguous)
+                const uint64_t bq = f_stride ? base / pw : base;
+                const uint32_t b0 = f_stride ? static_cast<uint32_t>(base - bq * pw) : 0u;
+                const float *__restrict__ fb = fsig + bq;
+#pragma unroll
+                for (int t = 0; t < NL; ++t) {
+                    const float v = fb[plane_ofs[t]];
+                    const uint32_t tw = static_cast<uint32_t>(lane) + 64u * t - b0;  // (unsigned: wraps past wlen)
+                    if (tw < wlen) wa[tw] = v;
+                }
+            } else if (f_stride == 0) {
+                const float *__restrict__ fb = fsig + base;
+                for (uint32_t t = lane; t < wlen; t += 64) wa[t] = fb[t];
+            } else {
+                // planes: from the multiple of pw at or below the window's first sample on one base — a lane's plane and
+                // index are those of its offset from it — and the b0 samples in front of the window dropped
+                const uint64_t bq = base / pw;
+                const uint32_t b0 = static_cast<uint32_t>(base - bq * pw);
+                const float *__restrict__ fb = fsig + bq;
+                for (uint32_t t = lane; t < wlen + b0; t += 64) {
+                    const uint32_t q = t / pw;
+                    const float v = fb[static_cast<uint64_t>(t - q * pw) * f_stride + q];
+                    if (t >= b0) wa[t - b0] = v;
+                }
+            }
         } else {
             for (uint32_t t = lane; t < wlen; t += 64) {
                 const uint64_t j = base + t;
-                wa[t] = (t < wneed && j < w) ? fsig[j] : 0.f;
+                wa[t] = (t < wneed && j < w) ? fsig[f_index(j, pw, f_stride)] : 0.f;
             }
         }
         __builtin_amdgcn_wave_barrier();
@@ -515,6 +550,7 @@ k_sync_words(const CallArgs call, const SlotPtrs *__restrict__ slots, uint32_t p
             float cv[kBatch], c2v[kBatch];
             bool inv[kBatch];
             float fa[kBatch][NLR];
+            [[maybe_unused]] uint32_t b0v[kBatch];  // (interior, planes) samples the loaded window starts in front of the group
             APT_WMARK("BEGIN window-load");
 #pragma unroll
             for (int e = 0; e < kBatch; ++e) {
@@ -529,9 +565,15 @@ k_sync_words(const CallArgs call, const SlotPtrs *__restrict__ slots, uint32_t p
                 if constexpr (INT) {
                     // (corr == nullptr) unpredicated: 64 NL samples from the group's first lie inside F, and what lies
                     // past the window is never read back; an empty entry loads group 0's window and drops it
-                    const float *__restrict__ fb = fsig + static_cast<uint64_t>(g) * GS;
+                    // Planes: the window is loaded from the multiple of pw at or below the group's first sample, b0 samples
+                    // early, so that a lane's offsets (plane_ofs: plane and index of lane + 64 t) are the same for every
+                    // candidate and the base stays scalar; the b0 extra samples are dropped on the way to LDS.
+                    const uint64_t base = static_cast<uint64_t>(g) * GS;
+                    const uint64_t bq = f_stride ? base / pw : base;
+                    b0v[e] = f_stride ? static_cast<uint32_t>(base - bq * pw) : 0u;
+                    const float *__restrict__ fb = fsig + bq;
 #pragma unroll
-                    for (int t = 0; t < NL; ++t) fa[e][t] = fb[static_cast<uint32_t>(lane) + 64u * t];
+                    for (int t = 0; t < NL; ++t) fa[e][t] = fb[plane_ofs[t]];
                 } else if (corr != nullptr) {
                     if (inv[e]) {
                         cv[e] = corr[i];
@@ -541,7 +583,7 @@ k_sync_words(const CallArgs call, const SlotPtrs *__restrict__ slots, uint32_t p
 #pragma unroll
                     for (int t = 0; t < NL; ++t) {
                         const uint64_t j = static_cast<uint64_t>(g) * GS + lane + 64u * t;
-                        fa[e][t] = (qv[e] >= 0 && lane + 64u * t < wneed && j < w) ? fsig[j] : 0.f;
+                        fa[e][t] = (qv[e] >= 0 && lane + 64u * t < wneed && j < w) ? fsig[f_index(j, pw, f_stride)] : 0.f;
                     }
                 }
             }
@@ -553,9 +595,18 @@ k_sync_words(const CallArgs call, const SlotPtrs *__restrict__ slots, uint32_t p
                 if (corr == nullptr) {
                     // F window of the candidate group -> LDS -> its 52 correlation values
                     if constexpr (NL > 0) {
+                        if constexpr (INT) {
+                            // (unsigned: a lane in front of the group's first sample wraps past wlen)
+#pragma unroll
+                            for (int t = 0; t < NL; ++t) {
+                                const uint32_t tw = static_cast<uint32_t>(lane) + 64u * t - b0v[e];
+                                if (tw < wlen) wa[tw] = fa[e][t];
+                            }
+                        } else {
 #pragma unroll
                         for (int t = 0; t < NL; ++t)
                             if (lane + 64u * t < wlen) wa[lane + 64 * t] = fa[e][t];
+                        }
                         __builtin_amdgcn_wave_barrier();
                         cv[e] = nodes_eval_window<NL, PWC>(wa, inv[e], lane, pw, fast);
                         __builtin_amdgcn_wave_barrier();  // the window is dead from here on: wa is reused

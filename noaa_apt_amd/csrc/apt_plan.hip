@@ -396,9 +396,12 @@ aptgpu_plan *plan_create(const aptgpu_context *ctx, const aptgpu_settings &setti
     // workspace: one set of max_batch slots per stream
     plan->slots.resize(static_cast<size_t>(depth) * static_cast<size_t>(max_batch));
     const uint64_t w = plan->max_work_len;
+    // (F in pixel-phase planes where a k_fused instantiation writes it: pw planes of f_plane_stride floats)
+    plan->plane_stride = plan->writes_planes() ? gpu::f_plane_stride(w, plan->pw) : 0u;  // (then pw >= 1)
     for (auto &sl : plan->slots) {
         // (resampled / demodulated / correlation are only needed by the unfused kernels: allocated on first use)
-        sl.filtered.alloc(w + 64);
+        sl.filtered.alloc(std::max<uint64_t>(w, static_cast<uint64_t>(plan->pw) * plan->plane_stride) + 64);
+        sl.f_stride = plan->plane_stride;  // (what a call without step export leaves: run_call)
         if (sync) {
             sl.peaks.alloc(plan->max_rows + 2);
             const uint64_t ng = w / gpu::sync_group_size() + 2;
@@ -446,13 +449,13 @@ void aptgpu_plan::upload_slot_table()
         t.peaks = sl.peaks.ptr;
         t.res = d_results.ptr + k;
         t.peaks_cap = static_cast<uint32_t>(sl.peaks.count);
-        t.reserved = 0;
+        t.f_stride = sl.f_stride;
     }
     apt::hip_check(hipMemcpyAsync(d_slots.ptr, tab.data(), tab.size() * sizeof(apt::gpu::SlotPtrs),
                                   hipMemcpyHostToDevice, stream),
                    "hipMemcpy slot table");
     apt::gpu::FusedParams prm{};
-    if (fused == 1 || fused == 3 || fused == 4) {
+    if (writes_planes()) {
         prm.hs = d_taps_branch.ptr;
         prm.table = d_taps_any.ptr;
         prm.tab = table_geom;
@@ -574,18 +577,25 @@ void aptgpu_plan::run_call(int count, const Input *ins, float *const *d_rows, co
 
     const bool use_fused = fused != 0 && !keep_steps;
     const bool want_sync = sync && work_is_multiple;
-    if (!use_fused && sync) {
-        // the unfused kernels keep the full correlation; a fused plan that exports steps gets the
-        // buffers (and their entry in the slot table) on first use
-        bool grew = false;
+    // The layout of F this call leaves in its slots: pixel-phase planes from the k_fused instantiations, contiguous from
+    // k_fused_any and the unfused kernels (a fused plan that exports steps).  Every consumer reads it from the slot table.
+    const uint32_t f_stride = use_fused ? plane_stride : 0u;
+    {
+        bool changed = false;
         for (int i = 0; i < count; ++i) {
             Slot &sl = slots[static_cast<size_t>(slot0 + i)];
-            if (!sl.correlation.ptr) {
+            // the unfused kernels keep the full correlation; a fused plan that exports steps gets the
+            // buffers (and their entry in the slot table) on first use
+            if (!use_fused && sync && !sl.correlation.ptr) {
                 sl.correlation.alloc(max_work_len + 64);
-                grew = true;
+                changed = true;
+            }
+            if (sl.f_stride != f_stride) {
+                sl.f_stride = f_stride;
+                changed = true;
             }
         }
-        if (grew) {
+        if (changed) {
             sync_all();  // (no launch in flight may be reading the table while it is rewritten)
             upload_slot_table();
         }
@@ -659,7 +669,7 @@ void aptgpu_plan::run_call(int count, const Input *ins, float *const *d_rows, co
 
     const uint32_t t1 = static_cast<uint32_t>(taps_resample.size());
     const uint32_t t2 = static_cast<uint32_t>(taps_lowpass.size());
-    if (use_fused && (fused == 1 || fused == 3 || fused == 4)) {
+    if (use_fused && writes_planes()) {
         // 1-3 fused: resample -> envelope -> low-pass (-> correlation maxima) in one launch per input
         // kind (apt_kernels_fused.hip), behind the previous call's front end (see front_serial, apt_plan.hpp)
         hipStream_t fs = cur;
@@ -835,6 +845,9 @@ void aptgpu_plan::run_call(int count, const Input *ins, float *const *d_rows, co
         } else
         for (int i : live) {
             Slot &sl = slots[static_cast<size_t>(slot0 + i)];
+            // (the kernels below read F as one contiguous signal: step exports run unfused, and l2 > 1 — a work rate
+            // that is no multiple of 4160 Hz — has no k_fused instantiation)
+            if (sl.f_stride != 0) throw apt::Error{apt::ErrorKind::Internal, "no-sync tail: F is in pixel-phase planes"};
             const uint64_t w = wlen[static_cast<size_t>(i)];
             const uint64_t aligned = w / spr * spr;
             uint64_t n_out = out_len_nosync(w);

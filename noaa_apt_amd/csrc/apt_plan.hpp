@@ -196,10 +196,18 @@ struct aptgpu_plan {
         // k_fused_any or the unfused kernels) and whether it was the 16-bit PCM one (read_internal "fused_variant")
         int fused_variant = -1;
         bool fused_variant_i16 = false;
+        // layout of `filtered` as the slot's last call left it (apt::gpu::f_index): 0 contiguous, else the plane length —
+        // the k_fused instantiations write pixel-phase planes; k_fused_any, the unfused kernels and every step export do not
+        uint32_t f_stride = 0;
     };
     std::vector<Slot> slots;
     apt::DeviceBuffer<apt::gpu::SlotPtrs> d_slots;  // the slots' pointers, for the per-call launches
     apt::DeviceBuffer<apt::gpu::FusedParams> d_fused_params;  // parameters of the specialised front end
+    // Does this plan's front end write F in pixel-phase planes (apt::gpu::f_index)?  The k_fused instantiations do (SPLIT,
+    // TABLE and PHASE stage 1: fused 1, 3, 4); k_fused_any (2) and the unfused kernels (0) write it contiguously.  The ONE
+    // place that says so: the slots' buffer size, their f_stride and run_call's choice of front end all ask here.
+    bool writes_planes() const { return fused == 1 || fused == 3 || fused == 4; }
+    uint32_t plane_stride = 0;  // plane length of such a plan (f_plane_stride of max_work_len), else 0
     void upload_slot_table();                       // (re)writes d_slots + d_fused_params; synchronises plan->stream
     apt::DeviceBuffer<apt::gpu::Result> d_results;
     apt::DeviceBuffer<apt::gpu::ImageResult> d_image_results;  // one per slot, on first use
