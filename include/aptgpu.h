@@ -429,7 +429,7 @@ typedef struct aptgpu_image_result {
                                 (telemetry.rs:199-203), 3 no low bucket (misc.rs:172 panics),
                                 4 the decode before it failed, 5-8 the map overlay's limits
                                 (APTGPU_MAP_REASON_*), 9 APTGPU_PNG_REASON_CAPACITY, 10 APTGPU_SAT_REASON_SGP4,
-                                11 APTGPU_PROJECT_REASON_CAPACITY */
+                                11 APTGPU_PROJECT_REASON_CAPACITY, 12 APTGPU_COMPOSITE_REASON_PASS */
     uint32_t height;         /* rows of 2080 px */
     uint32_t telemetry_row;  /* best frame start, telemetry.rs:196,228-230 */
     float low, high;         /* the contrast limits used by map_signal_u8 */
@@ -756,6 +756,71 @@ int aptgpu_plan_process_device_image_project(aptgpu_plan *plan, int count, const
                                              const aptgpu_projection_settings *proj, uint8_t *const *d_out,
                                              const size_t *out_cap, const aptgpu_png_settings *png,
                                              uint8_t *const *d_png, const size_t *png_cap, char *err, size_t err_cap);
+
+/* ---- composite: several passes on one map grid ----
+ * A station records several passes a day; what follows their reprojection is one map of all of them.  Each of the
+ * 1 <= count <= APTGPU_COMPOSITE_MAX_PASSES passes is an unrotated swath image of its own height, gray or RGBA, with
+ * its own track and its own yaw / hscale / vscale; one aptgpu_projection_settings describes the shared grid, and its
+ * channel, sampling, grid_deg and grid_color apply to every pass.  Per output pixel every pass, in list order, goes
+ * through the reprojection above unchanged (the same kernel text, so a pass's sample c_p has aptgpu_project_image's
+ * bits) and also keeps its corrected off-nadir distance x_p.  Over the passes that cover the pixel:
+ *   APTGPU_COMPOSITE_FIRST    c_p of the first covering pass: the caller orders the passes by priority
+ *   APTGPU_COMPOSITE_NADIR    c_p of the covering pass with the smallest |x_p|, the lower index on an exact tie: the
+ *                             pass that saw the pixel with the least panoramic distortion
+ *   APTGPU_COMPOSITE_FEATHER  per channel (alpha too), in f64 and in pass order, v = sum(w_p c_p) / sum(w_p) with
+ *                             w_p = 456 - |x_p| (> 0 where a pass covers), the channel = floor(v + 0.5) clamped to u8
+ * No covering pass gives (0, 0, 0, 0).  The graticule is blended last and once, as the reprojection does.  The
+ * coverage plane, where asked for, holds the number of covering passes of every pixel (0..16), one byte each: the
+ * mask that tells "black" from "not seen".
+ * A pass whose own record carries a status fails the composite (a position count that differs from its height,
+ * APTGPU_MAP_REASON_COUNT; an SGP4 error, APTGPU_SAT_REASON_SGP4): the composite's record gets
+ * APTGPU_COMPOSITE_REASON_PASS, that pass's record keeps its own reason, and nothing is written.  An output capacity
+ * below width * height * 4 is APTGPU_PROJECT_REASON_CAPACITY.  The images are unrotated by contract: no entry point
+ * here takes a rotation. */
+#define APTGPU_COMPOSITE_FIRST 0
+#define APTGPU_COMPOSITE_NADIR 1
+#define APTGPU_COMPOSITE_FEATHER 2
+#define APTGPU_COMPOSITE_MAX_PASSES 16
+#define APTGPU_COMPOSITE_REASON_PASS 12 /* aptgpu_image_result.reason of the composite's record: a pass failed */
+typedef struct aptgpu_composite_settings {
+    uint32_t struct_size; /* sizeof(aptgpu_composite_settings) */
+    int32_t blend;        /* APTGPU_COMPOSITE_* */
+    uint32_t reserved;    /* 0 */
+} aptgpu_composite_settings;
+/* Host only: aptgpu_projection_fit for the union of the swaths of n_tracks tracks (counts[t] pairs each).  Every
+ * track's longitudes are unwrapped from the first track's first position, so passes on both sides of the antimeridian
+ * share one axis.  One track gives aptgpu_projection_fit's grid. */
+int aptgpu_projection_fit_many(const double *const *tracks, const size_t *counts, size_t n_tracks, double hscale,
+                               int kind, double step_deg, uint32_t max_width, aptgpu_projection_settings *out,
+                               char *err, size_t err_cap);
+/* Composites host images: images[p] holds heights[p] rows of 2080 px of channels[p] (1 or 4) bytes, sat_positions[p]
+ * its track (n_positions[p] = heights[p] pairs), map[p] its yaw / hscale / vscale (map and its entries nullable:
+ * 0, 1, 1).  output as aptgpu_project_image: *out is the RGBA grid or its PNG file.  coverage is nullable; otherwise
+ * *coverage receives proj->width * proj->height bytes.  Both are released with aptgpu_free.  count 0 or above 16, a
+ * null entry, an unknown blend or a non-zero reserved is APTGPU_ERR_INVALID before the device is touched. */
+int aptgpu_composite_images(const aptgpu_context *ctx, int count, const uint8_t *const *images,
+                            const uint32_t *heights, const int *channels, const double *const *sat_positions,
+                            const size_t *n_positions, const aptgpu_map_settings *const *map,
+                            const aptgpu_projection_settings *proj, const aptgpu_composite_settings *composite,
+                            int output, const aptgpu_png_settings *png, uint8_t **out, size_t *n_out,
+                            uint8_t **coverage, char *err, size_t err_cap);
+/* Device-resident: d_images[p] is what aptgpu_plan_process_device_image[_map] left for recording p of the last decode
+ * call (unrotated, heights[p] rows of capacity; the height itself is the recording's record's).  Exactly one of
+ * sat_positions / n_positions and orbit is given (arrays of count); with orbit a track is computed on the GPU and a
+ * pass's geometry defaults to its draw_map.  Each pass's track stage runs on its recording's stream; the composite
+ * launch runs on recording 0's behind one event per pass that ran elsewhere, without a host round trip.  d_out holds
+ * out_cap bytes (4-byte aligned), d_coverage (nullable) width * height bytes, d_png (nullable, png_cap bytes;
+ * aptgpu_png_bound(width, height, 4) always suffices) the PNG file of the grid.  After it,
+ * aptgpu_plan_image_results with a count of count + 1 returns the passes' records followed by the composite's (status,
+ * reason, height = the grid's, png_bytes). */
+int aptgpu_plan_composite_device_images(aptgpu_plan *plan, int count, const uint8_t *const *d_images,
+                                        const uint32_t *heights, const int *channels,
+                                        const double *const *sat_positions, const size_t *n_positions,
+                                        const aptgpu_orbit_settings *const *orbit,
+                                        const aptgpu_map_settings *const *map, const aptgpu_projection_settings *proj,
+                                        const aptgpu_composite_settings *composite, uint8_t *d_out, size_t out_cap,
+                                        uint8_t *d_coverage, const aptgpu_png_settings *png, uint8_t *d_png,
+                                        size_t png_cap, char *err, size_t err_cap);
 
 /* ---- despeckle: a band-aware median of the rows, in front of process() ----
  * The reference's to-do list names it (docs/development.md:139 "Investigate about despeckle") and has no code for it,

@@ -28,6 +28,8 @@ Names, argument meaning and error behaviour follow the reference:
     file of the image, encoded on the GPU
     process(projection=ProjectionSettings(...)),           the reference's to-do list, docs/development.md:112,99:
     project_image, projection_fit, Projection              the image on an equirectangular or Mercator grid
+    composite_images, Composite,                           what every APT user does next with reprojected passes:
+    Plan.composite_device_images                           several of them on one map grid
     despeckle, despeckle_host, DespeckleSettings,          the reference's to-do list, docs/development.md:139: a
     process(despeckle=...), Plan.despeckle_device          band-aware median of the f32 rows in front of process()
     percent, get_min, get_max, map_signal_u8               /root/reference/src/misc.rs:119, dsp.rs:20-54
@@ -49,6 +51,7 @@ from .api import (  # noqa: F401
     encode_png, png_bound, PNG_REASON_CAPACITY,
     DespeckleSettings, DespeckleResult, despeckle, despeckle_host,
     Projection, ProjectionSettings, projection_fit, project_image, PROJECT_REASON_CAPACITY,
+    Composite, composite_images, COMPOSITE_REASON_PASS, COMPOSITE_MAX_PASSES,
     SatName, RefTime, OrbitSettings, sat_track, sat_track_host, south_to_north_pass, SAT_REASON_SGP4,
     Plan, PlanInfo, Result, KernelTime, decode_batch, BatchStats, host_alloc_f32, host_free,
     lib, lib_path, use_library, build, device_count, version, abi_version, cache_clear, cache_info, host_affinity, host_affinity_from_sysfs,

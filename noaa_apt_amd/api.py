@@ -161,6 +161,11 @@ class _CProjectionSettings(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class _CCompositeSettings(C.Structure):
+    """aptgpu_composite_settings"""
+    _fields_ = [("struct_size", C.c_uint32), ("blend", C.c_int32), ("reserved", C.c_uint32)]
+
+
 class _CDespeckleSettings(C.Structure):
     """aptgpu_despeckle_settings"""
     _fields_ = [("struct_size", C.c_uint32), ("radius", C.c_int32), ("threshold", C.c_float)]
@@ -375,6 +380,15 @@ def lib():
                                                            cms, vp, C.POINTER(_f64p), C.POINTER(sz), C.POINTER(cos),
                                                            C.POINTER(vp), cpr, C.POINTER(vp), C.POINTER(sz), cps,
                                                            C.POINTER(vp), C.POINTER(sz), C.c_char_p, sz]
+    cco = C.POINTER(_CCompositeSettings)
+    L.aptgpu_projection_fit_many.argtypes = [C.POINTER(_f64p), C.POINTER(sz), sz, C.c_double, i32, C.c_double, u32, cpr,
+                                             C.c_char_p, sz]
+    L.aptgpu_composite_images.argtypes = [cp, i32, C.POINTER(_u8p), _u32p, i32p, C.POINTER(_f64p), C.POINTER(sz),
+                                          C.POINTER(cms), cpr, cco, i32, cps, C.POINTER(_u8p), C.POINTER(sz),
+                                          C.POINTER(_u8p), C.c_char_p, sz]
+    L.aptgpu_plan_composite_device_images.argtypes = [vp, i32, C.POINTER(vp), _u32p, i32p, C.POINTER(_f64p),
+                                                      C.POINTER(sz), C.POINTER(cos), C.POINTER(cms), cpr, cco, vp, sz,
+                                                      vp, cps, vp, sz, C.c_char_p, sz]
     cds = C.POINTER(_CDespeckleSettings)
     L.aptgpu_despeckle.argtypes = [cp, _f32p, sz, cds, C.POINTER(_f32p), C.POINTER(DespeckleResult), C.c_char_p, sz]
     L.aptgpu_despeckle_host.argtypes = [_f32p, sz, cds, C.POINTER(_f32p), C.POINTER(DespeckleResult), C.c_char_p, sz]
@@ -1187,10 +1201,22 @@ class ProjectionSettings:
 def projection_fit(sat_positions, kind=Projection.EQUIRECTANGULAR, step=None, max_width=None, hscale=1.0):
     """aptgpu_projection_fit (host only): a ProjectionSettings whose grid covers the swath of a track of (lat, lon)
     rows in radians, with `step` degrees per pixel or, without it, `max_width` columns.  Conservative, not tight:
-    the track's bounding box grown by the swath's half angle."""
-    pos = np.ascontiguousarray(np.asarray(sat_positions, dtype=np.float64).reshape(-1, 2))
+    the track's bounding box grown by the swath's half angle.  A list of tracks gives the grid of their union
+    (aptgpu_projection_fit_many), with longitudes unwrapped relative to the first track."""
     out = _CProjectionSettings()
     err = C.create_string_buffer(_ERRCAP)
+    if isinstance(sat_positions, (list, tuple)) and len(sat_positions) and np.ndim(sat_positions[0]) == 2:
+        # several tracks (aptgpu_projection_fit_many): the union box, longitudes unwrapped from the first track
+        tracks = [np.ascontiguousarray(np.asarray(t, dtype=np.float64).reshape(-1, 2)) for t in sat_positions]
+        k = len(tracks)
+        _check(lib().aptgpu_projection_fit_many((_f64p * k)(*[t.ctypes.data_as(_f64p) for t in tracks]),
+                                                (C.c_size_t * k)(*[len(t) for t in tracks]), k, float(hscale),
+                                                int(kind), float(step) if step is not None else 0.0,
+                                                int(max_width) if max_width is not None else 0, C.byref(out), err,
+                                                _ERRCAP), err)
+        return ProjectionSettings(out.kind, out.width, out.height, out.lat_north, out.lon_west, out.step, out.channel,
+                                  out.sampling, out.grid_deg)
+    pos = np.ascontiguousarray(np.asarray(sat_positions, dtype=np.float64).reshape(-1, 2))
     _check(lib().aptgpu_projection_fit(pos.ctypes.data_as(_f64p), len(pos), float(hscale), int(kind),
                                        float(step) if step is not None else 0.0,
                                        int(max_width) if max_width is not None else 0, C.byref(out), err, _ERRCAP), err)
@@ -1218,6 +1244,71 @@ def project_image(image, sat_positions, projection, settings=None, png=False, co
                                       C.byref(cps), C.byref(out), C.byref(n), err, _ERRCAP), err)
     data = _take(out, n.value, np.uint8)
     return data.tobytes() if png else data.reshape(projection.shape)
+
+
+COMPOSITE_REASON_PASS = 12  # ImageResult.reason of a composite's record: one of its passes failed
+COMPOSITE_MAX_PASSES = 16
+
+
+class Composite:
+    """How a composite chooses among the passes that cover a pixel (aptgpu_composite_settings.blend): the FIRST in
+    list order, the one nearest to its NADIR (smallest off-nadir distance |x|), or all of them FEATHERed with the
+    weights 456 - |x|."""
+    FIRST, NADIR, FEATHER = 0, 1, 2
+
+
+def _composite_passes(images):
+    """The images of a composite's passes as checked contiguous arrays."""
+    xs = []
+    for im in images:
+        x = np.ascontiguousarray(im)
+        if x.dtype != np.uint8 or x.ndim not in (2, 3) or x.shape[1] != PX_PER_ROW or (x.ndim == 3 and x.shape[2] != 4):
+            raise InvalidError("composite: every image is a uint8 array of (height, 2080) or (height, 2080, 4)")
+        xs.append(x)
+    return xs
+
+
+def _composite_maps(settings, projection, k):
+    ms = [settings] * k if settings is None or isinstance(settings, MapSettings) else list(settings)
+    if len(ms) != k or not all(m is None or isinstance(m, MapSettings) for m in ms):
+        raise InvalidError("settings: a MapSettings, or one (or None) per pass")
+    keep = [(m or projection.geometry or MapSettings())._c() for m in ms]
+    return (C.POINTER(_CMapSettings) * k)(*[C.pointer(c) for c in keep]), keep
+
+
+def composite_images(images, tracks, projection, blend=Composite.NADIR, settings=None, png=False,
+                     return_coverage=False, context=None):
+    """aptgpu_composite_images: up to 16 passes on one map grid.  images: unrotated (height, 2080) gray
+    or (height, 2080, 4) RGBA uint8 arrays, each of its own height; tracks: per image its (height, 2) positions (lat,
+    lon in radians); projection: the shared grid's ProjectionSettings (projection_fit accepts the list of tracks);
+    blend: a Composite value; settings: a MapSettings for every pass or a list of one per pass.  Returns the
+    (grid height, grid width, 4) RGBA array, or with png=True the PNG file's bytes; with return_coverage also the
+    (grid height, grid width) uint8 count of the passes that cover each pixel."""
+    if not isinstance(projection, ProjectionSettings):
+        raise InvalidError("projection must be a ProjectionSettings")
+    k = len(images)
+    if len(tracks) != k:
+        raise InvalidError("composite: one track per image")
+    xs = _composite_passes(images)
+    pos = [np.ascontiguousarray(np.asarray(t, dtype=np.float64).reshape(-1, 2)) for t in tracks]
+    maps, keep = _composite_maps(settings, projection, k)
+    cctx = (context or Context())._c()
+    cpr, cps = projection._c(), _CPngSettings(C.sizeof(_CPngSettings), 0)
+    cco = _CCompositeSettings(C.sizeof(_CCompositeSettings), int(blend), 0)
+    out, n, cov = _u8p(), C.c_size_t(), _u8p()
+    err = C.create_string_buffer(_ERRCAP)
+    _check(lib().aptgpu_composite_images(
+        C.byref(cctx), k, (_u8p * k)(*[x.ctypes.data_as(_u8p) for x in xs]),
+        (C.c_uint32 * k)(*[x.shape[0] for x in xs]), (C.c_int32 * k)(*[4 if x.ndim == 3 else 1 for x in xs]),
+        (_f64p * k)(*[p.ctypes.data_as(_f64p) for p in pos]), (C.c_size_t * k)(*[len(p) for p in pos]), maps,
+        C.byref(cpr), C.byref(cco), 1 if png else 0, C.byref(cps), C.byref(out), C.byref(n),
+        C.byref(cov) if return_coverage else None, err, _ERRCAP), err)
+    del keep
+    data = _take(out, n.value, np.uint8)
+    data = data.tobytes() if png else data.reshape(projection.shape)
+    if return_coverage:
+        return data, _take(cov, projection.width * projection.height, np.uint8).reshape(projection.shape[:2])
+    return data
 
 
 def _process_image_project(context, signal, contrast_adjustment, rotate, color, return_info, orbit, layers, png,
@@ -1752,6 +1843,50 @@ class Plan:
             (C.c_void_p * k)(*d_png) if png is not None else None,
             (C.c_size_t * k)(*[int(c) for c in png_cap]) if png is not None else None, err, _ERRCAP), err)
         del keep
+
+    def composite_device_images(self, d_images: Sequence[int], heights: Sequence[int], channels: Sequence[int],
+                                projection, d_out: int, out_cap: int, tracks=None, orbit=None,
+                                blend=Composite.NADIR, settings=None, d_coverage=None, png=None):
+        """aptgpu_plan_composite_device_images: the composite (composite_images) of the images that
+        process_device_image left on the device for the first len(d_images) recordings of the last decode_device
+        call, chained on the device.  heights[i] is the row capacity of d_images[i] (the height itself is the
+        recording's record's), channels[i] 1 or 4.  tracks: one (height, 2) array per pass, or orbit: an OrbitSettings
+        or one per pass (exactly one of the two).  d_out holds out_cap bytes (width * height * 4 are needed), d_coverage
+        (optional) width * height bytes, png = (d_png, png_cap) (optional) the PNG file of the grid.
+        image_results(len(d_images) + 1) then returns the passes' records followed by the composite's: a pass that
+        failed shows its own reason there and COMPOSITE_REASON_PASS on the composite's, and nothing is written."""
+        if not isinstance(projection, ProjectionSettings):
+            raise InvalidError("projection must be a ProjectionSettings")
+        k = len(d_images)
+        if len(heights) != k or len(channels) != k:
+            raise InvalidError("composite: one height and one channel count per image")
+        if (tracks is None) == (orbit is None):
+            raise InvalidError("a composite needs the tracks: exactly one of tracks and orbit")
+        pos = npos = ptrs = keep = None
+        if orbit is not None:
+            orbits = [orbit] * k if isinstance(orbit, OrbitSettings) else list(orbit)
+            if len(orbits) != k or not all(isinstance(o, OrbitSettings) for o in orbits):
+                raise InvalidError("orbit: an OrbitSettings or one per pass")
+            keep = [o._c() for o in orbits]
+            ptrs = (C.POINTER(_COrbitSettings) * k)(*[C.pointer(c) for c, _ in keep])
+        else:
+            keep = [np.ascontiguousarray(np.asarray(t, dtype=np.float64).reshape(-1, 2)) for t in tracks]
+            if len(keep) != k:
+                raise InvalidError("tracks: one sat_positions array per pass")
+            pos = (_f64p * k)(*[t.ctypes.data_as(_f64p) for t in keep])
+            npos = (C.c_size_t * k)(*[len(t) for t in keep])
+        maps, keep_maps = _composite_maps(settings, projection, k)
+        if settings is None and projection.geometry is None and orbit is not None:
+            maps = None  # (each pass's geometry is then its orbit's draw_map, or 0, 1, 1)
+        cpr, cps = projection._c(), _CPngSettings(C.sizeof(_CPngSettings), 0)
+        cco = _CCompositeSettings(C.sizeof(_CCompositeSettings), int(blend), 0)
+        d_png, png_cap = png if png is not None else (None, 0)
+        err = C.create_string_buffer(_ERRCAP)
+        _check(lib().aptgpu_plan_composite_device_images(
+            self._p, k, (C.c_void_p * k)(*d_images), (C.c_uint32 * k)(*[int(h) for h in heights]),
+            (C.c_int32 * k)(*[int(c) for c in channels]), pos, npos, ptrs, maps, C.byref(cpr), C.byref(cco),
+            d_out, int(out_cap), d_coverage, C.byref(cps), d_png, int(png_cap), err, _ERRCAP), err)
+        del keep, keep_maps
 
     @staticmethod
     def _maps(map, k):  # noqa: A002

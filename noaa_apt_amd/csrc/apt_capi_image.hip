@@ -43,6 +43,7 @@ const char *kMapCount = "map overlay: the number of satellite positions differs 
 const char *kSatSgp4 = "satellite track: SGP4 failed for a row of the image (APTGPU_SAT_REASON_SGP4)";
 const char *kPngCapacity = "PNG encoding: the output buffer is smaller than the file (APTGPU_PNG_REASON_CAPACITY)";
 const char *kProjectCapacity = "reprojection: the output buffer is smaller than width * height * 4 bytes (APTGPU_PROJECT_REASON_CAPACITY)";
+const char *kCompositePass = "composite: a pass failed, its position count differs from its height or SGP4 failed for a row (APTGPU_COMPOSITE_REASON_PASS)";
 const char *kChannelNames[9] = {"1", "2", "3a", "4", "5", "3b", "Unknown", "Unknown", "Unknown"};
 
 // Rust's `{}` for an f32: shortest decimal that round-trips, never in exponent form.
@@ -94,6 +95,7 @@ void throw_for(const ImageResult &r, int contrast)
     case apt::sat::kReasonSgp4: throw Error{ErrorKind::Internal, kSatSgp4};
     case apt::png::kReasonCapacity: throw Error{ErrorKind::Internal, kPngCapacity};
     case apt::project::kReasonCapacity: throw Error{ErrorKind::Internal, kProjectCapacity};
+    case apt::composite::kReasonPass: throw Error{ErrorKind::Internal, kCompositePass};
     default: throw Error{ErrorKind::Internal, "image stage failed"};
     }
     (void)contrast;
@@ -267,17 +269,22 @@ int extreme(const aptgpu_context *ctx, const float *signal, size_t n, float *out
     });
 }
 
+// yaw / hscale / vscale of one recording's geometry (nullable: 0, 1, 1)
+void geom_arg(Recording &r, const aptgpu_map_settings *map)
+{
+    if (!map) return;
+    if (map->struct_size < sizeof(aptgpu_map_settings))
+        throw Error{ErrorKind::Invalid, "aptgpu_map_settings: struct_size not set"};
+    r.geom = *map;
+}
+
 // The reprojection of one recording (the *_project entry points): the grid, its graticule and the yaw / hscale / vscale
 // of the geometry (`map`: the overlay's settings when one is drawn, nullable).
 void project_args(Recording &r, const aptgpu_projection_settings *proj, const aptgpu_map_settings *map)
 {
     r.grid = apt::project::checked(proj);
     r.flags = apt::project::graticule(r.grid, proj->grid_deg);
-    if (map) {
-        if (map->struct_size < sizeof(aptgpu_map_settings))
-            throw Error{ErrorKind::Invalid, "aptgpu_map_settings: struct_size not set"};
-        r.geom = *map;
-    }
+    geom_arg(r, map);
 }
 
 // The projection reads the unrotated image and north is up by construction.
@@ -368,6 +375,53 @@ void to_host(hipStream_t s, const uint8_t *d, size_t len, uint8_t **out, size_t 
     }
     *out = h;
     *n_out = len;
+}
+
+// The composite of `count` passes onto one grid (the *_composite_* entry points), every check before the device is
+// touched: the pass count, the settings struct, then per pass its image, its channels, its track (`positions` with
+// `n_positions`, or `orbit`: exactly one array is given) and its geometry (map and its entries nullable); the grid and
+// its graticule go to the first recording.  Fills q.rec, which it sizes, and the per-call part of q.comp.
+void composite_args(ImageRequest &q, int count, const uint8_t *const *images, const uint32_t *heights,
+                    const int *channels, const double *const *positions, const size_t *n_positions,
+                    const aptgpu_orbit_settings *const *orbit, const aptgpu_map_settings *const *map,
+                    const aptgpu_projection_settings *proj, const aptgpu_composite_settings *composite)
+{
+    if (count < 1 || count > APTGPU_COMPOSITE_MAX_PASSES)
+        throw Error{ErrorKind::Invalid, "a composite takes 1 to APTGPU_COMPOSITE_MAX_PASSES (16) passes"};
+    if (!composite || composite->struct_size < sizeof(aptgpu_composite_settings))
+        throw Error{ErrorKind::Invalid, "aptgpu_composite_settings: struct_size not set"};
+    if (composite->blend < APTGPU_COMPOSITE_FIRST || composite->blend > APTGPU_COMPOSITE_FEATHER)
+        throw Error{ErrorKind::Invalid, "aptgpu_composite_settings: unknown blend"};
+    if (composite->reserved) throw Error{ErrorKind::Invalid, "aptgpu_composite_settings: reserved must be 0"};
+    if (!images || !heights || !channels) throw Error{ErrorKind::Invalid, "composite: null images, heights or channels"};
+    if ((positions != nullptr) == (orbit != nullptr) || (positions && !n_positions))
+        throw Error{ErrorKind::Invalid, "a composite needs exactly one of sat_positions and aptgpu_orbit_settings"};
+    q.composite = true;
+    q.comp.blend = composite->blend;
+    q.rec.resize(static_cast<size_t>(count));
+    for (int i = 0; i < count; ++i) {
+        Recording &r = q.rec[static_cast<size_t>(i)];
+        if (!images[i] || heights[i] == 0) throw Error{ErrorKind::Invalid, "composite: a pass has no image or no row"};
+        channels_arg(channels[i]);
+        if (positions && !positions[i]) throw Error{ErrorKind::Invalid, "null sat_positions"};
+        if (orbit && !orbit[i]) throw Error{ErrorKind::Invalid, "aptgpu_orbit_settings: struct_size not set"};
+        const aptgpu_map_settings *m = map ? map[i] : nullptr;
+        if (i == 0)
+            project_args(r, proj, nullptr);
+        geom_arg(r, m ? m : (orbit ? orbit[i]->draw_map : nullptr));
+        r.channels = channels[i];
+        if (positions) {
+            r.track = Track::Positions;
+            r.positions = positions[i];
+            r.n_positions = n_positions[i];
+        }
+    }
+    // (SGP4 initialisation last: it is the only check with a cost)
+    if (orbit)
+        for (int i = 0; i < count; ++i) {
+            q.rec[static_cast<size_t>(i)].track = Track::Sat;
+            q.rec[static_cast<size_t>(i)].sat = orbit_args(orbit[i]).call;
+        }
 }
 
 // APTGPU_OUTPUT_*: whether the PNG file is asked for
@@ -1093,6 +1147,140 @@ int aptgpu_plan_process_device_image_project(aptgpu_plan *plan, int count, const
     });
 }
 
+int aptgpu_projection_fit_many(const double *const *tracks, const size_t *counts, size_t n_tracks, double hscale,
+                               int kind, double step_deg, uint32_t max_width, aptgpu_projection_settings *out,
+                               char *err, size_t err_cap)
+{
+    if (!tracks || !counts || !out) return APTGPU_ERR_INVALID;
+    for (size_t t = 0; t < n_tracks; ++t)
+        if (!tracks[t] && counts[t]) return APTGPU_ERR_INVALID;
+    return guarded(err, err_cap, [&] {
+        apt::project::fit_many(tracks, counts, n_tracks, hscale, kind, step_deg, max_width, out);
+        return APTGPU_OK;
+    });
+}
+
+int aptgpu_composite_images(const aptgpu_context *ctx, int count, const uint8_t *const *images,
+                            const uint32_t *heights, const int *channels, const double *const *sat_positions,
+                            const size_t *n_positions, const aptgpu_map_settings *const *map,
+                            const aptgpu_projection_settings *proj, const aptgpu_composite_settings *composite,
+                            int output, const aptgpu_png_settings *png, uint8_t **out, size_t *n_out,
+                            uint8_t **coverage, char *err, size_t err_cap)
+{
+    if (!out || !n_out) return APTGPU_ERR_INVALID;
+    *out = nullptr;
+    *n_out = 0;
+    if (coverage) *coverage = nullptr;
+    return guarded(err, err_cap, [&] {
+        // (every check before the device is touched)
+        ImageRequest q;
+        q.png = output_arg(output);
+        if (q.png) png_args(png);
+        if (!sat_positions) throw Error{ErrorKind::Invalid, "null sat_positions"};
+        composite_args(q, count, images, heights, channels, sat_positions, n_positions, nullptr, map, proj, composite);
+        const apt::project::Grid &g = q.rec[0].grid;
+        if (q.png) png_shape(g.width, g.height, 4);
+        const size_t k = static_cast<size_t>(count), pixels = static_cast<size_t>(g.width) * g.height;
+        std::vector<std::unique_ptr<apt::map::Device>> maps(k);  // (outlive the call's stream: ~Scratch synchronises it)
+        apt::composite::Device dev;
+        std::vector<ImageResult> recs(k);
+        Scratch sc(ctx);
+        hipStream_t s = sc.stream;
+        std::vector<apt::DeviceBuffer<uint8_t>> d_img(k);
+        apt::DeviceBuffer<uint8_t> d_grid, d_cov, d_png;
+        apt::DeviceBuffer<ImageResult> d_info;
+        q.comp.dev = &dev;
+        q.comp.out_cap = q.rec[0].grid_bytes();
+        if (q.png) q.comp.png_cap = apt::png::bound(g.width, g.height, 4);
+        d_grid.alloc(q.comp.out_cap + 16);
+        d_png.alloc(q.comp.png_cap);
+        if (coverage) d_cov.alloc(pixels);
+        d_info.alloc(k);
+        q.comp.d_out = d_grid.ptr;
+        q.comp.d_coverage = d_cov.ptr;
+        q.comp.d_png = d_png.ptr;
+        // every finished image as a job behind its colour stage, with a hand-made record
+        std::vector<ImageJob> jobs(k);
+        for (size_t i = 0; i < k; ++i) {
+            Recording &r = q.rec[i];
+            const size_t bytes = static_cast<size_t>(heights[i]) * 2080u * static_cast<size_t>(r.channels);
+            recs[i].height = heights[i];
+            recs[i].channel_a = recs[i].channel_b = -1;
+            recs[i].n_px = static_cast<uint64_t>(heights[i]) * 2080u;
+            maps[i] = std::make_unique<apt::map::Device>();
+            d_img[i].alloc(bytes + 16);
+            apt::hip_check(hipMemcpyAsync(d_img[i].ptr, images[i], bytes, hipMemcpyHostToDevice, s), "hipMemcpyAsync H2D");
+            r.d_image = d_img[i].ptr;
+            jobs[i].stream = s;
+            jobs[i].cap = recs[i].n_px;
+            jobs[i].info = d_info.ptr + i;
+            jobs[i].map = maps[i].get();
+        }
+        apt::hip_check(hipMemcpyAsync(d_info.ptr, recs.data(), k * sizeof(ImageResult), hipMemcpyHostToDevice, s),
+                       "hipMemcpyAsync H2D");
+        apt::enqueue_image_outputs(nullptr, q, jobs.data(), count);
+        apt::hip_check(hipGetLastError(), "kernel launch (composite)");
+        const ImageResult res = ImageCall::read(s, dev.info);
+        throw_for(res, APTGPU_CONTRAST_MINMAX);
+        if (coverage) {
+            size_t n_cov = 0;
+            to_host(s, d_cov.ptr, pixels, coverage, &n_cov);
+        }
+        try {
+            if (q.png)
+                to_host(s, d_png.ptr, res.reserved, out, n_out);
+            else
+                to_host(s, d_grid.ptr, q.comp.out_cap, out, n_out);
+        } catch (...) {
+            if (coverage) {
+                std::free(*coverage);
+                *coverage = nullptr;
+            }
+            throw;
+        }
+        return APTGPU_OK;
+    });
+}
+
+int aptgpu_plan_composite_device_images(aptgpu_plan *plan, int count, const uint8_t *const *d_images,
+                                        const uint32_t *heights, const int *channels,
+                                        const double *const *sat_positions, const size_t *n_positions,
+                                        const aptgpu_orbit_settings *const *orbit,
+                                        const aptgpu_map_settings *const *map, const aptgpu_projection_settings *proj,
+                                        const aptgpu_composite_settings *composite, uint8_t *d_out, size_t out_cap,
+                                        uint8_t *d_coverage, const aptgpu_png_settings *png, uint8_t *d_png,
+                                        size_t png_cap, char *err, size_t err_cap)
+{
+    return guarded(err, err_cap, [&] {
+        ImageRequest q;
+        q.png = d_png != nullptr;
+        if (q.png) png_args(png);
+        composite_args(q, count, d_images, heights, channels, sat_positions, n_positions, orbit, map, proj, composite);
+        if (q.png) png_shape(q.rec[0].grid.width, q.rec[0].grid.height, 4);
+        if (!plan) return APTGPU_ERR_INVALID;
+        if (!d_out || (reinterpret_cast<uintptr_t>(d_out) & 3u))
+            throw Error{ErrorKind::Invalid, "d_out must be non-null and 4-byte aligned"};
+        if (static_cast<size_t>(count) > plan->last_slots.size())
+            throw Error{ErrorKind::Invalid, "count exceeds the recordings of the last decode call"};
+        if (!plan->d_image_results.ptr)
+            throw Error{ErrorKind::Invalid, "composite: no image stage has run on this plan (aptgpu_plan_process_device_image first)"};
+        for (int i = 0; i < count; ++i) {
+            Recording &r = q.rec[static_cast<size_t>(i)];
+            if (r.channels == 4 && (reinterpret_cast<uintptr_t>(d_images[i]) & 3u))
+                throw Error{ErrorKind::Invalid, "d_images must be 4-byte aligned for channels = 4"};
+            r.d_image = const_cast<uint8_t *>(d_images[i]);
+        }
+        q.comp.d_out = d_out;
+        q.comp.out_cap = out_cap;
+        q.comp.d_coverage = d_coverage;
+        q.comp.d_png = d_png;
+        q.comp.png_cap = png_cap;
+        apt::hip_check(hipSetDevice(plan->device), "hipSetDevice");
+        plan->enqueue_composite(q, count, heights);
+        return APTGPU_OK;
+    });
+}
+
 int aptgpu_map_layers_create(aptgpu_map_layers **out)
 {
     if (!out) return APTGPU_ERR_INVALID;
@@ -1281,11 +1469,18 @@ int aptgpu_plan_despeckle_results(aptgpu_plan *plan, int count, aptgpu_despeckle
 int aptgpu_plan_image_results(aptgpu_plan *plan, int count, aptgpu_image_result *results)
 {
     if (!plan || count < 0 || (!results && count)) return APTGPU_ERR_INVALID;
+    // one record past the passes of the latest composite: the composite's own
+    const bool with_composite = plan->composite_count >= 0 && count == plan->composite_count + 1;
+    if (with_composite) --count;
     if (static_cast<size_t>(count) > plan->last_slots.size() || !plan->d_image_results.ptr)
         return APTGPU_ERR_INVALID;
     try {
         apt::hip_check(hipSetDevice(plan->device), "hipSetDevice");
         plan->sync_all();
+        if (with_composite)
+            apt::hip_check(hipMemcpy(results + count, plan->composite[static_cast<size_t>(plan->last_stream)]->info,
+                                     sizeof(aptgpu_image_result), hipMemcpyDeviceToHost),
+                           "hipMemcpy");
         for (int i = 0; i < count; ++i)
             apt::hip_check(hipMemcpy(results + i,
                                      plan->d_image_results.ptr + plan->last_slots[static_cast<size_t>(i)],

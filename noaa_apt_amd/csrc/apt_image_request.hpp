@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "apt_kernels_color.hpp"
+#include "apt_kernels_composite.hpp"
 #include "apt_kernels_map.hpp"
 #include "apt_kernels_project.hpp"
 #include "apt_kernels_track.hpp"
@@ -30,6 +31,15 @@ struct ImageRequest {
     const apt::map::Layers *layers = nullptr;
     bool project = false;  // the image goes through the reprojection onto every recording's grid
     bool png = false;      // the output is the PNG file of the image (of the grid with a projection)
+    // The recordings are the passes of one composite: each one's track stage runs, then one launch
+    // combines them onto rec[0]'s grid (with its graticule) into `comp`'s destinations.  Excludes `project`.
+    bool composite = false;
+    struct Composite {
+        int blend = APTGPU_COMPOSITE_NADIR;
+        apt::composite::Device *dev = nullptr;  // the plan's, or the one-shot call's
+        uint8_t *d_out = nullptr, *d_coverage = nullptr, *d_png = nullptr;  // (coverage nullable; d_png with `png`)
+        size_t out_cap = 0, png_cap = 0;
+    } comp;
     enum class Track { None, Positions, Sat };
     struct Recording {
         bool rotate = false;  // (Rotate::Orbit resolved)
@@ -38,6 +48,7 @@ struct ImageRequest {
         size_t n_positions = 0;
         apt::sat::TrackCall sat{};          // Track::Sat: the track is computed on the device
         aptgpu_map_settings geom{sizeof(aptgpu_map_settings), 0, 0., 1., 1.};  // yaw / hscale / vscale
+        int channels = 0;                   // with `composite`: this pass's source, 1 or 4 (the passes may differ)
         apt::project::Grid grid{};          // with `project`, and its graticule
         std::vector<uint8_t> flags;
         uint64_t grid_bytes() const { return static_cast<uint64_t>(grid.width) * grid.height * 4u; }
@@ -72,7 +83,8 @@ void enqueue_image_limits(aptgpu_plan *plan, const ImageJob &j, int contrast, fl
 // Equalisation and colour of one job, behind its limits.
 void enqueue_image_color(aptgpu_plan *plan, const ImageRequest &q, const ImageRequest::Recording &r, const ImageJob &j);
 // What follows the colour, stage by stage and job by job within a stage: the overlay, then the reprojection (behind
-// its track when no overlay left one) or the PNG.
+// its track when no overlay left one) or the PNG; or, for a composite, every pass's track and then the one launch of
+// all of them on the first job's stream, behind one event per pass that ran elsewhere.
 void enqueue_image_outputs(aptgpu_plan *plan, const ImageRequest &q, const ImageJob *jobs, int count);
 
 }  // namespace apt

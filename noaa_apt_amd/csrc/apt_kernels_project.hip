@@ -19,6 +19,7 @@
 #include "apt_kernels_project.hpp"
 
 #include "apt_kernels_map_dev.hpp"
+#include "apt_kernels_project_dev.hpp"
 #include "apt_kernels_png.hpp"
 
 #include <cstring>
@@ -33,31 +34,6 @@ using apt::gpu::ImageResult;
 using apt::map::kPi;
 using apt::map::kSkip;
 using apt::map::Scalars;
-
-constexpr int kTileW = 64, kTileH = 4;
-constexpr int kThreads = kTileW * kTileH;
-constexpr int kPx = 2080;
-
-// one source pixel as RGBA; neighbour indices are clamped to the band's pixels, x in [-455, 455], y in [0, h - 1]
-__device__ inline uint32_t fetch(const uint8_t *src, int channels, int base, int h, int x, int y)
-{
-    x = x < -455 ? -455 : (x > 455 ? 455 : x);
-    y = y < 0 ? 0 : (y > h - 1 ? h - 1 : y);
-    const size_t at = static_cast<size_t>(y) * kPx + static_cast<size_t>(x + base);
-    if (channels == 4) return reinterpret_cast<const uint32_t *>(src)[at];
-    const uint32_t g = src[at];
-    return g | (g << 8) | (g << 16) | 0xff000000u;
-}
-
-// (p00 (1 - fx) + p10 fx) (1 - fy) + (p01 (1 - fx) + p11 fx) fy of one channel, then (u8) floor(v + 0.5)
-__device__ inline uint32_t lerp_u8(uint32_t p00, uint32_t p10, uint32_t p01, uint32_t p11, int shift, double fx, double fy)
-{
-    const double a = static_cast<double>((p00 >> shift) & 255u), b = static_cast<double>((p10 >> shift) & 255u);
-    const double c = static_cast<double>((p01 >> shift) & 255u), d = static_cast<double>((p11 >> shift) & 255u);
-    const double v = (a * (1. - fx) + b * fx) * (1. - fy) + (c * (1. - fx) + d * fx) * fy;
-    const double r = floor(v + 0.5);
-    return (r >= 255. ? 255u : (r > 0. ? static_cast<uint32_t>(r) : 0u)) << shift;
-}
 
 __global__ __launch_bounds__(kThreads) void k_project(Grid g, Scalars sc_host, const Scalars *scp, const double *xoff,
                                                       const uint32_t *ctl, ImageResult *info, const uint8_t *src,
@@ -85,20 +61,9 @@ __global__ __launch_bounds__(kThreads) void k_project(Grid g, Scalars sc_host, c
     if (s_why != 0) return;  // (uniform per workgroup)
     const Scalars sc = scp ? *scp : sc_host;
     if (tid < kTileH) {
-        const double i = static_cast<double>(blockIdx.y * kTileH + tid);
-        const double lat = g.kind == APTGPU_PROJECTION_MERCATOR ? atan(sinh(g.y_north - i * g.step_rad))
-                                                                : (g.lat_north - i * g.step) / 180. * kPi;
-        s_row[tid][0] = sin(lat);
-        s_row[tid][1] = cos(lat);
-        s_row[tid][2] = tan(lat);
+        row_terms(g, blockIdx.y * kTileH + tid, s_row[tid]);
     } else if (tid >= 64 && tid < 64 + kTileW) {
-        const uint32_t c = tid - 64;
-        const double j = static_cast<double>(blockIdx.x * kTileW + c);
-        const double lon = (g.lon_west + j * g.step) / 180. * kPi;
-        const double dl = lon - sc.start_lon, dl2 = sc.start_lon - lon;
-        s_col[c][0] = sin(dl);
-        s_col[c][1] = cos(dl);
-        s_col[c][2] = cos(dl2);
+        col_terms(g, blockIdx.x * kTileW + (tid - 64), sc.start_lon, s_col[tid - 64]);
     } else if (tid == 128) {
         s_start[0] = sin(sc.start_lat);
         s_start[1] = cos(sc.start_lat);
@@ -106,32 +71,9 @@ __global__ __launch_bounds__(kThreads) void k_project(Grid g, Scalars sc_host, c
     __syncthreads();
     const uint32_t i = blockIdx.y * kTileH + threadIdx.y, j = blockIdx.x * kTileW + threadIdx.x;
     if (i >= g.height || j >= g.width) return;
-    double x, y, dist;
-    apt::map::rel_px_from(sc, s_start[0], s_start[1], s_row[threadIdx.y][0], s_row[threadIdx.y][1], s_row[threadIdx.y][2],
-                          s_col[threadIdx.x][0], s_col[threadIdx.x][1], s_col[threadIdx.x][2], x, y, dist);
-    const uint32_t h = info->height;
-    uint32_t px = 0;
-    bool valid = h != 0 && isfinite(x) && isfinite(y);
-    if (valid) {
-        x -= xoff[apt::map::est_row(y, h)];
-        valid = isfinite(x) && x > -456. && x < 456. && y > 0. && y < static_cast<double>(h) && dist < kPi / 3.;
-    }
-    if (valid) {
-        const int base = g.channel == APTGPU_PROJECTION_CHANNEL_B ? 1579 : 539, hi = static_cast<int>(h);
-        if (g.sampling == APTGPU_SAMPLING_BILINEAR) {
-            const double x0 = floor(x), y0 = floor(y);
-            const double fx = x - x0, fy = y - y0;
-            const int xi = static_cast<int>(x0), yi = static_cast<int>(y0);
-            const uint32_t p00 = fetch(src, src_channels, base, hi, xi, yi);
-            const uint32_t p10 = fetch(src, src_channels, base, hi, xi + 1, yi);
-            const uint32_t p01 = fetch(src, src_channels, base, hi, xi, yi + 1);
-            const uint32_t p11 = fetch(src, src_channels, base, hi, xi + 1, yi + 1);
-            px = lerp_u8(p00, p10, p01, p11, 0, fx, fy) | lerp_u8(p00, p10, p01, p11, 8, fx, fy) |
-                 lerp_u8(p00, p10, p01, p11, 16, fx, fy) | lerp_u8(p00, p10, p01, p11, 24, fx, fy);
-        } else {
-            px = fetch(src, src_channels, base, hi, static_cast<int>(floor(x + 0.5)), static_cast<int>(floor(y + 0.5)));
-        }
-    }
+    double x;
+    uint32_t px = 0;  // (stays 0 where the swath does not cover the pixel)
+    sample_pass(g, sc, s_start, s_row[threadIdx.y], s_col[threadIdx.x], xoff, info->height, src, src_channels, x, px);
     // a row and a column that cross are blended once
     if (g.graticule && (flags[j] | flags[g.width + i])) px = apt::map::blend(px, g.grid_color);
     out[static_cast<size_t>(i) * g.width + j] = px;

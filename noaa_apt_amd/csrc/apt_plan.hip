@@ -561,6 +561,7 @@ void aptgpu_plan::run_call(int count, const Input *ins, float *const *d_rows, co
     const int slot0 = last_stream * max_batch;
     last_slots.assign(static_cast<size_t>(count), 0);
     for (int i = 0; i < count; ++i) last_slots[static_cast<size_t>(i)] = slot0 + i;
+    composite_count = -1;
     // the call's stream waits for what is already enqueued on ctx.stream (inputs may be produced there)
     if (user_stream) {
         apt::hip_check(hipEventRecord(ev_user, user_stream), "hipEventRecord");
@@ -1043,6 +1044,24 @@ void aptgpu_plan::enqueue_images(const apt::ImageRequest &q, int count, const fl
     apt::enqueue_image_outputs(this, q, jobs.data(), count);
 }
 
+void aptgpu_plan::enqueue_composite(apt::ImageRequest &q, int count, const uint32_t *heights)
+{
+    if (composite.size() < streams.size()) composite.resize(streams.size());
+    std::unique_ptr<apt::composite::Device> &dev = composite[static_cast<size_t>(last_stream)];
+    if (!dev) dev = std::make_unique<apt::composite::Device>();
+    q.comp.dev = dev.get();
+    std::vector<apt::ImageJob> jobs(static_cast<size_t>(count));
+    for (int i = 0; i < count; ++i) {
+        const ImageTarget t = image_target(i, static_cast<uint64_t>(heights[i]) * 2080u);
+        if (!t.slot.map) t.slot.map = std::make_unique<apt::map::Device>();
+        apt::ImageJob &j = jobs[static_cast<size_t>(i)];
+        j = image_job(t, nullptr);
+        j.map = t.slot.map.get();
+    }
+    composite_count = count;
+    apt::enqueue_image_outputs(this, q, jobs.data(), count);
+}
+
 namespace apt {
 
 using Recording = ImageRequest::Recording;
@@ -1094,15 +1113,17 @@ static void enqueue_image_overlay(aptgpu_plan *plan, const ImageRequest &q, cons
     stage_done(plan, "kernel launch (map overlay)");
 }
 
-// (an overlay left the track's x offsets and scalars in the job's map device; without one they are computed first)
-static void enqueue_image_project(aptgpu_plan *plan, const ImageRequest &q, const Recording &r, const ImageJob &j)
+// The track's x offsets and scalars in the job's map device, for a consumer that inverts the geometry (an overlay left
+// them there; without one they are computed first).  Returns the host-fed form's scalars.
+static apt::map::Scalars enqueue_image_track(aptgpu_plan *plan, const ImageRequest &q, const Recording &r,
+                                             const ImageJob &j, const char *name)
 {
     const bool sat = r.track == ImageRequest::Track::Sat;
     apt::map::Scalars sc{};
     if (!sat) sc = apt::map::scalars(r.positions, r.n_positions, r.geom.yaw, r.geom.hscale, r.geom.vscale);
     if (!q.overlay) {
         j.map->prepare_track(j.stream, j.cap / 2080u);
-        launch_timed(plan, j.stream, "image_project_track", [&] {
+        launch_timed(plan, j.stream, name, [&] {
             if (sat) {
                 apt::map::image_map_track_sat(j.stream, *j.map, r.sat, r.geom.yaw, r.geom.hscale, r.geom.vscale, j.info);
             } else {
@@ -1111,6 +1132,13 @@ static void enqueue_image_project(aptgpu_plan *plan, const ImageRequest &q, cons
             }
         });
     }
+    return sc;
+}
+
+static void enqueue_image_project(aptgpu_plan *plan, const ImageRequest &q, const Recording &r, const ImageJob &j)
+{
+    const bool sat = r.track == ImageRequest::Track::Sat;
+    const apt::map::Scalars sc = enqueue_image_track(plan, q, r, j, "image_project_track");
     j.project->upload_flags(j.stream, r.flags);
     launch_timed(plan, j.stream, "image_project", [&] {
         apt::project::image_project(j.stream, *j.project, *j.map, sat ? nullptr : &sc, r.grid, r.d_image, q.channels,
@@ -1139,13 +1167,50 @@ static void enqueue_image_png(aptgpu_plan *plan, const ImageRequest &q, const Re
     stage_done(plan, "kernel launch (PNG encoder)");
 }
 
+// The composite of the request's passes: every pass's track stage on its own job's stream, the pass
+// table through the composite's pinned staging buffer, then the one launch (and the PNG of the grid) on the first
+// job's stream behind an event per pass that ran on another.
+static void enqueue_image_composite(aptgpu_plan *plan, const ImageRequest &q, const ImageJob *jobs, int count)
+{
+    using apt::composite::Pass;
+    apt::composite::Device &dev = *q.comp.dev;
+    hipStream_t s = jobs[0].stream;
+    const apt::project::Grid &g = q.rec[0].grid;
+    Pass table[apt::composite::kMaxPasses] = {};
+    for (int i = 0; i < count; ++i) {
+        const Recording &r = q.rec[static_cast<size_t>(i)];
+        const ImageJob &j = jobs[i];
+        Pass &p = table[i];
+        p.sc = enqueue_image_track(plan, q, r, j, "image_composite_track");
+        p.scp = r.track == ImageRequest::Track::Sat ? j.map->scalars : nullptr;
+        p.xoff = j.map->xoff;
+        p.ctl = j.map->ctl;
+        p.info = j.info;
+        p.src = r.d_image;
+        p.channels = r.channels;
+        apt::composite::wait_for_pass(s, dev, i, j.stream);
+    }
+    dev.upload_table(s, table, count);
+    dev.grid.upload_flags(s, q.rec[0].flags);
+    launch_timed(plan, s, "image_composite", [&] {
+        apt::composite::image_composite(s, dev, count, q.comp.blend, g, q.comp.d_out, q.comp.out_cap, q.comp.d_coverage);
+    });
+    if (q.png)
+        launch_timed(plan, s, "image_composite_png", [&] {
+            apt::project::image_project_png(s, dev.grid, g, q.comp.d_out, q.comp.d_png, q.comp.png_cap, dev.info);
+        });
+    stage_done(plan, "kernel launch (composite)");
+}
+
 void enqueue_image_outputs(aptgpu_plan *plan, const ImageRequest &q, const ImageJob *jobs, int count)
 {
     auto each = [&](auto stage) {
         for (int i = 0; i < count; ++i) stage(plan, q, q.rec[static_cast<size_t>(i)], jobs[i]);
     };
     if (q.overlay) each(enqueue_image_overlay);
-    if (q.project)
+    if (q.composite)
+        enqueue_image_composite(plan, q, jobs, count);
+    else if (q.project)
         each(enqueue_image_project);
     else if (q.png)
         each(enqueue_image_png);

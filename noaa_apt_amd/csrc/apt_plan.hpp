@@ -241,6 +241,14 @@ struct aptgpu_plan {
     // whose scratch is allocated on first use and whose palette / Lab tables are uploaded once per generation
     // (set_palette first), then the launches of apt_image_request.hpp.
     void enqueue_images(const apt::ImageRequest &q, int count, const float *const *d_rows, const size_t *rows_cap);
+    // The composite (aptgpu_plan_composite_device_images) of the finished images of the first `count` recordings of
+    // the last call: one ImageJob per pass from its slot (heights[i] rows of capacity; the height is the slot's
+    // record's), the plan's composite device as the request's, then the launches of apt_image_request.hpp.  The
+    // composite's record is the one past the passes' in aptgpu_plan_image_results.
+    void enqueue_composite(apt::ImageRequest &q, int count, const uint32_t *heights);
+    // per stream (calls in flight never share one): pass table, graticule, record and PNG scratch, on first use
+    std::vector<std::unique_ptr<apt::composite::Device>> composite;
+    int composite_count = -1;  // passes of the latest composite (-1: none since the last decode call)
     // The despeckle stage (apt_kernels_despeckle.hpp) of recording i, behind its decode on the same stream: the 98 %
     // limits of d_rows when threshold != 0 (into the slot's image scratch, which the image stage behind it rewrites),
     // then one k_despeckle launch into d_out (same capacity, no overlap).  The record stays in the slot.

@@ -87,28 +87,43 @@ std::vector<uint8_t> graticule(const Grid &g, double grid_deg)
 void fit(const double *track, size_t count, double hscale, int kind, double step_deg, uint32_t max_width,
          aptgpu_projection_settings *out)
 {
+    fit_many(&track, &count, 1, hscale, kind, step_deg, max_width, out);
+}
+
+void fit_many(const double *const *tracks, const size_t *counts, size_t n_tracks, double hscale, int kind,
+              double step_deg, uint32_t max_width, aptgpu_projection_settings *out)
+{
     auto bad = [](const char *msg) { throw Error{ErrorKind::Invalid, std::string("aptgpu_projection_fit: ") + msg}; };
     if (kind != APTGPU_PROJECTION_EQUIRECTANGULAR && kind != APTGPU_PROJECTION_MERCATOR) bad("unknown kind");
-    if (count == 0) bad("the track is empty");
+    if (n_tracks == 0) bad("no track");
+    for (size_t t = 0; t < n_tracks; ++t)
+        if (counts[t] == 0) bad("the track is empty");
+    const double *track = tracks[0];
     if (!std::isfinite(hscale) || !(hscale > 0.)) bad("hscale must be finite and > 0");
     const bool by_step = step_deg > 0.;
     if (by_step ? !std::isfinite(step_deg) : max_width < 2) bad("give a step > 0 or a maximum width of at least 2");
     double lat_min = track[0], lat_max = track[0], lon = track[1], lon_min = lon, lon_max = lon;
     double abs_max = std::fabs(track[0]);
-    for (size_t r = 0; r < count; ++r) {
-        const double lat = track[2 * r];
-        if (!std::isfinite(lat) || !std::isfinite(track[2 * r + 1])) bad("the track holds a non-finite position");
-        if (r) {
-            double d = std::fmod(track[2 * r + 1] - track[2 * r - 1], 2. * kPi);
-            if (d > kPi) d -= 2. * kPi;
-            if (d < -kPi) d += 2. * kPi;
-            lon += d;
+    for (size_t t = 0; t < n_tracks; ++t) {
+        track = tracks[t];
+        for (size_t r = 0; r < counts[t]; ++r) {
+            const double lat = track[2 * r];
+            if (!std::isfinite(lat) || !std::isfinite(track[2 * r + 1])) bad("the track holds a non-finite position");
+            if (r || t) {
+                // a later track starts from the first track's first longitude: one unwrapped axis for all of them
+                const double from = r ? track[2 * r - 1] : tracks[0][1];
+                if (!r) lon = from;
+                double d = std::fmod(track[2 * r + 1] - from, 2. * kPi);
+                if (d > kPi) d -= 2. * kPi;
+                if (d < -kPi) d += 2. * kPi;
+                lon += d;
+            }
+            lat_min = std::fmin(lat_min, lat);
+            lat_max = std::fmax(lat_max, lat);
+            lon_min = std::fmin(lon_min, lon);
+            lon_max = std::fmax(lon_max, lon);
+            abs_max = std::fmax(abs_max, std::fabs(lat));
         }
-        lat_min = std::fmin(lat_min, lat);
-        lat_max = std::fmax(lat_max, lat);
-        lon_min = std::fmin(lon_min, lon);
-        lon_max = std::fmax(lon_max, lon);
-        abs_max = std::fmax(abs_max, std::fabs(lat));
     }
     const double half = 456. * 0.0005 / hscale;  // the swath's half angle (map.rs:64, the band of map.rs:116-121)
     const double lat_cap = (kind == APTGPU_PROJECTION_MERCATOR ? 85. : 90.) / 180. * kPi;

@@ -39,5 +39,9 @@ std::vector<uint8_t> graticule(const Grid &g, double grid_deg);
 // aptgpu_projection_fit: a grid that covers the swath of `track` (count pairs lat, lon in radians).  Conservative.
 void fit(const double *track, size_t count, double hscale, int kind, double step_deg, uint32_t max_width,
          aptgpu_projection_settings *out);
+// aptgpu_projection_fit_many: the same for the union of several tracks' swaths, every track's longitudes unwrapped
+// from the first track's first position.  One track gives fit()'s grid.
+void fit_many(const double *const *tracks, const size_t *counts, size_t n_tracks, double hscale, int kind,
+              double step_deg, uint32_t max_width, aptgpu_projection_settings *out);
 
 }  // namespace apt::project

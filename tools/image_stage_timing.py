@@ -21,6 +21,11 @@ shape (16 recordings x 600 s at 48 kHz, 1198 rows each, one decode_device call),
                       sizes for the track at 0.04 degrees per pixel, nearest sampling
     project_bilinear  the same, bilinear
     project_nearest_png, project_bilinear_png   the same + the PNG encoder on the projected grid
+    composite_nadir   color_rgba + the composite of the 16 recordings, their tracks 1.5 degrees of
+                      longitude apart, onto the one grid projection_fit sizes for all of them at 0.04 degrees per
+                      pixel, nearest sampling, NADIR, with the coverage plane: image_composite is ONE launch per call
+                      (its row is ms per call, not per recording) beside project_nearest's 16 image_project launches
+    composite_feather the same, FEATHER
     despeckle_r1_t0, despeckle_r1_t01, despeckle_r2_t0, despeckle_r2_t01
                       the despeckle stage (radius 1 / 2, threshold 0 / 0.1: image_despeckle, and
                       image_percent when the threshold needs the 98 % limits) into a second rows buffer, then
@@ -155,6 +160,18 @@ def main():
             projection=(grids[sampling], ptr(d_grid), [grid_bytes] * RECORDINGS),
             png=(ptr(d_grid_png), grid_png_cap) if with_png else None)
 
+    shifted = [pos + np.array([0.0, np.radians(1.5 * i)]) for i in range(RECORDINGS)]
+    cfit = apt.projection_fit(shifted, apt.Projection.EQUIRECTANGULAR, step=0.04)
+    d_comp = torch.empty(cfit.width * cfit.height * 4, dtype=torch.uint8, device=dev)
+    d_cov = torch.empty(cfit.width * cfit.height, dtype=torch.uint8, device=dev)
+
+    def composite(blend):
+        def call():
+            plan.process_device_image(ptr(d_rows), caps, apt.Contrast.MINMAX, ptr(d_img), color=color)
+            plan.composite_device_images(ptr(d_img), caps, [4] * RECORDINGS, cfit, d_comp.data_ptr(), d_comp.numel(),
+                                         tracks=shifted, blend=blend, d_coverage=d_cov.data_ptr())
+        return call
+
     d_dsp = [torch.empty(cap * 2080, dtype=torch.float32, device=dev) for _ in range(RECORDINGS)]
 
     def despeckle(radius, threshold):
@@ -168,6 +185,8 @@ def main():
         "despeckle_r1_t01": despeckle(1, 0.1),
         "despeckle_r2_t0": despeckle(2, 0.0),
         "despeckle_r2_t01": despeckle(2, 0.1),
+        "composite_nadir": composite(apt.Composite.NADIR),
+        "composite_feather": composite(apt.Composite.FEATHER),
         "project_nearest": project(apt.Projection.NEAREST, False),
         "project_bilinear": project(apt.Projection.BILINEAR, False),
         "project_nearest_png": project(apt.Projection.NEAREST, True),
@@ -216,6 +235,9 @@ def main():
           f"recording), {args.calls} calls per variant; ms per recording")
     if any(k.startswith("project_") for k in variants):
         print(f"project_*: grid {fit.width} x {fit.height} = {fit.width * fit.height / 1e6:.2f} Mpx per recording")
+    if any(k.startswith("composite_") for k in variants):
+        print(f"composite_*: one grid {cfit.width} x {cfit.height} = {cfit.width * cfit.height / 1e6:.2f} Mpx for all "
+              f"{RECORDINGS} recordings; image_composite's row is ms per call (one launch)")
     print(f"{'variant':18s} {'kernel':20s} {'ms/rec':>8s}   (launches)")
     for name, call in variants.items():
         for _ in range(3):  # warm-up: code objects, first-use allocations, palette upload
