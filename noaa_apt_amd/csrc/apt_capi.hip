@@ -107,7 +107,7 @@ int aptgpu_plan_get_info(const aptgpu_plan *plan, aptgpu_plan_info *info)
     info->max_samples = plan->max_samples;
     info->max_work_len = plan->max_work_len;
     info->max_rows = plan->max_rows;
-    info->fused = plan->fused;
+    info->fused = plan->fused();
     info->max_batch = plan->max_batch;
     return APTGPU_OK;
 }
@@ -564,7 +564,7 @@ int decode_host(const aptgpu_context *ctx_in, const aptgpu_settings *settings, c
             stats->m = plan->m;
             stats->n_resample_taps = static_cast<uint32_t>(plan->taps_resample.size());
             stats->n_lowpass_taps = static_cast<uint32_t>(plan->taps_lowpass.size());
-            stats->fused = plan->fused;
+            stats->fused = plan->fused();
             stats->orbit_path = 1;
         }
         return APTGPU_OK;
@@ -771,7 +771,6 @@ int aptgpu_find_sync(const aptgpu_context *ctx, const float *signal, size_t n,
             d_cnt.alloc(chunks);
             d_flags.alloc(32);
             apt::hip_check(hipMemsetAsync(d_flags.ptr, 0, 32 * sizeof(uint32_t), sc.stream), "hipMemsetAsync");
-            const char *fw = std::getenv("APTGPU_FORCE_WALK");
             apt::DeviceBuffer<uint32_t> d_ws;
             d_ws.alloc(apt::gpu::sync_orbit_ws_words(n, spr));
             // a one-recording "call" over a one-entry slot table
@@ -802,7 +801,7 @@ int aptgpu_find_sync(const aptgpu_context *ctx, const float *signal, size_t n,
             apt::gpu::group_max(sc.stream, d_c.ptr, n_corr, d_gm.ptr);
             const apt::gpu::LaunchSwitches sw = apt::gpu::read_launch_switches();  // (once per API call)
             apt::gpu::sync_nodes(sc.stream, call, d_sp.ptr, n, pw, spr, md, false, true, sw);
-            apt::gpu::sync_orbit(sc.stream, call, d_sp.ptr, spr, md, pw, (fw && fw[0] == '1') ? 1 : 0, sw);
+            apt::gpu::sync_orbit(sc.stream, call, d_sp.ptr, spr, md, pw, apt::gpu::read_plan_switches().force_walk == '1' ? 1 : 0, sw);  // (no plan here: the same reader)
             apt::hip_check(hipGetLastError(), "kernel launch (find_sync)");
             apt::hip_check(hipStreamSynchronize(sc.stream), "hipStreamSynchronize");
         }

@@ -7,6 +7,8 @@
 
 #include <cstdint>
 
+#include "apt_front_end.hpp"
+
 namespace apt::gpu {
 
 // Device-side result record == aptgpu_result (include/aptgpu.h).
@@ -146,71 +148,21 @@ void gather_rows_call(hipStream_t s, const CallArgs &call, const SlotPtrs *d_slo
 void nosync_rows_call(hipStream_t s, const CallArgs &call, const SlotPtrs *d_slots, uint32_t spr, uint32_t m2, uint64_t max_w);
 
 // ---- fused specialised front end (apt_kernels_fused.hip) --------------------------
-// true when a <L, M, T1, T2, PW> specialisation exists
-bool fused_supported(uint32_t l, uint32_t m, uint32_t t1, uint32_t t2, uint32_t pw);
-uint32_t fused_group_size(uint32_t l);
-// does the specialisation for these factors take mono PCM16 payloads as they are (else they are converted to f32 first)?
-bool fused_takes_pcm16(uint32_t l, uint32_t m);
 // host: stage-1 tap-pair table [WIN][PS][2] (see apt_kernels_fused.hip) and its size in floats
 uint32_t fused_tap_table_floats(uint32_t l, uint32_t m, uint32_t t1, int ch);
 void fused_branch_taps(uint32_t l, uint32_t m, const float *coeff, uint32_t t1, int ch, float *hs, uint32_t t1_layout = 0);
-// kModeStrictPad (mode 4 of fused_front_end): the tap-count bound of the padded strict kernel that serves (l, m, t1, t2, pw),
-// or 0 where there is none (then t1 must match a kernel exactly: fused_supported)
-uint32_t fused_pad_t1(uint32_t l, uint32_t m, uint32_t t1, uint32_t t2, uint32_t pw);
-// kModeStrictPad2: the low-pass bound of the padded kernel when t2 is not the profile's own (a tuned demodulation_atten:
-// h2 / h2p must then be laid out for that many taps, zeros behind the filter's last), else 0
-uint32_t fused_pad_t2(uint32_t l, uint32_t m, uint32_t t2, uint32_t pw);
-// ... and of the PHASE kernels (fused_phase_supported accepts such a t2 at the standard profile's pixel width): 0 = t2 is
-// the profile's own or beyond the bound
-uint32_t fused_phase_pad_t2(uint32_t t2, uint32_t pw);
 int fused_chunk_of(uint32_t m, bool fast);  // window samples per stage-1 chunk of the specialised kernel for (m, strict / fast)
 // host: stage-3 tap pairs h2p[k] = (h2[k-1], h2[k]), k = 0 .. t2  (2*(t2+1) floats)
 void fused_lowpass_pairs(const float *h2, uint32_t t2, float *h2p);
 // fp16-tap stage 1 (APTGPU_MODE_FP16_TAPS): table size in dwords, host-side table builder (returns
-// the power-of-two unscale factor), availability
+// the power-of-two unscale factor)
 uint32_t fused_f16_table_dwords(uint32_t l, uint32_t m, uint32_t t1);
 float fused_f16_branch_taps(uint32_t l, uint32_t m, const float *coeff, uint32_t t1, uint32_t *table);
-bool fused_f16_supported(uint32_t l, uint32_t m, uint32_t t1, uint32_t t2, uint32_t pw);
 // strict front ends: |pulse-sum correlation - sequential chain| <= fused_gm_slack(pw) * sum|F| (see stage 4)
 float fused_gm_slack(uint32_t pw, float scale = 1.f);
-// fast mode (APTGPU_MODE_FAST): availability (same tables as strict)
-bool fused_fast_supported(uint32_t l, uint32_t m, uint32_t t1, uint32_t t2, uint32_t pw);
 // Per-plan parameters of the specialised front end, resident in HBM (the kernel fetches each when
 // the stage that needs it starts, instead of holding them in SGPRs from its first instruction on).
-// Run-time geometry of the table-driven stage 1 (k_fused in TABLE mode; fused_table_geom fills it)
-struct TableGeom {
-    uint32_t l, m;             // interpolation / decimation factors
-    uint32_t jlim;             // taps the reference uses (2*off + 1)
-    uint32_t tpp;              // row stride of the phase-major table (>= taps per phase, odd)
-    uint32_t xt;               // input tile, floats (multiple of 4)
-    uint32_t off_x;            // LDS offset of the input tile in floats (the table sits at 0)
-    uint32_t step_q, step_r;   // (NTHR*m) / l and % l: x0 / phase update between a thread's outputs
-    uint32_t jl_a, jl_b;       // jlim / l and % l: taps of phase p = jl_a + (p < jl_b)
-    // PHASE mode: the thread -> branch-slot assignment (fused_phase_table): `nperm` lists of `nthr` uint32 entries at
-    // float offset `perm_off` of the table buffer, list (tile % nperm) for a tile; an entry >= step_r marks an idle thread
-    uint32_t nthr, perm_off, nperm;
-    uint32_t nq;               // PHASE mode: branches per thread (1, 2, 4, 8, 16)
-    // PHASE mode: the slot stride — a thread with list entry u < sq holds the slots u + q sq (q < nq) that are < step_r.
-    // nq == 1: sq = step_r.  nq == 4 (standard and slow profile), 8: sq = nthr (round 6: every thread has work and only the LAST slots of some threads
-    // do not exist — l = 832: four slots for threads 0-63, three for the others, 13 wave-branches per tile instead of the 16
-    // of sq = step_r / nq = 208, whose fourth wave ran every branch for 16 lanes: 2-3 % on the front end, not the 5 % the
-    // instruction count promised — these kernels wait more than they issue, profiles/r06_phase_balanced_ab.txt).  Else
-    // sq = step_r / nq (no gain / a loss measured).  APTGPU_PHASE_BALANCED=0 / 1 forces one form for every nq.
-    uint32_t sq;
-    uint32_t stream;           // PHASE mode: taps streamed from the table (filters too long for the registers), rows padded to 16
-    // PHASE mode, exact != 0 (the tile phases repeat with a period nperm = 1 << perm_shift <= 8): list (tile % nperm) is
-    // built for that tile's phase, and everything a tile derives from its index by division is tabulated — per phase r the
-    // first input sample's quotient x0r[r] and remainder rbr[r] (tile = nperm t + r: X0 = x0r[r] + t xd), per thread the
-    // window start and polyphase branch of each of its nq slots, packed (c | p << 16) at float offset cp_off
-    // ([nperm][nthr][nq] uint32).  exact == 0: one list serves every tile and the kernel divides.
-    uint32_t exact, perm_shift, cp_off, xd;
-    // ... and the taps once more in THREAD order at float offset tt_off: [nperm][nq][tpp / 4][nthr] quads — quad e of
-    // the branch of thread t's slot q — so that a wave's tap load is 1 KB of consecutive memory (from the phase-major
-    // table every lane reads a row of its own: 64 cache lines per load)
-    uint32_t tt_off;
-    int32_t x0r[8];
-    uint32_t rbr[8];
-};
+// (TableGeom, the run-time geometry of the TABLE / PHASE stage 1: apt_front_end.hpp)
 struct FusedParams {
     const float *hs;        // stage-1 table: tap pairs (fused_branch_taps), or the fp16 table
     const float *h2;        // low-pass taps [T2]
@@ -228,48 +180,22 @@ struct FusedParams {
     uint32_t t1;
     uint32_t t2;            // kModeStrictPad2: the low-pass filter's own tap count (h2 / h2p are padded to kPadT2Max)
 };
-// One launch over the recordings of `call`: x -> F (slot's filtered buffer) and, if prm->want_gm, the
-// per-group maxima of the sync cross-correlation.  Returns false if no specialisation matches.
-// Inputs are f32 Signals, or (pcm16) mono int16 samples at 4-byte aligned addresses.
-// mode: 0 strict, 1 fp16 taps, 2 fast.
-// variant_out (this and the two front ends below): receives the row of apt_kernels_fused_variants.hpp whose kernel the
-// call launched (a FusedVariant; -1 where none was) — introspection, aptgpu_plan_read_internal("fused_variant").
-bool fused_front_end(hipStream_t s, uint32_t l, uint32_t m, uint32_t t1, uint32_t t2, uint32_t pw, int mode,
-                     bool pcm16, const CallArgs &call, const FusedParams *d_prm, uint64_t max_w, int lds_pad = 0,
-                     int *variant_out = nullptr);
-// kModeMfma (mode 3 of fused_front_end): which geometries have a matrix-core instantiation, and its table —
-// [3 pieces][K / 32][64 lanes][4 dwords] bf16 fragments of the banded Toeplitz matrix of the resampler (h = h0 + h1 + h2
-// exactly)
-bool fused_mfma_supported(uint32_t l, uint32_t m, uint32_t t1, uint32_t t2, uint32_t pw);
+// One launch over the recordings of `call` of the k_fused instantiation the plan chose (fe.variant, with its LDS size): x
+// -> F (slot's filtered buffer) and, if prm->want_gm, the per-group maxima of the sync cross-correlation.  Returns false
+// where there is no instantiation for the input type or an input is misaligned.
+// Inputs are f32 Signals, or (pcm16) mono int16 samples at 4-byte (SPLIT: dword loads of sample pairs) / even addresses.
+// variant_out: receives the row of apt_kernels_fused_variants.hpp whose kernel the call launched (a FusedVariant; -1 where
+// none was) — introspection, aptgpu_plan_read_internal("fused_variant").
+bool fused_front_end(hipStream_t s, const FrontEnd &fe, bool pcm16, const CallArgs &call, const FusedParams *d_prm,
+                     uint64_t max_w, int lds_pad = 0, int *variant_out = nullptr);
+// kModeMfma: the matrix-core instantiations' table — [3 pieces][K / 32][64 lanes][4 dwords] bf16 fragments of the banded
+// Toeplitz matrix of the resampler (h = h0 + h1 + h2 exactly)
 uint32_t fused_mfma_table_dwords(uint32_t l, uint32_t m);
 void fused_mfma_table(uint32_t l, uint32_t m, const float *coeff, uint32_t t1, uint32_t *table);
-// Table-driven stage 1 + the specialised work-rate stages (k_fused in TABLE mode): any (l, m, taps) whose
-// phase-major table and input tile fit two 512-thread workgroups per CU, standard-profile work-rate
-// stages (37-tap low-pass, pw = 3).  11 025 Hz (l = 832) is the rate this exists for.
-bool fused_table_supported(uint32_t l, uint32_t m, uint32_t t1, uint32_t t2, uint32_t pw, TableGeom *geom);
-bool fused_table_front_end(hipStream_t s, const TableGeom &geom, int mode, bool pcm16, const CallArgs &call,
-                           const FusedParams *d_prm, uint64_t max_w, int *variant_out = nullptr);
-
-// Phase-resident stage 1 + the specialised work-rate stages (k_fused in PHASE mode): a thread holds nq slots u + q S'
-// (S' = step_r / nq <= threads) of the step_r outputs after which the polyphase branches repeat, and computes the
-// 16 / nq outputs of each that fall into the tile, with the taps of their common branch in registers (or, `stream`,
-// fetched sixteen at a time).  256 threads with nq = 1, 2, 4 (l <= 256, 512, 1024) at the standard profile, nq = 1, 4, 8,
-// 16 at the fast profile, nq = 1, 2, 4 with streamed taps at the slow profile; 512- / 1024-thread forms with nq = 1 as
-// fallbacks.  Every rate a sound card records at is served this way (44 100 Hz: l = 208; 22 050: 416; 11 025: 832).
-// TableGeom use: step_r = S, step_q = S*m/l, tpp = row stride of the table (multiple of 4; 16 when streamed), off_x = f2
-// entries per region of the paired input tile, xt = floats of the whole tile; the rest: see the struct.
-bool fused_phase_supported(uint32_t l, uint32_t m, uint32_t t1, uint32_t t2, uint32_t pw, TableGeom *geom);
-uint32_t fused_phase_table_floats(const TableGeom &geom);
-// host: [l][tpp] taps, rows 16-byte aligned, then the thread assignment lists (geom.perm_off)
-void fused_phase_table(const TableGeom &geom, uint32_t t2, uint32_t pw, const float *coeff, uint32_t t1, float *table);
-bool fused_phase_front_end(hipStream_t s, const TableGeom &geom, uint32_t t2, uint32_t pw, int mode, bool pcm16,
-                           const CallArgs &call, const FusedParams *d_prm, uint64_t max_w, int *variant_out = nullptr);
 
 // ---- fused front end for any rate / profile (apt_kernels_fused_any.hip) -------------
-// run-time parameters, taps phase-major in LDS; same outputs as fused_front_end
-bool fused_any_supported(uint32_t l, uint32_t m, uint32_t t1, uint32_t t2, uint32_t pw);
-uint32_t fused_any_table_floats(uint32_t l, uint32_t t1);
-void fused_any_table(uint32_t l, const float *coeff, uint32_t t1, float *table);  // host
+// run-time parameters, taps phase-major in LDS; same outputs as fused_front_end (which geometries, and the table:
+// apt_kernels_fused_any_geom.hpp)
 // One launch over the recordings of `call` (f32 Signals, or — pcm16 — mono int16 payloads at even addresses): F into
 // the slots' filtered buffers and, if want_gm, the per-group maxima of the sync correlation into their gm buffers.
 bool fused_any_front_end(hipStream_t s, uint32_t l, uint32_t m, uint32_t t1, uint32_t t2, uint32_t pw, bool pcm16,

@@ -41,141 +41,16 @@
 
 namespace apt::gpu {
 
-namespace {
-
-constexpr int kGS = 52;  // correlation positions per group (apt_kernels_sync.hip)
-
-constexpr size_t kLdsLimit = 160 * 1024;
-
-struct Candidate {
-    int nthr, kpt;
-};
-// most resident waves per CU first (LDS permitting), then the larger tile
-// (round 6: {256, 4} — a tile of 1024 work samples — for input rates beyond seventeen times the work rate's 1 / l share:
-// 250 kHz SDR recordings, whose 2048-sample tile needs more input than the LDS holds, ran the unfused kernels)
-constexpr Candidate kCandidates[] = {{256, 8}, {1024, 8}, {1024, 4}, {256, 4}};
-
-bool make_geom(uint32_t l, uint32_t m, uint32_t t1, uint32_t t2, uint32_t pw, int nthr, int kpt, bool table_in_global,
-               AnyGeom *out, size_t *lds_bytes)
-{
-    AnyGeom g{};
-    g.l = l;
-    g.m = m;
-    g.jlim = 2 * ((t1 - 1) / 2) + 1;
-    const uint32_t per_phase = (g.jlim + l - 1) / l;
-    g.tpp = per_phase | 1u;  // odd stride: rows of consecutive phases start in different banks
-    g.t2 = t2;
-    g.g = 38 * pw;
-    g.pulse = 2 * pw;
-    g.kt = static_cast<uint32_t>(nthr * kpt);
-    if (38 * pw > 256) return false;  // sign bitmap
-    // 32-bit in-tile index math: (tile outputs + look-ahead) * m + l must stay below 2^31 (per launch shape since round 6:
-    // the old blanket test for the largest tile sent every rate above 170 kHz that is coprime to the work rate to the
-    // unfused kernels)
-    if ((static_cast<uint64_t>(g.kt) + 4096u) * m + l > 0x7fffffffull) return false;
-    g.pre = (t2 + 2 * static_cast<uint32_t>(kpt) + static_cast<uint32_t>(kpt) - 1) / static_cast<uint32_t>(kpt) *
-            static_cast<uint32_t>(kpt);  // multiple of KPT (and of 4)
-    if (g.kt < g.pre + g.g + kGS) return false;
-    g.own = (g.kt - g.pre - (g.g - 1)) / kGS * kGS;
-    if (g.own == 0) return false;
-    g.xt = (static_cast<uint32_t>((static_cast<uint64_t>(g.kt) * m + l - 1) / l) + per_phase + 8 + 3) & ~3u;
-    if (g.xt < static_cast<uint32_t>(nthr)) g.xt = static_cast<uint32_t>(nthr);  // (stage 4 keeps one float per thread there)
-    const uint32_t slack = 64;
-    // (a table that does not fit LDS beside the tile — 44 100 Hz at the slow profile: 29 k taps, 116 KB — stays in
-    // HBM / L2 and stage 1 reads its rows from there: every thread 856 bytes per output, but fused: R, D and C still
-    // never leave the CU)
-    g.table_in_global = table_in_global ? 1u : 0u;
-    g.off_x = table_in_global ? 0u : ((l * g.tpp + 3u) & ~3u);
-    const uint32_t ab_len = ((g.kt + slack) + (g.kt + slack) / static_cast<uint32_t>(kpt) + 8u) & ~3u;  // padded
-    g.off_a = g.off_x + g.xt;
-    g.off_b = g.off_a + ab_len;
-    g.step_q = static_cast<uint32_t>((static_cast<uint64_t>(nthr) * m) / l);
-    g.step_r = static_cast<uint32_t>((static_cast<uint64_t>(nthr) * m) % l);
-    g.jl_a = g.jlim / l;
-    g.jl_b = g.jlim % l;
-    for (uint32_t j = 0; j < g.g; ++j) {
-        const bool plus = j >= g.pulse && j < 15 * g.pulse && (((j - g.pulse) / g.pulse) & 1) == 1;
-        if (plus) g.sign[j >> 6] |= 1ull << (j & 63);
-    }
-    const size_t floats = static_cast<size_t>(g.off_b) + ab_len;
-    *lds_bytes = floats * sizeof(float);
-    *out = g;
-    return *lds_bytes <= kLdsLimit;
-}
-
-// picks the launch shape: maximise resident waves per CU, then tile size
-bool choose_with(uint32_t l, uint32_t m, uint32_t t1, uint32_t t2, uint32_t pw, bool in_global, Candidate *best, AnyGeom *geom,
-                 size_t *lds)
-{
-    int best_score = 0;
-    uint32_t best_kt = 0;
-    bool found = false;
-    for (const Candidate &c : kCandidates) {
-        AnyGeom g;
-        size_t bytes;
-        if (!make_geom(l, m, t1, t2, pw, c.nthr, c.kpt, in_global, &g, &bytes)) continue;
-        int wgs = static_cast<int>(kLdsLimit / bytes);
-        int waves = wgs * (c.nthr / 64);
-        if (waves > 32) waves = 32;  // 8 per SIMD is plenty
-        // tile efficiency matters too: weight by the owned fraction
-        const int score = waves * 1000 + static_cast<int>(1000.0 * g.own / g.kt);
-        if (!found || score > best_score || (score == best_score && g.kt > best_kt)) {
-            best_score = score;
-            best_kt = g.kt;
-            *best = c;
-            *geom = g;
-            *lds = bytes;
-            found = true;
-        }
-    }
-    return found;
-}
-
-// the table in LDS where a launch shape exists for that; else in HBM / L2
-bool choose(uint32_t l, uint32_t m, uint32_t t1, uint32_t t2, uint32_t pw, Candidate *best, AnyGeom *geom, size_t *lds)
-{
-    return choose_with(l, m, t1, t2, pw, false, best, geom, lds) || choose_with(l, m, t1, t2, pw, true, best, geom, lds);
-}
-
-}  // namespace
-
-bool fused_any_supported(uint32_t l, uint32_t m, uint32_t t1, uint32_t t2, uint32_t pw)
-{
-    if (l == 0 || m == 0 || t1 == 0 || t2 == 0 || pw == 0) return false;
-    Candidate c;
-    AnyGeom g;
-    size_t lds;
-    return choose(l, m, t1, t2, pw, &c, &g, &lds);
-}
-
-uint32_t fused_any_table_floats(uint32_t l, uint32_t t1)
-{
-    const uint32_t jlim = 2 * ((t1 - 1) / 2) + 1;
-    return l * (((jlim + l - 1) / l) | 1u);
-}
-
-// host: phase-major table [l][tpp], row p = coeff[p], coeff[p + l], ... (zero padded)
-void fused_any_table(uint32_t l, const float *coeff, uint32_t t1, float *table)
-{
-    const uint32_t jlim = 2 * ((t1 - 1) / 2) + 1;
-    const uint32_t tpp = ((jlim + l - 1) / l) | 1u;
-    for (uint32_t p = 0; p < l; ++p)
-        for (uint32_t i = 0; i < tpp; ++i) {
-            const uint64_t j = p + static_cast<uint64_t>(i) * l;
-            table[static_cast<size_t>(p) * tpp + i] = j < jlim ? coeff[j] : 0.f;
-        }
-}
-
 bool fused_any_front_end(hipStream_t s, uint32_t l, uint32_t m, uint32_t t1, uint32_t t2, uint32_t pw, bool pcm16,
                          const CallArgs &call, const SlotPtrs *d_slots, uint64_t max_w, const float *table,
                          const float *h2, const float *h2p, float cosphi2, float sinphi, float inv_sinphi, bool want_gm,
                          float gm_slack_scale)
 {
-    Candidate c;
+    AnyCandidate c;
     AnyGeom g;
     size_t lds;
     if (call.count == 0) return true;
-    if (!choose(l, m, t1, t2, pw, &c, &g, &lds)) return false;
+    if (!any_choose(l, m, t1, t2, pw, &c, &g, &lds)) return false;
     g.gm_slack_scale = gm_slack_scale;
     if (pcm16)
         for (uint32_t i = 0; i < call.count; ++i)

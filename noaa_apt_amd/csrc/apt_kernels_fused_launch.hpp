@@ -8,18 +8,7 @@
 
 namespace apt::gpu {
 
-// PHASE stage 1 with ONE branch per thread (l <= 256: 44 100 Hz, 48 kHz at the fast profile, 8 / 16 / 24 / 32 kHz ...): the
-// paired input tile goes through LDS in two halves of eight windows each (round 6; kernel and phase_geom must agree, hence
-// a macro).  Its 45-52 KB were what held these kernels at three workgroups per CU.
-#ifndef APT_PHASE_HALVES
-#define APT_PHASE_HALVES 1
-#endif
-// (not the standard profile's kernel in APTGPU_MODE_FAST: its 68-tap branch is then fetched twice, in segments, by a kernel
-// that has half the arithmetic to hide it under — 0.80 -> 0.86 ms per 16 at 44 100 Hz, profiles/r06_phase_halves_ab.txt)
-constexpr bool phase_halves(int nq, bool stream, int nthr, int t2, bool fast)
-{
-    return APT_PHASE_HALVES != 0 && nq == 1 && !stream && nthr == 256 && !(fast && t2 == 37);
-}
+// (phase_halves — PHASE stage 1 with one branch per thread takes its tile through LDS in two halves: apt_front_end.hpp)
 // FusedGeom's variant argument for a mode
 constexpr int fused_geom_var(int mode)
 {

@@ -1,7 +1,8 @@
 // apt_kernels_fused_variants.hpp — every k_fused instantiation the library is built with, in ONE list, and which of
 // them serves which plan.  Host-only and free of HIP: apt_kernels_fused_variant.hip is compiled once per row and input
 // type from this list, the Makefile reads the names from it, apt_kernels_fused.hip builds its table of launch functions
-// from it, and tests/test_fused_variants.py checks the selection functions below without a GPU.
+// from it, select_front_end (apt_front_end.hpp) chooses a plan's rows with the selection functions below, and
+// tests/test_fused_variants.py checks those functions without a GPU.
 // A new geometry, profile or mode: add a row, and the condition that selects it.
 #pragma once
 
@@ -181,7 +182,7 @@ constexpr bool fused_mfma_fits(uint32_t l, uint32_t m, uint32_t t1, uint32_t t2,
     return false;
 }
 
-// SPLIT stage 1 (fused_front_end): 48 / 96 kHz
+// SPLIT stage 1: 48 / 96 kHz
 constexpr FusedVariant fused_split_variant(uint32_t l, uint32_t m, uint32_t t1, uint32_t t2, uint32_t pw, int mode, bool pcm16)
 {
     if (mode == kModeStrictPad) {
@@ -209,13 +210,13 @@ constexpr FusedVariant fused_split_variant(uint32_t l, uint32_t m, uint32_t t1, 
     return kFusedNone;
 }
 
-// TABLE stage 1 (fused_table_front_end)
+// TABLE stage 1
 constexpr FusedVariant fused_table_variant(int mode)
 {
     return mode == kModeFast ? kFused_tab_std_fast : mode == kModeStrict ? kFused_tab_std : kFusedNone;
 }
 
-// PHASE stage 1 (fused_phase_front_end): workgroups of nthr threads with nq branches each (TableGeom's; 0 counts as 1),
+// PHASE stage 1: workgroups of nthr threads with nq branches each (TableGeom's; 0 counts as 1),
 // taps streamed or resident, and the work-rate stages of the profile (t2, pw) names
 constexpr FusedVariant fused_phase_variant(uint32_t nq, uint32_t nthr, bool stream, uint32_t t2, uint32_t pw, int mode)
 {

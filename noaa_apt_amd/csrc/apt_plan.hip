@@ -87,6 +87,184 @@ std::vector<aptgpu_kernel_time> KernelTimer::collect(hipStream_t s)
 }
 
 // ---------------------------------------------------------------- plan_create
+namespace {
+
+// the source is a temporary of the caller, so wait for the copy before returning (on the plan's own stream: the null
+// stream would serialise against other plans' work)
+void upload(aptgpu_plan *plan, DeviceBuffer<float> &dst, const float *src, size_t n)
+{
+    dst.alloc(n);
+    hip_check(hipMemcpyAsync(dst.ptr, src, n * sizeof(float), hipMemcpyHostToDevice, plan->stream), "hipMemcpy taps");
+    hip_check(hipStreamSynchronize(plan->stream), "hipStreamSynchronize");
+}
+void upload(aptgpu_plan *plan, DeviceBuffer<float> &dst, const Signal &src) { upload(plan, dst, src.data(), src.size()); }
+
+// Calls in flight = streams (call j runs on stream j % depth and owns that stream's slots), and the events that order
+// the front ends of consecutive calls.
+void create_streams(aptgpu_plan *plan, const aptgpu_context *ctx, int depth)
+{
+    const gpu::PlanSwitches &sw = plan->psw;
+    const int max_batch = plan->max_batch;
+    if (ctx && ctx->stream) {
+        plan->user_stream = static_cast<hipStream_t>(ctx->stream);
+        hip_check(hipEventCreateWithFlags(&plan->ev_user, hipEventDisableTiming), "hipEventCreate");
+    }
+    if (depth <= 0) depth = sw.streams ? sw.streams : (max_batch >= 4 ? 3 : 6);
+    depth = std::max(1, std::min(depth, 16));
+    plan->streams.resize(static_cast<size_t>(depth));
+    // A/B switches of the pipeline's shape (tools/sweep.py; read at plan creation):
+    //   APTGPU_FRONT_STREAM=1  all front ends on one extra stream (apt_plan.hpp)
+    //   APTGPU_CHAIN_CUS=n     with it: the per-call streams (words, slots, orbit, gather) are created with a CU mask of
+    //                          n CUs, APTGPU_FRONT_EXCL=1: and the front-end stream with the mask of the others
+    int cu_count = 0;
+    (void)hipDeviceGetAttribute(&cu_count, hipDeviceAttributeMultiprocessorCount, plan->device);
+    const bool want_front_stream = sw.front_stream == '1' && !plan->user_stream && depth > 1 && max_batch >= 4;
+    plan->chain_cus = want_front_stream ? std::max(0, std::min(sw.chain_cus, cu_count - 8)) : 0;
+    auto masked_stream = [&](hipStream_t *st, int first, int count) {
+        // bit i of the mask = CU i in the runtime's numbering (consecutive bits go round the XCDs)
+        std::vector<uint32_t> mask(static_cast<size_t>((cu_count + 31) / 32), 0u);
+        for (int c = first; c < first + count && c < cu_count; ++c) mask[static_cast<size_t>(c / 32)] |= 1u << (c % 32);
+        hip_check(hipExtStreamCreateWithCUMask(st, static_cast<uint32_t>(mask.size()), mask.data()), "hipExtStreamCreateWithCUMask");
+    };
+    for (auto &st : plan->streams) {
+        if (plan->chain_cus > 0) masked_stream(&st, 0, plan->chain_cus);
+        else hip_check(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "hipStreamCreate");
+    }
+    plan->stream = plan->streams[0];
+    if (want_front_stream) {
+        if (plan->chain_cus > 0 && sw.front_excl == '1') masked_stream(&plan->front_stream, plan->chain_cus, cu_count - plan->chain_cus);
+        else hip_check(hipStreamCreateWithFlags(&plan->front_stream, hipStreamNonBlocking), "hipStreamCreate");
+        plan->ev_pre.resize(static_cast<size_t>(depth));
+        for (auto &ev : plan->ev_pre) hip_check(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
+    }
+    // (not with a user stream: such plans may be captured into a HIP graph, call by call, and an event
+    // recorded before the capture cannot be waited for inside it)
+    plan->front_serial = ((sw.front_serial >= 0 ? sw.front_serial != '0' : max_batch >= 4) && !plan->user_stream && depth > 1) ||
+                         plan->front_stream;
+    if (plan->front_serial) {
+        plan->ev_front.resize(static_cast<size_t>(depth));
+        for (auto &ev : plan->ev_front) hip_check(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
+    }
+}
+
+// A plan whose resampling factors have a specialised kernel but whose tap COUNT differs (a tuned
+// resample_atten / resample_delta_freq) lands on a slower kernel — the count fixes which window samples each
+// polyphase branch uses, a compile-time pattern.  Same results; say so once instead of leaving it to
+// stats.fused (APTGPU_QUIET=1 silences it).
+void note_unspecialised(const aptgpu_plan *plan)
+{
+    const bool specialisable = (plan->mode == APTGPU_MODE_STRICT || plan->mode == APTGPU_MODE_FAST) && plan->l > 1 &&
+                               plan->work_is_multiple && !plan->export_filtered && plan->psw.fused_any != '1';
+    if (!specialisable || plan->fe.kind == gpu::FrontEndKind::Split || plan->l != 13 || (plan->m != 50 && plan->m != 100) ||
+        plan->pw != 3)
+        return;
+    static std::atomic<bool> told{false};
+    if (plan->psw.quiet != '1' && !told.exchange(true))
+        std::fprintf(stderr,
+                     "aptgpu: %u -> %u Hz with %zu resample / %zu low-pass taps has no compile-time specialised front end "
+                     "(those exist for up to 1079 / 2145 resample taps and up to 45 low-pass taps at 48 / 96 kHz); using kernel path %d "
+                     "(same results, lower throughput)\n",
+                     plan->input_rate, plan->settings.work_rate, plan->taps_resample.size(), plan->taps_lowpass.size(), plan->fused());
+}
+
+// The tables of the plan's front end (plan->fe), in the layouts its kernel reads.
+void upload_front_end_tables(aptgpu_plan *plan)
+{
+    using gpu::FrontEndKind;
+    const gpu::FrontEnd &fe = plan->fe;
+    const uint32_t t1 = static_cast<uint32_t>(plan->taps_resample.size());
+    if (plan->mode == APTGPU_MODE_FP16_TAPS && plan->l > 1) {  // (also the unfused step-export path of the fused fp16 mode)
+        std::vector<uint16_t> tab(static_cast<size_t>(plan->l) * gpu::f16taps_pairs_per_phase(plan->l, t1) * 2 + 8, 0);
+        plan->f16_unscale = gpu::f16taps_pack(plan->l, plan->taps_resample.data(), t1, tab.data());
+        plan->d_taps_f16.alloc(tab.size());
+        hip_check(hipMemcpyAsync(plan->d_taps_f16.ptr, tab.data(), tab.size() * 2, hipMemcpyHostToDevice, plan->stream),
+                  "hipMemcpy f16 taps");
+        hip_check(hipStreamSynchronize(plan->stream), "hipStreamSynchronize");  // `tab` dies here
+    }
+    if (fe.kind == FrontEndKind::Unfused) return;
+    {
+        // division by sin(phi) through its reciprocal: only if it is exactly rounded for every x
+        const float rc = 1.0f / plan->sinphi;
+        if (fe.fast) plan->inv_sinphi = rc;  // a plain multiplication by the rounded reciprocal
+        else if (plan->psw.general_envelope != '1' && gpu::verify_fast_divide(plan->device, plan->sinphi, rc)) plan->inv_sinphi = rc;
+    }
+    if (fe.kind == FrontEndKind::Split) {
+        // (the kernel that will read it: fast plans run the fast instantiation, whose chunks may differ)
+        const int ch = gpu::fused_chunk_of(plan->m, fe.fast);
+        const uint32_t t1_layout = fe.pad_t1 ? fe.pad_t1 : t1;
+        Signal hs(static_cast<size_t>(gpu::fused_tap_table_floats(plan->l, plan->m, t1_layout, ch)) + 16, 0.f);
+        if (fe.mfma || fe.f16) {
+            // same buffer, different content: the bf16 fragments of the resampler's Toeplitz matrix / half2 tap pairs as raw dwords
+            std::vector<uint32_t> tab((fe.mfma ? gpu::fused_mfma_table_dwords(plan->l, plan->m) : gpu::fused_f16_table_dwords(plan->l, plan->m, t1)) + 16, 0u);
+            if (fe.mfma) gpu::fused_mfma_table(plan->l, plan->m, plan->taps_resample.data(), t1, tab.data());
+            else plan->f16_unscale = gpu::fused_f16_branch_taps(plan->l, plan->m, plan->taps_resample.data(), t1, tab.data());
+            hs.assign(tab.size(), 0.f);
+            std::memcpy(hs.data(), tab.data(), tab.size() * sizeof(uint32_t));
+        } else {
+            gpu::fused_branch_taps(plan->l, plan->m, plan->taps_resample.data(), t1, ch, hs.data(), t1_layout);
+        }
+        upload(plan, plan->d_taps_branch, hs);
+    } else {
+        const bool phase = fe.kind == FrontEndKind::Phase;
+        Signal tab(static_cast<size_t>(phase ? gpu::fused_phase_table_floats(fe.geom) : gpu::fused_any_table_floats(plan->l, t1)) + 16, 0.f);
+        if (phase) {
+            const gpu::FusedVariantRow &row = gpu::kFusedVariants[fe.variant[0]];  // (the tile is the kernel's: its own T2)
+            gpu::fused_phase_table(fe.geom, static_cast<uint32_t>(row.t2), plan->pw, plan->taps_resample.data(), tab.data(), plan->psw);
+        } else gpu::fused_any_table(plan->l, plan->taps_resample.data(), t1, tab.data());
+        upload(plan, plan->d_taps_any, tab);
+    }
+    // the low-pass taps in pairs, and (kModeStrictPad2) laid out for the kernel's bound: zeros behind the filter's last tap
+    Signal lp(plan->taps_lowpass);
+    if (fe.pad_t2) {
+        lp.resize(fe.pad_t2, 0.f);
+        Signal padded(lp);
+        padded.resize(lp.size() + 16, 0.f);
+        upload(plan, plan->d_taps_lowpass_pad, padded);
+    }
+    Signal h2p(2 * (lp.size() + 1) + 16, 0.f);
+    gpu::fused_lowpass_pairs(lp.data(), static_cast<uint32_t>(lp.size()), h2p.data());
+    upload(plan, plan->d_taps_lowpass_pairs, h2p);
+}
+
+// workspace: one set of max_batch slots per stream
+void alloc_workspace(aptgpu_plan *plan)
+{
+    plan->slots.resize(plan->streams.size() * static_cast<size_t>(plan->max_batch));
+    const uint64_t w = plan->max_work_len;
+    // (F in pixel-phase planes where a k_fused instantiation writes it: pw planes of f_plane_stride floats)
+    plan->plane_stride = plan->writes_planes() ? gpu::f_plane_stride(w, plan->pw) : 0u;  // (then pw >= 1)
+    for (auto &sl : plan->slots) {
+        // (resampled / demodulated / correlation are only needed by the unfused kernels: allocated on first use)
+        sl.filtered.alloc(std::max<uint64_t>(w, static_cast<uint64_t>(plan->pw) * plan->plane_stride) + 64);
+        sl.f_stride = plan->plane_stride;  // (what a call without step export leaves: run_call)
+        if (plan->sync) {
+            sl.peaks.alloc(plan->max_rows + 2);
+            const uint64_t ng = w / gpu::sync_group_size() + 2;
+            const uint64_t chunks = ng / gpu::sync_chunk_groups() + 2;
+            sl.gm.alloc(ng + 64);
+            sl.words.alloc(ng + 64);
+            sl.nanw.alloc(ng + 64);
+            sl.slot_nt.alloc(chunks * gpu::sync_slot_cap());
+            sl.slot_cnt.alloc(chunks);
+            sl.orbit_ws.alloc(gpu::sync_orbit_ws_words(w, plan->spr));
+            sl.flags.alloc(32);
+            hip_check(hipMemsetAsync(sl.flags.ptr, 0, 32 * sizeof(uint32_t), plan->stream), "hipMemset flags");
+            if (plan->fe.kind == gpu::FrontEndKind::Unfused) sl.correlation.alloc(w + 64);
+            if (plan->mode == APTGPU_MODE_GENERIC) sl.bits.alloc(w / 64 + plan->md / 64 + 4);
+        }
+    }
+    plan->d_results.alloc(plan->slots.size());
+    hip_check(hipMemsetAsync(plan->d_results.ptr, 0, sizeof(gpu::Result) * plan->slots.size(), plan->stream),
+              "hipMemset");
+    plan->d_slots.alloc(plan->slots.size());
+    // the uploads and memsets above ran on the plan's first stream: make them land before a decode can
+    // be enqueued on any of the others (a stream sync, not a device sync — other plans of this process,
+    // e.g. concurrent aptgpu_decode calls on other host threads, keep running)
+    plan->upload_slot_table();
+}
+
+}  // namespace
+
 aptgpu_plan *plan_create(const aptgpu_context *ctx, const aptgpu_settings &settings,
                          uint32_t input_rate, bool sync, size_t max_samples, int max_batch, int depth)
 {
@@ -102,330 +280,29 @@ aptgpu_plan *plan_create(const aptgpu_context *ctx, const aptgpu_settings &setti
     plan->max_samples = max_samples;
     plan->max_batch = max_batch;
     plan->sw = gpu::read_launch_switches();
+    plan->psw = gpu::read_plan_switches();
     plan->export_filtered = settings.export_resample_filtered != 0;
-    if (const char *e = std::getenv("APTGPU_FORCE_WALK")) plan->picker_force = e[0] == '1' ? 1 : 0;
-    if (const char *e = std::getenv("APTGPU_PICKER_LDS")) if (e[0] == '1') plan->picker_force = 4;
+    plan->picker_force = plan->psw.picker_lds == '1' ? 4 : plan->psw.force_walk == '1' ? 1 : 0;
 
-    // decode.rs:55 — u32 arithmetic; the reference would panic on overflow
-    const uint64_t spr64 = static_cast<uint64_t>(PX_PER_ROW) * settings.work_rate;
-    if (spr64 > 0xFFFFFFFFull) throw Error{ErrorKind::Invalid, "work_rate too large"};
-    plan->spr = static_cast<uint32_t>(spr64 / FINAL_RATE);
-    // (the reference would divide by zero at decode.rs:142 / find nothing to sync on)
-    if (plan->spr == 0) throw Error{ErrorKind::Invalid, "work_rate too small"};
+    // the filters, factors and sync geometry (pure host code: apt_front_end.cpp)
+    static_cast<PlanDesign &>(*plan) = design_plan(settings, input_rate, sync);
 
-    const Rate in_rate = Rate::hz(input_rate);
-    const Rate work_rate = Rate::hz(settings.work_rate);
-
-    // ---- first resample: decode.rs:65-77 -> dsp.rs:62-126
-    if (work_rate.get_hz() == 0) throw Error{ErrorKind::Internal, "Can't resample to 0Hz"};
-    LowpassDcRemoval f1(Freq::hz(settings.resample_cutout, in_rate), settings.resample_atten,
-                        Freq::hz(settings.resample_delta_freq, in_rate));
-    const LM lm = interpolation_factors(in_rate, work_rate);
-    plan->l = lm.l;
-    plan->m = lm.m;
-    if (lm.l > 1) {
-        Rate interpolated{};
-        if (!in_rate.checked_mul(lm.l, &interpolated)) {
-            char buf[512];
-            std::snprintf(buf, sizeof buf,
-                          "Can't resample, looks like the sample rates do not have a big\n"
-                          "                divisor in common. input_rate: %u, output_rate: %u, "
-                          "l: %u, m: %u",
-                          in_rate.get_hz(), work_rate.get_hz(), lm.l, lm.m);
-            throw Error{ErrorKind::RateOverflow, buf};
-        }
-        f1.resample(in_rate, interpolated);
-    }
-    plan->taps_resample = f1.design();
-
-    // ---- demodulation constants: decode.rs:89, dsp.rs:360-363 (phi = 2*get_rad())
-    const Freq carrier = Freq::hz(static_cast<float>(CARRIER_FREQ), work_rate);
-    const float phi = 2.f * carrier.get_rad();
-    plan->cosphi2 = cosf(phi) * 2.f;
-    plan->sinphi = sinf(phi);
-
-    // ---- low-pass: decode.rs:95-100
-    const Freq cutout = Freq::pi_rad(static_cast<float>(FINAL_RATE) /
-                                     static_cast<float>(work_rate.get_hz()));
-    Lowpass f2(cutout, settings.demodulation_atten, cutout / 5.f);
-    plan->taps_lowpass = f2.design();
-
-    // ---- sync geometry: decode.rs:204-216
-    plan->work_is_multiple = (work_rate.get_hz() % FINAL_RATE) == 0;
-    plan->pw = work_rate.get_hz() / FINAL_RATE;
-    plan->n_sync_taps = 38 * plan->pw;
-    plan->md = static_cast<uint32_t>(static_cast<uint64_t>(plan->spr) * 8 / 10);
-    if (sync && plan->work_is_multiple && static_cast<uint64_t>(plan->md) * 8 > 160u * 1024u)
-        throw Error{ErrorKind::Unsupported, "work_rate too large for the sync search (LDS)"};
-
-    // ---- final resample to 4160 Hz: decode.rs:158-159
-    const LM lm2 = interpolation_factors(work_rate, Rate::hz(FINAL_RATE));
-    plan->l2 = lm2.l;
-    plan->m2 = lm2.m;
-    if (lm2.l > 1) {
-        Rate tmp{};
-        if (!work_rate.checked_mul(lm2.l, &tmp)) {
-            char buf[512];
-            std::snprintf(buf, sizeof buf,
-                          "Can't resample, looks like the sample rates do not have a big\n"
-                          "                divisor in common. input_rate: %u, output_rate: %u, "
-                          "l: %u, m: %u",
-                          work_rate.get_hz(), FINAL_RATE, lm2.l, lm2.m);
-            throw Error{ErrorKind::RateOverflow, buf};
-        }
-    }
-
-    // ---- device side
     hip_check(hipSetDevice(plan->device), "hipSetDevice");
-    if (ctx && ctx->stream) {
-        plan->user_stream = static_cast<hipStream_t>(ctx->stream);
-        hip_check(hipEventCreateWithFlags(&plan->ev_user, hipEventDisableTiming), "hipEventCreate");
-    }
-    // Calls in flight = streams (call j runs on stream j % depth and owns that stream's slots).
-    if (depth <= 0) {
-        const char *e = std::getenv("APTGPU_STREAMS");
-        depth = e ? std::atoi(e) : (max_batch >= 4 ? 3 : 6);
-    }
-    depth = std::max(1, std::min(depth, 16));
-    plan->streams.resize(static_cast<size_t>(depth));
-    // A/B switches of the pipeline's shape (tools/sweep.py; read at plan creation):
-    //   APTGPU_FRONT_STREAM=1  all front ends on one extra stream (apt_plan.hpp)
-    //   APTGPU_CHAIN_CUS=n     with it: the per-call streams (words, slots, orbit, gather) are created with a CU mask of
-    //                          n CUs, APTGPU_FRONT_EXCL=1: and the front-end stream with the mask of the others
-    int cu_count = 0;
-    (void)hipDeviceGetAttribute(&cu_count, hipDeviceAttributeMultiprocessorCount, plan->device);
-    const char *e_fs = std::getenv("APTGPU_FRONT_STREAM");
-    const bool want_front_stream = e_fs && e_fs[0] == '1' && !plan->user_stream && depth > 1 && max_batch >= 4;
-    const char *e_cc = std::getenv("APTGPU_CHAIN_CUS");
-    plan->chain_cus = (want_front_stream && e_cc) ? std::max(0, std::min(std::atoi(e_cc), cu_count - 8)) : 0;
-    auto masked_stream = [&](hipStream_t *st, int first, int count) {
-        // bit i of the mask = CU i in the runtime's numbering (consecutive bits go round the XCDs)
-        std::vector<uint32_t> mask(static_cast<size_t>((cu_count + 31) / 32), 0u);
-        for (int c = first; c < first + count && c < cu_count; ++c) mask[static_cast<size_t>(c / 32)] |= 1u << (c % 32);
-        hip_check(hipExtStreamCreateWithCUMask(st, static_cast<uint32_t>(mask.size()), mask.data()), "hipExtStreamCreateWithCUMask");
-    };
-    for (auto &st : plan->streams) {
-        if (plan->chain_cus > 0) masked_stream(&st, 0, plan->chain_cus);
-        else hip_check(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "hipStreamCreate");
-    }
-    plan->stream = plan->streams[0];
-    if (want_front_stream) {
-        const char *e_ex = std::getenv("APTGPU_FRONT_EXCL");
-        if (plan->chain_cus > 0 && e_ex && e_ex[0] == '1') masked_stream(&plan->front_stream, plan->chain_cus, cu_count - plan->chain_cus);
-        else hip_check(hipStreamCreateWithFlags(&plan->front_stream, hipStreamNonBlocking), "hipStreamCreate");
-        plan->ev_pre.resize(static_cast<size_t>(depth));
-        for (auto &ev : plan->ev_pre) hip_check(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
-    }
-    {
-        // (not with a user stream: such plans may be captured into a HIP graph, call by call, and an event
-        // recorded before the capture cannot be waited for inside it)
-        const char *e = std::getenv("APTGPU_FRONT_SERIAL");  // A/B switch
-        plan->front_serial = ((e ? e[0] != '0' : max_batch >= 4) && !plan->user_stream && depth > 1) || plan->front_stream;
-        if (plan->front_serial) {
-            plan->ev_front.resize(static_cast<size_t>(depth));
-            for (auto &ev : plan->ev_front) hip_check(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
-        }
-    }
+    create_streams(plan.get(), ctx, depth);
 
     plan->max_work_len = plan->work_len_for(max_samples);
     const uint64_t rows = plan->spr ? plan->max_work_len / plan->spr + 2 : 2;
     plan->max_rows = static_cast<uint32_t>(rows);
 
-    auto upload = [&](DeviceBuffer<float> &dst, const Signal &src) {
-        dst.alloc(src.size());
-        // on the plan's own stream (the null stream would serialise against other plans' work);
-        // the source is a temporary of the caller, so wait for the copy before returning
-        hip_check(hipMemcpyAsync(dst.ptr, src.data(), src.size() * sizeof(float),
-                                 hipMemcpyHostToDevice, plan->stream),
-                  "hipMemcpy taps");
-        hip_check(hipStreamSynchronize(plan->stream), "hipStreamSynchronize");
-    };
-    upload(plan->d_taps_resample, plan->taps_resample);
-    upload(plan->d_taps_lowpass, plan->taps_lowpass);
-    upload(plan->d_one, Signal{1.f});
-    {
-        const uint32_t t1 = static_cast<uint32_t>(plan->taps_resample.size());
-        const uint32_t t2 = static_cast<uint32_t>(plan->taps_lowpass.size());
-        // APTGPU_MODE_FAST permits deviations within the stated tolerance; where no fast kernel exists
-        // (other rates / profiles) the strict kernels serve it
-        const bool eligible = (plan->mode == APTGPU_MODE_STRICT || plan->mode == APTGPU_MODE_FAST) && plan->l > 1 &&
-                              plan->work_is_multiple && !plan->export_filtered;
-        const char *force_any = std::getenv("APTGPU_FUSED_ANY");  // tests: run-time kernel even if specialised
-        plan->fused = 0;
-        const bool no_spec = force_any && force_any[0] == '1';
-        const char *phase_first = std::getenv("APTGPU_PHASE_FIRST");  // tests: 0 = the table-driven stage 1 wherever it exists
-        // APTGPU_MODE_FAST on the matrix cores (kModeMfma: 48 / 96 kHz at the standard profile, ANY tap count its K holds).
-        // Measured at parity with / a few percent behind the VALU fast kernels at the stock tap counts (fast
-        // mode is bound by the tile's HBM round trip, not by the FIRs), so it serves the plans those kernels cannot — a tuned
-        // resample_atten / resample_delta_freq, which changes the tap count — and, APTGPU_FAST_MFMA=1 (A/B switch, tests), all
-        // it has an instantiation for; APTGPU_FAST_MFMA=0 switches it off.
-        const char *mfma_env = std::getenv("APTGPU_FAST_MFMA");
-        const bool mfma_want = mfma_env ? mfma_env[0] == '1' : !gpu::fused_supported(plan->l, plan->m, t1, t2, plan->pw);
-        const bool mfma_ok = eligible && !no_spec && plan->mode == APTGPU_MODE_FAST && mfma_want &&
-                             gpu::fused_mfma_supported(plan->l, plan->m, t1, t2, plan->pw);
-        // a tap count no specialised kernel is compiled for (a tuned resample_atten / resample_delta_freq): the strict kernel
-        // compiled for a tap-count BOUND, its table zero-padded (kModeStrictPad; APTGPU_FUSED_PAD=1 forces it for the stock
-        // counts too, =0 switches it off: A/B, tests)
-        const char *pad_env = std::getenv("APTGPU_FUSED_PAD");
-        const bool exact = gpu::fused_supported(plan->l, plan->m, t1, t2, plan->pw);
-        const uint32_t pad_t1 = (eligible && !no_spec && !mfma_ok && (pad_env ? pad_env[0] == '1' : !exact))
-                                    ? gpu::fused_pad_t1(plan->l, plan->m, t1, t2, plan->pw) : 0u;
-        plan->fused_pad_t1 = 0;
-        plan->fused_pad_t2 = 0;
-        if (eligible && (exact || mfma_ok || pad_t1 != 0) && !no_spec) {
-            plan->fused = 1;
-            plan->fused_pad_t1 = pad_t1;
-            plan->fused_pad_t2 = pad_t1 ? gpu::fused_pad_t2(plan->l, plan->m, t2, plan->pw) : 0u;  // (a tuned demodulation_atten)
-        }
-        // (where both the table-driven and the phase-resident stage 1 exist, the latter: since round 5 — thread assignment
-        // lists, interior tile loads, pipelined taps, two / four branches per thread — it is the faster one at every rate
-        // measured (8 / 11.025 / 16 / 32 kHz: 0.60 / 0.64 / 0.71 / 0.95 against 0.70 / 0.68 / 0.94 / 1.56 ms per 16 recordings,
-        // profiles/r05_sweeps.txt); APTGPU_PHASE_FIRST=0 (tests) puts the table-driven form first again)
-        else if (eligible && !no_spec && !(phase_first && phase_first[0] == '0') &&
-                 gpu::fused_phase_supported(plan->l, plan->m, t1, t2, plan->pw, &plan->table_geom))
-            plan->fused = 4;
-        else if (eligible && !no_spec && gpu::fused_table_supported(plan->l, plan->m, t1, t2, plan->pw, &plan->table_geom))
-            plan->fused = 3;  // table-driven stage 1 + the specialised work-rate stages (11 025 Hz)
-        else if (eligible && !no_spec && gpu::fused_phase_supported(plan->l, plan->m, t1, t2, plan->pw, &plan->table_geom))
-            plan->fused = 4;  // phase-resident taps in stage 1 + the specialised work-rate stages (44 100 Hz)
-        else if (eligible && gpu::fused_any_supported(plan->l, plan->m, t1, t2, plan->pw))
-            plan->fused = 2;
-        // A plan whose resampling factors have a specialised kernel but whose tap COUNT differs (a tuned
-        // resample_atten / resample_delta_freq) lands on a slower kernel — the count fixes which window samples each
-        // polyphase branch uses, a compile-time pattern.  Same results; say so once instead of leaving it to
-        // stats.fused (APTGPU_QUIET=1 silences it).
-        if (eligible && !no_spec && plan->fused != 1 && plan->l == 13 && (plan->m == 50 || plan->m == 100) && plan->pw == 3) {
-            static std::atomic<bool> told{false};
-            const char *q = std::getenv("APTGPU_QUIET");
-            if (!(q && q[0] == '1') && !told.exchange(true))
-                std::fprintf(stderr,
-                             "aptgpu: %u -> %u Hz with %u resample / %u low-pass taps has no compile-time specialised front end "
-                             "(those exist for up to 1079 / 2145 resample taps and up to 45 low-pass taps at 48 / 96 kHz); using kernel path %d "
-                             "(same results, lower throughput)\n",
-                             plan->input_rate, plan->settings.work_rate, t1, t2, plan->fused);
-        }
-        plan->fused_mfma = mfma_ok && plan->fused == 1;
-        plan->fused_fast = plan->mode == APTGPU_MODE_FAST &&
-                           ((plan->fused == 1 && plan->fused_pad_t1 == 0 &&
-                             (plan->fused_mfma || gpu::fused_fast_supported(plan->l, plan->m, t1, t2, plan->pw))) ||
-                            plan->fused == 3 ||
-                            // (a tuned low-pass on the PHASE kernels: strict kModeStrictPad2 instantiations only)
-                            (plan->fused == 4 && gpu::fused_phase_pad_t2(t2, plan->pw) == 0));
-        // fp16-tap mode inside the specialised fused kernel where one exists (else the generic kernel)
-        // (not with export_resample_filtered: the fused kernels decimate at t = off + k m, the flag moves the phase —
-        // dsp.rs:265-273 — and work_len_for() follows the flag; the unfused k_resample_at path serves such a plan)
-        if (plan->mode == APTGPU_MODE_FP16_TAPS && plan->l > 1 && plan->work_is_multiple && !plan->export_filtered &&
-            gpu::fused_f16_supported(plan->l, plan->m, t1, t2, plan->pw)) {
-            plan->fused = 1;
-            plan->fused_f16 = true;
-        }
-    }
-    if (plan->mode == APTGPU_MODE_FP16_TAPS && plan->l > 1) {  // (also the unfused step-export path of the fused fp16 mode)
-        const uint32_t t1 = static_cast<uint32_t>(plan->taps_resample.size());
-        std::vector<uint16_t> tab(static_cast<size_t>(plan->l) * gpu::f16taps_pairs_per_phase(plan->l, t1) * 2 + 8, 0);
-        plan->f16_unscale = gpu::f16taps_pack(plan->l, plan->taps_resample.data(), t1, tab.data());
-        plan->d_taps_f16.alloc(tab.size());
-        hip_check(hipMemcpyAsync(plan->d_taps_f16.ptr, tab.data(), tab.size() * 2, hipMemcpyHostToDevice, plan->stream),
-                  "hipMemcpy f16 taps");
-        hip_check(hipStreamSynchronize(plan->stream), "hipStreamSynchronize");  // `tab` dies here
-    }
-    if (plan->fused != 0) {
-        // division by sin(phi) through its reciprocal: only if it is exactly rounded for every x
-        const float rc = 1.0f / plan->sinphi;
-        const char *off = std::getenv("APTGPU_GENERAL_ENVELOPE");  // tests: force the general code
-        if (plan->fused_fast) plan->inv_sinphi = rc;  // a plain multiplication by the rounded reciprocal
-        else if (!(off && off[0] == '1') && gpu::verify_fast_divide(plan->device, plan->sinphi, rc)) plan->inv_sinphi = rc;
-    }
-    if (plan->fused == 2 || plan->fused == 3 || plan->fused == 4) {
-        const uint32_t t1 = static_cast<uint32_t>(plan->taps_resample.size());
-        Signal tab(static_cast<size_t>(plan->fused == 4 ? gpu::fused_phase_table_floats(plan->table_geom)
-                                                        : gpu::fused_any_table_floats(plan->l, t1)) + 16, 0.f);
-        if (plan->fused == 4)
-            gpu::fused_phase_table(plan->table_geom, static_cast<uint32_t>(plan->taps_lowpass.size()), plan->pw,
-                                   plan->taps_resample.data(), t1, tab.data());
-        else gpu::fused_any_table(plan->l, plan->taps_resample.data(), t1, tab.data());
-        upload(plan->d_taps_any, tab);
-        // (PHASE kernels with a tuned low-pass — kModeStrictPad2: the low-pass tables laid out for the kernel's bound)
-        Signal lp(plan->taps_lowpass);
-        plan->fused_pad_t2 = plan->fused == 4 ? gpu::fused_phase_pad_t2(static_cast<uint32_t>(lp.size()), plan->pw) : 0u;
-        if (plan->fused_pad_t2) {
-            lp.resize(plan->fused_pad_t2, 0.f);
-            Signal padded(lp);
-            padded.resize(lp.size() + 16, 0.f);
-            upload(plan->d_taps_lowpass_pad, padded);
-        }
-        Signal h2p(2 * (lp.size() + 1) + 16, 0.f);
-        gpu::fused_lowpass_pairs(lp.data(), static_cast<uint32_t>(lp.size()), h2p.data());
-        upload(plan->d_taps_lowpass_pairs, h2p);
-    }
-    if (plan->fused == 1) {
-        const uint32_t t1 = static_cast<uint32_t>(plan->taps_resample.size());
-        // (the kernel that will read it: fast plans run the fast instantiation, whose chunks may differ)
-        const int ch = gpu::fused_chunk_of(plan->m, plan->fused_fast);
-        const uint32_t t1_layout = plan->fused_pad_t1 ? plan->fused_pad_t1 : t1;
-        Signal hs(static_cast<size_t>(gpu::fused_tap_table_floats(plan->l, plan->m, t1_layout, ch)) + 16, 0.f);
-        if (plan->fused_mfma) {
-            // same buffer, different content: the bf16 fragments of the resampler's Toeplitz matrix
-            std::vector<uint32_t> tab(gpu::fused_mfma_table_dwords(plan->l, plan->m) + 16, 0u);
-            gpu::fused_mfma_table(plan->l, plan->m, plan->taps_resample.data(), t1, tab.data());
-            hs.assign(tab.size(), 0.f);
-            std::memcpy(hs.data(), tab.data(), tab.size() * sizeof(uint32_t));
-        } else if (plan->fused_f16) {
-            // same buffer, different content: half2 tap pairs as raw dwords
-            std::vector<uint32_t> tab(gpu::fused_f16_table_dwords(plan->l, plan->m, t1) + 16, 0u);
-            plan->f16_unscale = gpu::fused_f16_branch_taps(plan->l, plan->m, plan->taps_resample.data(), t1, tab.data());
-            hs.assign(tab.size(), 0.f);
-            std::memcpy(hs.data(), tab.data(), tab.size() * sizeof(uint32_t));
-        } else {
-            gpu::fused_branch_taps(plan->l, plan->m, plan->taps_resample.data(), t1, ch, hs.data(), t1_layout);
-        }
-        upload(plan->d_taps_branch, hs);
-        // (kModeStrictPad2: the low-pass tables laid out for the kernel's bound, zeros behind the filter's last tap)
-        Signal lp(plan->taps_lowpass);
-        if (plan->fused_pad_t2) {
-            lp.resize(plan->fused_pad_t2, 0.f);
-            Signal padded(lp);
-            padded.resize(lp.size() + 16, 0.f);
-            upload(plan->d_taps_lowpass_pad, padded);
-        }
-        Signal h2p(2 * (lp.size() + 1) + 16, 0.f);
-        gpu::fused_lowpass_pairs(lp.data(), static_cast<uint32_t>(lp.size()), h2p.data());
-        upload(plan->d_taps_lowpass_pairs, h2p);
-    }
-
-    // workspace: one set of max_batch slots per stream
-    plan->slots.resize(static_cast<size_t>(depth) * static_cast<size_t>(max_batch));
-    const uint64_t w = plan->max_work_len;
-    // (F in pixel-phase planes where a k_fused instantiation writes it: pw planes of f_plane_stride floats)
-    plan->plane_stride = plan->writes_planes() ? gpu::f_plane_stride(w, plan->pw) : 0u;  // (then pw >= 1)
-    for (auto &sl : plan->slots) {
-        // (resampled / demodulated / correlation are only needed by the unfused kernels: allocated on first use)
-        sl.filtered.alloc(std::max<uint64_t>(w, static_cast<uint64_t>(plan->pw) * plan->plane_stride) + 64);
-        sl.f_stride = plan->plane_stride;  // (what a call without step export leaves: run_call)
-        if (sync) {
-            sl.peaks.alloc(plan->max_rows + 2);
-            const uint64_t ng = w / gpu::sync_group_size() + 2;
-            const uint64_t chunks = ng / gpu::sync_chunk_groups() + 2;
-            sl.gm.alloc(ng + 64);
-            sl.words.alloc(ng + 64);
-            sl.nanw.alloc(ng + 64);
-            sl.slot_nt.alloc(chunks * gpu::sync_slot_cap());
-            sl.slot_cnt.alloc(chunks);
-            sl.orbit_ws.alloc(gpu::sync_orbit_ws_words(w, plan->spr));
-            sl.flags.alloc(32);
-            hip_check(hipMemsetAsync(sl.flags.ptr, 0, 32 * sizeof(uint32_t), plan->stream), "hipMemset flags");
-            if (plan->fused == 0) sl.correlation.alloc(w + 64);
-            if (plan->mode == APTGPU_MODE_GENERIC) sl.bits.alloc(w / 64 + plan->md / 64 + 4);
-        }
-    }
-    plan->d_results.alloc(plan->slots.size());
-    hip_check(hipMemsetAsync(plan->d_results.ptr, 0, sizeof(gpu::Result) * plan->slots.size(), plan->stream),
-              "hipMemset");
-    plan->d_slots.alloc(plan->slots.size());
-    // the uploads and memsets above ran on the plan's first stream: make them land before a decode can
-    // be enqueued on any of the others (a stream sync, not a device sync — other plans of this process,
-    // e.g. concurrent aptgpu_decode calls on other host threads, keep running)
-    plan->upload_slot_table();
+    upload(plan.get(), plan->d_taps_resample, plan->taps_resample);
+    upload(plan.get(), plan->d_taps_lowpass, plan->taps_lowpass);
+    upload(plan.get(), plan->d_one, Signal{1.f});
+    plan->fe = gpu::select_front_end(plan->l, plan->m, static_cast<uint32_t>(plan->taps_resample.size()),
+                                     static_cast<uint32_t>(plan->taps_lowpass.size()), plan->pw, plan->mode,
+                                     plan->work_is_multiple, plan->export_filtered, plan->psw);
+    note_unspecialised(plan.get());
+    upload_front_end_tables(plan.get());
+    alloc_workspace(plan.get());
     return plan.release();
 }
 
@@ -458,15 +335,15 @@ void aptgpu_plan::upload_slot_table()
     if (writes_planes()) {
         prm.hs = d_taps_branch.ptr;
         prm.table = d_taps_any.ptr;
-        prm.tab = table_geom;
-        prm.h2 = fused_pad_t2 ? d_taps_lowpass_pad.ptr : d_taps_lowpass.ptr;
+        prm.tab = fe.geom;
+        prm.h2 = fe.pad_t2 ? d_taps_lowpass_pad.ptr : d_taps_lowpass.ptr;
         prm.h2p = d_taps_lowpass_pairs.ptr;
         prm.t2 = static_cast<uint32_t>(taps_lowpass.size());
         prm.slots = d_slots.ptr;
         prm.cosphi2 = cosphi2;
         prm.sinphi = sinphi;
         prm.inv_sinphi = inv_sinphi;
-        prm.f16_unscale = fused_f16 ? f16_unscale : 0.f;
+        prm.f16_unscale = fe.f16 ? f16_unscale : 0.f;
         prm.coeff = d_taps_resample.ptr;
         prm.t1 = static_cast<uint32_t>(taps_resample.size());
         prm.want_gm = (sync && work_is_multiple) ? 1 : 0;
@@ -576,7 +453,7 @@ void aptgpu_plan::run_call(int count, const Input *ins, float *const *d_rows, co
     };
     auto timed = [&](const char *name, auto &&launch) { timed_on(cur, name, launch); };
 
-    const bool use_fused = fused != 0 && !keep_steps;
+    const bool use_fused = fe.kind != FrontEndKind::Unfused && !keep_steps;
     const bool want_sync = sync && work_is_multiple;
     // The layout of F this call leaves in its slots: pixel-phase planes from the k_fused instantiations, contiguous from
     // k_fused_any and the unfused kernels (a fused plan that exports steps).  Every consumer reads it from the slot table.
@@ -621,9 +498,10 @@ void aptgpu_plan::run_call(int count, const Input *ins, float *const *d_rows, co
         }
         // WAV ingest (wav.rs:30-51): mono PCM16 goes straight into the fused front end, anything
         // else is converted into the slot's f32 staging buffer first
+        // (a k_fused instantiation for f32 input only — odd m: no dword reads of sample pairs — gets the payload staged)
         const bool pcm16 = in.codec == static_cast<int>(apt::WavCodec::I16) && in.channels == 1 && use_fused &&
-                           (reinterpret_cast<uintptr_t>(in.ptr) & (fused == 1 ? 3u : 1u)) == 0 &&
-                           (fused != 1 || apt::gpu::fused_takes_pcm16(l, m));
+                           (reinterpret_cast<uintptr_t>(in.ptr) & (fe.kind == FrontEndKind::Split ? 3u : 1u)) == 0 &&
+                           (!writes_planes() || fe.variant[1] != kFusedNone);
         xin[static_cast<size_t>(i)] = in.ptr;
         is_pcm[static_cast<size_t>(i)] = pcm16 ? 1 : 0;
         if (in.codec >= 0 && !pcm16) {
@@ -693,14 +571,8 @@ void aptgpu_plan::run_call(int count, const Input *ins, float *const *d_rows, co
             for (int rf = 0; rf < rep_f; ++rf)
             for_chunks(idx, [&](const CallArgs &c, uint64_t max_w, uint32_t) {
                 timed_on(fs, "fused_front_end", [&] {
-                    const int kmode = fused_f16 ? 1 : (fused_mfma ? 3 : (fused_pad_t1 ? 4 : (fused_fast ? 2 : 0)));
                     int variant = -1;
-                    const bool ok = fused == 4 ? fused_phase_front_end(fs, table_geom, t2, pw, kmode, kind == 1, c,
-                                                                       d_fused_params.ptr, max_w, &variant)
-                                  : fused == 3 ? fused_table_front_end(fs, table_geom, kmode, kind == 1, c,
-                                                                       d_fused_params.ptr, max_w, &variant)
-                                               : fused_front_end(fs, l, m, t1, t2, pw, kmode, kind == 1, c,
-                                                                 d_fused_params.ptr, max_w, sw.fused_lds_pad, &variant);
+                    const bool ok = fused_front_end(fs, fe, kind == 1, c, d_fused_params.ptr, max_w, sw.fused_lds_pad, &variant);
                     for (uint32_t k = 0; k < c.count; ++k) {
                         slots[c.rec[k].slot].fused_variant = variant;
                         slots[c.rec[k].slot].fused_variant_i16 = kind == 1;
@@ -817,7 +689,7 @@ void aptgpu_plan::run_call(int count, const Input *ins, float *const *d_rows, co
             for_chunks(live, [&](const CallArgs &c, uint64_t max_w, uint32_t) {
                 if (!(skip & 1))
                     for (int r = 0; r < rep_w; ++r)
-                        timed("sync_nodes", [&] { sync_nodes(cur, c, d_slots.ptr, max_w, pw, spr, md, use_fused && fused_fast, !use_fused, sw); });
+                        timed("sync_nodes", [&] { sync_nodes(cur, c, d_slots.ptr, max_w, pw, spr, md, use_fused && fe.fast, !use_fused, sw); });
                 if (!(skip & 2))
                     for (int r = 0; r < rep_o; ++r)
                         timed("sync_orbit", [&] { sync_orbit(cur, c, d_slots.ptr, spr, md, pw, picker_force, sw); });

@@ -95,8 +95,9 @@ void resample_at(hipStream_t s, const float *x, uint64_t n, const float *coeff, 
                  uint32_t step, float *out, uint64_t w);
 }  // namespace apt
 
-// The opaque C-ABI plan.
-struct aptgpu_plan {
+// The opaque C-ABI plan: the host-side design of decode() (apt::PlanDesign: l, m, the taps, the sync geometry ...) and
+// what runs it on the device.
+struct aptgpu_plan : apt::PlanDesign {
     int device = 0;
     int mode = APTGPU_MODE_STRICT;
     // Pipeline over consecutive calls: the recordings of ONE decode_device call go through ONE launch
@@ -137,19 +138,6 @@ struct aptgpu_plan {
     uint32_t input_rate = 0;
     bool sync = true;
 
-    // first resample (decode.rs:65-77)
-    uint32_t l = 1, m = 1;
-    apt::Signal taps_resample;
-    // demodulation (decode.rs:89; dsp.rs:360-363)
-    float cosphi2 = 0.f, sinphi = 0.f;
-    // low-pass (decode.rs:95-102)
-    apt::Signal taps_lowpass;
-    // sync (decode.rs:204-216)
-    uint32_t spr = 0, md = 0, pw = 0, n_sync_taps = 0;
-    bool work_is_multiple = false;
-    // final resample to 4160 (decode.rs:158-159)
-    uint32_t l2 = 1, m2 = 1;
-
     size_t max_samples = 0;
     uint64_t max_work_len = 0;
     uint32_t max_rows = 0;
@@ -157,17 +145,11 @@ struct aptgpu_plan {
     // strict: RN(1/sinphi) if the exactly rounded fast divide verified for it, else 0 (apt_envelope.hpp);
     // fast mode: RN(1/sinphi)
     float inv_sinphi = 0.f;
-    bool fused_f16 = false;   // APTGPU_MODE_FP16_TAPS served by the specialised fused kernel (fp16 stage 1)
-    bool fused_fast = false;  // APTGPU_MODE_FAST served by the specialised fused kernel
-    bool fused_mfma = false;  // ... by its matrix-core form (kModeMfma: tuned tap counts, or APTGPU_FAST_MFMA=1)
-    uint32_t fused_pad_t1 = 0;  // != 0: the strict kernel compiled for this tap-count bound serves the plan (kModeStrictPad)
-    uint32_t fused_pad_t2 = 0;  // != 0: ... and for this low-pass bound (kModeStrictPad2: d_taps_lowpass_pad, FusedParams::t2)
-    // 0 unfused generic kernels, 1 compile-time specialised k_fused, 2 run-time k_fused_any,
-    // 3 k_fused with the table-driven stage 1 (run-time l / m / taps, specialised work-rate stages)
-    int fused = 0;
-    apt::gpu::TableGeom table_geom{};
+    apt::gpu::FrontEnd fe{};  // the front end of the plan's calls, chosen once (apt::gpu::select_front_end)
+    int fused() const { return static_cast<int>(fe.kind); }  // (stats.fused, aptgpu_plan_info.fused)
     apt::gpu::LaunchSwitches sw{};  // the A/B switches of the launch wrappers as the environment had them at plan creation
-    int picker_force = 0;  // 0 parallel picker; APTGPU_FORCE_WALK=1 -> 1 (the sequential fallback)
+    apt::gpu::PlanSwitches psw{};   // ... and the switches of the plan's shape
+    int picker_force = 0;  // 0 parallel picker; APTGPU_FORCE_WALK=1 -> 1 (the sequential fallback), APTGPU_PICKER_LDS=1 -> 4
 
     apt::DeviceBuffer<float> d_taps_resample, d_taps_lowpass, d_one, d_taps_branch, d_taps_lowpass_pairs, d_taps_any, d_taps_lowpass_pad;
     apt::DeviceBuffer<uint16_t> d_taps_f16;  // APTGPU_MODE_FP16_TAPS
@@ -203,10 +185,7 @@ struct aptgpu_plan {
     std::vector<Slot> slots;
     apt::DeviceBuffer<apt::gpu::SlotPtrs> d_slots;  // the slots' pointers, for the per-call launches
     apt::DeviceBuffer<apt::gpu::FusedParams> d_fused_params;  // parameters of the specialised front end
-    // Does this plan's front end write F in pixel-phase planes (apt::gpu::f_index)?  The k_fused instantiations do (SPLIT,
-    // TABLE and PHASE stage 1: fused 1, 3, 4); k_fused_any (2) and the unfused kernels (0) write it contiguously.  The ONE
-    // place that says so: the slots' buffer size, their f_stride and run_call's choice of front end all ask here.
-    bool writes_planes() const { return fused == 1 || fused == 3 || fused == 4; }
+    bool writes_planes() const { return fe.writes_planes(); }  // F in pixel-phase planes (apt::gpu::f_index)
     uint32_t plane_stride = 0;  // plane length of such a plan (f_plane_stride of max_work_len), else 0
     void upload_slot_table();                       // (re)writes d_slots + d_fused_params; synchronises plan->stream
     apt::DeviceBuffer<apt::gpu::Result> d_results;

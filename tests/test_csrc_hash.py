@@ -12,7 +12,7 @@ def _tree(tmp_path):
     d = tmp_path / "noaa_apt_amd" / "csrc"
     d.mkdir(parents=True)
     src = os.path.join(ROOT, "noaa_apt_amd", "csrc")
-    for n in ("apt_kernels.hpp", "apt_sync_corr.hpp", "apt_envelope.hpp", "Makefile", "apt_kernels_sync.hip",
+    for n in ("apt_kernels.hpp", "apt_front_end.hpp", "apt_front_end.cpp", "apt_kernels_fused_any_geom.hpp", "apt_sync_corr.hpp", "apt_envelope.hpp", "Makefile", "apt_kernels_sync.hip",
               "apt_kernels_generic.hip", "apt_kernels_fused_impl.hpp", "apt_kernels_fused_variant.hip",
               "apt_kernels_fused_variants.hpp",
               "apt_kernels_fused_any_impl.hpp", "apt_plan.hip"):

@@ -16,8 +16,9 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# headers every kernel translation unit includes, and the build flags
-_COMMON = ("apt_kernels.hpp", "apt_sync_corr.hpp", "apt_envelope.hpp", "Makefile")
+# headers every kernel translation unit includes (apt_kernels.hpp takes the run-time geometry structs of the front ends from
+# apt_front_end.hpp), and the build flags
+_COMMON = ("apt_kernels.hpp", "apt_front_end.hpp", "apt_sync_corr.hpp", "apt_envelope.hpp", "Makefile")
 _GROUPS = {
     # k_fused<...>: the specialised front ends (SPLIT / TABLE / PHASE): one source compiled once per row of the list in
     # apt_kernels_fused_variants.hpp

@@ -1,7 +1,7 @@
 // tools/ubench/lds_pat.hip <patterns.txt> — LDS read throughput of 8-byte reads for arbitrary per-lane start entries: each line of the
 // file is "name e0 e1 ... e255" (entries of 8 bytes, one per thread of a 256-thread workgroup; -1 = lane idle).  Eight
 // ds_read_b64 in flight per wave, three workgroups per CU: cycles per wave-read (round 5: the model behind the PHASE
-// stage 1's thread assignment lists, apt_kernels_fused.hip fused_phase_table).
+// stage 1's thread assignment lists, apt_front_end.cpp fused_phase_table).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
