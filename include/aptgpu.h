@@ -875,6 +875,98 @@ int aptgpu_plan_despeckle_device(aptgpu_plan *plan, int count, const float *cons
 /* Waits for the despeckle stage of the last call and copies the records. */
 int aptgpu_plan_despeckle_results(aptgpu_plan *plan, int count, aptgpu_despeckle_result *results);
 
+/* ---- thermal calibration: brightness temperature of an infrared channel ----
+ * The reference has no calibration, so the definition is this library's; tests/np_thermal_model.py states it in
+ * numpy.  It follows the procedure of the NOAA KLM User's Guide §7.1.2.4 with the 8-bit APT telemetry scaled to
+ * 10-bit counts.  Opt-in, a stage of its own behind the decode: rows in, a Kelvin plane (and optionally a u8 scale
+ * image in the standard row layout) out; nothing else changes when it is not called.
+ *  - h = n / 2080 whole rows.  aptgpu_read_telemetry's stage runs first and gives telemetry_row, the wedge values
+ *    v[1..16] of the selected channel (settings.channel: 0 = A, 1 = B; its columns start at base = 1040 * channel)
+ *    and its index for aptgpu_channel_name().  h < 200 is reason 2; a failed decode in front of it (plan form) 4.
+ *  - The identity is settings.channel_id, or with -1 the telemetry's index.  3 ("4"), 4 ("5") and 5 ("3b") pick the
+ *    coefficient set; anything else is reason 13 (APTGPU_THERMAL_REASON_CHANNEL), not a thermal channel.
+ *  - Space view: for each of the 128 rows from telemetry_row the f32 mean of columns [base + 44, base + 82), summed
+ *    sequentially and divided by 38.  The 128 means are ranked by IEEE totalOrder on their bits, ties by row; the 16
+ *    lowest and the 16 highest are dropped (minute markers) and `space` is the f64 mean of the other 96, in row order.
+ *  - Scalars, all f64, plain + - * / in this order, never contracted:
+ *      y = {31, 63, 95, 127, 159, 191, 224, 255, 0}, x = v[1..9]; mx = sum(x) / 9, my = sum(y) / 9,
+ *      sxy = sum((x - mx) * (y - my)), sxx = sum((x - mx) * (x - mx)), slope = sxy / sxx, icpt = my - slope * mx,
+ *      count10(u) = 4 * (slope * u + icpt);
+ *      C_i = count10(v[9 + i]), T_i = (prt[i][0] + prt[i][1] * C_i) + prt[i][2] * (C_i * C_i), i = 1..4,
+ *      t_bb = (((T_1 + T_2) + T_3) + T_4) / 4, t_bb* = A + B * t_bb,
+ *      n_bb = (c1 * ((nu * nu) * nu)) / (exp((c2 * nu) / t_bb*) - 1), c1 = 1.1910427e-5, c2 = 1.4387752,
+ *      c_bb = count10(v[15]), c_space = count10(space).
+ *    sxx == 0, a non-finite scalar or c_space == c_bb is reason 14 (APTGPU_THERMAL_REASON_DEGENERATE).
+ *  - Per pixel x of the video columns [base + 86, base + 995), 909 a row, in f32 with every scalar rounded to f32
+ *    (k1 = c1 * nu^3 and k2 = c2 * nu are rounded after the f64 product):
+ *      C_e = 4 * (slope * x + icpt), N_lin = N_s + ((n_bb - N_s) * (c_space - C_e)) / (c_space - c_bb),
+ *      N_e = N_lin + ((b0 + b1 * N_lin) + b2 * (N_lin * N_lin)), T = (k2 / log(1 + k1 / N_e) - A) / B,
+ *      T = NaN unless N_e > 0 and N_e is finite.
+ *  - The scale image (image_channels 1 or 4), in f32: s = (T - t_low) / (t_high - t_low),
+ *    level = (uint8)(min(max(s, 0), 1) * 255 + 0.5), with APTGPU_THERMAL_COLD_WHITE 255 - level.  Gray: the level,
+ *    0 where T is NaN.  RGBA: palette[level] (default R = G = B = level) with A = 255; (0, 0, 0, 0) where T is NaN.
+ *    Every column outside the channel's video is 0 (A = 255).
+ *  - A failed record (any reason) leaves the planes of its rows all NaN / level 0 (A = 0) in the plan form; the
+ *    host-array forms return APTGPU_ERR_INTERNAL with the record filled and no planes.
+ * The coefficients are the caller's.  The per-satellite values (the four PRT polynomials, and per channel the
+ * centroid wave number nu, the effective-temperature line A, B, the space radiance N_s and the non-linearity
+ * b0, b1, b2) are tabulated in the NOAA KLM User's Guide, Appendix D (one section per satellite); this library
+ * ships no presets. */
+#define APTGPU_THERMAL_COLD_WHITE 1u        /* settings.flags: cold is white (the usual infrared rendering) */
+#define APTGPU_THERMAL_REASON_CHANNEL 13    /* aptgpu_thermal_result.reason */
+#define APTGPU_THERMAL_REASON_DEGENERATE 14
+#define APTGPU_THERMAL_PX 909               /* floats per row of the Kelvin plane */
+typedef struct aptgpu_thermal_coeffs {
+    uint32_t struct_size; /* sizeof(aptgpu_thermal_coeffs) */
+    uint32_t reserved;
+    double prt[4][3];     /* T_i = prt[i][0] + prt[i][1] * C + prt[i][2] * C^2 */
+    double channel[3][7]; /* 3B, 4, 5 (in this order): nu, A, B, N_s, b0, b1, b2 */
+} aptgpu_thermal_coeffs;  /* a non-finite value or B == 0: APTGPU_ERR_INVALID */
+typedef struct aptgpu_thermal_settings {
+    uint32_t struct_size;   /* sizeof(aptgpu_thermal_settings) */
+    int32_t channel;        /* 0 = A, 1 = B */
+    int32_t channel_id;     /* -1: from the telemetry; else an index of aptgpu_channel_name() */
+    int32_t image_channels; /* 0: no scale image; 1 gray; 4 RGBA */
+    uint32_t flags;         /* APTGPU_THERMAL_COLD_WHITE; any other bit is APTGPU_ERR_INVALID */
+    float t_low, t_high;    /* Kelvin at levels 0 and 255; finite, t_high > t_low (else APTGPU_ERR_INVALID) */
+    uint32_t reserved;
+    const uint8_t *palette; /* nullable: 256 * 3 RGB bytes by level (image_channels 4 only, else APTGPU_ERR_INVALID) */
+} aptgpu_thermal_settings;
+typedef struct aptgpu_thermal_result {
+    int32_t status;         /* APTGPU_OK or APTGPU_ERR_INTERNAL */
+    int32_t reason;         /* 0; 2 too short for telemetry; 4 the decode before it failed; 13; 14 */
+    uint32_t height;        /* whole rows */
+    uint32_t telemetry_row;
+    int32_t channel_id;     /* the identity used (-1: the telemetry gave none) */
+    uint32_t reserved;
+    uint64_t n_nan;         /* NaN pixels of the Kelvin plane */
+    double slope, icpt, space, c_space, c_bb, t_bb, n_bb;
+    float t_min, t_max;     /* over the finite pixels of the Kelvin plane; NaN when there is none */
+} aptgpu_thermal_result;
+/* coeffs and settings are required.  *kelvin: malloc'd, height * 909 floats; *image (required iff image_channels != 0):
+ * malloc'd, height * 2080 * image_channels bytes (aptgpu_free both); info nullable. */
+int aptgpu_calibrate_thermal(const aptgpu_context *ctx, const float *signal, size_t n,
+                             const aptgpu_thermal_coeffs *coeffs, const aptgpu_thermal_settings *settings,
+                             float **kelvin, uint8_t **image, aptgpu_thermal_result *info, char *err, size_t err_cap);
+/* The same on the CPU, in plain C++ (no GPU needed): the same scalars bit for bit, the same f32 pixel arithmetic
+ * except for the C library's logf. */
+int aptgpu_calibrate_thermal_host(const float *signal, size_t n, const aptgpu_thermal_coeffs *coeffs,
+                                  const aptgpu_thermal_settings *settings, float **kelvin, uint8_t **image,
+                                  aptgpu_thermal_result *info, char *err, size_t err_cap);
+/* Device-resident, chained behind the last aptgpu_plan_decode_device call on each recording's stream without a host
+ * round trip (the row count comes from the decode record on the device; with a rows_cap below the decoded height the
+ * rows the decode wrote).  d_rows[i] is the rows buffer given to the decode call (same rows_cap[i]); d_kelvin[i]
+ * holds rows_cap[i] * 909 floats; d_images (required iff image_channels != 0) rows_cap[i] * 2080 * image_channels
+ * bytes each, 4-byte aligned for RGBA, which the PNG, projection and composite calls on device images take as they
+ * are.  Neither may overlap any d_rows[j] (APTGPU_ERR_INVALID).  Timer names: image_telemetry,
+ * image_thermal_space, image_thermal_setup, image_thermal_map. */
+int aptgpu_plan_calibrate_thermal_device(aptgpu_plan *plan, int count, const float *const *d_rows,
+                                         const size_t *rows_cap, const aptgpu_thermal_coeffs *coeffs,
+                                         const aptgpu_thermal_settings *settings, float *const *d_kelvin,
+                                         uint8_t *const *d_images, char *err, size_t err_cap);
+/* Waits for the thermal stage of the last call and copies the records. */
+int aptgpu_plan_thermal_results(aptgpu_plan *plan, int count, aptgpu_thermal_result *results);
+
 /* ====================================================================== */
 /* 5. WAV ingest in front of decode()                 */
 /* ====================================================================== */

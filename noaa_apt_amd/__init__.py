@@ -32,6 +32,9 @@ Names, argument meaning and error behaviour follow the reference:
     Plan.composite_device_images                           several of them on one map grid
     despeckle, despeckle_host, DespeckleSettings,          the reference's to-do list, docs/development.md:139: a
     process(despeckle=...), Plan.despeckle_device          band-aware median of the f32 rows in front of process()
+    calibrate_thermal, calibrate_thermal_host,             brightness temperature of an infrared channel from the
+    ThermalCoefficients, ThermalSettings,                  telemetry frame (NOAA KLM User's Guide §7.1.2.4), DESIGN.md §19
+    Plan.calibrate_thermal_device
     percent, get_min, get_max, map_signal_u8               /root/reference/src/misc.rs:119, dsp.rs:20-54
     read_telemetry, Telemetry                              /root/reference/src/telemetry.rs:19-243
 
@@ -50,6 +53,8 @@ from .api import (  # noqa: F401
     get_min, get_max, percent, map_signal_u8, read_telemetry, process, lab_from_rgb, lab_to_rgb,
     encode_png, png_bound, PNG_REASON_CAPACITY,
     DespeckleSettings, DespeckleResult, despeckle, despeckle_host,
+    ThermalCoefficients, ThermalSettings, ThermalResult, calibrate_thermal, calibrate_thermal_host,
+    THERMAL_COLD_WHITE, THERMAL_REASON_CHANNEL, THERMAL_REASON_DEGENERATE, THERMAL_PX,
     Projection, ProjectionSettings, projection_fit, project_image, PROJECT_REASON_CAPACITY,
     Composite, composite_images, COMPOSITE_REASON_PASS, COMPOSITE_MAX_PASSES,
     SatName, RefTime, OrbitSettings, sat_track, sat_track_host, south_to_north_pass, SAT_REASON_SGP4,

@@ -178,6 +178,28 @@ class DespeckleResult(C.Structure):
                 ("reserved2", C.c_uint32)]
 
 
+class _CThermalCoeffs(C.Structure):
+    """aptgpu_thermal_coeffs"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("prt", (C.c_double * 3) * 4),
+                ("channel", (C.c_double * 7) * 3)]
+
+
+class _CThermalSettings(C.Structure):
+    """aptgpu_thermal_settings"""
+    _fields_ = [("struct_size", C.c_uint32), ("channel", C.c_int32), ("channel_id", C.c_int32),
+                ("image_channels", C.c_int32), ("flags", C.c_uint32), ("t_low", C.c_float), ("t_high", C.c_float),
+                ("reserved", C.c_uint32), ("palette", C.c_void_p)]
+
+
+class ThermalResult(C.Structure):
+    """aptgpu_thermal_result: the frame and identity used, the f64 scalars of the calibration and what the Kelvin
+    plane holds (n_nan, t_min, t_max)."""
+    _fields_ = [("status", C.c_int32), ("reason", C.c_int32), ("height", C.c_uint32), ("telemetry_row", C.c_uint32),
+                ("channel_id", C.c_int32), ("reserved", C.c_uint32), ("n_nan", C.c_uint64), ("slope", C.c_double),
+                ("icpt", C.c_double), ("space", C.c_double), ("c_space", C.c_double), ("c_bb", C.c_double),
+                ("t_bb", C.c_double), ("n_bb", C.c_double), ("t_min", C.c_float), ("t_max", C.c_float)]
+
+
 class WavSpec(C.Structure):
     """aptgpu_wav_spec: hound::WavSpec plus where the samples are."""
     _fields_ = [("channels", C.c_uint16), ("bits_per_sample", C.c_uint16),
@@ -394,6 +416,14 @@ def lib():
     L.aptgpu_despeckle_host.argtypes = [_f32p, sz, cds, C.POINTER(_f32p), C.POINTER(DespeckleResult), C.c_char_p, sz]
     L.aptgpu_plan_despeckle_device.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz), cds, C.POINTER(vp), C.c_char_p, sz]
     L.aptgpu_plan_despeckle_results.argtypes = [vp, i32, C.POINTER(DespeckleResult)]
+    cth = (C.POINTER(_CThermalCoeffs), C.POINTER(_CThermalSettings))
+    L.aptgpu_calibrate_thermal.argtypes = [cp, _f32p, sz, *cth, C.POINTER(_f32p), C.POINTER(_u8p),
+                                           C.POINTER(ThermalResult), C.c_char_p, sz]
+    L.aptgpu_calibrate_thermal_host.argtypes = [_f32p, sz, *cth, C.POINTER(_f32p), C.POINTER(_u8p),
+                                                C.POINTER(ThermalResult), C.c_char_p, sz]
+    L.aptgpu_plan_calibrate_thermal_device.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz), *cth, C.POINTER(vp),
+                                                       C.POINTER(vp), C.c_char_p, sz]
+    L.aptgpu_plan_thermal_results.argtypes = [vp, i32, C.POINTER(ThermalResult)]
     _lib = L
     return L
 
@@ -1409,6 +1439,115 @@ def despeckle_host(signal, settings=None, return_info=False):
     return (y, info) if return_info else y
 
 
+THERMAL_COLD_WHITE = 1
+THERMAL_REASON_CHANNEL = 13
+THERMAL_REASON_DEGENERATE = 14
+THERMAL_PX = 909
+_THERMAL_IDS = {"4": 3, "5": 4, "3b": 5}
+
+
+class ThermalCoefficients:
+    """aptgpu_thermal_coeffs: the caller's calibration coefficients (NOAA KLM User's Guide, Appendix D; no presets are
+    shipped).  prt: 4 x 3, T_i = prt[i][0] + prt[i][1] * C + prt[i][2] * C^2 of the four black-body thermometers;
+    ch3b, ch4, ch5: (nu, A, B, N_s, b0, b1, b2) of each infrared channel."""
+
+    def __init__(self, prt, ch3b, ch4, ch5):
+        self.prt = np.asarray(prt, dtype=np.float64)
+        self.channel = np.asarray([ch3b, ch4, ch5], dtype=np.float64)
+        if self.prt.shape != (4, 3) or self.channel.shape != (3, 7):
+            raise InvalidError("thermal: prt must be 4 x 3 and every channel set 7 values")
+
+    def _c(self, struct_size=None):
+        c = _CThermalCoeffs()
+        c.struct_size = C.sizeof(_CThermalCoeffs) if struct_size is None else int(struct_size)
+        for i in range(4):
+            for k in range(3):
+                c.prt[i][k] = self.prt[i, k]
+        for i in range(3):
+            for k in range(7):
+                c.channel[i][k] = self.channel[i, k]
+        return c
+
+
+class ThermalSettings:
+    """aptgpu_thermal_settings.  channel: "A" / "B" (or 0 / 1), the half of the row image to calibrate.  channel_id:
+    None takes the identity from the telemetry (wedge 16); "4", "5", "3b" (or an index of the channel-name table)
+    forces it.  t_low / t_high: Kelvin at levels 0 and 255 of the scale image; cold_white: 255 - level.  palette: 256 x 3
+    RGB bytes by level (RGBA image only).  image_channels: 0 no scale image, 1 gray, 4 RGBA (default: 4 with a palette,
+    else 0)."""
+
+    def __init__(self, channel, channel_id=None, *, t_low, t_high, cold_white=True, palette=None, image_channels=None,
+                 flags=None):
+        self.channel, self.channel_id, self.t_low, self.t_high = channel, channel_id, t_low, t_high
+        self.cold_white, self.palette, self.flags = cold_white, palette, flags
+        self.image_channels = (4 if palette is not None else 0) if image_channels is None else image_channels
+
+    def _c(self, struct_size=None):
+        """-> (struct, the object that keeps the palette's bytes alive)"""
+        ch = {"A": 0, "B": 1}.get(self.channel, self.channel)
+        cid = -1 if self.channel_id is None else _THERMAL_IDS.get(self.channel_id, self.channel_id)
+        if isinstance(cid, str):
+            raise InvalidError(f"thermal: unknown channel identity {self.channel_id!r}")
+        flags = (THERMAL_COLD_WHITE if self.cold_white else 0) if self.flags is None else int(self.flags)
+        pal = None
+        if self.palette is not None:
+            pal = np.ascontiguousarray(self.palette, dtype=np.uint8)
+            if pal.shape != (256, 3):
+                raise InvalidError("thermal: the palette must be 256 x 3 bytes")
+        c = _CThermalSettings(C.sizeof(_CThermalSettings) if struct_size is None else int(struct_size), int(ch),
+                              int(cid), int(self.image_channels), flags, float(self.t_low), float(self.t_high), 0,
+                              pal.ctypes.data if pal is not None else None)
+        return c, pal
+
+
+def _thermal_c(coeffs, settings):
+    if not isinstance(coeffs, ThermalCoefficients) or not isinstance(settings, ThermalSettings):
+        raise InvalidError("thermal: coeffs must be a ThermalCoefficients and settings a ThermalSettings")
+    try:
+        return (coeffs._c(),) + settings._c()
+    except (TypeError, ValueError, OverflowError) as e:
+        raise InvalidError(f"thermal: {e}") from None
+
+
+def _thermal_call(fn, head, signal, coeffs, settings):
+    cc, cs, keep = _thermal_c(coeffs, settings)
+    x, xp = _as_f32(signal)
+    kelvin, image, info = _f32p(), _u8p(), ThermalResult()
+    err = C.create_string_buffer(_ERRCAP)
+    ch = int(cs.image_channels)
+    try:
+        _check(fn(*head, xp, x.size, C.byref(cc), C.byref(cs), C.byref(kelvin), C.byref(image) if ch else None,
+                  C.byref(info), err, _ERRCAP), err)
+    except AptError as e:
+        e.info = info  # (the record of a failed calibration: status, reason, the scalars so far)
+        raise
+    del keep
+    h = x.size // PX_PER_ROW
+    k = _take(kelvin, h * THERMAL_PX).reshape(h, THERMAL_PX)
+    img = None
+    if ch:
+        img = _take(image, h * PX_PER_ROW * ch, np.uint8)
+        img = img.reshape(h, PX_PER_ROW) if ch == 1 else img.reshape(h, PX_PER_ROW, 4)
+    return k, img, info
+
+
+def calibrate_thermal(signal, coeffs, settings, context=None):
+    """Brightness temperature of an infrared channel of decoded rows, on the GPU: the telemetry
+    frame gives the count scale, the black body's thermometers and its view, the space columns the space view; every
+    video pixel of the channel becomes a temperature.  Returns (kelvin, image, info): the height x 909 f32 Kelvin
+    plane, the height x 2080 (x 4) u8 scale image in the standard row layout (None with image_channels 0) and the
+    ThermalResult.  A failed calibration (too short, not a thermal channel, degenerate) raises InternalError whose
+    `info` attribute is the record."""
+    cctx = (context or Context())._c()
+    return _thermal_call(lib().aptgpu_calibrate_thermal, (C.byref(cctx),), signal, coeffs, settings)
+
+
+def calibrate_thermal_host(signal, coeffs, settings):
+    """calibrate_thermal() on the CPU, in plain C++ (no GPU needed): the same scalars, the same f32 pixel
+    arithmetic up to the C library's logf."""
+    return _thermal_call(lib().aptgpu_calibrate_thermal_host, (), signal, coeffs, settings)
+
+
 def process(context, signal, contrast_adjustment, rotate=Rotate.NO, color=None, orbit=None,
             return_info=False, png=False, layers=None, projection=None, despeckle=None):  # noqa: A002
     """noaa_apt::process (noaa_apt.rs:132-235).  Returns the height x 2080 u8
@@ -1692,6 +1831,25 @@ class Plan:
     def despeckle_results(self, count=1) -> List["DespeckleResult"]:
         arr = (DespeckleResult * count)()
         _check(lib().aptgpu_plan_despeckle_results(self._p, count, arr))
+        return list(arr)
+
+    def calibrate_thermal_device(self, d_rows: Sequence[int], rows_cap: Sequence[int], d_kelvin: Sequence[int],
+                                 coeffs, settings, d_images: Optional[Sequence[int]] = None):
+        """The thermal calibration of the recordings of the last decode_device call, chained on the device behind their
+        decode.  d_kelvin[i] holds rows_cap[i] * 909 floats, d_images[i] (with settings.image_channels) rows_cap[i] *
+        2080 * image_channels bytes; neither may overlap d_rows.  Records through thermal_results()."""
+        k = len(d_rows)
+        cc, cs, keep = _thermal_c(coeffs, settings)
+        err = C.create_string_buffer(_ERRCAP)
+        _check(lib().aptgpu_plan_calibrate_thermal_device(
+            self._p, k, (C.c_void_p * k)(*d_rows), (C.c_size_t * k)(*rows_cap), C.byref(cc), C.byref(cs),
+            (C.c_void_p * k)(*d_kelvin), (C.c_void_p * k)(*d_images) if d_images is not None else None, err, _ERRCAP),
+            err)
+        del keep
+
+    def thermal_results(self, count=1) -> List["ThermalResult"]:
+        arr = (ThermalResult * count)()
+        _check(lib().aptgpu_plan_thermal_results(self._p, count, arr))
         return list(arr)
 
     def process_device_image(self, d_rows: Sequence[int], rows_cap: Sequence[int], contrast_adjustment,

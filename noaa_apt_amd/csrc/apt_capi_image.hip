@@ -8,6 +8,7 @@
 #include "apt_capi_util.hpp"
 #include "apt_kernels_color.hpp"
 #include "apt_kernels_despeckle.hpp"
+#include "apt_kernels_thermal.hpp"
 #include "apt_kernels_eqfloat.hpp"
 #include "apt_kernels_png.hpp"
 #include "apt_kernels_project.hpp"
@@ -618,6 +619,28 @@ int plan_process_image(aptgpu_plan *plan, int count, const float *const *d_rows,
     if (q.colored) plan->set_palette(q.palette, q.lab);
     plan->enqueue_images(q, count, d_rows, rows_cap);
     return APTGPU_OK;
+}
+
+
+// the kernel-argument forms of the caller's coefficients and table
+apt::gpu::ThermalCoeffs thermal_coeffs(const aptgpu_thermal_coeffs &c)
+{
+    apt::gpu::ThermalCoeffs k;
+    std::memcpy(k.prt, c.prt, sizeof k.prt);
+    std::memcpy(k.channel, c.channel, sizeof k.channel);
+    return k;
+}
+apt::gpu::ThermalTable thermal_table(const apt::thermal::Settings &st)
+{
+    apt::gpu::ThermalTable t{};
+    t.has_palette = st.palette ? 1u : 0u;
+    if (st.palette) std::memcpy(t.rgb, st.palette, sizeof t.rgb);
+    return t;
+}
+apt::gpu::ThermalLaunch thermal_launch(const apt::thermal::Settings &st, const float *x, float *kelvin, uint8_t *image)
+{
+    return apt::gpu::ThermalLaunch{x,          nullptr,   0,         0,      st.channel, st.channel_id, st.image_channels,
+                                   st.cold_white, st.t_low, st.t_high, kelvin, image};
 }
 
 }  // namespace
@@ -1460,6 +1483,146 @@ int aptgpu_plan_despeckle_results(aptgpu_plan *plan, int count, aptgpu_despeckle
             apt::hip_check(hipMemcpy(results + i, apt::gpu::despeckle_ws_record(plan->slot_of(i).despeckle_ws.ptr),
                                      sizeof(aptgpu_despeckle_result), hipMemcpyDeviceToHost),
                            "hipMemcpy");
+    } catch (const apt::Error &) {
+        return APTGPU_ERR_HIP;
+    }
+    return APTGPU_OK;
+}
+
+int aptgpu_calibrate_thermal(const aptgpu_context *ctx, const float *signal, size_t n,
+                             const aptgpu_thermal_coeffs *coeffs, const aptgpu_thermal_settings *settings,
+                             float **kelvin, uint8_t **image, aptgpu_thermal_result *info, char *err, size_t err_cap)
+{
+    if ((!signal && n) || !kelvin) return APTGPU_ERR_INVALID;
+    *kelvin = nullptr;
+    if (image) *image = nullptr;
+    return guarded(err, err_cap, [&] {
+        const apt::thermal::Settings st = apt::thermal::check_settings(coeffs, settings);
+        if ((st.image_channels != 0) != (image != nullptr))
+            throw Error{ErrorKind::Invalid, "thermal: image is required exactly when image_channels is not 0"};
+        ImageCall c(ctx, signal, n);
+        hipStream_t s = c.sc.stream;
+        const size_t h = n / 2080u;
+        const size_t image_bytes = h * 2080u * static_cast<size_t>(st.image_channels);
+        apt::DeviceBuffer<float> d_kelvin;
+        apt::DeviceBuffer<uint8_t> d_image;
+        apt::DeviceBuffer<char> ws;
+        d_kelvin.alloc(h * APTGPU_THERMAL_PX + 16);
+        d_image.alloc(image_bytes + 16);
+        ws.alloc(apt::gpu::thermal_ws_bytes());
+        apt::gpu::ThermalLaunch l = thermal_launch(st, c.d_x.ptr, d_kelvin.ptr, st.image_channels ? d_image.ptr : nullptr);
+        l.n = l.cap = n;
+        apt::gpu::image_telemetry(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, apt::gpu::thermal_ws_telemetry(ws.ptr), false);
+        apt::gpu::thermal_space(s, l, ws.ptr);
+        apt::gpu::thermal_setup(s, l, thermal_coeffs(*coeffs), ws.ptr);
+        apt::gpu::thermal_map(s, l, thermal_table(st), ws.ptr);
+        apt::hip_check(hipGetLastError(), "kernel launch (thermal stage)");
+        apt::gpu::ThermalRecord r{};
+        apt::hip_check(hipMemcpyAsync(&r, apt::gpu::thermal_ws_record(ws.ptr), sizeof r, hipMemcpyDeviceToHost, s),
+                       "hipMemcpyAsync D2H");
+        apt::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
+        if (info) apt::gpu::thermal_record_to_public(r, info);
+        if (r.status != 0) throw Error{ErrorKind::Internal, apt::thermal::reason_text(r.reason)};
+        float *hk = c.sc.download_malloc(d_kelvin.ptr, h * APTGPU_THERMAL_PX);
+        if (st.image_channels) {
+            size_t n_out = 0;
+            try {
+                to_host(s, d_image.ptr, image_bytes, image, &n_out);
+            } catch (...) {
+                std::free(hk);
+                throw;
+            }
+        }
+        *kelvin = hk;
+        return APTGPU_OK;
+    });
+}
+
+int aptgpu_calibrate_thermal_host(const float *signal, size_t n, const aptgpu_thermal_coeffs *coeffs,
+                                  const aptgpu_thermal_settings *settings, float **kelvin, uint8_t **image,
+                                  aptgpu_thermal_result *info, char *err, size_t err_cap)
+{
+    if ((!signal && n) || !kelvin) return APTGPU_ERR_INVALID;
+    *kelvin = nullptr;
+    if (image) *image = nullptr;
+    return guarded(err, err_cap, [&] {
+        const apt::thermal::Settings st = apt::thermal::check_settings(coeffs, settings);
+        if ((st.image_channels != 0) != (image != nullptr))
+            throw Error{ErrorKind::Invalid, "thermal: image is required exactly when image_channels is not 0"};
+        const size_t h = n / 2080u;
+        float *hk = host_alloc<float>(h * APTGPU_THERMAL_PX);
+        uint8_t *hi = nullptr;
+        try {
+            if (st.image_channels) hi = host_alloc<uint8_t>(h * 2080u * static_cast<size_t>(st.image_channels));
+            apt::thermal::run_host(signal, n, *coeffs, st, hk, hi, info);
+        } catch (...) {
+            std::free(hk);
+            std::free(hi);
+            throw;
+        }
+        *kelvin = hk;
+        if (image) *image = hi;
+        return APTGPU_OK;
+    });
+}
+
+int aptgpu_plan_calibrate_thermal_device(aptgpu_plan *plan, int count, const float *const *d_rows,
+                                         const size_t *rows_cap, const aptgpu_thermal_coeffs *coeffs,
+                                         const aptgpu_thermal_settings *settings, float *const *d_kelvin,
+                                         uint8_t *const *d_images, char *err, size_t err_cap)
+{
+    if (!plan || count < 0 || !d_rows || !rows_cap || !d_kelvin) return APTGPU_ERR_INVALID;
+    return guarded(err, err_cap, [&] {
+        const apt::thermal::Settings st = apt::thermal::check_settings(coeffs, settings);
+        if ((st.image_channels != 0) != (d_images != nullptr))
+            throw Error{ErrorKind::Invalid, "thermal: d_images is required exactly when image_channels is not 0"};
+        if (static_cast<size_t>(count) > plan->last_slots.size())
+            throw Error{ErrorKind::Invalid, "count exceeds the recordings of the last decode call"};
+        const auto overlaps_rows = [&](const void *p, size_t bytes) {
+            const uintptr_t o0 = reinterpret_cast<uintptr_t>(p), o1 = o0 + bytes;
+            for (int j = 0; j < count; ++j) {
+                const uintptr_t r0 = reinterpret_cast<uintptr_t>(d_rows[j]);
+                const uintptr_t r1 = r0 + rows_cap[j] * 2080u * sizeof(float);
+                if (r0 && ((o0 < r1 && r0 < o1) || o0 == r0)) return true;
+            }
+            return false;
+        };
+        for (int i = 0; i < count; ++i) {
+            if (!d_rows[i] || !d_kelvin[i] || (d_images && !d_images[i]))
+                throw Error{ErrorKind::Invalid, "null device pointer"};
+            if (overlaps_rows(d_kelvin[i], rows_cap[i] * APTGPU_THERMAL_PX * sizeof(float)))
+                throw Error{ErrorKind::Invalid, "d_kelvin overlaps d_rows"};
+            if (d_images && overlaps_rows(d_images[i], rows_cap[i] * 2080u * static_cast<size_t>(st.image_channels)))
+                throw Error{ErrorKind::Invalid, "d_images overlaps d_rows"};
+            if (st.image_channels == 4 && (reinterpret_cast<uintptr_t>(d_images[i]) & 3u))
+                throw Error{ErrorKind::Invalid, "d_images must be 4-byte aligned"};
+        }
+        apt::hip_check(hipSetDevice(plan->device), "hipSetDevice");
+        const apt::gpu::ThermalCoeffs kc = thermal_coeffs(*coeffs);
+        const apt::gpu::ThermalTable table = thermal_table(st);
+        for (int i = 0; i < count; ++i)
+            plan->enqueue_thermal(i, static_cast<uint64_t>(rows_cap[i]) * 2080u,
+                                  thermal_launch(st, d_rows[i], d_kelvin[i], d_images ? d_images[i] : nullptr), kc, table);
+        return APTGPU_OK;
+    });
+}
+
+int aptgpu_plan_thermal_results(aptgpu_plan *plan, int count, aptgpu_thermal_result *results)
+{
+    if (!plan || count < 0 || (!results && count)) return APTGPU_ERR_INVALID;
+    if (static_cast<size_t>(count) > plan->last_slots.size()) return APTGPU_ERR_INVALID;
+    for (int i = 0; i < count; ++i)
+        if (!plan->slot_of(i).thermal_ws.ptr) return APTGPU_ERR_INVALID;
+    try {
+        apt::hip_check(hipSetDevice(plan->device), "hipSetDevice");
+        plan->sync_all();
+        for (int i = 0; i < count; ++i) {
+            apt::gpu::ThermalRecord r{};
+            apt::hip_check(hipMemcpy(&r, apt::gpu::thermal_ws_record(plan->slot_of(i).thermal_ws.ptr), sizeof r,
+                                     hipMemcpyDeviceToHost),
+                           "hipMemcpy");
+            apt::gpu::thermal_record_to_public(r, results + i);
+        }
     } catch (const apt::Error &) {
         return APTGPU_ERR_HIP;
     }

@@ -817,6 +817,25 @@ void aptgpu_plan::enqueue_despeckle(int i, const float *d_rows, uint64_t rows_ca
     apt::hip_check(hipGetLastError(), "kernel launch (despeckle stage)");
 }
 
+void aptgpu_plan::enqueue_thermal(int i, uint64_t rows_cap_floats, apt::gpu::ThermalLaunch l,
+                                  const apt::gpu::ThermalCoeffs &coeffs, const apt::gpu::ThermalTable &table)
+{
+    using namespace apt::gpu;
+    const ImageTarget t = image_target(i, rows_cap_floats);
+    Slot &sl = t.slot;
+    if (!sl.thermal_ws.ptr) sl.thermal_ws.alloc(thermal_ws_bytes());
+    void *ws = sl.thermal_ws.ptr;
+    l.res = t.res;
+    l.n = 0;
+    l.cap = t.cap;
+    timed(t.stream, "image_telemetry",
+          [&] { image_telemetry(t.stream, l.x, t.res, 0, t.cap, t.ws, thermal_ws_telemetry(ws), false); });
+    timed(t.stream, "image_thermal_space", [&] { thermal_space(t.stream, l, ws); });
+    timed(t.stream, "image_thermal_setup", [&] { thermal_setup(t.stream, l, coeffs, ws); });
+    timed(t.stream, "image_thermal_map", [&] { thermal_map(t.stream, l, table, ws); });
+    apt::hip_check(hipGetLastError(), "kernel launch (thermal stage)");
+}
+
 aptgpu_plan::Palette::~Palette()
 {
     for (hipEvent_t ev : uploaded)

@@ -15,6 +15,7 @@
 #include "apt_kernels.hpp"
 #include "apt_kernels_color.hpp"
 #include "apt_kernels_despeckle.hpp"
+#include "apt_kernels_thermal.hpp"
 #include "apt_kernels_eqfloat.hpp"
 #include "apt_kernels_map.hpp"
 #include "apt_kernels_png.hpp"
@@ -170,6 +171,7 @@ struct aptgpu_plan : apt::PlanDesign {
         uint64_t lab_gen = 0;              // generation of the palette whose Lab tables lab_ws holds (0 = none)
         apt::DeviceBuffer<char> eqfloat_ws;  // counters, select records and thresholds of HISTOGRAM_FLOAT, on first use
         apt::DeviceBuffer<char> despeckle_ws;  // record + limits record of the despeckle stage, on first use
+        apt::DeviceBuffer<char> thermal_ws;    // record, pixel parameters, telemetry record and row means of the thermal stage, on first use
         std::unique_ptr<apt::map::Device> map;  // the map overlay's layer set, lists and track, on first use
         std::unique_ptr<apt::project::Device> project;  // the reprojection's graticule, record and PNG scratch, on first use
         apt::DeviceBuffer<char> png_ws;    // the PNG encoder's filtered stream, staging and chunk records, on first use
@@ -233,6 +235,12 @@ struct aptgpu_plan : apt::PlanDesign {
     // then one k_despeckle launch into d_out (same capacity, no overlap).  The record stays in the slot.
     void enqueue_despeckle(int i, const float *d_rows, uint64_t rows_cap_floats, int radius, float threshold,
                            float *d_out);
+    // The thermal stage (apt_kernels_thermal.hpp) of recording i, behind its decode on the same stream: the telemetry
+    // stage's launches (into the slot's image scratch, which the image stage behind it rewrites, and a record of the
+    // stage's own), then k_thermal_space, k_thermal_setup and k_thermal_map.  launch.x / kelvin / image are the
+    // recording's buffers; res, n and cap are filled in here.  The record stays in the slot.
+    void enqueue_thermal(int i, uint64_t rows_cap_floats, apt::gpu::ThermalLaunch launch, const apt::gpu::ThermalCoeffs &coeffs,
+                         const apt::gpu::ThermalTable &table);
     // The false-colour palette (256*256*3 RGB).  The plan keeps a host copy; bytes that differ from it start a new
     // generation, which every slot uploads on its own stream the next time it colours an image.  lab: also the
     // palette's Lab tables (apt_lab.hpp), computed once per generation and uploaded per slot likewise.

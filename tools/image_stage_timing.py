@@ -30,6 +30,12 @@ shape (16 recordings x 600 s at 48 kHz, 1198 rows each, one decode_device call),
                       the despeckle stage (radius 1 / 2, threshold 0 / 0.1: image_despeckle, and
                       image_percent when the threshold needs the 98 % limits) into a second rows buffer, then
                       minmax_gray on the filtered rows: image_minmax, one pass over the same samples, stands beside it
+    thermal_kelvin, thermal_gray, thermal_rgba
+                      the thermal calibration of channel B with the identity forced to "4": the
+                      telemetry stage, image_thermal_space, image_thermal_setup and image_thermal_map, which writes
+                      the Kelvin plane alone, with the gray scale image, or with the RGBA one; beside image_thermal_map
+                      the bytes it moves per second (the 909 video columns read, the Kelvin plane and the whole scale
+                      image written) against the 8 TB/s of HBM
 
 Per kernel: the plan's event timing (every launch bracketed, one call in flight), ms per recording.  Per variant also
 the wall time of one call of 16 recordings with timing off (host clock around enqueue + synchronise).  Last, the host
@@ -180,7 +186,22 @@ def main():
             plan.process_device(ptr(d_dsp), caps, apt.Contrast.MINMAX, ptr(d_img))
         return call
 
+    # (coefficients with the magnitudes of an AVHRR/3, the values of no satellite)
+    thermal_co = apt.ThermalCoefficients([(276.6, 0.0511, 1.4e-6)] * 4, (2670.0, 1.70, 0.9975, 0.0, 0.0, 0.0, 0.0),
+                                         (928.0, 0.55, 0.9985, -5.5, 5.8, -0.11, 0.00052),
+                                         (834.0, 0.40, 0.9990, -3.5, 2.7, -0.05, 0.00024))
+    d_kelvin = [torch.empty(cap * 909, dtype=torch.float32, device=dev) for _ in range(RECORDINGS)]
+    thermal_channels = {"thermal_kelvin": 0, "thermal_gray": 1, "thermal_rgba": 4}
+
+    def thermal(channels):
+        st = apt.ThermalSettings("B", "4", t_low=180.0, t_high=320.0, image_channels=channels)
+        return lambda: plan.calibrate_thermal_device(ptr(d_rows), caps, ptr(d_kelvin), thermal_co, st,
+                                                     ptr(d_img) if channels else None)
+
     variants = {
+        "thermal_kelvin": thermal(0),
+        "thermal_gray": thermal(1),
+        "thermal_rgba": thermal(4),
         "despeckle_r1_t0": despeckle(1, 0.0),
         "despeckle_r1_t01": despeckle(1, 0.1),
         "despeckle_r2_t0": despeckle(2, 0.0),
@@ -288,6 +309,12 @@ def main():
                 continue
             total += ms
             print(f"{name:18s} {kname:20s} {ms:8.4f}   ({launches})")
+            if kname == "image_thermal_map":
+                r = plan.thermal_results(1)[0]
+                moved = rows * (909 * 8 + 2080 * thermal_channels[name])
+                print(f"{name:18s} {'  bytes / s':20s} {moved / ms / 1e9:8.4f}   TB/s = {moved / ms / 1e9 / 8.0 * 100:.1f} % of "
+                      f"8 TB/s ({moved / 1e6:.2f} MB per recording; record: status {r.status}, {r.n_nan} NaN of "
+                      f"{rows * 909} px, {r.t_min:.1f} .. {r.t_max:.1f} K)")
         print(f"{name:18s} {'sum (events)':16s} {total:8.4f}")
         print(f"{name:18s} {'wall / rec':16s} {wall * 1e3 / RECORDINGS:8.4f}   (one call of {RECORDINGS}, timing off)")
     if any(k in png_channels for k in variants):
