@@ -968,6 +968,100 @@ int aptgpu_plan_calibrate_thermal_device(aptgpu_plan *plan, int count, const flo
 int aptgpu_plan_thermal_results(aptgpu_plan *plan, int count, aptgpu_thermal_result *results);
 
 /* ====================================================================== */
+/* 4b. FM demodulation of IQ recordings, in front of decode() */
+/* ====================================================================== */
+/* The reference reads audio only ("IQ files are not supported, these files should be FM demodulated into WAVs
+ * first", docs/usage.md), so the definition is this library's; tests/np_fm_model.py states it in numpy f64.  Opt-in, a
+ * stage of its own: IQ frames in, audio at fs / D out, which any decode entry point takes at that rate.
+ *  - Input: N complex frames, interleaved I then Q.  APTGPU_IQ_U8: v - 127.5 (the rtl_sdr convention); APTGPU_IQ_S8;
+ *    APTGPU_IQ_S16: little endian, `as f32`; APTGPU_IQ_F32: the bits.  Values are never scaled.
+ *    APTGPU_FM_SWAP_IQ exchanges I and Q.
+ *  - Taps: h = aptgpu_filter_design(Lowpass{cutout_pi_rad = 2 channel_cutout_hz / fs, channel_atten,
+ *    delta_w_pi_rad = 2 channel_delta_hz / fs}), the quotients in f32 as Freq::hz takes them (2.f * f / (float) fs);
+ *    T is its length.
+ *  - Mix: pw = (uint32) llround(shift_hz / fs * 2^32) in two's complement; theta_i = 2 pi ((uint32) i * pw) / 2^32,
+ *    the product in 32-bit unsigned arithmetic (exact for every i); u[i] = x[i] * e^{-j theta_i}.  The frequency
+ *    actually used is (int32) pw * fs / 2^32 (aptgpu_fm_info.shift_hz_used).  pw == 0 skips the mix.  The phasor of
+ *    frame i is that of the integer phase at i - i % 8, advanced i % 8 times by one f32 complex multiply with
+ *    e^{-j theta_1}.
+ *  - Filter and decimate, the valid part only: v[m] = sum_{k < T} h[k] * u[m D + T - 1 - k], m in [0, M),
+ *    M = (N - T) / D + 1 for N >= T, else 0; summed from k = T - 1 down to 0.
+ *  - Discriminate: a[m] = (fs_out / (2 pi deviation_hz)) * atan2(Im p, Re p), p = v[m + 1] * conj(v[m]),
+ *    m in [0, M - 1): n_out = max(M - 1, 0) floats at fs_out = fs / D.  p == 0 gives 0.  A non-finite component of
+ *    v[m] or v[m + 1] gives NaN: NaN and +-Inf frames reach exactly the outputs whose two windows contain them.
+ *    n_out == 0 is APTGPU_OK with an empty result (the decode behind it says "too short" in its own words).
+ *  - All device arithmetic is f32, contraction allowed; nothing is bit-pinned against the model.  With
+ *    e = sqrt(2) * 2 (T + 8) * 2^-24 * sum|h| * max|x| an output is within
+ *    g (e / |v[m]| + e / |v[m + 1]|) + 4 * 2^-24 * max(|a|, 1e-3 g), g = fs_out / (2 pi deviation_hz), of the model.
+ *  - Refused on the host, before a device is touched, with APTGPU_ERR_INVALID and a text naming the field: a short
+ *    struct_size; an unknown format or flag; sample_rate_hz == 0; decimation == 0 or > 4096; sample_rate_hz %
+ *    decimation != 0 (the output rate is a whole number of Hz); a non-finite or non-positive channel_cutout_hz,
+ *    channel_delta_hz or deviation_hz; a non-finite shift_hz or |shift_hz| > fs / 2; channel_atten not finite or not
+ *    above 8 dB; channel_cutout_hz + channel_delta_hz / 2 > fs_out / 2 (the filter would alias); more than 4096 taps. */
+#define APTGPU_IQ_U8 0
+#define APTGPU_IQ_S8 1
+#define APTGPU_IQ_S16 2
+#define APTGPU_IQ_F32 3
+#define APTGPU_FM_SWAP_IQ 1u
+#define APTGPU_FM_MAX_BATCH 64 /* recordings of one aptgpu_fm_demodulate_device call */
+typedef struct aptgpu_fm_settings {
+    uint32_t struct_size;     /* sizeof(aptgpu_fm_settings) */
+    int32_t format;           /* APTGPU_IQ_* */
+    uint32_t sample_rate_hz;  /* fs, complex frames per second */
+    uint32_t decimation;      /* D >= 1 */
+    double shift_hz;          /* the signal's offset from the recording's centre */
+    float channel_cutout_hz;  /* usually 18000 */
+    float channel_atten;      /* dB, usually 40 */
+    float channel_delta_hz;   /* usually 8000 */
+    float deviation_hz;       /* usually 17000 (APT) */
+    uint32_t flags;           /* APTGPU_FM_SWAP_IQ */
+    uint32_t reserved;
+} aptgpu_fm_settings;
+/* The usual values above, format U8, D = 1, no shift; sample_rate_hz is left 0 for the caller. */
+void aptgpu_fm_default_settings(aptgpu_fm_settings *settings);
+
+typedef struct aptgpu_fm aptgpu_fm;
+typedef struct aptgpu_fm_info {
+    uint32_t struct_size; /* in: sizeof(aptgpu_fm_info) */
+    uint32_t fs_out;      /* Hz */
+    uint32_t n_taps;      /* T */
+    uint32_t decimation;  /* D */
+    uint32_t pw;          /* phase increment per frame, 2^32 = one turn */
+    uint32_t reserved;
+    double shift_hz_used;
+    const float *taps;    /* h, n_taps floats, owned by the demodulator */
+} aptgpu_fm_info;
+/* Checks the settings, designs the taps and uploads them, once.  Runs on ctx->device and ctx->stream (NULL: the null
+ * stream); ctx NULL = device 0. */
+int aptgpu_fm_create(const aptgpu_context *ctx, const aptgpu_fm_settings *settings, aptgpu_fm **fm, char *err,
+                     size_t err_cap);
+void aptgpu_fm_destroy(aptgpu_fm *fm);
+int aptgpu_fm_get_info(const aptgpu_fm *fm, aptgpu_fm_info *info);
+size_t aptgpu_fm_out_len(const aptgpu_fm *fm, size_t n_frames);
+/* The checks and the design alone (no GPU): info as above, *taps malloc'd (aptgpu_free), info->taps NULL. */
+int aptgpu_fm_design(const aptgpu_fm_settings *settings, aptgpu_fm_info *info, float **taps, char *err, size_t err_cap);
+/* Host arrays: iq holds n_frames * 2 components; *audio malloc'd (aptgpu_free), *n_out floats at *rate_hz. */
+int aptgpu_fm_demodulate(const aptgpu_context *ctx, const aptgpu_fm_settings *settings, const void *iq, size_t n_frames,
+                         float **audio, size_t *n_out, uint32_t *rate_hz, char *err, size_t err_cap);
+/* The same on the CPU, in plain C++ (no GPU needed): the same f32 arithmetic except sincos and atan2 (and the
+ * compiler's contraction). */
+int aptgpu_fm_demodulate_host(const aptgpu_fm_settings *settings, const void *iq, size_t n_frames, float **audio,
+                              size_t *n_out, uint32_t *rate_hz, char *err, size_t err_cap);
+/* Device-resident: `count` (<= APTGPU_FM_MAX_BATCH) recordings in one kernel launch, asynchronous on the
+ * demodulator's stream, with no host synchronisation and no allocation.  This is the way to put work in front of a
+ * plan: a plan created on the same stream orders its decode after it.  d_iq[i]: n_frames[i] frames, aligned to one
+ * component (1, 2 or 4 bytes); 16-byte alignment lets the loads be 16 bytes wide, with the same result bit for bit.
+ * d_audio[i] receives aptgpu_fm_out_len(fm, n_frames[i]) floats and nothing behind them.  A null pointer (with
+ * something to read or write), a misaligned one or audio_cap[i] below the output length is APTGPU_ERR_INVALID before
+ * anything is enqueued.  A recording's result does not depend on its place in the batch. */
+int aptgpu_fm_demodulate_device(aptgpu_fm *fm, int count, const void *const *d_iq, const size_t *n_frames,
+                                float *const *d_audio, const size_t *audio_cap, char *err, size_t err_cap);
+/* A two-channel WAV (16-bit integer or 32-bit float) as the IQ recording, through aptgpu_wav_parse: the rate and the
+ * format come from the header and overrule the settings' fields.  Anything else is APTGPU_ERR_UNSUPPORTED. */
+int aptgpu_fm_demodulate_wav(const aptgpu_context *ctx, const aptgpu_fm_settings *settings, const void *file_bytes,
+                             size_t n, float **audio, size_t *n_out, uint32_t *rate_hz, char *err, size_t err_cap);
+
+/* ====================================================================== */
 /* 5. WAV ingest in front of decode()                 */
 /* ====================================================================== */
 /* noaa_apt::load / wav::load_wav (src/noaa_apt.rs:114-130, src/wav.rs:11-57): the container is */

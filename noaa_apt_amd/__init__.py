@@ -35,6 +35,9 @@ Names, argument meaning and error behaviour follow the reference:
     calibrate_thermal, calibrate_thermal_host,             brightness temperature of an infrared channel from the
     ThermalCoefficients, ThermalSettings,                  telemetry frame (NOAA KLM User's Guide §7.1.2.4), DESIGN.md §19
     Plan.calibrate_thermal_device
+    fm_demodulate, fm_demodulate_host, fm_demodulate_wav,  FM demodulation of an IQ recording in front of decode()
+    fm_design, load_iq, IqFormat, FmSettings,              (the reference takes audio only, docs/usage.md:87),
+    FmDemodulator                                          DESIGN.md §20
     percent, get_min, get_max, map_signal_u8               /root/reference/src/misc.rs:119, dsp.rs:20-54
     read_telemetry, Telemetry                              /root/reference/src/telemetry.rs:19-243
 
@@ -55,6 +58,8 @@ from .api import (  # noqa: F401
     DespeckleSettings, DespeckleResult, despeckle, despeckle_host,
     ThermalCoefficients, ThermalSettings, ThermalResult, calibrate_thermal, calibrate_thermal_host,
     THERMAL_COLD_WHITE, THERMAL_REASON_CHANNEL, THERMAL_REASON_DEGENERATE, THERMAL_PX,
+    IqFormat, FmSettings, FmInfo, FmDemodulator, fm_demodulate, fm_demodulate_host, fm_demodulate_wav, fm_design, load_iq,
+    FM_SWAP_IQ, FM_MAX_BATCH,
     Projection, ProjectionSettings, projection_fit, project_image, PROJECT_REASON_CAPACITY,
     Composite, composite_images, COMPOSITE_REASON_PASS, COMPOSITE_MAX_PASSES,
     SatName, RefTime, OrbitSettings, sat_track, sat_track_host, south_to_north_pass, SAT_REASON_SGP4,

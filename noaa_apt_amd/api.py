@@ -200,6 +200,20 @@ class ThermalResult(C.Structure):
                 ("t_bb", C.c_double), ("n_bb", C.c_double), ("t_min", C.c_float), ("t_max", C.c_float)]
 
 
+class _CFmSettings(C.Structure):
+    """aptgpu_fm_settings"""
+    _fields_ = [("struct_size", C.c_uint32), ("format", C.c_int32), ("sample_rate_hz", C.c_uint32),
+                ("decimation", C.c_uint32), ("shift_hz", C.c_double), ("channel_cutout_hz", C.c_float),
+                ("channel_atten", C.c_float), ("channel_delta_hz", C.c_float), ("deviation_hz", C.c_float),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class _CFmInfo(C.Structure):
+    """aptgpu_fm_info"""
+    _fields_ = [("struct_size", C.c_uint32), ("fs_out", C.c_uint32), ("n_taps", C.c_uint32), ("decimation", C.c_uint32),
+                ("pw", C.c_uint32), ("reserved", C.c_uint32), ("shift_hz_used", C.c_double), ("taps", _f32p)]
+
+
 class WavSpec(C.Structure):
     """aptgpu_wav_spec: hound::WavSpec plus where the samples are."""
     _fields_ = [("channels", C.c_uint16), ("bits_per_sample", C.c_uint16),
@@ -424,6 +438,22 @@ def lib():
     L.aptgpu_plan_calibrate_thermal_device.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz), *cth, C.POINTER(vp),
                                                        C.POINTER(vp), C.c_char_p, sz]
     L.aptgpu_plan_thermal_results.argtypes = [vp, i32, C.POINTER(ThermalResult)]
+    cfm = C.POINTER(_CFmSettings)
+    fm_out = (C.POINTER(_f32p), C.POINTER(sz), _u32p, C.c_char_p, sz)
+    L.aptgpu_fm_default_settings.argtypes = [cfm]
+    L.aptgpu_fm_default_settings.restype = None
+    L.aptgpu_fm_design.argtypes = [cfm, C.POINTER(_CFmInfo), C.POINTER(_f32p), C.c_char_p, sz]
+    L.aptgpu_fm_create.argtypes = [cp, cfm, C.POINTER(vp), C.c_char_p, sz]
+    L.aptgpu_fm_destroy.argtypes = [vp]
+    L.aptgpu_fm_destroy.restype = None
+    L.aptgpu_fm_get_info.argtypes = [vp, C.POINTER(_CFmInfo)]
+    L.aptgpu_fm_out_len.argtypes = [vp, sz]
+    L.aptgpu_fm_out_len.restype = sz
+    L.aptgpu_fm_demodulate.argtypes = [cp, cfm, vp, sz, *fm_out]
+    L.aptgpu_fm_demodulate_host.argtypes = [cfm, vp, sz, *fm_out]
+    L.aptgpu_fm_demodulate_device.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz),
+                                              C.c_char_p, sz]
+    L.aptgpu_fm_demodulate_wav.argtypes = [cp, cfm, C.c_char_p, sz, *fm_out]
     _lib = L
     return L
 
@@ -1546,6 +1576,205 @@ def calibrate_thermal_host(signal, coeffs, settings):
     """calibrate_thermal() on the CPU, in plain C++ (no GPU needed): the same scalars, the same f32 pixel
     arithmetic up to the C library's logf."""
     return _thermal_call(lib().aptgpu_calibrate_thermal_host, (), signal, coeffs, settings)
+
+
+# ------------------------------------------------------------------ FM demodulation of IQ recordings (DESIGN.md §20)
+class IqFormat:
+    """aptgpu_fm_settings.format: how one component of a frame is stored (interleaved I then Q, never scaled)."""
+    U8 = 0   # v - 127.5, the rtl_sdr convention
+    S8 = 1
+    S16 = 2  # little endian
+    F32 = 3
+    _DTYPES = {0: np.uint8, 1: np.int8, 2: np.dtype("<i2"), 3: np.dtype("<f4")}
+
+    @staticmethod
+    def dtype(fmt):
+        try:
+            return np.dtype(IqFormat._DTYPES[int(fmt)])
+        except (KeyError, TypeError, ValueError):
+            raise InvalidError(f"aptgpu_fm_settings: format is not an IqFormat value: {fmt!r}") from None
+
+
+FM_SWAP_IQ = 1
+FM_MAX_BATCH = 64
+
+
+@dataclass
+class FmSettings:
+    """aptgpu_fm_settings.  format: an IqFormat; sample_rate: complex frames per second (fs); decimation: D, the audio
+    comes out at fs / D; shift_hz: the signal's offset from the recording's centre; channel_*: the Kaiser low-pass in
+    front of the discriminator; deviation_hz: the deviation that maps to +-1; swap_iq: exchange I and Q."""
+    format: int
+    sample_rate: int
+    decimation: int = 1
+    shift_hz: float = 0.0
+    channel_cutout_hz: float = 18000.0
+    channel_atten: float = 40.0
+    channel_delta_hz: float = 8000.0
+    deviation_hz: float = 17000.0
+    swap_iq: bool = False
+    flags: Optional[int] = None  # overrides swap_iq (raw aptgpu_fm_settings.flags)
+
+    def _c(self, struct_size=None):
+        try:
+            rate = self.sample_rate.get_hz() if isinstance(self.sample_rate, Rate) else self.sample_rate
+            flags = (FM_SWAP_IQ if self.swap_iq else 0) if self.flags is None else int(self.flags)
+            return _CFmSettings(C.sizeof(_CFmSettings) if struct_size is None else int(struct_size), int(self.format),
+                                int(rate), int(self.decimation), float(self.shift_hz), float(self.channel_cutout_hz),
+                                float(self.channel_atten), float(self.channel_delta_hz), float(self.deviation_hz),
+                                flags, 0)
+        except (TypeError, ValueError, OverflowError) as e:
+            raise InvalidError(f"aptgpu_fm_settings: {e}") from None
+
+
+@dataclass(frozen=True)
+class FmInfo:
+    """aptgpu_fm_info: the output rate, the taps h (T of them), D, the phase increment per frame (2^32 = one turn)
+    and the shift it stands for."""
+    rate: Rate
+    taps: np.ndarray
+    decimation: int
+    pw: int
+    shift_hz_used: float
+
+    @property
+    def n_taps(self):
+        return int(self.taps.size)
+
+
+def _fm_settings_c(settings, struct_size=None):
+    if not isinstance(settings, FmSettings):
+        raise InvalidError("fm: settings must be an FmSettings")
+    return settings._c(struct_size)
+
+
+def fm_design(settings, struct_size=None) -> FmInfo:
+    """The checks and the design of an FmSettings alone, on the host (no GPU): every refusal raises InvalidError with
+    the field's name."""
+    cs = _fm_settings_c(settings, struct_size)
+    info, taps = _CFmInfo(struct_size=C.sizeof(_CFmInfo)), _f32p()
+    err = C.create_string_buffer(_ERRCAP)
+    _check(lib().aptgpu_fm_design(C.byref(cs), C.byref(info), C.byref(taps), err, _ERRCAP), err)
+    return FmInfo(Rate.hz(info.fs_out), _take(taps, info.n_taps), int(info.decimation), int(info.pw),
+                  float(info.shift_hz_used))
+
+
+def _fm_iq(iq, cs):
+    """-> (contiguous array of the format's components, frames)"""
+    dt = IqFormat.dtype(cs.format)
+    if isinstance(iq, (bytes, bytearray, memoryview)):
+        a = np.frombuffer(iq, dtype=np.uint8)
+        a = a[:a.size - a.size % (2 * dt.itemsize)].view(dt)
+    else:
+        a = np.asarray(iq)
+        if a.dtype == np.complex64 and dt == np.dtype("<f4"):
+            a = np.ascontiguousarray(a).view(np.float32)
+        if a.dtype != dt:
+            raise InvalidError(f"fm: iq has dtype {a.dtype}, the format's is {dt}")
+        a = np.ascontiguousarray(a).reshape(-1)
+    return a, a.size // 2
+
+
+def _fm_call(fn, head, iq, settings):
+    cs = _fm_settings_c(settings)
+    a, frames = _fm_iq(iq, cs)
+    out, n, rate = _f32p(), C.c_size_t(), C.c_uint32()
+    err = C.create_string_buffer(_ERRCAP)
+    _check(fn(*head, C.byref(cs), a.ctypes.data if a.size else None, frames, C.byref(out), C.byref(n), C.byref(rate),
+              err, _ERRCAP), err)
+    return _take(out, n.value), Rate.hz(rate.value)
+
+
+def fm_demodulate(iq, settings, context=None):
+    """FM-demodulate an IQ recording on the GPU: convert, mix by settings.shift_hz, low-pass and
+    decimate by settings.decimation, discriminate.  iq: interleaved I, Q components in the format's dtype (or bytes;
+    complex64 for F32).  Returns (audio, Rate): f32 at sample_rate / decimation, for decode() at that rate."""
+    cctx = (context or Context())._c()
+    return _fm_call(lib().aptgpu_fm_demodulate, (C.byref(cctx),), iq, settings)
+
+
+def fm_demodulate_host(iq, settings):
+    """fm_demodulate() on the CPU, in plain C++ (no GPU needed): the same f32 arithmetic up to sincos and atan2."""
+    return _fm_call(lib().aptgpu_fm_demodulate_host, (), iq, settings)
+
+
+def fm_demodulate_wav(file_bytes, settings, context=None):
+    """fm_demodulate() of a two-channel WAV (16-bit integer or 32-bit float): the format and the rate come from the
+    header and overrule the settings' fields."""
+    cctx, cs = (context or Context())._c(), _fm_settings_c(settings)
+    data = bytes(file_bytes)
+    out, n, rate = _f32p(), C.c_size_t(), C.c_uint32()
+    err = C.create_string_buffer(_ERRCAP)
+    _check(lib().aptgpu_fm_demodulate_wav(C.byref(cctx), C.byref(cs), data, len(data), C.byref(out), C.byref(n),
+                                          C.byref(rate), err, _ERRCAP), err)
+    return _take(out, n.value), Rate.hz(rate.value)
+
+
+def load_iq(path, fmt=None, sample_rate=None):
+    """An IQ recording from a file: (iq, IqFormat value, Rate), iq being the interleaved components in the format's
+    dtype.  A two-channel WAV (16-bit integer or 32-bit float) is read through its header; with both `fmt` and
+    `sample_rate` given the file is raw frames (a trailing partial frame is dropped).  Also accepts the file's bytes."""
+    if isinstance(path, (bytes, bytearray, memoryview)):
+        data = bytes(path)
+    else:
+        with open(path, "rb") as f:
+            data = f.read()
+    if (fmt is None) != (sample_rate is None):
+        raise InvalidError("load_iq: a raw file needs both fmt and sample_rate")
+    if fmt is not None:
+        dt = IqFormat.dtype(fmt)
+        rate = sample_rate if isinstance(sample_rate, Rate) else Rate.hz(sample_rate)
+        n = len(data) - len(data) % (2 * dt.itemsize)
+        return np.frombuffer(data, dtype=dt, count=n // dt.itemsize), int(fmt), rate
+    spec = wav_parse(data)
+    if spec.channels != 2 or spec.codec not in (1, 5):
+        raise UnsupportedError("fm: an IQ WAV has two channels of 16-bit integer or 32-bit float samples")
+    fmt = IqFormat.S16 if spec.codec == 1 else IqFormat.F32
+    dt = IqFormat.dtype(fmt)
+    iq = np.frombuffer(data, dtype=dt, count=int(spec.n_frames) * 2, offset=int(spec.data_offset))
+    return iq, fmt, Rate.hz(spec.sample_rate)
+
+
+class FmDemodulator:
+    """aptgpu_fm: the taps of one FmSettings on the device, for recordings already in HBM.  Runs on `stream` (0: the
+    null stream) of `device`; a Plan created on the same stream orders its decode behind demodulate_device()."""
+
+    def __init__(self, settings, device=0, stream=0):
+        cs = _fm_settings_c(settings)
+        self._ctx = Context(device=device, stream=stream)
+        cctx = self._ctx._c()
+        self._p = C.c_void_p()
+        err = C.create_string_buffer(_ERRCAP)
+        _check(lib().aptgpu_fm_create(C.byref(cctx), C.byref(cs), C.byref(self._p), err, _ERRCAP), err)
+        info = _CFmInfo(struct_size=C.sizeof(_CFmInfo))
+        _check(lib().aptgpu_fm_get_info(self._p, C.byref(info)))
+        taps = np.ctypeslib.as_array(info.taps, shape=(int(info.n_taps),)).copy()
+        self.info = FmInfo(Rate.hz(info.fs_out), taps, int(info.decimation), int(info.pw), float(info.shift_hz_used))
+
+    def close(self):
+        if self._p:
+            lib().aptgpu_fm_destroy(self._p)
+            self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def out_len(self, n_frames):
+        return int(lib().aptgpu_fm_out_len(self._p, int(n_frames)))
+
+    def demodulate_device(self, d_iq: Sequence[int], n_frames: Sequence[int], d_audio: Sequence[int],
+                          audio_cap: Sequence[int]):
+        """Up to FM_MAX_BATCH recordings in one launch, asynchronous on the demodulator's stream: d_iq[i] holds
+        n_frames[i] frames (aligned to one component), d_audio[i] receives out_len(n_frames[i]) floats and must hold
+        audio_cap[i] >= that."""
+        k = len(d_iq)
+        err = C.create_string_buffer(_ERRCAP)
+        _check(lib().aptgpu_fm_demodulate_device(self._p, k, (C.c_void_p * k)(*d_iq), (C.c_size_t * k)(*n_frames),
+                                                 (C.c_void_p * k)(*d_audio), (C.c_size_t * k)(*audio_cap), err,
+                                                 _ERRCAP), err)
 
 
 def process(context, signal, contrast_adjustment, rotate=Rotate.NO, color=None, orbit=None,
