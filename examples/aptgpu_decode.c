@@ -4,7 +4,7 @@
  *     aptgpu_decode in.wav out.pgm [contrast: telemetry|percent|minmax] [--no-sync]
  *                   [--histogram | --histogram-float] [--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE] [--png]
  *                   [--tle FILE --sat NAME (--start-ms N | --end-ms N)] [--rotate no|yes|orbit]
- *                   [--project equirect|mercator[:step_deg] [--grid DEG]] [--despeckle R[:T]]
+ *                   [--project equirect|mercator[:step_deg] [--grid DEG]] [--despeckle R[:T]] [--track=[W,LAMBDA]]
  *
  * What `noaa-apt in.wav -o out.png` does (main.rs:91-110, noaa_apt.rs:114-235): load -> decode ->
  * contrast limits -> 8-bit image, written as a binary PGM, or with --png as the PNG file the GPU
@@ -24,7 +24,11 @@
  * PPM of the grid's size, or with --png as the RGBA PNG (transparent off the swath).
  * --despeckle R[:T]: the decoded rows go through aptgpu_despeckle first, a (2R+1) x (2R+1) median (R = 1 or 2) that
  * never leaves a pixel's column band; T (default 0) is the fraction of the 98 % range a sample must differ from the
- * median by to be replaced.  Plain C99, links only libaptgpu.so.
+ * median by to be replaced.
+ * --track=W,LAMBDA (or --track= for the defaults 8,0.1; with the equals sign: --track FILE is the satellite's track):
+ * the rows come from aptgpu_decode_tracked, the flywheel sync stage in place of find_sync — row starts tracked through
+ * noise and dropouts, W work samples of jitter per row at LAMBDA per sample; it also decodes what the plain decode
+ * refuses as "less than 5 sync frames".  Plain C99, links only libaptgpu.so.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -44,14 +48,14 @@ int main(int argc, char **argv)
         fprintf(stderr, "usage: %s in.wav out.pgm [telemetry|percent|minmax] [--no-sync] [--histogram | --histogram-float] "
                 "[--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE] [--png]\n"
                 "       [--tle FILE --sat NAME (--start-ms N | --end-ms N)] [--rotate no|yes|orbit]\n"
-                "       [--project equirect|mercator[:step_deg] [--grid DEG]] [--despeckle R[:T]]\n", argv[0]);
+                "       [--project equirect|mercator[:step_deg] [--grid DEG]] [--despeckle R[:T]] [--track=[W,LAMBDA]]\n", argv[0]);
         return 2;
     }
     int contrast = APTGPU_CONTRAST_PERCENT, sync = 1, lab = 0, png = 0;
     const char *palette_path = NULL, *map_dir = NULL, *track_path = NULL, *tle_path = NULL, *sat = NULL;
     int rotate = APTGPU_ROTATE_NO, ref_kind = -1;
     long long ref_ms = 0;
-    const char *project = NULL, *despeckle = NULL;
+    const char *project = NULL, *despeckle = NULL, *flywheel = NULL;
     double grid_deg = 0.0;
     for (int i = 3; i < argc; ++i) {
         if (!strcmp(argv[i], "telemetry")) contrast = APTGPU_CONTRAST_TELEMETRY;
@@ -65,6 +69,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--palette") && i + 1 < argc) palette_path = argv[++i];
         else if (!strcmp(argv[i], "--map") && i + 1 < argc) map_dir = argv[++i];
         else if (!strcmp(argv[i], "--track") && i + 1 < argc) track_path = argv[++i];
+        else if (!strncmp(argv[i], "--track=", 8)) flywheel = argv[i] + 8;
         else if (!strcmp(argv[i], "--tle") && i + 1 < argc) tle_path = argv[++i];
         else if (!strcmp(argv[i], "--sat") && i + 1 < argc) sat = argv[++i];
         else if (!strcmp(argv[i], "--start-ms") && i + 1 < argc) ref_kind = APTGPU_REF_TIME_START, ref_ms = atoll(argv[++i]);
@@ -124,12 +129,41 @@ int main(int argc, char **argv)
     size_t n_rows_px = 0;
     aptgpu_stats stats;
     uint32_t rate = 0;
-    int rc = aptgpu_decode_wav(&ctx, &settings, bytes, (size_t)n, sync, &rows, &n_rows_px, &stats, &rate, err,
+    int rc;
+    if (flywheel) {
+        /* load -> front end -> flywheel sync: the rows of the tracked path, with each row's lock indicator */
+        aptgpu_track_settings ts = {sizeof(aptgpu_track_settings), 8, 0.1f, 0};
+        if (*flywheel && sscanf(flywheel, "%u,%f", &ts.max_jitter, &ts.penalty) != 2) {
+            fprintf(stderr, "--track=W,LAMBDA: cannot read \"%s\"\n", flywheel);
+            return 2;
+        }
+        float *signal = NULL, *scores = NULL;
+        size_t n_signal = 0;
+        aptgpu_wav_spec spec;
+        rc = aptgpu_load_wav(&ctx, bytes, (size_t)n, &signal, &n_signal, &rate, &spec, err, sizeof err);
+        if (rc != APTGPU_OK) { fprintf(stderr, "load failed (%d): %s\n", rc, err); return 1; }
+        aptgpu_track_result tr;
+        memset(&tr, 0, sizeof tr);
+        tr.struct_size = sizeof tr;
+        rc = aptgpu_decode_tracked(&ctx, &settings, signal, n_signal, rate, &ts, &rows, &n_rows_px, NULL, &scores, &tr, err,
+                                   sizeof err);
+        aptgpu_free(signal);
+        free(bytes);
+        if (rc != APTGPU_OK) { fprintf(stderr, "tracked decode failed (%d): %s\n", rc, err); return 1; }
+        unsigned locked = 0;
+        for (uint32_t k = 0; k < tr.n_positions; ++k) locked += scores[k] > 0.5f;
+        aptgpu_free(scores);
+        memset(&stats, 0, sizeof stats);
+        fprintf(stderr, "%u Hz, tracked %u row starts (jitter %u, penalty %g), %u with a score above 0.5, %llu rows\n", rate,
+                tr.n_positions, ts.max_jitter, ts.penalty, locked, (unsigned long long)(n_rows_px / 2080));
+    } else {
+    rc = aptgpu_decode_wav(&ctx, &settings, bytes, (size_t)n, sync, &rows, &n_rows_px, &stats, &rate, err,
                                sizeof err);
     free(bytes);
     if (rc != APTGPU_OK) { fprintf(stderr, "decode failed (%d): %s\n", rc, err); return 1; }
     fprintf(stderr, "%u Hz, %llu sync frames, %llu rows\n", rate, (unsigned long long)stats.n_sync,
             (unsigned long long)(n_rows_px / 2080));
+    }
 
     if (despeckle) {
         /* on the f32 rows, before any contrast limit is taken from them */

@@ -1062,6 +1062,106 @@ int aptgpu_fm_demodulate_wav(const aptgpu_context *ctx, const aptgpu_fm_settings
                              size_t n, float **audio, size_t *n_out, uint32_t *rate_hz, char *err, size_t err_cap);
 
 /* ====================================================================== */
+/* 4c. flywheel sync: row starts tracked through noise and dropouts */
+/* ====================================================================== */
+/* find_sync (decode.rs:204-263) keeps the largest value of an unnormalised +-1 correlation inside 0.8 of a row: one
+ * noise maximum moves a row by up to half a row, a dropout shuffles the lines, and under five frames the decode fails.
+ * The reference lists the remedy among its open items ("Improve syncing ... more resilient to noise, maybe working
+ * with the mean and variance", docs/development.md:148) and has no code for it, so the definition is this library's;
+ * tests/np_track_model.py states it in numpy.  Opt-in, a stage of its own behind the front end: nothing else changes
+ * when it is not called.
+ *
+ * All arithmetic is IEEE f32 in the order written; every product is rounded before it is added or subtracted (no
+ * contraction); division and square root are the correctly rounded ones.
+ *
+ * Input   x[0..n): the low-passed envelope at the work rate (decode()'s "filter_result" step, a plan's `filtered`
+ *         buffer).  pw = work_rate / 4160 must be an integer in 1..8; L = 2080 pw, G = 38 pw, M = n - G; g[j] is
+ *         generate_sync_frame's template.  n < L + G is refused.
+ * Score   for every i in [0, M):
+ *             c  = 0, then +- x[i+j] for j ascending                 (the reference's chain)
+ *             S1 = 0 (+ x[i+j]),  S2 = 0 (+ x[i+j]*x[i+j]),  j ascending
+ *             m = S1 / f32(G);  V = S2 - S1*m
+ *             num = c + S1 * f32(10.0/38.0)                          (the template minus its mean, -10/38)
+ *             den = sqrt(V * f32(G * (1 - (10/38)^2)))               (constant evaluated in f64, rounded once)
+ *             s[i] = num / den  if V > 1e-4f * S2 and num, den finite;  else 0
+ *         the zero-mean normalised cross-correlation.  The relative floor makes silence, a constant, NaN / +-Inf
+ *         windows and overflowing squares score 0 (no evidence) instead of noise; s is bit-identical under a
+ *         power-of-two gain while no square overflows or underflows.
+ * Track   settings max_jitter = w (work samples, 0..64, default 8; 4 w < L) and penalty = lambda (finite, >= 0,
+ *         default 0.1).  In chunks of C = L - w positions, ascending (bp: the back-pointer kept per position):
+ *             cur = 0 and bp = START if i < L, else -inf
+ *             for d in 0, -1, +1, -2, +2, ..., -w, +w:   j = i - L - d
+ *                 if j >= 0:  v = best[j] - (lambda * f32(|d|));  if v > cur: cur = v, bp = d    (strictly greater)
+ *             best[i] = s[i] + cur
+ *         End: the first maximum of best over [max(0, M - L), M).  Positions: follow bp back to START; they come out
+ *         ascending, K of them.  Rows: every p_k with p_k + L <= n gives row[c] = x[p_k + pw c], c < 2080 (the
+ *         sample's own bits).  Per position also s[p_k], the caller's lock indicator (near 1 on a clean frame, near
+ *         0 in noise). */
+typedef struct aptgpu_track_settings {
+    uint32_t struct_size; /* sizeof(aptgpu_track_settings) */
+    uint32_t max_jitter;  /* w: 0..64 work samples a row start may move against the previous one */
+    float penalty;        /* lambda: finite, >= 0; what one sample of such a move costs, in units of s */
+    uint32_t reserved;
+} aptgpu_track_settings;
+typedef struct aptgpu_track_result {
+    uint32_t struct_size; /* sizeof(aptgpu_track_result): set by the caller of the host-array forms and of
+                             aptgpu_plan_track_results (every record), written by the device otherwise */
+    int32_t status;       /* APTGPU_OK or APTGPU_ERR_INTERNAL */
+    int32_t reason;       /* 0; 1 the decode before it refused the recording (less than 10 rows: no filtered signal);
+                             2 shorter than L + G; 3 more positions than the list holds; 4 ok, rows truncated to
+                             rows_cap */
+    uint32_t n_positions; /* K */
+    uint32_t n_rows;      /* rows written: the positions with p + L <= n, never more than rows_cap */
+    uint32_t end;         /* the path's last position */
+    uint64_t n;           /* work samples of the recording */
+    float total;          /* best[end]: the path's score sum minus its penalties */
+    uint32_t reserved;
+} aptgpu_track_result;
+#define APTGPU_TRACK_MAX_JITTER 64
+/* settings nullable (= w 8, lambda 0.1) in every entry point below; outputs malloc'd (aptgpu_free).  Every refusal —
+ * a struct_size not set, w > 64, 4 w >= L, a negative or non-finite penalty, a work rate that is no multiple of 4160 Hz
+ * or above 8 x 4160, n < L + G — is APTGPU_ERR_INVALID before a device is touched.
+ *
+ * aptgpu_track_sync: `count` (>= 1) host signals of n[i] work-rate samples through one launch per kernel.
+ * positions[i] / scores[i]: results[i].n_positions entries; rows (nullable): rows[i] holds results[i].n_rows * 2080
+ * floats.  results[i].struct_size must be set. */
+int aptgpu_track_sync(const aptgpu_context *ctx, int count, const float *const *signals, const size_t *n,
+                      uint32_t work_rate_hz, const aptgpu_track_settings *settings, uint64_t **positions,
+                      float **scores, float **rows /* nullable */, aptgpu_track_result *results, char *err,
+                      size_t err_cap);
+/* The same for one signal on the CPU, in plain C++ (no GPU needed): the same bits.  score_out (nullable): all n - G
+ * values of s. */
+int aptgpu_track_sync_host(const float *signal, size_t n, uint32_t work_rate_hz, const aptgpu_track_settings *settings,
+                           uint64_t **positions, float **scores, float **rows /* nullable */,
+                           float **score_out /* nullable */, aptgpu_track_result *info, char *err, size_t err_cap);
+/* s alone: scores[i] receives n[i] - G floats. */
+int aptgpu_sync_score(const aptgpu_context *ctx, int count, const float *const *signals, const size_t *n,
+                      uint32_t work_rate_hz, float **scores, char *err, size_t err_cap);
+/* Device-resident: re-aligns the first `count` recordings of the plan's last decode call from their slots' filtered
+ * buffers (in either layout the front end left) into d_rows[i] (rows_cap[i] rows of 2080 floats, which may be the
+ * decode's own buffer), chained behind the decode on the call's stream: asynchronous, no host synchronisation, no
+ * allocation after the first use on a slot.  The sample count comes from the decode record on the device.  Works on
+ * sync = 0 and sync = 1 plans, and where the decode's own record says "less than 5 sync frames"; a recording the
+ * decode refused as shorter than 10 rows is recorded with reason 1.  The decode's own records, positions and rows (in
+ * another buffer) are left alone.  Timer names: track_score, track_dp, track_rows. */
+int aptgpu_plan_track_device(aptgpu_plan *plan, int count, const aptgpu_track_settings *settings, float *const *d_rows,
+                             const size_t *rows_cap, char *err, size_t err_cap);
+/* Waits for the stage of the last call and copies the records (every results[i].struct_size set). */
+int aptgpu_plan_track_results(aptgpu_plan *plan, int count, aptgpu_track_result *results);
+/* Positions and their scores of recording i of the last aptgpu_plan_track_device call: min(cap, K) entries each
+ * (pos, scores nullable), K in *n_positions. */
+int aptgpu_plan_track_positions(aptgpu_plan *plan, int i, uint64_t *pos, float *scores, size_t cap,
+                                size_t *n_positions);
+/* Input signal -> tracked rows in one call: the front end of a sync = 0 plan (same settings, same refusals as
+ * aptgpu_decode, "less than 10 rows" included), then the stage.  *rows_out: *n_out = rows * 2080 floats exactly as the
+ * stage gathers them (no final filter pass: the sample's own bits); positions / scores (nullable): info->n_positions
+ * entries.  info nullable. */
+int aptgpu_decode_tracked(const aptgpu_context *ctx, const aptgpu_settings *settings, const float *signal, size_t n,
+                          uint32_t input_rate_hz, const aptgpu_track_settings *track, float **rows_out, size_t *n_out,
+                          uint64_t **positions /* nullable */, float **scores /* nullable */,
+                          aptgpu_track_result *info /* nullable */, char *err, size_t err_cap);
+
+/* ====================================================================== */
 /* 5. WAV ingest in front of decode()                 */
 /* ====================================================================== */
 /* noaa_apt::load / wav::load_wav (src/noaa_apt.rs:114-130, src/wav.rs:11-57): the container is */

@@ -38,6 +38,8 @@ Names, argument meaning and error behaviour follow the reference:
     fm_demodulate, fm_demodulate_host, fm_demodulate_wav,  FM demodulation of an IQ recording in front of decode()
     fm_design, load_iq, IqFormat, FmSettings,              (the reference takes audio only, docs/usage.md:87),
     FmDemodulator                                          DESIGN.md §20
+    track_sync, track_sync_host, sync_score,               the reference's to-do list, docs/development.md:148: row
+    decode_tracked, TrackSettings, Plan.track_device       starts tracked through noise and dropouts, DESIGN.md §21
     percent, get_min, get_max, map_signal_u8               /root/reference/src/misc.rs:119, dsp.rs:20-54
     read_telemetry, Telemetry                              /root/reference/src/telemetry.rs:19-243
 
@@ -60,6 +62,7 @@ from .api import (  # noqa: F401
     THERMAL_COLD_WHITE, THERMAL_REASON_CHANNEL, THERMAL_REASON_DEGENERATE, THERMAL_PX,
     IqFormat, FmSettings, FmInfo, FmDemodulator, fm_demodulate, fm_demodulate_host, fm_demodulate_wav, fm_design, load_iq,
     FM_SWAP_IQ, FM_MAX_BATCH,
+    TrackSettings, TrackResult, track_sync, track_sync_host, sync_score, decode_tracked, TRACK_MAX_JITTER,
     Projection, ProjectionSettings, projection_fit, project_image, PROJECT_REASON_CAPACITY,
     Composite, composite_images, COMPOSITE_REASON_PASS, COMPOSITE_MAX_PASSES,
     SatName, RefTime, OrbitSettings, sat_track, sat_track_host, south_to_north_pass, SAT_REASON_SGP4,

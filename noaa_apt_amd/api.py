@@ -178,6 +178,18 @@ class DespeckleResult(C.Structure):
                 ("reserved2", C.c_uint32)]
 
 
+class _CTrackSettings(C.Structure):
+    """aptgpu_track_settings"""
+    _fields_ = [("struct_size", C.c_uint32), ("max_jitter", C.c_uint32), ("penalty", C.c_float), ("reserved", C.c_uint32)]
+
+
+class TrackResult(C.Structure):
+    """aptgpu_track_result: positions and rows of the flywheel sync stage, the path's last position and its total."""
+    _fields_ = [("struct_size", C.c_uint32), ("status", C.c_int32), ("reason", C.c_int32), ("n_positions", C.c_uint32),
+                ("n_rows", C.c_uint32), ("end", C.c_uint32), ("n", C.c_uint64), ("total", C.c_float),
+                ("reserved", C.c_uint32)]
+
+
 class _CThermalCoeffs(C.Structure):
     """aptgpu_thermal_coeffs"""
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("prt", (C.c_double * 3) * 4),
@@ -454,6 +466,17 @@ def lib():
     L.aptgpu_fm_demodulate_device.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz),
                                               C.c_char_p, sz]
     L.aptgpu_fm_demodulate_wav.argtypes = [cp, cfm, C.c_char_p, sz, *fm_out]
+    cts, ctr = C.POINTER(_CTrackSettings), C.POINTER(TrackResult)
+    L.aptgpu_track_sync.argtypes = [cp, i32, C.POINTER(_f32p), C.POINTER(sz), u32, cts, C.POINTER(_u64p),
+                                    C.POINTER(_f32p), C.POINTER(_f32p), ctr, C.c_char_p, sz]
+    L.aptgpu_track_sync_host.argtypes = [_f32p, sz, u32, cts, C.POINTER(_u64p), C.POINTER(_f32p), C.POINTER(_f32p),
+                                         C.POINTER(_f32p), ctr, C.c_char_p, sz]
+    L.aptgpu_sync_score.argtypes = [cp, i32, C.POINTER(_f32p), C.POINTER(sz), u32, C.POINTER(_f32p), C.c_char_p, sz]
+    L.aptgpu_plan_track_device.argtypes = [vp, i32, cts, C.POINTER(vp), C.POINTER(sz), C.c_char_p, sz]
+    L.aptgpu_plan_track_results.argtypes = [vp, i32, ctr]
+    L.aptgpu_plan_track_positions.argtypes = [vp, i32, _u64p, _f32p, sz, C.POINTER(sz)]
+    L.aptgpu_decode_tracked.argtypes = [cp, C.POINTER(_CSettings), _f32p, sz, u32, cts, C.POINTER(_f32p), C.POINTER(sz),
+                                        C.POINTER(_u64p), C.POINTER(_f32p), ctr, C.c_char_p, sz]
     _lib = L
     return L
 
@@ -1469,6 +1492,126 @@ def despeckle_host(signal, settings=None, return_info=False):
     return (y, info) if return_info else y
 
 
+TRACK_MAX_JITTER = 64
+
+
+class TrackSettings:
+    """aptgpu_track_settings: the flywheel sync stage.  max_jitter: how many work samples (0..64) a row
+    start may move against the one before it; penalty (finite, >= 0): what one sample of such a move costs, in units
+    of the normalised sync score."""
+
+    def __init__(self, max_jitter=8, penalty=0.1):
+        self.max_jitter, self.penalty = max_jitter, penalty
+
+    def _c(self, struct_size=None):
+        return _CTrackSettings(C.sizeof(_CTrackSettings) if struct_size is None else int(struct_size),
+                               int(self.max_jitter), float(self.penalty), 0)
+
+
+def _track_c(settings):
+    if settings is None:
+        return None
+    if isinstance(settings, _CTrackSettings):  # (tests: a struct_size of their own)
+        return settings
+    if not isinstance(settings, TrackSettings):
+        raise InvalidError("track: settings must be a TrackSettings")
+    try:
+        return settings._c()
+    except (TypeError, ValueError, OverflowError) as e:
+        raise InvalidError(f"track: {e}") from None
+
+
+def _track_result(struct_size=None):
+    r = TrackResult()
+    r.struct_size = C.sizeof(TrackResult) if struct_size is None else int(struct_size)
+    return r
+
+
+def _track_signals(signal):
+    many = isinstance(signal, (list, tuple))
+    xs = [_as_f32(x) for x in (signal if many else [signal])]
+    k = len(xs)
+    ptrs = (_f32p * k)(*[p for _, p in xs])
+    ns = (C.c_size_t * k)(*[x.size for x, _ in xs])
+    return many, xs, k, ptrs, ns
+
+
+def track_sync(signal, work_rate: "Rate", settings=None, context=None, rows=True, return_info=False):
+    """The flywheel sync stage on the GPU.  signal: the low-passed envelope at the work rate (decode()'s
+    "filter_result" step), or a list of such signals, which then share one launch per kernel.  Returns (positions
+    u64, scores f32, rows f32 [n_rows, 2080] or None) — with return_info also the TrackResult — per signal."""
+    cs = _track_c(settings)
+    cctx = (context or Context())._c()
+    many, xs, k, ptrs, ns = _track_signals(signal)
+    pos, sc, rw = (_u64p * k)(), (_f32p * k)(), (_f32p * k)()
+    info = (TrackResult * k)()
+    for r in info:
+        r.struct_size = C.sizeof(TrackResult)
+    err = C.create_string_buffer(_ERRCAP)
+    _check(lib().aptgpu_track_sync(C.byref(cctx), k, ptrs, ns, work_rate.get_hz(), C.byref(cs) if cs is not None else None,
+                                   pos, sc, rw if rows else None, info, err, _ERRCAP), err)
+    out = []
+    for i in range(k):
+        r = info[i]
+        item = (_take(pos[i], r.n_positions, np.uint64), _take(sc[i], r.n_positions),
+                _take(rw[i], r.n_rows * PX_PER_ROW).reshape(-1, PX_PER_ROW) if rows else None)
+        out.append(item + (r,) if return_info else item)
+    return out if many else out[0]
+
+
+def track_sync_host(signal, work_rate: "Rate", settings=None, rows=True, return_score=False, return_info=False,
+                    result_struct_size=None):
+    """track_sync() for one signal on the CPU, in plain C++ (no GPU needed): the same bits.  return_score: also s, the
+    score of every position."""
+    cs = _track_c(settings)
+    x, xp = _as_f32(signal)
+    pos, sc, rw, s = _u64p(), _f32p(), _f32p(), _f32p()
+    info = _track_result(result_struct_size)
+    err = C.create_string_buffer(_ERRCAP)
+    _check(lib().aptgpu_track_sync_host(xp, x.size, work_rate.get_hz(), C.byref(cs) if cs is not None else None,
+                                        C.byref(pos), C.byref(sc), C.byref(rw) if rows else None,
+                                        C.byref(s) if return_score else None, C.byref(info), err, _ERRCAP), err)
+    out = (_take(pos, info.n_positions, np.uint64), _take(sc, info.n_positions),
+           _take(rw, info.n_rows * PX_PER_ROW).reshape(-1, PX_PER_ROW) if rows else None)
+    if return_score:
+        pw = work_rate.get_hz() // FINAL_RATE
+        out += (_take(s, x.size - 38 * pw),)
+    return out + (info,) if return_info else out
+
+
+def sync_score(signal, work_rate: "Rate", context=None):
+    """s alone, on the GPU: the zero-mean normalised correlation of the signal (or of every signal of a list, in one
+    launch) with the sync template at every position, 0 where a window holds no evidence."""
+    cctx = (context or Context())._c()
+    many, xs, k, ptrs, ns = _track_signals(signal)
+    sc = (_f32p * k)()
+    err = C.create_string_buffer(_ERRCAP)
+    _check(lib().aptgpu_sync_score(C.byref(cctx), k, ptrs, ns, work_rate.get_hz(), sc, err, _ERRCAP), err)
+    pw = work_rate.get_hz() // FINAL_RATE
+    out = [_take(sc[i], xs[i][0].size - 38 * pw) for i in range(k)]
+    return out if many else out[0]
+
+
+def decode_tracked(context: Optional["Context"], settings: "Settings", signal, input_rate: "Rate", track=None,
+                   return_info=False):
+    """decode() with the flywheel sync stage in place of find_sync: the front end of a sync = 0 plan, then the stage.
+    Returns the rows (flat f32, rows * 2080, the filtered samples' own bits) — with return_info also (positions,
+    scores, TrackResult).  Holds where decode() raises "less than 5 sync frames"; keeps its "less than 10 rows"."""
+    cs = _track_c(track)
+    cctx = (context or Context())._c()
+    c_settings = settings._c()
+    x, xp = _as_f32(signal)
+    rw, n_out, pos, sc = _f32p(), C.c_size_t(0), _u64p(), _f32p()
+    info = _track_result()
+    err = C.create_string_buffer(_ERRCAP)
+    _check(lib().aptgpu_decode_tracked(C.byref(cctx), C.byref(c_settings), xp, x.size, input_rate.get_hz(),
+                                       C.byref(cs) if cs is not None else None, C.byref(rw), C.byref(n_out),
+                                       C.byref(pos), C.byref(sc), C.byref(info), err, _ERRCAP), err)
+    rows = _take(rw, n_out.value)
+    p, q = _take(pos, info.n_positions, np.uint64), _take(sc, info.n_positions)
+    return (rows, p, q, info) if return_info else rows
+
+
 THERMAL_COLD_WHITE = 1
 THERMAL_REASON_CHANNEL = 13
 THERMAL_REASON_DEGENERATE = 14
@@ -2061,6 +2204,31 @@ class Plan:
         arr = (DespeckleResult * count)()
         _check(lib().aptgpu_plan_despeckle_results(self._p, count, arr))
         return list(arr)
+
+    def track_device(self, d_rows: Sequence[int], rows_cap: Sequence[int], settings=None):
+        """The flywheel sync stage of the recordings of the last decode_device call, chained on the device behind their
+        decode: re-aligns each from its slot's filtered signal into d_rows[i] (rows_cap[i] rows of 2080 floats).
+        Records through track_results(), positions through track_positions()."""
+        k = len(d_rows)
+        cs = _track_c(settings)
+        err = C.create_string_buffer(_ERRCAP)
+        _check(lib().aptgpu_plan_track_device(self._p, k, C.byref(cs) if cs is not None else None,
+                                              (C.c_void_p * k)(*d_rows), (C.c_size_t * k)(*rows_cap), err, _ERRCAP), err)
+
+    def track_results(self, count=1) -> List["TrackResult"]:
+        arr = (TrackResult * count)()
+        for r in arr:
+            r.struct_size = C.sizeof(TrackResult)
+        _check(lib().aptgpu_plan_track_results(self._p, count, arr))
+        return list(arr)
+
+    def track_positions(self, i=0, cap=1 << 16):
+        """(positions u64, scores f32) of recording i of the last track_device call"""
+        pos, sc, n = np.zeros(cap, np.uint64), np.zeros(cap, np.float32), C.c_size_t(0)
+        _check(lib().aptgpu_plan_track_positions(self._p, i, pos.ctypes.data_as(_u64p), sc.ctypes.data_as(_f32p), cap,
+                                                 C.byref(n)))
+        k = min(int(n.value), cap)
+        return pos[:k].copy(), sc[:k].copy()
 
     def calibrate_thermal_device(self, d_rows: Sequence[int], rows_cap: Sequence[int], d_kelvin: Sequence[int],
                                  coeffs, settings, d_images: Optional[Sequence[int]] = None):

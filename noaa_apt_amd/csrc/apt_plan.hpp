@@ -172,6 +172,7 @@ struct aptgpu_plan : apt::PlanDesign {
         apt::DeviceBuffer<char> eqfloat_ws;  // counters, select records and thresholds of HISTOGRAM_FLOAT, on first use
         apt::DeviceBuffer<char> despeckle_ws;  // record + limits record of the despeckle stage, on first use
         apt::DeviceBuffer<char> thermal_ws;    // record, pixel parameters, telemetry record and row means of the thermal stage, on first use
+        apt::DeviceBuffer<char> track_ws;      // scores, back-pointers, position lists and record of the flywheel sync stage, on first use
         std::unique_ptr<apt::map::Device> map;  // the map overlay's layer set, lists and track, on first use
         std::unique_ptr<apt::project::Device> project;  // the reprojection's graticule, record and PNG scratch, on first use
         apt::DeviceBuffer<char> png_ws;    // the PNG encoder's filtered stream, staging and chunk records, on first use
