@@ -5,6 +5,7 @@
  *                   [--histogram | --histogram-float] [--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE] [--png]
  *                   [--tle FILE --sat NAME (--start-ms N | --end-ms N)] [--rotate no|yes|orbit]
  *                   [--project equirect|mercator[:step_deg] [--grid DEG]] [--despeckle R[:T]] [--track=[W,LAMBDA]]
+ *                   [--live SECONDS]
  *
  * What `noaa-apt in.wav -o out.png` does (main.rs:91-110, noaa_apt.rs:114-235): load -> decode ->
  * contrast limits -> 8-bit image, written as a binary PGM, or with --png as the PNG file the GPU
@@ -28,7 +29,10 @@
  * --track=W,LAMBDA (or --track= for the defaults 8,0.1; with the equals sign: --track FILE is the satellite's track):
  * the rows come from aptgpu_decode_tracked, the flywheel sync stage in place of find_sync — row starts tracked through
  * noise and dropouts, W work samples of jitter per row at LAMBDA per sample; it also decodes what the plain decode
- * refuses as "less than 5 sync frames".  Plain C99, links only libaptgpu.so.
+ * refuses as "less than 5 sync frames".
+ * --live SECONDS: the recording goes through a live-decode stream (aptgpu_stream_*) in chunks of SECONDS, as a ground
+ * station would feed it during the pass; every push hands back the rows that are final, and their concatenation — the
+ * image written — is the same PGM as without the flag.  Plain C99, links only libaptgpu.so.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -48,7 +52,8 @@ int main(int argc, char **argv)
         fprintf(stderr, "usage: %s in.wav out.pgm [telemetry|percent|minmax] [--no-sync] [--histogram | --histogram-float] "
                 "[--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE] [--png]\n"
                 "       [--tle FILE --sat NAME (--start-ms N | --end-ms N)] [--rotate no|yes|orbit]\n"
-                "       [--project equirect|mercator[:step_deg] [--grid DEG]] [--despeckle R[:T]] [--track=[W,LAMBDA]]\n", argv[0]);
+                "       [--project equirect|mercator[:step_deg] [--grid DEG]] [--despeckle R[:T]] [--track=[W,LAMBDA]]\n"
+                "       [--live SECONDS]\n", argv[0]);
         return 2;
     }
     int contrast = APTGPU_CONTRAST_PERCENT, sync = 1, lab = 0, png = 0;
@@ -56,7 +61,7 @@ int main(int argc, char **argv)
     int rotate = APTGPU_ROTATE_NO, ref_kind = -1;
     long long ref_ms = 0;
     const char *project = NULL, *despeckle = NULL, *flywheel = NULL;
-    double grid_deg = 0.0;
+    double grid_deg = 0.0, live_seconds = 0.0;
     for (int i = 3; i < argc; ++i) {
         if (!strcmp(argv[i], "telemetry")) contrast = APTGPU_CONTRAST_TELEMETRY;
         else if (!strcmp(argv[i], "percent")) contrast = APTGPU_CONTRAST_PERCENT;
@@ -77,6 +82,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--project") && i + 1 < argc) project = argv[++i];
         else if (!strcmp(argv[i], "--grid") && i + 1 < argc) grid_deg = atof(argv[++i]);
         else if (!strcmp(argv[i], "--despeckle") && i + 1 < argc) despeckle = argv[++i];
+        else if (!strcmp(argv[i], "--live") && i + 1 < argc) live_seconds = atof(argv[++i]);
         else if (!strcmp(argv[i], "--rotate") && i + 1 < argc) {
             const char *r = argv[++i];
             rotate = !strcmp(r, "orbit") ? APTGPU_ROTATE_ORBIT : !strcmp(r, "yes") ? APTGPU_ROTATE_YES : APTGPU_ROTATE_NO;
@@ -156,6 +162,50 @@ int main(int argc, char **argv)
         memset(&stats, 0, sizeof stats);
         fprintf(stderr, "%u Hz, tracked %u row starts (jitter %u, penalty %g), %u with a score above 0.5, %llu rows\n", rate,
                 tr.n_positions, ts.max_jitter, ts.penalty, locked, (unsigned long long)(n_rows_px / 2080));
+    } else if (live_seconds > 0.0) {
+        /* load, then the samples in chunks through a stream: each push returns the rows that became final */
+        float *signal = NULL;
+        size_t n_signal = 0;
+        aptgpu_wav_spec spec;
+        rc = aptgpu_load_wav(&ctx, bytes, (size_t)n, &signal, &n_signal, &rate, &spec, err, sizeof err);
+        free(bytes);
+        if (rc != APTGPU_OK) { fprintf(stderr, "load failed (%d): %s\n", rc, err); return 1; }
+        aptgpu_stream_settings ss;
+        memset(&ss, 0, sizeof ss);
+        ss.struct_size = sizeof ss;
+        ss.input_rate_hz = rate;
+        ss.sync = sync;
+        ss.format = APTGPU_STREAM_F32;
+        aptgpu_stream *stream = NULL;
+        rc = aptgpu_stream_create(&ctx, &settings, &ss, &stream, err, sizeof err);
+        if (rc != APTGPU_OK) { fprintf(stderr, "stream failed (%d): %s\n", rc, err); return 1; }
+        size_t chunk = (size_t)(live_seconds * rate);
+        if (chunk == 0) chunk = 1;
+        aptgpu_stream_result sr;
+        memset(&sr, 0, sizeof sr);
+        sr.struct_size = sizeof sr;
+        size_t n_rows = 0, pushes = 0;
+        for (size_t at = 0; rc == APTGPU_OK; at += chunk, ++pushes) {
+            const int last = at >= n_signal;  /* the call after the last chunk is the finish */
+            const size_t take = last ? 0 : (n_signal - at < chunk ? n_signal - at : chunk);
+            const size_t cap = aptgpu_stream_rows_bound(stream, take);
+            float *grown = realloc(rows, (n_rows + cap) * 2080 * sizeof(float));
+            uint64_t *pos = malloc(cap * sizeof(uint64_t));
+            if (!grown || !pos) { fprintf(stderr, "out of memory\n"); return 1; }
+            rows = grown;
+            rc = last ? aptgpu_stream_finish(stream, rows + n_rows * 2080, pos, cap, &sr, err, sizeof err)
+                      : aptgpu_stream_push(stream, signal + at, take, rows + n_rows * 2080, pos, cap, &sr, err, sizeof err);
+            free(pos);
+            if (rc == APTGPU_OK) n_rows += sr.n_rows;
+            if (last) break;
+        }
+        aptgpu_stream_destroy(stream);
+        aptgpu_free(signal);
+        if (rc != APTGPU_OK) { fprintf(stderr, "live decode failed (%d): %s\n", rc, err); return 1; }
+        n_rows_px = n_rows * 2080;
+        memset(&stats, 0, sizeof stats);
+        fprintf(stderr, "%u Hz, %llu sync frames, %llu rows from %llu pushes of %g s\n", rate, (unsigned long long)sr.n_sync,
+                (unsigned long long)n_rows, (unsigned long long)pushes, live_seconds);
     } else {
     rc = aptgpu_decode_wav(&ctx, &settings, bytes, (size_t)n, sync, &rows, &n_rows_px, &stats, &rate, err,
                                sizeof err);

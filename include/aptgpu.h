@@ -1162,6 +1162,100 @@ int aptgpu_decode_tracked(const aptgpu_context *ctx, const aptgpu_settings *sett
                           aptgpu_track_result *info /* nullable */, char *err, size_t err_cap);
 
 /* ====================================================================== */
+/* 4d. live decode: audio pushed in chunks, finished rows handed back */
+/* ====================================================================== */
+/* The reference lists "Live decoding, from a TCP stream or using librtlsdr or from audio" among its open items
+ * (docs/development.md:151).  A stream takes the recording in pushes of any size and hands out, after every push, the
+ * image rows that are FINAL: a row (a work-rate sample, a correlation, a peak) is final when it exists in strict
+ * decode() of the complete recording with the same bits for EVERY continuation of what has been pushed, the empty one
+ * included.  It is released in the first push after which that holds — never earlier, never later — so the rows of all
+ * pushes and of aptgpu_stream_finish, concatenated, are bit-identical to decode() of the whole recording, and how many
+ * come out of which push is a function of the chunk boundaries alone.
+ *   work sample i   final once every input sample its resampler window reads has been pushed (l > 1), or i < n / m
+ *                   (l == 1); finish adds the tail the reference computes with absent samples skipped (dsp.rs:257)
+ *   position i      scanned once i + 38 pw < work_len (decode.rs:225)
+ *   row of peak k   final once a later peak was pushed and p_k + samples_per_row < work_len; the last peak never gives a
+ *                   row (decode.rs:125-131); sync == 0: row r once (r + 1) samples_per_row <= work_len
+ * aptgpu_stream_finish then reports what decode() would: "Got less than 10 rows of samples, ..." or "Found less than 5
+ * sync frames, ..." with APTGPU_ERR_INTERNAL.  The one difference from decode(): rows released before such an error
+ * stay released (a failing finish itself releases none).
+ * Strict arithmetic only: APTGPU_MODE_FAST, APTGPU_MODE_FP16_TAPS, the matrix-core switch, export_wav and
+ * export_resample_filtered are APTGPU_ERR_UNSUPPORTED; no step callback is invoked.  work_rate must be a multiple of
+ * 4160 Hz (the reference's message, APTGPU_ERR_INTERNAL) with sync == 0 as well.  All state lives on the device in a
+ * record and three rings of fixed size (input, F, correlation); nothing grows with the recording. */
+#define APTGPU_STREAM_F32 0 /* samples are f32, as wav::load_wav produces them */
+#define APTGPU_STREAM_S16 1 /* mono int16 (the value `as f32`) */
+typedef struct aptgpu_stream aptgpu_stream;
+typedef struct aptgpu_stream_settings {
+    uint32_t struct_size;   /* sizeof(aptgpu_stream_settings); 0 is refused */
+    uint32_t input_rate_hz;
+    int32_t sync;
+    int32_t format;         /* APTGPU_STREAM_* */
+    uint32_t max_push;      /* samples one launch sequence takes (longer pushes are split); 0 = 65536; at most 2^24 */
+    uint32_t reserved;
+} aptgpu_stream_settings;
+typedef struct aptgpu_stream_info {
+    uint32_t struct_size;   /* set by the caller */
+    uint32_t work_rate;
+    uint32_t pw;
+    uint32_t samples_per_row;
+    uint32_t l, m;
+    uint32_t n_resample_taps, n_lowpass_taps;
+    uint32_t max_push;
+    uint32_t cap_in, cap_f, cap_corr; /* ring capacities in samples (powers of two; cap_corr 0 when sync == 0) */
+    uint64_t device_bytes;  /* what the stream holds on the device (host handle: in host memory): the record, the rings,
+                               the taps — fixed at creation — and the host-fed form's staging of 64 rows, which grows only
+                               when one push can release more */
+} aptgpu_stream_info;
+typedef struct aptgpu_stream_result {
+    uint32_t struct_size;   /* set by the caller */
+    int32_t status;         /* APTGPU_OK or APTGPU_ERR_INTERNAL */
+    int32_t reason;         /* 0; 1 "<10 rows"; 2 "<5 sync frames"; 5-7 an internal bound was exceeded (a defect: the
+                               stream stays failed until reset) */
+    uint32_t n_rows;        /* rows released by this push (or finish) */
+    uint64_t rows_total;    /* rows released so far */
+    uint64_t n_sync;        /* peaks found so far (0 when sync == 0) */
+    uint64_t n_in;          /* samples pushed so far */
+    uint64_t work_len;      /* final work-rate samples */
+    uint64_t scan_pos;      /* correlation positions the picker has consumed (0 when sync == 0) */
+} aptgpu_stream_result;
+/* ctx nullable (device 0, strict, a stream of its own).  Every refusal happens before a device is touched. */
+int aptgpu_stream_create(const aptgpu_context *ctx, const aptgpu_settings *settings,
+                         const aptgpu_stream_settings *stream_settings, aptgpu_stream **out, char *err, size_t err_cap);
+/* The same state machine in plain C++ on the CPU (no GPU needed): same handle type, same bits, same release schedule;
+ * ctx (nullable) is read for its mode only.  The *_device entry points refuse such a handle. */
+int aptgpu_stream_create_host(const aptgpu_context *ctx, const aptgpu_settings *settings,
+                              const aptgpu_stream_settings *stream_settings, aptgpu_stream **out, char *err,
+                              size_t err_cap);
+void aptgpu_stream_destroy(aptgpu_stream *stream);
+int aptgpu_stream_get_info(const aptgpu_stream *stream, aptgpu_stream_info *info);
+/* Back to the state after creation (nothing is reallocated). */
+int aptgpu_stream_reset(aptgpu_stream *stream, char *err, size_t err_cap);
+/* Upper bound of the rows a push of n more samples — or, n == 0, a finish — can release now.  One event of the
+ * reference's picker can push any number of peaks at once (decode.rs:244-246: a correlation that climbs for rows on end
+ * is followed by as many copies as rows went by), so the bound does not follow from n alone: it is
+ * work_len(samples so far + n) / samples_per_row + 1 minus the rows the host knows to be out (the host-fed calls and
+ * aptgpu_stream_results learn that count; device-resident pushes that never ask see the bound grow by a row per row
+ * pushed).  Two or three on a pass that keeps its sync.  0 for a null stream. */
+size_t aptgpu_stream_rows_bound(const aptgpu_stream *stream, size_t n);
+/* Host-fed: n samples (float or int16_t, as created) in; result->n_rows rows of 2080 floats and their work-rate
+ * positions out (rows_cap rows of room in each; below aptgpu_stream_rows_bound(stream, n) is APTGPU_ERR_INVALID before
+ * anything is consumed).  result->struct_size must be set.  One record is read back per call, whatever n is.  After a
+ * finish only reset and destroy are accepted. */
+int aptgpu_stream_push(aptgpu_stream *stream, const void *samples, size_t n, float *rows, uint64_t *positions,
+                       size_t rows_cap, aptgpu_stream_result *result, char *err, size_t err_cap);
+int aptgpu_stream_finish(aptgpu_stream *stream, float *rows, uint64_t *positions, size_t rows_cap,
+                         aptgpu_stream_result *result, char *err, size_t err_cap);
+/* Device-resident: samples, rows and positions are device pointers; asynchronous on the context's stream, no host
+ * synchronisation, nothing read back.  A push longer than max_push becomes several launch sequences.  The end-of-signal
+ * errors are reported by aptgpu_stream_results, which waits and returns the record of the last push. */
+int aptgpu_stream_push_device(aptgpu_stream *stream, const void *d_samples, size_t n, float *d_rows,
+                              uint64_t *d_positions, size_t rows_cap, char *err, size_t err_cap);
+int aptgpu_stream_finish_device(aptgpu_stream *stream, float *d_rows, uint64_t *d_positions, size_t rows_cap, char *err,
+                                size_t err_cap);
+int aptgpu_stream_results(aptgpu_stream *stream, aptgpu_stream_result *result, char *err, size_t err_cap);
+
+/* ====================================================================== */
 /* 5. WAV ingest in front of decode()                 */
 /* ====================================================================== */
 /* noaa_apt::load / wav::load_wav (src/noaa_apt.rs:114-130, src/wav.rs:11-57): the container is */

@@ -190,6 +190,24 @@ class TrackResult(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class _CStreamSettings(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("input_rate_hz", C.c_uint32), ("sync", C.c_int32), ("format", C.c_int32),
+                ("max_push", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class StreamInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("work_rate", C.c_uint32), ("pw", C.c_uint32),
+                ("samples_per_row", C.c_uint32), ("l", C.c_uint32), ("m", C.c_uint32),
+                ("n_resample_taps", C.c_uint32), ("n_lowpass_taps", C.c_uint32), ("max_push", C.c_uint32),
+                ("cap_in", C.c_uint32), ("cap_f", C.c_uint32), ("cap_corr", C.c_uint32), ("device_bytes", C.c_uint64)]
+
+
+class StreamResult(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("status", C.c_int32), ("reason", C.c_int32), ("n_rows", C.c_uint32),
+                ("rows_total", C.c_uint64), ("n_sync", C.c_uint64), ("n_in", C.c_uint64), ("work_len", C.c_uint64),
+                ("scan_pos", C.c_uint64)]
+
+
 class _CThermalCoeffs(C.Structure):
     """aptgpu_thermal_coeffs"""
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("prt", (C.c_double * 3) * 4),
@@ -477,6 +495,20 @@ def lib():
     L.aptgpu_plan_track_positions.argtypes = [vp, i32, _u64p, _f32p, sz, C.POINTER(sz)]
     L.aptgpu_decode_tracked.argtypes = [cp, C.POINTER(_CSettings), _f32p, sz, u32, cts, C.POINTER(_f32p), C.POINTER(sz),
                                         C.POINTER(_u64p), C.POINTER(_f32p), ctr, C.c_char_p, sz]
+    css, csr = C.POINTER(_CStreamSettings), C.POINTER(StreamResult)
+    for name in ("aptgpu_stream_create", "aptgpu_stream_create_host"):
+        getattr(L, name).argtypes = [cp, C.POINTER(_CSettings), css, C.POINTER(vp), C.c_char_p, sz]
+    L.aptgpu_stream_destroy.argtypes = [vp]
+    L.aptgpu_stream_destroy.restype = None
+    L.aptgpu_stream_get_info.argtypes = [vp, C.POINTER(StreamInfo)]
+    L.aptgpu_stream_reset.argtypes = [vp, C.c_char_p, sz]
+    L.aptgpu_stream_rows_bound.argtypes = [vp, sz]
+    L.aptgpu_stream_rows_bound.restype = sz
+    L.aptgpu_stream_push.argtypes = [vp, vp, sz, _f32p, _u64p, sz, csr, C.c_char_p, sz]
+    L.aptgpu_stream_finish.argtypes = [vp, _f32p, _u64p, sz, csr, C.c_char_p, sz]
+    L.aptgpu_stream_push_device.argtypes = [vp, vp, sz, vp, vp, sz, C.c_char_p, sz]
+    L.aptgpu_stream_finish_device.argtypes = [vp, vp, vp, sz, C.c_char_p, sz]
+    L.aptgpu_stream_results.argtypes = [vp, csr, C.c_char_p, sz]
     _lib = L
     return L
 
@@ -1610,6 +1642,131 @@ def decode_tracked(context: Optional["Context"], settings: "Settings", signal, i
     rows = _take(rw, n_out.value)
     p, q = _take(pos, info.n_positions, np.uint64), _take(sc, info.n_positions)
     return (rows, p, q, info) if return_info else rows
+
+
+class LiveDecoder:
+    """aptgpu_stream: live decode.  Push the recording in chunks of any size; every push returns the
+    image rows that are final — bit-identical to what strict decode() of the complete recording holds at that place,
+    whatever is pushed later — and their work-rate positions.  finish() releases the rest and raises what decode()
+    would raise ("less than 10 rows", "less than 5 sync frames"); rows handed out before stay handed out.  dtype:
+    np.float32 or np.int16 (mono PCM16, the value as f32).  host=True: the plain C++ twin on the CPU (same bits, no GPU).
+    `result` is the record of the last call, `info` the stream's geometry and ring capacities."""
+
+    def __init__(self, settings, input_rate, sync=True, context=None, dtype=np.float32, max_push=None, host=False):
+        self._dtype = np.dtype(dtype)
+        fmt = {np.dtype(np.float32): 0, np.dtype(np.int16): 1}.get(self._dtype)
+        if fmt is None:
+            raise InvalidError("stream: dtype must be float32 or int16")
+        self._ctx = context or Context()
+        cctx, cs = self._ctx._c(), settings._c()
+        css = _CStreamSettings(C.sizeof(_CStreamSettings), int(input_rate.get_hz()), 1 if sync else 0, fmt, int(max_push or 0), 0)
+        self._p = C.c_void_p()
+        self.host = bool(host)
+        err = C.create_string_buffer(_ERRCAP)
+        fn = lib().aptgpu_stream_create_host if host else lib().aptgpu_stream_create
+        _check(fn(C.byref(cctx), C.byref(cs), C.byref(css), C.byref(self._p), err, _ERRCAP), err)
+        self.info = StreamInfo(struct_size=C.sizeof(StreamInfo))
+        _check(lib().aptgpu_stream_get_info(self._p, C.byref(self.info)))
+        self.result = StreamResult(struct_size=C.sizeof(StreamResult))
+
+    def close(self):
+        if self._p:
+            lib().aptgpu_stream_destroy(self._p)
+            self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def get_info(self):
+        info = StreamInfo(struct_size=C.sizeof(StreamInfo))
+        _check(lib().aptgpu_stream_get_info(self._p, C.byref(info)))
+        return info
+
+    def rows_bound(self, n=0):
+        """Upper bound of the rows a push of n more samples (0: a finish) can release now: from the work signal's length
+        after it and the rows known to be out (one event of the picker can push any number of peaks)."""
+        return int(lib().aptgpu_stream_rows_bound(self._p, int(n)))
+
+    def reset(self):
+        err = C.create_string_buffer(_ERRCAP)
+        _check(lib().aptgpu_stream_reset(self._p, err, _ERRCAP), err)
+        self.result = StreamResult(struct_size=C.sizeof(StreamResult))
+
+    def _call(self, chunk, rows_cap):
+        finish = chunk is None
+        n = 0 if finish else chunk.size
+        cap = self.rows_bound(n) if rows_cap is None else int(rows_cap)
+        rows = np.empty((max(cap, 1), PX_PER_ROW), np.float32)
+        pos = np.empty(max(cap, 1), np.uint64)
+        res = StreamResult(struct_size=C.sizeof(StreamResult))
+        err = C.create_string_buffer(_ERRCAP)
+        rp, pp = rows.ctypes.data_as(_f32p), pos.ctypes.data_as(_u64p)
+        if finish:
+            rc = lib().aptgpu_stream_finish(self._p, rp, pp, cap, C.byref(res), err, _ERRCAP)
+        else:
+            rc = lib().aptgpu_stream_push(self._p, chunk.ctypes.data_as(C.c_void_p), n, rp, pp, cap, C.byref(res), err,
+                                          _ERRCAP)
+        if rc in (0, 1):  # (an end-of-signal error fills the record; a refused call leaves it alone)
+            self.result = res
+        _check(rc, err)
+        k = int(res.n_rows)
+        return rows[:k].copy(), pos[:k].copy()
+
+    def push(self, chunk, rows_cap=None):
+        """chunk: 1-D samples of the stream's dtype -> (rows [n, 2080] f32, positions [n] u64) that became final."""
+        return self._call(np.ascontiguousarray(chunk, dtype=self._dtype).reshape(-1), rows_cap)
+
+    def finish(self, rows_cap=None):
+        """The end of the recording: the remaining rows, or the error decode() would raise."""
+        return self._call(None, rows_cap)
+
+    def push_device(self, d_samples, n, d_rows, d_positions, rows_cap):
+        """Device pointers (ints); asynchronous on the context's stream.  rows_cap >= rows_bound(n)."""
+        err = C.create_string_buffer(_ERRCAP)
+        _check(lib().aptgpu_stream_push_device(self._p, d_samples, int(n), d_rows, d_positions, int(rows_cap), err,
+                                               _ERRCAP), err)
+
+    def finish_device(self, d_rows, d_positions, rows_cap):
+        err = C.create_string_buffer(_ERRCAP)
+        _check(lib().aptgpu_stream_finish_device(self._p, d_rows, d_positions, int(rows_cap), err, _ERRCAP), err)
+
+    def results(self):
+        """Waits for the device-resident calls and returns the record of the last one (raising its error)."""
+        res = StreamResult(struct_size=C.sizeof(StreamResult))
+        err = C.create_string_buffer(_ERRCAP)
+        rc = lib().aptgpu_stream_results(self._p, C.byref(res), err, _ERRCAP)
+        if rc in (0, 1):
+            self.result = res
+        _check(rc, err)
+        return res
+
+
+def decode_live(context: Optional["Context"], settings: "Settings", chunks, input_rate: "Rate", sync: bool, host=False,
+                max_push=None):
+    """decode() over an iterable of chunks through a LiveDecoder: returns what decode() returns for their
+    concatenation (flat f32, rows * 2080) and raises what it raises.  The chunks' dtype (float32 or int16) is the
+    first chunk's."""
+    it = iter(chunks)
+    first = next(it, None)
+    dtype = np.int16 if first is not None and np.asarray(first).dtype == np.int16 else np.float32
+    out = []
+    with LiveDecoder(settings, input_rate, sync, context, dtype, max_push, host) as dec:
+        if first is not None:
+            out.append(dec.push(first)[0])
+        for chunk in it:
+            out.append(dec.push(chunk)[0])
+        out.append(dec.finish()[0])
+    return np.concatenate(out).reshape(-1) if out else np.zeros(0, np.float32)
 
 
 THERMAL_COLD_WHITE = 1
