@@ -5,7 +5,7 @@
  *                   [--histogram | --histogram-float] [--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE] [--png]
  *                   [--tle FILE --sat NAME (--start-ms N | --end-ms N)] [--rotate no|yes|orbit]
  *                   [--project equirect|mercator[:step_deg] [--grid DEG]] [--despeckle R[:T]] [--track=[W,LAMBDA]]
- *                   [--live SECONDS]
+ *                   [--live SECONDS] [--iq FMT:FS:D[:SHIFT_HZ]]
  *
  * What `noaa-apt in.wav -o out.png` does (main.rs:91-110, noaa_apt.rs:114-235): load -> decode ->
  * contrast limits -> 8-bit image, written as a binary PGM, or with --png as the PNG file the GPU
@@ -32,7 +32,12 @@
  * refuses as "less than 5 sync frames".
  * --live SECONDS: the recording goes through a live-decode stream (aptgpu_stream_*) in chunks of SECONDS, as a ground
  * station would feed it during the pass; every push hands back the rows that are final, and their concatenation — the
- * image written — is the same PGM as without the flag.  Plain C99, links only libaptgpu.so.
+ * image written — is the same PGM as without the flag.
+ * --iq FMT:FS:D[:SHIFT_HZ]: the input file is raw interleaved IQ (FMT u8, s8, s16 or f32; FS frames per second; the
+ * audio comes out at FS / D; the signal sits SHIFT_HZ off the centre) with the library's usual channel filter.  Without
+ * --live the frames go through aptgpu_fm_demodulate and aptgpu_decode; with --live SECONDS through aptgpu_iq_live_* in
+ * chunks of SECONDS of frames, the audio never leaving the device.  Both write the same PGM.
+ * Plain C99, links only libaptgpu.so.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -53,14 +58,14 @@ int main(int argc, char **argv)
                 "[--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE] [--png]\n"
                 "       [--tle FILE --sat NAME (--start-ms N | --end-ms N)] [--rotate no|yes|orbit]\n"
                 "       [--project equirect|mercator[:step_deg] [--grid DEG]] [--despeckle R[:T]] [--track=[W,LAMBDA]]\n"
-                "       [--live SECONDS]\n", argv[0]);
+                "       [--live SECONDS] [--iq u8|s8|s16|f32:FS:D[:SHIFT_HZ]]\n", argv[0]);
         return 2;
     }
     int contrast = APTGPU_CONTRAST_PERCENT, sync = 1, lab = 0, png = 0;
     const char *palette_path = NULL, *map_dir = NULL, *track_path = NULL, *tle_path = NULL, *sat = NULL;
     int rotate = APTGPU_ROTATE_NO, ref_kind = -1;
     long long ref_ms = 0;
-    const char *project = NULL, *despeckle = NULL, *flywheel = NULL;
+    const char *project = NULL, *despeckle = NULL, *flywheel = NULL, *iq_spec = NULL;
     double grid_deg = 0.0, live_seconds = 0.0;
     for (int i = 3; i < argc; ++i) {
         if (!strcmp(argv[i], "telemetry")) contrast = APTGPU_CONTRAST_TELEMETRY;
@@ -83,6 +88,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--grid") && i + 1 < argc) grid_deg = atof(argv[++i]);
         else if (!strcmp(argv[i], "--despeckle") && i + 1 < argc) despeckle = argv[++i];
         else if (!strcmp(argv[i], "--live") && i + 1 < argc) live_seconds = atof(argv[++i]);
+        else if (!strcmp(argv[i], "--iq") && i + 1 < argc) iq_spec = argv[++i];
         else if (!strcmp(argv[i], "--rotate") && i + 1 < argc) {
             const char *r = argv[++i];
             rotate = !strcmp(r, "orbit") ? APTGPU_ROTATE_ORBIT : !strcmp(r, "yes") ? APTGPU_ROTATE_YES : APTGPU_ROTATE_NO;
@@ -136,7 +142,74 @@ int main(int argc, char **argv)
     aptgpu_stats stats;
     uint32_t rate = 0;
     int rc;
-    if (flywheel) {
+    if (iq_spec) {
+        /* raw IQ frames: FM demodulation in front of the decode, in one piece or as a live stream */
+        aptgpu_fm_settings fs;
+        aptgpu_fm_default_settings(&fs);
+        char fmt[8] = "";
+        unsigned fs_hz = 0, dec = 0;
+        double shift = 0.0;
+        if (sscanf(iq_spec, "%7[^:]:%u:%u:%lf", fmt, &fs_hz, &dec, &shift) < 3) {
+            fprintf(stderr, "--iq FMT:FS:D[:SHIFT_HZ]: cannot read \"%s\"\n", iq_spec);
+            return 2;
+        }
+        fs.format = !strcmp(fmt, "u8") ? APTGPU_IQ_U8 : !strcmp(fmt, "s8") ? APTGPU_IQ_S8 : !strcmp(fmt, "s16") ? APTGPU_IQ_S16
+                    : !strcmp(fmt, "f32") ? APTGPU_IQ_F32 : -1;
+        fs.sample_rate_hz = fs_hz;
+        fs.decimation = dec;
+        fs.shift_hz = shift;
+        const size_t frame_bytes = fs.format == APTGPU_IQ_S16 ? 4 : fs.format == APTGPU_IQ_F32 ? 8 : 2;
+        const size_t n_frames = (size_t)n / frame_bytes;  /* (a trailing partial frame is dropped) */
+        memset(&stats, 0, sizeof stats);
+        if (live_seconds > 0.0) {
+            aptgpu_iq_live_settings ls;
+            memset(&ls, 0, sizeof ls);
+            ls.struct_size = sizeof ls;
+            ls.sync = sync;
+            aptgpu_iq_live *live = NULL;
+            rc = aptgpu_iq_live_create(&ctx, &settings, &fs, &ls, &live, err, sizeof err);
+            if (rc != APTGPU_OK) { fprintf(stderr, "iq live failed (%d): %s\n", rc, err); return 1; }
+            size_t chunk = (size_t)(live_seconds * fs_hz);
+            if (chunk == 0) chunk = 1;
+            aptgpu_stream_result sr;
+            memset(&sr, 0, sizeof sr);
+            sr.struct_size = sizeof sr;
+            size_t n_rows = 0, pushes = 0;
+            for (size_t at = 0; rc == APTGPU_OK; at += chunk, ++pushes) {
+                const int last = at >= n_frames;  /* the call after the last chunk is the finish */
+                const size_t take = last ? 0 : (n_frames - at < chunk ? n_frames - at : chunk);
+                const size_t cap = aptgpu_iq_live_rows_bound(live, take);
+                float *grown = realloc(rows, (n_rows + cap + 1) * 2080 * sizeof(float));
+                uint64_t *pos = malloc((cap + 1) * sizeof(uint64_t));
+                if (!grown || !pos) { fprintf(stderr, "out of memory\n"); return 1; }
+                rows = grown;
+                rc = last ? aptgpu_iq_live_finish(live, rows + n_rows * 2080, pos, cap, &sr, err, sizeof err)
+                          : aptgpu_iq_live_push(live, bytes + at * frame_bytes, take, rows + n_rows * 2080, pos, cap, &sr, err,
+                                                sizeof err);
+                free(pos);
+                if (rc == APTGPU_OK) n_rows += sr.n_rows;
+                if (last) break;
+            }
+            aptgpu_iq_live_destroy(live);
+            free(bytes);
+            if (rc != APTGPU_OK) { fprintf(stderr, "live decode failed (%d): %s\n", rc, err); return 1; }
+            n_rows_px = n_rows * 2080;
+            rate = fs_hz / (dec ? dec : 1);
+            fprintf(stderr, "%u Hz audio from %u Hz IQ, %llu sync frames, %llu rows from %llu pushes of %g s\n", rate, fs_hz,
+                    (unsigned long long)sr.n_sync, (unsigned long long)n_rows, (unsigned long long)pushes, live_seconds);
+        } else {
+            float *audio = NULL;
+            size_t n_audio = 0;
+            rc = aptgpu_fm_demodulate(&ctx, &fs, bytes, n_frames, &audio, &n_audio, &rate, err, sizeof err);
+            free(bytes);
+            if (rc != APTGPU_OK) { fprintf(stderr, "fm demodulation failed (%d): %s\n", rc, err); return 1; }
+            rc = aptgpu_decode(&ctx, &settings, audio, n_audio, rate, sync, &rows, &n_rows_px, &stats, err, sizeof err);
+            aptgpu_free(audio);
+            if (rc != APTGPU_OK) { fprintf(stderr, "decode failed (%d): %s\n", rc, err); return 1; }
+            fprintf(stderr, "%u Hz audio from %u Hz IQ, %llu sync frames, %llu rows\n", rate, fs_hz,
+                    (unsigned long long)stats.n_sync, (unsigned long long)(n_rows_px / 2080));
+        }
+    } else if (flywheel) {
         /* load -> front end -> flywheel sync: the rows of the tracked path, with each row's lock indicator */
         aptgpu_track_settings ts = {sizeof(aptgpu_track_settings), 8, 0.1f, 0};
         if (*flywheel && sscanf(flywheel, "%u,%f", &ts.max_jitter, &ts.penalty) != 2) {

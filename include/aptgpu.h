@@ -1256,6 +1256,105 @@ int aptgpu_stream_finish_device(aptgpu_stream *stream, float *d_rows, uint64_t *
 int aptgpu_stream_results(aptgpu_stream *stream, aptgpu_stream_result *result, char *err, size_t err_cap);
 
 /* ====================================================================== */
+/* 4b'. FM demodulation in streaming form, and live decode from IQ */
+/* ====================================================================== */
+/* An SDR delivers IQ frames, not audio.  An FM stream takes them in pushes of any size and returns the outputs of §4b
+ * as they become final.  Let x be the frames pushed so far, n their count, x* any continuation of x:
+ *   M(n) = (n - T) / D + 1 for n >= T, else 0;  out_len(n) = max(M(n) - 1, 0) (aptgpu_fm_out_len).
+ *   a[m] is FINAL once n >= (m + 1) D + T: from then on it has the bits aptgpu_fm_demodulate(x*) gives it on the same
+ *   side (kernel or twin).  A push that takes the count from n0 to n1 returns exactly a[out_len(n0) .. out_len(n1)),
+ *   never earlier and never later: the release schedule is a function of the chunk sizes alone.  There is no finish:
+ *   the definition keeps the valid part only, so nothing is held back at the end.
+ * The frame counter is 64 bits; the phase uses its low 32 bits ((uint32) i * pw), the runs of 8 its low 3.  A stream
+ * created with first_frame counts its first frame as absolute frame first_frame: that offsets the phase and the run
+ * grid (a station that runs on passes 2^32 frames after half an hour at 2.4 MS/s); the decimation grid counts from the
+ * first frame pushed.  reset returns to first_frame.
+ * State: the raw frames from max(M(n) - 1, 0) D on, fewer than T + D of them, in the input format, in two device
+ * buffers used in turn; the next push computes the v it shares with the previous one again, from the same frames in
+ * the same order.  The host mirrors n and nothing else: a device-resident push synchronises nothing and allocates
+ * nothing.  A push of more than max_push_frames is a sequence of launches back to back.
+ * Refused with APTGPU_ERR_INVALID and a text naming the field, before anything is enqueued and with the stream left as
+ * it was: everything §4b refuses; a short struct_size; max_push_frames == 0 or above 2^28; a null pointer or one not
+ * aligned to a component (audio: to a float) with something to read or write; audio_cap below
+ * aptgpu_fm_stream_out_len. */
+typedef struct aptgpu_fm_stream aptgpu_fm_stream;
+typedef struct aptgpu_fm_stream_settings {
+    uint32_t struct_size;      /* sizeof(aptgpu_fm_stream_settings) */
+    uint32_t max_push_frames;  /* frames one launch takes (longer pushes are split; the host-fed staging): 1 ... 2^28 */
+    uint64_t first_frame;      /* absolute index of the first frame pushed */
+    uint64_t reserved;
+} aptgpu_fm_stream_settings;
+typedef struct aptgpu_fm_stream_info {
+    uint32_t struct_size;      /* set by the caller */
+    uint32_t fs_out, n_taps, decimation, pw; /* as aptgpu_fm_info */
+    uint32_t carry_frames;     /* frames held now: frames - max(M(frames) - 1, 0) D */
+    double shift_hz_used;
+    const float *taps;         /* h, owned by the stream */
+    uint64_t frames;           /* pushed so far */
+    uint64_t outputs;          /* returned so far: out_len(frames) */
+    uint64_t first_frame;
+    uint64_t device_bytes;     /* fixed at creation (host handle: host memory, which follows the pushes' sizes) */
+    uint32_t max_push_frames;
+    uint32_t reserved;
+} aptgpu_fm_stream_info;
+/* stream_settings nullable (max_push_frames 2^20, first_frame 0).  ctx as aptgpu_fm_create: its device and stream (NULL: the null stream). */
+int aptgpu_fm_stream_create(const aptgpu_context *ctx, const aptgpu_fm_settings *settings,
+                            const aptgpu_fm_stream_settings *stream_settings, aptgpu_fm_stream **out, char *err,
+                            size_t err_cap);
+/* The twin in plain C++ (no GPU needed): the same indexing; equals aptgpu_fm_demodulate_host of the whole recording
+ * bit for bit.  aptgpu_fm_stream_push_device refuses such a handle. */
+int aptgpu_fm_stream_create_host(const aptgpu_fm_settings *settings, const aptgpu_fm_stream_settings *stream_settings,
+                                 aptgpu_fm_stream **out, char *err, size_t err_cap);
+void aptgpu_fm_stream_destroy(aptgpu_fm_stream *s);
+int aptgpu_fm_stream_reset(aptgpu_fm_stream *s, char *err, size_t err_cap);
+int aptgpu_fm_stream_get_info(const aptgpu_fm_stream *s, aptgpu_fm_stream_info *info);
+/* The outputs a push of n_frames more frames returns now. */
+size_t aptgpu_fm_stream_out_len(const aptgpu_fm_stream *s, size_t n_frames);
+/* Host-fed: iq and audio are host arrays; returns when the audio is there. */
+int aptgpu_fm_stream_push(aptgpu_fm_stream *s, const void *iq, size_t n_frames, float *audio, size_t audio_cap,
+                          size_t *n_out, char *err, size_t err_cap);
+/* Device-resident: asynchronous on the context's stream; the chunk is read in place (16-byte alignment of its runs
+ * lets the loads be 16 bytes wide, with the same bits) and must stay until the stream has passed the call.  *n_out is
+ * known on return; nothing is written behind it. */
+int aptgpu_fm_stream_push_device(aptgpu_fm_stream *s, const void *d_iq, size_t n_frames, float *d_audio,
+                                 size_t audio_cap, size_t *n_out, char *err, size_t err_cap);
+
+/* Live decode from IQ: one object owns an FM stream, an aptgpu_stream created for fs_out in f32 and a device audio
+ * scratch, all on the context's HIP stream; frames go in, final rows come out, the audio never leaves the device.  A
+ * push is aptgpu_fm_stream_push_device into the scratch followed by aptgpu_stream_push_device of what it returned, in
+ * pieces of at most max_push_frames frames; rows, positions, the record, finish and its errors are the decode
+ * stream's (§4d), fed the one-shot's audio. */
+typedef struct aptgpu_iq_live aptgpu_iq_live;
+typedef struct aptgpu_iq_live_settings {
+    uint32_t struct_size;      /* sizeof(aptgpu_iq_live_settings) */
+    int32_t sync;
+    uint32_t max_push_frames;  /* the FM stream's; 0 = 2^20 */
+    uint32_t max_push;         /* the decode stream's (audio samples); 0 = its default */
+    uint64_t first_frame;
+} aptgpu_iq_live_settings;
+int aptgpu_iq_live_create(const aptgpu_context *ctx, const aptgpu_settings *decode_settings,
+                          const aptgpu_fm_settings *fm_settings, const aptgpu_iq_live_settings *live_settings,
+                          aptgpu_iq_live **out, char *err, size_t err_cap);
+int aptgpu_iq_live_create_host(const aptgpu_context *ctx, const aptgpu_settings *decode_settings,
+                               const aptgpu_fm_settings *fm_settings, const aptgpu_iq_live_settings *live_settings,
+                               aptgpu_iq_live **out, char *err, size_t err_cap);
+void aptgpu_iq_live_destroy(aptgpu_iq_live *s);
+int aptgpu_iq_live_reset(aptgpu_iq_live *s, char *err, size_t err_cap);
+/* either info may be NULL */
+int aptgpu_iq_live_get_info(const aptgpu_iq_live *s, aptgpu_fm_stream_info *fm_info, aptgpu_stream_info *stream_info);
+/* aptgpu_stream_rows_bound of the audio a push of n_frames more frames produces (n_frames == 0: a finish) */
+size_t aptgpu_iq_live_rows_bound(const aptgpu_iq_live *s, size_t n_frames);
+int aptgpu_iq_live_push(aptgpu_iq_live *s, const void *iq, size_t n_frames, float *rows, uint64_t *positions,
+                        size_t rows_cap, aptgpu_stream_result *result, char *err, size_t err_cap);
+int aptgpu_iq_live_finish(aptgpu_iq_live *s, float *rows, uint64_t *positions, size_t rows_cap,
+                          aptgpu_stream_result *result, char *err, size_t err_cap);
+int aptgpu_iq_live_push_device(aptgpu_iq_live *s, const void *d_iq, size_t n_frames, float *d_rows,
+                               uint64_t *d_positions, size_t rows_cap, char *err, size_t err_cap);
+int aptgpu_iq_live_finish_device(aptgpu_iq_live *s, float *d_rows, uint64_t *d_positions, size_t rows_cap, char *err,
+                                 size_t err_cap);
+int aptgpu_iq_live_results(aptgpu_iq_live *s, aptgpu_stream_result *result, char *err, size_t err_cap);
+
+/* ====================================================================== */
 /* 5. WAV ingest in front of decode()                 */
 /* ====================================================================== */
 /* noaa_apt::load / wav::load_wav (src/noaa_apt.rs:114-130, src/wav.rs:11-57): the container is */

@@ -42,6 +42,8 @@ Names, argument meaning and error behaviour follow the reference:
     decode_tracked, TrackSettings, Plan.track_device       starts tracked through noise and dropouts, DESIGN.md §21
     LiveDecoder, decode_live                               the reference's to-do list, docs/development.md:151: audio
                                                            pushed in chunks, finished rows handed back, DESIGN.md §22
+    FmStream, LiveIqDecoder, decode_live_iq                the same from IQ frames: the FM demodulator in streaming form
+                                                           and its coupling to the live decode, DESIGN.md §23
     percent, get_min, get_max, map_signal_u8               /root/reference/src/misc.rs:119, dsp.rs:20-54
     read_telemetry, Telemetry                              /root/reference/src/telemetry.rs:19-243
 
@@ -66,6 +68,7 @@ from .api import (  # noqa: F401
     FM_SWAP_IQ, FM_MAX_BATCH,
     TrackSettings, TrackResult, track_sync, track_sync_host, sync_score, decode_tracked, TRACK_MAX_JITTER,
     LiveDecoder, decode_live, StreamInfo, StreamResult,
+    FmStream, FmStreamInfo, LiveIqDecoder, decode_live_iq, FM_STREAM_MAX_PUSH_FRAMES,
     Projection, ProjectionSettings, projection_fit, project_image, PROJECT_REASON_CAPACITY,
     Composite, composite_images, COMPOSITE_REASON_PASS, COMPOSITE_MAX_PASSES,
     SatName, RefTime, OrbitSettings, sat_track, sat_track_host, south_to_north_pass, SAT_REASON_SGP4,

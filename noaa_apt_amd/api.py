@@ -244,6 +244,27 @@ class _CFmInfo(C.Structure):
                 ("pw", C.c_uint32), ("reserved", C.c_uint32), ("shift_hz_used", C.c_double), ("taps", _f32p)]
 
 
+class _CFmStreamSettings(C.Structure):
+    """aptgpu_fm_stream_settings"""
+    _fields_ = [("struct_size", C.c_uint32), ("max_push_frames", C.c_uint32), ("first_frame", C.c_uint64),
+                ("reserved", C.c_uint64)]
+
+
+class FmStreamInfo(C.Structure):
+    """aptgpu_fm_stream_info: the aptgpu_fm_info fields, the frames pushed and the outputs returned so far, the frames
+    held (carry_frames) and what the stream holds on the device."""
+    _fields_ = [("struct_size", C.c_uint32), ("fs_out", C.c_uint32), ("n_taps", C.c_uint32), ("decimation", C.c_uint32),
+                ("pw", C.c_uint32), ("carry_frames", C.c_uint32), ("shift_hz_used", C.c_double), ("taps", _f32p),
+                ("frames", C.c_uint64), ("outputs", C.c_uint64), ("first_frame", C.c_uint64),
+                ("device_bytes", C.c_uint64), ("max_push_frames", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class _CIqLiveSettings(C.Structure):
+    """aptgpu_iq_live_settings"""
+    _fields_ = [("struct_size", C.c_uint32), ("sync", C.c_int32), ("max_push_frames", C.c_uint32),
+                ("max_push", C.c_uint32), ("first_frame", C.c_uint64)]
+
+
 class WavSpec(C.Structure):
     """aptgpu_wav_spec: hound::WavSpec plus where the samples are."""
     _fields_ = [("channels", C.c_uint16), ("bits_per_sample", C.c_uint16),
@@ -509,6 +530,31 @@ def lib():
     L.aptgpu_stream_push_device.argtypes = [vp, vp, sz, vp, vp, sz, C.c_char_p, sz]
     L.aptgpu_stream_finish_device.argtypes = [vp, vp, vp, sz, C.c_char_p, sz]
     L.aptgpu_stream_results.argtypes = [vp, csr, C.c_char_p, sz]
+    cfss = C.POINTER(_CFmStreamSettings)
+    L.aptgpu_fm_stream_create.argtypes = [cp, cfm, cfss, C.POINTER(vp), C.c_char_p, sz]
+    L.aptgpu_fm_stream_create_host.argtypes = [cfm, cfss, C.POINTER(vp), C.c_char_p, sz]
+    L.aptgpu_fm_stream_destroy.argtypes = [vp]
+    L.aptgpu_fm_stream_destroy.restype = None
+    L.aptgpu_fm_stream_reset.argtypes = [vp, C.c_char_p, sz]
+    L.aptgpu_fm_stream_get_info.argtypes = [vp, C.POINTER(FmStreamInfo)]
+    L.aptgpu_fm_stream_out_len.argtypes = [vp, sz]
+    L.aptgpu_fm_stream_out_len.restype = sz
+    L.aptgpu_fm_stream_push.argtypes = [vp, vp, sz, vp, sz, C.POINTER(sz), C.c_char_p, sz]
+    L.aptgpu_fm_stream_push_device.argtypes = [vp, vp, sz, vp, sz, C.POINTER(sz), C.c_char_p, sz]
+    for name in ("aptgpu_iq_live_create", "aptgpu_iq_live_create_host"):
+        getattr(L, name).argtypes = [cp, C.POINTER(_CSettings), cfm, C.POINTER(_CIqLiveSettings), C.POINTER(vp),
+                                     C.c_char_p, sz]
+    L.aptgpu_iq_live_destroy.argtypes = [vp]
+    L.aptgpu_iq_live_destroy.restype = None
+    L.aptgpu_iq_live_reset.argtypes = [vp, C.c_char_p, sz]
+    L.aptgpu_iq_live_get_info.argtypes = [vp, C.POINTER(FmStreamInfo), C.POINTER(StreamInfo)]
+    L.aptgpu_iq_live_rows_bound.argtypes = [vp, sz]
+    L.aptgpu_iq_live_rows_bound.restype = sz
+    L.aptgpu_iq_live_push.argtypes = [vp, vp, sz, _f32p, _u64p, sz, csr, C.c_char_p, sz]
+    L.aptgpu_iq_live_finish.argtypes = [vp, _f32p, _u64p, sz, csr, C.c_char_p, sz]
+    L.aptgpu_iq_live_push_device.argtypes = [vp, vp, sz, vp, vp, sz, C.c_char_p, sz]
+    L.aptgpu_iq_live_finish_device.argtypes = [vp, vp, vp, sz, C.c_char_p, sz]
+    L.aptgpu_iq_live_results.argtypes = [vp, csr, C.c_char_p, sz]
     _lib = L
     return L
 
@@ -2075,6 +2121,207 @@ class FmDemodulator:
         _check(lib().aptgpu_fm_demodulate_device(self._p, k, (C.c_void_p * k)(*d_iq), (C.c_size_t * k)(*n_frames),
                                                  (C.c_void_p * k)(*d_audio), (C.c_size_t * k)(*audio_cap), err,
                                                  _ERRCAP), err)
+
+
+FM_STREAM_MAX_PUSH_FRAMES = 1 << 20
+
+
+class FmStream:
+    """aptgpu_fm_stream: fm_demodulate() in streaming form (DESIGN.md §23).  Push the frames in chunks of any size;
+    every push returns the outputs that became final, with the bits fm_demodulate() of the whole recording gives them
+    (host=True: fm_demodulate_host(), in plain C++ on the CPU).  A push that takes the frame count from n0 to n1 returns
+    exactly a[out_len(n0) .. out_len(n1)).  first_frame: the absolute index of the first frame (the phase uses its low
+    32 bits).  There is no finish: nothing is held back."""
+
+    def __init__(self, settings, context=None, max_push_frames=None, first_frame=0, host=False, struct_size=None):
+        cs = _fm_settings_c(settings)
+        self._ctx = context or Context()
+        self._cs = cs
+        try:
+            css = _CFmStreamSettings(C.sizeof(_CFmStreamSettings) if struct_size is None else int(struct_size),
+                                     FM_STREAM_MAX_PUSH_FRAMES if max_push_frames is None else int(max_push_frames),
+                                     int(first_frame), 0)
+        except (TypeError, ValueError, OverflowError) as e:
+            raise InvalidError(f"aptgpu_fm_stream_settings: {e}") from None
+        self._p = C.c_void_p()
+        self.host = bool(host)
+        err = C.create_string_buffer(_ERRCAP)
+        if host:
+            rc = lib().aptgpu_fm_stream_create_host(C.byref(cs), C.byref(css), C.byref(self._p), err, _ERRCAP)
+        else:
+            cctx = self._ctx._c()
+            rc = lib().aptgpu_fm_stream_create(C.byref(cctx), C.byref(cs), C.byref(css), C.byref(self._p), err, _ERRCAP)
+        _check(rc, err)
+        self.info = self.get_info()
+        self.rate = Rate.hz(self.info.fs_out)
+
+    def close(self):
+        if self._p:
+            lib().aptgpu_fm_stream_destroy(self._p)
+            self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def get_info(self):
+        info = FmStreamInfo(struct_size=C.sizeof(FmStreamInfo))
+        _check(lib().aptgpu_fm_stream_get_info(self._p, C.byref(info)))
+        return info
+
+    def out_len(self, n_frames):
+        """The outputs a push of n_frames more frames returns now."""
+        return int(lib().aptgpu_fm_stream_out_len(self._p, int(n_frames)))
+
+    def reset(self):
+        err = C.create_string_buffer(_ERRCAP)
+        _check(lib().aptgpu_fm_stream_reset(self._p, err, _ERRCAP), err)
+
+    def push(self, iq, audio_cap=None):
+        """iq: interleaved components of the format's dtype (or bytes; complex64 for F32) -> the f32 outputs that
+        became final."""
+        a, frames = _fm_iq(iq, self._cs)
+        cap = self.out_len(frames) if audio_cap is None else int(audio_cap)
+        out = np.empty(max(cap, 1), np.float32)
+        n = C.c_size_t()
+        err = C.create_string_buffer(_ERRCAP)
+        _check(lib().aptgpu_fm_stream_push(self._p, a.ctypes.data if a.size else None, frames, out.ctypes.data, cap,
+                                           C.byref(n), err, _ERRCAP), err)
+        return out[:n.value].copy()
+
+    def push_device(self, d_iq, n_frames, d_audio, audio_cap):
+        """Device pointers (ints); asynchronous on the context's stream.  Returns the outputs the push writes."""
+        n = C.c_size_t()
+        err = C.create_string_buffer(_ERRCAP)
+        _check(lib().aptgpu_fm_stream_push_device(self._p, d_iq or None, int(n_frames), d_audio or None, int(audio_cap),
+                                                  C.byref(n), err, _ERRCAP), err)
+        return int(n.value)
+
+
+class LiveIqDecoder:
+    """aptgpu_iq_live: live decode from IQ frames: an FmStream in front of a LiveDecoder on one HIP
+    stream, the audio staying on the device.  The surface is LiveDecoder's, with frames for samples: push() returns
+    the rows that became final and their positions, finish() the rest or decode()'s error.  `fm_info` and `info` are
+    the two stages' infos, `result` the record of the last call."""
+
+    def __init__(self, settings, fm_settings, sync=True, context=None, max_push_frames=None, max_push=None, first_frame=0,
+                 host=False):
+        cfm = _fm_settings_c(fm_settings)
+        self._cfm = cfm
+        self._ctx = context or Context()
+        cctx, cs = self._ctx._c(), settings._c()
+        cls = _CIqLiveSettings(C.sizeof(_CIqLiveSettings), 1 if sync else 0, int(max_push_frames or 0), int(max_push or 0),
+                               int(first_frame))
+        self._p = C.c_void_p()
+        self.host = bool(host)
+        err = C.create_string_buffer(_ERRCAP)
+        fn = lib().aptgpu_iq_live_create_host if host else lib().aptgpu_iq_live_create
+        _check(fn(C.byref(cctx), C.byref(cs), C.byref(cfm), C.byref(cls), C.byref(self._p), err, _ERRCAP), err)
+        self.fm_info, self.info = self.get_info()
+        self.result = StreamResult(struct_size=C.sizeof(StreamResult))
+
+    def close(self):
+        if self._p:
+            lib().aptgpu_iq_live_destroy(self._p)
+            self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def get_info(self):
+        """-> (FmStreamInfo, StreamInfo)"""
+        fi, si = FmStreamInfo(struct_size=C.sizeof(FmStreamInfo)), StreamInfo(struct_size=C.sizeof(StreamInfo))
+        _check(lib().aptgpu_iq_live_get_info(self._p, C.byref(fi), C.byref(si)))
+        return fi, si
+
+    def rows_bound(self, n_frames=0):
+        """Upper bound of the rows a push of n_frames more frames (0: a finish) can release now."""
+        return int(lib().aptgpu_iq_live_rows_bound(self._p, int(n_frames)))
+
+    def reset(self):
+        err = C.create_string_buffer(_ERRCAP)
+        _check(lib().aptgpu_iq_live_reset(self._p, err, _ERRCAP), err)
+        self.result = StreamResult(struct_size=C.sizeof(StreamResult))
+
+    def _call(self, chunk, frames, rows_cap):
+        finish = chunk is None
+        cap = self.rows_bound(frames) if rows_cap is None else int(rows_cap)
+        rows = np.empty((max(cap, 1), PX_PER_ROW), np.float32)
+        pos = np.empty(max(cap, 1), np.uint64)
+        res = StreamResult(struct_size=C.sizeof(StreamResult))
+        err = C.create_string_buffer(_ERRCAP)
+        rp, pp = rows.ctypes.data_as(_f32p), pos.ctypes.data_as(_u64p)
+        if finish:
+            rc = lib().aptgpu_iq_live_finish(self._p, rp, pp, cap, C.byref(res), err, _ERRCAP)
+        else:
+            rc = lib().aptgpu_iq_live_push(self._p, chunk.ctypes.data if chunk.size else None, frames, rp, pp, cap,
+                                           C.byref(res), err, _ERRCAP)
+        if rc in (0, 1):  # (an end-of-signal error fills the record; a refused call leaves it alone)
+            self.result = res
+        _check(rc, err)
+        k = int(res.n_rows)
+        return rows[:k].copy(), pos[:k].copy()
+
+    def push(self, iq, rows_cap=None):
+        """iq: interleaved components of the format's dtype -> (rows [n, 2080] f32, positions [n] u64) that became
+        final."""
+        a, frames = _fm_iq(iq, self._cfm)
+        return self._call(a, frames, rows_cap)
+
+    def finish(self, rows_cap=None):
+        """The end of the recording: the remaining rows, or the error decode() would raise."""
+        return self._call(None, 0, rows_cap)
+
+    def push_device(self, d_iq, n_frames, d_rows, d_positions, rows_cap):
+        """Device pointers (ints); asynchronous on the context's stream.  rows_cap >= rows_bound(n_frames)."""
+        err = C.create_string_buffer(_ERRCAP)
+        _check(lib().aptgpu_iq_live_push_device(self._p, d_iq or None, int(n_frames), d_rows, d_positions, int(rows_cap),
+                                                err, _ERRCAP), err)
+
+    def finish_device(self, d_rows, d_positions, rows_cap):
+        err = C.create_string_buffer(_ERRCAP)
+        _check(lib().aptgpu_iq_live_finish_device(self._p, d_rows, d_positions, int(rows_cap), err, _ERRCAP), err)
+
+    def results(self):
+        """Waits for the device-resident calls and returns the record of the last one (raising its error)."""
+        res = StreamResult(struct_size=C.sizeof(StreamResult))
+        err = C.create_string_buffer(_ERRCAP)
+        rc = lib().aptgpu_iq_live_results(self._p, C.byref(res), err, _ERRCAP)
+        if rc in (0, 1):
+            self.result = res
+        _check(rc, err)
+        return res
+
+
+def decode_live_iq(context: Optional["Context"], settings: "Settings", fm_settings: "FmSettings", chunks, sync: bool,
+                   host=False, max_push_frames=None):
+    """decode(fm_demodulate(...)) over an iterable of IQ chunks through a LiveIqDecoder: returns the rows of the
+    chunks' concatenation (flat f32, rows * 2080) and raises what decode() raises."""
+    out = []
+    with LiveIqDecoder(settings, fm_settings, sync, context, max_push_frames, host=host) as dec:
+        for chunk in chunks:
+            out.append(dec.push(chunk)[0])
+        out.append(dec.finish()[0])
+    return np.concatenate(out).reshape(-1)
 
 
 def process(context, signal, contrast_adjustment, rotate=Rotate.NO, color=None, orbit=None,

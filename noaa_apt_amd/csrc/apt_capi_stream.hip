@@ -4,6 +4,7 @@
 #include <memory>
 #include <vector>
 
+#include "apt_capi_stream_parts.hpp"
 #include "apt_capi_util.hpp"
 #include "apt_kernels_stream.hpp"
 
@@ -45,6 +46,7 @@ struct aptgpu_stream {
 namespace {
 
 using namespace apt::capi;
+using apt::capi::stream_parts::Target;
 
 constexpr uint32_t kStageRows = 64;
 
@@ -105,13 +107,14 @@ void reset_device(aptgpu_stream *s)
 }
 
 // n samples (host or device memory) into the ring and the four kernels, in segments of at most max_push; nothing waits
-void enqueue(aptgpu_stream *s, const void *samples, size_t n, bool finish, float *d_rows, uint64_t *d_pos, uint32_t rows_cap)
+// (first: this call opens a push; false continues one whose samples arrive in pieces)
+void enqueue(aptgpu_stream *s, const void *samples, size_t n, bool finish, float *d_rows, uint64_t *d_pos, uint32_t rows_cap,
+             bool first = true)
 {
     const st::Params &P = s->d.P;
     const size_t es = P.s16 ? 2 : 4;
     const char *src = static_cast<const char *>(samples);
     size_t done = 0;
-    bool first = true;
     do {
         const size_t seg = std::min<size_t>(n - done, P.max_push);
         if (seg) {
@@ -165,51 +168,71 @@ void check_call(const aptgpu_stream *s, size_t n, size_t rows_cap, const aptgpu_
     if (rows_cap < bound_of(s, n)) throw Error{ErrorKind::Invalid, "stream: rows_cap is below aptgpu_stream_rows_bound"};
 }
 
-// host-fed: rows and positions in host memory
-void push_host_fed(aptgpu_stream *s, const void *samples, size_t n, bool finish, float *rows, uint64_t *positions, size_t rows_cap,
-                   aptgpu_stream_result *result)
+// The host-fed form in three parts (apt_capi_stream_parts.hpp): where the rows of the push go, its samples in one or
+// more pieces, then ONE record and the rows it counts.
+Target begin_host_fed(aptgpu_stream *s, size_t n, float *rows, uint64_t *positions, size_t rows_cap)
 {
-    const st::Params &P = s->d.P;
-    const size_t es = P.s16 ? 2 : 4;
-    const uint32_t cap = static_cast<uint32_t>(std::min<size_t>(rows_cap, 0xFFFFFFFFu));
-    if (s->host) {
-        size_t done = 0;
-        do {
-            const size_t seg = std::min<size_t>(n - done, P.max_push);
-            const bool first = done == 0;
-            done += seg;
-            s->twin->push_segment(static_cast<const char *>(samples) + (done - seg) * es, seg, finish && done == n, first, rows, positions, cap);
-        } while (done < n);
-        if (finish) s->finished = true;
-        copy_result(s->twin->state(), result);
-        fail_record(*result);
-        return;
-    }
+    if (s->host) return Target{rows, positions, static_cast<uint32_t>(std::min<size_t>(rows_cap, 0xFFFFFFFFu))};
     apt::hip_check(hipSetDevice(s->device), "hipSetDevice");
-    // every launch sequence of the push into the staging, then ONE record and the rows it counts
     const uint32_t need = bound_of(s, n);
     if (need > s->stage_cap) {
         apt::hip_check(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
         s->stage.alloc(static_cast<size_t>(need) * (8 + st::kPx * 4));
         s->stage_cap = need;
     }
-    uint64_t *d_pos = reinterpret_cast<uint64_t *>(s->stage.ptr);
-    float *d_rows = reinterpret_cast<float *>(s->stage.ptr + static_cast<size_t>(s->stage_cap) * 8);
-    enqueue(s, samples, n, finish, d_rows, d_pos, need);
+    return Target{reinterpret_cast<float *>(s->stage.ptr + static_cast<size_t>(s->stage_cap) * 8),
+                  reinterpret_cast<uint64_t *>(s->stage.ptr), need};
+}
+
+void piece_of_push(aptgpu_stream *s, const void *samples, size_t n, bool first, bool finish, const Target &t)
+{
+    if (!s->host) {
+        enqueue(s, samples, n, finish, t.rows, t.positions, t.cap, first);
+        return;
+    }
+    const st::Params &P = s->d.P;
+    const size_t es = P.s16 ? 2 : 4;
+    size_t done = 0;
+    do {
+        const size_t seg = std::min<size_t>(n - done, P.max_push);
+        const bool head = first && done == 0;
+        done += seg;
+        s->twin->push_segment(static_cast<const char *>(samples) + (done - seg) * es, seg, finish && done == n, head, t.rows,
+                              t.positions, t.cap);
+    } while (done < n);
+    if (finish) s->finished = true;
+}
+
+void end_host_fed(aptgpu_stream *s, const Target &t, float *rows, uint64_t *positions, aptgpu_stream_result *result)
+{
+    if (s->host) {
+        copy_result(s->twin->state(), result);
+        fail_record(*result);
+        return;
+    }
     st::State rec{};
     apt::hip_check(hipMemcpyAsync(&rec, s->b.state, sizeof rec, hipMemcpyDeviceToHost, s->stream), "hipMemcpyAsync D2H");
     apt::hip_check(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
     s->rows_seen = rec.rows_total;
-    if (rec.n_rows > need) throw Error{ErrorKind::Internal, st::reason_text(st::kReasonOverflow)};
+    if (rec.n_rows > t.cap) throw Error{ErrorKind::Internal, st::reason_text(st::kReasonOverflow)};
     if (rec.n_rows) {
-        apt::hip_check(hipMemcpyAsync(rows, d_rows, static_cast<size_t>(rec.n_rows) * st::kPx * 4, hipMemcpyDeviceToHost, s->stream),
+        apt::hip_check(hipMemcpyAsync(rows, t.rows, static_cast<size_t>(rec.n_rows) * st::kPx * 4, hipMemcpyDeviceToHost, s->stream),
                        "hipMemcpyAsync D2H");
-        apt::hip_check(hipMemcpyAsync(positions, d_pos, static_cast<size_t>(rec.n_rows) * 8, hipMemcpyDeviceToHost, s->stream),
+        apt::hip_check(hipMemcpyAsync(positions, t.positions, static_cast<size_t>(rec.n_rows) * 8, hipMemcpyDeviceToHost, s->stream),
                        "hipMemcpyAsync D2H");
         apt::hip_check(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
     }
     copy_result(rec, result);
     fail_record(*result);
+}
+
+// host-fed: rows and positions in host memory
+void push_host_fed(aptgpu_stream *s, const void *samples, size_t n, bool finish, float *rows, uint64_t *positions, size_t rows_cap,
+                   aptgpu_stream_result *result)
+{
+    const Target t = begin_host_fed(s, n, rows, positions, rows_cap);
+    piece_of_push(s, samples, n, true, finish, t);
+    end_host_fed(s, t, rows, positions, result);
 }
 
 int create(const aptgpu_context *ctx, const aptgpu_settings *settings, const aptgpu_stream_settings *ss, bool host, aptgpu_stream **out,
@@ -235,6 +258,29 @@ int create(const aptgpu_context *ctx, const aptgpu_settings *settings, const apt
 }
 
 }  // namespace
+
+namespace apt::capi::stream_parts {
+
+bool is_host(const aptgpu_stream *s) { return s->host; }
+void check(const aptgpu_stream *s, size_t n, size_t rows_cap, const aptgpu_stream_result *result, bool want_result)
+{
+    check_call(s, n, rows_cap, result, want_result);
+}
+Target begin(aptgpu_stream *s, size_t n, float *rows, uint64_t *positions, size_t rows_cap)
+{
+    return begin_host_fed(s, n, rows, positions, rows_cap);
+}
+void piece(aptgpu_stream *s, const void *samples, size_t n, bool first, bool finish, const Target &t)
+{
+    if (!s->host) apt::hip_check(hipSetDevice(s->device), "hipSetDevice");
+    piece_of_push(s, samples, n, first, finish, t);
+}
+void end(aptgpu_stream *s, const Target &t, float *rows, uint64_t *positions, aptgpu_stream_result *result)
+{
+    end_host_fed(s, t, rows, positions, result);
+}
+
+}  // namespace apt::capi::stream_parts
 
 extern "C" {
 

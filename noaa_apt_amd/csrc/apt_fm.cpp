@@ -5,6 +5,8 @@
 
 #include <cstdio>
 
+#include "apt_kernels_fm_stream.hpp"
+
 namespace apt::fm {
 
 namespace {
@@ -12,8 +14,9 @@ namespace {
 
 bool positive(float v) { return std::isfinite(v) && v > 0.f; }
 
+// frame 0 of iq is absolute frame `base`: the phase and the runs of 8 are the absolute axis's
 template <int FMT>
-void run(const Design &d, const uint8_t *iq, size_t n_frames, float *audio)
+void run(const Design &d, uint64_t base, const uint8_t *iq, size_t n_frames, float *audio)
 {
     const size_t n_out = out_len(d, n_frames);
     if (!n_out) return;
@@ -22,21 +25,21 @@ void run(const Design &d, const uint8_t *iq, size_t n_frames, float *audio)
     std::vector<Cx> u(used);
     const int a = d.swap ? 1 : 0;
     const size_t cb = component_bytes(FMT);
-    for (size_t i0 = 0; i0 < used; i0 += kRun) {
+    const uint64_t end = base + used;
+    for (uint64_t i0 = base - base % kRun; i0 < end; i0 += kRun) {
         Cx ph = d.pw ? phasor_of_phase(static_cast<uint32_t>(i0) * d.pw) : Cx{1.f, 0.f};
-        for (size_t i = i0; i < i0 + kRun && i < used; ++i) {
-            uint32_t raw[2];
-            for (int k = 0; k < 2; ++k) {
-                raw[k] = 0;
-                std::memcpy(&raw[k], iq + (2 * i + static_cast<size_t>(k)) * cb, cb);  // little endian
+        for (uint64_t j = i0; j < i0 + kRun && j < end; ++j) {
+            if (j >= base) {
+                const size_t i = static_cast<size_t>(j - base);
+                uint32_t raw[2];
+                for (int k = 0; k < 2; ++k) {
+                    raw[k] = 0;
+                    std::memcpy(&raw[k], iq + (2 * i + static_cast<size_t>(k)) * cb, cb);  // little endian
+                }
+                const Cx x{component<FMT>(raw[a]), component<FMT>(raw[1 - a])};
+                u[i] = d.pw ? cmul(x, ph) : x;
             }
-            const Cx x{component<FMT>(raw[a]), component<FMT>(raw[1 - a])};
-            if (d.pw) {
-                u[i] = cmul(x, ph);
-                ph = cmul(ph, d.step);
-            } else {
-                u[i] = x;
-            }
+            if (d.pw) ph = cmul(ph, d.step);
         }
     }
     Cx prev{};
@@ -97,15 +100,17 @@ Design design_of(const aptgpu_fm_settings *s)
     return d;
 }
 
-void run_host(const Design &d, const void *iq, size_t n_frames, float *audio)
+void run_host_based(const Design &d, uint64_t base, const void *iq, size_t n_frames, float *audio)
 {
     const uint8_t *p = static_cast<const uint8_t *>(iq);
     switch (d.format) {
-    case APTGPU_IQ_U8: return run<APTGPU_IQ_U8>(d, p, n_frames, audio);
-    case APTGPU_IQ_S8: return run<APTGPU_IQ_S8>(d, p, n_frames, audio);
-    case APTGPU_IQ_S16: return run<APTGPU_IQ_S16>(d, p, n_frames, audio);
-    default: return run<APTGPU_IQ_F32>(d, p, n_frames, audio);
+    case APTGPU_IQ_U8: return run<APTGPU_IQ_U8>(d, base, p, n_frames, audio);
+    case APTGPU_IQ_S8: return run<APTGPU_IQ_S8>(d, base, p, n_frames, audio);
+    case APTGPU_IQ_S16: return run<APTGPU_IQ_S16>(d, base, p, n_frames, audio);
+    default: return run<APTGPU_IQ_F32>(d, base, p, n_frames, audio);
     }
 }
+
+void run_host(const Design &d, const void *iq, size_t n_frames, float *audio) { run_host_based(d, 0, iq, n_frames, audio); }
 
 }  // namespace apt::fm

@@ -40,7 +40,17 @@ struct Cx {
     float re, im;
 };
 
-APT_FM_HD Cx cmul(Cx a, Cx b) { return Cx{a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
+// On the device the object is built with -ffp-contract=fast, under which `a b - c d` may be fused around either
+// product, and which one the compiler takes has changed with the code around it.  The fused forms are therefore
+// written out: the ones k_fm has always had (one rounding of a.re's product, the other product rounded first).
+APT_FM_HD Cx cmul(Cx a, Cx b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return Cx{__fmaf_rn(a.re, b.re, -(a.im * b.im)), __fmaf_rn(a.re, b.im, a.im * b.re)};
+#else
+    return Cx{a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re};
+#endif
+}
 
 // bytes of one component
 APT_FM_HD uint32_t component_bytes(int format)
@@ -93,8 +103,13 @@ APT_FM_HD float discriminate(Cx v0, Cx v1, float gain)
         return std::nanf("");
 #endif
     }
+#if defined(__HIP_DEVICE_COMPILE__)  // (fused as cmul is, for the same reason)
+    const float re = __fmaf_rn(v1.re, v0.re, v1.im * v0.im);
+    const float im = __fmaf_rn(v1.im, v0.re, -(v1.re * v0.im));
+#else
     const float re = v1.re * v0.re + v1.im * v0.im;
     const float im = v1.im * v0.re - v1.re * v0.im;
+#endif
     if (re == 0.f && im == 0.f) return 0.f;
     return gain * atan2f(im, re);
 }
