@@ -4,7 +4,7 @@
  *     aptgpu_decode in.wav out.pgm [contrast: telemetry|percent|minmax] [--no-sync]
  *                   [--histogram | --histogram-float] [--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE] [--png]
  *                   [--tle FILE --sat NAME (--start-ms N | --end-ms N)] [--rotate no|yes|orbit]
- *                   [--project equirect|mercator[:step_deg] [--grid DEG]] [--despeckle R[:T]] [--track=[W,LAMBDA]]
+ *                   [--project equirect|mercator[:step_deg] [--grid DEG]] [--despeckle R[:T]] [--track=[W,LAMBDA[,LAG]]]
  *                   [--live SECONDS] [--iq FMT:FS:D[:SHIFT_HZ]]
  *
  * What `noaa-apt in.wav -o out.png` does (main.rs:91-110, noaa_apt.rs:114-235): load -> decode ->
@@ -30,6 +30,9 @@
  * the rows come from aptgpu_decode_tracked, the flywheel sync stage in place of find_sync — row starts tracked through
  * noise and dropouts, W work samples of jitter per row at LAMBDA per sample; it also decodes what the plain decode
  * refuses as "less than 5 sync frames".
+ * --live SECONDS --track=W,LAMBDA[,LAG] together: a live-decode stream whose rows the flywheel tracker finds, committed LAG
+ * rows (default 8) behind the best survivor (aptgpu_stream_create_tracked; with --iq: aptgpu_iq_live_create_tracked).  LAG
+ * without --live, and --iq with --track= without --live, are refused.
  * --live SECONDS: the recording goes through a live-decode stream (aptgpu_stream_*) in chunks of SECONDS, as a ground
  * station would feed it during the pass; every push hands back the rows that are final, and their concatenation — the
  * image written — is the same PGM as without the flag.
@@ -57,7 +60,7 @@ int main(int argc, char **argv)
         fprintf(stderr, "usage: %s in.wav out.pgm [telemetry|percent|minmax] [--no-sync] [--histogram | --histogram-float] "
                 "[--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE] [--png]\n"
                 "       [--tle FILE --sat NAME (--start-ms N | --end-ms N)] [--rotate no|yes|orbit]\n"
-                "       [--project equirect|mercator[:step_deg] [--grid DEG]] [--despeckle R[:T]] [--track=[W,LAMBDA]]\n"
+                "       [--project equirect|mercator[:step_deg] [--grid DEG]] [--despeckle R[:T]] [--track=[W,LAMBDA[,LAG]]]\n"
                 "       [--live SECONDS] [--iq u8|s8|s16|f32:FS:D[:SHIFT_HZ]]\n", argv[0]);
         return 2;
     }
@@ -142,6 +145,23 @@ int main(int argc, char **argv)
     aptgpu_stats stats;
     uint32_t rate = 0;
     int rc;
+    /* --track=W,LAMBDA[,LAG]: read once; LAG belongs to the live tracker, and raw IQ is tracked as a live stream only */
+    aptgpu_live_track_settings lt = {sizeof(aptgpu_live_track_settings), 8, 8, 0.1f};
+    if (flywheel) {
+        const int fields = *flywheel ? sscanf(flywheel, "%u,%f,%u", &lt.max_jitter, &lt.penalty, &lt.lag_rows) : 2;
+        if (fields < 2) {
+            fprintf(stderr, "--track=W,LAMBDA[,LAG]: cannot read \"%s\"\n", flywheel);
+            return 2;
+        }
+        if (fields == 3 && live_seconds <= 0.0) {
+            fprintf(stderr, "--track=W,LAMBDA,LAG: LAG is the live tracker's decision lag and needs --live SECONDS\n");
+            return 2;
+        }
+        if (iq_spec && live_seconds <= 0.0) {
+            fprintf(stderr, "--iq with --track=: raw IQ is tracked as a live stream only; add --live SECONDS\n");
+            return 2;
+        }
+    }
     if (iq_spec) {
         /* raw IQ frames: FM demodulation in front of the decode, in one piece or as a live stream */
         aptgpu_fm_settings fs;
@@ -167,7 +187,8 @@ int main(int argc, char **argv)
             ls.struct_size = sizeof ls;
             ls.sync = sync;
             aptgpu_iq_live *live = NULL;
-            rc = aptgpu_iq_live_create(&ctx, &settings, &fs, &ls, &live, err, sizeof err);
+            rc = flywheel ? aptgpu_iq_live_create_tracked(&ctx, &settings, &fs, &ls, &lt, &live, err, sizeof err)
+                          : aptgpu_iq_live_create(&ctx, &settings, &fs, &ls, &live, err, sizeof err);
             if (rc != APTGPU_OK) { fprintf(stderr, "iq live failed (%d): %s\n", rc, err); return 1; }
             size_t chunk = (size_t)(live_seconds * fs_hz);
             if (chunk == 0) chunk = 1;
@@ -190,6 +211,13 @@ int main(int argc, char **argv)
                 if (rc == APTGPU_OK) n_rows += sr.n_rows;
                 if (last) break;
             }
+            aptgpu_stream_track_result tr;
+            memset(&tr, 0, sizeof tr);
+            tr.struct_size = sizeof tr;
+            if (flywheel && rc == APTGPU_OK) rc = aptgpu_iq_live_track_results(live, &tr, err, sizeof err);
+            if (flywheel && rc == APTGPU_OK)
+                fprintf(stderr, "tracked live: %llu row starts %u rows behind the best survivor (jitter %u, penalty %g), %u relocks\n",
+                        (unsigned long long)tr.n_positions, lt.lag_rows, lt.max_jitter, lt.penalty, tr.n_relocks);
             aptgpu_iq_live_destroy(live);
             free(bytes);
             if (rc != APTGPU_OK) { fprintf(stderr, "live decode failed (%d): %s\n", rc, err); return 1; }
@@ -209,13 +237,9 @@ int main(int argc, char **argv)
             fprintf(stderr, "%u Hz audio from %u Hz IQ, %llu sync frames, %llu rows\n", rate, fs_hz,
                     (unsigned long long)stats.n_sync, (unsigned long long)(n_rows_px / 2080));
         }
-    } else if (flywheel) {
+    } else if (flywheel && live_seconds <= 0.0) {
         /* load -> front end -> flywheel sync: the rows of the tracked path, with each row's lock indicator */
-        aptgpu_track_settings ts = {sizeof(aptgpu_track_settings), 8, 0.1f, 0};
-        if (*flywheel && sscanf(flywheel, "%u,%f", &ts.max_jitter, &ts.penalty) != 2) {
-            fprintf(stderr, "--track=W,LAMBDA: cannot read \"%s\"\n", flywheel);
-            return 2;
-        }
+        aptgpu_track_settings ts = {sizeof(aptgpu_track_settings), lt.max_jitter, lt.penalty, 0};
         float *signal = NULL, *scores = NULL;
         size_t n_signal = 0;
         aptgpu_wav_spec spec;
@@ -250,7 +274,9 @@ int main(int argc, char **argv)
         ss.sync = sync;
         ss.format = APTGPU_STREAM_F32;
         aptgpu_stream *stream = NULL;
-        rc = aptgpu_stream_create(&ctx, &settings, &ss, &stream, err, sizeof err);
+        /* with --track=W,LAMBDA[,LAG]: the same stream with the flywheel tracker in the picker's place */
+        rc = flywheel ? aptgpu_stream_create_tracked(&ctx, &settings, &ss, &lt, &stream, err, sizeof err)
+                      : aptgpu_stream_create(&ctx, &settings, &ss, &stream, err, sizeof err);
         if (rc != APTGPU_OK) { fprintf(stderr, "stream failed (%d): %s\n", rc, err); return 1; }
         size_t chunk = (size_t)(live_seconds * rate);
         if (chunk == 0) chunk = 1;
@@ -272,11 +298,18 @@ int main(int argc, char **argv)
             if (rc == APTGPU_OK) n_rows += sr.n_rows;
             if (last) break;
         }
+        aptgpu_stream_track_result tr;
+        memset(&tr, 0, sizeof tr);
+        tr.struct_size = sizeof tr;
+        if (flywheel && rc == APTGPU_OK) rc = aptgpu_stream_track_results(stream, &tr, err, sizeof err);
         aptgpu_stream_destroy(stream);
         aptgpu_free(signal);
         if (rc != APTGPU_OK) { fprintf(stderr, "live decode failed (%d): %s\n", rc, err); return 1; }
         n_rows_px = n_rows * 2080;
         memset(&stats, 0, sizeof stats);
+        if (flywheel)
+            fprintf(stderr, "tracked live: %llu row starts %u rows behind the best survivor (jitter %u, penalty %g), %u relocks\n",
+                    (unsigned long long)tr.n_positions, lt.lag_rows, lt.max_jitter, lt.penalty, tr.n_relocks);
         fprintf(stderr, "%u Hz, %llu sync frames, %llu rows from %llu pushes of %g s\n", rate, (unsigned long long)sr.n_sync,
                 (unsigned long long)n_rows, (unsigned long long)pushes, live_seconds);
     } else {

@@ -1256,6 +1256,81 @@ int aptgpu_stream_finish_device(aptgpu_stream *stream, float *d_rows, uint64_t *
 int aptgpu_stream_results(aptgpu_stream *stream, aptgpu_stream_result *result, char *err, size_t err_cap);
 
 /* ====================================================================== */
+/* 4e. live flywheel sync: tracked row starts for the live decoder */
+/* ====================================================================== */
+/* A tracked stream finds its rows with §4c's tracker in place of the reference's picker.  Opt-in: a stream that is not
+ * created through the entry points below is §4d's, unchanged.  tests/np_live_track_model.py states the definition in
+ * numpy.
+ *
+ * §22's finality ("the same for every continuation") does not exist for the tracker: the survivors of the dynamic
+ * programme merge only after hundreds of rows.  A tracked stream therefore commits with a fixed decision lag.
+ * Notation is §4c's: L = 2080 pw, G = 38 pw, w, lambda; s, best and bp are §4c's values of the whole recording bit for
+ * bit.  They are causal: s[i], best[i] and bp[i] are final once i + G <= work_len (§4d's count of final F).
+ * m = work_len - G, or 0 when work_len < G; K = lag_rows.
+ *  1. Checkpoints are absolute.  Checkpoint e = 1, 2, ... is processed as soon as m >= e L, in order, however many a
+ *     push crosses; nothing about the tracker happens between checkpoints.  Positions, scores, rows and the release
+ *     schedule are functions of the samples and of which push first makes m >= e L.
+ *  2. Commit behind the best survivor.  At checkpoint e let n = e L.  `end` is the first maximum of best over
+ *     [n - L, n); the survivor is the chain from `end` through bp to a START node.  Committed, ascending, is every node
+ *     v of it with  v + (K + 1) L <= n  and  v >= c + L - w,  c being the last committed position (the second
+ *     condition is void before the first commit).
+ *  3. Relock.  If a checkpoint commits at least one node and c is not a node of its survivor, n_relocks increases by
+ *     one.  Steps between committed positions are in [L - w, L + w] except across a relock, where they are >= L - w.
+ *  4. A committed position is released in the push that committed it: row[c] = F[v + pw c], c < 2080 (the sample's own
+ *     bits, §4c's rule, not §4d's final filter pass), its lock indicator s[v].  v + L <= n - K L <= work_len: the row
+ *     exists.
+ *  5. finish() flushes the tail as §4d does (work_len is then the one-shot's n, M = n - G), processes the checkpoints
+ *     with e L <= M, takes `end` as the first maximum of best over [max(0, M - L), M) and commits every node of its
+ *     survivor under the second condition alone.  Those with v + L <= n are released; a last position without a full row
+ *     counts in n_positions only.  n < L + G: "track: the signal is shorter than one row and one sync frame"
+ *     (APTGPU_ERR_INTERNAL), nothing released.
+ *  6. When lag_rows is at least the number of checkpoints of the recording nothing is released before finish(), and
+ *     finish() releases exactly aptgpu_track_sync of the whole F: positions, scores and rows bit for bit.
+ * The stream's record then reports n_sync = positions committed so far and scan_pos = m.  State on the device, all of
+ * fixed size: §4d's record and input ring, an F ring and a score ring that reach back to the oldest position still
+ * committable, 2 L sums, one back-pointer byte per position over the deepest back-track, the tracker's record. */
+#define APTGPU_LIVE_TRACK_MAX_LAG 64
+typedef struct aptgpu_live_track_settings {
+    uint32_t struct_size; /* sizeof(aptgpu_live_track_settings) */
+    uint32_t lag_rows;    /* K: 0..64 rows a position is held back (0 = greedy); default 8, four seconds */
+    uint32_t max_jitter;  /* aptgpu_track_settings' w */
+    float penalty;        /* ... and lambda */
+} aptgpu_live_track_settings;
+typedef struct aptgpu_stream_track_result {
+    uint32_t struct_size;     /* set by the caller */
+    uint32_t n_relocks;
+    uint64_t n_positions;     /* committed so far */
+    uint64_t m;               /* positions whose score and sums are final */
+    uint64_t next_checkpoint; /* e of the next checkpoint */
+    uint64_t last_position;   /* c; meaningful when has_position */
+    int32_t has_position;
+    uint32_t reserved;
+    uint32_t cap_best;        /* capacities of the sums' ring (floats) and of the back-pointers' (bytes), powers of two; */
+    uint32_t cap_bp;          /* the score ring has aptgpu_stream_info.cap_f entries */
+} aptgpu_stream_track_result;
+/* §4d's aptgpu_stream_create / _create_host with a tracker: stream_settings->sync is ignored.  track nullable (= lag 8,
+ * w 8, lambda 0.1).  Refused besides what §4d refuses, before a device is touched: a struct_size not set, lag_rows > 64
+ * and what §4c refuses of w, lambda and the work rate (APTGPU_ERR_INVALID).  The handle is accepted by every
+ * aptgpu_stream_* entry point of §4d; aptgpu_stream_rows_bound follows from rule 2 (three rows per checkpoint the call
+ * can reach, and the nodes a finish can commit). */
+int aptgpu_stream_create_tracked(const aptgpu_context *ctx, const aptgpu_settings *settings,
+                                 const aptgpu_stream_settings *stream_settings, const aptgpu_live_track_settings *track,
+                                 aptgpu_stream **out, char *err, size_t err_cap);
+int aptgpu_stream_create_tracked_host(const aptgpu_context *ctx, const aptgpu_settings *settings,
+                                      const aptgpu_stream_settings *stream_settings,
+                                      const aptgpu_live_track_settings *track, aptgpu_stream **out, char *err,
+                                      size_t err_cap);
+/* The lock indicators of the rows the last host-fed push or finish released: min(cap, n_rows) floats, n_rows in *n.
+ * APTGPU_ERR_INVALID for a stream that is not tracked. */
+int aptgpu_stream_track_scores(aptgpu_stream *stream, float *scores, size_t cap, size_t *n, char *err, size_t err_cap);
+/* Device-resident form: where the *_device calls that follow write the lock indicators of their rows (rows_cap floats of
+ * device memory, row for row beside d_rows).  NULL (the state after creation and after reset): the stream keeps them to
+ * itself. */
+int aptgpu_stream_track_scores_device(aptgpu_stream *stream, float *d_scores, char *err, size_t err_cap);
+/* Waits like aptgpu_stream_results and returns the tracker's record. */
+int aptgpu_stream_track_results(aptgpu_stream *stream, aptgpu_stream_track_result *result, char *err, size_t err_cap);
+
+/* ====================================================================== */
 /* 4b'. FM demodulation in streaming form, and live decode from IQ */
 /* ====================================================================== */
 /* An SDR delivers IQ frames, not audio.  An FM stream takes them in pushes of any size and returns the outputs of §4b
@@ -1353,6 +1428,24 @@ int aptgpu_iq_live_push_device(aptgpu_iq_live *s, const void *d_iq, size_t n_fra
 int aptgpu_iq_live_finish_device(aptgpu_iq_live *s, float *d_rows, uint64_t *d_positions, size_t rows_cap, char *err,
                                  size_t err_cap);
 int aptgpu_iq_live_results(aptgpu_iq_live *s, aptgpu_stream_result *result, char *err, size_t err_cap);
+/* Live decode from IQ with §4e's tracker: aptgpu_iq_live_create / _host whose decode stream is a tracked one
+ * (live_settings->sync is ignored; track nullable = the defaults; §4e's refusals besides §4b''s and §4d's, all before a
+ * device is touched).  The FM stream runs in front on the same HIP stream and the audio never leaves the device.  Every
+ * aptgpu_iq_live_* entry point accepts the handle; rows, positions, lock indicators and records are those of a tracked
+ * stream fed aptgpu_fm_demodulate's audio of the same pushes.  The three calls below are §4e's aptgpu_stream_track_* on
+ * the coupling's decode stream; APTGPU_ERR_INVALID for a coupling that is not tracked. */
+int aptgpu_iq_live_create_tracked(const aptgpu_context *ctx, const aptgpu_settings *decode_settings,
+                                  const aptgpu_fm_settings *fm_settings, const aptgpu_iq_live_settings *live_settings,
+                                  const aptgpu_live_track_settings *track, aptgpu_iq_live **out, char *err,
+                                  size_t err_cap);
+int aptgpu_iq_live_create_tracked_host(const aptgpu_context *ctx, const aptgpu_settings *decode_settings,
+                                       const aptgpu_fm_settings *fm_settings,
+                                       const aptgpu_iq_live_settings *live_settings,
+                                       const aptgpu_live_track_settings *track, aptgpu_iq_live **out, char *err,
+                                       size_t err_cap);
+int aptgpu_iq_live_track_scores(aptgpu_iq_live *s, float *scores, size_t cap, size_t *n, char *err, size_t err_cap);
+int aptgpu_iq_live_track_scores_device(aptgpu_iq_live *s, float *d_scores, char *err, size_t err_cap);
+int aptgpu_iq_live_track_results(aptgpu_iq_live *s, aptgpu_stream_track_result *result, char *err, size_t err_cap);
 
 /* ====================================================================== */
 /* 5. WAV ingest in front of decode()                 */

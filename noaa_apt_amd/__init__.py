@@ -40,6 +40,8 @@ Names, argument meaning and error behaviour follow the reference:
     FmDemodulator                                          DESIGN.md §20
     track_sync, track_sync_host, sync_score,               the reference's to-do list, docs/development.md:148: row
     decode_tracked, TrackSettings, Plan.track_device       starts tracked through noise and dropouts, DESIGN.md §21
+    LiveTrackSettings, LiveDecoder(track=...),             live decode with the flywheel tracker's row starts, from audio
+    LiveIqDecoder(track=...)                               and from IQ frames, DESIGN.md §24
     LiveDecoder, decode_live                               the reference's to-do list, docs/development.md:151: audio
                                                            pushed in chunks, finished rows handed back, DESIGN.md §22
     FmStream, LiveIqDecoder, decode_live_iq                the same from IQ frames: the FM demodulator in streaming form
@@ -67,7 +69,7 @@ from .api import (  # noqa: F401
     IqFormat, FmSettings, FmInfo, FmDemodulator, fm_demodulate, fm_demodulate_host, fm_demodulate_wav, fm_design, load_iq,
     FM_SWAP_IQ, FM_MAX_BATCH,
     TrackSettings, TrackResult, track_sync, track_sync_host, sync_score, decode_tracked, TRACK_MAX_JITTER,
-    LiveDecoder, decode_live, StreamInfo, StreamResult,
+    LiveDecoder, decode_live, StreamInfo, StreamResult, LiveTrackSettings, StreamTrackResult,
     FmStream, FmStreamInfo, LiveIqDecoder, decode_live_iq, FM_STREAM_MAX_PUSH_FRAMES,
     Projection, ProjectionSettings, projection_fit, project_image, PROJECT_REASON_CAPACITY,
     Composite, composite_images, COMPOSITE_REASON_PASS, COMPOSITE_MAX_PASSES,

@@ -208,6 +208,18 @@ class StreamResult(C.Structure):
                 ("scan_pos", C.c_uint64)]
 
 
+class _CLiveTrackSettings(C.Structure):
+    """aptgpu_live_track_settings"""
+    _fields_ = [("struct_size", C.c_uint32), ("lag_rows", C.c_uint32), ("max_jitter", C.c_uint32), ("penalty", C.c_float)]
+
+
+class StreamTrackResult(C.Structure):
+    """aptgpu_stream_track_result: the live tracker's record."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_relocks", C.c_uint32), ("n_positions", C.c_uint64), ("m", C.c_uint64),
+                ("next_checkpoint", C.c_uint64), ("last_position", C.c_uint64), ("has_position", C.c_int32),
+                ("reserved", C.c_uint32), ("cap_best", C.c_uint32), ("cap_bp", C.c_uint32)]
+
+
 class _CThermalCoeffs(C.Structure):
     """aptgpu_thermal_coeffs"""
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("prt", (C.c_double * 3) * 4),
@@ -530,6 +542,12 @@ def lib():
     L.aptgpu_stream_push_device.argtypes = [vp, vp, sz, vp, vp, sz, C.c_char_p, sz]
     L.aptgpu_stream_finish_device.argtypes = [vp, vp, vp, sz, C.c_char_p, sz]
     L.aptgpu_stream_results.argtypes = [vp, csr, C.c_char_p, sz]
+    for name in ("aptgpu_stream_create_tracked", "aptgpu_stream_create_tracked_host"):
+        getattr(L, name).argtypes = [cp, C.POINTER(_CSettings), css, C.POINTER(_CLiveTrackSettings), C.POINTER(vp),
+                                     C.c_char_p, sz]
+    L.aptgpu_stream_track_scores.argtypes = [vp, _f32p, sz, C.POINTER(sz), C.c_char_p, sz]
+    L.aptgpu_stream_track_scores_device.argtypes = [vp, vp, C.c_char_p, sz]
+    L.aptgpu_stream_track_results.argtypes = [vp, C.POINTER(StreamTrackResult), C.c_char_p, sz]
     cfss = C.POINTER(_CFmStreamSettings)
     L.aptgpu_fm_stream_create.argtypes = [cp, cfm, cfss, C.POINTER(vp), C.c_char_p, sz]
     L.aptgpu_fm_stream_create_host.argtypes = [cfm, cfss, C.POINTER(vp), C.c_char_p, sz]
@@ -555,6 +573,12 @@ def lib():
     L.aptgpu_iq_live_push_device.argtypes = [vp, vp, sz, vp, vp, sz, C.c_char_p, sz]
     L.aptgpu_iq_live_finish_device.argtypes = [vp, vp, vp, sz, C.c_char_p, sz]
     L.aptgpu_iq_live_results.argtypes = [vp, csr, C.c_char_p, sz]
+    for name in ("aptgpu_iq_live_create_tracked", "aptgpu_iq_live_create_tracked_host"):
+        getattr(L, name).argtypes = [cp, C.POINTER(_CSettings), cfm, C.POINTER(_CIqLiveSettings),
+                                     C.POINTER(_CLiveTrackSettings), C.POINTER(vp), C.c_char_p, sz]
+    L.aptgpu_iq_live_track_scores.argtypes = [vp, _f32p, sz, C.POINTER(sz), C.c_char_p, sz]
+    L.aptgpu_iq_live_track_scores_device.argtypes = [vp, vp, C.c_char_p, sz]
+    L.aptgpu_iq_live_track_results.argtypes = [vp, C.POINTER(StreamTrackResult), C.c_char_p, sz]
     _lib = L
     return L
 
@@ -1690,15 +1714,43 @@ def decode_tracked(context: Optional["Context"], settings: "Settings", signal, i
     return (rows, p, q, info) if return_info else rows
 
 
+class LiveTrackSettings:
+    """aptgpu_live_track_settings: live flywheel sync.  lag_rows (0..64): how many rows behind the best
+    survivor a row start is committed — 8 is four seconds behind real time, 0 is greedy; max_jitter and penalty are
+    TrackSettings'."""
+
+    def __init__(self, lag_rows=8, max_jitter=8, penalty=0.1):
+        self.lag_rows, self.max_jitter, self.penalty = lag_rows, max_jitter, penalty
+
+    def _c(self, struct_size=None):
+        return _CLiveTrackSettings(C.sizeof(_CLiveTrackSettings) if struct_size is None else int(struct_size),
+                                   int(self.lag_rows), int(self.max_jitter), float(self.penalty))
+
+
+def _live_track_c(settings):
+    if isinstance(settings, _CLiveTrackSettings):  # (tests: a struct_size of their own)
+        return settings
+    if not isinstance(settings, LiveTrackSettings):
+        raise InvalidError("stream: track must be a LiveTrackSettings")
+    try:
+        return settings._c()
+    except (TypeError, ValueError, OverflowError) as e:
+        raise InvalidError(f"stream: {e}") from None
+
+
 class LiveDecoder:
     """aptgpu_stream: live decode.  Push the recording in chunks of any size; every push returns the
     image rows that are final — bit-identical to what strict decode() of the complete recording holds at that place,
     whatever is pushed later — and their work-rate positions.  finish() releases the rest and raises what decode()
     would raise ("less than 10 rows", "less than 5 sync frames"); rows handed out before stay handed out.  dtype:
     np.float32 or np.int16 (mono PCM16, the value as f32).  host=True: the plain C++ twin on the CPU (same bits, no GPU).
-    `result` is the record of the last call, `info` the stream's geometry and ring capacities."""
+    `result` is the record of the last call, `info` the stream's geometry and ring capacities.
+    track: a LiveTrackSettings finds the rows with the flywheel tracker in place of the reference's picker (DESIGN.md
+    §24; `sync` is then not read): rows are the filtered samples' own bits, committed lag_rows behind real time;
+    `scores` holds the lock indicators of the last call's rows and `track_result` the tracker's record."""
 
-    def __init__(self, settings, input_rate, sync=True, context=None, dtype=np.float32, max_push=None, host=False):
+    def __init__(self, settings, input_rate, sync=True, context=None, dtype=np.float32, max_push=None, host=False,
+                 track=None):
         self._dtype = np.dtype(dtype)
         fmt = {np.dtype(np.float32): 0, np.dtype(np.int16): 1}.get(self._dtype)
         if fmt is None:
@@ -1709,8 +1761,16 @@ class LiveDecoder:
         self._p = C.c_void_p()
         self.host = bool(host)
         err = C.create_string_buffer(_ERRCAP)
-        fn = lib().aptgpu_stream_create_host if host else lib().aptgpu_stream_create
-        _check(fn(C.byref(cctx), C.byref(cs), C.byref(css), C.byref(self._p), err, _ERRCAP), err)
+        self.tracked = track is not None
+        self.scores, self.track_result = None, None
+        if self.tracked:
+            ct = _live_track_c(track)
+            fn = lib().aptgpu_stream_create_tracked_host if host else lib().aptgpu_stream_create_tracked
+            _check(fn(C.byref(cctx), C.byref(cs), C.byref(css), C.byref(ct), C.byref(self._p), err, _ERRCAP), err)
+            self.scores = np.zeros(0, np.float32)
+        else:
+            fn = lib().aptgpu_stream_create_host if host else lib().aptgpu_stream_create
+            _check(fn(C.byref(cctx), C.byref(cs), C.byref(css), C.byref(self._p), err, _ERRCAP), err)
         self.info = StreamInfo(struct_size=C.sizeof(StreamInfo))
         _check(lib().aptgpu_stream_get_info(self._p, C.byref(self.info)))
         self.result = StreamResult(struct_size=C.sizeof(StreamResult))
@@ -1764,9 +1824,32 @@ class LiveDecoder:
                                           _ERRCAP)
         if rc in (0, 1):  # (an end-of-signal error fills the record; a refused call leaves it alone)
             self.result = res
+            if self.tracked:
+                self._read_track(0 if rc else int(res.n_rows))
         _check(rc, err)
         k = int(res.n_rows)
         return rows[:k].copy(), pos[:k].copy()
+
+    def _read_track(self, k):
+        sc, n = np.zeros(max(k, 1), np.float32), C.c_size_t(0)
+        err = C.create_string_buffer(_ERRCAP)
+        _check(lib().aptgpu_stream_track_scores(self._p, sc.ctypes.data_as(_f32p), k, C.byref(n), err, _ERRCAP), err)
+        self.scores = sc[:min(k, int(n.value))].copy()
+        self.track_results()
+
+    def track_results(self):
+        """Waits like results() and returns the tracker's record (a tracked stream only)."""
+        res = StreamTrackResult(struct_size=C.sizeof(StreamTrackResult))
+        err = C.create_string_buffer(_ERRCAP)
+        _check(lib().aptgpu_stream_track_results(self._p, C.byref(res), err, _ERRCAP), err)
+        self.track_result = res
+        return res
+
+    def scores_device(self, d_scores):
+        """Where the device-resident calls that follow write the lock indicators of their rows (a device pointer to
+        rows_cap floats; None: the stream keeps them)."""
+        err = C.create_string_buffer(_ERRCAP)
+        _check(lib().aptgpu_stream_track_scores_device(self._p, d_scores, err, _ERRCAP), err)
 
     def push(self, chunk, rows_cap=None):
         """chunk: 1-D samples of the stream's dtype -> (rows [n, 2080] f32, positions [n] u64) that became final."""
@@ -1798,21 +1881,32 @@ class LiveDecoder:
 
 
 def decode_live(context: Optional["Context"], settings: "Settings", chunks, input_rate: "Rate", sync: bool, host=False,
-                max_push=None):
+                max_push=None, track=None, return_info=False):
     """decode() over an iterable of chunks through a LiveDecoder: returns what decode() returns for their
     concatenation (flat f32, rows * 2080) and raises what it raises.  The chunks' dtype (float32 or int16) is the
-    first chunk's."""
+    first chunk's.  track: a LiveTrackSettings; return_info then gives (rows, positions, scores,
+    StreamTrackResult)."""
     it = iter(chunks)
     first = next(it, None)
     dtype = np.int16 if first is not None and np.asarray(first).dtype == np.int16 else np.float32
-    out = []
-    with LiveDecoder(settings, input_rate, sync, context, dtype, max_push, host) as dec:
+    out, pos, sc = [], [], []
+    with LiveDecoder(settings, input_rate, sync, context, dtype, max_push, host, track) as dec:
+        def take(call):
+            out.append(call[0])
+            pos.append(call[1])
+            if dec.tracked:
+                sc.append(dec.scores)
+
         if first is not None:
-            out.append(dec.push(first)[0])
+            take(dec.push(first))
         for chunk in it:
-            out.append(dec.push(chunk)[0])
-        out.append(dec.finish()[0])
-    return np.concatenate(out).reshape(-1) if out else np.zeros(0, np.float32)
+            take(dec.push(chunk))
+        take(dec.finish())
+        info = dec.track_result
+    rows = np.concatenate(out).reshape(-1) if out else np.zeros(0, np.float32)
+    if return_info and track is not None:
+        return rows, np.concatenate(pos), np.concatenate(sc), info
+    return rows
 
 
 THERMAL_COLD_WHITE = 1
@@ -2211,10 +2305,12 @@ class LiveIqDecoder:
     """aptgpu_iq_live: live decode from IQ frames: an FmStream in front of a LiveDecoder on one HIP
     stream, the audio staying on the device.  The surface is LiveDecoder's, with frames for samples: push() returns
     the rows that became final and their positions, finish() the rest or decode()'s error.  `fm_info` and `info` are
-    the two stages' infos, `result` the record of the last call."""
+    the two stages' infos, `result` the record of the last call.  track: a LiveTrackSettings, as for LiveDecoder
+    (DESIGN.md §24): `scores` and `track_result` then hold the lock indicators of the last call's rows and the
+    tracker's record."""
 
     def __init__(self, settings, fm_settings, sync=True, context=None, max_push_frames=None, max_push=None, first_frame=0,
-                 host=False):
+                 host=False, track=None):
         cfm = _fm_settings_c(fm_settings)
         self._cfm = cfm
         self._ctx = context or Context()
@@ -2224,8 +2320,16 @@ class LiveIqDecoder:
         self._p = C.c_void_p()
         self.host = bool(host)
         err = C.create_string_buffer(_ERRCAP)
-        fn = lib().aptgpu_iq_live_create_host if host else lib().aptgpu_iq_live_create
-        _check(fn(C.byref(cctx), C.byref(cs), C.byref(cfm), C.byref(cls), C.byref(self._p), err, _ERRCAP), err)
+        self.tracked = track is not None
+        self.scores, self.track_result = None, None
+        if self.tracked:
+            ct = _live_track_c(track)
+            fn = lib().aptgpu_iq_live_create_tracked_host if host else lib().aptgpu_iq_live_create_tracked
+            _check(fn(C.byref(cctx), C.byref(cs), C.byref(cfm), C.byref(cls), C.byref(ct), C.byref(self._p), err, _ERRCAP), err)
+            self.scores = np.zeros(0, np.float32)
+        else:
+            fn = lib().aptgpu_iq_live_create_host if host else lib().aptgpu_iq_live_create
+            _check(fn(C.byref(cctx), C.byref(cs), C.byref(cfm), C.byref(cls), C.byref(self._p), err, _ERRCAP), err)
         self.fm_info, self.info = self.get_info()
         self.result = StreamResult(struct_size=C.sizeof(StreamResult))
 
@@ -2277,9 +2381,32 @@ class LiveIqDecoder:
                                            C.byref(res), err, _ERRCAP)
         if rc in (0, 1):  # (an end-of-signal error fills the record; a refused call leaves it alone)
             self.result = res
+            if self.tracked:
+                self._read_track(0 if rc else int(res.n_rows))
         _check(rc, err)
         k = int(res.n_rows)
         return rows[:k].copy(), pos[:k].copy()
+
+    def _read_track(self, k):
+        sc, n = np.zeros(max(k, 1), np.float32), C.c_size_t(0)
+        err = C.create_string_buffer(_ERRCAP)
+        _check(lib().aptgpu_iq_live_track_scores(self._p, sc.ctypes.data_as(_f32p), k, C.byref(n), err, _ERRCAP), err)
+        self.scores = sc[:min(k, int(n.value))].copy()
+        self.track_results()
+
+    def track_results(self):
+        """Waits like results() and returns the tracker's record (a tracked coupling only)."""
+        res = StreamTrackResult(struct_size=C.sizeof(StreamTrackResult))
+        err = C.create_string_buffer(_ERRCAP)
+        _check(lib().aptgpu_iq_live_track_results(self._p, C.byref(res), err, _ERRCAP), err)
+        self.track_result = res
+        return res
+
+    def scores_device(self, d_scores):
+        """Where the device-resident calls that follow write the lock indicators of their rows (a device pointer to
+        rows_cap floats; None: the stream keeps them)."""
+        err = C.create_string_buffer(_ERRCAP)
+        _check(lib().aptgpu_iq_live_track_scores_device(self._p, d_scores, err, _ERRCAP), err)
 
     def push(self, iq, rows_cap=None):
         """iq: interleaved components of the format's dtype -> (rows [n, 2080] f32, positions [n] u64) that became
@@ -2313,15 +2440,26 @@ class LiveIqDecoder:
 
 
 def decode_live_iq(context: Optional["Context"], settings: "Settings", fm_settings: "FmSettings", chunks, sync: bool,
-                   host=False, max_push_frames=None):
+                   host=False, max_push_frames=None, track=None, return_info=False):
     """decode(fm_demodulate(...)) over an iterable of IQ chunks through a LiveIqDecoder: returns the rows of the
-    chunks' concatenation (flat f32, rows * 2080) and raises what decode() raises."""
-    out = []
-    with LiveIqDecoder(settings, fm_settings, sync, context, max_push_frames, host=host) as dec:
+    chunks' concatenation (flat f32, rows * 2080) and raises what decode() raises.  track: a LiveTrackSettings
+    (DESIGN.md §24); return_info then gives (rows, positions, scores, StreamTrackResult)."""
+    out, pos, sc = [], [], []
+    with LiveIqDecoder(settings, fm_settings, sync, context, max_push_frames, host=host, track=track) as dec:
+        def take(call):
+            out.append(call[0])
+            pos.append(call[1])
+            if dec.tracked:
+                sc.append(dec.scores)
+
         for chunk in chunks:
-            out.append(dec.push(chunk)[0])
-        out.append(dec.finish()[0])
-    return np.concatenate(out).reshape(-1)
+            take(dec.push(chunk))
+        take(dec.finish())
+        info = dec.track_result
+    rows = np.concatenate(out).reshape(-1)
+    if return_info and track is not None:
+        return rows, np.concatenate(pos), np.concatenate(sc), info
+    return rows
 
 
 def process(context, signal, contrast_adjustment, rotate=Rotate.NO, color=None, orbit=None,

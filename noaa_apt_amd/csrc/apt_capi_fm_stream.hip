@@ -8,6 +8,7 @@
 #include "apt_capi_stream_parts.hpp"
 #include "apt_capi_util.hpp"
 #include "apt_kernels_fm_stream.hpp"
+#include "apt_kernels_stream_track.hpp"
 
 namespace fms = apt::fm;
 namespace parts = apt::capi::stream_parts;
@@ -206,7 +207,8 @@ size_t push_fm_host_fed(aptgpu_fm_stream *s, const void *iq, size_t n_frames, fl
 
 // ---- the coupling
 int create_live(const aptgpu_context *ctx, const aptgpu_settings *decode_settings, const aptgpu_fm_settings *fm_settings,
-                const aptgpu_iq_live_settings *ls, bool host, aptgpu_iq_live **out, char *err, size_t err_cap)
+                const aptgpu_iq_live_settings *ls, bool host, aptgpu_iq_live **out, char *err, size_t err_cap, bool tracked = false,
+                const aptgpu_live_track_settings *track = nullptr)
 {
     if (!out) {
         put_err(err, err_cap, "iq live: null argument");
@@ -226,6 +228,14 @@ int create_live(const aptgpu_context *ctx, const aptgpu_settings *decode_setting
         aptgpu_context c{};
         if (ctx) c = *ctx;
         live->device = c.device;
+        aptgpu_stream_settings ss{};
+        ss.struct_size = sizeof ss;
+        ss.input_rate_hz = checked.fm.fs_out;
+        ss.sync = ls->sync;
+        ss.format = APTGPU_STREAM_F32;
+        ss.max_push = ls->max_push;
+        // (a tracked coupling: the tracker's and the decode stream's refusals, before a device is touched)
+        if (tracked) (void)apt::stream_track::design_tracked(decode_settings, &ss, track, c.mode, apt::gpu::read_plan_switches().fast_mfma == '1');
         if (!host) {
             apt::hip_check(hipSetDevice(c.device), "hipSetDevice");
             if (!c.stream) {
@@ -236,15 +246,11 @@ int create_live(const aptgpu_context *ctx, const aptgpu_settings *decode_setting
                 live->stream = static_cast<hipStream_t>(c.stream);
             }
         }
-        aptgpu_stream_settings ss{};
-        ss.struct_size = sizeof ss;
-        ss.input_rate_hz = checked.fm.fs_out;
-        ss.sync = ls->sync;
-        ss.format = APTGPU_STREAM_F32;
-        ss.max_push = ls->max_push;
         char text[1024] = "";
-        const int rc = host ? aptgpu_stream_create_host(&c, decode_settings, &ss, &live->dec, text, sizeof text)
-                            : aptgpu_stream_create(&c, decode_settings, &ss, &live->dec, text, sizeof text);
+        // (a tracked coupling: the same handle with the flywheel tracker in the picker's place, include/aptgpu.h §4e)
+        const int rc = tracked ? parts::create_tracked(&c, decode_settings, &ss, track, host, &live->dec, text, sizeof text)
+                       : host  ? aptgpu_stream_create_host(&c, decode_settings, &ss, &live->dec, text, sizeof text)
+                               : aptgpu_stream_create(&c, decode_settings, &ss, &live->dec, text, sizeof text);
         if (rc != APTGPU_OK) throw Error{static_cast<ErrorKind>(rc), text};
         live->fm = make_fm_stream(fm_settings, &fss, host, c.device, live->stream).release();
         live->audio_cap = piece_outputs(live->fm->d);
@@ -410,6 +416,47 @@ int aptgpu_iq_live_create_host(const aptgpu_context *ctx, const aptgpu_settings 
                                aptgpu_iq_live **out, char *err, size_t err_cap)
 {
     return create_live(ctx, decode_settings, fm_settings, live_settings, true, out, err, err_cap);
+}
+
+int aptgpu_iq_live_create_tracked(const aptgpu_context *ctx, const aptgpu_settings *decode_settings,
+                                  const aptgpu_fm_settings *fm_settings, const aptgpu_iq_live_settings *live_settings,
+                                  const aptgpu_live_track_settings *track, aptgpu_iq_live **out, char *err, size_t err_cap)
+{
+    return create_live(ctx, decode_settings, fm_settings, live_settings, false, out, err, err_cap, true, track);
+}
+
+int aptgpu_iq_live_create_tracked_host(const aptgpu_context *ctx, const aptgpu_settings *decode_settings,
+                                       const aptgpu_fm_settings *fm_settings, const aptgpu_iq_live_settings *live_settings,
+                                       const aptgpu_live_track_settings *track, aptgpu_iq_live **out, char *err, size_t err_cap)
+{
+    return create_live(ctx, decode_settings, fm_settings, live_settings, true, out, err, err_cap, true, track);
+}
+
+int aptgpu_iq_live_track_scores(aptgpu_iq_live *s, float *scores, size_t cap, size_t *n, char *err, size_t err_cap)
+{
+    if (!s) {
+        put_err(err, err_cap, "iq live: null argument");
+        return APTGPU_ERR_INVALID;
+    }
+    return aptgpu_stream_track_scores(s->dec, scores, cap, n, err, err_cap);
+}
+
+int aptgpu_iq_live_track_scores_device(aptgpu_iq_live *s, float *d_scores, char *err, size_t err_cap)
+{
+    if (!s) {
+        put_err(err, err_cap, "iq live: null argument");
+        return APTGPU_ERR_INVALID;
+    }
+    return aptgpu_stream_track_scores_device(s->dec, d_scores, err, err_cap);
+}
+
+int aptgpu_iq_live_track_results(aptgpu_iq_live *s, aptgpu_stream_track_result *result, char *err, size_t err_cap)
+{
+    if (!s) {
+        put_err(err, err_cap, "iq live: null argument");
+        return APTGPU_ERR_INVALID;
+    }
+    return aptgpu_stream_track_results(s->dec, result, err, err_cap);
 }
 
 void aptgpu_iq_live_destroy(aptgpu_iq_live *s)

@@ -4,44 +4,14 @@
 #include <memory>
 #include <vector>
 
+#include "apt_capi_stream_handle.hpp"
 #include "apt_capi_stream_parts.hpp"
-#include "apt_capi_util.hpp"
-#include "apt_kernels_stream.hpp"
 
 namespace st = apt::stream;
 
 static_assert(sizeof(aptgpu_stream_result) == 56, "aptgpu_stream_result is part of the ABI");
 static_assert(offsetof(st::State, p) == sizeof(aptgpu_stream_result), "State's head must mirror aptgpu_stream_result");
 static_assert(offsetof(st::State, scan_pos) == offsetof(aptgpu_stream_result, scan_pos), "State's head must mirror aptgpu_stream_result");
-
-struct aptgpu_stream {
-    bool host = false;
-    st::Design d;
-    std::unique_ptr<st::HostStream> twin;
-    // ---- the device form
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    apt::DeviceBuffer<char> mem;  // the record, the rings and the taps: one allocation, fixed at creation
-    apt::gpu::StreamBuffers b{};
-    // the host-fed form's staging: stage_cap positions, then as many rows; kStageRows at creation, grown only when one
-    // push can release more (rows_bound)
-    apt::DeviceBuffer<char> stage;
-    uint32_t stage_cap = 0;
-    // what the host knows without asking the device: both are functions of the sample count alone
-    uint64_t n_in = 0, work_len = 0;
-    uint64_t rows_seen = 0;  // rows_total of the last record read back (a lower bound of the device's)
-    bool finished = false;
-
-    ~aptgpu_stream()
-    {
-        if (!host && stream) {
-            (void)hipSetDevice(device);
-            (void)hipStreamSynchronize(stream);
-            if (own_stream) (void)hipStreamDestroy(stream);
-        }
-    }
-};
 
 namespace {
 
@@ -50,7 +20,17 @@ using apt::capi::stream_parts::Target;
 
 constexpr uint32_t kStageRows = 64;
 
+namespace tparts = apt::capi::stream_track_parts;
+
 size_t align256(size_t v) { return (v + 255u) & ~static_cast<size_t>(255u); }
+
+// bytes of the staging per row: its position, its pixels and, on a tracked stream, its lock indicator
+size_t stage_row_bytes(const aptgpu_stream *s) { return 8 + st::kPx * 4 + (s->tracked ? 4 : 0); }
+float *stage_scores(const aptgpu_stream *s)
+{
+    return s->tracked ? reinterpret_cast<float *>(s->stage.ptr + static_cast<size_t>(s->stage_cap) * (8 + st::kPx * 4)) : nullptr;
+}
+const st::State &host_state(const aptgpu_stream *s) { return s->tracked ? s->ttwin->state() : s->twin->state(); }
 
 st::Design design_of(const aptgpu_context *ctx, const aptgpu_settings *settings, const aptgpu_stream_settings *ss)
 {
@@ -89,7 +69,10 @@ void create_device(aptgpu_stream *s, const aptgpu_context *ctx)
     s->b.table = reinterpret_cast<const float *>(base + o_tab);
     s->b.h2 = reinterpret_cast<const float *>(base + o_h2);
     s->stage_cap = kStageRows;
-    s->stage.alloc(static_cast<size_t>(s->stage_cap) * (8 + st::kPx * 4));
+    // (a tracked stream: what a push of max_push samples or a finish can release, so that only longer pushes grow it)
+    if (s->tracked) s->stage_cap = std::max(kStageRows, apt::stream_track::rows_bound(s->tp, 0, st::new_work_max(P, P.max_push) + s->tp.L));
+    s->stage.alloc(static_cast<size_t>(s->stage_cap) * stage_row_bytes(s));
+    if (s->tracked) tparts::create_device(s);
     apt::hip_check(hipMemsetAsync(base, 0, off, s->stream), "hipMemsetAsync");
     apt::hip_check(hipMemcpyAsync(base + o_tab, s->d.table.data(), s->d.table.size() * 4, hipMemcpyHostToDevice, s->stream), "hipMemcpyAsync H2D");
     apt::hip_check(hipMemcpyAsync(base + o_h2, s->d.h2.data(), s->d.h2.size() * 4, hipMemcpyHostToDevice, s->stream), "hipMemcpyAsync H2D");
@@ -101,7 +84,9 @@ void reset_device(aptgpu_stream *s)
     st::State z{};
     z.struct_size = sizeof(aptgpu_stream_result);
     st::state_reset(z);
+    if (s->tracked) z.n_sync = 0;  // (positions committed, not the picker's peaks)
     apt::hip_check(hipSetDevice(s->device), "hipSetDevice");
+    if (s->tracked) tparts::reset_device(s);
     apt::hip_check(hipMemcpyAsync(s->b.state, &z, sizeof z, hipMemcpyHostToDevice, s->stream), "hipMemcpyAsync H2D");
     apt::hip_check(hipStreamSynchronize(s->stream), "hipStreamSynchronize");  // z leaves scope
 }
@@ -109,7 +94,7 @@ void reset_device(aptgpu_stream *s)
 // n samples (host or device memory) into the ring and the four kernels, in segments of at most max_push; nothing waits
 // (first: this call opens a push; false continues one whose samples arrive in pieces)
 void enqueue(aptgpu_stream *s, const void *samples, size_t n, bool finish, float *d_rows, uint64_t *d_pos, uint32_t rows_cap,
-             bool first = true)
+             bool first = true, float *d_scores = nullptr)
 {
     const st::Params &P = s->d.P;
     const size_t es = P.s16 ? 2 : 4;
@@ -131,6 +116,12 @@ void enqueue(aptgpu_stream *s, const void *samples, size_t n, bool finish, float
         s->n_in += seg;
         const uint64_t w1 = st::work_count(P, s->n_in, fin);
         apt::gpu::stream_front(s->stream, P, s->b, w0, w1, s->n_in);
+        if (s->tracked) {  // (the tracker in the picker's place: §4e)
+            tparts::enqueue_segment(s, d_rows, d_pos, d_scores, rows_cap, w1, first, fin);
+            s->work_len = w1;
+            first = false;
+            continue;
+        }
         apt::gpu::stream_corr(s->stream, P, s->b, w0, w1);
         apt::gpu::stream_sync(s->stream, P, s->b, d_pos, rows_cap, s->n_in, w1, first, fin);
         apt::gpu::stream_rows(s->stream, P, s->b, d_pos, d_rows, rows_cap, std::min<uint32_t>(rows_cap, 32u));
@@ -156,6 +147,7 @@ void fail_record(const aptgpu_stream_result &r)
 // aptgpu_stream_rows_bound: from the sample count after the push and the rows the host knows to be out
 uint32_t bound_of(const aptgpu_stream *s, size_t n)
 {
+    if (s->tracked) return tparts::bound_of(s, n);
     if (s->host) return st::rows_bound(s->d.P, s->twin->state().n_in + n, s->twin->state().rows_total);
     return st::rows_bound(s->d.P, s->n_in + n, s->rows_seen);
 }
@@ -172,12 +164,16 @@ void check_call(const aptgpu_stream *s, size_t n, size_t rows_cap, const aptgpu_
 // more pieces, then ONE record and the rows it counts.
 Target begin_host_fed(aptgpu_stream *s, size_t n, float *rows, uint64_t *positions, size_t rows_cap)
 {
-    if (s->host) return Target{rows, positions, static_cast<uint32_t>(std::min<size_t>(rows_cap, 0xFFFFFFFFu))};
+    if (s->host) {
+        const uint32_t cap = static_cast<uint32_t>(std::min<size_t>(rows_cap, 0xFFFFFFFFu));
+        if (s->tracked) s->last_scores.assign(std::max<uint32_t>(bound_of(s, n), 1u), 0.f);
+        return Target{rows, positions, s->tracked ? std::min<uint32_t>(cap, static_cast<uint32_t>(s->last_scores.size())) : cap};
+    }
     apt::hip_check(hipSetDevice(s->device), "hipSetDevice");
     const uint32_t need = bound_of(s, n);
     if (need > s->stage_cap) {
         apt::hip_check(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
-        s->stage.alloc(static_cast<size_t>(need) * (8 + st::kPx * 4));
+        s->stage.alloc(static_cast<size_t>(need) * stage_row_bytes(s));
         s->stage_cap = need;
     }
     return Target{reinterpret_cast<float *>(s->stage.ptr + static_cast<size_t>(s->stage_cap) * 8),
@@ -187,7 +183,12 @@ Target begin_host_fed(aptgpu_stream *s, size_t n, float *rows, uint64_t *positio
 void piece_of_push(aptgpu_stream *s, const void *samples, size_t n, bool first, bool finish, const Target &t)
 {
     if (!s->host) {
-        enqueue(s, samples, n, finish, t.rows, t.positions, t.cap, first);
+        // a tracked stream's lock indicators go beside the rows: into the staging when the rows do (the host-fed form),
+        // else where the device-resident form puts them
+        float *scores = nullptr;
+        if (s->tracked)
+            scores = t.positions == reinterpret_cast<uint64_t *>(s->stage.ptr) ? stage_scores(s) : tparts::scores_target(s, t.cap);
+        enqueue(s, samples, n, finish, t.rows, t.positions, t.cap, first, scores);
         return;
     }
     const st::Params &P = s->d.P;
@@ -197,8 +198,9 @@ void piece_of_push(aptgpu_stream *s, const void *samples, size_t n, bool first, 
         const size_t seg = std::min<size_t>(n - done, P.max_push);
         const bool head = first && done == 0;
         done += seg;
-        s->twin->push_segment(static_cast<const char *>(samples) + (done - seg) * es, seg, finish && done == n, head, t.rows,
-                              t.positions, t.cap);
+        const char *src = static_cast<const char *>(samples) + (done - seg) * es;
+        if (s->tracked) s->ttwin->push_segment(src, seg, finish && done == n, head, t.rows, t.positions, s->last_scores.data(), t.cap);
+        else s->twin->push_segment(src, seg, finish && done == n, head, t.rows, t.positions, t.cap);
     } while (done < n);
     if (finish) s->finished = true;
 }
@@ -206,7 +208,8 @@ void piece_of_push(aptgpu_stream *s, const void *samples, size_t n, bool first, 
 void end_host_fed(aptgpu_stream *s, const Target &t, float *rows, uint64_t *positions, aptgpu_stream_result *result)
 {
     if (s->host) {
-        copy_result(s->twin->state(), result);
+        copy_result(host_state(s), result);
+        if (s->tracked) s->last_scores.resize(result->n_rows);
         fail_record(*result);
         return;
     }
@@ -220,7 +223,15 @@ void end_host_fed(aptgpu_stream *s, const Target &t, float *rows, uint64_t *posi
                        "hipMemcpyAsync D2H");
         apt::hip_check(hipMemcpyAsync(positions, t.positions, static_cast<size_t>(rec.n_rows) * 8, hipMemcpyDeviceToHost, s->stream),
                        "hipMemcpyAsync D2H");
+        if (s->tracked) {
+            s->last_scores.resize(rec.n_rows);
+            apt::hip_check(hipMemcpyAsync(s->last_scores.data(), stage_scores(s), static_cast<size_t>(rec.n_rows) * 4, hipMemcpyDeviceToHost,
+                                          s->stream),
+                           "hipMemcpyAsync D2H");
+        }
         apt::hip_check(hipStreamSynchronize(s->stream), "hipStreamSynchronize");
+    } else {
+        s->last_scores.clear();
     }
     copy_result(rec, result);
     fail_record(*result);
@@ -236,7 +247,7 @@ void push_host_fed(aptgpu_stream *s, const void *samples, size_t n, bool finish,
 }
 
 int create(const aptgpu_context *ctx, const aptgpu_settings *settings, const aptgpu_stream_settings *ss, bool host, aptgpu_stream **out,
-           char *err, size_t err_cap)
+           char *err, size_t err_cap, bool tracked = false, const aptgpu_live_track_settings *track = nullptr)
 {
     if (!out) {
         put_err(err, err_cap, "stream: null argument");
@@ -246,9 +257,18 @@ int create(const aptgpu_context *ctx, const aptgpu_settings *settings, const apt
     return guarded(err, err_cap, [&] {
         auto s = std::make_unique<aptgpu_stream>();
         s->host = host;
-        s->d = design_of(ctx, settings, ss);
-        if (host) s->twin = std::make_unique<st::HostStream>(s->d);
-        else {
+        s->tracked = tracked;
+        if (tracked) {
+            apt::stream_track::Design td = apt::stream_track::design_tracked(settings, ss, track, ctx ? ctx->mode : APTGPU_MODE_STRICT,
+                                                                             apt::gpu::read_plan_switches().fast_mfma == '1');
+            s->d = td.stream;
+            s->tp = td.T;
+            if (host) s->ttwin = std::make_unique<apt::stream_track::HostTrackStream>(std::move(td));
+        } else {
+            s->d = design_of(ctx, settings, ss);
+            if (host) s->twin = std::make_unique<st::HostStream>(s->d);
+        }
+        if (!host) {
             create_device(s.get(), ctx);
             reset_device(s.get());
         }
@@ -279,6 +299,11 @@ void end(aptgpu_stream *s, const Target &t, float *rows, uint64_t *positions, ap
 {
     end_host_fed(s, t, rows, positions, result);
 }
+int create_tracked(const aptgpu_context *ctx, const aptgpu_settings *settings, const aptgpu_stream_settings *ss,
+                   const aptgpu_live_track_settings *track, bool host, aptgpu_stream **out, char *err, size_t err_cap)
+{
+    return create(ctx, settings, ss, host, out, err, err_cap, true, track);
+}
 
 }  // namespace apt::capi::stream_parts
 
@@ -301,7 +326,8 @@ void aptgpu_stream_destroy(aptgpu_stream *stream) { delete stream; }
 int aptgpu_stream_get_info(const aptgpu_stream *stream, aptgpu_stream_info *info)
 {
     if (!stream || !info || info->struct_size < sizeof(aptgpu_stream_info)) return APTGPU_ERR_INVALID;
-    st::fill_info(stream->d, stream->host ? stream->twin->bytes() : stream->mem.count + stream->stage.count, info);
+    const uint64_t host_bytes = !stream->host ? 0 : stream->tracked ? stream->ttwin->bytes() : stream->twin->bytes();
+    st::fill_info(stream->d, stream->host ? host_bytes : stream->mem.count + stream->stage.count + stream->tmem.count, info);
     return APTGPU_OK;
 }
 
@@ -312,8 +338,12 @@ int aptgpu_stream_reset(aptgpu_stream *stream, char *err, size_t err_cap)
         return APTGPU_ERR_INVALID;
     }
     return guarded(err, err_cap, [&] {
-        if (stream->host) stream->twin->reset();
+        if (stream->host && stream->tracked) stream->ttwin->reset();
+        else if (stream->host) stream->twin->reset();
         else reset_device(stream);
+        stream->m = 0;
+        stream->d_scores = nullptr;
+        stream->last_scores.clear();
         stream->n_in = 0;
         stream->work_len = 0;
         stream->rows_seen = 0;
@@ -363,7 +393,8 @@ int aptgpu_stream_push_device(aptgpu_stream *stream, const void *d_samples, size
         if (stream->host) throw Error{ErrorKind::Invalid, "stream: a host handle has no device entry points"};
         check_call(stream, n, rows_cap, nullptr, false);
         apt::hip_check(hipSetDevice(stream->device), "hipSetDevice");
-        enqueue(stream, d_samples, n, false, d_rows, d_positions, static_cast<uint32_t>(std::min<size_t>(rows_cap, 0xFFFFFFFFu)));
+        const uint32_t cap = static_cast<uint32_t>(std::min<size_t>(rows_cap, 0xFFFFFFFFu));
+        enqueue(stream, d_samples, n, false, d_rows, d_positions, cap, true, stream->tracked ? tparts::scores_target(stream, cap) : nullptr);
         return APTGPU_OK;
     });
 }
@@ -378,7 +409,8 @@ int aptgpu_stream_finish_device(aptgpu_stream *stream, float *d_rows, uint64_t *
         if (stream->host) throw Error{ErrorKind::Invalid, "stream: a host handle has no device entry points"};
         check_call(stream, 0, rows_cap, nullptr, false);
         apt::hip_check(hipSetDevice(stream->device), "hipSetDevice");
-        enqueue(stream, nullptr, 0, true, d_rows, d_positions, static_cast<uint32_t>(std::min<size_t>(rows_cap, 0xFFFFFFFFu)));
+        const uint32_t cap = static_cast<uint32_t>(std::min<size_t>(rows_cap, 0xFFFFFFFFu));
+        enqueue(stream, nullptr, 0, true, d_rows, d_positions, cap, true, stream->tracked ? tparts::scores_target(stream, cap) : nullptr);
         return APTGPU_OK;
     });
 }
@@ -392,7 +424,7 @@ int aptgpu_stream_results(aptgpu_stream *stream, aptgpu_stream_result *result, c
     return guarded(err, err_cap, [&] {
         if (result->struct_size < sizeof(aptgpu_stream_result)) throw Error{ErrorKind::Invalid, "aptgpu_stream_result: struct_size not set"};
         if (stream->host) {
-            copy_result(stream->twin->state(), result);
+            copy_result(host_state(stream), result);
         } else {
             st::State rec{};
             apt::hip_check(hipSetDevice(stream->device), "hipSetDevice");

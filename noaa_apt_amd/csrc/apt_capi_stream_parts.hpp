@@ -26,5 +26,8 @@ void check(const aptgpu_stream *s, size_t n, size_t rows_cap, const aptgpu_strea
 Target begin(aptgpu_stream *s, size_t n, float *rows, uint64_t *positions, size_t rows_cap);
 void piece(aptgpu_stream *s, const void *samples, size_t n, bool first, bool finish, const Target &t);
 void end(aptgpu_stream *s, const Target &t, float *rows, uint64_t *positions, aptgpu_stream_result *result);
+// aptgpu_stream_create_tracked / _host (include/aptgpu.h §4e): the same handle with the tracker in the picker's place
+int create_tracked(const aptgpu_context *ctx, const aptgpu_settings *settings, const aptgpu_stream_settings *ss,
+                   const aptgpu_live_track_settings *track, bool host, aptgpu_stream **out, char *err, size_t err_cap);
 
 }  // namespace apt::capi::stream_parts

@@ -40,6 +40,10 @@ constexpr int kReasonFewSync = 2;    // "Found less than 5 sync frames, ..."
 constexpr int kReasonTripCap = 5;    // the picker's loop reached its trip-count cap (a defect if it happens: DESIGN.md §22)
 constexpr int kReasonOverflow = 6;   // the pending list or the caller's row buffer is full (a defect if it happens)
 constexpr int kReasonWindow = 7;     // a tile's input window exceeds the LDS the launch reserved (a defect if it happens)
+// ... of a tracked stream (apt_kernels_stream_track.hpp)
+constexpr int kReasonTrackTooShort = 8;  // finish: shorter than one row and one sync frame (the one-shot tracker's refusal)
+constexpr int kReasonTrackWalkCap = 9;   // a back-track reached its bound (a defect if it happens)
+constexpr int kReasonTrackTripCap = 10;  // the checkpoint loop reached its bound (likewise)
 
 // What a stream is created with (host-designed; by value in the kernel arguments).
 struct Params {
@@ -416,13 +420,16 @@ public:
     void reset();
     // one segment of at most max_push samples (finish: none); rows / positions as the kernels would write them
     void push_segment(const void *samples, uint64_t n, bool finish, bool first, float *rows, uint64_t *positions, uint32_t rows_cap);
+    // the front end alone (what push_segment begins with): the samples into the input ring, F up to the new work_len
+    void front_segment(const void *samples, uint64_t n, bool finish);
+    float f_at(uint64_t i) const;  // refuses an index that is not live
+    State &state_mut() { return st_; }
     const State &state() const { return st_; }
     const Design &design() const { return d_; }
     uint64_t bytes() const;
 
 private:
     float in_at(uint64_t i) const;
-    float f_at(uint64_t i) const;
     Design d_;
     State st_{};
     std::vector<float> in_f32_;

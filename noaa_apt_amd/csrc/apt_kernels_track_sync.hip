@@ -21,9 +21,9 @@ namespace {
 using apt::track::kPx;
 using apt::track::kStart;
 
-constexpr int kScoreThreads = 256;
-constexpr int kScorePer = 4;                              // positions per thread
-constexpr int kScoreTile = kScoreThreads * kScorePer;     // positions per workgroup
+using apt::track::kScorePer;
+using apt::track::kScoreThreads;
+using apt::track::kScoreTile;
 constexpr int kDpThreads = 1024;
 
 // the recording's sample count as the kernels see it: 0 where there is nothing to track (*reason says why)
@@ -51,9 +51,7 @@ template <int PW>
 __global__ void __launch_bounds__(kScoreThreads)
 k_track_score(const TrackCall call)
 {
-    constexpr int G = 38 * PW;
-    constexpr int Q = (G + kScorePer - 1 + 3) / 4;  // quads a thread reads: its G + 3 samples
-    constexpr int LEN = kScoreTile + 4 * Q;         // floats of the tile with its halo (Q quads from the last thread's first)
+    constexpr int G = apt::track::ScoreTile<PW>::G, LEN = apt::track::ScoreTile<PW>::LEN;
     __shared__ __attribute__((aligned(16))) float tile[LEN];
 
     const TrackRec r = call.rec[blockIdx.y];
@@ -84,52 +82,8 @@ k_track_score(const TrackCall call)
     }
     __syncthreads();
 
-    float c[kScorePer], s1[kScorePer], s2[kScorePer];
-#pragma unroll
-    for (int p = 0; p < kScorePer; ++p) c[p] = s1[p] = s2[p] = 0.f;
-    const float4 *__restrict__ quads = reinterpret_cast<const float4 *>(tile) + tid;
-    // One quad of the thread's run: sample j = j0 + e is sample j - p of position p's window.  j0 is a compile-time
-    // constant wherever this is called (signs and window tests fold away).
-    auto quad = [&](const float4 v4, const int j0) {
-        const float v[4] = {v4.x, v4.y, v4.z, v4.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int j = j0 + e;
-            const float q = __fmul_rn(v[e], v[e]);
-#pragma unroll
-            for (int p = 0; p < kScorePer; ++p)
-                if (j - p >= 0 && j - p < G)
-                    apt::track::score_step_sq(v[e], q, apt::track::template_plus(j - p, PW), c[p], s1[p], s2[p]);
-        }
-    };
-    // Unrolled whole, the Q quads' LDS reads are all issued up front (241 VGPRs at pw = 3, the budget's 256 above).  The
-    // template repeats every 4 pw samples = pw quads between its first pulse and its tail, and its tail is all minus:
-    // where every one of the four windows is inside such a zone the loop over it stays a loop, with the signs of its
-    // first turn.  Same additions in the same order: same bits.
-    constexpr int K0 = (2 * PW + 3 + 3) / 4;                  // first quad with j - 3 >= 2 pw
-    constexpr int P = (30 * PW - 4 * K0) / (4 * PW);          // whole periods from there that end by 30 pw
-    constexpr int K1 = K0 + P * PW;
-    constexpr int K2 = (30 * PW + 3 + 3) / 4;                 // first quad with j - 3 >= 30 pw
-    constexpr int K3 = G / 4;                                 // quads that end inside the window of position 0
-    static_assert(K1 <= K2 && K2 <= K3 && K3 <= Q, "zones of the score loop");
-#pragma unroll
-    for (int k = 0; k < K0; ++k) quad(quads[k], 4 * k);
-#pragma unroll 1
-    for (int it = 0; it < P; ++it) {
-        const float4 *__restrict__ qp = quads + K0 + it * PW;
-#pragma unroll
-        for (int kk = 0; kk < PW; ++kk) quad(qp[kk], 4 * (K0 + kk));
-    }
-#pragma unroll
-    for (int k = K1; k < K2; ++k) quad(quads[k], 4 * k);
-#pragma unroll 1
-    for (int k = K2; k < K3; ++k) quad(quads[k], 4 * K2);
-#pragma unroll
-    for (int k = K3; k < Q; ++k) quad(quads[k], 4 * k);
-    const float fg = static_cast<float>(G), norm = apt::track::norm_of(G), wmean = apt::track::mean_weight();
     float out[kScorePer];
-#pragma unroll
-    for (int p = 0; p < kScorePer; ++p) out[p] = apt::track::score_finish(c[p], s1[p], s2[p], fg, norm, wmean);
+    apt::track::score_four<PW>(tile, tid, out);  // (the zone loop: apt_kernels_track_sync.hpp)
     // through the tile, so that lanes store consecutive addresses
     __syncthreads();
 #pragma unroll

@@ -117,6 +117,9 @@ const char *reason_text(int reason)
     case kReasonTripCap: return "stream: the picker exceeded its trip-count bound";
     case kReasonOverflow: return "stream: more rows or pending peaks than the bound allows";
     case kReasonWindow: return "stream: a tile's input window exceeds its LDS";
+    case kReasonTrackTooShort: return "track: the signal is shorter than one row and one sync frame";
+    case kReasonTrackWalkCap: return "stream: the tracker's back-track exceeded its bound";
+    case kReasonTrackTripCap: return "stream: the tracker's checkpoint loop exceeded its trip-count bound";
     default: return "stream failed";
     }
 }
@@ -154,12 +157,10 @@ float HostStream::f_at(uint64_t i) const
     return f_[static_cast<size_t>(i & (P.cap_f - 1))];
 }
 
-void HostStream::push_segment(const void *samples, uint64_t n, bool finish, bool first, float *rows, uint64_t *positions,
-                              uint32_t rows_cap)
+void HostStream::front_segment(const void *samples, uint64_t n, bool finish)
 {
     const Params &P = d_.P;
     if (n > P.max_push) throw Error{ErrorKind::Internal, "stream: segment longer than max_push"};
-    release_begin(st_, first);
     for (uint64_t i = 0; i < n; ++i) {
         const size_t q = static_cast<size_t>((st_.n_in + i) & (P.cap_in - 1));
         if (P.s16) in_s16_[q] = static_cast<const int16_t *>(samples)[i];
@@ -184,6 +185,15 @@ void HostStream::push_segment(const void *samples, uint64_t n, bool finish, bool
                 lowpass_at(i, P.t2, [&](uint64_t q) { return D[static_cast<size_t>(q - ka)]; }, [&](uint32_t j) { return d_.h2[j]; });
     }
     st_.work_len = w1;
+}
+
+void HostStream::push_segment(const void *samples, uint64_t n, bool finish, bool first, float *rows, uint64_t *positions,
+                              uint32_t rows_cap)
+{
+    const Params &P = d_.P;
+    release_begin(st_, first);
+    front_segment(samples, n, finish);
+    const uint64_t w1 = st_.work_len;
 
     // ---- sync: corr for the newly scannable positions, then the picker
     if (P.sync && st_.status == 0) {
