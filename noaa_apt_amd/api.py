@@ -1,5 +1,6 @@
 """ctypes binding of include/aptgpu.h with the reference's names (see package docstring)."""
 import ctypes as C
+import itertools
 import os
 import sys
 import subprocess
@@ -1738,46 +1739,35 @@ def _live_track_c(settings):
         raise InvalidError(f"stream: {e}") from None
 
 
-class LiveDecoder:
-    """aptgpu_stream: live decode (DESIGN.md §22).  Push the recording in chunks of any size; every push returns the
-    image rows that are final — bit-identical to what strict decode() of the complete recording holds at that place,
-    whatever is pushed later — and their work-rate positions.  finish() releases the rest and raises what decode()
-    would raise ("less than 10 rows", "less than 5 sync frames"); rows handed out before stay handed out.  dtype:
-    np.float32 or np.int16 (mono PCM16, the value as f32).  host=True: the plain C++ twin on the CPU (same bits, no GPU).
-    `result` is the record of the last call, `info` the stream's geometry and ring capacities.
-    track: a LiveTrackSettings finds the rows with the flywheel tracker in place of the reference's picker (DESIGN.md
-    §24; `sync` is then not read): rows are the filtered samples' own bits, committed lag_rows behind real time;
-    `scores` holds the lock indicators of the last call's rows and `track_result` the tracker's record."""
+class _LiveBase:
+    """What LiveDecoder and LiveIqDecoder share: the handle, the calls and the records.  _PREFIX names the C functions
+    (<prefix>_create[_tracked][_host], _push, _finish, ...); a subclass adds its constructor's argument handling,
+    get_info and the conversion of a chunk to (pointer, count)."""
+    _PREFIX = None
 
-    def __init__(self, settings, input_rate, sync=True, context=None, dtype=np.float32, max_push=None, host=False,
-                 track=None):
-        self._dtype = np.dtype(dtype)
-        fmt = {np.dtype(np.float32): 0, np.dtype(np.int16): 1}.get(self._dtype)
-        if fmt is None:
-            raise InvalidError("stream: dtype must be float32 or int16")
-        self._ctx = context or Context()
-        cctx, cs = self._ctx._c(), settings._c()
-        css = _CStreamSettings(C.sizeof(_CStreamSettings), int(input_rate.get_hz()), 1 if sync else 0, fmt, int(max_push or 0), 0)
+    def _fn(self, name):
+        return getattr(lib(), f"{self._PREFIX}_{name}")
+
+    def _create(self, host, track, *head):
+        """head: the structures in front of the track settings in the create call"""
         self._p = C.c_void_p()
         self.host = bool(host)
         err = C.create_string_buffer(_ERRCAP)
         self.tracked = track is not None
         self.scores, self.track_result = None, None
+        args = [C.byref(a) for a in head]
         if self.tracked:
             ct = _live_track_c(track)
-            fn = lib().aptgpu_stream_create_tracked_host if host else lib().aptgpu_stream_create_tracked
-            _check(fn(C.byref(cctx), C.byref(cs), C.byref(css), C.byref(ct), C.byref(self._p), err, _ERRCAP), err)
+            args.append(C.byref(ct))
+        fn = self._fn("create" + ("_tracked" if self.tracked else "") + ("_host" if host else ""))
+        _check(fn(*args, C.byref(self._p), err, _ERRCAP), err)
+        if self.tracked:
             self.scores = np.zeros(0, np.float32)
-        else:
-            fn = lib().aptgpu_stream_create_host if host else lib().aptgpu_stream_create
-            _check(fn(C.byref(cctx), C.byref(cs), C.byref(css), C.byref(self._p), err, _ERRCAP), err)
-        self.info = StreamInfo(struct_size=C.sizeof(StreamInfo))
-        _check(lib().aptgpu_stream_get_info(self._p, C.byref(self.info)))
         self.result = StreamResult(struct_size=C.sizeof(StreamResult))
 
     def close(self):
         if self._p:
-            lib().aptgpu_stream_destroy(self._p)
+            self._fn("destroy")(self._p)
             self._p = C.c_void_p()
 
     def __del__(self):
@@ -1793,24 +1783,12 @@ class LiveDecoder:
         self.close()
         return False
 
-    def get_info(self):
-        info = StreamInfo(struct_size=C.sizeof(StreamInfo))
-        _check(lib().aptgpu_stream_get_info(self._p, C.byref(info)))
-        return info
-
-    def rows_bound(self, n=0):
-        """Upper bound of the rows a push of n more samples (0: a finish) can release now: from the work signal's length
-        after it and the rows known to be out (one event of the picker can push any number of peaks)."""
-        return int(lib().aptgpu_stream_rows_bound(self._p, int(n)))
-
     def reset(self):
         err = C.create_string_buffer(_ERRCAP)
-        _check(lib().aptgpu_stream_reset(self._p, err, _ERRCAP), err)
+        _check(self._fn("reset")(self._p, err, _ERRCAP), err)
         self.result = StreamResult(struct_size=C.sizeof(StreamResult))
 
-    def _call(self, chunk, rows_cap):
-        finish = chunk is None
-        n = 0 if finish else chunk.size
+    def _call(self, ptr, n, rows_cap, finish=False):
         cap = self.rows_bound(n) if rows_cap is None else int(rows_cap)
         rows = np.empty((max(cap, 1), PX_PER_ROW), np.float32)
         pos = np.empty(max(cap, 1), np.uint64)
@@ -1818,10 +1796,9 @@ class LiveDecoder:
         err = C.create_string_buffer(_ERRCAP)
         rp, pp = rows.ctypes.data_as(_f32p), pos.ctypes.data_as(_u64p)
         if finish:
-            rc = lib().aptgpu_stream_finish(self._p, rp, pp, cap, C.byref(res), err, _ERRCAP)
+            rc = self._fn("finish")(self._p, rp, pp, cap, C.byref(res), err, _ERRCAP)
         else:
-            rc = lib().aptgpu_stream_push(self._p, chunk.ctypes.data_as(C.c_void_p), n, rp, pp, cap, C.byref(res), err,
-                                          _ERRCAP)
+            rc = self._fn("push")(self._p, ptr, n, rp, pp, cap, C.byref(res), err, _ERRCAP)
         if rc in (0, 1):  # (an end-of-signal error fills the record; a refused call leaves it alone)
             self.result = res
             if self.tracked:
@@ -1833,15 +1810,15 @@ class LiveDecoder:
     def _read_track(self, k):
         sc, n = np.zeros(max(k, 1), np.float32), C.c_size_t(0)
         err = C.create_string_buffer(_ERRCAP)
-        _check(lib().aptgpu_stream_track_scores(self._p, sc.ctypes.data_as(_f32p), k, C.byref(n), err, _ERRCAP), err)
+        _check(self._fn("track_scores")(self._p, sc.ctypes.data_as(_f32p), k, C.byref(n), err, _ERRCAP), err)
         self.scores = sc[:min(k, int(n.value))].copy()
         self.track_results()
 
     def track_results(self):
-        """Waits like results() and returns the tracker's record (a tracked stream only)."""
+        """Waits like results() and returns the tracker's record (a tracked stream or coupling only)."""
         res = StreamTrackResult(struct_size=C.sizeof(StreamTrackResult))
         err = C.create_string_buffer(_ERRCAP)
-        _check(lib().aptgpu_stream_track_results(self._p, C.byref(res), err, _ERRCAP), err)
+        _check(self._fn("track_results")(self._p, C.byref(res), err, _ERRCAP), err)
         self.track_result = res
         return res
 
@@ -1849,35 +1826,93 @@ class LiveDecoder:
         """Where the device-resident calls that follow write the lock indicators of their rows (a device pointer to
         rows_cap floats; None: the stream keeps them)."""
         err = C.create_string_buffer(_ERRCAP)
-        _check(lib().aptgpu_stream_track_scores_device(self._p, d_scores, err, _ERRCAP), err)
-
-    def push(self, chunk, rows_cap=None):
-        """chunk: 1-D samples of the stream's dtype -> (rows [n, 2080] f32, positions [n] u64) that became final."""
-        return self._call(np.ascontiguousarray(chunk, dtype=self._dtype).reshape(-1), rows_cap)
+        _check(self._fn("track_scores_device")(self._p, d_scores, err, _ERRCAP), err)
 
     def finish(self, rows_cap=None):
         """The end of the recording: the remaining rows, or the error decode() would raise."""
-        return self._call(None, rows_cap)
+        return self._call(None, 0, rows_cap, finish=True)
 
-    def push_device(self, d_samples, n, d_rows, d_positions, rows_cap):
-        """Device pointers (ints); asynchronous on the context's stream.  rows_cap >= rows_bound(n)."""
+    def _push_device(self, d_in, n, d_rows, d_positions, rows_cap):
         err = C.create_string_buffer(_ERRCAP)
-        _check(lib().aptgpu_stream_push_device(self._p, d_samples, int(n), d_rows, d_positions, int(rows_cap), err,
-                                               _ERRCAP), err)
+        _check(self._fn("push_device")(self._p, d_in, int(n), d_rows, d_positions, int(rows_cap), err, _ERRCAP), err)
 
     def finish_device(self, d_rows, d_positions, rows_cap):
         err = C.create_string_buffer(_ERRCAP)
-        _check(lib().aptgpu_stream_finish_device(self._p, d_rows, d_positions, int(rows_cap), err, _ERRCAP), err)
+        _check(self._fn("finish_device")(self._p, d_rows, d_positions, int(rows_cap), err, _ERRCAP), err)
 
     def results(self):
         """Waits for the device-resident calls and returns the record of the last one (raising its error)."""
         res = StreamResult(struct_size=C.sizeof(StreamResult))
         err = C.create_string_buffer(_ERRCAP)
-        rc = lib().aptgpu_stream_results(self._p, C.byref(res), err, _ERRCAP)
+        rc = self._fn("results")(self._p, C.byref(res), err, _ERRCAP)
         if rc in (0, 1):
             self.result = res
         _check(rc, err)
         return res
+
+
+def _collect_live(dec, chunks, return_info):
+    """What decode_live and decode_live_iq do with an open decoder: every chunk pushed, then the finish."""
+    out, pos, sc = [], [], []
+    with dec:
+        def take(call):
+            out.append(call[0])
+            pos.append(call[1])
+            if dec.tracked:
+                sc.append(dec.scores)
+
+        for chunk in chunks:
+            take(dec.push(chunk))
+        take(dec.finish())
+        info = dec.track_result
+    rows = np.concatenate(out).reshape(-1)
+    if return_info and dec.tracked:
+        return rows, np.concatenate(pos), np.concatenate(sc), info
+    return rows
+
+
+class LiveDecoder(_LiveBase):
+    """aptgpu_stream: live decode (DESIGN.md §22).  Push the recording in chunks of any size; every push returns the
+    image rows that are final — bit-identical to what strict decode() of the complete recording holds at that place,
+    whatever is pushed later — and their work-rate positions.  finish() releases the rest and raises what decode()
+    would raise ("less than 10 rows", "less than 5 sync frames"); rows handed out before stay handed out.  dtype:
+    np.float32 or np.int16 (mono PCM16, the value as f32).  host=True: the plain C++ twin on the CPU (same bits, no GPU).
+    `result` is the record of the last call, `info` the stream's geometry and ring capacities.
+    track: a LiveTrackSettings finds the rows with the flywheel tracker in place of the reference's picker (DESIGN.md
+    §24; `sync` is then not read): rows are the filtered samples' own bits, committed lag_rows behind real time;
+    `scores` holds the lock indicators of the last call's rows and `track_result` the tracker's record."""
+    _PREFIX = "aptgpu_stream"
+
+    def __init__(self, settings, input_rate, sync=True, context=None, dtype=np.float32, max_push=None, host=False,
+                 track=None):
+        self._dtype = np.dtype(dtype)
+        fmt = {np.dtype(np.float32): 0, np.dtype(np.int16): 1}.get(self._dtype)
+        if fmt is None:
+            raise InvalidError("stream: dtype must be float32 or int16")
+        self._ctx = context or Context()
+        cctx, cs = self._ctx._c(), settings._c()
+        css = _CStreamSettings(C.sizeof(_CStreamSettings), int(input_rate.get_hz()), 1 if sync else 0, fmt, int(max_push or 0), 0)
+        self._create(host, track, cctx, cs, css)
+        self.info = self.get_info()
+
+    def get_info(self):
+        info = StreamInfo(struct_size=C.sizeof(StreamInfo))
+        _check(lib().aptgpu_stream_get_info(self._p, C.byref(info)))
+        return info
+
+    def rows_bound(self, n=0):
+        """Upper bound of the rows a push of n more samples (0: a finish) can release now: from the work signal's length
+        after it and the rows known to be out (one event of the picker can push any number of peaks)."""
+        return int(lib().aptgpu_stream_rows_bound(self._p, int(n)))
+
+    def push(self, chunk, rows_cap=None):
+        """chunk: 1-D samples of the stream's dtype -> (rows [n, 2080] f32, positions [n] u64) that became final."""
+        chunk = np.ascontiguousarray(chunk, dtype=self._dtype).reshape(-1)
+        return self._call(chunk.ctypes.data_as(C.c_void_p), chunk.size, rows_cap)
+
+    def push_device(self, d_samples, n, d_rows, d_positions, rows_cap):
+        """Device pointers (ints); asynchronous on the context's stream.  rows_cap >= rows_bound(n)."""
+        self._push_device(d_samples, n, d_rows, d_positions, rows_cap)
 
 
 def decode_live(context: Optional["Context"], settings: "Settings", chunks, input_rate: "Rate", sync: bool, host=False,
@@ -1889,24 +1924,8 @@ def decode_live(context: Optional["Context"], settings: "Settings", chunks, inpu
     it = iter(chunks)
     first = next(it, None)
     dtype = np.int16 if first is not None and np.asarray(first).dtype == np.int16 else np.float32
-    out, pos, sc = [], [], []
-    with LiveDecoder(settings, input_rate, sync, context, dtype, max_push, host, track) as dec:
-        def take(call):
-            out.append(call[0])
-            pos.append(call[1])
-            if dec.tracked:
-                sc.append(dec.scores)
-
-        if first is not None:
-            take(dec.push(first))
-        for chunk in it:
-            take(dec.push(chunk))
-        take(dec.finish())
-        info = dec.track_result
-    rows = np.concatenate(out).reshape(-1) if out else np.zeros(0, np.float32)
-    if return_info and track is not None:
-        return rows, np.concatenate(pos), np.concatenate(sc), info
-    return rows
+    rest = it if first is None else itertools.chain([first], it)
+    return _collect_live(LiveDecoder(settings, input_rate, sync, context, dtype, max_push, host, track), rest, return_info)
 
 
 THERMAL_COLD_WHITE = 1
@@ -2301,55 +2320,24 @@ class FmStream:
         return int(n.value)
 
 
-class LiveIqDecoder:
+class LiveIqDecoder(_LiveBase):
     """aptgpu_iq_live: live decode from IQ frames: an FmStream in front of a LiveDecoder on one HIP
     stream, the audio staying on the device.  The surface is LiveDecoder's, with frames for samples: push() returns
     the rows that became final and their positions, finish() the rest or decode()'s error.  `fm_info` and `info` are
     the two stages' infos, `result` the record of the last call.  track: a LiveTrackSettings, as for LiveDecoder
     (DESIGN.md §24): `scores` and `track_result` then hold the lock indicators of the last call's rows and the
     tracker's record."""
+    _PREFIX = "aptgpu_iq_live"
 
     def __init__(self, settings, fm_settings, sync=True, context=None, max_push_frames=None, max_push=None, first_frame=0,
                  host=False, track=None):
-        cfm = _fm_settings_c(fm_settings)
-        self._cfm = cfm
+        self._cfm = _fm_settings_c(fm_settings)
         self._ctx = context or Context()
         cctx, cs = self._ctx._c(), settings._c()
         cls = _CIqLiveSettings(C.sizeof(_CIqLiveSettings), 1 if sync else 0, int(max_push_frames or 0), int(max_push or 0),
                                int(first_frame))
-        self._p = C.c_void_p()
-        self.host = bool(host)
-        err = C.create_string_buffer(_ERRCAP)
-        self.tracked = track is not None
-        self.scores, self.track_result = None, None
-        if self.tracked:
-            ct = _live_track_c(track)
-            fn = lib().aptgpu_iq_live_create_tracked_host if host else lib().aptgpu_iq_live_create_tracked
-            _check(fn(C.byref(cctx), C.byref(cs), C.byref(cfm), C.byref(cls), C.byref(ct), C.byref(self._p), err, _ERRCAP), err)
-            self.scores = np.zeros(0, np.float32)
-        else:
-            fn = lib().aptgpu_iq_live_create_host if host else lib().aptgpu_iq_live_create
-            _check(fn(C.byref(cctx), C.byref(cs), C.byref(cfm), C.byref(cls), C.byref(self._p), err, _ERRCAP), err)
+        self._create(host, track, cctx, cs, self._cfm, cls)
         self.fm_info, self.info = self.get_info()
-        self.result = StreamResult(struct_size=C.sizeof(StreamResult))
-
-    def close(self):
-        if self._p:
-            lib().aptgpu_iq_live_destroy(self._p)
-            self._p = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
 
     def get_info(self):
         """-> (FmStreamInfo, StreamInfo)"""
@@ -2361,82 +2349,15 @@ class LiveIqDecoder:
         """Upper bound of the rows a push of n_frames more frames (0: a finish) can release now."""
         return int(lib().aptgpu_iq_live_rows_bound(self._p, int(n_frames)))
 
-    def reset(self):
-        err = C.create_string_buffer(_ERRCAP)
-        _check(lib().aptgpu_iq_live_reset(self._p, err, _ERRCAP), err)
-        self.result = StreamResult(struct_size=C.sizeof(StreamResult))
-
-    def _call(self, chunk, frames, rows_cap):
-        finish = chunk is None
-        cap = self.rows_bound(frames) if rows_cap is None else int(rows_cap)
-        rows = np.empty((max(cap, 1), PX_PER_ROW), np.float32)
-        pos = np.empty(max(cap, 1), np.uint64)
-        res = StreamResult(struct_size=C.sizeof(StreamResult))
-        err = C.create_string_buffer(_ERRCAP)
-        rp, pp = rows.ctypes.data_as(_f32p), pos.ctypes.data_as(_u64p)
-        if finish:
-            rc = lib().aptgpu_iq_live_finish(self._p, rp, pp, cap, C.byref(res), err, _ERRCAP)
-        else:
-            rc = lib().aptgpu_iq_live_push(self._p, chunk.ctypes.data if chunk.size else None, frames, rp, pp, cap,
-                                           C.byref(res), err, _ERRCAP)
-        if rc in (0, 1):  # (an end-of-signal error fills the record; a refused call leaves it alone)
-            self.result = res
-            if self.tracked:
-                self._read_track(0 if rc else int(res.n_rows))
-        _check(rc, err)
-        k = int(res.n_rows)
-        return rows[:k].copy(), pos[:k].copy()
-
-    def _read_track(self, k):
-        sc, n = np.zeros(max(k, 1), np.float32), C.c_size_t(0)
-        err = C.create_string_buffer(_ERRCAP)
-        _check(lib().aptgpu_iq_live_track_scores(self._p, sc.ctypes.data_as(_f32p), k, C.byref(n), err, _ERRCAP), err)
-        self.scores = sc[:min(k, int(n.value))].copy()
-        self.track_results()
-
-    def track_results(self):
-        """Waits like results() and returns the tracker's record (a tracked coupling only)."""
-        res = StreamTrackResult(struct_size=C.sizeof(StreamTrackResult))
-        err = C.create_string_buffer(_ERRCAP)
-        _check(lib().aptgpu_iq_live_track_results(self._p, C.byref(res), err, _ERRCAP), err)
-        self.track_result = res
-        return res
-
-    def scores_device(self, d_scores):
-        """Where the device-resident calls that follow write the lock indicators of their rows (a device pointer to
-        rows_cap floats; None: the stream keeps them)."""
-        err = C.create_string_buffer(_ERRCAP)
-        _check(lib().aptgpu_iq_live_track_scores_device(self._p, d_scores, err, _ERRCAP), err)
-
     def push(self, iq, rows_cap=None):
         """iq: interleaved components of the format's dtype -> (rows [n, 2080] f32, positions [n] u64) that became
         final."""
         a, frames = _fm_iq(iq, self._cfm)
-        return self._call(a, frames, rows_cap)
-
-    def finish(self, rows_cap=None):
-        """The end of the recording: the remaining rows, or the error decode() would raise."""
-        return self._call(None, 0, rows_cap)
+        return self._call(a.ctypes.data if a.size else None, frames, rows_cap)
 
     def push_device(self, d_iq, n_frames, d_rows, d_positions, rows_cap):
         """Device pointers (ints); asynchronous on the context's stream.  rows_cap >= rows_bound(n_frames)."""
-        err = C.create_string_buffer(_ERRCAP)
-        _check(lib().aptgpu_iq_live_push_device(self._p, d_iq or None, int(n_frames), d_rows, d_positions, int(rows_cap),
-                                                err, _ERRCAP), err)
-
-    def finish_device(self, d_rows, d_positions, rows_cap):
-        err = C.create_string_buffer(_ERRCAP)
-        _check(lib().aptgpu_iq_live_finish_device(self._p, d_rows, d_positions, int(rows_cap), err, _ERRCAP), err)
-
-    def results(self):
-        """Waits for the device-resident calls and returns the record of the last one (raising its error)."""
-        res = StreamResult(struct_size=C.sizeof(StreamResult))
-        err = C.create_string_buffer(_ERRCAP)
-        rc = lib().aptgpu_iq_live_results(self._p, C.byref(res), err, _ERRCAP)
-        if rc in (0, 1):
-            self.result = res
-        _check(rc, err)
-        return res
+        self._push_device(d_iq or None, n_frames, d_rows, d_positions, rows_cap)
 
 
 def decode_live_iq(context: Optional["Context"], settings: "Settings", fm_settings: "FmSettings", chunks, sync: bool,
@@ -2444,22 +2365,8 @@ def decode_live_iq(context: Optional["Context"], settings: "Settings", fm_settin
     """decode(fm_demodulate(...)) over an iterable of IQ chunks through a LiveIqDecoder: returns the rows of the
     chunks' concatenation (flat f32, rows * 2080) and raises what decode() raises.  track: a LiveTrackSettings
     (DESIGN.md §24); return_info then gives (rows, positions, scores, StreamTrackResult)."""
-    out, pos, sc = [], [], []
-    with LiveIqDecoder(settings, fm_settings, sync, context, max_push_frames, host=host, track=track) as dec:
-        def take(call):
-            out.append(call[0])
-            pos.append(call[1])
-            if dec.tracked:
-                sc.append(dec.scores)
-
-        for chunk in chunks:
-            take(dec.push(chunk))
-        take(dec.finish())
-        info = dec.track_result
-    rows = np.concatenate(out).reshape(-1)
-    if return_info and track is not None:
-        return rows, np.concatenate(pos), np.concatenate(sc), info
-    return rows
+    dec = LiveIqDecoder(settings, fm_settings, sync, context, max_push_frames, host=host, track=track)
+    return _collect_live(dec, chunks, return_info)
 
 
 def process(context, signal, contrast_adjustment, rotate=Rotate.NO, color=None, orbit=None,

@@ -62,6 +62,13 @@ namespace {
 using namespace apt::capi;
 
 size_t frame_bytes(const aptgpu_fm_stream *s) { return 2u * fms::component_bytes(s->d.fm.format); }
+// frames pushed so far, and the outputs n_frames more would return: the one place that knows where the count lives
+uint64_t frames(const aptgpu_fm_stream *s) { return s->host ? s->twin->frames() : s->n; }
+size_t out_len_after(const aptgpu_fm_stream *s, size_t n_frames)
+{
+    const uint64_t n = frames(s);
+    return static_cast<size_t>(fms::stream_out_len(s->d.fm, n + n_frames) - fms::stream_out_len(s->d.fm, n));
+}
 // outputs one piece of at most max_push_frames frames can return
 size_t piece_outputs(const fms::StreamDesign &d) { return d.max_push_frames / d.fm.D + 2u; }
 
@@ -153,7 +160,7 @@ void fill_info(const aptgpu_fm_stream *s, aptgpu_fm_stream_info *info)
     info->n_taps = d.T;
     info->decimation = d.D;
     info->pw = d.pw;
-    const uint64_t n = s->host ? s->twin->frames() : s->n;
+    const uint64_t n = frames(s);
     info->carry_frames = static_cast<uint32_t>(n - fms::stream_carry_start(d, n));
     info->shift_hz_used = d.shift_used;
     info->taps = d.taps.data();
@@ -207,13 +214,10 @@ size_t push_fm_host_fed(aptgpu_fm_stream *s, const void *iq, size_t n_frames, fl
 
 // ---- the coupling
 int create_live(const aptgpu_context *ctx, const aptgpu_settings *decode_settings, const aptgpu_fm_settings *fm_settings,
-                const aptgpu_iq_live_settings *ls, bool host, aptgpu_iq_live **out, char *err, size_t err_cap, bool tracked = false,
-                const aptgpu_live_track_settings *track = nullptr)
+                const aptgpu_iq_live_settings *ls, bool tracked, const aptgpu_live_track_settings *track, bool host,
+                aptgpu_iq_live **out, char *err, size_t err_cap)
 {
-    if (!out) {
-        put_err(err, err_cap, "iq live: null argument");
-        return APTGPU_ERR_INVALID;
-    }
+    if (!out) return null_argument(err, err_cap, "iq live");
     *out = nullptr;
     return guarded(err, err_cap, [&] {
         if (!ls || ls->struct_size < sizeof(aptgpu_iq_live_settings))
@@ -248,9 +252,7 @@ int create_live(const aptgpu_context *ctx, const aptgpu_settings *decode_setting
         }
         char text[1024] = "";
         // (a tracked coupling: the same handle with the flywheel tracker in the picker's place, include/aptgpu.h §4e)
-        const int rc = tracked ? parts::create_tracked(&c, decode_settings, &ss, track, host, &live->dec, text, sizeof text)
-                       : host  ? aptgpu_stream_create_host(&c, decode_settings, &ss, &live->dec, text, sizeof text)
-                               : aptgpu_stream_create(&c, decode_settings, &ss, &live->dec, text, sizeof text);
+        const int rc = parts::create(&c, decode_settings, &ss, tracked, track, host, &live->dec, text, sizeof text);
         if (rc != APTGPU_OK) throw Error{static_cast<ErrorKind>(rc), text};
         live->fm = make_fm_stream(fm_settings, &fss, host, c.device, live->stream).release();
         live->audio_cap = piece_outputs(live->fm->d);
@@ -290,18 +292,8 @@ void live_pieces(aptgpu_iq_live *s, const void *iq, size_t n_frames, bool iq_on_
 void check_live_push(const aptgpu_iq_live *s, const void *iq, size_t n_frames, size_t rows_cap, const aptgpu_stream_result *result,
                      bool want_result, const char *iq_name)
 {
-    const aptgpu_fm_stream *fm = s->fm;
-    const uint64_t n = s->host ? fm->twin->frames() : fm->n;
-    fms::check_push(fm->d, n, iq, n_frames, nullptr, 0, iq_name, nullptr);
-    const size_t n_audio = static_cast<size_t>(fms::stream_out_len(fm->d.fm, n + n_frames) - fms::stream_out_len(fm->d.fm, n));
-    parts::check(s->dec, n_audio, rows_cap, result, want_result);
-}
-
-size_t live_audio_of(const aptgpu_iq_live *s, size_t n_frames)
-{
-    const aptgpu_fm_stream *fm = s->fm;
-    const uint64_t n = s->host ? fm->twin->frames() : fm->n;
-    return static_cast<size_t>(fms::stream_out_len(fm->d.fm, n + n_frames) - fms::stream_out_len(fm->d.fm, n));
+    fms::check_push(s->fm->d, frames(s->fm), iq, n_frames, nullptr, 0, iq_name, nullptr);
+    parts::check(s->dec, out_len_after(s->fm, n_frames), rows_cap, result, want_result);
 }
 
 }  // namespace
@@ -311,10 +303,7 @@ extern "C" {
 int aptgpu_fm_stream_create(const aptgpu_context *ctx, const aptgpu_fm_settings *settings,
                             const aptgpu_fm_stream_settings *stream_settings, aptgpu_fm_stream **out, char *err, size_t err_cap)
 {
-    if (!out) {
-        put_err(err, err_cap, "fm stream: null argument");
-        return APTGPU_ERR_INVALID;
-    }
+    if (!out) return null_argument(err, err_cap, "fm stream");
     *out = nullptr;
     return guarded(err, err_cap, [&] {
         *out = make_fm_stream(settings, stream_settings, false, ctx ? ctx->device : 0,
@@ -327,10 +316,7 @@ int aptgpu_fm_stream_create(const aptgpu_context *ctx, const aptgpu_fm_settings 
 int aptgpu_fm_stream_create_host(const aptgpu_fm_settings *settings, const aptgpu_fm_stream_settings *stream_settings,
                                  aptgpu_fm_stream **out, char *err, size_t err_cap)
 {
-    if (!out) {
-        put_err(err, err_cap, "fm stream: null argument");
-        return APTGPU_ERR_INVALID;
-    }
+    if (!out) return null_argument(err, err_cap, "fm stream");
     *out = nullptr;
     return guarded(err, err_cap, [&] {
         *out = make_fm_stream(settings, stream_settings, true, 0, nullptr).release();
@@ -342,10 +328,7 @@ void aptgpu_fm_stream_destroy(aptgpu_fm_stream *s) { delete s; }
 
 int aptgpu_fm_stream_reset(aptgpu_fm_stream *s, char *err, size_t err_cap)
 {
-    if (!s) {
-        put_err(err, err_cap, "fm stream: null argument");
-        return APTGPU_ERR_INVALID;
-    }
+    if (!s) return null_argument(err, err_cap, "fm stream");
     reset_fm(s);
     return APTGPU_OK;
 }
@@ -359,21 +342,16 @@ int aptgpu_fm_stream_get_info(const aptgpu_fm_stream *s, aptgpu_fm_stream_info *
 
 size_t aptgpu_fm_stream_out_len(const aptgpu_fm_stream *s, size_t n_frames)
 {
-    if (!s) return 0;
-    const uint64_t n = s->host ? s->twin->frames() : s->n;
-    return static_cast<size_t>(fms::stream_out_len(s->d.fm, n + n_frames) - fms::stream_out_len(s->d.fm, n));
+    return s ? out_len_after(s, n_frames) : 0;
 }
 
 int aptgpu_fm_stream_push(aptgpu_fm_stream *s, const void *iq, size_t n_frames, float *audio, size_t audio_cap, size_t *n_out,
                           char *err, size_t err_cap)
 {
-    if (!s || !n_out) {
-        put_err(err, err_cap, "fm stream: null argument");
-        return APTGPU_ERR_INVALID;
-    }
+    if (!s || !n_out) return null_argument(err, err_cap, "fm stream");
     *n_out = 0;
     return guarded(err, err_cap, [&] {
-        fms::check_push(s->d, s->host ? s->twin->frames() : s->n, iq, n_frames, audio, audio_cap, "iq", "audio");
+        fms::check_push(s->d, frames(s), iq, n_frames, audio, audio_cap, "iq", "audio");
         *n_out = push_fm_host_fed(s, iq, n_frames, audio);
         return APTGPU_OK;
     });
@@ -382,10 +360,7 @@ int aptgpu_fm_stream_push(aptgpu_fm_stream *s, const void *iq, size_t n_frames, 
 int aptgpu_fm_stream_push_device(aptgpu_fm_stream *s, const void *d_iq, size_t n_frames, float *d_audio, size_t audio_cap,
                                  size_t *n_out, char *err, size_t err_cap)
 {
-    if (!s || !n_out) {
-        put_err(err, err_cap, "fm stream: null argument");
-        return APTGPU_ERR_INVALID;
-    }
+    if (!s || !n_out) return null_argument(err, err_cap, "fm stream");
     *n_out = 0;
     return guarded(err, err_cap, [&] {
         if (s->host) throw Error{ErrorKind::Invalid, "fm stream: a host handle has no device entry points"};
@@ -408,54 +383,45 @@ int aptgpu_fm_stream_push_device(aptgpu_fm_stream *s, const void *d_iq, size_t n
 int aptgpu_iq_live_create(const aptgpu_context *ctx, const aptgpu_settings *decode_settings, const aptgpu_fm_settings *fm_settings,
                           const aptgpu_iq_live_settings *live_settings, aptgpu_iq_live **out, char *err, size_t err_cap)
 {
-    return create_live(ctx, decode_settings, fm_settings, live_settings, false, out, err, err_cap);
+    return create_live(ctx, decode_settings, fm_settings, live_settings, false, nullptr, false, out, err, err_cap);
 }
 
 int aptgpu_iq_live_create_host(const aptgpu_context *ctx, const aptgpu_settings *decode_settings,
                                const aptgpu_fm_settings *fm_settings, const aptgpu_iq_live_settings *live_settings,
                                aptgpu_iq_live **out, char *err, size_t err_cap)
 {
-    return create_live(ctx, decode_settings, fm_settings, live_settings, true, out, err, err_cap);
+    return create_live(ctx, decode_settings, fm_settings, live_settings, false, nullptr, true, out, err, err_cap);
 }
 
 int aptgpu_iq_live_create_tracked(const aptgpu_context *ctx, const aptgpu_settings *decode_settings,
                                   const aptgpu_fm_settings *fm_settings, const aptgpu_iq_live_settings *live_settings,
                                   const aptgpu_live_track_settings *track, aptgpu_iq_live **out, char *err, size_t err_cap)
 {
-    return create_live(ctx, decode_settings, fm_settings, live_settings, false, out, err, err_cap, true, track);
+    return create_live(ctx, decode_settings, fm_settings, live_settings, true, track, false, out, err, err_cap);
 }
 
 int aptgpu_iq_live_create_tracked_host(const aptgpu_context *ctx, const aptgpu_settings *decode_settings,
                                        const aptgpu_fm_settings *fm_settings, const aptgpu_iq_live_settings *live_settings,
                                        const aptgpu_live_track_settings *track, aptgpu_iq_live **out, char *err, size_t err_cap)
 {
-    return create_live(ctx, decode_settings, fm_settings, live_settings, true, out, err, err_cap, true, track);
+    return create_live(ctx, decode_settings, fm_settings, live_settings, true, track, true, out, err, err_cap);
 }
 
 int aptgpu_iq_live_track_scores(aptgpu_iq_live *s, float *scores, size_t cap, size_t *n, char *err, size_t err_cap)
 {
-    if (!s) {
-        put_err(err, err_cap, "iq live: null argument");
-        return APTGPU_ERR_INVALID;
-    }
+    if (!s) return null_argument(err, err_cap, "iq live");
     return aptgpu_stream_track_scores(s->dec, scores, cap, n, err, err_cap);
 }
 
 int aptgpu_iq_live_track_scores_device(aptgpu_iq_live *s, float *d_scores, char *err, size_t err_cap)
 {
-    if (!s) {
-        put_err(err, err_cap, "iq live: null argument");
-        return APTGPU_ERR_INVALID;
-    }
+    if (!s) return null_argument(err, err_cap, "iq live");
     return aptgpu_stream_track_scores_device(s->dec, d_scores, err, err_cap);
 }
 
 int aptgpu_iq_live_track_results(aptgpu_iq_live *s, aptgpu_stream_track_result *result, char *err, size_t err_cap)
 {
-    if (!s) {
-        put_err(err, err_cap, "iq live: null argument");
-        return APTGPU_ERR_INVALID;
-    }
+    if (!s) return null_argument(err, err_cap, "iq live");
     return aptgpu_stream_track_results(s->dec, result, err, err_cap);
 }
 
@@ -471,10 +437,7 @@ void aptgpu_iq_live_destroy(aptgpu_iq_live *s)
 
 int aptgpu_iq_live_reset(aptgpu_iq_live *s, char *err, size_t err_cap)
 {
-    if (!s) {
-        put_err(err, err_cap, "iq live: null argument");
-        return APTGPU_ERR_INVALID;
-    }
+    if (!s) return null_argument(err, err_cap, "iq live");
     const int rc = aptgpu_stream_reset(s->dec, err, err_cap);
     if (rc == APTGPU_OK) reset_fm(s->fm);
     return rc;
@@ -493,20 +456,17 @@ int aptgpu_iq_live_get_info(const aptgpu_iq_live *s, aptgpu_fm_stream_info *fm_i
 
 size_t aptgpu_iq_live_rows_bound(const aptgpu_iq_live *s, size_t n_frames)
 {
-    return s ? aptgpu_stream_rows_bound(s->dec, live_audio_of(s, n_frames)) : 0;
+    return s ? aptgpu_stream_rows_bound(s->dec, out_len_after(s->fm, n_frames)) : 0;
 }
 
 int aptgpu_iq_live_push(aptgpu_iq_live *s, const void *iq, size_t n_frames, float *rows, uint64_t *positions, size_t rows_cap,
                         aptgpu_stream_result *result, char *err, size_t err_cap)
 {
-    if (!s || !rows || !positions || !result) {
-        put_err(err, err_cap, "iq live: null argument");
-        return APTGPU_ERR_INVALID;
-    }
+    if (!s || !rows || !positions || !result) return null_argument(err, err_cap, "iq live");
     return guarded(err, err_cap, [&] {
         check_live_push(s, iq, n_frames, rows_cap, result, true, "iq");
         if (!s->host) apt::hip_check(hipSetDevice(s->device), "hipSetDevice");
-        const parts::Target t = parts::begin(s->dec, live_audio_of(s, n_frames), rows, positions, rows_cap);
+        const parts::Target t = parts::begin(s->dec, out_len_after(s->fm, n_frames), rows, positions, rows_cap);
         live_pieces(s, iq, n_frames, true, t);
         parts::end(s->dec, t, rows, positions, result);
         return APTGPU_OK;
@@ -516,25 +476,19 @@ int aptgpu_iq_live_push(aptgpu_iq_live *s, const void *iq, size_t n_frames, floa
 int aptgpu_iq_live_finish(aptgpu_iq_live *s, float *rows, uint64_t *positions, size_t rows_cap, aptgpu_stream_result *result,
                           char *err, size_t err_cap)
 {
-    if (!s) {
-        put_err(err, err_cap, "iq live: null argument");
-        return APTGPU_ERR_INVALID;
-    }
+    if (!s) return null_argument(err, err_cap, "iq live");
     return aptgpu_stream_finish(s->dec, rows, positions, rows_cap, result, err, err_cap);
 }
 
 int aptgpu_iq_live_push_device(aptgpu_iq_live *s, const void *d_iq, size_t n_frames, float *d_rows, uint64_t *d_positions,
                                size_t rows_cap, char *err, size_t err_cap)
 {
-    if (!s || !d_rows || !d_positions) {
-        put_err(err, err_cap, "iq live: null argument");
-        return APTGPU_ERR_INVALID;
-    }
+    if (!s || !d_rows || !d_positions) return null_argument(err, err_cap, "iq live");
     return guarded(err, err_cap, [&] {
         if (s->host) throw Error{ErrorKind::Invalid, "iq live: a host handle has no device entry points"};
         check_live_push(s, d_iq, n_frames, rows_cap, nullptr, false, "d_iq");
         apt::hip_check(hipSetDevice(s->device), "hipSetDevice");
-        const parts::Target t{d_rows, d_positions, static_cast<uint32_t>(std::min<size_t>(rows_cap, 0xFFFFFFFFu))};
+        const parts::Target t = parts::device_target(s->dec, d_rows, d_positions, rows_cap);
         live_pieces(s, d_iq, n_frames, false, t);
         return APTGPU_OK;
     });
@@ -542,19 +496,13 @@ int aptgpu_iq_live_push_device(aptgpu_iq_live *s, const void *d_iq, size_t n_fra
 
 int aptgpu_iq_live_finish_device(aptgpu_iq_live *s, float *d_rows, uint64_t *d_positions, size_t rows_cap, char *err, size_t err_cap)
 {
-    if (!s) {
-        put_err(err, err_cap, "iq live: null argument");
-        return APTGPU_ERR_INVALID;
-    }
+    if (!s) return null_argument(err, err_cap, "iq live");
     return aptgpu_stream_finish_device(s->dec, d_rows, d_positions, rows_cap, err, err_cap);
 }
 
 int aptgpu_iq_live_results(aptgpu_iq_live *s, aptgpu_stream_result *result, char *err, size_t err_cap)
 {
-    if (!s) {
-        put_err(err, err_cap, "iq live: null argument");
-        return APTGPU_ERR_INVALID;
-    }
+    if (!s) return null_argument(err, err_cap, "iq live");
     return aptgpu_stream_results(s->dec, result, err, err_cap);
 }
 

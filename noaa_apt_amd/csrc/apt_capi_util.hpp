@@ -1,5 +1,6 @@
 // apt_capi_util.hpp — helpers shared by the extern "C" translation units (apt_capi.hip,
-// apt_capi_image.hip): error mapping, malloc'd outputs, context callbacks, a per-call stream.
+// apt_capi_image.hip, the stream units): error mapping, the null-argument refusal, malloc'd outputs, context callbacks,
+// a per-call stream.
 #pragma once
 
 #include <cstdio>
@@ -41,6 +42,17 @@ int guarded(char *err, size_t cap, Fn &&fn)
         return APTGPU_ERR_INTERNAL;
     }
 }
+
+// the refusal of a null argument by the stream, fm-stream and iq-live entry points: "<who>: null argument"
+inline int null_argument(char *err, size_t cap, const char *who)
+{
+    put_err(err, cap, std::string(who) + ": null argument");
+    return APTGPU_ERR_INVALID;
+}
+
+inline size_t align256(size_t v) { return (v + 255u) & ~static_cast<size_t>(255u); }
+// a caller's rows_cap as the kernels take it
+inline uint32_t clamp_cap(size_t cap) { return cap > 0xFFFFFFFFu ? 0xFFFFFFFFu : static_cast<uint32_t>(cap); }
 
 template <typename T>
 T *host_alloc(size_t n)

@@ -399,6 +399,10 @@ APT_STR_HD void release_rows(const Params &P, State &st, bool finish, uint64_t *
 #include "../../include/aptgpu.h"
 #include "apt_host.hpp"
 
+namespace apt::stream_track {
+struct Record;  // apt_kernels_stream_track.hpp
+}
+
 namespace apt::stream {
 
 // The design of a stream: every refusal of §4d (none touches a device), the taps and the ring capacities.
@@ -413,22 +417,45 @@ Design design_stream(const aptgpu_settings *settings, const aptgpu_stream_settin
 void fill_info(const Design &d, uint64_t device_bytes, aptgpu_stream_info *info);
 const char *reason_text(int reason);
 
-// The twin: the same state machine over host rings.
-class HostStream {
+// What the C API asks of a twin (picker or tracker): one interface, so that a handle holds one engine and never names
+// the concrete class outside creation.
+class HostLive {
+public:
+    virtual ~HostLive() = default;
+    virtual void reset() = 0;
+    virtual const State &state() const = 0;
+    virtual uint64_t bytes() const = 0;
+    // aptgpu_stream_rows_bound: the rows a push of n more samples (or a finish there) can release
+    virtual uint32_t rows_bound(uint64_t n) const = 0;
+    virtual const apt::stream_track::Record *track_record() const { return nullptr; }  // null: the picker
+    // n samples in segments of at most max_push (first: this call opens a push, false continues one whose samples arrive
+    // in pieces; finish closes the recording with the last segment); scores: the tracker's lock indicators, null for the picker
+    void push(const void *samples, uint64_t n, bool first, bool finish, float *rows, uint64_t *positions, float *scores, uint32_t rows_cap);
+    // one segment of at most max_push samples (finish: none); rows / positions (/ scores) as the kernels would write them
+    virtual void push_segment(const void *samples, uint64_t n, bool finish, bool first, float *rows, uint64_t *positions, float *scores,
+                              uint32_t rows_cap) = 0;
+
+protected:
+    virtual const Params &params() const = 0;
+};
+
+// The picker's twin: the same state machine over host rings.
+class HostStream final : public HostLive {
 public:
     explicit HostStream(Design d);
-    void reset();
-    // one segment of at most max_push samples (finish: none); rows / positions as the kernels would write them
-    void push_segment(const void *samples, uint64_t n, bool finish, bool first, float *rows, uint64_t *positions, uint32_t rows_cap);
+    void reset() override;
+    void push_segment(const void *samples, uint64_t n, bool finish, bool first, float *rows, uint64_t *positions, float *scores,
+                      uint32_t rows_cap) override;
     // the front end alone (what push_segment begins with): the samples into the input ring, F up to the new work_len
     void front_segment(const void *samples, uint64_t n, bool finish);
     float f_at(uint64_t i) const;  // refuses an index that is not live
     State &state_mut() { return st_; }
-    const State &state() const { return st_; }
-    const Design &design() const { return d_; }
-    uint64_t bytes() const;
+    const State &state() const override { return st_; }
+    uint64_t bytes() const override;
+    uint32_t rows_bound(uint64_t n) const override { return apt::stream::rows_bound(d_.P, st_.n_in + n, st_.rows_total); }
 
 private:
+    const Params &params() const override { return d_.P; }
     float in_at(uint64_t i) const;
     Design d_;
     State st_{};

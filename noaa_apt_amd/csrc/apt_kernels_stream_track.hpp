@@ -67,6 +67,13 @@ APT_STR_HD uint32_t rows_bound(const Params &T, uint64_t m0, uint64_t m1)
     return b > 0xFFFFFFFFull ? 0xFFFFFFFFu : static_cast<uint32_t>(b);
 }
 
+// aptgpu_stream_rows_bound of a tracked stream: m stands at m0 and the sample count comes to n_after
+// (a finish makes more work samples final than a push of the same samples: the bound serves both)
+APT_STR_HD uint32_t rows_bound_after(const Params &T, const apt::stream::Params &P, uint64_t m0, uint64_t n_after)
+{
+    return rows_bound(T, m0, positions_final(T, apt::stream::work_count(P, n_after, true)));
+}
+
 // One position of the dynamic programme.  s_at(i), best_at(j): the rings; returns best[i] and the back-pointer.
 template <typename Best>
 APT_STR_HD void dp_position(const Params &T, uint64_t i, float s, Best &&best_at, float &best_out, int &bp_out)
@@ -142,18 +149,19 @@ Design design_tracked(const aptgpu_settings *settings, const aptgpu_stream_setti
                       bool mfma_switch);
 
 // The twin: the front end of apt::stream::HostStream, then the same tracker over host rings.
-class HostTrackStream {
+class HostTrackStream final : public apt::stream::HostLive {
 public:
     explicit HostTrackStream(Design d);
-    void reset();
+    void reset() override;
     void push_segment(const void *samples, uint64_t n, bool finish, bool first, float *rows, uint64_t *positions, float *scores,
-                      uint32_t rows_cap);
-    const apt::stream::State &state() const { return front_.state(); }
-    const Record &record() const { return rec_; }
-    const Design &design() const { return d_; }
-    uint64_t bytes() const;
+                      uint32_t rows_cap) override;
+    const apt::stream::State &state() const override { return front_.state(); }
+    const Record *track_record() const override { return &rec_; }
+    uint64_t bytes() const override;
+    uint32_t rows_bound(uint64_t n) const override { return rows_bound_after(d_.T, d_.stream.P, rec_.m, state().n_in + n); }
 
 private:
+    const apt::stream::Params &params() const override { return d_.stream.P; }
     Design d_;
     apt::stream::HostStream front_;
     Record rec_{};

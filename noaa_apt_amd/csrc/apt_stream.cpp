@@ -2,6 +2,7 @@
 // device is touched), and the state machine of apt_kernels_stream.hpp in plain C++ over host rings
 // (aptgpu_stream_create_host), which the kernels are tested against besides the model of tests/np_stream_model.py.
 // The twin indexes its rings exactly as the kernels do and refuses to read an index that is no longer (or not yet) live.
+// HostLive::push, the splitting of a push into segments of max_push for either twin, is here too.
 #include "apt_kernels_stream.hpp"
 
 #include <algorithm>
@@ -187,7 +188,21 @@ void HostStream::front_segment(const void *samples, uint64_t n, bool finish)
     st_.work_len = w1;
 }
 
-void HostStream::push_segment(const void *samples, uint64_t n, bool finish, bool first, float *rows, uint64_t *positions,
+void HostLive::push(const void *samples, uint64_t n, bool first, bool finish, float *rows, uint64_t *positions, float *scores,
+                    uint32_t rows_cap)
+{
+    const Params &P = params();
+    const size_t es = P.s16 ? 2 : 4;
+    uint64_t done = 0;
+    do {
+        const uint64_t seg = std::min<uint64_t>(n - done, P.max_push);
+        const bool head = first && done == 0;
+        done += seg;
+        push_segment(static_cast<const char *>(samples) + (done - seg) * es, seg, finish && done == n, head, rows, positions, scores, rows_cap);
+    } while (done < n);
+}
+
+void HostStream::push_segment(const void *samples, uint64_t n, bool finish, bool first, float *rows, uint64_t *positions, float *,
                               uint32_t rows_cap)
 {
     const Params &P = d_.P;

@@ -10,9 +10,11 @@
 // 48 kHz, 24 960 Hz and 12 480 Hz, f32 and s16, sync and no sync, through the twin in awkward chunkings — one chunk,
 // 1-sample pushes across a row boundary, sizes 0 / 1 / primes, pushes longer than a small max_push, a max_push of a
 // quarter row (every ring wraps), a fading carrier whose picker pushes two dozen peaks in one event, 25 rows in one
-// launch sequence — with the sample, row and position buffers allocated at exactly their sizes (an
-// access past either end is the sanitizer's to report).  Every chunking must give the first one's rows bit for bit;
-// the twin itself refuses a read of a ring index that is not live.
+// launch sequence — with the sample, row and position buffers allocated at exactly their sizes (the rows at exactly
+// rows_bound: an access past either end is the sanitizer's to report).  Every push goes through HostLive::push, the
+// interface and the splitting into segments of max_push that the C API uses; pushes of 0 samples and one of more than
+// max_push are among the chunkings.  Every chunking must give the first one's rows bit for bit; the twin itself refuses
+// a read of a ring index that is not live.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -90,26 +92,22 @@ struct Output {
 // pushes x in chunks of the given sizes (the last one takes the rest), then finishes
 Output run(const st::Design &d, const std::vector<float> &x, const std::vector<size_t> &sizes)
 {
-    st::HostStream hs(d);
+    st::HostStream twin(d);
+    st::HostLive &hs = twin;  // (what the C API holds)
     const st::Params &P = d.P;
     Output out;
     size_t at = 0, k = 0;
     auto call = [&](size_t n, bool finish) {
         // exact-size buffers: the samples of this push, the rows and positions its bound allows
-        const uint32_t cap = st::rows_bound(P, hs.state().n_in + n, hs.state().rows_total);
+        const uint32_t cap = hs.rows_bound(n);
+        expect(cap == st::rows_bound(P, hs.state().n_in + n, hs.state().rows_total), "rows_bound is the picker's");
         std::vector<float> rows(static_cast<size_t>(cap) * st::kPx);
         std::vector<uint64_t> pos(cap);
         std::vector<float> f(x.begin() + at, x.begin() + at + n);
         std::vector<int16_t> s(n);
         for (size_t i = 0; i < n; ++i) s[i] = static_cast<int16_t>(std::isfinite(f[i]) ? f[i] : 0.f);
         const char *src = P.s16 ? reinterpret_cast<const char *>(s.data()) : reinterpret_cast<const char *>(f.data());
-        const size_t es = P.s16 ? 2 : 4;
-        size_t done = 0;
-        do {
-            const size_t seg = std::min<size_t>(n - done, P.max_push);
-            hs.push_segment(src + done * es, seg, finish && done + seg == n, done == 0, rows.data(), pos.data(), cap);
-            done += seg;
-        } while (done < n);
+        hs.push(n ? src : nullptr, n, true, finish, rows.data(), pos.data(), nullptr, cap);
         at += n;
         const st::State &r = hs.state();
         expect(r.n_rows <= cap, "rows within the bound");
@@ -166,6 +164,11 @@ void chunkings(uint32_t rate, bool sync, int format, bool nonfinite)
     expect(x.size() >= 3 * static_cast<size_t>(small.P.cap_in) && one.last.work_len >= 3ull * small.P.cap_f, tag + ": the rings wrap");
     const Output o = run(small, x, {x.size() / 3, 5, x.size() / 2});
     expect(same_bits(o.rows, one.rows) && o.pos == one.pos, tag + ": quarter-row max_push");
+    // n above max_push (x.size() / 3 and x.size() / 2 are many segments each), n == 0 in the middle, and a push that is
+    // exactly max_push + 1 samples: one full segment and one of a single sample
+    expect(x.size() / 3 > 4 * static_cast<size_t>(quarter_row), tag + ": pushes above max_push");
+    const Output e = run(small, x, {0, static_cast<size_t>(quarter_row) + 1, 0, 0, x.size() / 2, 0});
+    expect(same_bits(e.rows, one.rows) && e.pos == one.pos, tag + ": max_push + 1 and empty pushes");
 }
 
 // A carrier that fades for 14 s and then stays level: the picker replaces one peak for 28 rows and then pushes all the

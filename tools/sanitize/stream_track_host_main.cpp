@@ -12,7 +12,8 @@
 // awkward chunkings — one chunk, 1-sample pushes across a checkpoint, sizes 0 / 1 / primes, half seconds, a max_push of
 // a quarter row (pushes are split, the rings wrap) — with the sample, row, position and score buffers allocated at
 // exactly their sizes (the rows at exactly rows_bound: an access past either end is the sanitizer's to report).  Every
-// chunking must give the first one's positions, scores and rows bit for bit; lag_rows = 64 must give the one-shot
+// push goes through HostLive::push, the interface and the splitting into segments of max_push that the C API uses;
+// pushes of 0 samples and one of more than max_push are among the chunkings.  Every chunking must give the first one's positions, scores and rows bit for bit; lag_rows = 64 must give the one-shot
 // tracker's (track_host on the twin's own F is not available here: the positions' steps are checked instead); the twin
 // itself refuses a read of a ring index that is not live.
 #include <algorithm>
@@ -103,26 +104,22 @@ struct Output {
 
 Output run(const tk::Design &d, const std::vector<float> &x, const std::vector<size_t> &sizes)
 {
-    tk::HostTrackStream hs(d);
+    tk::HostTrackStream twin(d);
+    st::HostLive &hs = twin;  // (what the C API holds)
     const st::Params &P = d.stream.P;
     Output out;
     size_t at = 0, k = 0;
     auto call = [&](size_t n, bool finish) {
-        const uint32_t cap =
-            tk::rows_bound(d.T, hs.record().m, tk::positions_final(d.T, st::work_count(P, hs.state().n_in + n, true)));
+        const uint32_t cap = hs.rows_bound(n);
+        expect(cap == tk::rows_bound(d.T, hs.track_record()->m, tk::positions_final(d.T, st::work_count(P, hs.state().n_in + n, true))),
+               "rows_bound is the tracker's");
         std::vector<float> rows(static_cast<size_t>(cap) * st::kPx), scores(cap);
         std::vector<uint64_t> pos(cap);
         std::vector<float> f(x.begin() + at, x.begin() + at + n);
         std::vector<int16_t> s(n);
         for (size_t i = 0; i < n; ++i) s[i] = static_cast<int16_t>(std::isfinite(f[i]) ? f[i] : 0.f);
         const char *src = P.s16 ? reinterpret_cast<const char *>(s.data()) : reinterpret_cast<const char *>(f.data());
-        const size_t es = P.s16 ? 2 : 4;
-        size_t done = 0;
-        do {
-            const size_t seg = std::min<size_t>(n - done, P.max_push);
-            hs.push_segment(src + done * es, seg, finish && done + seg == n, done == 0, rows.data(), pos.data(), scores.data(), cap);
-            done += seg;
-        } while (done < n);
+        hs.push(n ? src : nullptr, n, true, finish, rows.data(), pos.data(), scores.data(), cap);
         at += n;
         const st::State &r = hs.state();
         expect(r.status == 0, "no internal bound reached (reason " + std::to_string(r.reason) + ")");
@@ -140,7 +137,7 @@ Output run(const tk::Design &d, const std::vector<float> &x, const std::vector<s
     }
     call(0, true);
     out.last = hs.state();
-    out.rec = hs.record();
+    out.rec = *hs.track_record();
     return out;
 }
 
@@ -189,6 +186,11 @@ void chunkings(uint32_t rate, int format, uint32_t lag, bool nonfinite)
     if (lag <= 1) expect(one.last.work_len >= 2ull * small.stream.P.cap_f && one.last.work_len >= 2ull * small.T.cap_bp, tag + ": F and bp wrap");
     const Output o = run(small, x, {x.size() / 3, 5, x.size() / 2});
     expect(same_bits(o.rows, one.rows) && same_bits(o.scores, one.scores) && o.pos == one.pos, tag + ": quarter-row max_push");
+    // n above max_push (x.size() / 3 and x.size() / 2 are many segments each), n == 0 in the middle, and a push that is
+    // exactly max_push + 1 samples: one full segment and one of a single sample
+    expect(x.size() / 3 > 4 * static_cast<size_t>(ss.max_push), tag + ": pushes above max_push");
+    const Output e = run(small, x, {0, static_cast<size_t>(ss.max_push) + 1, 0, 0, x.size() / 2, 0});
+    expect(same_bits(e.rows, one.rows) && same_bits(e.scores, one.scores) && e.pos == one.pos, tag + ": max_push + 1 and empty pushes");
 }
 
 void refusals()
@@ -223,8 +225,8 @@ void refusals()
     tk::HostTrackStream hs(tk::design_tracked(&s, &ok, &ts, APTGPU_MODE_STRICT, false));
     std::vector<float> rows(64 * st::kPx), scores(64);
     std::vector<uint64_t> pos(64);
-    hs.push_segment(x.data(), x.size(), false, true, rows.data(), pos.data(), scores.data(), 64);
-    hs.push_segment(nullptr, 0, true, true, rows.data(), pos.data(), scores.data(), 64);
+    hs.push(x.data(), x.size(), true, false, rows.data(), pos.data(), scores.data(), 64);
+    hs.push(nullptr, 0, true, true, rows.data(), pos.data(), scores.data(), 64);
     expect(hs.state().status == 1 && hs.state().reason == tk::kReasonTooShort && hs.state().n_rows == 0, "too short");
 }
 
