@@ -11,35 +11,7 @@
 #include "apt_kernels_fused_variants.hpp"
 #include "apt_session.hpp"
 
-namespace {
-
 using namespace apt::capi;
-
-using PlanPtr = std::unique_ptr<aptgpu_plan, apt::capi::PlanDeleter>;
-
-
-apt::Signal download(const float *d, size_t n, hipStream_t s)
-{
-    apt::Signal h(n);
-    if (n) {
-        apt::hip_check(hipMemcpyAsync(h.data(), d, n * sizeof(float), hipMemcpyDeviceToHost, s),
-                       "hipMemcpyAsync D2H");
-        apt::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
-    }
-    return h;
-}
-
-const char *kTooShort = "Got less than 10 rows of samples, audio file is too short";
-const char *kFewSync = "Found less than 5 sync frames, audio file is too short or too noisy";
-const char *kNotMultiple = "work_rate is not multiple of FINAL_RATE";
-
-aptgpu_context default_ctx()
-{
-    aptgpu_context c{};
-    return c;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -299,292 +271,6 @@ int aptgpu_plan_read_internal(aptgpu_plan *plan, int i, const char *name, void *
         hipMemcpy(host_out, src, take, hipMemcpyDeviceToHost) != hipSuccess)
         return APTGPU_ERR_HIP;
     return APTGPU_OK;
-}
-
-// ------------------------------------------------------------------ decode()
-}  // extern "C"
-
-namespace apt::capi {
-
-// decode() on a host buffer: the f32 Signal, or (wav != nullptr) the payload of a WAV data chunk
-// that is uploaded as it is and converted on the device (wav.rs:30-51).
-int decode_host(const aptgpu_context *ctx_in, const aptgpu_settings *settings, const float *signal,
-                const uint8_t *wav_data, const apt::WavInfo *wav, size_t n, uint32_t input_rate_hz, int sync,
-                float **rows_out, size_t *n_out, aptgpu_stats *stats, char *err, size_t err_cap)
-{
-    *rows_out = nullptr;
-    *n_out = 0;
-    aptgpu_context ctx = ctx_in ? *ctx_in : default_ctx();
-    const bool steps = settings->export_wav != 0 && ctx.step != nullptr;
-
-    return guarded(err, err_cap, [&]() -> int {
-        const uint32_t work = settings->work_rate;
-        // decode.rs:59 (a WAV input is exported after its conversion, below)
-        if (!wav) step(&ctx, steps, "input", 0, signal, n, input_rate_hz);
-        // decode.rs:63
-        if (!wav || !steps) status(&ctx, 0.1f, "Resampling to " + std::to_string(work));
-
-        // The plan (designed taps, HBM workspace, streams) and the device input / output buffers come from the
-        // process-wide session cache (apt_session.hpp; SURVEY.md §8(b), threading row) unless the caller wants the
-        // step export (unfused kernels, every intermediate kept) or runs on a stream of their own: building and
-        // tearing them down cost 2 ms per call, as much as the PCIe time of a ten-minute recording.
-        const bool cached = !steps && ctx.stream == nullptr;
-        SessionLease lease;
-        struct PoisonOnThrow {  // a session that an exception left half-way through a call is not reused
-            SessionLease &l;
-            bool ok = false;
-            ~PoisonOnThrow() { if (!ok && l) l.poison(); }
-        } guard{lease};
-        hipStream_t s_for_errors = nullptr;
-        // decode()'s own per-recording errors (decode.rs:79-83,112-118,172-176) leave the GPU state perfectly valid:
-        // wait for what the call enqueued and hand the session back to the cache — only a HIP failure or an unknown
-        // exception poisons it
-        auto decode_error = [&](const char *msg) -> Error {
-            if (s_for_errors == nullptr || hipStreamSynchronize(s_for_errors) == hipSuccess) guard.ok = true;
-            return Error{ErrorKind::Internal, msg};
-        };
-        PlanPtr own_plan;
-        aptgpu_plan *plan = nullptr;
-        if (cached) {
-            SessionKey key;
-            key.device = ctx.device;
-            key.mode = ctx.mode;
-            key.rate = input_rate_hz;
-            key.sync = sync != 0;
-            key.per_call = 1;
-            key.settings = *settings;
-            key.settings.export_wav = 0;
-            key.settings.export_resample_filtered = settings->export_resample_filtered ? 1 : 0;  // another plan (dsp.rs:265-273)
-            lease = session_acquire(key, n);
-            plan = lease->plan.get();
-        } else {
-            own_plan.reset(apt::plan_create(&ctx, *settings, input_rate_hz, sync != 0, n, 1, /*depth*/ 1));
-            plan = own_plan.get();
-        }
-        if (plan->spr == 0) throw Error{ErrorKind::Invalid, "work_rate too small"};
-        hipStream_t s = plan->stream;  // a single-stream plan: every call runs on streams[0] == stream
-        s_for_errors = s;
-        const uint64_t w = plan->work_len_for(n);
-        const uint64_t out_cap =
-            sync ? (plan->spr ? w / plan->spr + 2 : 2) * 2080u : plan->out_len_nosync(w) + 16;
-
-        apt::DeviceBuffer<float> own_in, own_rows;
-        apt::DeviceBuffer<uint8_t> own_wav;
-        const size_t in_bytes = wav ? wav->data_len : n * sizeof(float);
-        void *d_in_ptr = nullptr;
-        float *d_rows_ptr = nullptr;
-        if (cached) {
-            lease->ensure_set(0, in_bytes + 64, out_cap);
-            d_in_ptr = lease->sets[0].in[0].ptr;
-            d_rows_ptr = lease->sets[0].out[0].ptr;
-        } else if (wav) {
-            own_wav.alloc(in_bytes + 16);
-            d_in_ptr = own_wav.ptr;
-        } else {
-            own_in.alloc(n + 16);
-            d_in_ptr = own_in.ptr;
-        }
-        if (!cached) {
-            own_rows.alloc(out_cap);
-            d_rows_ptr = own_rows.ptr;
-        }
-        struct { float *ptr; } d_rows{d_rows_ptr};
-        aptgpu_plan::Input in;
-        in.n = n;
-        in.ptr = d_in_ptr;
-        if (in_bytes)
-            apt::hip_check(hipMemcpyAsync(d_in_ptr, wav ? static_cast<const void *>(wav_data) : static_cast<const void *>(signal),
-                                          in_bytes, hipMemcpyHostToDevice, s), "hipMemcpyAsync H2D");
-        if (wav) {
-            in.channels = wav->channels;
-            in.bytes_per_sample = wav->bytes_per_sample;
-            in.codec = static_cast<int>(wav->codec);
-        }
-
-        float *rows_ptr = d_rows.ptr;
-        const uint64_t cap64 = out_cap;
-        plan->run_call(1, &in, &rows_ptr, &cap64, steps);
-        aptgpu_plan::Slot &sl = plan->slot_of(0);
-        if (steps) plan->sync_all();  // the step exports below read the slot's buffers
-        // (... F among them, as one contiguous signal: run_call's unfused kernels leave it so, never a k_fused launch)
-        if (steps && sl.f_stride != 0) throw Error{ErrorKind::Internal, "step export: F is in pixel-phase planes"};
-        if (wav && steps) {
-            apt::Signal x = download(sl.ingest.ptr, n, s);
-            step(&ctx, steps, "input", 0, x.data(), x.size(), input_rate_hz);
-            status(&ctx, 0.1f, "Resampling to " + std::to_string(work));
-        }
-
-        // The expanded signal of export_resample_filtered (n * l floats: gigabytes for a whole pass) on the device and on
-        // the host.  Where either allocation fails the step is delivered empty and the decode goes on — the reference logs
-        // "Expanded filtered signal can't fit in memory, skipping step" and does the same (dsp.rs:211-220).
-        auto export_expanded = [&](uint64_t cnt, uint32_t rate, auto &&fill) {
-            try {
-                apt::DeviceBuffer<float> d_ex;
-                d_ex.alloc(cnt + 16);
-                fill(d_ex.ptr);
-                apt::Signal ex = download(d_ex.ptr, cnt, s);
-                step(&ctx, steps, "resample_filtered", 0, ex.data(), ex.size(), rate);
-                return;
-            } catch (const Error &e) {
-                if (e.kind != ErrorKind::Hip || e.hip_code != static_cast<int>(hipErrorOutOfMemory)) throw;
-                (void)hipGetLastError();
-            } catch (const std::bad_alloc &) {
-            }
-            std::fprintf(stderr, "aptgpu: expanded filtered signal (%llu samples) can't fit in memory, skipping step\n",
-                         static_cast<unsigned long long>(cnt));
-            step(&ctx, steps, "resample_filtered", 0, nullptr, 0, rate);
-        };
-        // dsp.rs:96 / :106 — the resample filter, then the resample steps
-        step(&ctx, steps, "resample_filter", 1, plan->taps_resample.data(),
-             plan->taps_resample.size(), 0);
-        if (w < 10ull * plan->spr) throw decode_error(kTooShort);  // decode.rs:79-83
-        if (steps) {
-            if (plan->l > 1 && plan->export_filtered) {
-                // dsp.rs:269,281-285: every sum of the interpolated axis (gigabytes for a whole pass, as the
-                // reference's documentation warns)
-                const uint64_t cnt = apt::fast_resampling_export_geom(n, plan->l, plan->m, plan->taps_resample.size()).expanded;
-                export_expanded(cnt, input_rate_hz * plan->l, [&](float *d_ex) {
-                    plan->expanded_filtered(s, wav ? sl.ingest.ptr : static_cast<const float *>(d_in_ptr), n, false, d_ex, cnt);
-                });
-            } else if (plan->l > 1) {
-                // dsp.rs:281-285: expanded signal is empty unless export_resample_filtered
-                step(&ctx, steps, "resample_filtered", 0, nullptr, 0, input_rate_hz * plan->l);
-            } else {
-                // l == 1 (dsp.rs:106-116): filter() then decimate(); the step carries the filtered signal, at the input rate
-                apt::DeviceBuffer<float> d_fl;
-                d_fl.alloc(n + 16);
-                apt::gpu::fir_decimate(s, wav ? sl.ingest.ptr : static_cast<const float *>(d_in_ptr), n, plan->d_taps_resample.ptr,
-                                       static_cast<uint32_t>(plan->taps_resample.size()), 1, d_fl.ptr, n);
-                apt::Signal fl = download(d_fl.ptr, n, s);
-                step(&ctx, steps, "resample_filtered", 0, fl.data(), fl.size(), input_rate_hz);
-            }
-            apt::Signal r = download(sl.resampled.ptr, w, s);
-            step(&ctx, steps, "resample_decimated", 0, r.data(), r.size(), work);
-        }
-
-        status(&ctx, 0.4f, "Demodulating");  // decode.rs:87
-        if (steps) {
-            apt::Signal d = download(sl.demodulated.ptr, w, s);
-            step(&ctx, steps, "demodulation_result", 0, d.data(), d.size(), 0);
-        }
-        status(&ctx, 0.42f, "Filtering");  // decode.rs:93
-        apt::Signal filtered_host;
-        if (steps) {
-            step(&ctx, steps, "filter_filter", 1, plan->taps_lowpass.data(),
-                 plan->taps_lowpass.size(), 0);
-            filtered_host = download(sl.filtered.ptr, w, s);
-            step(&ctx, steps, "filter_result", 0, filtered_host.data(), filtered_host.size(), 0);
-        }
-
-        aptgpu_result res{};
-        if (sync) {
-            status(&ctx, 0.5f, "Syncing");  // decode.rs:107
-            if (!plan->work_is_multiple) throw decode_error(kNotMultiple);
-            if (steps) {
-                apt::Signal c = download(sl.correlation.ptr, w - plan->n_sync_taps, s);
-                step(&ctx, steps, "sync_correlation", 0, c.data(), c.size(), 0);
-            }
-            if (aptgpu_plan_results(plan, 1, &res) != APTGPU_OK)
-                throw Error{ErrorKind::Hip, "could not read the result record"};
-            if (res.n_sync < 5) throw decode_error(kFewSync);  // decode.rs:112-118
-            if (steps) {
-                // "sync_result": the aligned rows at work_rate (decode.rs:150)
-                apt::DeviceBuffer<float> d_al;
-                d_al.alloc(static_cast<uint64_t>(res.n_rows) * plan->spr + 16);
-                apt::gpu::gather_rows(s, sl.filtered.ptr, sl.peaks.ptr, plan->result_of(0), plan->spr,
-                                      1, true, d_al.ptr, res.n_rows);
-                apt::Signal al = download(d_al.ptr, static_cast<uint64_t>(res.n_rows) * plan->spr, s);
-                step(&ctx, steps, "sync_result", 0, al.data(), al.size(), work);
-                status(&ctx, 0.90f, "Resampling to 4160");
-                // final resample_with_filter(NoFilter), l == 1 branch (dsp.rs:106-122)
-                const float one = 1.f;
-                step(&ctx, steps, "resample_filter", 1, &one, 1, 0);
-                apt::gpu::gather_rows(s, sl.filtered.ptr, sl.peaks.ptr, plan->result_of(0), plan->spr,
-                                      1, false, d_al.ptr, res.n_rows);
-                al = download(d_al.ptr, static_cast<uint64_t>(res.n_rows) * plan->spr, s);
-                step(&ctx, steps, "filter_filter", 1, &one, 1, 0);
-                step(&ctx, steps, "filter_result", 0, al.data(), al.size(), 0);
-                step(&ctx, steps, "resample_filtered", 0, al.data(), al.size(), work);
-            } else {
-                status(&ctx, 0.90f, "Resampling to 4160");  // decode.rs:154
-            }
-        } else {
-            status(&ctx, 0.5f, "Skipping Syncing");  // decode.rs:136
-            step(&ctx, steps, "sync_correlation", 0, nullptr, 0, work);  // decode.rs:139
-            if (aptgpu_plan_results(plan, 1, &res) != APTGPU_OK)
-                throw Error{ErrorKind::Hip, "could not read the result record"};
-            if (steps) {
-                const uint64_t aligned = w / plan->spr * plan->spr;
-                step(&ctx, steps, "sync_result", 0, filtered_host.data(), aligned, work);
-                status(&ctx, 0.90f, "Resampling to 4160");
-                // final resample_with_filter(NoFilter) (decode.rs:158-159): the steps of dsp.rs:96-122
-                const float one = 1.f;
-                step(&ctx, steps, "resample_filter", 1, &one, 1, 0);
-                if (plan->l2 > 1 && plan->export_filtered) {
-                    const uint64_t cnt = apt::fast_resampling_export_geom(aligned, plan->l2, plan->m2, 1).expanded;
-                    export_expanded(cnt, work * plan->l2, [&](float *d_ex) { plan->expanded_filtered(s, sl.filtered.ptr, aligned, true, d_ex, cnt); });
-                } else if (plan->l2 > 1) {
-                    // fast_resampling: the expanded signal is empty unless export_resample_filtered
-                    step(&ctx, steps, "resample_filtered", 0, nullptr, 0, work * plan->l2);
-                } else {
-                    // filter([1.]): 0.0 + x*1.0, and nothing at all for sample 0 (the `i > j` guard)
-                    apt::DeviceBuffer<float> d_fl;
-                    d_fl.alloc(aligned + 16);
-                    apt::gpu::fir_decimate(s, sl.filtered.ptr, aligned, plan->d_one.ptr, 1, 1, d_fl.ptr, aligned);
-                    apt::Signal fl = download(d_fl.ptr, aligned, s);
-                    step(&ctx, steps, "filter_filter", 1, &one, 1, 0);
-                    step(&ctx, steps, "filter_result", 0, fl.data(), fl.size(), 0);
-                    step(&ctx, steps, "resample_filtered", 0, fl.data(), fl.size(), work);
-                }
-            } else {
-                status(&ctx, 0.90f, "Resampling to 4160");
-            }
-        }
-        if (res.status != APTGPU_OK)
-            throw decode_error(res.reason == 2 ? kFewSync : res.reason == 3 ? kNotMultiple : kTooShort);
-
-        float *rows = host_alloc<float>(res.n_out);
-        if (res.n_out) {
-            if (hipMemcpyAsync(rows, d_rows.ptr, res.n_out * sizeof(float), hipMemcpyDeviceToHost,
-                               s) != hipSuccess ||
-                hipStreamSynchronize(s) != hipSuccess) {
-                std::free(rows);
-                throw Error{ErrorKind::Hip, "D2H copy of the image rows failed"};
-            }
-        }
-        if (steps) step(&ctx, steps, "resample_decimated", 0, rows, res.n_out, apt::FINAL_RATE);
-        *rows_out = rows;
-        *n_out = res.n_out;
-        guard.ok = true;
-        if (stats) {
-            stats->work_len = w;
-            stats->n_sync = res.n_sync;
-            stats->n_rows = res.n_rows;
-            stats->l = plan->l;
-            stats->m = plan->m;
-            stats->n_resample_taps = static_cast<uint32_t>(plan->taps_resample.size());
-            stats->n_lowpass_taps = static_cast<uint32_t>(plan->taps_lowpass.size());
-            stats->fused = plan->fused();
-            stats->orbit_path = 1;
-        }
-        return APTGPU_OK;
-    });
-}
-
-}  // namespace apt::capi
-
-extern "C" {
-
-int aptgpu_decode(const aptgpu_context *ctx_in, const aptgpu_settings *settings,
-                  const float *signal, size_t n, uint32_t input_rate_hz, int sync,
-                  float **rows_out, size_t *n_out, aptgpu_stats *stats, char *err, size_t err_cap)
-{
-    if (!settings || (!signal && n) || !rows_out || !n_out) {
-        put_err(err, err_cap, "null argument");
-        return APTGPU_ERR_INVALID;
-    }
-    return apt::capi::decode_host(ctx_in, settings, signal, nullptr, nullptr, n, input_rate_hz, sync, rows_out,
-                                  n_out, stats, err, err_cap);
 }
 
 // ------------------------------------------------------------------ building blocks

@@ -460,24 +460,11 @@ void worker(Shared &sh, int device, std::vector<Item> items)
             max_bytes = std::max(max_bytes, it.bytes);
         }
         const int B = std::max(1, std::min<int>(sh.per_call, static_cast<int>(items.size())));
-        SessionKey key;
-        key.device = device;
-        key.mode = sh.mode;
-        key.rate = sh.rate;
-        key.sync = sh.sync;
-        key.per_call = B;
-        key.depth = Session::kSets;
-        key.settings = *sh.settings;
-        key.settings.export_wav = 0;
-        key.settings.export_resample_filtered = sh.settings->export_resample_filtered ? 1 : 0;  // another plan (dsp.rs:265-273)
+        const SessionKey key = SessionKey::of_decode(device, sh.mode, sh.rate, sh.sync, B, Session::kSets, *sh.settings);
         lease = session_acquire(key, max_n);
         Session &S = *lease;
         aptgpu_plan *plan = S.plan.get();
-        auto rows_bound = [&](uint64_t n) -> uint64_t {  // floats the rows of an n-sample recording can take
-            const uint64_t w = plan->work_len_for(n);
-            return sh.sync ? (plan->spr ? w / plan->spr + 2 : 2) * 2080u : plan->out_len_nosync(w) + 16;
-        };
-        const uint64_t out_cap = rows_bound(max_n);
+        const uint64_t out_cap = plan->rows_bound(max_n);
         const size_t n_chunks = (items.size() + static_cast<size_t>(B) - 1) / static_cast<size_t>(B);
         const int n_sets = static_cast<int>(std::min<size_t>(Session::kSets, n_chunks));
         for (int k = 0; k < n_sets; ++k) S.ensure_set(k, max_bytes + 64, out_cap);
@@ -527,14 +514,8 @@ void worker(Shared &sh, int device, std::vector<Item> items)
             std::vector<uint64_t> caps(static_cast<size_t>(cnt), s.out_cap);
             for (int b = 0; b < cnt; ++b) {
                 const Item &it = items[from + static_cast<size_t>(b)];
-                aptgpu_plan::Input &in = ins[static_cast<size_t>(b)];
-                in.ptr = s.in[static_cast<size_t>(b)].ptr;
-                in.n = it.n;
-                if (it.is_wav) {
-                    in.channels = it.wav.channels;
-                    in.bytes_per_sample = it.wav.bytes_per_sample;
-                    in.codec = static_cast<int>(it.wav.codec);
-                }
+                const void *d_in = s.in[static_cast<size_t>(b)].ptr;
+                ins[static_cast<size_t>(b)] = it.is_wav ? aptgpu_plan::Input::wav(d_in, it.n, it.wav) : aptgpu_plan::Input{d_in, it.n};
                 rows[static_cast<size_t>(b)] = s.out[static_cast<size_t>(b)].ptr;
             }
             hipStream_t next = plan->streams[static_cast<size_t>(plan->calls % plan->streams.size())];
@@ -554,14 +535,6 @@ void worker(Shared &sh, int device, std::vector<Item> items)
             bool locked = false;
         };
         std::vector<std::vector<Dest>> dests(n_chunks);
-        auto release_dests = [&](size_t c, bool free_rows) {
-            for (Dest &d : dests[c]) {
-                if (d.locked) (void)hipHostUnregister(d.rows);
-                d.locked = false;
-                if (free_rows && d.rows) std::free(d.rows);
-                if (free_rows) d.rows = nullptr;
-            }
-        };
         auto download = [&](size_t c) {
             IoSet &s = S.sets[c % Session::kSets];
             size_t from, to;
@@ -571,7 +544,7 @@ void worker(Shared &sh, int device, std::vector<Item> items)
             const auto a = clock::now();
             dests[c].resize(static_cast<size_t>(cnt));
             for (int b = 0; b < cnt; ++b) {
-                const uint64_t fl = std::min<uint64_t>(rows_bound(items[from + static_cast<size_t>(b)].n), s.out_cap);
+                const uint64_t fl = std::min<uint64_t>(plan->rows_bound(items[from + static_cast<size_t>(b)].n), s.out_cap);
                 Dest &d = dests[c][static_cast<size_t>(b)];
                 d.rows = static_cast<float *>(std::malloc((fl ? fl : 1) * sizeof(float)));
                 if (!d.rows) throw std::bad_alloc();
@@ -590,7 +563,7 @@ void worker(Shared &sh, int device, std::vector<Item> items)
                                                   hipMemcpyDeviceToHost, S.down), "hipMemcpyAsync results");
             }
             for (int b = 0; b < cnt; ++b) {
-                const uint64_t fl = std::min<uint64_t>(rows_bound(items[from + static_cast<size_t>(b)].n), s.out_cap);
+                const uint64_t fl = std::min<uint64_t>(plan->rows_bound(items[from + static_cast<size_t>(b)].n), s.out_cap);
                 Dest &d = dests[c][static_cast<size_t>(b)];
                 float *dst = d.locked ? d.rows : staging_rows(s, static_cast<size_t>(S.key.per_call)) + static_cast<size_t>(b) * s.out_cap;
                 apt::hip_check(hipMemcpyAsync(dst, s.out[static_cast<size_t>(b)].ptr, fl * sizeof(float), hipMemcpyDeviceToHost, S.down),
@@ -650,7 +623,6 @@ void worker(Shared &sh, int device, std::vector<Item> items)
                     }
             }
         } dest_guard{dests, S.down};
-        (void)release_dests;
 
         for (size_t c = 0; c < std::min<size_t>(2, n_chunks); ++c) upload(c);
         for (size_t c = 0; c < n_chunks; ++c) {

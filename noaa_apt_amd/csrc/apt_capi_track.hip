@@ -203,8 +203,6 @@ void run_host_arrays(const aptgpu_context *ctx, int count, const float *const *s
     apt::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
 }
 
-const char *kTooShort = "Got less than 10 rows of samples, audio file is too short";
-
 }  // namespace
 
 extern "C" {

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 
@@ -76,6 +77,40 @@ inline void step(const aptgpu_context *ctx, bool on, const char *id, int variant
         throw Error{ErrorKind::Internal, std::string("step callback failed at \"") + id + "\""};
 }
 
+// D2H into malloc'd memory, waited for: what the ABI hands out (aptgpu_free) and what a step callback reads
+inline float *download_malloc(const float *d, size_t n, hipStream_t s)
+{
+    float *p = host_alloc<float>(n);
+    if (n) {
+        if (hipMemcpyAsync(p, d, n * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess) {
+            std::free(p);
+            throw Error{ErrorKind::Hip, "D2H copy failed"};
+        }
+    }
+    return p;
+}
+struct HostFree {
+    void operator()(void *p) const { std::free(p); }
+};
+using HostSignal = std::unique_ptr<float, HostFree>;
+
+// A signal that a step carries: in HBM (downloaded for the callback) or on the host already.
+struct StepSignal {
+    const float *dev = nullptr, *host = nullptr;
+    uint64_t n = 0;
+    static StepSignal device(const float *d, uint64_t n) { return {d, nullptr, n}; }
+    static StepSignal on_host(const float *h, uint64_t n) { return {nullptr, h, n}; }
+};
+
+// Step::signal (context.rs) of such a signal
+inline void step_signal(const aptgpu_context *ctx, hipStream_t s, const char *id, StepSignal x, uint32_t rate)
+{
+    if (!ctx || !ctx->step) return;
+    HostSignal h(x.dev ? download_malloc(x.dev, x.n, s) : nullptr);
+    step(ctx, true, id, 0, x.dev ? h.get() : x.host, x.n, rate);
+}
+
 struct Scratch {
     int device;
     hipStream_t stream = nullptr;
@@ -107,38 +142,76 @@ struct Scratch {
                            "hipMemcpyAsync H2D");
         return d;
     }
-    float *download_malloc(const float *d, size_t n)
-    {
-        float *p = host_alloc<float>(n);
-        if (n) {
-            if (hipMemcpyAsync(p, d, n * sizeof(float), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-                hipStreamSynchronize(stream) != hipSuccess) {
-                std::free(p);
-                throw Error{ErrorKind::Hip, "D2H copy failed"};
-            }
-        }
-        return p;
-    }
+    float *download_malloc(const float *d, size_t n) { return apt::capi::download_malloc(d, n, stream); }
 };
 
+// The Context::step calls of one resample_with_filter stage, in the reference's order: "resample_filter" (dsp.rs:96 /
+// :106), "resample_filtered" (l > 1: fast_resampling's expanded signal, empty unless export_resample_filtered,
+// dsp.rs:269,281-285; l == 1: the filtered signal before its decimation, dsp.rs:108-114), "resample_decimated"
+// (dsp.rs:100-104,118-122).  The only place that delivers them: decode()'s two stages and the WAV tool's come here.
+//   x  the stage's input in HBM, from which one auxiliary launch computes the signal of "resample_filtered" — or, on
+//      the host, that signal itself where the caller has it already (decode()'s sync branch: gather_rows writes the rows
+//      as filter([1.]) leaves them)
+//   y  the stage's output, in HBM or on the host
+//   filter_steps  at l == 1 the reference's filter() also delivers "filter_filter" / "filter_result" (dsp.rs:407-408)
+//      ahead of "resample_filtered".  Here only decode()'s final stage does; its first stage and the WAV tool never have
+//      (a known deviation, pinned by test_first_resample_with_l_equal_1_delivers_the_filtered_signal and
+//      test_resample_tool_steps_and_flag).  Passing true there is the whole correction.
+inline void export_stage_steps(const aptgpu_context *ctx, hipStream_t s, const apt::ResampleStage &st, const apt::Signal &taps,
+                               uint32_t in_hz, uint32_t out_hz, StepSignal x, StepSignal y, bool filter_steps)
+{
+    if (!ctx || !ctx->step) return;
+    const apt::ResampleGeom &g = st.g;
+    step(ctx, true, "resample_filter", 1, taps.data(), taps.size(), 0);
+    HostSignal own;
+    StepSignal filtered = StepSignal::on_host(x.host, x.host ? x.n : 0);  // (empty: l > 1 without the flag)
+    if (x.dev && (g.l == 1 || g.flagged)) {
+        const uint64_t count = g.expanded_len(x.n);
+        auto compute = [&] {
+            apt::DeviceBuffer<float> d_f;
+            d_f.alloc(count + 16);
+            st.enqueue_filtered(s, x.dev, x.n, d_f.ptr);
+            own.reset(download_malloc(d_f.ptr, count, s));
+            filtered = StepSignal::on_host(own.get(), count);
+        };
+        // The expanded signal is n * l floats (gigabytes for a whole pass) on the device and on the host.  Where either
+        // allocation fails the step is delivered empty and the work goes on — the reference logs "Expanded filtered
+        // signal can't fit in memory, skipping step" and does the same (dsp.rs:211-220).  Nothing of the caller's runs
+        // inside the try: an exception from the step callback is the callback's.
+        if (g.l > 1) {
+            try {
+                compute();
+            } catch (const Error &e) {
+                if (e.kind != ErrorKind::Hip || e.hip_code != static_cast<int>(hipErrorOutOfMemory)) throw;
+                (void)hipGetLastError();
+            } catch (const std::bad_alloc &) {
+            }
+            if (!own)
+                std::fprintf(stderr, "aptgpu: expanded filtered signal (%llu samples) can't fit in memory, skipping step\n",
+                             static_cast<unsigned long long>(count));
+        } else {
+            compute();
+        }
+    }
+    if (g.l == 1 && filter_steps) {
+        step(ctx, true, "filter_filter", 1, taps.data(), taps.size(), 0);
+        step(ctx, true, "filter_result", 0, filtered.host, filtered.n, 0);
+    }
+    step(ctx, true, "resample_filtered", 0, filtered.host, filtered.n, g.filtered_rate(in_hz));
+    step_signal(ctx, s, "resample_decimated", y, out_hz);
+}
+
 // resample_with_filter (dsp.rs:62-126) on a signal already in HBM; returns the output length.
-// steps_ctx (nullable; used when it has a step callback): the Context::step calls of dsp.rs:96-122 and of
-// fast_resampling (:281-285) in the reference's order.  export_filtered: context.export_resample_filtered — the other
-// decimation phase of fast_resampling (dsp.rs:265-273) and, with steps, the expanded signal.
+// steps_ctx (nullable; used when it has a step callback): the stage's Context::step calls.  export_filtered:
+// context.export_resample_filtered — the other decimation phase of fast_resampling (dsp.rs:265-273) and, with steps, the
+// expanded signal.
 inline uint64_t resample_device(Scratch &sc, const float *d_x, size_t n, uint32_t in_hz, uint32_t out_hz,
                                 apt::Filter &filt, apt::DeviceBuffer<float> &d_y, bool export_filtered = false,
                                 const aptgpu_context *steps_ctx = nullptr)
 {
     if (out_hz == 0) throw Error{ErrorKind::Internal, "Can't resample to 0Hz"};  // dsp.rs:69-71
-    const bool on = steps_ctx && steps_ctx->step;
     const apt::Rate in_rate = apt::Rate::hz(in_hz), out_rate = apt::Rate::hz(out_hz);
     const apt::LM lm = apt::interpolation_factors(in_rate, out_rate);
-    auto export_signal = [&](const char *id, const float *d, uint64_t count, uint32_t rate) {
-        float *h = sc.download_malloc(d, count);
-        struct Free { float *p; ~Free() { std::free(p); } } guard{h};
-        step(steps_ctx, on, id, 0, h, count, rate);
-    };
-    uint64_t w;
     if (lm.l > 1) {
         apt::Rate interpolated{};
         if (!in_rate.checked_mul(lm.l, &interpolated)) {
@@ -151,61 +224,25 @@ inline uint64_t resample_device(Scratch &sc, const float *d_x, size_t n, uint32_
             throw Error{ErrorKind::RateOverflow, buf};
         }
         filt.resample(in_rate, interpolated);
-        const apt::Signal coeff = filt.design();
-        const uint32_t ntaps = static_cast<uint32_t>(coeff.size());
-        step(steps_ctx, on, "resample_filter", 1, coeff.data(), coeff.size(), 0);  // dsp.rs:96
-        auto d_c = sc.upload(coeff.data(), coeff.size());
-        if (export_filtered) {
-            const apt::ExportGeom g = apt::fast_resampling_export_geom(n, lm.l, lm.m, coeff.size());
-            w = g.count;
-            d_y.alloc(w + 16);
-            apt::resample_at(sc.stream, d_x, n, d_c.ptr, ntaps, lm.l, g.d0, lm.m, d_y.ptr, w);
-            if (on) {  // dsp.rs:269,281-285; where the n * l floats do not fit: an empty step, as dsp.rs:211-220 skips it
-                bool done = false;
-                try {
-                    apt::DeviceBuffer<float> d_ex;
-                    d_ex.alloc(g.expanded + 16);
-                    apt::resample_at(sc.stream, d_x, n, d_c.ptr, ntaps, lm.l, 0, 1, d_ex.ptr, g.expanded);
-                    export_signal("resample_filtered", d_ex.ptr, g.expanded, in_hz * lm.l);
-                    done = true;
-                } catch (const Error &e) {
-                    if (e.kind != ErrorKind::Hip || e.hip_code != static_cast<int>(hipErrorOutOfMemory)) throw;
-                    (void)hipGetLastError();
-                } catch (const std::bad_alloc &) {
-                }
-                if (!done) {
-                    std::fprintf(stderr, "aptgpu: expanded filtered signal (%llu samples) can't fit in memory, skipping step\n",
-                                 static_cast<unsigned long long>(g.expanded));
-                    step(steps_ctx, on, "resample_filtered", 0, nullptr, 0, in_hz * lm.l);
-                }
-            }
-        } else {
-            w = apt::fast_resampling_len(n, lm.l, lm.m, coeff.size());
-            d_y.alloc(w + 16);
-            apt::gpu::resample_generic(sc.stream, d_x, n, d_c.ptr, ntaps, lm.l, lm.m, d_y.ptr, w);
-            step(steps_ctx, on, "resample_filtered", 0, nullptr, 0, in_hz * lm.l);  // empty unless exporting it
-        }
-        apt::hip_check(hipStreamSynchronize(sc.stream), "hipStreamSynchronize");  // d_c goes out of scope
-    } else {
-        const apt::Signal coeff = filt.design();
-        step(steps_ctx, on, "resample_filter", 1, coeff.data(), coeff.size(), 0);  // dsp.rs:106
-        w = n / lm.m;
-        auto d_c = sc.upload(coeff.data(), coeff.size());
-        d_y.alloc(w + 16);
-        if (on) {  // dsp.rs:108-114: the filtered signal before the decimation
-            apt::DeviceBuffer<float> d_f;
-            d_f.alloc(n + 16);
-            apt::gpu::fir_decimate(sc.stream, d_x, n, d_c.ptr, static_cast<uint32_t>(coeff.size()), 1, d_f.ptr, n);
-            export_signal("resample_filtered", d_f.ptr, n, in_hz);
-        }
-        apt::gpu::fir_decimate(sc.stream, d_x, n, d_c.ptr, static_cast<uint32_t>(coeff.size()), lm.m, d_y.ptr, w);
-        apt::hip_check(hipStreamSynchronize(sc.stream), "hipStreamSynchronize");
     }
-    if (on) export_signal("resample_decimated", d_y.ptr, w, out_hz);  // dsp.rs:100-104,118-122
+    const apt::Signal coeff = filt.design();
+    auto d_c = sc.upload(coeff.data(), coeff.size());
+    const apt::ResampleStage st{{lm.l, lm.m, coeff.size(), export_filtered}, d_c.ptr};
+    const uint64_t w = st.g.out_len(n);
+    d_y.alloc(w + 16);
+    st.enqueue(sc.stream, d_x, n, d_y.ptr, w);
+    export_stage_steps(steps_ctx, sc.stream, st, coeff, in_hz, out_hz, StepSignal::device(d_x, n),
+                       StepSignal::device(d_y.ptr, w), /*filter_steps*/ false);
+    apt::hip_check(hipStreamSynchronize(sc.stream), "hipStreamSynchronize");  // d_c goes out of scope
     return w;
 }
 
-// apt_capi.hip
+// decode()'s own errors (decode.rs:79-83,112-118,172-176)
+inline constexpr const char *kTooShort = "Got less than 10 rows of samples, audio file is too short";
+inline constexpr const char *kFewSync = "Found less than 5 sync frames, audio file is too short or too noisy";
+inline constexpr const char *kNotMultiple = "work_rate is not multiple of FINAL_RATE";
+
+// apt_capi_decode.hip
 int decode_host(const aptgpu_context *ctx_in, const aptgpu_settings *settings, const float *signal,
                 const uint8_t *wav_data, const apt::WavInfo *wav, size_t n, uint32_t input_rate_hz, int sync,
                 float **rows_out, size_t *n_out, aptgpu_stats *stats, char *err, size_t err_cap);

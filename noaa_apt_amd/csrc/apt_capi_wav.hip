@@ -129,12 +129,7 @@ std::vector<uint8_t> resample_wav_impl(const aptgpu_context *ctx, const uint8_t 
     d_sig.alloc(w.n_frames + 16);
     apt::gpu::wav_to_signal(sc.stream, d_raw.ptr, w.n_frames, w.channels, w.bytes_per_sample,
                             static_cast<int>(w.codec), d_sig.ptr);
-    if (ctx && ctx->step) {  // resample.rs:31
-        float *x = sc.download_malloc(d_sig.ptr, w.n_frames);
-        const int rc = ctx->step("input", 0, x, w.n_frames, w.sample_rate, ctx->user);
-        std::free(x);
-        if (rc != 0) throw Error{ErrorKind::Internal, "step callback failed at \"input\""};
-    }
+    step_signal(ctx, sc.stream, "input", StepSignal::device(d_sig.ptr, w.n_frames), w.sample_rate);  // resample.rs:31
     status(ctx, 0.2f, "Resampling to " + std::to_string(output_rate));  // resample.rs:34
     if (w.sample_rate == 0) throw Error{ErrorKind::Invalid, "input_rate is 0"};
     // dsp::resample, dsp.rs:132-162
@@ -314,12 +309,7 @@ int aptgpu_plan_decode_device_wav(aptgpu_plan *plan, int count, const void *cons
         std::vector<aptgpu_plan::Input> ins(static_cast<size_t>(count));
         std::vector<uint64_t> caps(static_cast<size_t>(count));
         for (int i = 0; i < count; ++i) {
-            aptgpu_plan::Input &in = ins[static_cast<size_t>(i)];
-            in.ptr = d_data[i];
-            in.n = specs[i].n_frames;
-            in.channels = specs[i].channels;
-            in.bytes_per_sample = specs[i].bytes_per_sample;
-            in.codec = specs[i].codec;
+            ins[static_cast<size_t>(i)] = aptgpu_plan::Input::wav(d_data[i], specs[i].n_frames, specs[i]);
             caps[static_cast<size_t>(i)] = static_cast<uint64_t>(rows_cap[i]) * 2080u;
         }
         plan->run_call(count, ins.data(), d_rows, caps.data(), false);

@@ -170,29 +170,29 @@ LM interpolation_factors(Rate input_rate, Rate output_rate)
     return LM{output_rate.get_hz() / g, input_rate.get_hz() / g};
 }
 
-uint64_t fast_resampling_len(uint64_t n, uint32_t l, uint32_t m, uint64_t ntaps)
+uint64_t ResampleGeom::expanded_len(uint64_t n) const
 {
-    const uint64_t off = (ntaps - 1) / 2;
-    const uint64_t total = n * l;
-    if (total <= off) return 0;
-    return (total - off + m - 1) / m;
+    if (l == 1) return n;
+    const uint64_t off = (ntaps - 1) / 2, total = n * l;
+    return total > off ? total - off : 0;
 }
 
-// fast_resampling with context.export_resample_filtered set (dsp.rs:265-273): t walks the interpolated axis one
-// by one from `off`, and the output keeps the sums whose t + 1 is a multiple of m, i.e. t = j*m - 1 for
-// ceil((off + 1) / m) <= j <= n*l / m.
-ExportGeom fast_resampling_export_geom(uint64_t n, uint32_t l, uint32_t m, uint64_t ntaps)
+uint64_t ResampleGeom::d0(uint64_t n) const
 {
-    ExportGeom g{0, 0, 0};
+    if (l == 1 || !flagged || expanded_len(n) == 0) return 0;
     const uint64_t off = (ntaps - 1) / 2;
-    const uint64_t total = n * l;
-    if (total <= off) return g;
-    g.expanded = total - off;
-    const uint64_t j0 = (off + m) / m;
-    const uint64_t j1 = total / m;
-    g.d0 = j0 * m - 1 - off;
-    g.count = j1 >= j0 ? j1 - j0 + 1 : 0;
-    return g;
+    return (off + m) / m * m - 1 - off;
+}
+
+uint64_t ResampleGeom::out_len(uint64_t n) const
+{
+    if (l == 1) return n / m;  // decimate, dsp.rs:299-303
+    const uint64_t ex = expanded_len(n);
+    if (ex == 0) return 0;
+    if (!flagged) return (ex + m - 1) / m;
+    const uint64_t off = (ntaps - 1) / 2;
+    const uint64_t j0 = (off + m) / m, j1 = n * l / m;
+    return j1 >= j0 ? j1 - j0 + 1 : 0;
 }
 
 }  // namespace apt

@@ -115,14 +115,19 @@ struct LM {
 };
 LM interpolation_factors(Rate input_rate, Rate output_rate);
 
-// Number of outputs fast_resampling produces (dsp.rs:226-277):
-// t = off, off+m, ... while t < n*l.
-uint64_t fast_resampling_len(uint64_t n, uint32_t l, uint32_t m, uint64_t ntaps);
-// The other branch of the same loop (context.export_resample_filtered, dsp.rs:265-273): the output is taken at
-// t = off + d0 + k*m, k < count, and `expanded` sums (every t in [off, n*l)) go to the "resample_filtered" step.
-struct ExportGeom {
-    uint64_t d0, count, expanded;
+// The lengths and positions of one resample_with_filter stage (dsp.rs:62-126) over an n-sample input: l > 1 is
+// fast_resampling (dsp.rs:186-289), whose loop walks t of the interpolated axis from off = (ntaps - 1) / 2 while
+// t < n*l; l == 1 is filter() + decimate() (dsp.rs:106-122, :299-303).  flagged: context.export_resample_filtered —
+// fast_resampling then evaluates every t and keeps the sums whose t + 1 is a multiple of m (dsp.rs:265-273), i.e.
+// t = j*m - 1 for ceil((off + 1) / m) <= j <= n*l / m, instead of t = off + k*m; at l == 1 the flag changes nothing.
+struct ResampleGeom {
+    uint32_t l = 1, m = 1;
+    uint64_t ntaps = 1;
+    bool flagged = false;
+    uint64_t out_len(uint64_t n) const;       // samples the stage produces
+    uint64_t d0(uint64_t n) const;            // the output is taken at t = off + d0 + k*m; 0 unless flagged and l > 1
+    uint64_t expanded_len(uint64_t n) const;  // l > 1: every sum t in [off, n*l); l == 1: the filtered signal, n
+    uint32_t filtered_rate(uint32_t in_hz) const { return in_hz * l; }  // rate of that signal (dsp.rs:110-114,281-285)
 };
-ExportGeom fast_resampling_export_geom(uint64_t n, uint32_t l, uint32_t m, uint64_t ntaps);
 
 }  // namespace apt

@@ -355,30 +355,12 @@ void aptgpu_plan::upload_slot_table()
     apt::hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
 }
 
-// ------------------------------------------------------------------ geometry
-uint64_t aptgpu_plan::work_len_for(uint64_t n) const
-{
-    if (l > 1)
-        return export_filtered ? apt::fast_resampling_export_geom(n, l, m, taps_resample.size()).count
-                               : apt::fast_resampling_len(n, l, m, taps_resample.size());
-    return n / m;  // decimate, dsp.rs:299-303
-}
-
-uint64_t aptgpu_plan::out_len_nosync(uint64_t work_len) const
-{
-    const uint64_t aligned = spr ? work_len / spr * spr : 0;  // decode.rs:142-147
-    if (l2 > 1)
-        return export_filtered ? apt::fast_resampling_export_geom(aligned, l2, m2, 1).count
-                               : apt::fast_resampling_len(aligned, l2, m2, 1);
-    return aligned / m2;
-}
-
 // ------------------------------------------------------- export_resample_filtered
 // fast_resampling (dsp.rs:186-289) evaluated at t = off + d0 + k*step of the interpolated axis: the window of
 // such a t starts at the first multiple of l at or after t - off = d (:237-248), input x0 = ceil(d / l), tap
 // p = x0*l - d, then taps p + i*l while they stay <= 2*off (:254); inputs at or beyond n are skipped (:257).
 // step == m, d0 == 0 is the normal branch (k_resample_generic); the export branch (:265-273) needs d0 =
-// fast_resampling_export_geom().d0 for the output and step == 1 for the expanded signal.  Only this mode uses the
+// ResampleGeom::d0 for the output and step == 1 for the expanded signal.  Only this mode uses the
 // kernel, which is why it lives beside the plan and not with the hot kernels.
 namespace {
 __global__ void __launch_bounds__(256)
@@ -410,15 +392,43 @@ void resample_at(hipStream_t s, const float *x, uint64_t n, const float *coeff, 
                        out, w);
 }
 }  // namespace apt
-using apt::resample_at;
 
-void aptgpu_plan::expanded_filtered(hipStream_t s, const float *d_x, uint64_t n, bool final_stage, float *d_out,
-                                    uint64_t count)
+// ------------------------------------------------------- one resample_with_filter stage
+namespace apt {
+// resample_with_filter's choice (dsp.rs:77-124) among the kernels that compute it
+ResampleStage::Kernel ResampleStage::kernel() const
 {
-    if (final_stage) resample_at(s, d_x, n, d_one.ptr, 1, l2, 0, 1, d_out, count);
-    else resample_at(s, d_x, n, d_taps_resample.ptr, static_cast<uint32_t>(taps_resample.size()), l, 0, 1, d_out, count);
-    apt::hip_check(hipGetLastError(), "kernel launch (expanded signal)");
+    if (g.l == 1) return kFirDecimate;  // filter + decimate
+    if (g.flagged) return kResampleAt;  // fast_resampling's other decimation phase (dsp.rs:265-273)
+    return d_taps_f16 ? kResampleF16Taps : kResampleGeneric;
 }
+
+const char *ResampleStage::label(bool final_stage) const
+{
+    static const char *const first[] = {"resample_generic", "resample_f16taps", "resample_generic", "fir_decimate"};
+    static const char *const last[] = {"final_resample", "final_resample", "final_resample", "final_decimate"};
+    return (final_stage ? last : first)[kernel()];
+}
+
+void ResampleStage::enqueue(hipStream_t s, const float *d_x, uint64_t n, float *d_out, uint64_t w) const
+{
+    const uint32_t t = static_cast<uint32_t>(g.ntaps);
+    switch (kernel()) {
+        case kResampleAt: resample_at(s, d_x, n, d_taps, t, g.l, g.d0(n), g.m, d_out, w); break;
+        case kResampleF16Taps: gpu::resample_f16taps(s, d_x, n, d_taps_f16, t, g.l, g.m, f16_unscale, d_out, w); break;
+        case kResampleGeneric: gpu::resample_generic(s, d_x, n, d_taps, t, g.l, g.m, d_out, w); break;
+        case kFirDecimate: gpu::fir_decimate(s, d_x, n, d_taps, t, g.m, d_out, w); break;
+    }
+}
+
+void ResampleStage::enqueue_filtered(hipStream_t s, const float *d_x, uint64_t n, float *d_out) const
+{
+    const uint32_t t = static_cast<uint32_t>(g.ntaps);
+    if (g.l > 1) resample_at(s, d_x, n, d_taps, t, g.l, 0, 1, d_out, g.expanded_len(n));
+    else gpu::fir_decimate(s, d_x, n, d_taps, t, 1, d_out, n);
+    hip_check(hipGetLastError(), "kernel launch (resample_filtered step)");
+}
+}  // namespace apt
 
 void aptgpu_plan::sync_all()
 {
@@ -614,22 +624,8 @@ void aptgpu_plan::run_call(int count, const Input *ins, float *const *d_rows, co
                 sl.demodulated.alloc(max_work_len + 64);
             }
             // 1. resample to work_rate (dsp.rs:62-126)
-            if (l > 1 && export_filtered) {
-                const uint64_t d0 = apt::fast_resampling_export_geom(n, l, m, t1).d0;
-                timed("resample_generic", [&] { resample_at(cur, d_signal, n, d_taps_resample.ptr, t1, l, d0, m, sl.resampled.ptr, w); });
-            } else if (l > 1 && mode == APTGPU_MODE_FP16_TAPS) {
-                timed("resample_f16taps", [&] {
-                    resample_f16taps(cur, d_signal, n, d_taps_f16.ptr, t1, l, m, f16_unscale, sl.resampled.ptr, w);
-                });
-            } else if (l > 1) {
-                timed("resample_generic", [&] {
-                    resample_generic(cur, d_signal, n, d_taps_resample.ptr, t1, l, m, sl.resampled.ptr, w);
-                });
-            } else {
-                timed("fir_decimate", [&] {
-                    fir_decimate(cur, d_signal, n, d_taps_resample.ptr, t1, m, sl.resampled.ptr, w);
-                });
-            }
+            const apt::ResampleStage st = first_stage();
+            timed(st.label(false), [&] { st.enqueue(cur, d_signal, n, sl.resampled.ptr, w); });
             // 2. AM envelope (dsp.rs:350-383)
             timed("demodulate", [&] { demodulate(cur, sl.resampled.ptr, w, cosphi2, sinphi, sl.demodulated.ptr); });
             // 3. low-pass (dsp.rs:386-410)
@@ -722,21 +718,10 @@ void aptgpu_plan::run_call(int count, const Input *ins, float *const *d_rows, co
             // that is no multiple of 4160 Hz — has no k_fused instantiation)
             if (sl.f_stride != 0) throw apt::Error{apt::ErrorKind::Internal, "no-sync tail: F is in pixel-phase planes"};
             const uint64_t w = wlen[static_cast<size_t>(i)];
-            const uint64_t aligned = w / spr * spr;
             uint64_t n_out = out_len_nosync(w);
             if (n_out > rows_cap_floats[i]) n_out = rows_cap_floats[i];
-            if (l2 > 1 && export_filtered) {
-                const uint64_t d0 = apt::fast_resampling_export_geom(aligned, l2, m2, 1).d0;
-                timed("final_resample", [&] { resample_at(cur, sl.filtered.ptr, aligned, d_one.ptr, 1, l2, d0, m2, d_rows[i], n_out); });
-            } else if (l2 > 1) {
-                timed("final_resample", [&] {
-                    resample_generic(cur, sl.filtered.ptr, aligned, d_one.ptr, 1, l2, m2, d_rows[i], n_out);
-                });
-            } else {
-                timed("final_decimate", [&] {
-                    fir_decimate(cur, sl.filtered.ptr, aligned, d_one.ptr, 1, m2, d_rows[i], n_out);
-                });
-            }
+            const apt::ResampleStage st = final_stage();
+            timed(st.label(true), [&] { st.enqueue(cur, sl.filtered.ptr, whole_rows(w), d_rows[i], n_out); });
             set_result(cur, d_results.ptr + slot0 + i,
                        Result{APTGPU_OK, 0, static_cast<uint32_t>(n_out / 2080u), 0, w, n_out});
         }

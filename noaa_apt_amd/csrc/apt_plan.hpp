@@ -90,10 +90,31 @@ private:
 
 namespace apt {
 // fast_resampling (dsp.rs:186-289) evaluated at t = off + d0 + k*step of the interpolated axis, k < w (apt_plan.hip):
-// the export_resample_filtered branch (dsp.rs:265-273) — d0 from fast_resampling_export_geom and step = m for the output,
-// d0 = 0 and step = 1 for the expanded signal
+// the export_resample_filtered branch (dsp.rs:265-273) — d0 = ResampleGeom::d0 and step = m for the output, d0 = 0 and
+// step = 1 for the expanded signal
 void resample_at(hipStream_t s, const float *x, uint64_t n, const float *coeff, uint32_t ntaps, uint32_t l, uint64_t d0,
                  uint32_t step, float *out, uint64_t w);
+
+// One resample_with_filter stage (dsp.rs:62-126) on the device: its geometry, its taps in HBM and the fp16-taps option.
+// decode()'s first resample, its final resample to 4160 Hz (NoFilter: one tap) and the WAV tool's are each one of these.
+struct ResampleStage {
+    ResampleGeom g;
+    const float *d_taps = nullptr;
+    const uint16_t *d_taps_f16 = nullptr;  // APTGPU_MODE_FP16_TAPS tables (apt::gpu::f16taps_pack), else null
+    float f16_unscale = 1.f;
+    // the name of enqueue()'s kernel in a plan's timing (aptgpu_plan_collect_timing): of decode()'s first stage, or of
+    // its final one
+    const char *label(bool final_stage) const;
+    // the stage's output: the first w <= g.out_len(n) samples into d_out
+    void enqueue(hipStream_t s, const float *d_x, uint64_t n, float *d_out, uint64_t w) const;
+    // the signal of the stage's "resample_filtered" step, g.expanded_len(n) samples into d_out: the expanded signal
+    // (l > 1: dsp.rs:269,281-285) or the filtered one before its decimation (l == 1: dsp.rs:108-114)
+    void enqueue_filtered(hipStream_t s, const float *d_x, uint64_t n, float *d_out) const;
+
+private:
+    enum Kernel { kResampleAt, kResampleF16Taps, kResampleGeneric, kFirDecimate };
+    Kernel kernel() const;
+};
 }  // namespace apt
 
 // The opaque C-ABI plan: the host-side design of decode() (apt::PlanDesign: l, m, the taps, the sync geometry ...) and
@@ -263,18 +284,28 @@ struct aptgpu_plan : apt::PlanDesign {
 
     apt::KernelTimer timer;
 
-    // geometry for an n-sample recording
-    uint64_t work_len_for(uint64_t n) const;
-    uint64_t out_len_nosync(uint64_t work_len) const;
-
     // Settings.export_resample_filtered (config.rs:83 -> context.rs:113): fast_resampling then walks every t of the
     // interpolated axis and decimates at (t + 1) % m == 0 (dsp.rs:265-273) — another phase than the t = off + k*m of
     // the normal branch, whether or not anything is exported.  Such a plan runs the unfused kernels.
     bool export_filtered = false;
-    // the "resample_filtered" step of that mode (dsp.rs:269,281-285): every sum of the interpolated axis from t = off
-    // on, `count` of them into d_out; final_stage: the NoFilter resample to 4160 Hz (decode.rs:158-159) instead of
-    // the first one
-    void expanded_filtered(hipStream_t s, const float *d_x, uint64_t n, bool final_stage, float *d_out, uint64_t count);
+    // decode()'s two resample_with_filter stages: input rate -> work_rate, and (no-sync: decode.rs:158-159) the whole
+    // rows at work_rate -> 4160 Hz with NoFilter
+    apt::ResampleStage first_stage() const
+    {
+        return {{l, m, taps_resample.size(), export_filtered}, d_taps_resample.ptr, d_taps_f16.ptr, f16_unscale};
+    }
+    apt::ResampleStage final_stage() const { return {{l2, m2, 1, export_filtered}, d_one.ptr, nullptr, 1.f}; }
+
+    // geometry for an n-sample recording
+    uint64_t work_len_for(uint64_t n) const { return first_stage().g.out_len(n); }
+    uint64_t whole_rows(uint64_t work_len) const { return spr ? work_len / spr * spr : 0; }  // decode.rs:142-147
+    uint64_t out_len_nosync(uint64_t work_len) const { return final_stage().g.out_len(whole_rows(work_len)); }
+    // floats the rows of an n-sample recording can take (what a rows buffer for it holds)
+    uint64_t rows_bound(uint64_t n) const
+    {
+        const uint64_t w = work_len_for(n);
+        return sync ? (spr ? w / spr + 2 : 2) * 2080u : out_len_nosync(w) + 16;
+    }
 
     // what a recording looks like in HBM: the f32 Signal (codec < 0), or the payload of a WAV
     // data chunk (codec = apt::WavCodec) that is converted on the device — inside the fused
@@ -284,6 +315,12 @@ struct aptgpu_plan : apt::PlanDesign {
         uint64_t n = 0;  // samples of the Signal == WAV frames
         uint32_t channels = 1, bytes_per_sample = 4;
         int codec = -1;
+        // from what describes a WAV payload: apt::WavInfo, or the C ABI's aptgpu_wav_spec
+        template <typename Wav>
+        static Input wav(const void *data, uint64_t n_frames, const Wav &w)
+        {
+            return {data, n_frames, w.channels, w.bytes_per_sample, static_cast<int>(w.codec)};
+        }
     };
     // enqueue the whole decode() of the `count` device-resident recordings of one call (count <=
     // max_batch) on the next stream; never synchronises with the host.  keep_steps: unfused kernels,

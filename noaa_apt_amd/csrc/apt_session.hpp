@@ -30,6 +30,15 @@ struct SessionKey {
     int depth = 1;  // calls in flight the plan is built for: 1 (aptgpu_decode: one stream, `plan->stream`), kSets (batch workers)
     aptgpu_settings settings{};  // the five fields decode() reads + export_resample_filtered (it changes the plan); export_wav zeroed
     bool operator==(const SessionKey &o) const;
+    // the key of a decode under `s`: the step export never comes from the cache, and any nonzero
+    // export_resample_filtered is the one other plan (dsp.rs:265-273)
+    static SessionKey of_decode(int device, int mode, uint32_t rate, bool sync, int per_call, int depth, const aptgpu_settings &s)
+    {
+        SessionKey k{device, mode, rate, sync, per_call, depth, s};
+        k.settings.export_wav = 0;
+        k.settings.export_resample_filtered = s.export_resample_filtered ? 1 : 0;
+        return k;
+    }
 };
 
 struct PlanDeleter {

@@ -194,3 +194,77 @@ def test_first_resample_with_l_equal_1_delivers_the_filtered_signal(oracle, flag
     first = [g for g in got if g[0] == "resample_filtered"][0]
     assert first[2] == 24960 and first[1].size == x.size
     assert_bitexact(first[1], st["expanded1"], "filtered signal of the l == 1 branch")
+
+
+# ---- the complete step sequence of decode(): (id, variant, rate, length) of every Context::step call, in order, for
+# both values of the flag.  The lists are literal; a length is the name of the oracle array the step carries ("x": the
+# input, "rows": decode()'s result, 0 / 1: that many samples) — except the filtered signal of an l == 1 stage, which the
+# oracle hands out only with the flag set and whose length is the stage's input (dsp.rs:108-114).
+# Read off dsp.rs:96-122,281-285,381,407-408 and decode.rs:59-159; the first stage at l == 1 leaves out the
+# "filter_filter" / "filter_result" pair of filter() (the deviation test_first_resample_with_l_equal_1_... pins).
+_DEMOD_FILTER = [("demodulation_result", 0, None, "demodulated"), ("filter_filter", 1, None, "filter_filter"),
+                 ("filter_result", 0, None, "filtered")]
+_SYNC = [("sync_correlation", 0, None, "correlation"), ("sync_result", 0, 12480, "aligned")]
+_NOSYNC = [("sync_correlation", 0, 12480, 0), ("sync_result", 0, 12480, "aligned")]
+# the final resample_with_filter(NoFilter) of a work rate that 4160 divides: l == 1, filter([1.]) + decimate
+_FINAL_L1 = [("resample_filter", 1, None, 1), ("filter_filter", 1, None, 1), ("filter_result", 0, None, "aligned"),
+             ("resample_filtered", 0, 12480, "aligned"), ("resample_decimated", 0, 4160, "rows")]
+_FIRST_48K = [("input", 0, 48000, "x"), ("resample_filter", 1, None, "resample_filter"),
+              ("resample_filtered", 0, 48000 * 13, "expanded1"), ("resample_decimated", 0, 12480, "resampled")]
+STEP_SEQUENCES = {
+    (48000, 12480, True): _FIRST_48K + _DEMOD_FILTER + _SYNC + _FINAL_L1,
+    (48000, 12480, False): _FIRST_48K + _DEMOD_FILTER + _NOSYNC + _FINAL_L1,
+    # first stage l == 1 (m == 2): the filtered signal, at the input rate
+    (24960, 12480, True): [("input", 0, 24960, "x"), ("resample_filter", 1, None, "resample_filter"),
+                           ("resample_filtered", 0, 24960, "x"), ("resample_decimated", 0, 12480, "resampled")]
+                          + _DEMOD_FILTER + _SYNC + _FINAL_L1,
+    # final stage l2 = 832 > 1: fast_resampling again, its expanded signal
+    (48000, 11025, False): [("input", 0, 48000, "x"), ("resample_filter", 1, None, "resample_filter"),
+                            ("resample_filtered", 0, 48000 * 147, "expanded1"),
+                            ("resample_decimated", 0, 11025, "resampled")]
+                           + _DEMOD_FILTER
+                           + [("sync_correlation", 0, 11025, 0), ("sync_result", 0, 11025, "aligned"),
+                              ("resample_filter", 1, None, 1), ("resample_filtered", 0, 11025 * 832, "expanded2"),
+                              ("resample_decimated", 0, 4160, "rows")],
+}
+STEP_CASES = [(48000, 12480, True, False), (48000, 12480, False, False), (24960, 12480, True, False),
+              (48000, 11025, False, False),
+              (48000, 12480, True, True), (48000, 12480, False, True)]  # the last two: as PCM16 WAV through decode_wav
+
+_step_reference = {}
+
+
+def _reference_lengths(oracle, rate, work, sync, flag):
+    """The oracle's decode of the case, once per module: its rows and the length of every array a step carries."""
+    key = (rate, work, sync, flag)
+    if key not in _step_reference:
+        x = synth_apt(rate, 6, 50 + rate % 89)
+        rows, st = oracle.decode(x, rate, sync, settings=dict(oracle.STANDARD, work_rate=work), want_steps=True,
+                                 export_resample_filtered=flag)
+        lens = {k: int(np.asarray(v).size) for k, v in st.items() if isinstance(v, np.ndarray)}
+        lens.update(x=x.size, rows=rows.size)
+        if not flag:  # fast_resampling's expanded signal is empty without the flag (dsp.rs:281-285)
+            lens.update(expanded1=0, expanded2=0)
+        _step_reference[key] = (x, rows, lens)
+    return _step_reference[key]
+
+
+@pytest.mark.parametrize("flag", [False, True])
+@pytest.mark.parametrize("rate,work,sync,as_wav", STEP_CASES)
+def test_complete_step_sequence(oracle, rate, work, sync, as_wav, flag):
+    x, want_rows, lens = _reference_lengths(oracle, rate, work, sync, flag)
+    got = []
+    c = apt.Context(step_callback=lambda i, v, d, r: got.append((i, v, r, int(d.size))), device=0)
+    s = apt.Settings(export_wav=True, export_resample_filtered=flag, work_rate=work)
+    if as_wav:
+        rows = apt.decode_wav(c, s, make_wav(x.astype(np.int16), rate), sync)
+    else:
+        rows = apt.decode(c, s, x, apt.Rate.hz(rate), sync)
+    want = [(i, v, r, n if isinstance(n, int) else lens[n]) for i, v, r, n in STEP_SEQUENCES[(rate, work, sync)]]
+    for k, (g, w) in enumerate(zip(got, want)):
+        assert g == w, (k, g, w)
+    assert len(got) == len(want), [g[0] for g in got]
+    assert_bitexact(rows, want_rows)
+    if flag and rate != 24960:  # the closed form of tests/test_oracle_export_filtered.py: every t in [off, n*l)
+        l = work // int(np.gcd(rate, work))
+        assert lens["expanded1"] == x.size * l - (lens["resample_filter"] - 1) // 2

@@ -68,7 +68,7 @@ def test_export_branch_matches_the_transcription(oracle, l, m, ntaps, n):
 
 @pytest.mark.parametrize("l,m,ntaps,n", CASES)
 def test_export_branch_closed_form(oracle, l, m, ntaps, n):
-    """What the product computes lengths and positions from (apt_host.cpp fast_resampling_export_geom): expanded has
+    """What the product computes lengths and positions from (apt_host.cpp ResampleGeom): expanded has
     n*l - off sums; the output is expanded[d0 + k*m] with d0 = j0*m - 1 - off, j0 = ceil((off + 1) / m), for
     j0 <= j <= n*l / m; and the normal branch is expanded[k*m]."""
     rng = np.random.default_rng(7 + n)
