@@ -5,7 +5,7 @@
  *                   [--histogram | --histogram-float] [--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE] [--png]
  *                   [--tle FILE --sat NAME (--start-ms N | --end-ms N)] [--rotate no|yes|orbit]
  *                   [--project equirect|mercator[:step_deg] [--grid DEG]] [--despeckle R[:T]] [--track=[W,LAMBDA[,LAG]]]
- *                   [--live SECONDS] [--iq FMT:FS:D[:SHIFT_HZ]]
+ *                   [--live SECONDS] [--iq FMT:FS:D[:SHIFT_HZ]] [--sun A|B:UNIX_MS[:BLACK] --track FILE]
  *
  * What `noaa-apt in.wav -o out.png` does (main.rs:91-110, noaa_apt.rs:114-235): load -> decode ->
  * contrast limits -> 8-bit image, written as a binary PGM, or with --png as the PNG file the GPU
@@ -40,6 +40,9 @@
  * audio comes out at FS / D; the signal sits SHIFT_HZ off the centre) with the library's usual channel filter.  Without
  * --live the frames go through aptgpu_fm_demodulate and aptgpu_decode; with --live SECONDS through aptgpu_iq_live_* in
  * chunks of SECONDS of frames, the audio never leaving the device.  Both write the same PGM.
+ * --sun A|B:UNIX_MS[:BLACK] --track FILE: the rows go through aptgpu_geolocate first, which divides channel A's or B's
+ * video by the cosine of the solar zenith angle at every pixel (capped at 80 degrees), for a pass that starts at
+ * UNIX_MS; BLACK is the zero level in row units (default: wedge 9 of the telemetry, the zero-modulation wedge).
  * Plain C99, links only libaptgpu.so.
  */
 #include <stdio.h>
@@ -61,14 +64,14 @@ int main(int argc, char **argv)
                 "[--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE] [--png]\n"
                 "       [--tle FILE --sat NAME (--start-ms N | --end-ms N)] [--rotate no|yes|orbit]\n"
                 "       [--project equirect|mercator[:step_deg] [--grid DEG]] [--despeckle R[:T]] [--track=[W,LAMBDA[,LAG]]]\n"
-                "       [--live SECONDS] [--iq u8|s8|s16|f32:FS:D[:SHIFT_HZ]]\n", argv[0]);
+                "       [--live SECONDS] [--iq u8|s8|s16|f32:FS:D[:SHIFT_HZ]] [--sun A|B:UNIX_MS[:BLACK] --track FILE]\n", argv[0]);
         return 2;
     }
     int contrast = APTGPU_CONTRAST_PERCENT, sync = 1, lab = 0, png = 0;
     const char *palette_path = NULL, *map_dir = NULL, *track_path = NULL, *tle_path = NULL, *sat = NULL;
     int rotate = APTGPU_ROTATE_NO, ref_kind = -1;
     long long ref_ms = 0;
-    const char *project = NULL, *despeckle = NULL, *flywheel = NULL, *iq_spec = NULL;
+    const char *project = NULL, *despeckle = NULL, *flywheel = NULL, *iq_spec = NULL, *sun = NULL;
     double grid_deg = 0.0, live_seconds = 0.0;
     for (int i = 3; i < argc; ++i) {
         if (!strcmp(argv[i], "telemetry")) contrast = APTGPU_CONTRAST_TELEMETRY;
@@ -92,6 +95,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--despeckle") && i + 1 < argc) despeckle = argv[++i];
         else if (!strcmp(argv[i], "--live") && i + 1 < argc) live_seconds = atof(argv[++i]);
         else if (!strcmp(argv[i], "--iq") && i + 1 < argc) iq_spec = argv[++i];
+        else if (!strcmp(argv[i], "--sun") && i + 1 < argc) sun = argv[++i];
         else if (!strcmp(argv[i], "--rotate") && i + 1 < argc) {
             const char *r = argv[++i];
             rotate = !strcmp(r, "orbit") ? APTGPU_ROTATE_ORBIT : !strcmp(r, "yes") ? APTGPU_ROTATE_YES : APTGPU_ROTATE_NO;
@@ -334,6 +338,48 @@ int main(int argc, char **argv)
                 (unsigned long long)dr.replaced, (unsigned long long)dr.height * 2080ull, dr.t);
         aptgpu_free(rows);
         rows = filtered;
+    }
+
+    if (sun) {
+        /* on the f32 rows, in front of the image stage: the visible channel normalised by the sun's elevation */
+        const size_t height = n_rows_px / 2080;
+        aptgpu_geoloc_settings gs;
+        memset(&gs, 0, sizeof gs);
+        gs.struct_size = sizeof gs;
+        gs.channel = sun[0] == 'B' ? 1 : 0;
+        gs.time_kind = APTGPU_REF_TIME_START;
+        gs.max_zenith_deg = 80.f;
+        const char *colon = strchr(sun + 2, ':');
+        double *track = malloc((height ? height : 1) * 2 * sizeof(double));
+        FILE *t = track_path ? fopen(track_path, "rb") : NULL;
+        if ((sun[0] != 'A' && sun[0] != 'B') || sun[1] != ':' || !track || !t ||
+            fread(track, sizeof(double), 2 * height, t) != 2 * height || fgetc(t) != EOF) {
+            fprintf(stderr, "--sun A|B:UNIX_MS[:BLACK] needs --track FILE with exactly %zu (lat, lon) f64 pairs\n", height);
+            return 1;
+        }
+        fclose(t);
+        gs.unix_ms = atoll(sun + 2);
+        if (colon) {
+            gs.black_level = (float)atof(colon + 1);
+        } else {
+            aptgpu_image_result tel;
+            rc = aptgpu_read_telemetry(&ctx, rows, n_rows_px, &tel, err, sizeof err);
+            if (rc != APTGPU_OK) { fprintf(stderr, "--sun: no telemetry for the black level (%d): %s\n", rc, err); return 1; }
+            gs.black_level = gs.channel ? tel.values_b[8] : tel.values_a[8];
+        }
+        aptgpu_geoloc_result gr;
+        memset(&gr, 0, sizeof gr);
+        gr.struct_size = sizeof gr;
+        float *normalised = NULL;
+        rc = aptgpu_geolocate(&ctx, rows, n_rows_px, track, height, NULL, NULL, &gs, NULL, NULL, &normalised, &gr, err,
+                              sizeof err);
+        free(track);
+        if (rc != APTGPU_OK) { fprintf(stderr, "sun normalisation failed (%d): %s\n", rc, err); return 1; }
+        fprintf(stderr, "sun: channel %c, black %g, cos(zenith) %.3f .. %.3f, %llu of %llu pixels capped at 80 degrees\n",
+                sun[0], gs.black_level, gr.cos_min, gr.cos_max, (unsigned long long)gr.n_capped,
+                (unsigned long long)gr.height * 909ull);
+        aptgpu_free(rows);
+        rows = normalised;
     }
 
     uint8_t *image = NULL;

@@ -967,6 +967,100 @@ int aptgpu_plan_calibrate_thermal_device(aptgpu_plan *plan, int count, const flo
 /* Waits for the thermal stage of the last call and copies the records. */
 int aptgpu_plan_thermal_results(aptgpu_plan *plan, int count, aptgpu_thermal_result *results);
 
+/* ---- geolocation of the swath: lat / lon, sun angle, sun-normalised rows ----
+ * The overlay and the reprojection go from a place on the Earth to a pixel (latlon_to_rel_px, map.rs:71-100).  This
+ * stage goes the other way, for the 909 video columns of a channel.  The reference has nothing like it, so the
+ * definition is this library's; tests/np_geoloc_model.py states it in numpy.  Opt-in, a stage of its own behind the
+ * decode; nothing else changes when it is not called.
+ *  - h = n / 2080 rows; a track of h (lat, lon) pairs in radians, the caller's (sat_positions) or SGP4's on the GPU
+ *    from an aptgpu_orbit_settings (exactly one of the two); aptgpu_map_settings for yaw, hscale, vscale (nullable:
+ *    0, 1, 1).  start, ref_az, x_res, y_res, yaw are the overlay's scalars (map.rs:59-69) and xoff[r] the x of
+ *    latlon_to_rel_px(track[r]) (map.rs:110-114), as the overlay and the reprojection use them, except xoff[0] = 0:
+ *    track[0] is the start point, whose relative pixel is (0, 0) by definition, where the evaluated expression returns
+ *    either 0 or up to acos(1 - 2^-53) / x_res = 3e-5 px depending on how one cosine rounds.
+ *  - Sample points: video column k = 0 .. 908 of a row is image column base + 86 + k (base = 1040 * channel) and
+ *    relative pixel x_rel = k - 453 (image column 539 of channel A is relative pixel 0).  The geometry is the same
+ *    for both channels: the planes are h x 909 and carry no channel.
+ *  - Forward point of (r, k), all f64, never contracted; (phi0, lam0) = track[0]:
+ *      x = x_rel + xoff[r],  b = -x * x_res,  a = (r - yaw * x) * y_res,
+ *      S = (cos phi0 cos lam0, cos phi0 sin lam0, sin phi0),  N = (-sin phi0 cos lam0, -sin phi0 sin lam0, cos phi0),
+ *      E = (-sin lam0, cos lam0, 0),  T = cos(ref_az) N + sin(ref_az) E,  R = -sin(ref_az) N + cos(ref_az) E,
+ *      P = (cos b cos a) S + (cos b sin a) T + (sin b) R,
+ *      lat = atan2(Pz, hypot(Px, Py)),  lon = atan2(Py, Px)  (in (-pi, pi], never unwrapped),
+ *      valid iff acos(cos a * cos b) < pi / 3  (beyond that distance latlon_to_rel_px clamps and has no inverse).
+ *    An invalid pixel is NaN in both planes and unchanged in the rows.
+ *  - Sun: row r is seen at t = start_ms + 500 * r (map.rs:45), start_ms = unix_ms (APTGPU_REF_TIME_START) or
+ *    unix_ms - 500 * h (APTGPU_REF_TIME_END); with an orbit its reference time rules.  The Astronomical Almanac's
+ *    low-precision series, f64, C fmod:
+ *      n = t / 86400000 + 2440587.5 - 2451545.0,
+ *      L = fmod(280.460 + 0.9856474 n, 360),  g = rad(fmod(357.528 + 0.9856003 n, 360)),
+ *      lam = rad(L + 1.915 sin g + 0.020 sin 2g),  eps = rad(23.439 - 0.0000004 n),
+ *      alpha = atan2(cos eps sin lam, cos lam),  delta = asin(sin eps sin lam),
+ *      theta = rad(15 * fmod(18.697374558 + 24.06570982441908 n, 24)),
+ *      U = (cos delta cos(alpha - theta), cos delta sin(alpha - theta), sin delta),
+ *      cos_sun(r, k) = (float)((Px Ux + Py Uy) + Pz Uz).
+ *  - Normalised rows: the channel's 909 columns in f32, never contracted:
+ *      out = valid ? black + (x - black) / fmaxf(c, cmin) : x,  c = cos_sun,  cmin = (float)cos(max_zenith_deg / 180 * pi);
+ *    every other column is copied unchanged, a NaN x stays NaN.
+ *  - The record counts the invalid pixels (n_outside), the valid ones with c < cmin (n_capped) and gives the extremes
+ *    of c over the valid ones, whatever outputs were asked for.
+ *  - Record reasons (status APTGPU_ERR_INTERNAL): APTGPU_MAP_REASON_COUNT (7) the position count differs from the
+ *    height; APTGPU_SAT_REASON_SGP4 (10); APTGPU_GEOLOC_REASON_HEIGHT (15) fewer than two rows, so no direction of
+ *    flight; APTGPU_GEOLOC_REASON_DECODE (16) the decode in front failed (plan form).  The plan form then writes the
+ *    planes of the rows as NaN and copies the rows unchanged; the host-array forms return APTGPU_ERR_INTERNAL with
+ *    the record filled and no outputs. */
+#define APTGPU_GEOLOC_PX 909             /* samples per row of the planes */
+#define APTGPU_GEOLOC_REASON_HEIGHT 15   /* aptgpu_geoloc_result.reason */
+#define APTGPU_GEOLOC_REASON_DECODE 16
+typedef struct aptgpu_geoloc_settings {
+    uint32_t struct_size;  /* sizeof(aptgpu_geoloc_settings) */
+    uint32_t flags;        /* 0; any set bit is APTGPU_ERR_INVALID */
+    int32_t channel;       /* 0 = A, 1 = B: the half of the row image the normalisation rewrites */
+    int32_t time_kind;     /* APTGPU_REF_TIME_START / APTGPU_REF_TIME_END; used when no orbit is given */
+    int64_t unix_ms;       /* the reference time, milliseconds since 1970-01-01T00:00:00Z; likewise */
+    float black_level;     /* the zero level in row units; finite */
+    float max_zenith_deg;  /* in (0, 90), else APTGPU_ERR_INVALID; the bindings default to 80 */
+} aptgpu_geoloc_settings;
+typedef struct aptgpu_geoloc_result {
+    uint32_t struct_size;  /* the caller's sizeof(aptgpu_geoloc_result) */
+    int32_t status;        /* APTGPU_OK or APTGPU_ERR_INTERNAL */
+    int32_t reason;        /* 0, 7, 10, 15, 16 */
+    uint32_t height;       /* whole rows */
+    uint64_t n_outside;    /* invalid pixels of the h x 909 plane */
+    uint64_t n_capped;     /* valid pixels whose cos_sun is below cmin */
+    float cos_min, cos_max; /* over the valid pixels; NaN when there is none */
+} aptgpu_geoloc_result;
+/* settings is required.  Exactly one of sat_positions (n_positions pairs) and orbit.  Each output pointer is nullable
+ * and what is null is not computed: *latlon, malloc'd, height * 909 (lat, lon) pairs of f64, interleaved; *cos_sun,
+ * height * 909 floats; *rows_out, n floats, which needs the signal (APTGPU_ERR_INVALID without).  With signal NULL,
+ * n / 2080 still gives the height.  aptgpu_free all three; info nullable (its struct_size set by the caller). */
+int aptgpu_geolocate(const aptgpu_context *ctx, const float *signal, size_t n, const double *sat_positions,
+                     size_t n_positions, const aptgpu_orbit_settings *orbit, const aptgpu_map_settings *map,
+                     const aptgpu_geoloc_settings *settings, double **latlon, float **cos_sun, float **rows_out,
+                     aptgpu_geoloc_result *info, char *err, size_t err_cap);
+/* The same on the CPU, in plain C++ (no GPU needed): the same source text per pixel, the C library's f64 functions. */
+int aptgpu_geolocate_host(const float *signal, size_t n, const double *sat_positions, size_t n_positions,
+                          const aptgpu_orbit_settings *orbit, const aptgpu_map_settings *map,
+                          const aptgpu_geoloc_settings *settings, double **latlon, float **cos_sun, float **rows_out,
+                          aptgpu_geoloc_result *info, char *err, size_t err_cap);
+/* The sun of the series above at one instant (CPU): out[0] = declination, out[1] = sub-solar longitude in (-pi, pi],
+ * both in radians. */
+int aptgpu_sun_position(int64_t unix_ms, double out[2]);
+/* Device-resident, chained behind the last aptgpu_plan_decode_device call on each recording's stream without a host
+ * round trip (the height comes from the decode record on the device; with a rows_cap below it, rows_cap rows).
+ * Exactly one of sat_positions (with n_positions) and orbit, per recording as in the map entry points.  d_latlon[i]
+ * holds rows_cap[i] * 909 * 2 doubles and must be 16-byte aligned; d_cos[i] rows_cap[i] * 909 floats, d_out[i]
+ * rows_cap[i] * 2080 floats, both 4-byte aligned.  Each of the three arrays is nullable: what is null is not
+ * computed.  d_out[i] == d_rows[i] normalises in place; any other overlap of an output with a rows buffer or with
+ * another output is APTGPU_ERR_INVALID.  Timer names: image_geoloc_track, image_geoloc_rows, image_geoloc. */
+int aptgpu_plan_geolocate_device(aptgpu_plan *plan, int count, const float *const *d_rows, const size_t *rows_cap,
+                                 const double *const *sat_positions, const size_t *n_positions,
+                                 const aptgpu_orbit_settings *const *orbit, const aptgpu_map_settings *map,
+                                 const aptgpu_geoloc_settings *settings, double *const *d_latlon,
+                                 float *const *d_cos, float *const *d_out, char *err, size_t err_cap);
+/* Waits for the geolocation stage of the last call and copies the records (each results[i].struct_size set). */
+int aptgpu_plan_geoloc_results(aptgpu_plan *plan, int count, aptgpu_geoloc_result *results);
+
 /* ====================================================================== */
 /* 4b. FM demodulation of IQ recordings, in front of decode() */
 /* ====================================================================== */

@@ -35,6 +35,10 @@ Names, argument meaning and error behaviour follow the reference:
     calibrate_thermal, calibrate_thermal_host,             brightness temperature of an infrared channel from the
     ThermalCoefficients, ThermalSettings,                  telemetry frame (NOAA KLM User's Guide §7.1.2.4), DESIGN.md §19
     Plan.calibrate_thermal_device
+    geolocate, geolocate_host, sun_position,               where on the Earth a swath pixel lies (the overlay's projection
+    normalize_sun, GeolocSettings, Plan.geolocate_device   inverted), the sun's zenith angle there and the visible rows
+                                                           normalised by it (the reference only advises daylight passes,
+                                                           docs/usage.md:409-417), DESIGN.md §25
     fm_demodulate, fm_demodulate_host, fm_demodulate_wav,  FM demodulation of an IQ recording in front of decode()
     fm_design, load_iq, IqFormat, FmSettings,              (the reference takes audio only, docs/usage.md:87),
     FmDemodulator                                          DESIGN.md §20
@@ -66,6 +70,8 @@ from .api import (  # noqa: F401
     DespeckleSettings, DespeckleResult, despeckle, despeckle_host,
     ThermalCoefficients, ThermalSettings, ThermalResult, calibrate_thermal, calibrate_thermal_host,
     THERMAL_COLD_WHITE, THERMAL_REASON_CHANNEL, THERMAL_REASON_DEGENERATE, THERMAL_PX,
+    GeolocSettings, GeolocResult, geolocate, geolocate_host, sun_position, normalize_sun,
+    GEOLOC_PX, GEOLOC_REASON_HEIGHT, GEOLOC_REASON_DECODE,
     IqFormat, FmSettings, FmInfo, FmDemodulator, fm_demodulate, fm_demodulate_host, fm_demodulate_wav, fm_design, load_iq,
     FM_SWAP_IQ, FM_MAX_BATCH,
     TrackSettings, TrackResult, track_sync, track_sync_host, sync_score, decode_tracked, TRACK_MAX_JITTER,

@@ -243,6 +243,19 @@ class ThermalResult(C.Structure):
                 ("t_bb", C.c_double), ("n_bb", C.c_double), ("t_min", C.c_float), ("t_max", C.c_float)]
 
 
+class _CGeolocSettings(C.Structure):
+    """aptgpu_geoloc_settings"""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("channel", C.c_int32), ("time_kind", C.c_int32),
+                ("unix_ms", C.c_int64), ("black_level", C.c_float), ("max_zenith_deg", C.c_float)]
+
+
+class GeolocResult(C.Structure):
+    """aptgpu_geoloc_result: the height, the pixels beyond the geometry's limit (n_outside), those whose cos_sun is
+    below the cap (n_capped) and the extremes of cos_sun over the valid pixels."""
+    _fields_ = [("struct_size", C.c_uint32), ("status", C.c_int32), ("reason", C.c_int32), ("height", C.c_uint32),
+                ("n_outside", C.c_uint64), ("n_capped", C.c_uint64), ("cos_min", C.c_float), ("cos_max", C.c_float)]
+
+
 class _CFmSettings(C.Structure):
     """aptgpu_fm_settings"""
     _fields_ = [("struct_size", C.c_uint32), ("format", C.c_int32), ("sample_rate_hz", C.c_uint32),
@@ -502,6 +515,16 @@ def lib():
     L.aptgpu_plan_calibrate_thermal_device.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz), *cth, C.POINTER(vp),
                                                        C.POINTER(vp), C.c_char_p, sz]
     L.aptgpu_plan_thermal_results.argtypes = [vp, i32, C.POINTER(ThermalResult)]
+    geo = (_f64p, sz, C.POINTER(_COrbitSettings), C.POINTER(_CMapSettings), C.POINTER(_CGeolocSettings),
+           C.POINTER(_f64p), C.POINTER(_f32p), C.POINTER(_f32p), C.POINTER(GeolocResult), C.c_char_p, sz)
+    L.aptgpu_geolocate.argtypes = [cp, _f32p, sz, *geo]
+    L.aptgpu_geolocate_host.argtypes = [_f32p, sz, *geo]
+    L.aptgpu_sun_position.argtypes = [C.c_int64, _f64p]
+    L.aptgpu_plan_geolocate_device.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz), C.POINTER(_f64p), C.POINTER(sz),
+                                               C.POINTER(C.POINTER(_COrbitSettings)), C.POINTER(_CMapSettings),
+                                               C.POINTER(_CGeolocSettings), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                               C.c_char_p, sz]
+    L.aptgpu_plan_geoloc_results.argtypes = [vp, i32, C.POINTER(GeolocResult)]
     cfm = C.POINTER(_CFmSettings)
     fm_out = (C.POINTER(_f32p), C.POINTER(sz), _u32p, C.c_char_p, sz)
     L.aptgpu_fm_default_settings.argtypes = [cfm]
@@ -2038,6 +2061,125 @@ def calibrate_thermal_host(signal, coeffs, settings):
 
 
 # ------------------------------------------------------------------ FM demodulation of IQ recordings
+GEOLOC_PX = 909
+GEOLOC_REASON_HEIGHT = 15
+GEOLOC_REASON_DECODE = 16
+
+
+class GeolocSettings:
+    """aptgpu_geoloc_settings.  channel: "A" / "B" (or 0 / 1), the half of the row image normalize_sun() rewrites.
+    ref_time: RefTime.Start(t) / RefTime.End(t) of the image, used for the sun when the track is an array (an
+    OrbitSettings brings its own).  black: the zero level in row units.  max_zenith_deg: the normalisation divides by
+    max(cos_sun, cos(max_zenith_deg)); in (0, 90)."""
+
+    def __init__(self, channel="A", ref_time=None, black=0.0, max_zenith_deg=80.0, flags=0):
+        self.channel, self.ref_time, self.black, self.max_zenith_deg = channel, ref_time, black, max_zenith_deg
+        self.flags = flags
+
+    def _c(self, struct_size=None):
+        ch = {"A": 0, "B": 1}.get(self.channel, self.channel)
+        rt = self.ref_time if self.ref_time is not None else RefTime.Start(0)
+        if not isinstance(rt, RefTime):
+            raise InvalidError("geoloc: ref_time is RefTime.Start(t) or RefTime.End(t)")
+        return _CGeolocSettings(C.sizeof(_CGeolocSettings) if struct_size is None else int(struct_size), int(self.flags),
+                                int(ch), rt.kind, rt.unix_ms, float(self.black), float(self.max_zenith_deg))
+
+
+def _geoloc_c(track_or_orbit, map_settings, settings):
+    """(positions pointer, count, orbit pointer, map pointer, settings, keepalive)"""
+    settings = settings if settings is not None else GeolocSettings()
+    if not isinstance(settings, GeolocSettings):
+        raise InvalidError("geoloc: settings must be a GeolocSettings")
+    if map_settings is not None and not isinstance(map_settings, MapSettings):
+        raise InvalidError("geoloc: map_settings must be a MapSettings or None")
+    try:
+        cs = settings._c()
+    except (TypeError, ValueError, OverflowError) as e:
+        raise InvalidError(f"geoloc: {e}") from None
+    cms = map_settings._c() if map_settings is not None else None
+    if isinstance(track_or_orbit, OrbitSettings):
+        co, keep = track_or_orbit._c()
+        return None, 0, C.byref(co), (C.byref(cms) if cms is not None else None), cs, (co, keep, cms)
+    if track_or_orbit is None:
+        return None, 0, None, (C.byref(cms) if cms is not None else None), cs, (cms,)
+    track = np.ascontiguousarray(np.asarray(track_or_orbit, dtype=np.float64).reshape(-1, 2))
+    return (track.ctypes.data_as(_f64p), track.shape[0], None, (C.byref(cms) if cms is not None else None), cs,
+            (track, cms))
+
+
+def _geoloc_call(fn, head, signal_or_height, track_or_orbit, map_settings, settings, latlon, sun, rows):
+    if isinstance(signal_or_height, (int, np.integer)):
+        if rows:
+            raise InvalidError("geoloc: normalised rows need the signal")
+        xp, n = None, int(signal_or_height) * PX_PER_ROW
+    else:
+        x, xp = _as_f32(signal_or_height)
+        n = x.size
+    pos, count, co, cms, cs, keep = _geoloc_c(track_or_orbit, map_settings, settings)
+    p_ll, p_cos, p_rows, info = _f64p(), _f32p(), _f32p(), GeolocResult()
+    info.struct_size = C.sizeof(GeolocResult)
+    err = C.create_string_buffer(_ERRCAP)
+    try:
+        _check(fn(*head, xp, n, pos, count, co, cms, C.byref(cs), C.byref(p_ll) if latlon else None,
+                  C.byref(p_cos) if sun else None, C.byref(p_rows) if rows else None, C.byref(info), err, _ERRCAP), err)
+    except AptError as e:
+        e.info = info  # (the record of a failed call: status, reason, height)
+        raise
+    del keep
+    h = n // PX_PER_ROW
+    out_ll = _take(p_ll, h * GEOLOC_PX * 2, np.float64).reshape(h, GEOLOC_PX, 2) if latlon else None
+    out_cos = _take(p_cos, h * GEOLOC_PX).reshape(h, GEOLOC_PX) if sun else None
+    out_rows = _take(p_rows, n) if rows else None
+    return out_ll, out_cos, out_rows, info
+
+
+def geolocate(signal_or_height, track_or_orbit, map_settings=None, settings=None, latlon=True, sun=False, context=None):
+    """Where on the Earth every video pixel of the swath lies, on the GPU: the inverse of the map
+    overlay's projection.  signal_or_height: decoded rows, or just their number.  track_or_orbit: the satellite's
+    (lat, lon) in radians per row, or an OrbitSettings (SGP4 then runs on the GPU).  Returns (latlon, cos_sun, info):
+    the height x 909 x 2 f64 plane of (lat, lon) in radians, the height x 909 f32 cosine of the solar zenith angle
+    (each None unless asked for) and the GeolocResult.  Pixels beyond 60 degrees of arc from the track's start are NaN.
+    A failed call (fewer than two rows, a track of another length, SGP4) raises InternalError whose `info` attribute
+    is the record."""
+    cctx = (context or Context())._c()
+    ll, cs, _, info = _geoloc_call(lib().aptgpu_geolocate, (C.byref(cctx),), signal_or_height, track_or_orbit,
+                                   map_settings, settings, latlon, sun, False)
+    return ll, cs, info
+
+
+def geolocate_host(signal_or_height, track_or_orbit, map_settings=None, settings=None, latlon=True, sun=False,
+                   rows=False):
+    """geolocate() on the CPU, in plain C++ (no GPU needed): the same source text per pixel with the C library's f64
+    functions.  With rows=True the fourth value is the sun-normalised signal (normalize_sun's)."""
+    ll, cs, r, info = _geoloc_call(lib().aptgpu_geolocate_host, (), signal_or_height, track_or_orbit, map_settings,
+                                   settings, latlon, sun, rows)
+    return (ll, cs, r, info) if rows else (ll, cs, info)
+
+
+def sun_position(unix_ms):
+    """(declination, sub-solar longitude) in radians at a Unix time in milliseconds: the Astronomical Almanac's
+    low-precision series the stage uses (CPU)."""
+    out = (C.c_double * 2)()
+    _check(lib().aptgpu_sun_position(int(unix_ms), out))
+    return float(out[0]), float(out[1])
+
+
+def normalize_sun(signal, track_or_orbit, channel, black=None, ref_time=None, max_zenith_deg=80.0, map_settings=None,
+                  context=None, return_info=False):
+    """The visible channel's video divided by the cosine of the solar zenith angle, in front of process() (DESIGN.md
+    §25): out = black + (x - black) / max(cos_sun, cos(max_zenith_deg)) on the channel's 909 video columns, every other
+    sample unchanged.  black=None takes wedge 9 of read_telemetry(), the zero-modulation wedge of that channel.
+    ref_time: the image's RefTime when the track is an array."""
+    if black is None:
+        ch = {0: "A", 1: "B"}.get(channel, channel)
+        black = float(read_telemetry(context, signal).get_wedge_value(9, ch))
+    st = GeolocSettings(channel=channel, ref_time=ref_time, black=black, max_zenith_deg=max_zenith_deg)
+    cctx = (context or Context())._c()
+    _, _, rows, info = _geoloc_call(lib().aptgpu_geolocate, (C.byref(cctx),), signal, track_or_orbit, map_settings, st,
+                                    False, False, True)
+    return (rows, info) if return_info else rows
+
+
 class IqFormat:
     """aptgpu_fm_settings.format: how one component of a frame is stored (interleaved I then Q, never scaled)."""
     U8 = 0   # v - 127.5, the rtl_sdr convention
@@ -2692,6 +2834,47 @@ class Plan:
             (C.c_void_p * k)(*d_kelvin), (C.c_void_p * k)(*d_images) if d_images is not None else None, err, _ERRCAP),
             err)
         del keep
+
+    def geolocate_device(self, d_rows: Sequence[int], rows_cap: Sequence[int], tracks_or_orbits, settings=None,
+                         map_settings=None, d_latlon: Optional[Sequence[int]] = None,
+                         d_cos: Optional[Sequence[int]] = None, d_out: Optional[Sequence[int]] = None):
+        """The geolocation stage of the recordings of the last decode_device call, chained on the device behind their
+        decode.  tracks_or_orbits: per recording a (rows, 2) track in radians, or per recording an OrbitSettings.
+        d_latlon[i] holds rows_cap[i] * 909 * 2 doubles (16-byte aligned), d_cos[i] rows_cap[i] * 909 floats, d_out[i]
+        rows_cap[i] * 2080 floats (d_out[i] == d_rows[i]: in place); what is None is not computed.  Records through
+        geoloc_results()."""
+        k = len(d_rows)
+        if len(tracks_or_orbits) != k:
+            raise InvalidError("geoloc: one track or orbit per recording")
+        orbits = [isinstance(t, OrbitSettings) for t in tracks_or_orbits]
+        if any(orbits) and not all(orbits):
+            raise InvalidError("geoloc: tracks or orbits, not both")
+        _, _, _, cms, cs, keep = _geoloc_c(None, map_settings, settings)
+        pos = cnt = orb = None
+        if k and all(orbits):
+            cos_ = [t._c() for t in tracks_or_orbits]
+            orb = (C.POINTER(_COrbitSettings) * k)(*[C.pointer(c[0]) for c in cos_])
+            keep = (keep, cos_)
+        else:
+            tr = [np.ascontiguousarray(np.asarray(t, dtype=np.float64).reshape(-1, 2)) for t in tracks_or_orbits]
+            pos = (_f64p * k)(*[t.ctypes.data_as(_f64p) for t in tr])
+            cnt = (C.c_size_t * k)(*[t.shape[0] for t in tr])
+            keep = (keep, tr)
+
+        def arr(v):
+            return (C.c_void_p * k)(*v) if v is not None else None
+        err = C.create_string_buffer(_ERRCAP)
+        _check(lib().aptgpu_plan_geolocate_device(self._p, k, (C.c_void_p * k)(*d_rows), (C.c_size_t * k)(*rows_cap),
+                                                  pos, cnt, orb, cms, C.byref(cs), arr(d_latlon), arr(d_cos), arr(d_out),
+                                                  err, _ERRCAP), err)
+        del keep
+
+    def geoloc_results(self, count=1) -> List["GeolocResult"]:
+        arr = (GeolocResult * count)()
+        for r in arr:
+            r.struct_size = C.sizeof(GeolocResult)
+        _check(lib().aptgpu_plan_geoloc_results(self._p, count, arr))
+        return list(arr)
 
     def thermal_results(self, count=1) -> List["ThermalResult"]:
         arr = (ThermalResult * count)()

@@ -309,36 +309,6 @@ int layer_index(int layer)
     return layer;
 }
 
-// One recording's aptgpu_orbit_settings after its checks: the initialised satellite and the reference time for the
-// kernels, the map settings (null: no overlay) and Rotate::Orbit's outcome.
-struct SatCall {
-    apt::sat::TrackCall call;
-    const aptgpu_map_settings *draw_map;
-};
-
-// The checks of aptgpu_orbit_settings, then parse + sgp4init (cached for the last TLE and name).
-SatCall orbit_args(const aptgpu_orbit_settings *orbit)
-{
-    if (!orbit || orbit->struct_size < sizeof(aptgpu_orbit_settings))
-        throw Error{ErrorKind::Invalid, "aptgpu_orbit_settings: struct_size not set"};
-    if (orbit->flags) throw Error{ErrorKind::Invalid, "aptgpu_orbit_settings: unknown flags"};
-    if (!orbit->sat_name) throw Error{ErrorKind::Invalid, "aptgpu_orbit_settings: sat_name not set"};
-    if (orbit->ref_kind != APTGPU_REF_TIME_START && orbit->ref_kind != APTGPU_REF_TIME_END)
-        throw Error{ErrorKind::Invalid, "aptgpu_orbit_settings: unknown ref_kind"};
-    if (!orbit->tle)
-        throw Error{ErrorKind::Unsupported,
-                    "aptgpu_orbit_settings: tle is NULL (the reference then downloads the current TLE, "
-                    "misc::get_current_tle; pass the text)"};
-    if (orbit->draw_map && orbit->draw_map->struct_size < sizeof(aptgpu_map_settings))
-        throw Error{ErrorKind::Invalid, "aptgpu_map_settings: struct_size not set"};
-    SatCall c{};
-    c.call.rec = apt::sat::satrec_for(orbit->tle, orbit->sat_name);
-    c.call.ref_ms = orbit->ref_unix_ms;
-    c.call.ref_is_end = orbit->ref_kind == APTGPU_REF_TIME_END;
-    c.draw_map = orbit->draw_map;
-    return c;
-}
-
 // Rotate::Orbit -> Yes / No (noaa_apt.rs:229-234), before anything is launched
 int resolve_rotate(int rotate, const SatCall &c)
 {

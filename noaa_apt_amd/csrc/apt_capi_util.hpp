@@ -10,7 +10,9 @@
 #include <new>
 #include <string>
 
+#include "apt_kernels_track.hpp"
 #include "apt_plan.hpp"
+#include "apt_sat.hpp"
 
 namespace apt::capi {
 
@@ -235,6 +237,36 @@ inline uint64_t resample_device(Scratch &sc, const float *d_x, size_t n, uint32_
                        StepSignal::device(d_y.ptr, w), /*filter_steps*/ false);
     apt::hip_check(hipStreamSynchronize(sc.stream), "hipStreamSynchronize");  // d_c goes out of scope
     return w;
+}
+
+// One recording's aptgpu_orbit_settings after its checks: the initialised satellite and the reference time for the
+// kernels, the map settings (null: no overlay) and Rotate::Orbit's outcome.
+struct SatCall {
+    apt::sat::TrackCall call;
+    const aptgpu_map_settings *draw_map;
+};
+
+// The checks of aptgpu_orbit_settings, then parse + sgp4init (cached for the last TLE and name).
+inline SatCall orbit_args(const aptgpu_orbit_settings *orbit)
+{
+    if (!orbit || orbit->struct_size < sizeof(aptgpu_orbit_settings))
+        throw Error{ErrorKind::Invalid, "aptgpu_orbit_settings: struct_size not set"};
+    if (orbit->flags) throw Error{ErrorKind::Invalid, "aptgpu_orbit_settings: unknown flags"};
+    if (!orbit->sat_name) throw Error{ErrorKind::Invalid, "aptgpu_orbit_settings: sat_name not set"};
+    if (orbit->ref_kind != APTGPU_REF_TIME_START && orbit->ref_kind != APTGPU_REF_TIME_END)
+        throw Error{ErrorKind::Invalid, "aptgpu_orbit_settings: unknown ref_kind"};
+    if (!orbit->tle)
+        throw Error{ErrorKind::Unsupported,
+                    "aptgpu_orbit_settings: tle is NULL (the reference then downloads the current TLE, "
+                    "misc::get_current_tle; pass the text)"};
+    if (orbit->draw_map && orbit->draw_map->struct_size < sizeof(aptgpu_map_settings))
+        throw Error{ErrorKind::Invalid, "aptgpu_map_settings: struct_size not set"};
+    SatCall c{};
+    c.call.rec = apt::sat::satrec_for(orbit->tle, orbit->sat_name);
+    c.call.ref_ms = orbit->ref_unix_ms;
+    c.call.ref_is_end = orbit->ref_kind == APTGPU_REF_TIME_END;
+    c.draw_map = orbit->draw_map;
+    return c;
 }
 
 // decode()'s own errors (decode.rs:79-83,112-118,172-176)

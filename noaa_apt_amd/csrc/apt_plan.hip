@@ -821,6 +821,28 @@ void aptgpu_plan::enqueue_thermal(int i, uint64_t rows_cap_floats, apt::gpu::The
     apt::hip_check(hipGetLastError(), "kernel launch (thermal stage)");
 }
 
+void aptgpu_plan::enqueue_geoloc(int i, uint64_t rows_cap_floats, apt::gpu::GeolocLaunch l)
+{
+    using namespace apt::gpu;
+    const ImageTarget t = image_target(i, rows_cap_floats);
+    Slot &sl = t.slot;
+    l.res = t.res;
+    l.n = 0;
+    l.cap = t.cap;
+    const size_t rows = static_cast<size_t>(t.cap / 2080u);
+    if (!sl.geoloc_ws.ptr || sl.geoloc_rows < rows) {
+        sl.geoloc_ws.alloc(geoloc_ws_bytes(rows));
+        sl.geoloc_rows = rows;
+    }
+    if (!sl.map) sl.map = std::make_unique<apt::map::Device>();
+    sl.map->prepare_track(t.stream, rows);
+    void *ws = sl.geoloc_ws.ptr;
+    timed(t.stream, "image_geoloc_track", [&] { geoloc_track(t.stream, l, *sl.map, ws); });
+    timed(t.stream, "image_geoloc_rows", [&] { geoloc_rows(t.stream, l, *sl.map, ws); });
+    timed(t.stream, "image_geoloc", [&] { geoloc_pixels(t.stream, l, *sl.map, ws); });
+    apt::hip_check(hipGetLastError(), "kernel launch (geolocation stage)");
+}
+
 aptgpu_plan::Palette::~Palette()
 {
     for (hipEvent_t ev : uploaded)

@@ -16,6 +16,7 @@
 #include "apt_kernels_color.hpp"
 #include "apt_kernels_despeckle.hpp"
 #include "apt_kernels_thermal.hpp"
+#include "apt_kernels_geoloc.hpp"
 #include "apt_kernels_eqfloat.hpp"
 #include "apt_kernels_map.hpp"
 #include "apt_kernels_png.hpp"
@@ -193,6 +194,8 @@ struct aptgpu_plan : apt::PlanDesign {
         apt::DeviceBuffer<char> eqfloat_ws;  // counters, select records and thresholds of HISTOGRAM_FLOAT, on first use
         apt::DeviceBuffer<char> despeckle_ws;  // record + limits record of the despeckle stage, on first use
         apt::DeviceBuffer<char> thermal_ws;    // record, pixel parameters, telemetry record and row means of the thermal stage, on first use
+        apt::DeviceBuffer<char> geoloc_ws;     // record, frame, height record and per-row sun vectors of the geolocation stage, on first use
+        size_t geoloc_rows = 0;                // rows geoloc_ws has room for
         apt::DeviceBuffer<char> track_ws;      // scores, back-pointers, position lists and record of the flywheel sync stage, on first use
         std::unique_ptr<apt::map::Device> map;  // the map overlay's layer set, lists and track, on first use
         std::unique_ptr<apt::project::Device> project;  // the reprojection's graticule, record and PNG scratch, on first use
@@ -263,6 +266,11 @@ struct aptgpu_plan : apt::PlanDesign {
     // recording's buffers; res, n and cap are filled in here.  The record stays in the slot.
     void enqueue_thermal(int i, uint64_t rows_cap_floats, apt::gpu::ThermalLaunch launch, const apt::gpu::ThermalCoeffs &coeffs,
                          const apt::gpu::ThermalTable &table);
+    // The geolocation stage (apt_kernels_geoloc.hpp) of recording i, behind its decode on the same stream: the track's
+    // launches into the slot's map device (whose track and x offsets a later overlay or reprojection rewrites), then
+    // k_geoloc_rows and k_geoloc.  launch.x and the output planes are the recording's buffers; res, n and cap are
+    // filled in here.  The record stays in the slot.
+    void enqueue_geoloc(int i, uint64_t rows_cap_floats, apt::gpu::GeolocLaunch launch);
     // The false-colour palette (256*256*3 RGB).  The plan keeps a host copy; bytes that differ from it start a new
     // generation, which every slot uploads on its own stream the next time it colours an image.  lab: also the
     // palette's Lab tables (apt_lab.hpp), computed once per generation and uploaded per slot likewise.
