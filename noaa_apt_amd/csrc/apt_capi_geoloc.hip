@@ -64,9 +64,9 @@ int aptgpu_geolocate_host(const float *signal, size_t n, const double *sat_posit
             c.st.ref_is_end = sat.call.ref_is_end != 0;
             c.st.ref_ms = sat.call.ref_ms;
         }
-        std::unique_ptr<double, HostFree> hl(latlon ? host_alloc<double>(h * 2 * APTGPU_GEOLOC_PX) : nullptr);
-        std::unique_ptr<float, HostFree> hc(cos_sun ? host_alloc<float>(h * APTGPU_GEOLOC_PX) : nullptr);
-        std::unique_ptr<float, HostFree> hr(rows_out ? host_alloc<float>(n) : nullptr);
+        HostPtr<double> hl(latlon ? host_alloc<double>(h * 2 * APTGPU_GEOLOC_PX) : nullptr);
+        HostSignal hc(cos_sun ? host_alloc<float>(h * APTGPU_GEOLOC_PX) : nullptr);
+        HostSignal hr(rows_out ? host_alloc<float>(n) : nullptr);
         geo::run_host(signal, n, track, count, c.geom, c.st, hl.get(), hc.get(), hr.get(), info);
         if (latlon) *latlon = hl.release();
         if (cos_sun) *cos_sun = hc.release();
@@ -97,10 +97,8 @@ int aptgpu_geolocate(const aptgpu_context *ctx, const float *signal, size_t n, c
         if (cos_sun) d_cos.alloc(px + 16);
         if (rows_out) d_rows = sc.upload(signal, n);  // normalised in place, then copied back
         ws.alloc(apt::gpu::geoloc_ws_bytes(h));
-        dev.prepare_track(s, h);
         apt::gpu::GeolocLaunch l{};
         l.x = d_rows.ptr;
-        l.n = l.cap = h * 2080u;
         l.positions = sat_positions;
         l.n_positions = n_positions;
         l.sat = orbit ? &sat.call : nullptr;
@@ -109,17 +107,12 @@ int aptgpu_geolocate(const aptgpu_context *ctx, const float *signal, size_t n, c
         l.latlon = d_latlon.ptr;
         l.cos_sun = d_cos.ptr;
         l.rows = d_rows.ptr;
-        apt::gpu::geoloc_track(s, l, dev, ws.ptr);
-        apt::gpu::geoloc_rows(s, l, dev, ws.ptr);
-        apt::gpu::geoloc_pixels(s, l, dev, ws.ptr);
-        apt::hip_check(hipGetLastError(), "kernel launch (geolocation stage)");
-        apt::gpu::GeolocRecord r{};
-        apt::hip_check(hipMemcpyAsync(&r, apt::gpu::geoloc_ws_record(ws.ptr), sizeof r, hipMemcpyDeviceToHost, s),
-                       "hipMemcpyAsync D2H");
-        apt::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
+        // the call as one job of the row stages: whole rows only, (res, n, cap) = (null, h * 2080, h * 2080)
+        apt::enqueue_geoloc(nullptr, apt::ImageJob{s, d_rows.ptr, nullptr, h * 2080u, h * 2080u}, l, dev, ws.ptr);
+        const apt::gpu::GeolocRecord r = read_record(s, apt::gpu::geoloc_ws_record(ws.ptr));
         apt::gpu::geoloc_record_to_public(r, info);
         if (r.status != 0) throw Error{ErrorKind::Internal, geo::reason_text(r.reason)};
-        std::unique_ptr<double, HostFree> hl(latlon ? host_alloc<double>(2 * px) : nullptr);
+        HostPtr<double> hl(latlon ? host_alloc<double>(2 * px) : nullptr);
         if (latlon && px)
             apt::hip_check(hipMemcpyAsync(hl.get(), d_latlon.ptr, 2 * px * sizeof(double), hipMemcpyDeviceToHost, s),
                            "hipMemcpyAsync D2H");
@@ -171,7 +164,7 @@ int aptgpu_plan_geolocate_device(aptgpu_plan *plan, int count, const float *cons
         // rewrites them in place, which the d_out == d_rows case above left out of the list)
         for (size_t a = 0; a < spans.size(); ++a)
             for (size_t b = a + 1; b < spans.size(); ++b)
-                if (!(spans[a].rows && spans[b].rows) && geo::overlaps(spans[a].p, spans[a].bytes, spans[b].p, spans[b].bytes))
+                if (!(spans[a].rows && spans[b].rows) && overlaps(spans[a].p, spans[a].bytes, spans[b].p, spans[b].bytes))
                     throw Error{ErrorKind::Invalid, "geoloc: an output overlaps a rows buffer or another output"};
         if (!plan) throw Error{ErrorKind::Invalid, "geoloc: no plan"};
         if (static_cast<size_t>(count) > plan->last_slots.size())
@@ -199,24 +192,13 @@ int aptgpu_plan_geolocate_device(aptgpu_plan *plan, int count, const float *cons
 
 int aptgpu_plan_geoloc_results(aptgpu_plan *plan, int count, aptgpu_geoloc_result *results)
 {
-    if (!plan || count < 0 || (!results && count)) return APTGPU_ERR_INVALID;
-    if (static_cast<size_t>(count) > plan->last_slots.size()) return APTGPU_ERR_INVALID;
-    for (int i = 0; i < count; ++i)
-        if (!plan->slot_of(i).geoloc_ws.ptr) return APTGPU_ERR_INVALID;
-    try {
-        apt::hip_check(hipSetDevice(plan->device), "hipSetDevice");
-        plan->sync_all();
-        for (int i = 0; i < count; ++i) {
-            apt::gpu::GeolocRecord r{};
-            apt::hip_check(hipMemcpy(&r, apt::gpu::geoloc_ws_record(plan->slot_of(i).geoloc_ws.ptr), sizeof r,
-                                     hipMemcpyDeviceToHost),
-                           "hipMemcpy");
-            apt::gpu::geoloc_record_to_public(r, results + i);
-        }
-    } catch (const apt::Error &) {
-        return APTGPU_ERR_HIP;
-    }
-    return APTGPU_OK;
+    return plan_results(
+        plan, count, results,
+        [&](int i) -> apt::gpu::GeolocRecord * {
+            void *ws = plan->slot_of(i).geoloc_ws.ptr;
+            return ws ? apt::gpu::geoloc_ws_record(ws) : nullptr;
+        },
+        [&](int i, const apt::gpu::GeolocRecord &r) { apt::gpu::geoloc_record_to_public(r, results + i); });
 }
 
 }  // extern "C"

@@ -121,14 +121,7 @@ struct ImageCall {
     {
         return ImageJob{sc.stream, d_x.ptr, nullptr, n, n, ws.ptr, d_info.ptr};
     }
-    static ImageResult read(hipStream_t s, const ImageResult *d)
-    {
-        ImageResult r{};
-        apt::hip_check(hipMemcpyAsync(&r, d, sizeof r, hipMemcpyDeviceToHost, s), "hipMemcpyAsync D2H");
-        apt::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
-        return r;
-    }
-    ImageResult info() { return read(sc.stream, d_info.ptr); }
+    ImageResult info() { return read_record(sc.stream, d_info.ptr); }
     void limits(float *low, float *high)
     {
         float lim[2] = {0.f, 0.f};
@@ -1058,7 +1051,7 @@ int aptgpu_project_image(const aptgpu_context *ctx, const uint8_t *image, uint32
         apt::hip_check(hipMemcpyAsync(d_info.ptr, &rec, sizeof rec, hipMemcpyHostToDevice, s), "hipMemcpyAsync H2D");
         apt::enqueue_image_outputs(nullptr, q, &j, 1);
         apt::hip_check(hipGetLastError(), "kernel launch (reprojection)");
-        const ImageResult res = ImageCall::read(s, d_info.ptr);
+        const ImageResult res = read_record(s, d_info.ptr);
         throw_for(res, APTGPU_CONTRAST_MINMAX);
         if (q.png)
             to_host(s, d_png.ptr, res.reserved, out, n_out);
@@ -1213,24 +1206,20 @@ int aptgpu_composite_images(const aptgpu_context *ctx, int count, const uint8_t 
                        "hipMemcpyAsync H2D");
         apt::enqueue_image_outputs(nullptr, q, jobs.data(), count);
         apt::hip_check(hipGetLastError(), "kernel launch (composite)");
-        const ImageResult res = ImageCall::read(s, dev.info);
+        const ImageResult res = read_record(s, dev.info);
         throw_for(res, APTGPU_CONTRAST_MINMAX);
+        HostPtr<uint8_t> cov;
         if (coverage) {
+            uint8_t *h = nullptr;
             size_t n_cov = 0;
-            to_host(s, d_cov.ptr, pixels, coverage, &n_cov);
+            to_host(s, d_cov.ptr, pixels, &h, &n_cov);
+            cov.reset(h);
         }
-        try {
-            if (q.png)
-                to_host(s, d_png.ptr, res.reserved, out, n_out);
-            else
-                to_host(s, d_grid.ptr, q.comp.out_cap, out, n_out);
-        } catch (...) {
-            if (coverage) {
-                std::free(*coverage);
-                *coverage = nullptr;
-            }
-            throw;
-        }
+        if (q.png)
+            to_host(s, d_png.ptr, res.reserved, out, n_out);
+        else
+            to_host(s, d_grid.ptr, q.comp.out_cap, out, n_out);
+        if (coverage) *coverage = cov.release();
         return APTGPU_OK;
     });
 }
@@ -1347,16 +1336,12 @@ int aptgpu_map_read_shapefile(const char *path, int shape_type, double **xy, siz
     *n_points = *n_parts = 0;
     return guarded(err, err_cap, [&] {
         const apt::map::Layer l = apt::map::read_shp(path, shape_type);
-        double *h = host_alloc<double>(l.xy.size());
-        uint32_t *o = static_cast<uint32_t *>(std::malloc(l.parts.size() * sizeof(uint32_t)));
-        if (!o) {
-            std::free(h);
-            throw std::bad_alloc();
-        }
-        std::memcpy(h, l.xy.data(), l.xy.size() * sizeof(double));
-        std::memcpy(o, l.parts.data(), l.parts.size() * sizeof(uint32_t));
-        *xy = h;
-        *part_offsets = o;
+        HostPtr<double> h(host_alloc<double>(l.xy.size()));
+        HostPtr<uint32_t> o(host_alloc<uint32_t>(l.parts.size()));
+        std::memcpy(h.get(), l.xy.data(), l.xy.size() * sizeof(double));
+        std::memcpy(o.get(), l.parts.data(), l.parts.size() * sizeof(uint32_t));
+        *xy = h.release();
+        *part_offsets = o.release();
         *n_points = l.points();
         *n_parts = l.parts.size() - 1;
         return APTGPU_OK;
@@ -1374,19 +1359,12 @@ int aptgpu_despeckle(const aptgpu_context *ctx, const float *signal, size_t n,
     return guarded(err, err_cap, [&] {
         const apt::despeckle::Settings st = apt::despeckle::check_settings(settings);
         ImageCall c(ctx, signal, n);
-        hipStream_t s = c.sc.stream;
         apt::DeviceBuffer<float> d_out;
         apt::DeviceBuffer<apt::gpu::DespeckleResult> d_rec;
         d_out.alloc(n + 16);
         d_rec.alloc(1);
-        if (st.threshold != 0.f && n >= 2080)  // (the limits of the unfiltered signal, as Percent(0.98) reports them)
-            apt::gpu::image_percent(s, c.d_x.ptr, nullptr, n, n, 0.98f, c.ws.ptr, c.d_info.ptr);
-        apt::gpu::despeckle(s, c.d_x.ptr, nullptr, n, n, st.radius, st.threshold,
-                            apt::gpu::image_ws_pointers(c.ws.ptr, n).limits, c.d_info.ptr, d_out.ptr, d_rec.ptr);
-        apt::hip_check(hipGetLastError(), "kernel launch (despeckle stage)");
-        apt::gpu::DespeckleResult r{};
-        apt::hip_check(hipMemcpyAsync(&r, d_rec.ptr, sizeof r, hipMemcpyDeviceToHost, s), "hipMemcpyAsync D2H");
-        apt::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
+        apt::enqueue_despeckle(nullptr, c.job(), st.radius, st.threshold, d_out.ptr, d_rec.ptr);
+        const apt::gpu::DespeckleResult r = read_record(c.sc.stream, d_rec.ptr);
         if (info) std::memcpy(info, &r, sizeof r);
         if (r.status != 0) throw Error{ErrorKind::Internal, apt::despeckle::reason_text(r.reason)};
         *out = c.sc.download_malloc(d_out.ptr, n);
@@ -1401,14 +1379,9 @@ int aptgpu_despeckle_host(const float *signal, size_t n, const aptgpu_despeckle_
     *out = nullptr;
     return guarded(err, err_cap, [&] {
         const apt::despeckle::Settings st = apt::despeckle::check_settings(settings);
-        float *h = host_alloc<float>(n);
-        try {
-            apt::despeckle::run_host(signal, n, st, h, info);
-        } catch (...) {
-            std::free(h);
-            throw;
-        }
-        *out = h;
+        HostSignal h(host_alloc<float>(n));
+        apt::despeckle::run_host(signal, n, st, h.get(), info);
+        *out = h.release();
         return APTGPU_OK;
     });
 }
@@ -1424,13 +1397,8 @@ int aptgpu_plan_despeckle_device(aptgpu_plan *plan, int count, const float *cons
             throw Error{ErrorKind::Invalid, "count exceeds the recordings of the last decode call"};
         for (int i = 0; i < count; ++i) {
             if (!d_rows[i] || !d_out[i]) throw Error{ErrorKind::Invalid, "null device pointer"};
-            const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out[i]);
-            const uintptr_t o1 = o0 + rows_cap[i] * 2080u * sizeof(float);
-            for (int j = 0; j < count; ++j) {
-                const uintptr_t r0 = reinterpret_cast<uintptr_t>(d_rows[j]);
-                const uintptr_t r1 = r0 + rows_cap[j] * 2080u * sizeof(float);
-                if (r0 && ((o0 < r1 && r0 < o1) || o0 == r0)) throw Error{ErrorKind::Invalid, "d_out overlaps d_rows"};
-            }
+            if (overlaps_rows(d_out[i], rows_cap[i] * 2080u * sizeof(float), count, d_rows, rows_cap))
+                throw Error{ErrorKind::Invalid, "d_out overlaps d_rows"};
         }
         apt::hip_check(hipSetDevice(plan->device), "hipSetDevice");
         for (int i = 0; i < count; ++i)
@@ -1442,21 +1410,13 @@ int aptgpu_plan_despeckle_device(aptgpu_plan *plan, int count, const float *cons
 
 int aptgpu_plan_despeckle_results(aptgpu_plan *plan, int count, aptgpu_despeckle_result *results)
 {
-    if (!plan || count < 0 || (!results && count)) return APTGPU_ERR_INVALID;
-    if (static_cast<size_t>(count) > plan->last_slots.size()) return APTGPU_ERR_INVALID;
-    for (int i = 0; i < count; ++i)
-        if (!plan->slot_of(i).despeckle_ws.ptr) return APTGPU_ERR_INVALID;
-    try {
-        apt::hip_check(hipSetDevice(plan->device), "hipSetDevice");
-        plan->sync_all();
-        for (int i = 0; i < count; ++i)
-            apt::hip_check(hipMemcpy(results + i, apt::gpu::despeckle_ws_record(plan->slot_of(i).despeckle_ws.ptr),
-                                     sizeof(aptgpu_despeckle_result), hipMemcpyDeviceToHost),
-                           "hipMemcpy");
-    } catch (const apt::Error &) {
-        return APTGPU_ERR_HIP;
-    }
-    return APTGPU_OK;
+    return plan_results(
+        plan, count, results,
+        [&](int i) -> apt::gpu::DespeckleResult * {
+            void *ws = plan->slot_of(i).despeckle_ws.ptr;
+            return ws ? apt::gpu::despeckle_ws_record(ws) : nullptr;
+        },
+        [&](int i, const apt::gpu::DespeckleResult &r) { std::memcpy(results + i, &r, sizeof r); });
 }
 
 int aptgpu_calibrate_thermal(const aptgpu_context *ctx, const float *signal, size_t n,
@@ -1480,30 +1440,16 @@ int aptgpu_calibrate_thermal(const aptgpu_context *ctx, const float *signal, siz
         d_kelvin.alloc(h * APTGPU_THERMAL_PX + 16);
         d_image.alloc(image_bytes + 16);
         ws.alloc(apt::gpu::thermal_ws_bytes());
-        apt::gpu::ThermalLaunch l = thermal_launch(st, c.d_x.ptr, d_kelvin.ptr, st.image_channels ? d_image.ptr : nullptr);
-        l.n = l.cap = n;
-        apt::gpu::image_telemetry(s, c.d_x.ptr, nullptr, n, n, c.ws.ptr, apt::gpu::thermal_ws_telemetry(ws.ptr), false);
-        apt::gpu::thermal_space(s, l, ws.ptr);
-        apt::gpu::thermal_setup(s, l, thermal_coeffs(*coeffs), ws.ptr);
-        apt::gpu::thermal_map(s, l, thermal_table(st), ws.ptr);
-        apt::hip_check(hipGetLastError(), "kernel launch (thermal stage)");
-        apt::gpu::ThermalRecord r{};
-        apt::hip_check(hipMemcpyAsync(&r, apt::gpu::thermal_ws_record(ws.ptr), sizeof r, hipMemcpyDeviceToHost, s),
-                       "hipMemcpyAsync D2H");
-        apt::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
+        apt::enqueue_thermal(nullptr, c.job(),
+                             thermal_launch(st, c.d_x.ptr, d_kelvin.ptr, st.image_channels ? d_image.ptr : nullptr),
+                             thermal_coeffs(*coeffs), thermal_table(st), ws.ptr);
+        const apt::gpu::ThermalRecord r = read_record(s, apt::gpu::thermal_ws_record(ws.ptr));
         if (info) apt::gpu::thermal_record_to_public(r, info);
         if (r.status != 0) throw Error{ErrorKind::Internal, apt::thermal::reason_text(r.reason)};
-        float *hk = c.sc.download_malloc(d_kelvin.ptr, h * APTGPU_THERMAL_PX);
-        if (st.image_channels) {
-            size_t n_out = 0;
-            try {
-                to_host(s, d_image.ptr, image_bytes, image, &n_out);
-            } catch (...) {
-                std::free(hk);
-                throw;
-            }
-        }
-        *kelvin = hk;
+        HostSignal hk(c.sc.download_malloc(d_kelvin.ptr, h * APTGPU_THERMAL_PX));
+        size_t n_out = 0;
+        if (st.image_channels) to_host(s, d_image.ptr, image_bytes, image, &n_out);
+        *kelvin = hk.release();
         return APTGPU_OK;
     });
 }
@@ -1520,18 +1466,11 @@ int aptgpu_calibrate_thermal_host(const float *signal, size_t n, const aptgpu_th
         if ((st.image_channels != 0) != (image != nullptr))
             throw Error{ErrorKind::Invalid, "thermal: image is required exactly when image_channels is not 0"};
         const size_t h = n / 2080u;
-        float *hk = host_alloc<float>(h * APTGPU_THERMAL_PX);
-        uint8_t *hi = nullptr;
-        try {
-            if (st.image_channels) hi = host_alloc<uint8_t>(h * 2080u * static_cast<size_t>(st.image_channels));
-            apt::thermal::run_host(signal, n, *coeffs, st, hk, hi, info);
-        } catch (...) {
-            std::free(hk);
-            std::free(hi);
-            throw;
-        }
-        *kelvin = hk;
-        if (image) *image = hi;
+        HostSignal hk(host_alloc<float>(h * APTGPU_THERMAL_PX));
+        HostPtr<uint8_t> hi(st.image_channels ? host_alloc<uint8_t>(h * 2080u * static_cast<size_t>(st.image_channels)) : nullptr);
+        apt::thermal::run_host(signal, n, *coeffs, st, hk.get(), hi.get(), info);
+        *kelvin = hk.release();
+        if (image) *image = hi.release();
         return APTGPU_OK;
     });
 }
@@ -1548,21 +1487,13 @@ int aptgpu_plan_calibrate_thermal_device(aptgpu_plan *plan, int count, const flo
             throw Error{ErrorKind::Invalid, "thermal: d_images is required exactly when image_channels is not 0"};
         if (static_cast<size_t>(count) > plan->last_slots.size())
             throw Error{ErrorKind::Invalid, "count exceeds the recordings of the last decode call"};
-        const auto overlaps_rows = [&](const void *p, size_t bytes) {
-            const uintptr_t o0 = reinterpret_cast<uintptr_t>(p), o1 = o0 + bytes;
-            for (int j = 0; j < count; ++j) {
-                const uintptr_t r0 = reinterpret_cast<uintptr_t>(d_rows[j]);
-                const uintptr_t r1 = r0 + rows_cap[j] * 2080u * sizeof(float);
-                if (r0 && ((o0 < r1 && r0 < o1) || o0 == r0)) return true;
-            }
-            return false;
-        };
         for (int i = 0; i < count; ++i) {
             if (!d_rows[i] || !d_kelvin[i] || (d_images && !d_images[i]))
                 throw Error{ErrorKind::Invalid, "null device pointer"};
-            if (overlaps_rows(d_kelvin[i], rows_cap[i] * APTGPU_THERMAL_PX * sizeof(float)))
+            if (overlaps_rows(d_kelvin[i], rows_cap[i] * APTGPU_THERMAL_PX * sizeof(float), count, d_rows, rows_cap))
                 throw Error{ErrorKind::Invalid, "d_kelvin overlaps d_rows"};
-            if (d_images && overlaps_rows(d_images[i], rows_cap[i] * 2080u * static_cast<size_t>(st.image_channels)))
+            if (d_images && overlaps_rows(d_images[i], rows_cap[i] * 2080u * static_cast<size_t>(st.image_channels), count,
+                                          d_rows, rows_cap))
                 throw Error{ErrorKind::Invalid, "d_images overlaps d_rows"};
             if (st.image_channels == 4 && (reinterpret_cast<uintptr_t>(d_images[i]) & 3u))
                 throw Error{ErrorKind::Invalid, "d_images must be 4-byte aligned"};
@@ -1579,49 +1510,28 @@ int aptgpu_plan_calibrate_thermal_device(aptgpu_plan *plan, int count, const flo
 
 int aptgpu_plan_thermal_results(aptgpu_plan *plan, int count, aptgpu_thermal_result *results)
 {
-    if (!plan || count < 0 || (!results && count)) return APTGPU_ERR_INVALID;
-    if (static_cast<size_t>(count) > plan->last_slots.size()) return APTGPU_ERR_INVALID;
-    for (int i = 0; i < count; ++i)
-        if (!plan->slot_of(i).thermal_ws.ptr) return APTGPU_ERR_INVALID;
-    try {
-        apt::hip_check(hipSetDevice(plan->device), "hipSetDevice");
-        plan->sync_all();
-        for (int i = 0; i < count; ++i) {
-            apt::gpu::ThermalRecord r{};
-            apt::hip_check(hipMemcpy(&r, apt::gpu::thermal_ws_record(plan->slot_of(i).thermal_ws.ptr), sizeof r,
-                                     hipMemcpyDeviceToHost),
-                           "hipMemcpy");
-            apt::gpu::thermal_record_to_public(r, results + i);
-        }
-    } catch (const apt::Error &) {
-        return APTGPU_ERR_HIP;
-    }
-    return APTGPU_OK;
+    return plan_results(
+        plan, count, results,
+        [&](int i) -> apt::gpu::ThermalRecord * {
+            void *ws = plan->slot_of(i).thermal_ws.ptr;
+            return ws ? apt::gpu::thermal_ws_record(ws) : nullptr;
+        },
+        [&](int i, const apt::gpu::ThermalRecord &r) { apt::gpu::thermal_record_to_public(r, results + i); });
 }
 
 int aptgpu_plan_image_results(aptgpu_plan *plan, int count, aptgpu_image_result *results)
 {
-    if (!plan || count < 0 || (!results && count)) return APTGPU_ERR_INVALID;
-    // one record past the passes of the latest composite: the composite's own
+    if (!plan || count < 0 || (!results && count) || !plan->d_image_results.ptr) return APTGPU_ERR_INVALID;
+    // one record past the passes of the latest composite: the composite's own, read behind the passes'
     const bool with_composite = plan->composite_count >= 0 && count == plan->composite_count + 1;
     if (with_composite) --count;
-    if (static_cast<size_t>(count) > plan->last_slots.size() || !plan->d_image_results.ptr)
-        return APTGPU_ERR_INVALID;
-    try {
-        apt::hip_check(hipSetDevice(plan->device), "hipSetDevice");
-        plan->sync_all();
-        if (with_composite)
-            apt::hip_check(hipMemcpy(results + count, plan->composite[static_cast<size_t>(plan->last_stream)]->info,
-                                     sizeof(aptgpu_image_result), hipMemcpyDeviceToHost),
-                           "hipMemcpy");
-        for (int i = 0; i < count; ++i)
-            apt::hip_check(hipMemcpy(results + i,
-                                     plan->d_image_results.ptr + plan->last_slots[static_cast<size_t>(i)],
-                                     sizeof(aptgpu_image_result), hipMemcpyDeviceToHost),
-                           "hipMemcpy");
-    } catch (const apt::Error &) {
+    const int rc = plan_results(
+        plan, count, results, [&](int i) { return plan->d_image_results.ptr + plan->last_slots[static_cast<size_t>(i)]; },
+        [&](int i, const ImageResult &r) { copy_out(results + i, r); });
+    if (rc != APTGPU_OK || !with_composite) return rc;
+    if (hipMemcpy(results + count, plan->composite[static_cast<size_t>(plan->last_stream)]->info,
+                  sizeof(aptgpu_image_result), hipMemcpyDeviceToHost) != hipSuccess)
         return APTGPU_ERR_HIP;
-    }
     return APTGPU_OK;
 }
 

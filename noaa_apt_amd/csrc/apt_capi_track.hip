@@ -107,6 +107,14 @@ uint64_t *positions_malloc(const std::vector<uint32_t> &p)
     return out;
 }
 
+// the record into the caller's struct, whose struct_size stays the caller's
+void put_record(aptgpu_track_result *out, const TrackResult &r)
+{
+    const uint32_t size = out->struct_size;
+    std::memcpy(out, &r, sizeof r);
+    out->struct_size = size;
+}
+
 void fail_record(const TrackResult &r)
 {
     if (r.status != 0) throw Error{ErrorKind::Internal, apt::track::reason_text(r.reason)};
@@ -168,39 +176,34 @@ void run_host_arrays(const aptgpu_context *ctx, int count, const float *const *s
         }
         apt::hip_check(hipGetLastError(), "kernel launch (track stage)");
     }
-    try {
-        for (int i = 0; i < count; ++i) {
-            const size_t k = static_cast<size_t>(i);
-            if (!want_track) {
-                scores[i] = sc.download_malloc(ws[k].score, geo[k].M);
-                continue;
-            }
-            TrackResult r{};
-            apt::hip_check(hipMemcpyAsync(&r, ws[k].rec, sizeof r, hipMemcpyDeviceToHost, s), "hipMemcpyAsync D2H");
-            apt::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
-            const uint32_t size = results[i].struct_size;
-            std::memcpy(results + i, &r, sizeof r);
-            results[i].struct_size = size;
-            fail_record(r);
-            std::vector<uint32_t> p(r.n_positions);
-            if (!p.empty())
-                apt::hip_check(hipMemcpyAsync(p.data(), ws[k].pos, p.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s),
-                               "hipMemcpyAsync D2H");
-            scores[i] = sc.download_malloc(ws[k].pscore, r.n_positions);
-            apt::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
-            positions[i] = positions_malloc(p);
-            if (rows) rows[i] = sc.download_malloc(d_rows[k].ptr, static_cast<size_t>(r.n_rows) * 2080u);
+    // (every recording's outputs are handed out together, once the last one is on the host)
+    std::vector<HostPtr<uint64_t>> out_pos(static_cast<size_t>(count));
+    std::vector<HostSignal> out_scores(static_cast<size_t>(count)), out_rows(static_cast<size_t>(count));
+    for (int i = 0; i < count; ++i) {
+        const size_t k = static_cast<size_t>(i);
+        if (!want_track) {
+            out_scores[k].reset(sc.download_malloc(ws[k].score, geo[k].M));
+            continue;
         }
-    } catch (...) {
-        for (int i = 0; i < count; ++i) {
-            if (positions) { std::free(positions[i]); positions[i] = nullptr; }
-            if (scores) { std::free(scores[i]); scores[i] = nullptr; }
-            if (rows) { std::free(rows[i]); rows[i] = nullptr; }
-        }
-        (void)hipStreamSynchronize(s);
-        throw;
+        const TrackResult r = read_record(s, ws[k].rec);
+        put_record(results + i, r);
+        fail_record(r);
+        std::vector<uint32_t> p(r.n_positions);
+        if (!p.empty())
+            apt::hip_check(hipMemcpyAsync(p.data(), ws[k].pos, p.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s),
+                           "hipMemcpyAsync D2H");
+        out_scores[k].reset(sc.download_malloc(ws[k].pscore, r.n_positions));
+        apt::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
+        out_pos[k].reset(positions_malloc(p));
+        if (rows) out_rows[k].reset(sc.download_malloc(d_rows[k].ptr, static_cast<size_t>(r.n_rows) * 2080u));
     }
     apt::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
+    for (int i = 0; i < count; ++i) {
+        const size_t k = static_cast<size_t>(i);
+        if (positions) positions[i] = out_pos[k].release();
+        scores[i] = out_scores[k].release();
+        if (rows) rows[i] = out_rows[k].release();
+    }
 }
 
 }  // namespace
@@ -255,25 +258,17 @@ int aptgpu_track_sync_host(const float *signal, size_t n, uint32_t work_rate_hz,
         std::vector<uint32_t> p;
         apt::track::score_host(signal, g, s.data());
         apt::track::track_host(signal, n, g, st, s.data(), p, ps, rows ? &rw : nullptr, info);
-        uint64_t *out_p = positions_malloc(p);
-        float *out_s = nullptr, *out_r = nullptr, *out_all = nullptr;
-        try {
-            out_s = host_alloc<float>(ps.size());
-            if (rows) out_r = host_alloc<float>(rw.size());
-            if (score_out) out_all = host_alloc<float>(s.size());
-        } catch (...) {
-            std::free(out_p);
-            std::free(out_s);
-            std::free(out_r);
-            throw;
-        }
-        if (!ps.empty()) std::memcpy(out_s, ps.data(), ps.size() * sizeof(float));
-        if (out_r && !rw.empty()) std::memcpy(out_r, rw.data(), rw.size() * sizeof(float));
-        if (out_all) std::memcpy(out_all, s.data(), s.size() * sizeof(float));
-        *positions = out_p;
-        *scores = out_s;
-        if (rows) *rows = out_r;
-        if (score_out) *score_out = out_all;
+        HostPtr<uint64_t> out_p(positions_malloc(p));
+        HostSignal out_s(host_alloc<float>(ps.size()));
+        HostSignal out_r(rows ? host_alloc<float>(rw.size()) : nullptr);
+        HostSignal out_all(score_out ? host_alloc<float>(s.size()) : nullptr);
+        if (!ps.empty()) std::memcpy(out_s.get(), ps.data(), ps.size() * sizeof(float));
+        if (out_r && !rw.empty()) std::memcpy(out_r.get(), rw.data(), rw.size() * sizeof(float));
+        if (out_all) std::memcpy(out_all.get(), s.data(), s.size() * sizeof(float));
+        *positions = out_p.release();
+        *scores = out_s.release();
+        if (rows) *rows = out_r.release();
+        if (score_out) *score_out = out_all.release();
         return APTGPU_OK;
     });
 }
@@ -302,24 +297,14 @@ int aptgpu_plan_track_device(aptgpu_plan *plan, int count, const aptgpu_track_se
 
 int aptgpu_plan_track_results(aptgpu_plan *plan, int count, aptgpu_track_result *results)
 {
-    if (!plan || count < 0 || (!results && count)) return APTGPU_ERR_INVALID;
-    if (static_cast<size_t>(count) > plan->last_slots.size()) return APTGPU_ERR_INVALID;
-    for (int i = 0; i < count; ++i)
-        if (!plan->slot_of(i).track_ws.ptr || results[i].struct_size < sizeof(aptgpu_track_result)) return APTGPU_ERR_INVALID;
-    try {
-        apt::hip_check(hipSetDevice(plan->device), "hipSetDevice");
-        plan->sync_all();
-        for (int i = 0; i < count; ++i) {
-            const uint32_t size = results[i].struct_size;
-            apt::hip_check(hipMemcpy(results + i, plan->slot_of(i).track_ws.ptr, sizeof(aptgpu_track_result),
-                                     hipMemcpyDeviceToHost),
-                           "hipMemcpy");
-            results[i].struct_size = size;
-        }
-    } catch (const apt::Error &) {
-        return APTGPU_ERR_HIP;
-    }
-    return APTGPU_OK;
+    // (the record heads the slot's scratch; a struct too short for it is refused like a stage that never ran)
+    return plan_results(
+        plan, count, results,
+        [&](int i) -> TrackResult * {
+            if (results[i].struct_size < sizeof(aptgpu_track_result)) return nullptr;
+            return reinterpret_cast<TrackResult *>(plan->slot_of(i).track_ws.ptr);
+        },
+        [&](int i, const TrackResult &r) { put_record(results + i, r); });
 }
 
 int aptgpu_plan_track_positions(aptgpu_plan *plan, int i, uint64_t *pos, float *scores, size_t cap, size_t *n_positions)
@@ -389,32 +374,19 @@ int aptgpu_decode_tracked(const aptgpu_context *ctx, const aptgpu_settings *sett
         plan->sync_all();
         TrackWs ws;
         track_ws_layout(plan->slot_of(0).track_ws.ptr, plan->max_work_len, plan->spr, &ws);
-        TrackResult r{};
-        apt::hip_check(hipMemcpy(&r, ws.rec, sizeof r, hipMemcpyDeviceToHost), "hipMemcpy");
-        if (info) {
-            const uint32_t size = info->struct_size;
-            std::memcpy(info, &r, sizeof r);
-            info->struct_size = size;
-        }
+        const TrackResult r = read_record(s, ws.rec);
+        if (info) put_record(info, r);
         fail_record(r);
         Scratch sc(&c);
         std::vector<uint32_t> p(r.n_positions);
         if (!p.empty()) apt::hip_check(hipMemcpy(p.data(), ws.pos, p.size() * sizeof(uint32_t), hipMemcpyDeviceToHost), "hipMemcpy");
-        float *out_rows = sc.download_malloc(d_rows.ptr, static_cast<size_t>(r.n_rows) * 2080u);
-        float *out_scores = nullptr;
-        uint64_t *out_pos = nullptr;
-        try {
-            if (scores) out_scores = sc.download_malloc(ws.pscore, r.n_positions);
-            if (positions) out_pos = positions_malloc(p);
-        } catch (...) {
-            std::free(out_rows);
-            std::free(out_scores);
-            throw;
-        }
-        *rows_out = out_rows;
+        HostSignal out_rows(sc.download_malloc(d_rows.ptr, static_cast<size_t>(r.n_rows) * 2080u));
+        HostSignal out_scores(scores ? sc.download_malloc(ws.pscore, r.n_positions) : nullptr);
+        HostPtr<uint64_t> out_pos(positions ? positions_malloc(p) : nullptr);
+        *rows_out = out_rows.release();
         *n_out = static_cast<size_t>(r.n_rows) * 2080u;
-        if (scores) *scores = out_scores;
-        if (positions) *positions = out_pos;
+        if (scores) *scores = out_scores.release();
+        if (positions) *positions = out_pos.release();
         return APTGPU_OK;
     });
 }

@@ -1,6 +1,6 @@
 // apt_capi_util.hpp — helpers shared by the extern "C" translation units (apt_capi.hip,
 // apt_capi_image.hip, the stream units): error mapping, the null-argument refusal, malloc'd outputs, context callbacks,
-// a per-call stream.
+// a per-call stream, the readback of a stage's record (one-shot and plan), the buffer-overlap predicate.
 #pragma once
 
 #include <cstdio>
@@ -9,6 +9,7 @@
 #include <memory>
 #include <new>
 #include <string>
+#include <type_traits>
 
 #include "apt_kernels_track.hpp"
 #include "apt_plan.hpp"
@@ -92,10 +93,63 @@ inline float *download_malloc(const float *d, size_t n, hipStream_t s)
     }
     return p;
 }
+// A malloc'd output until the call has everything it hands out: released into the out-parameters last.
 struct HostFree {
     void operator()(void *p) const { std::free(p); }
 };
-using HostSignal = std::unique_ptr<float, HostFree>;
+template <typename T>
+using HostPtr = std::unique_ptr<T, HostFree>;
+using HostSignal = HostPtr<float>;
+
+// One record of a one-shot call: copied behind everything on s, waited for.
+template <typename T>
+T read_record(hipStream_t s, const T *d)
+{
+    T r{};
+    apt::hip_check(hipMemcpyAsync(&r, d, sizeof r, hipMemcpyDeviceToHost, s), "hipMemcpyAsync D2H");
+    apt::hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");
+    return r;
+}
+
+// The aptgpu_plan_*_results entry points: one record per recording of the first `count` of the last decode call, read
+// once every stream of the plan is idle.  record_of(i): where recording i's record is in HBM (null: its stage never ran
+// on that slot, which is refused before anything is waited for); publish(i, r): the record into results[i].
+template <typename RecordOf, typename Publish>
+int plan_results(aptgpu_plan *plan, int count, const void *results, RecordOf &&record_of, Publish &&publish)
+{
+    if (!plan || count < 0 || (!results && count)) return APTGPU_ERR_INVALID;
+    if (static_cast<size_t>(count) > plan->last_slots.size()) return APTGPU_ERR_INVALID;
+    for (int i = 0; i < count; ++i)
+        if (!record_of(i)) return APTGPU_ERR_INVALID;
+    try {
+        apt::hip_check(hipSetDevice(plan->device), "hipSetDevice");
+        plan->sync_all();
+        for (int i = 0; i < count; ++i) {
+            std::remove_cv_t<std::remove_pointer_t<decltype(record_of(i))>> r;
+            apt::hip_check(hipMemcpy(&r, record_of(i), sizeof r, hipMemcpyDeviceToHost), "hipMemcpy");
+            publish(i, r);
+        }
+    } catch (const Error &) {
+        return APTGPU_ERR_HIP;
+    }
+    return APTGPU_OK;
+}
+
+// base .. base + bytes of two buffers overlap: the half-open ranges intersect, or the starts are equal (an empty range
+// still has its place).  A null buffer overlaps nothing.
+inline bool overlaps(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
+{
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    if (!a0 || !b0) return false;
+    return (a0 < b0 + b_bytes && b0 < a0 + a_bytes) || a0 == b0;
+}
+// ... with any rows buffer of a plan call: rows_cap[j] rows of 2080 floats at d_rows[j]
+inline bool overlaps_rows(const void *p, size_t bytes, int count, const float *const *d_rows, const size_t *rows_cap)
+{
+    for (int j = 0; j < count; ++j)
+        if (overlaps(p, bytes, d_rows[j], rows_cap[j] * 2080u * sizeof(float))) return true;
+    return false;
+}
 
 // A signal that a step carries: in HBM (downloaded for the callback) or on the host already.
 struct StepSignal {

@@ -70,13 +70,6 @@ void check_call(const void *positions, const void *orbit, bool want_rows, bool h
     if (rows > kMaxRows) throw Error{ErrorKind::Invalid, "geoloc: more than 2^22 rows"};
 }
 
-bool overlaps(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
-{
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    if (!a0 || !b0) return false;
-    return (a0 < b0 + b_bytes && b0 < a0 + a_bytes) || a0 == b0;
-}
-
 const char *reason_text(int reason)
 {
     switch (reason) {

@@ -6,8 +6,11 @@
 
 #include "apt_kernels_color.hpp"
 #include "apt_kernels_composite.hpp"
+#include "apt_kernels_despeckle.hpp"
+#include "apt_kernels_geoloc.hpp"
 #include "apt_kernels_map.hpp"
 #include "apt_kernels_project.hpp"
+#include "apt_kernels_thermal.hpp"
 #include "apt_kernels_track.hpp"
 
 struct aptgpu_plan;
@@ -80,6 +83,20 @@ struct ImageJob {
 // behind everything.
 // The contrast limits of one job (noaa_apt.rs:141-175): the first kernel of every variant, which resets the record.
 void enqueue_image_limits(aptgpu_plan *plan, const ImageJob &j, int contrast, float percent);
+// The row stages in front of the image stage, one job each.  Of the job they read (stream, rows, res, n, cap, ws) and
+// `info` where it is said; the stage's own scratch and outputs travel as arguments.
+// Despeckle (apt_kernels_despeckle.hpp): with a threshold the 98 % limits of the rows into j.ws, their record into
+// j.info, then one k_despeckle launch into d_out with its record in *rec.  (A one-shot call of less than a row has no
+// limits to take: its launch is left out.)
+void enqueue_despeckle(aptgpu_plan *plan, const ImageJob &j, int radius, float threshold, float *d_out,
+                       apt::gpu::DespeckleResult *rec);
+// Thermal calibration (apt_kernels_thermal.hpp): the telemetry launches into j.ws with their record in thermal_ws, then
+// k_thermal_space, k_thermal_setup and k_thermal_map.  l.x is the job's rows; l.res, n and cap are filled in here.
+void enqueue_thermal(aptgpu_plan *plan, const ImageJob &j, apt::gpu::ThermalLaunch l, const apt::gpu::ThermalCoeffs &coeffs,
+                     const apt::gpu::ThermalTable &table, void *thermal_ws);
+// Geolocation (apt_kernels_geoloc.hpp): the track's launches into dev, prepared here for cap / 2080 rows, then
+// k_geoloc_rows and k_geoloc.  l.x is the job's rows; l.res, n and cap are filled in here.
+void enqueue_geoloc(aptgpu_plan *plan, const ImageJob &j, apt::gpu::GeolocLaunch l, apt::map::Device &dev, void *geoloc_ws);
 // Equalisation and colour of one job, behind its limits.
 void enqueue_image_color(aptgpu_plan *plan, const ImageRequest &q, const ImageRequest::Recording &r, const ImageJob &j);
 // What follows the colour, stage by stage and job by job within a stage: the overlay, then the reprojection (behind

@@ -168,8 +168,6 @@ Geom check_geom(const aptgpu_map_settings *map);
 // What every entry point refuses before it touches a device: both or neither of positions and orbit, rows asked for
 // without a signal, more than kMaxRows rows.
 void check_call(const void *positions, const void *orbit, bool want_rows, bool have_signal, size_t rows);
-// base..base+bytes of two buffers overlap
-bool overlaps(const void *a, size_t a_bytes, const void *b, size_t b_bytes);
 const char *reason_text(int reason);
 // delta and the sub-solar longitude in (-pi, pi], radians
 void sun_position(int64_t unix_ms, double out[2]);

@@ -784,6 +784,50 @@ void aptgpu_plan::enqueue_image(int i, const float *d_rows, uint64_t rows_cap_fl
     apt::hip_check(hipGetLastError(), "kernel launch (image stage)");
 }
 
+void apt::enqueue_despeckle(aptgpu_plan *plan, const ImageJob &j, int radius, float threshold, float *d_out,
+                            apt::gpu::DespeckleResult *rec)
+{
+    using namespace apt::gpu;
+    hipStream_t s = j.stream;
+    if (threshold != 0.f && (j.res || j.n >= 2080))  // (the limits of the unfiltered signal, as Percent(0.98) reports them)
+        enqueue_image_limits(plan, j, APTGPU_CONTRAST_PERCENT, 0.98f);
+    launch_timed(plan, s, "image_despeckle", [&] {
+        apt::gpu::despeckle(s, j.rows, j.res, j.n, j.cap, radius, threshold, image_ws_pointers(j.ws, j.cap).limits, j.info,
+                            d_out, rec);
+    });
+    apt::hip_check(hipGetLastError(), "kernel launch (despeckle stage)");
+}
+
+void apt::enqueue_thermal(aptgpu_plan *plan, const ImageJob &j, apt::gpu::ThermalLaunch l,
+                          const apt::gpu::ThermalCoeffs &coeffs, const apt::gpu::ThermalTable &table, void *ws)
+{
+    using namespace apt::gpu;
+    hipStream_t s = j.stream;
+    l.res = j.res;
+    l.n = j.n;
+    l.cap = j.cap;
+    launch_timed(plan, s, "image_telemetry",
+                 [&] { image_telemetry(s, j.rows, j.res, j.n, j.cap, j.ws, thermal_ws_telemetry(ws), false); });
+    launch_timed(plan, s, "image_thermal_space", [&] { thermal_space(s, l, ws); });
+    launch_timed(plan, s, "image_thermal_setup", [&] { thermal_setup(s, l, coeffs, ws); });
+    launch_timed(plan, s, "image_thermal_map", [&] { thermal_map(s, l, table, ws); });
+    apt::hip_check(hipGetLastError(), "kernel launch (thermal stage)");
+}
+
+void apt::enqueue_geoloc(aptgpu_plan *plan, const ImageJob &j, apt::gpu::GeolocLaunch l, apt::map::Device &dev, void *ws)
+{
+    using namespace apt::gpu;
+    hipStream_t s = j.stream;
+    l.res = j.res;
+    l.n = j.n;
+    l.cap = j.cap;
+    dev.prepare_track(s, static_cast<size_t>(j.cap / 2080u));
+    launch_timed(plan, s, "image_geoloc_track", [&] { geoloc_track(s, l, dev, ws); });
+    launch_timed(plan, s, "image_geoloc_rows", [&] { geoloc_rows(s, l, dev, ws); });
+    launch_timed(plan, s, "image_geoloc", [&] { geoloc_pixels(s, l, dev, ws); });
+    apt::hip_check(hipGetLastError(), "kernel launch (geolocation stage)");
+}
+
 void aptgpu_plan::enqueue_despeckle(int i, const float *d_rows, uint64_t rows_cap_floats, int radius, float threshold,
                                     float *d_out)
 {
@@ -791,56 +835,31 @@ void aptgpu_plan::enqueue_despeckle(int i, const float *d_rows, uint64_t rows_ca
     const ImageTarget t = image_target(i, rows_cap_floats);
     Slot &sl = t.slot;
     if (!sl.despeckle_ws.ptr) sl.despeckle_ws.alloc(despeckle_ws_bytes());
-    ImageResult *lim_info = despeckle_ws_limits_info(sl.despeckle_ws.ptr);
-    const float *limits = image_ws_pointers(t.ws, t.cap).limits;
-    if (threshold != 0.f)
-        timed(t.stream, "image_percent", [&] { image_percent(t.stream, d_rows, t.res, 0, t.cap, 0.98f, t.ws, lim_info); });
-    timed(t.stream, "image_despeckle", [&] {
-        despeckle(t.stream, d_rows, t.res, 0, t.cap, radius, threshold, limits, lim_info, d_out,
-                  despeckle_ws_record(sl.despeckle_ws.ptr));
-    });
-    apt::hip_check(hipGetLastError(), "kernel launch (despeckle stage)");
+    apt::ImageJob j = image_job(t, d_rows);
+    j.info = despeckle_ws_limits_info(sl.despeckle_ws.ptr);  // (the limits' record; the image stage's stays as it is)
+    apt::enqueue_despeckle(this, j, radius, threshold, d_out, despeckle_ws_record(sl.despeckle_ws.ptr));
 }
 
-void aptgpu_plan::enqueue_thermal(int i, uint64_t rows_cap_floats, apt::gpu::ThermalLaunch l,
+void aptgpu_plan::enqueue_thermal(int i, uint64_t rows_cap_floats, const apt::gpu::ThermalLaunch &l,
                                   const apt::gpu::ThermalCoeffs &coeffs, const apt::gpu::ThermalTable &table)
 {
-    using namespace apt::gpu;
     const ImageTarget t = image_target(i, rows_cap_floats);
     Slot &sl = t.slot;
-    if (!sl.thermal_ws.ptr) sl.thermal_ws.alloc(thermal_ws_bytes());
-    void *ws = sl.thermal_ws.ptr;
-    l.res = t.res;
-    l.n = 0;
-    l.cap = t.cap;
-    timed(t.stream, "image_telemetry",
-          [&] { image_telemetry(t.stream, l.x, t.res, 0, t.cap, t.ws, thermal_ws_telemetry(ws), false); });
-    timed(t.stream, "image_thermal_space", [&] { thermal_space(t.stream, l, ws); });
-    timed(t.stream, "image_thermal_setup", [&] { thermal_setup(t.stream, l, coeffs, ws); });
-    timed(t.stream, "image_thermal_map", [&] { thermal_map(t.stream, l, table, ws); });
-    apt::hip_check(hipGetLastError(), "kernel launch (thermal stage)");
+    if (!sl.thermal_ws.ptr) sl.thermal_ws.alloc(apt::gpu::thermal_ws_bytes());
+    apt::enqueue_thermal(this, image_job(t, l.x), l, coeffs, table, sl.thermal_ws.ptr);
 }
 
-void aptgpu_plan::enqueue_geoloc(int i, uint64_t rows_cap_floats, apt::gpu::GeolocLaunch l)
+void aptgpu_plan::enqueue_geoloc(int i, uint64_t rows_cap_floats, const apt::gpu::GeolocLaunch &l)
 {
-    using namespace apt::gpu;
     const ImageTarget t = image_target(i, rows_cap_floats);
     Slot &sl = t.slot;
-    l.res = t.res;
-    l.n = 0;
-    l.cap = t.cap;
     const size_t rows = static_cast<size_t>(t.cap / 2080u);
     if (!sl.geoloc_ws.ptr || sl.geoloc_rows < rows) {
-        sl.geoloc_ws.alloc(geoloc_ws_bytes(rows));
+        sl.geoloc_ws.alloc(apt::gpu::geoloc_ws_bytes(rows));
         sl.geoloc_rows = rows;
     }
     if (!sl.map) sl.map = std::make_unique<apt::map::Device>();
-    sl.map->prepare_track(t.stream, rows);
-    void *ws = sl.geoloc_ws.ptr;
-    timed(t.stream, "image_geoloc_track", [&] { geoloc_track(t.stream, l, *sl.map, ws); });
-    timed(t.stream, "image_geoloc_rows", [&] { geoloc_rows(t.stream, l, *sl.map, ws); });
-    timed(t.stream, "image_geoloc", [&] { geoloc_pixels(t.stream, l, *sl.map, ws); });
-    apt::hip_check(hipGetLastError(), "kernel launch (geolocation stage)");
+    apt::enqueue_geoloc(this, image_job(t, l.x), l, *sl.map, sl.geoloc_ws.ptr);
 }
 
 aptgpu_plan::Palette::~Palette()

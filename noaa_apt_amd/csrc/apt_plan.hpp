@@ -255,22 +255,20 @@ struct aptgpu_plan : apt::PlanDesign {
     // per stream (calls in flight never share one): pass table, graticule, record and PNG scratch, on first use
     std::vector<std::unique_ptr<apt::composite::Device>> composite;
     int composite_count = -1;  // passes of the latest composite (-1: none since the last decode call)
-    // The despeckle stage (apt_kernels_despeckle.hpp) of recording i, behind its decode on the same stream: the 98 %
-    // limits of d_rows when threshold != 0 (into the slot's image scratch, which the image stage behind it rewrites),
-    // then one k_despeckle launch into d_out (same capacity, no overlap).  The record stays in the slot.
+    // The row stages of recording i, behind its decode on the same stream: the slot's scratch on first use, the
+    // recording's job (image_job: the decode's record, the capacity), then the stage's launches of
+    // apt_image_request.hpp, which the one-shot entry points go through too.  The record stays in the slot.
+    // Despeckle: the limits go into the slot's image scratch, which the image stage behind it rewrites, and their
+    // record beside the stage's own; d_out has d_rows' capacity and does not overlap it.
     void enqueue_despeckle(int i, const float *d_rows, uint64_t rows_cap_floats, int radius, float threshold,
                            float *d_out);
-    // The thermal stage (apt_kernels_thermal.hpp) of recording i, behind its decode on the same stream: the telemetry
-    // stage's launches (into the slot's image scratch, which the image stage behind it rewrites, and a record of the
-    // stage's own), then k_thermal_space, k_thermal_setup and k_thermal_map.  launch.x / kelvin / image are the
-    // recording's buffers; res, n and cap are filled in here.  The record stays in the slot.
-    void enqueue_thermal(int i, uint64_t rows_cap_floats, apt::gpu::ThermalLaunch launch, const apt::gpu::ThermalCoeffs &coeffs,
-                         const apt::gpu::ThermalTable &table);
-    // The geolocation stage (apt_kernels_geoloc.hpp) of recording i, behind its decode on the same stream: the track's
-    // launches into the slot's map device (whose track and x offsets a later overlay or reprojection rewrites), then
-    // k_geoloc_rows and k_geoloc.  launch.x and the output planes are the recording's buffers; res, n and cap are
-    // filled in here.  The record stays in the slot.
-    void enqueue_geoloc(int i, uint64_t rows_cap_floats, apt::gpu::GeolocLaunch launch);
+    // Thermal: launch.x / kelvin / image are the recording's buffers; the telemetry launches use the slot's image
+    // scratch likewise.
+    void enqueue_thermal(int i, uint64_t rows_cap_floats, const apt::gpu::ThermalLaunch &launch,
+                         const apt::gpu::ThermalCoeffs &coeffs, const apt::gpu::ThermalTable &table);
+    // Geolocation: launch.x and the output planes are the recording's buffers; the track goes into the slot's map
+    // device, whose track and x offsets a later overlay or reprojection rewrites.
+    void enqueue_geoloc(int i, uint64_t rows_cap_floats, const apt::gpu::GeolocLaunch &launch);
     // The false-colour palette (256*256*3 RGB).  The plan keeps a host copy; bytes that differ from it start a new
     // generation, which every slot uploads on its own stream the next time it colours an image.  lab: also the
     // palette's Lab tables (apt_lab.hpp), computed once per generation and uploaded per slot likewise.

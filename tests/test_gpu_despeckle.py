@@ -162,6 +162,57 @@ def test_plan_path():
     plan.close()
 
 
+def test_plan_buffer_edges():
+    """What the plan form accepts and refuses at the edges of the "d_out overlaps d_rows" check: d_rows[0] and the
+    output are carved from one tensor, so the addresses are exact."""
+    torch = pytest.importorskip("torch")
+    dev = torch.device("cuda:0")
+    recs = [synth_apt(48000, s, 700 + i) for i, s in enumerate((6, 8, 11))]
+    k = len(recs)
+    plan = apt.Plan(apt.Settings(), apt.Rate.hz(48000), True, max_samples=max(r.size for r in recs), max_batch=k)
+    cap = int(plan.info.max_rows)
+    floats = cap * 2080
+    d_in = [torch.from_numpy(r).to(dev) for r in recs]
+    both = torch.full((2 * floats,), -7.0, dtype=torch.float32, device=dev)  # d_rows[0], then room for an output
+    d_rows = [both[:floats]] + [torch.zeros(floats, dtype=torch.float32, device=dev) for _ in recs[1:]]
+    d_out = [torch.full((floats,), -7.0, dtype=torch.float32, device=dev) for _ in recs]
+    rows_p, out_p = [t.data_ptr() for t in d_rows], [t.data_ptr() for t in d_out]
+    assert rows_p[0] == both.data_ptr()
+    plan.decode_device([t.data_ptr() for t in d_in], [r.size for r in recs], rows_p, [cap] * k)
+    assert all(r.status == 0 for r in plan.results(k))
+    ds = apt.DespeckleSettings(1, 0.1)
+    plan.despeckle_device(rows_p, [cap] * k, out_p, ds)
+    apart = plan.despeckle_results(k)
+    assert all(r.status == 0 and r.height > 0 for r in apart)
+    # an output that begins exactly where d_rows[0] ends: accepted, and the separate buffer's bits
+    plan.despeckle_device(rows_p, [cap] * k, [rows_p[0] + 4 * floats] + out_p[1:], ds)
+    adjacent = plan.despeckle_results(k)
+    assert [bytes(r) for r in adjacent] == [bytes(r) for r in apart]
+    assert torch.equal(both[floats:], d_out[0])
+    # one float earlier: refused
+    with pytest.raises(apt.InvalidError, match="overlaps"):
+        plan.despeckle_device(rows_p, [cap] * k, [rows_p[0] + 4 * (floats - 1)] + out_p[1:], ds)
+    # equal starts overlap even where the rows buffer is empty
+    with pytest.raises(apt.InvalidError, match="overlaps"):
+        plan.despeckle_device(rows_p, [cap, 0, cap], [rows_p[1]] + out_p[1:], ds)
+    # two recordings may share one d_out (outputs are compared with rows only)
+    plan.despeckle_device(rows_p, [cap] * k, [out_p[0], out_p[0], out_p[2]], ds)
+    plan.synchronize()
+    plan.close()
+
+
+@pytest.mark.parametrize("n", [0, 2079])
+def test_one_shot_below_one_row(n):
+    """No whole row: status 0 and the input's bits, with a threshold too (the one-shot form leaves the limits launch
+    out), and the host twin likewise."""
+    x = dm.family("special", 0, seed=n, extra=n)
+    assert x.size == n
+    for fn in (apt.despeckle, apt.despeckle_host):
+        got, info = fn(x, apt.DespeckleSettings(1, 0.1), return_info=True)
+        assert (info.status, info.reason, info.height, info.replaced) == (0, 0, 0, 0), fn.__name__
+        assert got.dtype == f32 and got.tobytes() == x.tobytes(), fn.__name__
+
+
 @pytest.fixture(scope="module")
 def recording(oracle):
     rows = oracle.decode(synth_apt(48000, 600, seed=7), 48000, True)

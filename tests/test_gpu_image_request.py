@@ -3,6 +3,7 @@ ImageResult through the one-shot entry points (rows on the host) and through the
 launches exactly the kernels written down here, the one-shot status callbacks are the lists written down here, and the
 checks that need a live plan give the codes and texts written down here.  Two recordings, decoded once: 250 rows
 (enough for Telemetry) and 60 rows (too short for it)."""
+import ctypes
 import itertools
 import os
 
@@ -388,3 +389,99 @@ def test_zero_length_one_shot(env):
                 apt.process(None, empty, contrast, **kw)
         with pytest.raises(apt.InternalError, match="^" + TOO_SHORT + "$"):  # (from the record)
             apt.process(None, empty, C.TELEMETRY, **kw)
+
+
+# ------------------------------------------------------------------ the plan's record readbacks
+READBACKS = ("despeckle_results", "thermal_results", "geoloc_results", "track_results", "image_results")
+
+
+def test_plan_result_readbacks():
+    """aptgpu_plan_{despeckle,thermal,geoloc,track,image}_results on a plan of its own: refused until their stage has
+    run on the recordings asked for, refused beyond the recordings of the last decode call, empty for count 0, and
+    record i the same whatever the count; the struct_size of the two records that carry one."""
+    import torch
+    import np_thermal_model as tm
+    dev = torch.device("cuda:0")
+    recs = [synth_apt(48000, s, 700 + i) for i, s in enumerate((6, 8, 11))]
+    plan = apt.Plan(apt.Settings(), apt.Rate.hz(48000), True, max_samples=max(r.size for r in recs), max_batch=3)
+    cap = int(plan.info.max_rows)
+    k = 2  # (of the three the plan has room for)
+    d_in = [torch.from_numpy(r).to(dev) for r in recs[:k]]
+    new = lambda n, dtype=torch.float32: [torch.zeros(n, dtype=dtype, device=dev) for _ in range(k)]  # noqa: E731
+    d_rows, d_out, d_trk, d_kelvin = new(cap * 2080), new(cap * 2080), new(cap * 2080), new(cap * 909)
+    d_cos, d_img = new(cap * 909), new(cap * 2080, torch.uint8)
+    caps = [cap] * k
+    plan.decode_device(ptr(d_in), [r.size for r in recs[:k]], ptr(d_rows), caps)
+    heights = [int(r.n_rows) for r in plan.results(k)]
+    assert min(heights) >= 2
+    # before any stage has run (image_results has no records at all then, whatever the count)
+    for name in READBACKS:
+        for count in (1, 2):
+            with pytest.raises(apt.InvalidError):
+                getattr(plan, name)(count)
+        if name == "image_results":
+            with pytest.raises(apt.InvalidError):
+                plan.image_results(0)
+        else:
+            assert getattr(plan, name)(0) == []
+    tracks = [mm.great_circle_track(35.0, -80.0, 191.0, h) for h in heights]
+    stages = {
+        "despeckle_results": lambda: plan.despeckle_device(ptr(d_rows), caps, ptr(d_out), apt.DespeckleSettings(1, 0.1)),
+        "thermal_results": lambda: plan.calibrate_thermal_device(
+            ptr(d_rows), caps, ptr(d_kelvin), apt.ThermalCoefficients(tm.PRT, tm.CH3B, tm.CH4, tm.CH5),
+            apt.ThermalSettings("B", "4", t_low=180, t_high=320, image_channels=0)),
+        "geoloc_results": lambda: plan.geolocate_device(
+            ptr(d_rows), caps, tracks, apt.GeolocSettings("A", apt.RefTime.Start(1730635200000), 0.0), None, None,
+            ptr(d_cos), None),
+        "track_results": lambda: plan.track_device(ptr(d_trk), caps),
+        "image_results": lambda: plan.process_device_image(ptr(d_rows), caps, CONTRASTS["minmax"], ptr(d_img)),
+    }
+    plan.enable_timing(2)
+    plan.collect_timing()
+    for name in READBACKS:
+        stages[name]()
+        read = getattr(plan, name)
+        both = read(2)
+        assert len(both) == 2, name
+        if name != "track_results":  # (the tracker finds its own rows)
+            assert [r.height for r in both] == heights, name
+        with pytest.raises(apt.InvalidError):
+            read(3)
+        assert read(0) == []
+        one = read(1)
+        assert len(one) == 1 and bytes(one[0]) == bytes(both[0]), name
+    # the launches of the five stages under the plan's timer, in the order of their first appearance
+    assert list(plan.collect_timing()) == [
+        "image_percent", "image_despeckle", "image_telemetry", "image_thermal_space", "image_thermal_setup",
+        "image_thermal_map", "image_geoloc_track", "image_geoloc_rows", "image_geoloc", "track_score", "track_dp",
+        "track_rows", "image_minmax", "image_color"]
+    # a caller built against a shorter geolocation record gets its own size back and nothing beyond it
+    arr = (apt.GeolocResult * 2)()
+    ctypes.memset(arr, 0xAB, ctypes.sizeof(arr))
+    for r in arr:
+        r.struct_size = 16
+    assert apt.lib().aptgpu_plan_geoloc_results(plan._p, 2, arr) == 0
+    full = plan.geoloc_results(2)
+    for r, want in zip(arr, full):
+        assert bytes(r)[:16] == bytes(apt.GeolocResult(16, want.status, want.reason, want.height))[:16]
+        assert bytes(r)[16:] == b"\xab" * 24
+    # the tracker's record is refused when shorter (nothing written), and a longer one keeps its size and its tail
+    size = ctypes.sizeof(apt.TrackResult)
+    arr = (apt.TrackResult * 2)()
+    ctypes.memset(arr, 0xAB, ctypes.sizeof(arr))
+    arr[0].struct_size = size
+    arr[1].struct_size = size - 4
+    assert apt.lib().aptgpu_plan_track_results(plan._p, 2, arr) == apt.InvalidError.code
+    assert bytes(arr)[4:size] == b"\xab" * (size - 4) and bytes(arr[1])[4:] == b"\xab" * (size - 4)
+
+    class Longer(ctypes.Structure):
+        _fields_ = [("r", apt.TrackResult), ("tail", ctypes.c_uint8 * 8)]
+    longer = Longer()
+    ctypes.memset(ctypes.byref(longer), 0xAB, ctypes.sizeof(longer))
+    longer.r.struct_size = size + 8
+    assert apt.lib().aptgpu_plan_track_results(plan._p, 1, ctypes.cast(ctypes.byref(longer),
+                                                                       ctypes.POINTER(apt.TrackResult))) == 0
+    want = plan.track_results(1)[0]
+    assert longer.r.struct_size == size + 8 and bytes(longer.r)[4:] == bytes(want)[4:]
+    assert bytes(longer.tail) == b"\xab" * 8
+    plan.close()

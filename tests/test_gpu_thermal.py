@@ -169,3 +169,56 @@ def test_plan_path():
             plan.calibrate_thermal_device([d_rows.data_ptr()], [cap], [d_kelvin.data_ptr()], co, st, [d_image.data_ptr() + 2])
         plan.synchronize()
     plan.close()
+
+
+def test_plan_buffer_edges():
+    """What the plan form accepts and refuses at the edges of its "overlaps d_rows" checks: d_rows[0] and the outputs
+    are carved from one tensor, so the addresses are exact.  (The recordings are too short for a telemetry frame: the
+    record says so and the planes are NaN / level 0, written all the same.)"""
+    torch = pytest.importorskip("torch")
+    dev = torch.device("cuda:0")
+    recs = [synth_apt(48000, s, 700 + i) for i, s in enumerate((6, 8, 11))]
+    k = len(recs)
+    co = tc.coeffs()
+    plan = apt.Plan(apt.Settings(), apt.Rate.hz(48000), True, max_samples=max(r.size for r in recs), max_batch=k)
+    cap = int(plan.info.max_rows)
+    floats = cap * 2080
+    d_in = [torch.from_numpy(r).to(dev) for r in recs]
+    both = torch.full((2 * floats,), -7.0, dtype=torch.float32, device=dev)  # d_rows[0], then room for an output
+    d_rows = [both[:floats]] + [torch.zeros(floats, dtype=torch.float32, device=dev) for _ in recs[1:]]
+    d_kelvin = [torch.full((cap * 909,), -7.0, dtype=torch.float32, device=dev) for _ in recs]
+    d_image = [torch.full((floats,), 77, dtype=torch.uint8, device=dev) for _ in recs]
+    rows_p, kelvin_p, image_p = ([t.data_ptr() for t in ts] for ts in (d_rows, d_kelvin, d_image))
+    end = rows_p[0] + 4 * floats
+    assert rows_p[0] == both.data_ptr()
+    plan.decode_device([t.data_ptr() for t in d_in], [r.size for r in recs], rows_p, [cap] * k)
+    res = plan.results(k)
+    assert all(r.status == 0 for r in res)
+    heights = [int(r.n_out) // 2080 for r in res]
+    st = apt.ThermalSettings("B", "4", t_low=180, t_high=320, image_channels=1)
+    plan.calibrate_thermal_device(rows_p, [cap] * k, kelvin_p, co, st, image_p)
+    apart = plan.thermal_results(k)
+    assert [(r.status, r.reason, r.height) for r in apart] == [(1, 2, h) for h in heights]
+    # an output that begins exactly where d_rows[0] ends: accepted, and the separate buffer's bits
+    h = heights[0]
+    plan.calibrate_thermal_device(rows_p, [cap] * k, [end] + kelvin_p[1:], co, st, image_p)
+    assert [_record(r) for r in plan.thermal_results(k)] == [_record(r) for r in apart]
+    assert both[floats:floats + h * 909].cpu().numpy().tobytes() == d_kelvin[0][:h * 909].cpu().numpy().tobytes()
+    want_image = d_image[0].clone()
+    d_image[0].fill_(77)
+    plan.calibrate_thermal_device(rows_p, [cap] * k, kelvin_p, co, st, [end] + image_p[1:])
+    assert [_record(r) for r in plan.thermal_results(k)] == [_record(r) for r in apart]
+    assert torch.equal(both.view(torch.uint8)[4 * floats:4 * floats + h * 2080], want_image[:h * 2080])
+    assert torch.all(want_image[h * 2080:] == 77) and torch.all(d_image[0] == 77)
+    # one float (one byte) earlier: refused
+    with pytest.raises(apt.InvalidError, match="d_kelvin overlaps"):
+        plan.calibrate_thermal_device(rows_p, [cap] * k, [end - 4] + kelvin_p[1:], co, st, image_p)
+    with pytest.raises(apt.InvalidError, match="d_images overlaps"):
+        plan.calibrate_thermal_device(rows_p, [cap] * k, kelvin_p, co, st, [end - 1] + image_p[1:])
+    # equal starts overlap even where the rows buffer is empty
+    with pytest.raises(apt.InvalidError, match="d_kelvin overlaps"):
+        plan.calibrate_thermal_device(rows_p, [cap, 0, cap], [rows_p[1]] + kelvin_p[1:], co, st, image_p)
+    with pytest.raises(apt.InvalidError, match="d_images overlaps"):
+        plan.calibrate_thermal_device(rows_p, [cap, 0, cap], kelvin_p, co, st, [rows_p[1]] + image_p[1:])
+    plan.synchronize()
+    plan.close()
