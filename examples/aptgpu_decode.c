@@ -2,7 +2,7 @@
  * aptgpu_decode.c — minimal C caller of the drop-in boundary (include/aptgpu.h):
  *
  *     aptgpu_decode in.wav out.pgm [contrast: telemetry|percent|minmax] [--no-sync]
- *                   [--histogram | --histogram-float] [--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE] [--png]
+ *                   [--histogram | --histogram-float] [--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE [--fit]] [--png]
  *                   [--tle FILE --sat NAME (--start-ms N | --end-ms N)] [--rotate no|yes|orbit]
  *                   [--project equirect|mercator[:step_deg] [--grid DEG]] [--despeckle R[:T]] [--track=[W,LAMBDA[,LAG]]]
  *                   [--live SECONDS] [--iq FMT:FS:D[:SHIFT_HZ]] [--sun A|B:UNIX_MS[:BLACK] --track FILE]
@@ -18,7 +18,9 @@
  * reference does, channel A in CIE Lab (APTGPU_COLOR_EQUALIZE_LAB); without it that combination
  * is refused.  --map DIR --track FILE: the map overlay (`--map`) of DIR/states.shp, countries.shp and
  * lakes.shp with the default settings and colours; FILE holds the satellite's raw f64 (lat, lon)
- * pairs in radians, one per image row (SGP4 is the caller's job); written as a PPM.
+ * pairs in radians, one per image row (SGP4 is the caller's job); written as a PPM.  With --fit the overlay's yaw,
+ * hscale and vscale and the pass's time offset are fitted to the image first (aptgpu_fit_overlay with its default
+ * settings, printed): FILE then holds 120 more rows at either end, image row 0 being its row 120.
  * --project KIND[:STEP]: the finished image (channel A) reprojected onto a north-up equirectangular or
  * Mercator grid of STEP degrees per pixel (default 0.04) that aptgpu_projection_fit sizes from the track
  * (--track FILE, or --tle: aptgpu_sat_track_host), bilinear; --grid DEG adds a graticule.  Written as a
@@ -61,13 +63,13 @@ int main(int argc, char **argv)
 {
     if (argc < 3) {
         fprintf(stderr, "usage: %s in.wav out.pgm [telemetry|percent|minmax] [--no-sync] [--histogram | --histogram-float] "
-                "[--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE] [--png]\n"
+                "[--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE [--fit]] [--png]\n"
                 "       [--tle FILE --sat NAME (--start-ms N | --end-ms N)] [--rotate no|yes|orbit]\n"
                 "       [--project equirect|mercator[:step_deg] [--grid DEG]] [--despeckle R[:T]] [--track=[W,LAMBDA[,LAG]]]\n"
                 "       [--live SECONDS] [--iq u8|s8|s16|f32:FS:D[:SHIFT_HZ]] [--sun A|B:UNIX_MS[:BLACK] --track FILE]\n", argv[0]);
         return 2;
     }
-    int contrast = APTGPU_CONTRAST_PERCENT, sync = 1, lab = 0, png = 0;
+    int contrast = APTGPU_CONTRAST_PERCENT, sync = 1, lab = 0, png = 0, fit = 0;
     const char *palette_path = NULL, *map_dir = NULL, *track_path = NULL, *tle_path = NULL, *sat = NULL;
     int rotate = APTGPU_ROTATE_NO, ref_kind = -1;
     long long ref_ms = 0;
@@ -82,6 +84,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--no-sync")) sync = 0;
         else if (!strcmp(argv[i], "--lab")) lab = 1;
         else if (!strcmp(argv[i], "--png")) png = 1;
+        else if (!strcmp(argv[i], "--fit")) fit = 1;
         else if (!strcmp(argv[i], "--palette") && i + 1 < argc) palette_path = argv[++i];
         else if (!strcmp(argv[i], "--map") && i + 1 < argc) map_dir = argv[++i];
         else if (!strcmp(argv[i], "--track") && i + 1 < argc) track_path = argv[++i];
@@ -482,19 +485,49 @@ int main(int argc, char **argv)
         fprintf(stderr, "--rotate orbit needs --tle FILE --sat NAME and a time\n");
         return 1;
     } else if (map_dir) {
-        /* the track: one (lat, lon) per image row, as map.rs:41-58 computes it with SGP4 */
+        /* the track: one (lat, lon) per image row, as map.rs:41-58 computes it with SGP4; with --fit the long one,
+         * margin_rows rows more at either end */
         const size_t height = n_rows_px / 2080;
-        double *track = malloc((height ? height : 1) * 2 * sizeof(double));
+        aptgpu_fit_settings fs;
+        aptgpu_fit_default_settings(&fs);
+        const size_t margin = fit ? (size_t)fs.margin_rows : 0, track_rows = height + 2 * margin;
+        double *track_buf = malloc((track_rows ? track_rows : 1) * 2 * sizeof(double));
         FILE *t = track_path ? fopen(track_path, "rb") : NULL;
-        if (!track || !t || fread(track, sizeof(double), 2 * height, t) != 2 * height || fgetc(t) != EOF) {
-            fprintf(stderr, "--map needs --track FILE with exactly %zu (lat, lon) f64 pairs\n", height);
+        if (!track_buf || !t || fread(track_buf, sizeof(double), 2 * track_rows, t) != 2 * track_rows || fgetc(t) != EOF) {
+            fprintf(stderr, "--map%s needs --track FILE with exactly %zu (lat, lon) f64 pairs\n", fit ? " --fit" : "", track_rows);
             return 1;
         }
         fclose(t);
+        const double *track = track_buf + 2 * margin;
         aptgpu_map_layers *layers = NULL;
         aptgpu_map_settings ms = {sizeof(aptgpu_map_settings), 0, 0.0, 1.0, 1.0};  /* config.rs:646-648 */
         rc = aptgpu_map_layers_create(&layers);
         if (rc == APTGPU_OK) rc = aptgpu_map_layers_load_dir(layers, map_dir, err, sizeof err);
+        if (rc == APTGPU_OK && fit) {
+            /* --fit: yaw, scales and the time offset from the image itself (the unrotated gray image against the
+             * layers' lines), then the overlay with what was found */
+            uint8_t *gray = NULL;
+            size_t n_gray = 0;
+            aptgpu_image_result gi;
+            aptgpu_fit_result fr;
+            memset(&fr, 0, sizeof fr);
+            fr.struct_size = sizeof fr;
+            rc = aptgpu_process_gray(&ctx, rows, n_rows_px, contrast, 0.98f, APTGPU_ROTATE_NO, &gray, &n_gray, &gi, err,
+                                     sizeof err);
+            if (rc == APTGPU_OK)
+                rc = aptgpu_fit_overlay(&ctx, gray, height, track_buf, track_rows, NULL, layers, &ms, &fs, &fr, NULL, NULL,
+                                        err, sizeof err);
+            aptgpu_free(gray);
+            if (rc == APTGPU_OK) {
+                fprintf(stderr, "fit: yaw %g, hscale %g, vscale %g, %d rows = %lld ms (q %g over %u points%s)\n", fr.yaw,
+                        fr.hscale, fr.vscale, fr.shift_rows, (long long)fr.time_offset_ms, fr.q, fr.count,
+                        fr.reason == APTGPU_FIT_REASON_FLAT ? "; a flat image: the initial settings" : "");
+                ms.yaw = fr.yaw;
+                ms.hscale = fr.hscale;
+                ms.vscale = fr.vscale;
+                track = track_buf + 2 * (size_t)((long long)margin + fr.shift_rows);
+            }
+        }
         if (rc == APTGPU_OK && png)
             rc = aptgpu_process_image_png(&ctx, rows, n_rows_px, contrast, 0.98f, rotate,
                                           palette_path ? &color : NULL, 4, &ms, layers, track, &ps, &image, &n_px,
@@ -504,7 +537,7 @@ int main(int argc, char **argv)
                                           palette_path ? &color : NULL, 4, &ms, layers, track, &image, &n_px, &info,
                                           err, sizeof err);
         aptgpu_map_layers_destroy(layers);
-        free(track);
+        free(track_buf);
     } else if (png)
         rc = aptgpu_process_image_png(&ctx, rows, n_rows_px, contrast, 0.98f, rotate,
                                       palette_path ? &color : NULL, palette_path ? 4 : 1, NULL, NULL, NULL, &ps, &image,

@@ -1061,6 +1061,126 @@ int aptgpu_plan_geolocate_device(aptgpu_plan *plan, int count, const float *cons
 /* Waits for the geolocation stage of the last call and copies the records (each results[i].struct_size set). */
 int aptgpu_plan_geoloc_results(aptgpu_plan *plan, int count, aptgpu_geoloc_result *results);
 
+/* ---- fitting the map overlay to the image: yaw, hscale, vscale and the time offset ----
+ * Every stage that places the image on the Earth takes yaw, hscale, vscale and the pass's time on trust.  The
+ * reference leaves them to the user's eye (docs/development.md: "Look for defaults for yaw and scales?"), so the
+ * definition is this library's; tests/np_fit_model.py states it in numpy.  Opt-in, a stage of its own behind
+ * process(); nothing else changes when it is not called.  All real arithmetic is f64 and never contracted; everything
+ * summed is an integer, so no sum depends on its order.  The defaults of aptgpu_fit_default_settings have not been
+ * tried on a real pass: the stage has been judged on synthetic scenes only.
+ *  - Input: an unrotated 8-bit gray image of h rows of 2080 pixels (aptgpu_process_image with rotate = No and
+ *    channels = 1); a channel; the layer set and a mask of its layers (bit k = layer k; 0 = countries and lakes: states
+ *    are political lines and show in no image); a long track T of h + 2 M (lat, lon) pairs in radians, M =
+ *    margin_rows: image row r under shift s in [-M, M] is seen from T[M + s + r].  The track is the caller's
+ *    (n_positions must be h + 2 M, else reason 7) or SGP4's on the device from an aptgpu_orbit_settings, for
+ *    t = start_ms + 500 (r - M), r = 0 .. h + 2 M - 1, start_ms row 0's time as in "the satellite track" (exactly one
+ *    of the two).  Initial aptgpu_map_settings (nullable: 0, 1, 1).
+ *  - Edge planes, exact integers: v[r][k] = image[r][1040 ch + 86 + k], k = 0 .. 908;
+ *      G[r][k] = |v[r][min(k+1, 908)] - v[r][max(k-1, 0)]| + |v[min(r+1, h-1)][k] - v[max(r-1, 0)][k]|,
+ *      E_R[r][k] = the sum of G over |dr| <= R, |dk| <= R, clipped to the plane (u32).
+ *    Round p of `rounds` uses R_p = radius << (rounds - 1 - p); R_0 > 64 is APTGPU_ERR_INVALID.
+ *  - Sample points (host; aptgpu_fit_sample_points returns the list): the masked layers in draw order, each part, each
+ *    segment p0 -> p1 in (lon, lat) degrees: n = max(1, ceil(max(|dlon|, |dlat|) / spacing_deg)) points
+ *    p0 + (p1 - p0) * ((double) i / (double) n), i = 0 .. n - 1; a one-vertex part gives that vertex; the last vertex
+ *    of a longer part is not a point of its own.  More than 2^22 points: APTGPU_ERR_INVALID.
+ *  - Per shift s: start = T[M + s], end = T[M + s + h - 1], ref_az = geo::azimuth(start, end), D = geo::distance(start,
+ *    end) (the overlay's scalars, so the fitted numbers mean what aptgpu_map_settings means), S, T, R the frame of the
+ *    geolocation stage above from (start, ref_az).  For a point at (lat, lon) = (lat_deg / 180 * pi, lon_deg / 180 *
+ *    pi) with unit vector P = (cos lat cos lon, cos lat sin lon, sin lat) and U.V = (U0 V0 + U1 V1) + U2 V2:
+ *      a = atan2(P.T, P.S),  b = asin(clamp(P.R, -1, 1)),  valid iff P.S > 0.5
+ *    (latlon_to_rel_px's (a, b) inside its pi / 3 clamp, without its acos of a value near 1).  bx[r] is the b of
+ *    T[M + s + r], bx[0] = 0.
+ *  - Per candidate (s, yaw, hscale, vscale) and valid point: kx = hscale / 0.0005, ky = (double) h * vscale / D,
+ *      x0 = -b kx,  y = a ky + yaw x0,  e = (uint) min(max(y, 0), h - 1),  x = x0 - (-bx[e] kx),
+ *      col = floor(x + 0.5) + 453,  row = floor(y + 0.5);  inside iff 0 <= col < 909 and 0 <= row < h.
+ *    score = the sum of E_R[row][col] over the inside points (u64), count their number; q = (double) score / (double)
+ *    count when count >= min_points.  Otherwise, and when |s| > M, hscale <= 0 or vscale <= 0, the candidate is
+ *    invalid: q = -1, score 0, count 0.
+ *  - Round p evaluates the grid centre + i * step_p (one product, one sum), i in [-n, n] on each of the four axes, with
+ *    shift_step_p = max(1, shift_step >> p) rows and step / 2^p for the other three; candidate index
+ *    ((is Ny + iy) Nh + ih) Nv + iv, each from 0.  The winner has the greatest score / count, compared as exact
+ *    rationals; on a tie the lowest index wins.  It is the next round's centre, kept in the record on the device: no
+ *    launch waits on the host between rounds.
+ *  - Record reasons: with status APTGPU_ERR_INTERNAL, APTGPU_MAP_REASON_COUNT (7), APTGPU_SAT_REASON_SGP4 (10),
+ *    APTGPU_GEOLOC_REASON_HEIGHT (15: h < 16, refused before any launch) and APTGPU_FIT_REASON_NO_CANDIDATE (17: a
+ *    round without a valid candidate); with status APTGPU_OK, APTGPU_FIT_REASON_FLAT (18): the winning score of a round
+ *    is 0, as on a constant image, and the result is the initial settings with shift 0.  Later rounds do not run.
+ *  - scores_out (nullable; malloc'd, aptgpu_free) receives rounds * n_candidates records {u64 score, u32 count, u32 0}
+ *    in round, then index order; rounds that did not run are zero.
+ * Kernel groups (tools/fit_timing.py; with settings->timing their event-pair times land in the record):
+ * image_fit_edge, image_fit_angles, image_fit_score.  A plan-chained form, whose height is known only on the device,
+ * does not exist. */
+#define APTGPU_FIT_REASON_NO_CANDIDATE 17 /* aptgpu_fit_result.reason */
+#define APTGPU_FIT_REASON_FLAT 18
+#define APTGPU_FIT_MAX_ROUNDS 8
+#define APTGPU_FIT_MAX_POINTS (1u << 22)
+#define APTGPU_FIT_MAX_CANDIDATES (1u << 20)
+typedef struct aptgpu_fit_settings {
+    uint32_t struct_size;  /* sizeof(aptgpu_fit_settings) */
+    uint32_t flags;        /* 0; any set bit is APTGPU_ERR_INVALID */
+    int32_t channel;       /* 0 = A, 1 = B */
+    uint32_t layer_mask;   /* bit k = layer k (APTGPU_MAP_*); 0 = countries and lakes */
+    int32_t margin_rows;   /* M >= 0 */
+    int32_t rounds;        /* 1 .. 8 */
+    int32_t radius;        /* the last round's box radius, >= 0; radius << (rounds - 1) <= 64 */
+    int32_t min_points;    /* >= 1 */
+    int32_t shift_step, n_shift;   /* rows, >= 1; >= 0 */
+    int32_t n_yaw, n_hscale, n_vscale; /* >= 0 */
+    int32_t timing;        /* nonzero: time the kernel groups (aptgpu_fit_result.ms_*); GPU forms only */
+    double yaw_step, hscale_step, vscale_step; /* >= 0 */
+    double spacing_deg;    /* > 0 */
+} aptgpu_fit_settings;
+typedef struct aptgpu_fit_round {
+    double c_yaw, c_hscale, c_vscale; /* the centre the round started from */
+    double w_yaw, w_hscale, w_vscale; /* its winner */
+    double q;                         /* the winner's (double) score / (double) count; -1 without a winner */
+    int32_t c_shift, w_shift;         /* rows */
+    uint32_t count, index;            /* the winner's inside points and candidate index */
+    uint64_t score;
+} aptgpu_fit_round;
+typedef struct aptgpu_fit_result {
+    uint32_t struct_size;  /* the caller's sizeof(aptgpu_fit_result) */
+    int32_t status;        /* APTGPU_OK or APTGPU_ERR_INTERNAL */
+    int32_t reason;        /* 0, 7, 10, 15, 17, 18 */
+    uint32_t height;
+    uint32_t n_rounds;     /* rounds that ran */
+    uint32_t n_points;     /* sample points */
+    uint32_t n_candidates; /* per round */
+    int32_t shift_rows;
+    int64_t time_offset_ms; /* 500 * shift_rows: add it to the pass's reference time */
+    double yaw, hscale, vscale, q;
+    uint32_t count, done;  /* done: device bookkeeping, nonzero once the rounds have ended */
+    float ms_edge, ms_angles, ms_score, ms_pick; /* with settings->timing; else 0 */
+    aptgpu_fit_round round[APTGPU_FIT_MAX_ROUNDS];
+} aptgpu_fit_result;
+/* The suggested defaults: margin_rows 120; shift_step 8, n_shift 15; yaw_step 0.02, n 3; hscale_step and vscale_step
+ * 0.04, n 3; rounds 4; radius 2; spacing_deg 0.05; min_points 64; channel A; the default mask. */
+void aptgpu_fit_default_settings(aptgpu_fit_settings *out);
+/* image: height rows of 2080 bytes on the host.  settings and layers are required; exactly one of sat_positions and
+ * orbit; map nullable; info nullable (its struct_size set by the caller); scores_out nullable.  A failed record returns
+ * APTGPU_ERR_INTERNAL with *info filled. */
+int aptgpu_fit_overlay(const aptgpu_context *ctx, const uint8_t *image, size_t height, const double *sat_positions,
+                       size_t n_positions, const aptgpu_orbit_settings *orbit, const aptgpu_map_layers *layers,
+                       const aptgpu_map_settings *map, const aptgpu_fit_settings *settings, aptgpu_fit_result *info,
+                       void **scores_out, size_t *n_scores, char *err, size_t err_cap);
+/* The same for an image already in the memory of ctx's device (nullable ctx: device 0), of a height the caller
+ * states, on `stream` (a hipStream_t; NULL: the default stream).  The call returns once the record has been read. */
+int aptgpu_fit_overlay_device(const aptgpu_context *ctx, const uint8_t *d_image, size_t height, void *stream,
+                              const double *sat_positions, size_t n_positions, const aptgpu_orbit_settings *orbit,
+                              const aptgpu_map_layers *layers, const aptgpu_map_settings *map,
+                              const aptgpu_fit_settings *settings, aptgpu_fit_result *info, void **scores_out,
+                              size_t *n_scores, char *err, size_t err_cap);
+/* The same on the CPU, in plain C++ (no GPU needed): the same source text per point and candidate, the C library's
+ * f64 functions. */
+int aptgpu_fit_overlay_host(const uint8_t *image, size_t height, const double *sat_positions, size_t n_positions,
+                            const aptgpu_orbit_settings *orbit, const aptgpu_map_layers *layers,
+                            const aptgpu_map_settings *map, const aptgpu_fit_settings *settings,
+                            aptgpu_fit_result *info, void **scores_out, size_t *n_scores, char *err, size_t err_cap);
+/* The sample points alone (CPU): *xy malloc'd (aptgpu_free), *n_points (lon, lat) pairs in degrees.  layer_mask 0: the
+ * default mask. */
+int aptgpu_fit_sample_points(const aptgpu_map_layers *layers, uint32_t layer_mask, double spacing_deg, double **xy,
+                             size_t *n_points, char *err, size_t err_cap);
+
 /* ====================================================================== */
 /* 4b. FM demodulation of IQ recordings, in front of decode() */
 /* ====================================================================== */

@@ -39,6 +39,9 @@ Names, argument meaning and error behaviour follow the reference:
     normalize_sun, GeolocSettings, Plan.geolocate_device   inverted), the sun's zenith angle there and the visible rows
                                                            normalised by it (the reference only advises daylight passes,
                                                            docs/usage.md:409-417), DESIGN.md §25
+    fit_overlay, fit_overlay_host, fit_overlay_device,     the reference's to-do list, docs/development.md:90: yaw, scales
+    fit_sample_points, margin_track, FitSettings,          and the time offset fitted to the image's edges, DESIGN.md §26
+    OverlayFit
     fm_demodulate, fm_demodulate_host, fm_demodulate_wav,  FM demodulation of an IQ recording in front of decode()
     fm_design, load_iq, IqFormat, FmSettings,              (the reference takes audio only, docs/usage.md:87),
     FmDemodulator                                          DESIGN.md §20
@@ -72,6 +75,8 @@ from .api import (  # noqa: F401
     THERMAL_COLD_WHITE, THERMAL_REASON_CHANNEL, THERMAL_REASON_DEGENERATE, THERMAL_PX,
     GeolocSettings, GeolocResult, geolocate, geolocate_host, sun_position, normalize_sun,
     GEOLOC_PX, GEOLOC_REASON_HEIGHT, GEOLOC_REASON_DECODE,
+    FitSettings, FitResult, FitRound, OverlayFit, fit_overlay, fit_overlay_host, fit_overlay_device, fit_sample_points,
+    margin_track, FIT_REASON_NO_CANDIDATE, FIT_REASON_FLAT, FIT_SCORE_DTYPE,
     IqFormat, FmSettings, FmInfo, FmDemodulator, fm_demodulate, fm_demodulate_host, fm_demodulate_wav, fm_design, load_iq,
     FM_SWAP_IQ, FM_MAX_BATCH,
     TrackSettings, TrackResult, track_sync, track_sync_host, sync_score, decode_tracked, TRACK_MAX_JITTER,

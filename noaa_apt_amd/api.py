@@ -256,6 +256,32 @@ class GeolocResult(C.Structure):
                 ("n_outside", C.c_uint64), ("n_capped", C.c_uint64), ("cos_min", C.c_float), ("cos_max", C.c_float)]
 
 
+class _CFitSettings(C.Structure):
+    """aptgpu_fit_settings"""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("channel", C.c_int32), ("layer_mask", C.c_uint32),
+                ("margin_rows", C.c_int32), ("rounds", C.c_int32), ("radius", C.c_int32), ("min_points", C.c_int32),
+                ("shift_step", C.c_int32), ("n_shift", C.c_int32), ("n_yaw", C.c_int32), ("n_hscale", C.c_int32),
+                ("n_vscale", C.c_int32), ("timing", C.c_int32), ("yaw_step", C.c_double), ("hscale_step", C.c_double),
+                ("vscale_step", C.c_double), ("spacing_deg", C.c_double)]
+
+
+class FitRound(C.Structure):
+    """aptgpu_fit_round: the centre a round started from, its winner and the winner's sums."""
+    _fields_ = [("c_yaw", C.c_double), ("c_hscale", C.c_double), ("c_vscale", C.c_double), ("w_yaw", C.c_double),
+                ("w_hscale", C.c_double), ("w_vscale", C.c_double), ("q", C.c_double), ("c_shift", C.c_int32),
+                ("w_shift", C.c_int32), ("count", C.c_uint32), ("index", C.c_uint32), ("score", C.c_uint64)]
+
+
+class FitResult(C.Structure):
+    """aptgpu_fit_result"""
+    _fields_ = [("struct_size", C.c_uint32), ("status", C.c_int32), ("reason", C.c_int32), ("height", C.c_uint32),
+                ("n_rounds", C.c_uint32), ("n_points", C.c_uint32), ("n_candidates", C.c_uint32),
+                ("shift_rows", C.c_int32), ("time_offset_ms", C.c_int64), ("yaw", C.c_double), ("hscale", C.c_double),
+                ("vscale", C.c_double), ("q", C.c_double), ("count", C.c_uint32), ("done", C.c_uint32),
+                ("ms_edge", C.c_float), ("ms_angles", C.c_float), ("ms_score", C.c_float), ("ms_pick", C.c_float),
+                ("round", FitRound * 8)]
+
+
 class _CFmSettings(C.Structure):
     """aptgpu_fm_settings"""
     _fields_ = [("struct_size", C.c_uint32), ("format", C.c_int32), ("sample_rate_hz", C.c_uint32),
@@ -525,6 +551,14 @@ def lib():
                                                C.POINTER(_CGeolocSettings), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
                                                C.c_char_p, sz]
     L.aptgpu_plan_geoloc_results.argtypes = [vp, i32, C.POINTER(GeolocResult)]
+    fit = (_f64p, sz, C.POINTER(_COrbitSettings), vp, C.POINTER(_CMapSettings), C.POINTER(_CFitSettings),
+           C.POINTER(FitResult), C.POINTER(vp), C.POINTER(sz), C.c_char_p, sz)
+    L.aptgpu_fit_default_settings.argtypes = [C.POINTER(_CFitSettings)]
+    L.aptgpu_fit_default_settings.restype = None
+    L.aptgpu_fit_overlay.argtypes = [cp, _u8p, sz, *fit]
+    L.aptgpu_fit_overlay_device.argtypes = [cp, vp, sz, vp, *fit]
+    L.aptgpu_fit_overlay_host.argtypes = [_u8p, sz, *fit]
+    L.aptgpu_fit_sample_points.argtypes = [vp, C.c_uint32, C.c_double, C.POINTER(_f64p), C.POINTER(sz), C.c_char_p, sz]
     cfm = C.POINTER(_CFmSettings)
     fm_out = (C.POINTER(_f32p), C.POINTER(sz), _u32p, C.c_char_p, sz)
     L.aptgpu_fm_default_settings.argtypes = [cfm]
@@ -2178,6 +2212,168 @@ def normalize_sun(signal, track_or_orbit, channel, black=None, ref_time=None, ma
     _, _, rows, info = _geoloc_call(lib().aptgpu_geolocate, (C.byref(cctx),), signal, track_or_orbit, map_settings, st,
                                     False, False, True)
     return (rows, info) if return_info else rows
+
+
+FIT_REASON_NO_CANDIDATE = 17
+FIT_REASON_FLAT = 18
+FIT_SCORE_DTYPE = np.dtype([("score", np.uint64), ("count", np.uint32), ("zero", np.uint32)])
+
+
+class FitSettings:
+    """aptgpu_fit_settings with the suggested defaults, which have not been tried on a real pass.
+    channel: "A" / "B" (or 0 / 1).  layers: an iterable of MAP_* layer indices, None: countries and lakes.  Round p
+    of `rounds` searches centre + i * step / 2^p, i in [-n, n], on each axis (shift_step >> p rows, at least 1) and
+    scores against the gradient summed over a box of radius << (rounds - 1 - p)."""
+
+    def __init__(self, channel="A", layers=None, margin_rows=120, shift_step=8, n_shift=15, yaw_step=0.02, n_yaw=3,
+                 hscale_step=0.04, n_hscale=3, vscale_step=0.04, n_vscale=3, rounds=4, radius=2, spacing_deg=0.05,
+                 min_points=64, timing=False, flags=0):
+        self.channel, self.layers, self.margin_rows = channel, layers, margin_rows
+        self.shift_step, self.n_shift, self.yaw_step, self.n_yaw = shift_step, n_shift, yaw_step, n_yaw
+        self.hscale_step, self.n_hscale, self.vscale_step, self.n_vscale = hscale_step, n_hscale, vscale_step, n_vscale
+        self.rounds, self.radius, self.spacing_deg, self.min_points = rounds, radius, spacing_deg, min_points
+        self.timing, self.flags = timing, flags
+
+    def _mask(self):
+        if self.layers is None:
+            return 0
+        mask = 0
+        for k in self.layers:
+            mask |= 1 << int(k)
+        return mask
+
+    def _c(self, struct_size=None):
+        ch = {"A": 0, "B": 1}.get(self.channel, self.channel)
+        return _CFitSettings(C.sizeof(_CFitSettings) if struct_size is None else int(struct_size), int(self.flags),
+                             int(ch), self._mask(), int(self.margin_rows), int(self.rounds), int(self.radius),
+                             int(self.min_points), int(self.shift_step), int(self.n_shift), int(self.n_yaw),
+                             int(self.n_hscale), int(self.n_vscale), int(bool(self.timing)), float(self.yaw_step),
+                             float(self.hscale_step), float(self.vscale_step), float(self.spacing_deg))
+
+
+class OverlayFit:
+    """What fit_overlay() found, ready to hand on: map_settings (the initial colours kept), shift_rows and
+    time_offset_ms = 500 * shift_rows, the h-row `track` when a track was passed or `orbit`, the OrbitSettings with its
+    reference time moved and the fitted settings as draw_map; rounds (the FitRound entries that ran), q and count of
+    the winner, `info` (the FitResult) and, when asked for, `scores`: (rounds, candidates) records of score and count."""
+
+    def __init__(self, info, map_settings, track, orbit, scores):
+        self.info, self.map_settings, self.track, self.orbit, self.scores = info, map_settings, track, orbit, scores
+        self.shift_rows, self.time_offset_ms = int(info.shift_rows), int(info.time_offset_ms)
+        self.q, self.count, self.reason = float(info.q), int(info.count), int(info.reason)
+        self.rounds = [info.round[i] for i in range(int(info.n_rounds))]
+
+
+def margin_track(orbit: "OrbitSettings", height, margin_rows):
+    """The long track fit_overlay() takes, on the CPU: height + 2 * margin_rows (lat, lon) pairs in radians, row r at
+    start + 500 ms * (r - margin_rows), where start is the time of image row 0 under `orbit`."""
+    height, m = int(height), int(margin_rows)
+    start = orbit.ref_time.unix_ms - (500 * height if orbit.ref_time.kind == RefTime.END else 0)
+    return sat_track_host(OrbitSettings(orbit.sat_name, orbit.custom_tle, RefTime.Start(start - 500 * m)), height + 2 * m)
+
+
+def fit_sample_points(layers: "MapLayers", layer_ids=None, spacing_deg=0.05):
+    """The fit's sample points (aptgpu_fit_sample_points, CPU): an (n, 2) array of (lon, lat) in degrees."""
+    if not isinstance(layers, MapLayers):
+        raise InvalidError("fit: layers must be a MapLayers")
+    xy, n = _f64p(), C.c_size_t()
+    err = C.create_string_buffer(_ERRCAP)
+    _check(lib().aptgpu_fit_sample_points(layers._p, FitSettings(layers=layer_ids)._mask(), float(spacing_deg),
+                                          C.byref(xy), C.byref(n), err, _ERRCAP), err)
+    return _take(xy, 2 * n.value, np.float64).reshape(-1, 2)
+
+
+def _fit_call(fn, head, image, height, track_or_orbit, layers, map_settings, settings, return_scores):
+    settings = settings if settings is not None else FitSettings()
+    if not isinstance(settings, FitSettings):
+        raise InvalidError("fit: settings must be a FitSettings")
+    if map_settings is not None and not isinstance(map_settings, MapSettings):
+        raise InvalidError("fit: map_settings must be a MapSettings or None")
+    if not isinstance(layers, MapLayers):
+        raise InvalidError("fit: layers must be a MapLayers")
+    try:
+        cs = settings._c()
+    except (TypeError, ValueError, OverflowError) as e:
+        raise InvalidError(f"fit: {e}") from None
+    cms = map_settings._c() if map_settings is not None else None
+    pos, count, co, keep, track = None, 0, None, None, None
+    if isinstance(track_or_orbit, OrbitSettings):
+        c_orbit, keep = track_or_orbit._c()
+        co = C.byref(c_orbit)
+    elif track_or_orbit is not None:
+        track = np.ascontiguousarray(np.asarray(track_or_orbit, dtype=np.float64).reshape(-1, 2))
+        pos, count = track.ctypes.data_as(_f64p), track.shape[0]
+    info = FitResult()
+    info.struct_size = C.sizeof(FitResult)
+    p_scores, n_scores = C.c_void_p(), C.c_size_t()
+    err = C.create_string_buffer(_ERRCAP)
+    try:
+        _check(fn(*head, image, height, pos, count, co, layers._p, C.byref(cms) if cms is not None else None,
+                  C.byref(cs), C.byref(info), C.byref(p_scores) if return_scores else None,
+                  C.byref(n_scores) if return_scores else None, err, _ERRCAP), err)
+    except AptError as e:
+        e.info = info  # (the record of a failed call: status, reason, the rounds that ran)
+        raise
+    del keep
+    scores = None
+    if return_scores:
+        raw = C.string_at(p_scores, n_scores.value * FIT_SCORE_DTYPE.itemsize)
+        lib().aptgpu_free(p_scores)
+        scores = np.frombuffer(raw, FIT_SCORE_DTYPE).reshape(int(cs.rounds), -1)
+    base = map_settings if map_settings is not None else MapSettings()
+    fitted = MapSettings(info.yaw, info.hscale, info.vscale, base.countries_color, base.states_color, base.lakes_color)
+    out_track, out_orbit = None, None
+    if track is not None:
+        m = int(cs.margin_rows) + int(info.shift_rows)
+        out_track = track[m:m + int(height)].copy()
+    else:
+        rt = track_or_orbit.ref_time
+        out_orbit = OrbitSettings(track_or_orbit.sat_name, track_or_orbit.custom_tle,
+                                  RefTime(rt.kind, rt.unix_ms + int(info.time_offset_ms)), fitted)
+    return OverlayFit(info, fitted, out_track, out_orbit, scores)
+
+
+def _fit_image(image):
+    image = np.ascontiguousarray(image, dtype=np.uint8)
+    if image.ndim != 2 or image.shape[1] != PX_PER_ROW:
+        raise InvalidError("fit: the image is an unrotated (height, 2080) uint8 array")
+    return image
+
+
+def fit_overlay(image, track_or_orbit, layers, map_settings=None, settings=None, context=None, return_scores=False):
+    """Fits the map overlay to the image on the GPU: the yaw, hscale and vscale and the shift of the
+    track, in rows of 500 ms, under which the layers' lines lie on the image's edges.  image: the unrotated gray image
+    of process(rotate=Rotate.NO), (height, 2080) uint8.  track_or_orbit: a long track of height + 2 * margin_rows
+    (lat, lon) pairs in radians (margin_track() makes one), or an OrbitSettings (SGP4 then runs on the GPU).  Returns
+    an OverlayFit.  A failed call (a track of another length, SGP4, no candidate with min_points points inside)
+    raises InternalError whose `info` attribute is the record; a flat image returns the initial settings with
+    reason FIT_REASON_FLAT."""
+    image = _fit_image(image)
+    cctx = (context or Context())._c()
+    return _fit_call(lib().aptgpu_fit_overlay, (C.byref(cctx),), image.ctypes.data_as(_u8p), image.shape[0],
+                     track_or_orbit, layers, map_settings, settings, return_scores)
+
+
+def fit_overlay_host(image, track_or_orbit, layers, map_settings=None, settings=None, return_scores=False):
+    """fit_overlay() on the CPU, in plain C++ (no GPU needed): the same source text per point and candidate with the C
+    library's f64 functions."""
+    image = _fit_image(image)
+    return _fit_call(lib().aptgpu_fit_overlay_host, (), image.ctypes.data_as(_u8p), image.shape[0], track_or_orbit,
+                     layers, map_settings, settings, return_scores)
+
+
+def fit_overlay_device(d_image, height, track_or_orbit, layers, map_settings=None, settings=None, context=None,
+                       stream=None, return_scores=False):
+    """fit_overlay() for an image already in the memory of the context's device: d_image is the device address of
+    height rows of 2080 bytes, stream a hipStream_t as an integer (None: the default stream).  Returns once the record
+    has been read."""
+    cctx = (context or Context())._c()
+    c_stream = C.c_void_p(int(stream)) if stream is not None else None
+
+    def call(ctx, img, h, *rest):
+        return lib().aptgpu_fit_overlay_device(ctx, img, h, c_stream, *rest)
+    return _fit_call(call, (C.byref(cctx),), C.c_void_p(int(d_image)), int(height), track_or_orbit, layers,
+                     map_settings, settings, return_scores)
 
 
 class IqFormat:

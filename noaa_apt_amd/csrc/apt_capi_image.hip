@@ -16,11 +16,6 @@
 #include "apt_map.hpp"
 #include "apt_sat.hpp"
 
-// the opaque handle of include/aptgpu.h
-struct aptgpu_map_layers {
-    apt::map::Layers layers;
-};
-
 namespace {
 
 using namespace apt::capi;

@@ -15,6 +15,11 @@
 #include "apt_plan.hpp"
 #include "apt_sat.hpp"
 
+// the opaque layer-set handle of include/aptgpu.h (apt_capi_image.hip creates and fills it)
+struct aptgpu_map_layers {
+    apt::map::Layers layers;
+};
+
 namespace apt::capi {
 
 using apt::Error;
