@@ -42,6 +42,9 @@
  * audio comes out at FS / D; the signal sits SHIFT_HZ off the centre) with the library's usual channel filter.  Without
  * --live the frames go through aptgpu_fm_demodulate and aptgpu_decode; with --live SECONDS through aptgpu_iq_live_* in
  * chunks of SECONDS of frames, the audio never leaving the device.  Both write the same PGM.
+ * --afc[=MAX_HZ] (with --iq, without --live): the carrier is followed block by block and the frames go through
+ * aptgpu_fm_demodulate_afc instead: for a recording whose SHIFT_HZ is known only to within MAX_HZ (default 15000), the
+ * tuner's error and the Doppler shift of the pass.  The carrier's offset at the start, the middle and the end is printed.
  * --sun A|B:UNIX_MS[:BLACK] --track FILE: the rows go through aptgpu_geolocate first, which divides channel A's or B's
  * video by the cosine of the solar zenith angle at every pixel (capped at 80 degrees), for a pass that starts at
  * UNIX_MS; BLACK is the zero level in row units (default: wedge 9 of the telemetry, the zero-modulation wedge).
@@ -66,7 +69,7 @@ int main(int argc, char **argv)
                 "[--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE [--fit]] [--png]\n"
                 "       [--tle FILE --sat NAME (--start-ms N | --end-ms N)] [--rotate no|yes|orbit]\n"
                 "       [--project equirect|mercator[:step_deg] [--grid DEG]] [--despeckle R[:T]] [--track=[W,LAMBDA[,LAG]]]\n"
-                "       [--live SECONDS] [--iq u8|s8|s16|f32:FS:D[:SHIFT_HZ]] [--sun A|B:UNIX_MS[:BLACK] --track FILE]\n", argv[0]);
+                "       [--live SECONDS] [--iq u8|s8|s16|f32:FS:D[:SHIFT_HZ] [--afc[=MAX_HZ]]] [--sun A|B:UNIX_MS[:BLACK] --track FILE]\n", argv[0]);
         return 2;
     }
     int contrast = APTGPU_CONTRAST_PERCENT, sync = 1, lab = 0, png = 0, fit = 0;
@@ -74,7 +77,8 @@ int main(int argc, char **argv)
     int rotate = APTGPU_ROTATE_NO, ref_kind = -1;
     long long ref_ms = 0;
     const char *project = NULL, *despeckle = NULL, *flywheel = NULL, *iq_spec = NULL, *sun = NULL;
-    double grid_deg = 0.0, live_seconds = 0.0;
+    double grid_deg = 0.0, live_seconds = 0.0, afc_max_hz = 15000.0;
+    int afc = 0;
     for (int i = 3; i < argc; ++i) {
         if (!strcmp(argv[i], "telemetry")) contrast = APTGPU_CONTRAST_TELEMETRY;
         else if (!strcmp(argv[i], "percent")) contrast = APTGPU_CONTRAST_PERCENT;
@@ -99,6 +103,8 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--live") && i + 1 < argc) live_seconds = atof(argv[++i]);
         else if (!strcmp(argv[i], "--iq") && i + 1 < argc) iq_spec = argv[++i];
         else if (!strcmp(argv[i], "--sun") && i + 1 < argc) sun = argv[++i];
+        else if (!strcmp(argv[i], "--afc")) afc = 1;
+        else if (!strncmp(argv[i], "--afc=", 6)) afc = 1, afc_max_hz = atof(argv[i] + 6); /* (0 or no number: refused by the library) */
         else if (!strcmp(argv[i], "--rotate") && i + 1 < argc) {
             const char *r = argv[++i];
             rotate = !strcmp(r, "orbit") ? APTGPU_ROTATE_ORBIT : !strcmp(r, "yes") ? APTGPU_ROTATE_YES : APTGPU_ROTATE_NO;
@@ -169,6 +175,10 @@ int main(int argc, char **argv)
             return 2;
         }
     }
+    if (afc && (!iq_spec || live_seconds > 0.0)) {
+        fprintf(stderr, "--afc follows the carrier of a whole IQ recording: it needs --iq and excludes --live\n");
+        return 2;
+    }
     if (iq_spec) {
         /* raw IQ frames: FM demodulation in front of the decode, in one piece or as a live stream */
         aptgpu_fm_settings fs;
@@ -235,7 +245,29 @@ int main(int argc, char **argv)
         } else {
             float *audio = NULL;
             size_t n_audio = 0;
-            rc = aptgpu_fm_demodulate(&ctx, &fs, bytes, n_frames, &audio, &n_audio, &rate, err, sizeof err);
+            if (afc) {
+                /* the carrier is not where SHIFT_HZ says: estimate it per block, demodulate with an NCO that follows */
+                aptgpu_afc_settings as;
+                aptgpu_fm_afc_default_settings(&as);
+                as.max_offset_hz = (float)afc_max_hz;
+                aptgpu_afc_record *table = NULL;
+                uint8_t *good = NULL;
+                size_t n_blocks = 0, n_good = 0;
+                rc = aptgpu_fm_demodulate_afc(&ctx, &fs, &as, bytes, n_frames, &audio, &n_audio, &rate, &table, NULL, &good,
+                                              &n_blocks, err, sizeof err);
+                if (rc == APTGPU_OK && n_blocks) {
+                    const size_t at[3] = {0, n_blocks / 2, n_blocks - 1};
+                    double hz[3];
+                    for (int k = 0; k < 3; ++k) hz[k] = (double)(int32_t)table[at[k]].pw * fs_hz / 4294967296.0;
+                    for (size_t b = 0; b < n_blocks; ++b) n_good += good[b];
+                    fprintf(stderr, "afc: carrier at %+.0f Hz, %+.0f Hz, %+.0f Hz (start, middle, end); %llu of %llu blocks good\n",
+                            hz[0], hz[1], hz[2], (unsigned long long)n_good, (unsigned long long)n_blocks);
+                }
+                aptgpu_free(table);
+                aptgpu_free(good);
+            } else {
+                rc = aptgpu_fm_demodulate(&ctx, &fs, bytes, n_frames, &audio, &n_audio, &rate, err, sizeof err);
+            }
             free(bytes);
             if (rc != APTGPU_OK) { fprintf(stderr, "fm demodulation failed (%d): %s\n", rc, err); return 1; }
             rc = aptgpu_decode(&ctx, &settings, audio, n_audio, rate, sync, &rows, &n_rows_px, &stats, err, sizeof err);

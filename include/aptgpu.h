@@ -1276,6 +1276,133 @@ int aptgpu_fm_demodulate_wav(const aptgpu_context *ctx, const aptgpu_fm_settings
                              size_t n, float **audio, size_t *n_out, uint32_t *rate_hz, char *err, size_t err_cap);
 
 /* ====================================================================== */
+/* 4b'. AFC: follow the carrier of an IQ recording, in front of §4b */
+/* ====================================================================== */
+/* §4b needs shift_hz exactly; a recording's carrier is off by the tuner's error (30-60 ppm at 137 MHz: 4-8 kHz) and by
+ * a Doppler shift that changes through the pass (+-3.4 kHz).  This stage estimates the carrier block by block from the
+ * raw frames and demodulates with an NCO that follows the estimates.  The reference has nothing comparable, so the
+ * definition is this library's; tests/np_afc_model.py states it in numpy.  Opt-in: nothing of §4b changes.
+ *
+ * Settings (aptgpu_afc_settings) next to the aptgpu_fm_settings of §4b, with fs = sample_rate_hz:
+ *   block_frames  B, a power of two in 64 ... 2^20 (default 4096)
+ *   lag           L in 1 ... 64, or 0 = auto: floor(fs / (4 (max_offset_hz + deviation_hz))) clamped to 1 ... 64
+ *   smooth_blocks W, odd, 1 ... 1023 (default 15)
+ *   max_offset_hz finite, > 0 (default 15000): estimates further than this from shift_hz are not believed
+ *   min_coherence in [0, 1) (default 0.05)
+ * pw_base is §4b's pw of shift_hz.  A recording of n frames has nb = ceil(n / B) blocks, nb <= 2^20.
+ *
+ * Stage A, block sums.  Components are integers: u8 2 raw - 255 (twice §4b's value), s8 / s16 the value; SWAP_IQ is
+ *   applied.  For block b, over its frames i in [b B, min((b + 1) B, n)):
+ *     re[b] = sum I[i + L] I[i] + Q[i + L] Q[i]   over i with i + L < n (the terms reach into the next block)
+ *     im[b] = sum Q[i + L] I[i] - I[i + L] Q[i]   over the same i
+ *     en[b] = sum I[i]^2 + Q[i]^2                 over all frames of the block
+ *   exact in int64 (a block of s16 at -32768 reaches 2^51, a window of 1023 such 2^61).  F32: the components are the
+ *   floats; products and sums are f64, in any order.  The sums are returned as f64 triples {re, im, en} per block: for
+ *   the integer formats that conversion is exact.
+ * Stage B, the table.  All arithmetic is f64 without contraction; adds run in ascending block order from 0.
+ *   1. The window of b is [max(b - W / 2, 0), min(b + W / 2, nb - 1)]; R and E are its sums of (re, im) and en.
+ *   2. coherence[b] = sqrt(Rre^2 + Rim^2) / E, 0 where E == 0; returned as f32 (a NaN as 0x7FC00000).
+ *   3. If a component of R or E is not finite the block is not good and has no estimate.  Otherwise
+ *        q = (uint32) llrint(atan2(Rim, Rre) / (2 pi) * 2^32), d = (int32)(q - (uint32)(L * pw_base)),
+ *        rel = llround((double) d / L), est[b] = pw_base + rel.
+ *   4. b is good iff coherence[b] (the f64 value) >= min_coherence and |rel| * fs / 2^32 <= max_offset_hz.
+ *   5. Hold: pw[b] = est[j], j the nearest good block at or before b; if there is none, the first good block after b;
+ *      if no block is good, pw[b] = pw_base.
+ *   6. phase0[0] = 0, phase0[b + 1] = phase0[b] + B * pw[b] in uint32.
+ *   7. step[b] = (f32) cos t, (f32) -sin t in f64 with t = (int32) pw[b] * pi / 2^31: §4b's step of pw[b].
+ *   Per block: the 16-byte aptgpu_afc_record {pw, phase0, step_re, step_im}, coherence (f32) and good (u8).
+ * Stage C, tracked demodulation: §4b with one change.  The phase of frame i is phase0[b] + (uint32)(i - b B) * pw[b],
+ *   b = i / B.  A run of 8 lies inside one block; its first phasor is that of the phase at i - i % 8 and its step is
+ *   step[b].  The mix is always made (also where every pw is 0).  Filter, discriminate, the non-finite rules and §4b's
+ *   bound are unchanged, with the model's phasor that of the table's phase.  A table whose every block has
+ *   pw = pw_base != 0 and phase0 = (uint32)(b B pw_base) gives §4b's bits.
+ * The frequency steps between blocks are a few Hz (Doppler moves by at most about 100 Hz / s): under 1e-3 of the
+ * deviation, as DC that the AM demodulation behind it removes.  Not built: a chirp inside blocks, DC-spike removal, a
+ * streaming or causal form (§4f's streams are untouched), any narrowing of the estimator's band: stage A sees the whole
+ * recorded band, so a stronger signal elsewhere in it wins.
+ *
+ * Refused on the host, before a device is touched, with APTGPU_ERR_INVALID and a text naming the field: everything
+ * §4b refuses; a short struct_size; block_frames not a power of two or outside 64 ... 2^20; lag above 64;
+ * smooth_blocks even or outside 1 ... 1023; max_offset_hz not finite or not positive; min_coherence not in [0, 1);
+ * n_frames with more than 2^20 blocks; n_blocks that is not ceil(n_frames / B) where a table is passed in. */
+typedef struct aptgpu_afc_settings {
+    uint32_t struct_size;   /* sizeof(aptgpu_afc_settings) */
+    uint32_t block_frames;  /* B */
+    uint32_t lag;           /* L; 0 = auto */
+    uint32_t smooth_blocks; /* W */
+    float max_offset_hz;
+    float min_coherence;
+} aptgpu_afc_settings;
+void aptgpu_fm_afc_default_settings(aptgpu_afc_settings *settings);
+
+typedef struct aptgpu_afc_record {
+    uint32_t pw;     /* phase increment per frame of the block, 2^32 = one turn */
+    uint32_t phase0; /* phase of the block's first frame */
+    float step_re, step_im;
+} aptgpu_afc_record;
+
+typedef struct aptgpu_afc_info {
+    uint32_t struct_size; /* in: sizeof(aptgpu_afc_info) */
+    uint32_t block_frames, lag, smooth_blocks; /* lag: the one used */
+    uint32_t pw_base;
+    uint32_t sample_rate_hz;
+    double max_offset_hz, min_coherence;
+} aptgpu_afc_info;
+/* The checks of both settings and what they come to (no GPU). */
+int aptgpu_fm_afc_design(const aptgpu_fm_settings *fm_settings, const aptgpu_afc_settings *settings,
+                         aptgpu_afc_info *info, char *err, size_t err_cap);
+
+/* Stage A on host arrays: *sums malloc'd (aptgpu_free), 3 * *n_blocks doubles, {re, im, en} per block. */
+int aptgpu_fm_afc_sums(const aptgpu_context *ctx, const aptgpu_fm_settings *fm_settings,
+                       const aptgpu_afc_settings *settings, const void *iq, size_t n_frames, double **sums,
+                       size_t *n_blocks, char *err, size_t err_cap);
+int aptgpu_fm_afc_sums_host(const aptgpu_fm_settings *fm_settings, const aptgpu_afc_settings *settings, const void *iq,
+                            size_t n_frames, double **sums, size_t *n_blocks, char *err, size_t err_cap);
+/* Stage B on the caller's sums (3 * n_blocks doubles): *table, *coherence and *good malloc'd (aptgpu_free), n_blocks
+ * entries each; coherence and good nullable. */
+int aptgpu_fm_afc_estimate(const aptgpu_context *ctx, const aptgpu_fm_settings *fm_settings,
+                           const aptgpu_afc_settings *settings, const double *sums, size_t n_blocks,
+                           aptgpu_afc_record **table, float **coherence, uint8_t **good, char *err, size_t err_cap);
+int aptgpu_fm_afc_estimate_host(const aptgpu_fm_settings *fm_settings, const aptgpu_afc_settings *settings,
+                                const double *sums, size_t n_blocks, aptgpu_afc_record **table, float **coherence,
+                                uint8_t **good, char *err, size_t err_cap);
+/* Stage C with the caller's table of n_blocks = ceil(n_frames / B) records; the outputs as aptgpu_fm_demodulate's. */
+int aptgpu_fm_demodulate_tracked(const aptgpu_context *ctx, const aptgpu_fm_settings *fm_settings,
+                                 const aptgpu_afc_settings *settings, const void *iq, size_t n_frames,
+                                 const aptgpu_afc_record *table, size_t n_blocks, float **audio, size_t *n_out,
+                                 uint32_t *rate_hz, char *err, size_t err_cap);
+int aptgpu_fm_demodulate_tracked_host(const aptgpu_fm_settings *fm_settings, const aptgpu_afc_settings *settings,
+                                      const void *iq, size_t n_frames, const aptgpu_afc_record *table, size_t n_blocks,
+                                      float **audio, size_t *n_out, uint32_t *rate_hz, char *err, size_t err_cap);
+/* All three stages.  table, coherence, good and n_blocks are nullable: where given they receive stage B's outputs,
+ * malloc'd (aptgpu_free). */
+int aptgpu_fm_demodulate_afc(const aptgpu_context *ctx, const aptgpu_fm_settings *fm_settings,
+                             const aptgpu_afc_settings *settings, const void *iq, size_t n_frames, float **audio,
+                             size_t *n_out, uint32_t *rate_hz, aptgpu_afc_record **table, float **coherence,
+                             uint8_t **good, size_t *n_blocks, char *err, size_t err_cap);
+int aptgpu_fm_demodulate_afc_host(const aptgpu_fm_settings *fm_settings, const aptgpu_afc_settings *settings,
+                                  const void *iq, size_t n_frames, float **audio, size_t *n_out, uint32_t *rate_hz,
+                                  aptgpu_afc_record **table, float **coherence, uint8_t **good, size_t *n_blocks,
+                                  char *err, size_t err_cap);
+/* Device-resident, behind an aptgpu_fm (whose settings, device and stream it takes; the aptgpu_fm must be alive in
+ * every aptgpu_fm_afc_demodulate_device call; aptgpu_fm_afc_destroy does not need it):
+ * the work space for APTGPU_FM_MAX_BATCH recordings of up to max_frames frames is allocated here, once. */
+typedef struct aptgpu_fm_afc aptgpu_fm_afc;
+int aptgpu_fm_afc_create(aptgpu_fm *fm, const aptgpu_afc_settings *settings, size_t max_frames, aptgpu_fm_afc **afc,
+                         char *err, size_t err_cap);
+void aptgpu_fm_afc_destroy(aptgpu_fm_afc *afc);
+/* `count` (<= APTGPU_FM_MAX_BATCH) recordings through the three stages: three kernel launches on the demodulator's
+ * stream, no allocation and no host synchronisation.  d_iq, n_frames, d_audio, audio_cap as
+ * aptgpu_fm_demodulate_device.  d_sums, d_table, d_coherence, d_good: nullable arrays of `count` nullable device
+ * pointers; where one is given, recording i's stage-A sums (3 doubles per block, 8-byte aligned) or its table
+ * (ceil(n_frames[i] / B) entries; d_table[i] 16-byte aligned, d_coherence[i] 4-byte) is left there, otherwise in the
+ * work space.  n_frames[i] above max_frames is refused. */
+int aptgpu_fm_afc_demodulate_device(aptgpu_fm_afc *afc, int count, const void *const *d_iq, const size_t *n_frames,
+                                    float *const *d_audio, const size_t *audio_cap, double *const *d_sums,
+                                    aptgpu_afc_record *const *d_table, float *const *d_coherence,
+                                    uint8_t *const *d_good, char *err, size_t err_cap);
+
+/* ====================================================================== */
 /* 4c. flywheel sync: row starts tracked through noise and dropouts */
 /* ====================================================================== */
 /* find_sync (decode.rs:204-263) keeps the largest value of an unnormalised +-1 correlation inside 0.8 of a row: one

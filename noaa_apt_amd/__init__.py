@@ -45,6 +45,9 @@ Names, argument meaning and error behaviour follow the reference:
     fm_demodulate, fm_demodulate_host, fm_demodulate_wav,  FM demodulation of an IQ recording in front of decode()
     fm_design, load_iq, IqFormat, FmSettings,              (the reference takes audio only, docs/usage.md:87),
     FmDemodulator                                          DESIGN.md §20
+    fm_demodulate_afc, fm_afc_sums, fm_afc_estimate,       AFC in front of it: the carrier followed block by block, the
+    fm_demodulate_tracked (each with a _host form),        NCO reading a table (the reference has no IQ input at all),
+    fm_afc_design, AfcSettings, AfcTable, FmAfc            DESIGN.md §27
     track_sync, track_sync_host, sync_score,               the reference's to-do list, docs/development.md:148: row
     decode_tracked, TrackSettings, Plan.track_device       starts tracked through noise and dropouts, DESIGN.md §21
     LiveTrackSettings, LiveDecoder(track=...),             live decode with the flywheel tracker's row starts, from audio
@@ -79,6 +82,9 @@ from .api import (  # noqa: F401
     margin_track, FIT_REASON_NO_CANDIDATE, FIT_REASON_FLAT, FIT_SCORE_DTYPE,
     IqFormat, FmSettings, FmInfo, FmDemodulator, fm_demodulate, fm_demodulate_host, fm_demodulate_wav, fm_design, load_iq,
     FM_SWAP_IQ, FM_MAX_BATCH,
+    AfcSettings, AfcInfo, AfcTable, FmAfc, AFC_RECORD_DTYPE, fm_afc_design, fm_afc_sums, fm_afc_sums_host,
+    fm_afc_estimate, fm_afc_estimate_host, fm_demodulate_tracked, fm_demodulate_tracked_host, fm_demodulate_afc,
+    fm_demodulate_afc_host,
     TrackSettings, TrackResult, track_sync, track_sync_host, sync_score, decode_tracked, TRACK_MAX_JITTER,
     LiveDecoder, decode_live, StreamInfo, StreamResult, LiveTrackSettings, StreamTrackResult,
     FmStream, FmStreamInfo, LiveIqDecoder, decode_live_iq, FM_STREAM_MAX_PUSH_FRAMES,

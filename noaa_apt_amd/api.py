@@ -296,6 +296,19 @@ class _CFmInfo(C.Structure):
                 ("pw", C.c_uint32), ("reserved", C.c_uint32), ("shift_hz_used", C.c_double), ("taps", _f32p)]
 
 
+class _CAfcSettings(C.Structure):
+    """aptgpu_afc_settings"""
+    _fields_ = [("struct_size", C.c_uint32), ("block_frames", C.c_uint32), ("lag", C.c_uint32),
+                ("smooth_blocks", C.c_uint32), ("max_offset_hz", C.c_float), ("min_coherence", C.c_float)]
+
+
+class _CAfcInfo(C.Structure):
+    """aptgpu_afc_info"""
+    _fields_ = [("struct_size", C.c_uint32), ("block_frames", C.c_uint32), ("lag", C.c_uint32),
+                ("smooth_blocks", C.c_uint32), ("pw_base", C.c_uint32), ("sample_rate_hz", C.c_uint32),
+                ("max_offset_hz", C.c_double), ("min_coherence", C.c_double)]
+
+
 class _CFmStreamSettings(C.Structure):
     """aptgpu_fm_stream_settings"""
     _fields_ = [("struct_size", C.c_uint32), ("max_push_frames", C.c_uint32), ("first_frame", C.c_uint64),
@@ -575,6 +588,25 @@ def lib():
     L.aptgpu_fm_demodulate_device.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz),
                                               C.c_char_p, sz]
     L.aptgpu_fm_demodulate_wav.argtypes = [cp, cfm, C.c_char_p, sz, *fm_out]
+    cafc = C.POINTER(_CAfcSettings)
+    f64p, u8p = C.POINTER(C.c_double), C.POINTER(C.c_uint8)
+    afc_table_out = (C.POINTER(_u32p), C.POINTER(_f32p), C.POINTER(u8p))
+    L.aptgpu_fm_afc_default_settings.argtypes = [cafc]
+    L.aptgpu_fm_afc_default_settings.restype = None
+    L.aptgpu_fm_afc_design.argtypes = [cfm, cafc, C.POINTER(_CAfcInfo), C.c_char_p, sz]
+    L.aptgpu_fm_afc_sums.argtypes = [cp, cfm, cafc, vp, sz, C.POINTER(f64p), C.POINTER(sz), C.c_char_p, sz]
+    L.aptgpu_fm_afc_sums_host.argtypes = [cfm, cafc, vp, sz, C.POINTER(f64p), C.POINTER(sz), C.c_char_p, sz]
+    L.aptgpu_fm_afc_estimate.argtypes = [cp, cfm, cafc, vp, sz, *afc_table_out, C.c_char_p, sz]
+    L.aptgpu_fm_afc_estimate_host.argtypes = [cfm, cafc, vp, sz, *afc_table_out, C.c_char_p, sz]
+    L.aptgpu_fm_demodulate_tracked.argtypes = [cp, cfm, cafc, vp, sz, vp, sz, *fm_out]
+    L.aptgpu_fm_demodulate_tracked_host.argtypes = [cfm, cafc, vp, sz, vp, sz, *fm_out]
+    L.aptgpu_fm_demodulate_afc.argtypes = [cp, cfm, cafc, vp, sz, *fm_out[:3], *afc_table_out, C.POINTER(sz), C.c_char_p, sz]
+    L.aptgpu_fm_demodulate_afc_host.argtypes = [cfm, cafc, vp, sz, *fm_out[:3], *afc_table_out, C.POINTER(sz), C.c_char_p, sz]
+    L.aptgpu_fm_afc_create.argtypes = [vp, cafc, sz, C.POINTER(vp), C.c_char_p, sz]
+    L.aptgpu_fm_afc_destroy.argtypes = [vp]
+    L.aptgpu_fm_afc_destroy.restype = None
+    L.aptgpu_fm_afc_demodulate_device.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz),
+                                                  C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.c_char_p, sz]
     cts, ctr = C.POINTER(_CTrackSettings), C.POINTER(TrackResult)
     L.aptgpu_track_sync.argtypes = [cp, i32, C.POINTER(_f32p), C.POINTER(sz), u32, cts, C.POINTER(_u64p),
                                     C.POINTER(_f32p), C.POINTER(_f32p), ctr, C.c_char_p, sz]
@@ -2572,6 +2604,232 @@ class FmDemodulator:
         _check(lib().aptgpu_fm_demodulate_device(self._p, k, (C.c_void_p * k)(*d_iq), (C.c_size_t * k)(*n_frames),
                                                  (C.c_void_p * k)(*d_audio), (C.c_size_t * k)(*audio_cap), err,
                                                  _ERRCAP), err)
+
+
+# aptgpu_afc_record: one block of the tracked demodulator's table
+AFC_RECORD_DTYPE = np.dtype([("pw", "<u4"), ("phase0", "<u4"), ("step_re", "<f4"), ("step_im", "<f4")])
+
+
+@dataclass
+class AfcSettings:
+    """aptgpu_afc_settings (DESIGN.md §27).  block_frames: B, a power of two in 64 ... 2^20; lag: L in 1 ... 64, 0 = auto;
+    smooth_blocks: W, odd, 1 ... 1023; max_offset_hz: estimates further from shift_hz are not believed; min_coherence:
+    in [0, 1), below it a block holds its neighbour's estimate."""
+    block_frames: int = 4096
+    lag: int = 0
+    smooth_blocks: int = 15
+    max_offset_hz: float = 15000.0
+    min_coherence: float = 0.05
+
+    def _c(self, struct_size=None):
+        try:
+            return _CAfcSettings(C.sizeof(_CAfcSettings) if struct_size is None else int(struct_size),
+                                 int(self.block_frames), int(self.lag), int(self.smooth_blocks),
+                                 float(self.max_offset_hz), float(self.min_coherence))
+        except (TypeError, ValueError, OverflowError) as e:
+            raise InvalidError(f"aptgpu_afc_settings: {e}") from None
+
+
+@dataclass(frozen=True)
+class AfcInfo:
+    """aptgpu_afc_info: the settings as they are used (lag: the auto value where it was 0), the phase increment of
+    shift_hz and the rate."""
+    block_frames: int
+    lag: int
+    smooth_blocks: int
+    pw_base: int
+    sample_rate: int
+    max_offset_hz: float
+    min_coherence: float
+
+
+@dataclass(frozen=True)
+class AfcTable:
+    """Stage B's outputs: records (AFC_RECORD_DTYPE: pw, phase0, step_re, step_im per block), coherence (f32) and good
+    (bool), with the info they were made under."""
+    records: np.ndarray
+    coherence: Optional[np.ndarray]
+    good: Optional[np.ndarray]
+    info: AfcInfo
+
+    @property
+    def offset_hz(self):
+        """the carrier's offset from the recording's centre that every block's pw stands for, in Hz"""
+        return self.records["pw"].astype(np.int32).astype(np.float64) * self.info.sample_rate / 4294967296.0
+
+
+def _afc_settings_c(afc, struct_size=None):
+    afc = AfcSettings() if afc is None else afc
+    if not isinstance(afc, AfcSettings):
+        raise InvalidError("afc: afc_settings must be an AfcSettings")
+    return afc._c(struct_size)
+
+
+def fm_afc_design(settings, afc=None, struct_size=None) -> AfcInfo:
+    """The checks of an FmSettings and an AfcSettings alone, on the host (no GPU): every refusal raises InvalidError
+    with the field's name."""
+    cs, ca = _fm_settings_c(settings), _afc_settings_c(afc, struct_size)
+    info = _CAfcInfo(struct_size=C.sizeof(_CAfcInfo))
+    err = C.create_string_buffer(_ERRCAP)
+    _check(lib().aptgpu_fm_afc_design(C.byref(cs), C.byref(ca), C.byref(info), err, _ERRCAP), err)
+    return AfcInfo(int(info.block_frames), int(info.lag), int(info.smooth_blocks), int(info.pw_base),
+                   int(info.sample_rate_hz), float(info.max_offset_hz), float(info.min_coherence))
+
+
+def _afc_table(table, coh, good, n, info):
+    records = _take(table, 4 * n, np.uint32).view(AFC_RECORD_DTYPE)
+    return AfcTable(records, _take(coh, n), _take(good, n, np.uint8).astype(bool), info)
+
+
+def _afc_records(table):
+    a = table.records if isinstance(table, AfcTable) else np.asarray(table)
+    if a.dtype != AFC_RECORD_DTYPE:
+        raise InvalidError(f"afc: the table has dtype {a.dtype}, not AFC_RECORD_DTYPE")
+    return np.ascontiguousarray(a).reshape(-1)
+
+
+def _afc_sums_call(fn, head, iq, settings, afc):
+    cs, ca = _fm_settings_c(settings), _afc_settings_c(afc)
+    a, frames = _fm_iq(iq, cs)
+    out, n = C.POINTER(C.c_double)(), C.c_size_t()
+    err = C.create_string_buffer(_ERRCAP)
+    _check(fn(*head, C.byref(cs), C.byref(ca), a.ctypes.data if a.size else None, frames, C.byref(out), C.byref(n), err,
+              _ERRCAP), err)
+    return _take(out, 3 * n.value, np.float64).reshape(-1, 3)
+
+
+def fm_afc_sums(iq, settings, afc=None, context=None):
+    """Stage A of the AFC on the GPU: the block sums of an IQ recording, an (nb, 3) f64 array of {re, im, en}: the lag-L
+    autocorrelation and the energy of every block of block_frames frames (exact for the integer formats)."""
+    cctx = (context or Context())._c()
+    return _afc_sums_call(lib().aptgpu_fm_afc_sums, (C.byref(cctx),), iq, settings, afc)
+
+
+def fm_afc_sums_host(iq, settings, afc=None):
+    """fm_afc_sums() on the CPU, in plain C++ (no GPU needed)."""
+    return _afc_sums_call(lib().aptgpu_fm_afc_sums_host, (), iq, settings, afc)
+
+
+def _afc_estimate_call(fn, head, sums, settings, afc):
+    cs, ca = _fm_settings_c(settings), _afc_settings_c(afc)
+    s = np.ascontiguousarray(sums, dtype=np.float64)
+    if s.ndim != 2 or s.shape[1] != 3:
+        raise InvalidError("afc: sums must have shape (blocks, 3)")
+    nb = s.shape[0]
+    table, coh, good = _u32p(), _f32p(), C.POINTER(C.c_uint8)()
+    err = C.create_string_buffer(_ERRCAP)
+    _check(fn(*head, C.byref(cs), C.byref(ca), s.ctypes.data if nb else None, nb, C.byref(table), C.byref(coh),
+              C.byref(good), err, _ERRCAP), err)
+    return _afc_table(table, coh, good, nb, fm_afc_design(settings, afc))
+
+
+def fm_afc_estimate(sums, settings, afc=None, context=None) -> AfcTable:
+    """Stage B of the AFC on the GPU: the table of one record per block from the block sums of fm_afc_sums()."""
+    cctx = (context or Context())._c()
+    return _afc_estimate_call(lib().aptgpu_fm_afc_estimate, (C.byref(cctx),), sums, settings, afc)
+
+
+def fm_afc_estimate_host(sums, settings, afc=None) -> AfcTable:
+    """fm_afc_estimate() on the CPU, in plain C++ (no GPU needed): the same f64 arithmetic up to atan2, cos and sin."""
+    return _afc_estimate_call(lib().aptgpu_fm_afc_estimate_host, (), sums, settings, afc)
+
+
+def _afc_tracked_call(fn, head, iq, table, settings, afc):
+    cs, ca = _fm_settings_c(settings), _afc_settings_c(afc)
+    a, frames = _fm_iq(iq, cs)
+    t = _afc_records(table)
+    out, n, rate = _f32p(), C.c_size_t(), C.c_uint32()
+    err = C.create_string_buffer(_ERRCAP)
+    _check(fn(*head, C.byref(cs), C.byref(ca), a.ctypes.data if a.size else None, frames, t.ctypes.data if t.size else None,
+              t.size, C.byref(out), C.byref(n), C.byref(rate), err, _ERRCAP), err)
+    return _take(out, n.value), Rate.hz(rate.value)
+
+
+def fm_demodulate_tracked(iq, table, settings, afc=None, context=None):
+    """Stage C of the AFC on the GPU: fm_demodulate() with the phase of every frame taken from `table` (an AfcTable or an
+    AFC_RECORD_DTYPE array of ceil(frames / block_frames) records).  Returns (audio, Rate)."""
+    cctx = (context or Context())._c()
+    return _afc_tracked_call(lib().aptgpu_fm_demodulate_tracked, (C.byref(cctx),), iq, table, settings, afc)
+
+
+def fm_demodulate_tracked_host(iq, table, settings, afc=None):
+    """fm_demodulate_tracked() on the CPU, in plain C++ (no GPU needed)."""
+    return _afc_tracked_call(lib().aptgpu_fm_demodulate_tracked_host, (), iq, table, settings, afc)
+
+
+def _afc_call(fn, head, iq, settings, afc):
+    cs, ca = _fm_settings_c(settings), _afc_settings_c(afc)
+    a, frames = _fm_iq(iq, cs)
+    out, n, rate = _f32p(), C.c_size_t(), C.c_uint32()
+    table, coh, good, nb = _u32p(), _f32p(), C.POINTER(C.c_uint8)(), C.c_size_t()
+    err = C.create_string_buffer(_ERRCAP)
+    _check(fn(*head, C.byref(cs), C.byref(ca), a.ctypes.data if a.size else None, frames, C.byref(out), C.byref(n),
+              C.byref(rate), C.byref(table), C.byref(coh), C.byref(good), C.byref(nb), err, _ERRCAP), err)
+    return (_take(out, n.value), Rate.hz(rate.value),
+            _afc_table(table, coh, good, nb.value, fm_afc_design(settings, afc)))
+
+
+def fm_demodulate_afc(iq, settings, afc=None, context=None):
+    """FM-demodulate an IQ recording whose carrier is not where settings.shift_hz says, on the GPU:
+    estimate the carrier block by block from the raw frames, then demodulate with an NCO that follows the estimates.
+    Returns (audio, Rate, AfcTable): the audio for decode(), and the table with its offset_hz per block."""
+    cctx = (context or Context())._c()
+    return _afc_call(lib().aptgpu_fm_demodulate_afc, (C.byref(cctx),), iq, settings, afc)
+
+
+def fm_demodulate_afc_host(iq, settings, afc=None):
+    """fm_demodulate_afc() on the CPU, in plain C++ (no GPU needed)."""
+    return _afc_call(lib().aptgpu_fm_demodulate_afc_host, (), iq, settings, afc)
+
+
+class FmAfc:
+    """aptgpu_fm_afc: the AFC behind an FmDemodulator, for recordings already in HBM of up to max_frames frames each.
+    Runs on the demodulator's stream; the demodulator must stay open while this is."""
+
+    def __init__(self, demodulator: "FmDemodulator", afc=None, max_frames=1 << 24):
+        if not isinstance(demodulator, FmDemodulator) or not demodulator._p:
+            raise InvalidError("afc: demodulator must be an open FmDemodulator")
+        ca = _afc_settings_c(afc)
+        self._fmd = demodulator
+        self._p = C.c_void_p()
+        err = C.create_string_buffer(_ERRCAP)
+        _check(lib().aptgpu_fm_afc_create(demodulator._p, C.byref(ca), int(max_frames), C.byref(self._p), err, _ERRCAP),
+               err)
+        self.block_frames = int(ca.block_frames)
+
+    def close(self):
+        if self._p:
+            lib().aptgpu_fm_afc_destroy(self._p)  # (does not need the demodulator alive)
+            self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def n_blocks(self, n_frames):
+        return -(-int(n_frames) // self.block_frames)
+
+    def demodulate_device(self, d_iq: Sequence[int], n_frames: Sequence[int], d_audio: Sequence[int],
+                          audio_cap: Sequence[int], d_table: Optional[Sequence[int]] = None,
+                          d_coherence: Optional[Sequence[int]] = None, d_good: Optional[Sequence[int]] = None,
+                          d_sums: Optional[Sequence[int]] = None):
+        """Up to FM_MAX_BATCH recordings through the three stages: three launches, asynchronous on the demodulator's
+        stream.  d_iq, n_frames, d_audio, audio_cap as FmDemodulator.demodulate_device; d_table / d_coherence / d_good /
+        d_sums: optional device pointers (0: none) that receive recording i's n_blocks(n_frames[i]) records (16 bytes
+        each), f32 coherences, u8 good flags and f64 {re, im, en} sums."""
+        if not self._p or not self._fmd._p:
+            raise InvalidError("afc: the FmAfc or its FmDemodulator is closed")
+        k = len(d_iq)
+
+        def ptrs(v):
+            return None if v is None else (C.c_void_p * k)(*[int(x) or None for x in v])
+        err = C.create_string_buffer(_ERRCAP)
+        _check(lib().aptgpu_fm_afc_demodulate_device(self._p, k, (C.c_void_p * k)(*d_iq), (C.c_size_t * k)(*n_frames),
+                                                     (C.c_void_p * k)(*d_audio), (C.c_size_t * k)(*audio_cap),
+                                                     ptrs(d_sums), ptrs(d_table), ptrs(d_coherence), ptrs(d_good), err,
+                                                     _ERRCAP), err)
 
 
 FM_STREAM_MAX_PUSH_FRAMES = 1 << 20

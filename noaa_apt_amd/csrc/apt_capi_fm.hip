@@ -1,16 +1,7 @@
 // apt_capi_fm.hip — extern "C" surface of include/aptgpu.h §4b: FM demodulation of IQ recordings in front of decode().
+#include "apt_capi_fm_handle.hpp"
 #include "apt_capi_util.hpp"
-#include "apt_kernels_fm.hpp"
 #include "apt_wav.hpp"
-
-struct aptgpu_fm {
-    apt::fm::Design design;
-    apt::fm::Tile tile{};
-    int device = 0;
-    hipStream_t stream = nullptr;
-    apt::DeviceBuffer<float> d_taps_rev;
-    apt::DeviceBuffer<uint32_t> d_offsets;
-};
 
 namespace {
 
@@ -27,8 +18,11 @@ void fill_info(const apt::fm::Design &d, aptgpu_fm_info *info, const float *taps
     info->taps = taps;
 }
 
+}  // namespace
+
+namespace apt::capi {
 // the demodulator's state on `stream` of `device`; the taps are on the device when this returns
-void setup(aptgpu_fm &fm, const aptgpu_fm_settings *settings, int device, hipStream_t stream)
+void fm_setup(aptgpu_fm &fm, const aptgpu_fm_settings *settings, int device, hipStream_t stream)
 {
     fm.design = apt::fm::design_of(settings);  // every refusal, before a device is touched
     fm.tile = apt::fm::tile_of(fm.design.D, fm.design.T);
@@ -48,14 +42,13 @@ void setup(aptgpu_fm &fm, const aptgpu_fm_settings *settings, int device, hipStr
     apt::gpu::fm_prepare(fm.design.format, fm.design.pw != 0, fm.tile);
 }
 
-// checks, then one launch; nothing is enqueued when a check fails
-void enqueue(aptgpu_fm &fm, int count, const void *const *d_iq, const size_t *n_frames, float *const *d_audio,
-             const size_t *audio_cap)
+FmLaunch fm_launch_checks(const aptgpu_fm &fm, int count, const void *const *d_iq, const size_t *n_frames,
+                          float *const *d_audio, const size_t *audio_cap)
 {
     if (count > apt::fm::kMaxBatch) throw Error{ErrorKind::Invalid, "fm: more than APTGPU_FM_MAX_BATCH recordings"};
     const apt::fm::Design &d = fm.design;
     const uintptr_t align = apt::fm::component_bytes(d.format);
-    apt::gpu::FmBatch batch{};
+    FmLaunch t;
     uint64_t max_tiles = 0;
     for (int i = 0; i < count; ++i) {
         const size_t n_out = apt::fm::out_len(d, n_frames[i]);
@@ -65,15 +58,28 @@ void enqueue(aptgpu_fm &fm, int count, const void *const *d_iq, const size_t *n_
         if (reinterpret_cast<uintptr_t>(d_audio[i]) % sizeof(float) != 0)
             throw Error{ErrorKind::Invalid, "fm: d_audio is not aligned to a float"};
         if (audio_cap[i] < n_out) throw Error{ErrorKind::Invalid, "fm: audio_cap is below the output length"};
-        batch.r[i] = apt::gpu::FmRecording{static_cast<const uint8_t *>(d_iq[i]), d_audio[i], n_frames[i]};
+        t.batch.r[i] = apt::gpu::FmRecording{static_cast<const uint8_t *>(d_iq[i]), d_audio[i], n_frames[i]};
         const uint64_t tiles = (n_out + fm.tile.nv - 2) / (fm.tile.nv - 1);
         max_tiles = tiles > max_tiles ? tiles : max_tiles;
     }
     if (max_tiles > 0x7FFFFFFFull) throw Error{ErrorKind::Invalid, "fm: n_frames is too long for one launch"};
+    t.max_tiles = static_cast<uint32_t>(max_tiles);
+    return t;
+}
+}  // namespace apt::capi
+
+namespace {
+
+// checks, then one launch; nothing is enqueued when a check fails
+void enqueue(aptgpu_fm &fm, int count, const void *const *d_iq, const size_t *n_frames, float *const *d_audio,
+             const size_t *audio_cap)
+{
+    const FmLaunch t = fm_launch_checks(fm, count, d_iq, n_frames, d_audio, audio_cap);
+    const apt::fm::Design &d = fm.design;
     apt::hip_check(hipSetDevice(fm.device), "hipSetDevice");
     const apt::gpu::FmParams p{fm.d_taps_rev.ptr, fm.d_offsets.ptr, d.T, d.D, fm.tile.R, fm.tile.nv, d.pw, d.swap ? 1u : 0u,
                                d.step.re, d.step.im, d.gain};
-    apt::gpu::fm_demodulate(fm.stream, d.format, d.pw != 0, fm.tile, batch, count, static_cast<uint32_t>(max_tiles), p);
+    apt::gpu::fm_demodulate(fm.stream, d.format, d.pw != 0, fm.tile, t.batch, count, t.max_tiles, p);
     apt::hip_check(hipGetLastError(), "kernel launch (k_fm)");
 }
 
@@ -85,7 +91,7 @@ int demodulate_host_array(const aptgpu_context *ctx, const aptgpu_fm_settings *s
     if (!iq && apt::fm::out_len(checked, n_frames)) throw Error{ErrorKind::Invalid, "fm: iq is null"};
     Scratch sc(ctx);
     aptgpu_fm fm;
-    setup(fm, settings, sc.device, sc.stream);
+    fm_setup(fm, settings, sc.device, sc.stream);
     const size_t out = apt::fm::out_len(fm.design, n_frames);
     const size_t bytes = n_frames * 2u * apt::fm::component_bytes(fm.design.format);
     apt::DeviceBuffer<uint8_t> d_iq;
@@ -147,7 +153,7 @@ int aptgpu_fm_create(const aptgpu_context *ctx, const aptgpu_fm_settings *settin
     *out = nullptr;
     return guarded(err, err_cap, [&] {
         auto fm = std::make_unique<aptgpu_fm>();
-        setup(*fm, settings, ctx ? ctx->device : 0, ctx ? static_cast<hipStream_t>(ctx->stream) : nullptr);
+        fm_setup(*fm, settings, ctx ? ctx->device : 0, ctx ? static_cast<hipStream_t>(ctx->stream) : nullptr);
         *out = fm.release();
         return APTGPU_OK;
     });

@@ -14,9 +14,30 @@ namespace {
 
 bool positive(float v) { return std::isfinite(v) && v > 0.f; }
 
+// where the phasors come from: the design's one increment (§4b) ...
+struct UniformPhase {
+    const Design &d;
+    bool mix() const { return d.pw != 0; }
+    Cx first(uint64_t i0) const { return phasor_of_phase(static_cast<uint32_t>(i0) * d.pw); }
+    Cx step(uint64_t) const { return d.step; }
+};
+// ... or a table of one record per block of 2^log2_block frames (§4b', apt_afc.cpp): always mixed
+struct TablePhase {
+    const aptgpu_afc_record *table;
+    uint32_t log2_block;
+    bool mix() const { return true; }
+    const aptgpu_afc_record &of(uint64_t i0) const { return table[i0 >> log2_block]; }
+    Cx first(uint64_t i0) const
+    {
+        const aptgpu_afc_record &r = of(i0);
+        return phasor_of_phase(r.phase0 + static_cast<uint32_t>(i0 & ((1ull << log2_block) - 1u)) * r.pw);
+    }
+    Cx step(uint64_t i0) const { return Cx{of(i0).step_re, of(i0).step_im}; }
+};
+
 // frame 0 of iq is absolute frame `base`: the phase and the runs of 8 are the absolute axis's
-template <int FMT>
-void run(const Design &d, uint64_t base, const uint8_t *iq, size_t n_frames, float *audio)
+template <int FMT, class Phase>
+void run(const Design &d, uint64_t base, const uint8_t *iq, size_t n_frames, float *audio, const Phase &phase)
 {
     const size_t n_out = out_len(d, n_frames);
     if (!n_out) return;
@@ -26,8 +47,10 @@ void run(const Design &d, uint64_t base, const uint8_t *iq, size_t n_frames, flo
     const int a = d.swap ? 1 : 0;
     const size_t cb = component_bytes(FMT);
     const uint64_t end = base + used;
+    const bool mix = phase.mix();
     for (uint64_t i0 = base - base % kRun; i0 < end; i0 += kRun) {
-        Cx ph = d.pw ? phasor_of_phase(static_cast<uint32_t>(i0) * d.pw) : Cx{1.f, 0.f};
+        Cx ph = mix ? phase.first(i0) : Cx{1.f, 0.f};
+        const Cx step = mix ? phase.step(i0) : Cx{1.f, 0.f};
         for (uint64_t j = i0; j < i0 + kRun && j < end; ++j) {
             if (j >= base) {
                 const size_t i = static_cast<size_t>(j - base);
@@ -37,9 +60,9 @@ void run(const Design &d, uint64_t base, const uint8_t *iq, size_t n_frames, flo
                     std::memcpy(&raw[k], iq + (2 * i + static_cast<size_t>(k)) * cb, cb);  // little endian
                 }
                 const Cx x{component<FMT>(raw[a]), component<FMT>(raw[1 - a])};
-                u[i] = d.pw ? cmul(x, ph) : x;
+                u[i] = mix ? cmul(x, ph) : x;
             }
-            if (d.pw) ph = cmul(ph, d.step);
+            if (mix) ph = cmul(ph, step);
         }
     }
     Cx prev{};
@@ -95,6 +118,7 @@ Design design_of(const aptgpu_fm_settings *s)
     d.shift_used = static_cast<double>(static_cast<int32_t>(d.pw)) * fs / 4294967296.;
     const double t1 = static_cast<double>(static_cast<int32_t>(d.pw)) * (3.14159265358979323846 / 2147483648.);
     d.step = Cx{static_cast<float>(std::cos(t1)), static_cast<float>(-std::sin(t1))};
+    d.deviation_hz = s->deviation_hz;
     d.gain = static_cast<float>(static_cast<double>(d.fs_out) /
                                 (2. * 3.14159265358979323846 * static_cast<double>(s->deviation_hz)));
     return d;
@@ -103,11 +127,25 @@ Design design_of(const aptgpu_fm_settings *s)
 void run_host_based(const Design &d, uint64_t base, const void *iq, size_t n_frames, float *audio)
 {
     const uint8_t *p = static_cast<const uint8_t *>(iq);
+    const UniformPhase ph{d};
     switch (d.format) {
-    case APTGPU_IQ_U8: return run<APTGPU_IQ_U8>(d, base, p, n_frames, audio);
-    case APTGPU_IQ_S8: return run<APTGPU_IQ_S8>(d, base, p, n_frames, audio);
-    case APTGPU_IQ_S16: return run<APTGPU_IQ_S16>(d, base, p, n_frames, audio);
-    default: return run<APTGPU_IQ_F32>(d, base, p, n_frames, audio);
+    case APTGPU_IQ_U8: return run<APTGPU_IQ_U8>(d, base, p, n_frames, audio, ph);
+    case APTGPU_IQ_S8: return run<APTGPU_IQ_S8>(d, base, p, n_frames, audio, ph);
+    case APTGPU_IQ_S16: return run<APTGPU_IQ_S16>(d, base, p, n_frames, audio, ph);
+    default: return run<APTGPU_IQ_F32>(d, base, p, n_frames, audio, ph);
+    }
+}
+
+void run_host_tracked(const Design &d, const void *iq, size_t n_frames, const aptgpu_afc_record *table,
+                      uint32_t log2_block, float *audio)
+{
+    const uint8_t *p = static_cast<const uint8_t *>(iq);
+    const TablePhase ph{table, log2_block};
+    switch (d.format) {
+    case APTGPU_IQ_U8: return run<APTGPU_IQ_U8>(d, 0, p, n_frames, audio, ph);
+    case APTGPU_IQ_S8: return run<APTGPU_IQ_S8>(d, 0, p, n_frames, audio, ph);
+    case APTGPU_IQ_S16: return run<APTGPU_IQ_S16>(d, 0, p, n_frames, audio, ph);
+    default: return run<APTGPU_IQ_F32>(d, 0, p, n_frames, audio, ph);
     }
 }
 

@@ -123,6 +123,7 @@ struct Design {
     double shift_used = 0.;
     Cx step{1.f, 0.f};  // e^{-j theta_1}
     float gain = 0.f;   // fs_out / (2 pi deviation_hz)
+    float deviation_hz = 0.f;
     Signal taps;        // h
     Signal taps_rev;    // hr[j] = h[T - 1 - j]
 };
@@ -137,6 +138,10 @@ inline size_t out_len(const Design &d, size_t n_frames)
 }
 // The twin: plain C++.  iq: n_frames * 2 components; audio: out_len floats.
 void run_host(const Design &d, const void *iq, size_t n_frames, float *audio);
+// ... with the phase of every run of 8 from a table of one record per block of 2^log2_block frames (§4b', stage C);
+// table: ceil(n_frames / 2^log2_block) records.  The mix is always made.
+void run_host_tracked(const Design &d, const void *iq, size_t n_frames, const aptgpu_afc_record *table,
+                      uint32_t log2_block, float *audio);
 
 // The tile of one workgroup: nv consecutive v[m] (nv - 1 outputs), frames [m0 D, m0 D + (nv - 1) D + T) in LDS as
 // D rows (the frame's phase, local index mod D) of R complex columns (local index / D); every 8 rows the image is

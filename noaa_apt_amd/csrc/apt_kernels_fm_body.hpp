@@ -3,6 +3,9 @@
 // built with -ffp-contract=fast; convert, cmul, the phasor, the tap loop and discriminate exist once, here, so that
 // both kernels contract and order them alike.
 //
+// The phasors of a run come from a phase policy: UniformPhase is §4b (k_fm, k_fm_stream), TablePhase the tracked
+// demodulator of §4b' (apt_kernels_fm_tracked.hip).
+//
 // A source states where its frame 0 stands on the absolute frame axis (base(): the phase of frame i is
 // (uint32) i * pw and the runs of 8 start at multiples of 8 of that axis), how many frames it has, and how the run of
 // 8 frames at an absolute multiple of 8 is fetched: 16 raw component words, zero for frames outside the source.
@@ -122,10 +125,33 @@ struct TwoSegment {
     }
 };
 
+// Where the phasors of the run of 8 at absolute frame i0 come from: the first one and the step to each next.
+struct RunPhasors {
+    Cx first, step;
+};
+// §4b: one increment for the whole recording, the phase of frame i is (uint32) i * pw
+struct UniformPhase {
+    __device__ __forceinline__ RunPhasors run(uint64_t i0, const FmParams &P) const
+    {
+        return RunPhasors{apt::fm::phasor_of_phase(static_cast<uint32_t>(i0) * P.pw), Cx{P.step_re, P.step_im}};
+    }
+};
+// §4b' stage C: one record {pw, phase0, step} per block of 2^log2_block frames (a run of 8 lies inside one block)
+struct TablePhase {
+    const aptgpu_afc_record *table;
+    uint32_t log2_block;
+    __device__ __forceinline__ RunPhasors run(uint64_t i0, const FmParams &) const
+    {
+        const uint4 r = *reinterpret_cast<const uint4 *>(table + (i0 >> log2_block));  // one 16-byte load
+        const uint32_t in_block = static_cast<uint32_t>(i0) & ((1u << log2_block) - 1u);
+        return RunPhasors{apt::fm::phasor_of_phase(r.y + in_block * r.x), Cx{__uint_as_float(r.z), __uint_as_float(r.w)}};
+    }
+};
+
 // The tile of workgroup `block`: nv consecutive v[m] of the source from m0 = block (P.nv - 1) on, audio[m0 ...] out.
-template <int FMT, bool MIX, int VPT, class Source>
+template <int FMT, bool MIX, int VPT, class Source, class Phase = UniformPhase>
 __device__ __forceinline__ void fm_tile(const Source &src, float *__restrict__ audio, const FmParams &P, float2 *tile,
-                                        uint32_t block)
+                                        uint32_t block, const Phase &phase = Phase{})
 {
     const uint32_t T = P.T, D = P.D, R = P.R;
     const uint64_t n_frames = src.frames();
@@ -147,8 +173,12 @@ __device__ __forceinline__ void fm_tile(const Source &src, float *__restrict__ a
             const uint64_t i0 = (g0 + g) * kRun;
             uint32_t raw[2 * kRun];
             src.template load_run<FMT>(i0, raw);
-            Cx ph{1.f, 0.f};
-            if constexpr (MIX) ph = apt::fm::phasor_of_phase(static_cast<uint32_t>(i0) * P.pw);
+            Cx ph{1.f, 0.f}, step{1.f, 0.f};
+            if constexpr (MIX) {
+                const RunPhasors rp = phase.run(i0, P);
+                ph = rp.first;
+                step = rp.step;
+            }
             // local index of the run's first frame (negative: frames in front of the tile, dropped)
             const int64_t l0 = static_cast<int64_t>(i0) - static_cast<int64_t>(s);
             uint32_t row = 0, col = 0;
@@ -162,7 +192,7 @@ __device__ __forceinline__ void fm_tile(const Source &src, float *__restrict__ a
                 Cx x{swap ? cq : ci, swap ? ci : cq};
                 if constexpr (MIX) {
                     x = apt::fm::cmul(x, ph);
-                    ph = apt::fm::cmul(ph, Cx{P.step_re, P.step_im});
+                    ph = apt::fm::cmul(ph, step);
                 }
                 const int64_t l = l0 + k;
                 if (l >= 0 && l < static_cast<int64_t>(frames)) {
