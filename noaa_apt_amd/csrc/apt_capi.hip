@@ -61,8 +61,6 @@ void aptgpu_plan_destroy(aptgpu_plan *plan)
     if (plan->ev_user) (void)hipEventDestroy(plan->ev_user);
     for (hipStream_t st : plan->streams) (void)hipStreamDestroy(st);
     for (hipEvent_t ev : plan->ev_front) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : plan->ev_pre) (void)hipEventDestroy(ev);
-    if (plan->front_stream) (void)hipStreamDestroy(plan->front_stream);
     delete plan;
 }
 
@@ -487,7 +485,7 @@ int aptgpu_find_sync(const aptgpu_context *ctx, const float *signal, size_t n,
             apt::gpu::group_max(sc.stream, d_c.ptr, n_corr, d_gm.ptr);
             const apt::gpu::LaunchSwitches sw = apt::gpu::read_launch_switches();  // (once per API call)
             apt::gpu::sync_nodes(sc.stream, call, d_sp.ptr, n, pw, spr, md, false, true, sw);
-            apt::gpu::sync_orbit(sc.stream, call, d_sp.ptr, spr, md, pw, apt::gpu::read_plan_switches().force_walk == '1' ? 1 : 0, sw);  // (no plan here: the same reader)
+            apt::gpu::sync_orbit(sc.stream, call, d_sp.ptr, spr, md, pw, apt::gpu::read_plan_switches().force_walk == '1', sw);  // (no plan here: the same reader)
             apt::hip_check(hipGetLastError(), "kernel launch (find_sync)");
             apt::hip_check(hipStreamSynchronize(sc.stream), "hipStreamSynchronize");
         }

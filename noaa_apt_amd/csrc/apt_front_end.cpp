@@ -90,12 +90,7 @@ PlanSwitches read_plan_switches()
     };
     PlanSwitches sw;
     sw.force_walk = flag("APTGPU_FORCE_WALK");
-    sw.picker_lds = flag("APTGPU_PICKER_LDS");
     if (const char *e = std::getenv("APTGPU_STREAMS")) sw.streams = std::max(1, std::min(std::atoi(e), 16));
-    sw.front_stream = flag("APTGPU_FRONT_STREAM");
-    if (const char *e = std::getenv("APTGPU_CHAIN_CUS")) sw.chain_cus = std::max(0, std::atoi(e));
-    sw.front_excl = flag("APTGPU_FRONT_EXCL");
-    sw.front_serial = flag("APTGPU_FRONT_SERIAL");
     sw.fused_any = flag("APTGPU_FUSED_ANY");
     sw.phase_first = flag("APTGPU_PHASE_FIRST");
     sw.fast_mfma = flag("APTGPU_FAST_MFMA");
@@ -107,7 +102,6 @@ PlanSwitches read_plan_switches()
     sw.phase_wide = flag("APTGPU_PHASE_WIDE");
     if (const char *e = std::getenv("APTGPU_TABLE_LDS_KB")) sw.table_lds_kb = std::atol(e);
     sw.phase_identity = flag("APTGPU_PHASE_IDENTITY");
-    sw.phase_list_debug = flag("APTGPU_PHASE_LIST_DEBUG");
     return sw;
 }
 
@@ -421,9 +415,6 @@ void fused_phase_table(const TableGeom &g, uint32_t t2, uint32_t pw, const float
         for (uint32_t h = 0; h < NH; ++h)
             for (uint32_t e = 0; e < half[h].size(); ++e) list[32 * h + e] = half[h][e];
         const bool use_ident = sw.phase_identity == '1' || cost(ident_list) <= cost(list);
-        if (sw.phase_list_debug == '1')
-            std::fprintf(stderr, "aptgpu: phase lists l=%u m=%u nq=%u threads=%u rb=%lld: extra passes per tap %u (slot = thread: %u)%s\n", l, g.m,
-                         nq, g.nthr, static_cast<long long>(rb), cost(list), cost(ident_list), use_ident ? " -> slot = thread" : "");
         const std::vector<uint32_t> &chosen = use_ident ? ident_list : list;
         std::memcpy(table + g.perm_off + static_cast<size_t>(r) * g.nthr, chosen.data(), g.nthr * sizeof(uint32_t));
         // window start and branch of every slot of every thread (the kernel reads them when g.exact)

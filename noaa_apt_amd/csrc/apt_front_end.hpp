@@ -42,12 +42,7 @@ namespace apt::gpu {
 // must not change kernels in mid-life.  A 0 / 1 switch holds the first character of its value, -1 when it is not set.
 struct PlanSwitches {
     int force_walk = -1;        // APTGPU_FORCE_WALK=1: the picker's sequential fallback
-    int picker_lds = -1;        // APTGPU_PICKER_LDS=1: the picker's LDS form (picker_force 4)
     int streams = 0;            // APTGPU_STREAMS: calls in flight, clamped to 1 .. 16 (0: not set)
-    int front_stream = -1;      // APTGPU_FRONT_STREAM=1: all front ends on one extra stream (apt_plan.hpp)
-    int chain_cus = 0;          // APTGPU_CHAIN_CUS=n: with it, the per-call streams run on n CUs
-    int front_excl = -1;        // APTGPU_FRONT_EXCL=1: ... and the front-end stream on the others
-    int front_serial = -1;      // APTGPU_FRONT_SERIAL=0 / 1: front ends of consecutive calls one after the other
     int fused_any = -1;         // APTGPU_FUSED_ANY=1 (tests): the run-time kernel even where a specialised one exists
     int phase_first = -1;       // APTGPU_PHASE_FIRST=0 (tests): the table-driven stage 1 wherever it exists
     int fast_mfma = -1;         // APTGPU_FAST_MFMA=0 / 1: the matrix-core kernels never / wherever instantiated
@@ -59,7 +54,6 @@ struct PlanSwitches {
     int phase_wide = -1;        // APTGPU_PHASE_WIDE=1: the 512- / 1024-thread PHASE forms first
     long table_lds_kb = 0;      // APTGPU_TABLE_LDS_KB=16 .. 160: LDS the TABLE form may take (else 80 KB)
     int phase_identity = -1;    // APTGPU_PHASE_IDENTITY=1: PHASE slot = thread, as until round 4
-    int phase_list_debug = -1;  // APTGPU_PHASE_LIST_DEBUG=1: the thread lists' cost on stderr
 };
 PlanSwitches read_plan_switches();
 

@@ -55,14 +55,10 @@ struct GroupMax {
 // is created (read_launch_switches), and carried by the plan to every launch — not per launch: getenv is not safe
 // against a concurrent setenv of another thread, and a plan must not change kernels in mid-life.
 struct LaunchSwitches {
-    int gather_iters = 1;        // APTGPU_GATHER_ITERS: quads per thread of k_gather_rows_flat (0: the eight-rows form)
-    bool words_dpp = true;       // APTGPU_WORDS_DPP=0: k_sync_words without the DPP scans
     int words_form = 1;          // APTGPU_WORDS_FORM=0: k_sync_words / k_sync_slots in their earlier form (A/B)
     bool orbit_lds = true;       // APTGPU_ORBIT_LDS=0: the orbit kernel's tables in global memory
-    int orbit_threads = 0;       // APTGPU_ORBIT_THREADS=256: the 256-thread orbit kernel
     int orbit_alg = 1;           // APTGPU_ORBIT_ALG=0: the breadth-first closure form
     float gm_slack_scale = 1.f;  // APTGPU_GM_SLACK_SCALE (tests): widens the strict front ends' bounds
-    int fused_lds_pad = 0;       // APTGPU_FUSED_LDS_PAD: extra dynamic LDS bytes per front-end workgroup
 };
 LaunchSwitches read_launch_switches();
 
@@ -141,7 +137,7 @@ void gather_rows(hipStream_t s, const float *f, const uint32_t *peaks, Result *r
                  uint32_t spr, uint32_t pw, bool raw, float *rows, uint32_t rows_cap);
 // the same for the recordings of one call: rows / rows_cap from the call, F / peaks / res from the slots
 void gather_rows_call(hipStream_t s, const CallArgs &call, const SlotPtrs *d_slots, uint32_t spr, uint32_t pw,
-                      uint32_t max_rows_cap, const LaunchSwitches &sw = LaunchSwitches{});
+                      uint32_t max_rows_cap);
 
 // the no-sync branch's tail (decode.rs:135-159, final decimation by m2 through NoFilter) and the result records of the
 // recordings of one call in one launch; `rows_cap` of the call's records counts floats
@@ -187,7 +183,7 @@ struct FusedParams {
 // variant_out: receives the row of apt_kernels_fused_variants.hpp whose kernel the call launched (a FusedVariant; -1 where
 // none was) — introspection, aptgpu_plan_read_internal("fused_variant").
 bool fused_front_end(hipStream_t s, const FrontEnd &fe, bool pcm16, const CallArgs &call, const FusedParams *d_prm,
-                     uint64_t max_w, int lds_pad = 0, int *variant_out = nullptr);
+                     uint64_t max_w, int *variant_out = nullptr);
 // kModeMfma: the matrix-core instantiations' table — [3 pieces][K / 32][64 lanes][4 dwords] bf16 fragments of the banded
 // Toeplitz matrix of the resampler (h = h0 + h1 + h2 exactly)
 uint32_t fused_mfma_table_dwords(uint32_t l, uint32_t m);
@@ -220,7 +216,8 @@ void sync_nodes(hipStream_t s, const CallArgs &call, const SlotPtrs *d_slots, ui
 // list + result record of every recording
 size_t sync_orbit_ws_words(uint64_t w, uint32_t spr);  // uint32 words of scratch it needs
 void sync_orbit(hipStream_t s, const CallArgs &call, const SlotPtrs *d_slots, uint32_t spr, uint32_t md,
-                uint32_t pw, int force /* 0 parallel picker, 1 sequential walk */, const LaunchSwitches &sw = LaunchSwitches{});
+                uint32_t pw, bool force_walk /* the sequential walk instead of the parallel picker */,
+                const LaunchSwitches &sw = LaunchSwitches{});
 
 // ---- consumers of the pixel rows (apt_kernels_image.hip) ------
 // All take the pixel count from `res` (device) when it is non-null, else `n`; `cap` bounds it

@@ -230,7 +230,7 @@ void fused_mfma_table(uint32_t l, uint32_t m, const float *coeff, uint32_t t1, u
 }
 
 bool fused_front_end(hipStream_t s, const FrontEnd &fe, bool pcm16, const CallArgs &call, const FusedParams *d_prm,
-                     uint64_t max_w, int lds_pad, int *variant_out)
+                     uint64_t max_w, int *variant_out)
 {
     if (variant_out) *variant_out = static_cast<int>(kFusedNone);
     if (call.count == 0 || call.count > static_cast<uint32_t>(kMaxCall)) return false;
@@ -239,7 +239,7 @@ bool fused_front_end(hipStream_t s, const FrontEnd &fe, bool pcm16, const CallAr
         for (uint32_t i = 0; i < call.count; ++i)
             if (reinterpret_cast<uintptr_t>(call.rec[i].x) & (split ? 3u : 1u)) return false;
     const FusedVariant v = fe.variant[pcm16 ? 1 : 0];
-    const FusedLaunch a{s, &call, d_prm, max_w, fe.lds_floats, split ? lds_pad : 0};
+    const FusedLaunch a{s, &call, d_prm, max_w, fe.lds_floats};
 #ifdef APT_WITH_PROBES
     // APTGPU_PROBE_STOP: the timing probes stand in for the stock 48 kHz f32 kernels (fast: 1..5, 8, 9; strict: 11..17)
     static const int probe = [] {

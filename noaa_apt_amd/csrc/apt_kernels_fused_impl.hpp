@@ -2192,9 +2192,6 @@ void launch_fused_args(const FusedLaunch &a)
     using Gm = FusedGeom<L, M, T1, T2, PW, NTHR, static_cast<int>(sizeof(XT)), fused_geom_var(MODE)>;
     size_t lds = static_cast<size_t>(Gm::LDS_FLOATS) * sizeof(float);
     if constexpr (Gm::TABLE) lds = (std::max<size_t>(a.table_lds_floats, Gm::W_LDS_FLOATS) + (Gm::PAD ? 4 : 0)) * sizeof(float);
-    // APTGPU_FUSED_LDS_PAD=bytes (A/B switch, read at plan creation): more dynamic LDS than the kernel uses = fewer workgroups
-    // per CU (2048 takes the 48 kHz kernels from six back to five)
-    lds += static_cast<size_t>(a.lds_pad > 0 ? a.lds_pad : 0);
     constexpr auto kern = k_fused<L, M, T1, T2, PW, NTHR, XT, MODE>;
     ensure_dynamic_lds<kern>(lds);
     const unsigned tiles = static_cast<unsigned>((a.max_w + Gm::OWN_K - 1) / Gm::OWN_K);

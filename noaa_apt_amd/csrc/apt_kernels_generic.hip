@@ -429,7 +429,7 @@ k_gather_rows_call(const CallArgs call, const SlotPtrs *__restrict__ slots, uint
 
 // The same rows with the (row, pixel quad) pairs of a recording as ONE flat index walked by a fixed number of
 // workgroups (grid.x) per recording: no workgroup of a row's third, nearly empty block of quads (2080 px = 520 quads =
-// 2.03 blocks of 256 threads), and `iters` quads per thread instead of one wave launch per 256 pixels — the kernel
+// 2.03 blocks of 256 threads), and a grid-stride loop over the quads instead of one wave launch per 256 pixels — the kernel
 // runs beside the next call's front end, whose workgroups are dispatched through the same pipe.  QPR: quads per row
 // at compile time (520 whenever the work rate is a multiple of 4160 Hz: the division by it is a multiply).
 template <uint32_t QPR>
@@ -602,39 +602,31 @@ void orbit_walk(hipStream_t s, const uint64_t *bits, const float *corr, uint64_t
 LaunchSwitches read_launch_switches()
 {
     LaunchSwitches sw;
-    if (const char *e = std::getenv("APTGPU_GATHER_ITERS")) sw.gather_iters = std::atoi(e);
-    if (const char *e = std::getenv("APTGPU_WORDS_DPP")) sw.words_dpp = e[0] != '0';
     if (const char *e = std::getenv("APTGPU_WORDS_FORM")) sw.words_form = e[0] == '0' ? 0 : 1;
     if (const char *e = std::getenv("APTGPU_ORBIT_LDS")) sw.orbit_lds = e[0] != '0';
-    if (const char *e = std::getenv("APTGPU_ORBIT_THREADS")) sw.orbit_threads = std::atoi(e);
     if (const char *e = std::getenv("APTGPU_ORBIT_ALG")) sw.orbit_alg = e[0] == '0' ? 0 : 1;
     if (const char *e = std::getenv("APTGPU_GM_SLACK_SCALE")) {
         const float v = std::strtof(e, nullptr);
         if (v >= 1.f) sw.gm_slack_scale = v;
     }
-    if (const char *e = std::getenv("APTGPU_FUSED_LDS_PAD")) sw.fused_lds_pad = std::max(0, std::atoi(e));
     return sw;
 }
 
 void gather_rows_call(hipStream_t s, const CallArgs &call, const SlotPtrs *d_slots, uint32_t spr, uint32_t pw,
-                      uint32_t max_rows_cap, const LaunchSwitches &sw)
+                      uint32_t max_rows_cap)
 {
     if (call.count == 0) return;
     // The flat form wherever a row is 520 quads (every work rate that is a multiple of 4160 Hz) and the rows buffers are
     // 16-byte aligned: ONE quad per thread measured best beside the front end (pipelined step, 16 recordings per call:
     // 0.843 ms against 0.853 / 0.847 / 0.855 with 2 / 4 / 8 quads per thread and 0.869 with the form below;
-    // profiles/r04_sweeps.txt).  APTGPU_GATHER_ITERS=n (A/B switch, read at plan creation): n quads per thread, 0 = the form below.
-    {
-        const int iters = sw.gather_iters;
-        bool aligned = true;
-        for (uint32_t i = 0; i < call.count; ++i) aligned = aligned && (reinterpret_cast<uintptr_t>(call.rec[i].rows) & 15u) == 0;
-        if (iters > 0 && spr / pw == 2080u && spr % pw == 0 && aligned && max_rows_cap > 0) {
-            const uint64_t quads = static_cast<uint64_t>(max_rows_cap < 32768u ? max_rows_cap : 32768u) * 520u;
-            const uint64_t per_wg = static_cast<uint64_t>(kBlock) * static_cast<uint64_t>(iters);
-            const unsigned gx = static_cast<unsigned>((quads + per_wg - 1) / per_wg);
-            hipLaunchKernelGGL(k_gather_rows_flat<520u>, dim3(gx ? gx : 1, call.count), dim3(kBlock), 0, s, call, d_slots, spr, pw);
-            return;
-        }
+    // profiles/r04_sweeps.txt).
+    bool aligned = true;
+    for (uint32_t i = 0; i < call.count; ++i) aligned = aligned && (reinterpret_cast<uintptr_t>(call.rec[i].rows) & 15u) == 0;
+    if (spr / pw == 2080u && spr % pw == 0 && aligned && max_rows_cap > 0) {
+        const uint64_t quads = static_cast<uint64_t>(max_rows_cap < 32768u ? max_rows_cap : 32768u) * 520u;
+        const unsigned gx = static_cast<unsigned>((quads + kBlock - 1) / kBlock);
+        hipLaunchKernelGGL(k_gather_rows_flat<520u>, dim3(gx ? gx : 1, call.count), dim3(kBlock), 0, s, call, d_slots, spr, pw);
+        return;
     }
     // eight rows per workgroup (one row each made 57 600 workgroups of three loop iterations per thread for a call of
     // 16 recordings: the kernel ran at the rate workgroups can be dispatched, 118 us whatever it read)

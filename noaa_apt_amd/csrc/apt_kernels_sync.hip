@@ -226,8 +226,7 @@ __device__ __forceinline__ float nodes_eval_window(float *win, bool on, int lane
 // the md/GS + 1 groups BEHIND its own: it evaluated the candidates of that look-behind halo a second
 // time, 76 % more work.  The lists are now a second, trivially cheap launch, k_sync_slots, that reads
 // the words back — a kernel boundary instead of an inter-workgroup hand-over inside one launch.)
-// DPP: the two scans of a candidate's terminal test with DPP row operations (the default; APTGPU_WORDS_DPP=0 keeps
-// the ds_bpermute form for A/B).
+// The two scans of a candidate's terminal test are DPP row operations (wave_suffix_max_excl_dpp, wave_prefix_max_dpp).
 // LEAN (the default where PWC > 0 and R = 32 pw; APTGPU_WORDS_FORM=0 keeps the earlier form for A/B): the same predicate
 // and the same words with fewer instructions around the chains —
 //   coarse    prefix and suffix maxima of lo inside blocks of 64 entries, two DPP scans per block and ONE barrier (the
@@ -238,7 +237,7 @@ __device__ __forceinline__ float nodes_eval_window(float *win, bool on, int lane
 //             but a recording's last two — loads its windows unpredicated with 32-bit offsets on a scalar base and drops
 //             the per-lane 64-bit position compares;
 //   settle    the three wave-wide reductions of the open-bounds branch with the DPP scan instead of shuffles.
-template <int NL, int PWC, bool DPP, bool LEAN>
+template <int NL, int PWC, bool LEAN>
 __global__ void __launch_bounds__(kNodesThreads, 4)  // <= 128 VGPRs: must fit beside the front end's waves
 k_sync_words(const CallArgs call, const SlotPtrs *__restrict__ slots, uint32_t pw_arg, uint32_t r_groups /* md/GS */,
              int fast, int use_corr)
@@ -288,7 +287,7 @@ k_sync_words(const CallArgs call, const SlotPtrs *__restrict__ slots, uint32_t p
         sp.res->reason = -1;
     }
     APT_WMARK("BEGIN coarse");
-    static_assert(!LEAN || (DPP && NL > 0 && PWC > 0), "the lean form builds on the DPP scans and the register-held windows");
+    static_assert(!LEAN || (NL > 0 && PWC > 0), "the lean form builds on the register-held windows");
     static_assert(PWC == 0 || NL == 0 || 64u * NL >= nodes_window(PWC) + PWC - 1,
                   "an interior window loaded from up to PWC - 1 samples early (F in planes) still covers the window");
     if constexpr (LEAN) {
@@ -440,18 +439,7 @@ k_sync_words(const CallArgs call, const SlotPtrs *__restrict__ slots, uint32_t p
         const unsigned long long nanword = __ballot(in_v && cv != cv) & kGroupMask;
         if (cv != cv) cv = kNegInf;
         // suffix max over lanes > lane (rest of this group)
-        float sfx_ex;
-        if constexpr (DPP) {
-            sfx_ex = wave_suffix_max_excl_dpp(cv, lane);
-        } else {
-            float sfx = cv;
-            for (int d = 1; d < 64; d <<= 1) {
-                const float o = __shfl_down(sfx, d, 64);
-                if (lane + d < 64) sfx = fmaxf(sfx, o);
-            }
-            sfx_ex = __shfl_down(sfx, 1, 64);
-            if (lane == 63) sfx_ex = kNegInf;
-        }
+        const float sfx_ex = wave_suffix_max_excl_dpp(cv, lane);
         float wm = s_wm[q];
         const bool open_lo = in_v && !(sfx_ex > cv) && !(wm > cv);
         if (__ballot(open_lo) != 0ull) {
@@ -516,16 +504,7 @@ k_sync_words(const CallArgs call, const SlotPtrs *__restrict__ slots, uint32_t p
         if (corr == nullptr && __ballot(in2 && !(wmax > cv) && gm_ahead > cv) != 0ull) c2v = eval_group(int_tag, base + md, in2);
         if (c2v != c2v) c2v = kNegInf;
         // prefix max over lanes <= lane of the group md positions ahead
-        float pfx = c2v;
-        if constexpr (DPP) {
-            pfx = wave_prefix_max_dpp(pfx);
-        } else {
-            for (int d = 1; d < 64; d <<= 1) {
-                const float o = __shfl_up(pfx, d, 64);
-                if (lane >= d) pfx = fmaxf(pfx, o);
-            }
-        }
-        wmax = fmaxf(wmax, pfx);
+        wmax = fmaxf(wmax, wave_prefix_max_dpp(c2v));
         const bool term = in_v && !(wmax > cv);
         const unsigned long long word = __ballot(term) & kGroupMask;
         if (lane == 0) {
@@ -747,7 +726,7 @@ k_sync_slots(const CallArgs call, const SlotPtrs *__restrict__ slots, uint32_t p
 }
 
 // ------------------------------------------------------------------ k_sync_orbit
-constexpr int kOrbitThreadsMax = 1024;
+constexpr int kOrbitThreads = 1024;  // workgroup size of k_sync_orbit_global
 constexpr int kMaxLevels = 64;    // breadth-first levels before giving up on the parallel path
 
 struct OrbitGeom {
@@ -838,10 +817,8 @@ __device__ __forceinline__ void gst(uint32_t *p, uint32_t v)
 // front end.  Node terminals are looked up straight in the per-chunk slots k_sync_slots wrote
 // (no gather pass): chunk = position / (128*52), then the first entry >= s of that slot or of the
 // next non-empty one.  Node ids: 0 root, 1..n_grid grid cells 2..kc, base_d + slot entry, END.
-// NT threads: 1024 (the latency-bound phases finish soonest when the kernel has a CU's slots to itself) or 256 (a
-// workgroup that still finds room on a CU whose LDS and wave slots five front-end workgroups have taken).
-template <int NT>
-__global__ void __launch_bounds__(NT, NT >= 1024 ? 8 : 2)
+// kOrbitThreads = 1024: the latency-bound phases finish soonest when the kernel has a CU's slots to itself.
+__global__ void __launch_bounds__(kOrbitThreads, 8)
 k_sync_orbit_global(const CallArgs call, const SlotPtrs *__restrict__ slots, uint32_t spr_in, uint32_t md_in,
                     uint32_t pw, int force_walk, uint32_t lds_entries, int alg)
 {
@@ -865,7 +842,7 @@ k_sync_orbit_global(const CallArgs call, const SlotPtrs *__restrict__ slots, uin
     const uint32_t nt_cap = n_chunks * kSlotCap;  // node ids of slot entries: base_d + chunk*kSlotCap + k
     __shared__ uint32_t s_count, s_plen, s_conflict, s_endcell;
     __shared__ unsigned long long s_fit;
-    __shared__ uint32_t s_wtot[kOrbitThreadsMax / 64];
+    __shared__ uint32_t s_wtot[kOrbitThreads / 64];
     extern __shared__ uint16_t lds_orbit[];
     // this latency-bound workgroup shares its CU with VALU-saturated front-end waves of the next
     // recording: let its few instructions issue first
@@ -971,7 +948,7 @@ k_sync_orbit_global(const CallArgs call, const SlotPtrs *__restrict__ slots, uin
         // at 1024 threads) their entry counts AND their first sixteen entries are fetched in ONE round trip — the
         // addresses do not depend on the counts — where the scan and the gather below used to take three in a row
         constexpr uint32_t kPre = 2;
-        const uint32_t cpt = (n_chunks + NT - 1) / NT;
+        const uint32_t cpt = (n_chunks + kOrbitThreads - 1) / kOrbitThreads;
         const uint32_t c0 = static_cast<uint32_t>(tid) * cpt;
         const bool pre = cpt <= kPre;  // (uniform)
         uint32_t cnt_r[kPre] = {};
@@ -1033,7 +1010,7 @@ k_sync_orbit_global(const CallArgs call, const SlotPtrs *__restrict__ slots, uin
                     }
                 }
             }
-            if (tid == NT - 1) s_pref[n_chunks] = run;  // the last thread's run ends at the total
+            if (tid == kOrbitThreads - 1) s_pref[n_chunks] = run;  // the last thread's run ends at the total
             __syncthreads();
             n_ent = s_pref[n_chunks];
             fine(1);  // counts and entries fetched, counts scanned
@@ -1079,7 +1056,7 @@ k_sync_orbit_global(const CallArgs call, const SlotPtrs *__restrict__ slots, uin
                     }
                 }
             } else {
-                for (uint32_t ch = tid; ch < n_chunks; ch += NT) {
+                for (uint32_t ch = tid; ch < n_chunks; ch += kOrbitThreads) {
                     const uint32_t c = slot_cnt[ch];
                     const uint32_t lim = c < kSlotCap ? c : kSlotCap;
                     const uint32_t at = s_pref[ch];
@@ -1131,10 +1108,10 @@ k_sync_orbit_global(const CallArgs call, const SlotPtrs *__restrict__ slots, uin
             // the chunk's first entry 46 k (round 5); sixteen entries at a time, counted without a dependent chain, 29 k — 150
             // VALU instructions per node; runs of consecutive list nodes per thread with a carried lower bound 40 k — one
             // long dependent chain per thread; this form 21 k.)
-            const uint32_t npt = (n_all + NT - 1) / NT;
+            const uint32_t npt = (n_all + kOrbitThreads - 1) / kOrbitThreads;
             const uint32_t i_lo = static_cast<uint32_t>(tid) * npt;
             const uint32_t i_hi = i_lo + npt < n_all ? i_lo + npt : n_all;
-            for (uint32_t i = tid; i < n_all; i += NT) {
+            for (uint32_t i = tid; i < n_all; i += kOrbitThreads) {
                 uint32_t cell, sv;
                 if (i == 0) { cell = 1; sv = 0; }
                 else if (i < base_d) { cell = i + 1; sv = cell * spr; }
@@ -1148,14 +1125,14 @@ k_sync_orbit_global(const CallArgs call, const SlotPtrs *__restrict__ slots, uin
                 la[i] = static_cast<uint16_t>(nx);
             }
             if (tid == 0) { la[n_all] = ENDC; pth[0] = 0; }
-            for (uint32_t i = tid; i <= n_all; i += NT) nid[i] = 0;
+            for (uint32_t i = tid; i <= n_all; i += kOrbitThreads) nid[i] = 0;
             __syncthreads();
             stamp(0);  // successors known
             // ---- round 6: only a node that is SOME node's successor (or the root) can lie on the orbit, and recordings
             // are confluent — most of a row's ten or so candidate starts lead to the same next start — so the doubling
             // below runs over the few nodes with a predecessor, renumbered densely, not over all of them (its cost is
             // LDS gathers: nodes x rounds).
-            for (uint32_t i = tid; i < n_all; i += NT) {
+            for (uint32_t i = tid; i < n_all; i += kOrbitThreads) {
                 const uint16_t t = la[i];
                 if (t != ENDC) nid[t] = 1;  // (the same value from every writer)
             }
@@ -1175,7 +1152,7 @@ k_sync_orbit_global(const CallArgs call, const SlotPtrs *__restrict__ slots, uin
                 if (ln == 63) s_wtot[wave] = incl;
                 __syncthreads();
                 uint32_t before = 0;
-                for (int wq = 0; wq < NT / 64; ++wq) {
+                for (int wq = 0; wq < kOrbitThreads / 64; ++wq) {
                     if (wq < wave) before += s_wtot[wq];
                     n2 += s_wtot[wq];
                 }
@@ -1204,24 +1181,24 @@ k_sync_orbit_global(const CallArgs call, const SlotPtrs *__restrict__ slots, uin
                 __syncthreads();
                 // path[m + q 4^r] = J^q[path[m]], q = 1 .. 3;  J <- J^4: half the rounds (and barriers) of plain doubling
                 for (uint32_t span = 1; span < path_cap_a; span <<= 2) {
-                    for (uint32_t mI = tid; mI < span && mI + span < path_cap_a; mI += NT) {
+                    for (uint32_t mI = tid; mI < span && mI + span < path_cap_a; mI += kOrbitThreads) {
                         const uint16_t t1 = la2[pth[mI]], t2 = la2[t1], t3 = la2[t2];
                         pth[mI + span] = t1;
                         if (mI + 2 * span < path_cap_a) pth[mI + 2 * span] = t2;
                         if (mI + 3 * span < path_cap_a) pth[mI + 3 * span] = t3;
                     }
                     // (four entries per thread and pass, their four-deep chains side by side: the phase is LDS latency)
-                    for (uint32_t i = tid; i < n2; i += 4 * NT) {
+                    for (uint32_t i = tid; i < n2; i += 4 * kOrbitThreads) {
                         uint16_t t[4];
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) t[e] = la2[i + e * NT < n2 ? i + e * NT : n2];
+                        for (int e = 0; e < 4; ++e) t[e] = la2[i + e * kOrbitThreads < n2 ? i + e * kOrbitThreads : n2];
 #pragma unroll
                         for (int d = 0; d < 3; ++d)
 #pragma unroll
                             for (int e = 0; e < 4; ++e) t[e] = la2[t[e]];
 #pragma unroll
                         for (int e = 0; e < 4; ++e)
-                            if (i + e * NT < n2) lb2[i + e * NT] = t[e];
+                            if (i + e * kOrbitThreads < n2) lb2[i + e * kOrbitThreads] = t[e];
                     }
                     __syncthreads();
                     uint16_t *t = la2; la2 = lb2; lb2 = t;
@@ -1230,7 +1207,7 @@ k_sync_orbit_global(const CallArgs call, const SlotPtrs *__restrict__ slots, uin
                 fine(4);  // orbit known
                 // the path's starts, cells and terminals -> LDS (over `la`: dead)
                 uint32_t *p_sv = reinterpret_cast<uint32_t *>(la), *p_cell = p_sv + path_cap_a, *p_u = p_cell + path_cap_a;
-                for (uint32_t k = tid; k < path_cap_a; k += NT) {
+                for (uint32_t k = tid; k < path_cap_a; k += kOrbitThreads) {
                     const uint16_t q = pth[k];
                     uint32_t sv = 0xFFFFFFFFu, cell = 0, u = 0;
                     if (q != END2) {
@@ -1248,7 +1225,7 @@ k_sync_orbit_global(const CallArgs call, const SlotPtrs *__restrict__ slots, uin
                 __syncthreads();
                 stamp(1);  // orbit extracted
                 unsigned long long fit_l = 0;
-                for (uint32_t k = tid; k < path_cap_a; k += NT) {
+                for (uint32_t k = tid; k < path_cap_a; k += kOrbitThreads) {
                     const uint32_t sv = p_sv[k];
                     if (sv == 0xFFFFFFFFu) continue;
                     const uint32_t u = p_u[k];
@@ -1290,12 +1267,12 @@ k_sync_orbit_global(const CallArgs call, const SlotPtrs *__restrict__ slots, uin
                 if (tid == 0) { la2[n2] = END2; lb2[n2] = END2; }  // (pth[0] = 0: the root is the first numbered node)
                 __syncthreads();
                 for (uint32_t span = 1; span < path_cap_a; span <<= 1) {
-                    for (uint32_t mI = tid; mI < span && mI + span < path_cap_a; mI += NT) pth[mI + span] = la2[pth[mI]];
-                    for (uint32_t i = tid; i < n2; i += NT) lb2[i] = la2[la2[i]];
+                    for (uint32_t mI = tid; mI < span && mI + span < path_cap_a; mI += kOrbitThreads) pth[mI + span] = la2[pth[mI]];
+                    for (uint32_t i = tid; i < n2; i += kOrbitThreads) lb2[i] = la2[la2[i]];
                     __syncthreads();
                     uint16_t *t = la2; la2 = lb2; lb2 = t;
                 }
-                for (uint32_t k = tid; k < path_cap_a; k += NT) {
+                for (uint32_t k = tid; k < path_cap_a; k += kOrbitThreads) {
                     const uint16_t q = pth[k];
                     pth[k] = q == END2 ? ENDC : orig[q];
                 }
@@ -1303,8 +1280,8 @@ k_sync_orbit_global(const CallArgs call, const SlotPtrs *__restrict__ slots, uin
             } else {
                 if (tid == 0) lb[n_all] = ENDC;  // (over s_ent: dead from here on)
                 for (uint32_t span = 1; span < path_cap_a; span <<= 1) {
-                    for (uint32_t mI = tid; mI < span && mI + span < path_cap_a; mI += NT) pth[mI + span] = la[pth[mI]];
-                    for (uint32_t i = tid; i < n_all; i += NT) lb[i] = la[la[i]];
+                    for (uint32_t mI = tid; mI < span && mI + span < path_cap_a; mI += kOrbitThreads) pth[mI + span] = la[pth[mI]];
+                    for (uint32_t i = tid; i < n_all; i += kOrbitThreads) lb[i] = la[la[i]];
                     __syncthreads();
                     uint16_t *t = la; la = lb; lb = t;
                 }
@@ -1313,7 +1290,7 @@ k_sync_orbit_global(const CallArgs call, const SlotPtrs *__restrict__ slots, uin
             if (!fastp) fine(4);  // orbit known (LDS ids)
             // the path in the kernel's node ids (base_d + chunk * kSlotCap + k for list entries), and the terminal
             // each of its nodes reaches — what the peak-list code below reads
-            for (uint32_t k = tid; !fastp && k < path_cap_a; k += NT) {
+            for (uint32_t k = tid; !fastp && k < path_cap_a; k += kOrbitThreads) {
                 const uint32_t i = pth[k];
                 uint32_t v = END;
                 if (i != ENDC) {
@@ -1343,11 +1320,11 @@ k_sync_orbit_global(const CallArgs call, const SlotPtrs *__restrict__ slots, uin
     // ---- reachable set by breadth-first marking from the root and every grid node
     uint32_t count = 0;
     if (!walk && !all_done) {
-        for (uint32_t wq = tid; wq < n_nodes / 32 + 1; wq += NT) gst(w_mark + wq, 0u);
-        for (uint32_t c = tid; c < kc + 3; c += NT) gst(w_succ + c, 0xFFFFFFFFu);
+        for (uint32_t wq = tid; wq < n_nodes / 32 + 1; wq += kOrbitThreads) gst(w_mark + wq, 0u);
+        for (uint32_t c = tid; c < kc + 3; c += kOrbitThreads) gst(w_succ + c, 0xFFFFFFFFu);
         if (tid == 0) { s_count = base_d; s_conflict = 0; s_endcell = kc + 2; }
         __syncthreads();
-        for (uint32_t v = tid; v < base_d; v += NT) {
+        for (uint32_t v = tid; v < base_d; v += kOrbitThreads) {
             gst(w_list + v, v);
             atomicOr(w_mark + (v >> 5), 1u << (v & 31));
         }
@@ -1355,7 +1332,7 @@ k_sync_orbit_global(const CallArgs call, const SlotPtrs *__restrict__ slots, uin
         uint32_t lo = 0, hi = base_d;
         int level = 0;
         for (; level < kMaxLevels && lo < hi; ++level) {
-            for (uint32_t idx = lo + tid; idx < hi; idx += NT) {
+            for (uint32_t idx = lo + tid; idx < hi; idx += kOrbitThreads) {
                 const uint32_t v = gld(w_list + idx);
                 uint32_t cell, u = 0, nx = END, nxcell = 0;
                 const uint32_t sv = node_start(v, &cell);
@@ -1425,7 +1402,7 @@ k_sync_orbit_global(const CallArgs call, const SlotPtrs *__restrict__ slots, uin
         // orbit is read off without any pointer chasing: path[0] = root (acts as cell 1),
         // path[k] = succ[k] up to the first cell whose successor is END
         const uint32_t endc = s_endcell;
-        for (uint32_t k = tid + 1; k < path_cap; k += NT)
+        for (uint32_t k = tid + 1; k < path_cap; k += kOrbitThreads)
             gst(w_path + k, k < endc ? gld(w_succ + k) : END);
         __syncthreads();
     }
@@ -1442,19 +1419,19 @@ k_sync_orbit_global(const CallArgs call, const SlotPtrs *__restrict__ slots, uin
         uint16_t *la = pth + path_cap;          // [count + 1]
         uint16_t *lb = la + (count + 1);        // [count + 1]
         const uint16_t ENDC = static_cast<uint16_t>(count);
-        for (uint32_t idx = tid; idx < count; idx += NT) {
+        for (uint32_t idx = tid; idx < count; idx += kOrbitThreads) {
             const uint32_t nx = gld(w_ja + gld(w_list + idx));
             la[idx] = nx == END ? ENDC : static_cast<uint16_t>(nx < base_d ? nx : gld(w_jb + nx));  // seeds: index == id
         }
         if (tid == 0) { la[count] = ENDC; lb[count] = ENDC; pth[0] = 0; }
         __syncthreads();
         for (uint32_t span = 1; span < path_cap; span <<= 1) {
-            for (uint32_t mI = tid; mI < span && mI + span < path_cap; mI += NT) pth[mI + span] = la[pth[mI]];
-            for (uint32_t idx = tid; idx < count; idx += NT) lb[idx] = la[la[idx]];
+            for (uint32_t mI = tid; mI < span && mI + span < path_cap; mI += kOrbitThreads) pth[mI + span] = la[pth[mI]];
+            for (uint32_t idx = tid; idx < count; idx += kOrbitThreads) lb[idx] = la[la[idx]];
             __syncthreads();
             uint16_t *t = la; la = lb; lb = t;
         }
-        for (uint32_t k = tid; k < path_cap; k += NT)
+        for (uint32_t k = tid; k < path_cap; k += kOrbitThreads)
             gst(w_path + k, pth[k] == ENDC ? END : gld(w_list + pth[k]));
         __syncthreads();
     }
@@ -1464,19 +1441,19 @@ k_sync_orbit_global(const CallArgs call, const SlotPtrs *__restrict__ slots, uin
     uint32_t vk[kKeep], jk[kKeep];
 #pragma unroll
     for (int j = 0; j < kKeep; ++j) {
-        const uint32_t idx = tid + j * NT;
+        const uint32_t idx = tid + j * kOrbitThreads;
         vk[j] = (idx < count) ? gld(w_list + idx) : END;
     }
 #pragma unroll
     for (int j = 0; j < kKeep; ++j) jk[j] = gld(ja + vk[j]);
     for (uint32_t span = 1; span < path_cap; span <<= 1) {
-        for (uint32_t mI = tid; mI < span && mI + span < path_cap; mI += NT)
+        for (uint32_t mI = tid; mI < span && mI + span < path_cap; mI += kOrbitThreads)
             gst(w_path + mI + span, gld(ja + gld(w_path + mI)));
 #pragma unroll
         for (int j = 0; j < kKeep; ++j) jk[j] = gld(ja + jk[j]);  // J[J[v]], one round trip
 #pragma unroll
         for (int j = 0; j < kKeep; ++j) gst(jb + vk[j], jk[j]);
-        for (uint32_t idx = tid + kKeep * NT; idx < count; idx += NT) {
+        for (uint32_t idx = tid + kKeep * kOrbitThreads; idx < count; idx += kOrbitThreads) {
             const uint32_t v = gld(w_list + idx);
             gst(jb + v, gld(ja + gld(ja + v)));
         }
@@ -1493,7 +1470,7 @@ k_sync_orbit_global(const CallArgs call, const SlotPtrs *__restrict__ slots, uin
     __syncthreads();
     }
     unsigned long long fit_local = 0;
-    for (uint32_t k = tid; !peaks_done && k < path_cap; k += NT) {
+    for (uint32_t k = tid; !peaks_done && k < path_cap; k += kOrbitThreads) {
         const uint32_t v = gld(w_path + k);
         if (v == END) continue;
         uint32_t cell;
@@ -1574,36 +1551,27 @@ void sync_nodes(hipStream_t s, const CallArgs &call, const SlotPtrs *d_slots, ui
     const size_t lds = words_win_ofs(r) + static_cast<size_t>(kNodesWaves) * nodes_window(pw) * sizeof(float);
     const dim3 grid(chunks, call.count);
     const uint32_t wneed = GS + 38u * pw - 1u;
-    const bool dpp = sw.words_dpp;  // (APTGPU_WORDS_DPP, read at plan creation)
-    // the lean form (APTGPU_WORDS_FORM, read at plan creation): the compile-time pixel widths with the DPP scans and the
-    // reference's look-ahead, md = 0.8 rows = 32 pw groups
-    const bool lean = sw.words_form != 0 && dpp && r == 32u * pw;
-#define APT_WORDS_LAUNCH_(NL, PWC, DPP, LEAN)                                                                           \
-    hipLaunchKernelGGL((k_sync_words<NL, PWC, DPP, LEAN>), grid, dim3(kNodesThreads), lds, s, call, d_slots, pw, r,     \
+    // the lean form (APTGPU_WORDS_FORM, read at plan creation): the compile-time pixel widths with the reference's
+    // look-ahead, md = 0.8 rows = 32 pw groups
+    const bool lean = sw.words_form != 0 && r == 32u * pw;
+#define APT_WORDS_LAUNCH(NL, PWC, LEAN)                                                                                 \
+    hipLaunchKernelGGL((k_sync_words<NL, PWC, LEAN>), grid, dim3(kNodesThreads), lds, s, call, d_slots, pw, r,          \
                        fast ? 1 : 0, use_corr ? 1 : 0)
-#define APT_WORDS_LAUNCH(NL, PWC)                                                                                       \
-    do {                                                                                                                \
-        if (dpp)                                                                                                        \
-            APT_WORDS_LAUNCH_(NL, PWC, true, false);                                                                    \
-        else                                                                                                            \
-            APT_WORDS_LAUNCH_(NL, PWC, false, false);                                                                   \
-    } while (0)
 #define APT_WORDS_LAUNCH_PW(NL, PWC)                                                                                    \
     do {                                                                                                                \
         if (lean)                                                                                                       \
-            APT_WORDS_LAUNCH_(NL, PWC, true, true);                                                                     \
+            APT_WORDS_LAUNCH(NL, PWC, true);                                                                            \
         else                                                                                                            \
-            APT_WORDS_LAUNCH(NL, PWC);                                                                                  \
+            APT_WORDS_LAUNCH(NL, PWC, false);                                                                           \
     } while (0)
     if (pw == 3) APT_WORDS_LAUNCH_PW(3, 3);        // standard profile
     else if (pw == 4) APT_WORDS_LAUNCH_PW(4, 4);   // fast profile
     else if (pw == 5) APT_WORDS_LAUNCH_PW(4, 5);   // slow profile
-    else if (wneed <= 192) APT_WORDS_LAUNCH(3, 0);
-    else if (wneed <= 256) APT_WORDS_LAUNCH(4, 0);
-    else APT_WORDS_LAUNCH(0, 0);
+    else if (wneed <= 192) APT_WORDS_LAUNCH(3, 0, false);
+    else if (wneed <= 256) APT_WORDS_LAUNCH(4, 0, false);
+    else APT_WORDS_LAUNCH(0, 0, false);
 #undef APT_WORDS_LAUNCH_PW
 #undef APT_WORDS_LAUNCH
-#undef APT_WORDS_LAUNCH_
     if (sw.words_form != 0)
         hipLaunchKernelGGL(k_sync_slots<true>, grid, dim3(kNodesThreads), 0, s, call, d_slots, pw, r, spr / GS);
     else
@@ -1641,7 +1609,7 @@ static bool orbit_all_nodes_available(uint32_t bytes)
         int max_lds = 0;
         const bool ok = hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess &&
                         max_lds >= static_cast<int>(bytes) &&
-                        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sync_orbit_global<kOrbitThreadsMax>),
+                        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sync_orbit_global),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes)) == hipSuccess;
         (void)hipGetLastError();
         st = ok ? 1 : 2;
@@ -1651,10 +1619,10 @@ static bool orbit_all_nodes_available(uint32_t bytes)
 }
 
 void sync_orbit(hipStream_t s, const CallArgs &call, const SlotPtrs *d_slots, uint32_t spr, uint32_t md,
-                uint32_t pw, int force, const LaunchSwitches &sw)
+                uint32_t pw, bool force_walk, const LaunchSwitches &sw)
 {
     if (call.count == 0) return;
-    // force: 0 = parallel picker, 1 = sequential walk over the terminal words
+    // force_walk: the sequential walk over the terminal words instead of the parallel picker
     // 24 KB of LDS for the doubling path's jump tables: a recording's visited nodes (about one per image row plus
     // the seeds) fit unless it is hours long; the kernel falls back to tables in global memory when they do not
     // (APTGPU_ORBIT_LDS=0, tests: always through global memory)
@@ -1665,16 +1633,9 @@ void sync_orbit(hipStream_t s, const CallArgs &call, const SlotPtrs *d_slots, ui
     // recording.  (All switches are read at plan creation: LaunchSwitches.)
     constexpr uint32_t kAllEntries = 65536u;  // uint16 entries: 128 KB
     const int alg = (sw.orbit_alg == 0 || kOrbitLdsEntries == 0u || !orbit_all_nodes_available(kAllEntries * sizeof(uint16_t))) ? 0 : 1;
-    if (sw.orbit_threads == 256) {
-        hipLaunchKernelGGL(k_sync_orbit_global<256>, dim3(call.count), dim3(256), kOrbitLdsEntries * sizeof(uint16_t), s,
-                           call, d_slots, spr, md, pw, force == 1 ? 1 : 0, kOrbitLdsEntries, 0);
-    } else if (alg == 1) {
-        hipLaunchKernelGGL(k_sync_orbit_global<kOrbitThreadsMax>, dim3(call.count), dim3(kOrbitThreadsMax), kAllEntries * sizeof(uint16_t), s,
-                           call, d_slots, spr, md, pw, force == 1 ? 1 : 0, kAllEntries, 1);
-    } else {
-        hipLaunchKernelGGL(k_sync_orbit_global<kOrbitThreadsMax>, dim3(call.count), dim3(kOrbitThreadsMax), kOrbitLdsEntries * sizeof(uint16_t), s,
-                           call, d_slots, spr, md, pw, force == 1 ? 1 : 0, kOrbitLdsEntries, 0);
-    }
+    const uint32_t entries = alg == 1 ? kAllEntries : kOrbitLdsEntries;
+    hipLaunchKernelGGL(k_sync_orbit_global, dim3(call.count), dim3(kOrbitThreads), entries * sizeof(uint16_t), s,
+                       call, d_slots, spr, md, pw, force_walk ? 1 : 0, entries, alg);
 }
 
 }  // namespace apt::gpu

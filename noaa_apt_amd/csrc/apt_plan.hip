@@ -112,35 +112,11 @@ void create_streams(aptgpu_plan *plan, const aptgpu_context *ctx, int depth)
     if (depth <= 0) depth = sw.streams ? sw.streams : (max_batch >= 4 ? 3 : 6);
     depth = std::max(1, std::min(depth, 16));
     plan->streams.resize(static_cast<size_t>(depth));
-    // A/B switches of the pipeline's shape (tools/sweep.py; read at plan creation):
-    //   APTGPU_FRONT_STREAM=1  all front ends on one extra stream (apt_plan.hpp)
-    //   APTGPU_CHAIN_CUS=n     with it: the per-call streams (words, slots, orbit, gather) are created with a CU mask of
-    //                          n CUs, APTGPU_FRONT_EXCL=1: and the front-end stream with the mask of the others
-    int cu_count = 0;
-    (void)hipDeviceGetAttribute(&cu_count, hipDeviceAttributeMultiprocessorCount, plan->device);
-    const bool want_front_stream = sw.front_stream == '1' && !plan->user_stream && depth > 1 && max_batch >= 4;
-    plan->chain_cus = want_front_stream ? std::max(0, std::min(sw.chain_cus, cu_count - 8)) : 0;
-    auto masked_stream = [&](hipStream_t *st, int first, int count) {
-        // bit i of the mask = CU i in the runtime's numbering (consecutive bits go round the XCDs)
-        std::vector<uint32_t> mask(static_cast<size_t>((cu_count + 31) / 32), 0u);
-        for (int c = first; c < first + count && c < cu_count; ++c) mask[static_cast<size_t>(c / 32)] |= 1u << (c % 32);
-        hip_check(hipExtStreamCreateWithCUMask(st, static_cast<uint32_t>(mask.size()), mask.data()), "hipExtStreamCreateWithCUMask");
-    };
-    for (auto &st : plan->streams) {
-        if (plan->chain_cus > 0) masked_stream(&st, 0, plan->chain_cus);
-        else hip_check(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "hipStreamCreate");
-    }
+    for (auto &st : plan->streams) hip_check(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "hipStreamCreate");
     plan->stream = plan->streams[0];
-    if (want_front_stream) {
-        if (plan->chain_cus > 0 && sw.front_excl == '1') masked_stream(&plan->front_stream, plan->chain_cus, cu_count - plan->chain_cus);
-        else hip_check(hipStreamCreateWithFlags(&plan->front_stream, hipStreamNonBlocking), "hipStreamCreate");
-        plan->ev_pre.resize(static_cast<size_t>(depth));
-        for (auto &ev : plan->ev_pre) hip_check(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
-    }
     // (not with a user stream: such plans may be captured into a HIP graph, call by call, and an event
     // recorded before the capture cannot be waited for inside it)
-    plan->front_serial = ((sw.front_serial >= 0 ? sw.front_serial != '0' : max_batch >= 4) && !plan->user_stream && depth > 1) ||
-                         plan->front_stream;
+    plan->front_serial = max_batch >= 4 && !plan->user_stream && depth > 1;
     if (plan->front_serial) {
         plan->ev_front.resize(static_cast<size_t>(depth));
         for (auto &ev : plan->ev_front) hip_check(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
@@ -282,7 +258,7 @@ aptgpu_plan *plan_create(const aptgpu_context *ctx, const aptgpu_settings &setti
     plan->sw = gpu::read_launch_switches();
     plan->psw = gpu::read_plan_switches();
     plan->export_filtered = settings.export_resample_filtered != 0;
-    plan->picker_force = plan->psw.picker_lds == '1' ? 4 : plan->psw.force_walk == '1' ? 1 : 0;
+    plan->force_walk = plan->psw.force_walk == '1';
 
     // the filters, factors and sync geometry (pure host code: apt_front_end.cpp)
     static_cast<PlanDesign &>(*plan) = design_plan(settings, input_rate, sync);
@@ -432,7 +408,6 @@ void ResampleStage::enqueue_filtered(hipStream_t s, const float *d_x, uint64_t n
 
 void aptgpu_plan::sync_all()
 {
-    if (front_stream) apt::hip_check(hipStreamSynchronize(front_stream), "hipStreamSynchronize");
     for (hipStream_t st : streams) apt::hip_check(hipStreamSynchronize(st), "hipStreamSynchronize");
 }
 
@@ -454,14 +429,13 @@ void aptgpu_plan::run_call(int count, const Input *ins, float *const *d_rows, co
         apt::hip_check(hipEventRecord(ev_user, user_stream), "hipEventRecord");
         apt::hip_check(hipStreamWaitEvent(cur, ev_user, 0), "hipStreamWaitEvent");
     }
-    auto timed_on = [&](hipStream_t st, const char *name, auto &&launch) {
+    auto timed = [&](const char *name, auto &&launch) {
         const bool dominant = !std::strcmp(name, "fused_front_end") || !std::strcmp(name, "resample_generic") ||
                               !std::strcmp(name, "resample_f16taps");
-        timer.begin(st, name, dominant);
+        timer.begin(cur, name, dominant);
         launch();
-        timer.end(st);
+        timer.end(cur);
     };
-    auto timed = [&](const char *name, auto &&launch) { timed_on(cur, name, launch); };
 
     const bool use_fused = fe.kind != FrontEndKind::Unfused && !keep_steps;
     const bool want_sync = sync && work_is_multiple;
@@ -523,6 +497,10 @@ void aptgpu_plan::run_call(int count, const Input *ins, float *const *d_rows, co
         }
         live.push_back(i);
     }
+    // the fused front ends take one launch per input kind: the live recordings that are f32 Signals [0] / mono PCM16 [1]
+    std::vector<int> by_kind[2];
+    if (use_fused)
+        for (int i : live) by_kind[is_pcm[static_cast<size_t>(i)] ? 1 : 0].push_back(i);
 
     // per-stage launches cover up to kMaxCall recordings each
     auto make_call = [&](const std::vector<int> &idx, size_t from, size_t to, uint64_t *max_w, uint32_t *max_cap) {
@@ -561,28 +539,19 @@ void aptgpu_plan::run_call(int count, const Input *ins, float *const *d_rows, co
     if (use_fused && writes_planes()) {
         // 1-3 fused: resample -> envelope -> low-pass (-> correlation maxima) in one launch per input
         // kind (apt_kernels_fused.hip), behind the previous call's front end (see front_serial, apt_plan.hpp)
-        hipStream_t fs = cur;
-        if (front_stream && !live.empty()) {
-            // the front end runs on the front-end stream, behind everything the call's stream holds so far
-            fs = front_stream;
-            apt::hip_check(hipEventRecord(ev_pre[static_cast<size_t>(last_stream)], cur), "hipEventRecord");
-            apt::hip_check(hipStreamWaitEvent(fs, ev_pre[static_cast<size_t>(last_stream)], 0), "hipStreamWaitEvent");
-        } else if (front_serial && !live.empty() && prev_front >= 0 && prev_front != last_stream)
+        if (front_serial && !live.empty() && prev_front >= 0 && prev_front != last_stream)
             apt::hip_check(hipStreamWaitEvent(cur, ev_front[static_cast<size_t>(prev_front)], 0), "hipStreamWaitEvent");
         for (int kind = 0; kind < 2; ++kind) {
-            std::vector<int> idx;
-            for (int i : live)
-                if (is_pcm[static_cast<size_t>(i)] == kind) idx.push_back(i);
 #if defined(APT_WITH_PROBES) || defined(APT_DEBUG_SKIP)
             const int rep_f = [] { const char *e = std::getenv("APTGPU_DEBUG_REPEAT_FRONT"); return e ? std::max(1, std::atoi(e)) : 1; }();
 #else
             constexpr int rep_f = 1;
 #endif
             for (int rf = 0; rf < rep_f; ++rf)
-            for_chunks(idx, [&](const CallArgs &c, uint64_t max_w, uint32_t) {
-                timed_on(fs, "fused_front_end", [&] {
+            for_chunks(by_kind[kind], [&](const CallArgs &c, uint64_t max_w, uint32_t) {
+                timed("fused_front_end", [&] {
                     int variant = -1;
-                    const bool ok = fused_front_end(fs, fe, kind == 1, c, d_fused_params.ptr, max_w, sw.fused_lds_pad, &variant);
+                    const bool ok = fused_front_end(cur, fe, kind == 1, c, d_fused_params.ptr, max_w, &variant);
                     for (uint32_t k = 0; k < c.count; ++k) {
                         slots[c.rec[k].slot].fused_variant = variant;
                         slots[c.rec[k].slot].fused_variant_i16 = kind == 1;
@@ -593,18 +562,13 @@ void aptgpu_plan::run_call(int count, const Input *ins, float *const *d_rows, co
             });
         }
         if (front_serial && !live.empty()) {
-            apt::hip_check(hipEventRecord(ev_front[static_cast<size_t>(last_stream)], fs), "hipEventRecord");
+            apt::hip_check(hipEventRecord(ev_front[static_cast<size_t>(last_stream)], cur), "hipEventRecord");
             prev_front = last_stream;
-            // (the chain follows on the call's stream)
-            if (front_stream) apt::hip_check(hipStreamWaitEvent(cur, ev_front[static_cast<size_t>(last_stream)], 0), "hipStreamWaitEvent");
         }
     } else if (use_fused) {
         // the run-time front end (k_fused_any: fast / slow profiles, odd rates): one launch per input kind too
         for (int kind = 0; kind < 2; ++kind) {
-            std::vector<int> idx;
-            for (int i : live)
-                if (is_pcm[static_cast<size_t>(i)] == kind) idx.push_back(i);
-            for_chunks(idx, [&](const CallArgs &c, uint64_t max_w, uint32_t) {
+            for_chunks(by_kind[kind], [&](const CallArgs &c, uint64_t max_w, uint32_t) {
                 timed("fused_front_end", [&] {
                     if (!fused_any_front_end(cur, l, m, t1, t2, pw, kind == 1, c, d_slots.ptr, max_w, d_taps_any.ptr,
                                              d_taps_lowpass.ptr, d_taps_lowpass_pairs.ptr, cosphi2, sinphi, inv_sinphi,
@@ -688,7 +652,7 @@ void aptgpu_plan::run_call(int count, const Input *ins, float *const *d_rows, co
                         timed("sync_nodes", [&] { sync_nodes(cur, c, d_slots.ptr, max_w, pw, spr, md, use_fused && fe.fast, !use_fused, sw); });
                 if (!(skip & 2))
                     for (int r = 0; r < rep_o; ++r)
-                        timed("sync_orbit", [&] { sync_orbit(cur, c, d_slots.ptr, spr, md, pw, picker_force, sw); });
+                        timed("sync_orbit", [&] { sync_orbit(cur, c, d_slots.ptr, spr, md, pw, force_walk, sw); });
             });
             gather_wanted = !(skip & 4);
         }
@@ -696,7 +660,7 @@ void aptgpu_plan::run_call(int count, const Input *ins, float *const *d_rows, co
         if (gather_wanted)
             for (int r = 0; r < gather_reps; ++r)
                 for_chunks(live, [&](const CallArgs &c, uint64_t, uint32_t max_cap) {
-                    timed("gather_rows", [&] { gather_rows_call(cur, c, d_slots.ptr, spr, pw, max_cap, sw); });
+                    timed("gather_rows", [&] { gather_rows_call(cur, c, d_slots.ptr, spr, pw, max_cap); });
                 });
     } else {
         // decode.rs:135-159 — crop to whole rows, resample_with_filter(NoFilter).  Where that is a pure decimation

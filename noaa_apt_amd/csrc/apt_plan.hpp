@@ -138,19 +138,13 @@ struct aptgpu_plan : apt::PlanDesign {
     // call j+1.  Left alone, the front ends of `depth` consecutive calls start together, share the GPU,
     // finish together — and their latency-bound chains then run with nothing to overlap (a kernel trace showed
     // three calls marching in step: 2.4 ms of front ends, then 0.8 ms of chains).  Worth 7 % in a 20-step run
-    // (477 against 445 Gsamples/s), nothing in a long one (the chains cost their own time either way); one
-    // extra low-priority stream for all front ends was tried as well and is no better.
+    // (477 against 445 Gsamples/s), nothing in a long one (the chains cost their own time either way).  The front
+    // ends stay on the calls' own streams: on one stream of their own every chain starts an event hand-over later
+    // (0.0588 against 0.053 ms per recording, profiles/r04_sweeps.txt).
+    // Chosen from what the plan can see: max_batch >= 4, more than one stream, no user stream (create_streams).
     bool front_serial = false;
     std::vector<hipEvent_t> ev_front;   // [depth]: behind the front end of the latest call on that stream
     int prev_front = -1;                // stream index whose ev_front the next front end waits for
-    // Alternative (APTGPU_FRONT_STREAM=1, an A/B switch): every front end on ONE extra in-order stream — consecutive
-    // front ends then follow each other inside one hardware queue instead of through a cross-queue event — and the
-    // chain of call j on stream j % depth behind an event recorded after its front end.  The front-end stream
-    // waits for an event recorded on the call's stream first (whatever the caller ordered the call behind, and the
-    // previous chain on those workspace slots).
-    hipStream_t front_stream = nullptr;
-    std::vector<hipEvent_t> ev_pre;     // [depth]: the call's stream just before its front end is enqueued
-    int chain_cus = 0;                  // APTGPU_CHAIN_CUS=n: the per-call (chain) streams run on n CUs only
     hipStream_t user_stream = nullptr;  // ctx.stream: inputs are ordered after it (may be null)
     hipEvent_t ev_user = nullptr;
     uint64_t calls = 0;             // calls enqueued so far (stream = calls % depth)
@@ -172,7 +166,7 @@ struct aptgpu_plan : apt::PlanDesign {
     int fused() const { return static_cast<int>(fe.kind); }  // (stats.fused, aptgpu_plan_info.fused)
     apt::gpu::LaunchSwitches sw{};  // the A/B switches of the launch wrappers as the environment had them at plan creation
     apt::gpu::PlanSwitches psw{};   // ... and the switches of the plan's shape
-    int picker_force = 0;  // 0 parallel picker; APTGPU_FORCE_WALK=1 -> 1 (the sequential fallback), APTGPU_PICKER_LDS=1 -> 4
+    bool force_walk = false;  // APTGPU_FORCE_WALK=1: the picker's sequential fallback for every recording
 
     apt::DeviceBuffer<float> d_taps_resample, d_taps_lowpass, d_one, d_taps_branch, d_taps_lowpass_pairs, d_taps_any, d_taps_lowpass_pad;
     apt::DeviceBuffer<uint16_t> d_taps_f16;  // APTGPU_MODE_FP16_TAPS

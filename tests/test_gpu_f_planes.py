@@ -11,6 +11,7 @@ result record with the oracle's, bit for bit:
 * pixel widths 4 and 5 (fast / slow profile at 48 kHz, and the fast profile at 96 kHz, whose front end is a SPLIT
   instantiation where 48 kHz runs a PHASE one), a PHASE rate (44 100 Hz), a rate served by k_fused_any (60 kHz:
   contiguous F in every consumer), PCM16 input, sync=False, a run of NaN, rows_cap below the row count;
+* rows pointers off a 16-byte boundary: the eight-rows gather, storing quads and single floats in one call;
 * read_internal("filtered"): the oracle's filtered signal in natural order, and what an unfused plan returns;
 * widened bounds (APTGPU_GM_SLACK_SCALE), so that k_sync_words' exact settlement loads windows too;
 * both forms of k_sync_words (APTGPU_WORDS_FORM=0 and the default), each in a fresh child process.
@@ -103,17 +104,22 @@ def _same(got, want, what, nan_ok=False):
     assert bad.size == 0, (what, f"{bad.size} of {got.size} differ, first at {int(bad[0])}", got[bad[0]], want[bad[0]])
 
 
-def _decode(name, sync=True, pcm16=False, mode=apt.MODE_STRICT, cap=None, want_f=False, want_flags=False):
-    """the recordings of a case through ONE decode_device call of a fresh plan"""
+def _decode(name, sync=True, pcm16=False, mode=apt.MODE_STRICT, cap=None, want_f=False, want_flags=False, offsets=None):
+    """the recordings of a case through ONE decode_device call of a fresh plan.  offsets: floats per recording by which
+    its rows pointer lies behind the start of its (that much larger) tensor"""
     import torch  # (a missing module is an error here, not a skip)
     xs, rate, profile = _case(name)
+    offs = [0] * len(xs) if offsets is None else list(offsets)
+    assert len(offs) == len(xs)
     dev = torch.device("cuda:0")
     plan = apt.Plan(apt.Settings.profile(profile), apt.Rate.hz(rate), sync, max_samples=max(x.size for x in xs),
                     max_batch=len(xs), mode=mode)
     try:
         room = int(plan.info.max_rows) + 2
         caps = [room if cap is None else cap] * len(xs)
-        d_out = [torch.full((room * 2080,), -7.0, dtype=torch.float32, device=dev) for _ in xs]
+        d_full = [torch.full((room * 2080 + off,), -7.0, dtype=torch.float32, device=dev) for off in offs]
+        d_out = [t[off:] for t, off in zip(d_full, offs)]  # (data_ptr() of a view: the tensor's + 4 off bytes)
+        assert all(t.data_ptr() % 16 == 0 for t in d_full), "the allocator is meant to return 16-byte aligned tensors"
         if pcm16:
             for x in xs:
                 assert np.array_equal(x, x.astype(np.int16).astype(f32)), "the case is no 16-bit recording"
@@ -131,6 +137,7 @@ def _decode(name, sync=True, pcm16=False, mode=apt.MODE_STRICT, cap=None, want_f
             r = res[i]
             out.append(dict(
                 rows=d_out[i][:r.n_out].cpu().numpy(), behind=d_out[i][r.n_out:].cpu().numpy(),
+                front=d_full[i][:offs[i]].cpu().numpy(),
                 record=(int(r.status), int(r.reason), int(r.n_rows), int(r.n_sync), int(r.work_len), int(r.n_out)),
                 pos=plan.sync_positions(i) if sync else None,
                 variant=bytes(plan.read_internal("fused_variant", np.uint8, 64, i=i)).rstrip(b"\0").decode(),
@@ -149,6 +156,7 @@ def _check(name, got, nan_ok=False):
         assert g["pos"].tolist() == st["sync_pos"].tolist(), what
         _same(g["rows"], want, what, nan_ok)
         assert np.all(g["behind"] == f32(-7.0)), (what, "written behind the rows")
+        assert np.all(g["front"] == f32(-7.0)), (what, "written in front of the rows")
 
 
 @pytest.mark.parametrize("k", [0, 1, 2])
@@ -191,6 +199,16 @@ def test_k_fused_any_keeps_the_contiguous_layout(oracle):
     assert got[0]["variant"] == "", "60 kHz is meant to run k_fused_any"
     _check("any-60000", got)
     _same(got[0]["F"], _oracle("any-60000")[0][1]["filtered"], "any-60000 filtered")
+
+
+@pytest.mark.parametrize("name,offsets", [("four", [0, 1, 0, 2]), ("any-60000", [1])])
+def test_rows_pointers_that_are_not_16_byte_aligned(oracle, name, offsets):
+    """One rows pointer of a call off a 16-byte boundary sends the whole call through the eight-rows gather
+    (k_gather_rows_call): recordings whose own pointer is aligned store quads there, the others single floats.  `four`:
+    F in planes, both kinds in one call; `any-60000`: contiguous F.  Same rows, nothing written outside them."""
+    got = _decode(name, offsets=offsets)
+    assert [g["variant"] for g in got] == (["48k_f32"] * 4 if name == "four" else [""])
+    _check(name, got)
 
 
 def test_pcm16_input(oracle):

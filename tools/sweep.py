@@ -5,7 +5,7 @@ recordings-per-call / calls-in-flight, one process, inputs generated once.
     python tools/sweep.py --configs strict:1:6,strict:8:3,fast:1:6,fast:8:3 --steps 40
 
 Each config is mode:batch:streams[:ENV=VALUE;ENV=VALUE...] — the optional fourth field sets environment switches of
-the library (APTGPU_WORDS_DPP, APTGPU_GATHER_ITERS, APTGPU_FRONT_STREAM, ...: read at plan creation or per launch)
+the library (APTGPU_WORDS_FORM, APTGPU_ORBIT_ALG, APTGPU_ORBIT_LDS, ...: read at plan creation)
 for that config only.  Prints one JSON line per config: ms per recording in the
 pipelined loop, Msamples/s, and the per-kernel times with one call in flight at a time.
 """
