@@ -1482,10 +1482,8 @@ def projection_fit(sat_positions, kind=Projection.EQUIRECTANGULAR, step=None, ma
     err = C.create_string_buffer(_ERRCAP)
     if isinstance(sat_positions, (list, tuple)) and len(sat_positions) and np.ndim(sat_positions[0]) == 2:
         # several tracks (aptgpu_projection_fit_many): the union box, longitudes unwrapped from the first track
-        tracks = [np.ascontiguousarray(np.asarray(t, dtype=np.float64).reshape(-1, 2)) for t in sat_positions]
-        k = len(tracks)
-        _check(lib().aptgpu_projection_fit_many((_f64p * k)(*[t.ctypes.data_as(_f64p) for t in tracks]),
-                                                (C.c_size_t * k)(*[len(t) for t in tracks]), k, float(hscale),
+        tracks, pos, npos = _track_arrays(sat_positions)
+        _check(lib().aptgpu_projection_fit_many(pos, npos, len(tracks), float(hscale),
                                                 int(kind), float(step) if step is not None else 0.0,
                                                 int(max_width) if max_width is not None else 0, C.byref(out), err,
                                                 _ERRCAP), err)
@@ -1499,6 +1497,30 @@ def projection_fit(sat_positions, kind=Projection.EQUIRECTANGULAR, step=None, ma
                               out.sampling, out.grid_deg)
 
 
+def _one_per(x, cls, k, name, noun, per):
+    """x as a list of k `cls`: the one object that serves all of them, or one per recording (or pass)."""
+    xs = [x] * k if isinstance(x, cls) else list(x)
+    if len(xs) != k or not all(isinstance(v, cls) for v in xs):
+        raise InvalidError(f"{name}: {noun} or one per {per}")
+    return xs
+
+
+def _orbit_pointers(orbits):
+    """(the array of pointers to the OrbitSettings' structs, what those structs point into)"""
+    keep = [o._c() for o in orbits]
+    return (C.POINTER(_COrbitSettings) * len(keep))(*[C.pointer(c) for c, _ in keep]), keep
+
+
+def _track_arrays(tracks):
+    """sat_positions arrays as (contiguous (rows, 2) f64 arrays, the array of their pointers, their row counts)"""
+    tr = [np.ascontiguousarray(np.asarray(t, dtype=np.float64).reshape(-1, 2)) for t in tracks]
+    return tr, (_f64p * len(tr))(*[t.ctypes.data_as(_f64p) for t in tr]), (C.c_size_t * len(tr))(*[len(t) for t in tr])
+
+
+def _ref(struct):
+    return C.byref(struct) if struct is not None else None
+
+
 def project_image(image, sat_positions, projection, settings=None, png=False, context=None):
     """aptgpu_project_image: an unrotated (height, 2080) gray or (height, 2080, 4) RGBA uint8 image with its track
     (height rows of lat, lon in radians) onto the grid of `projection`: the (grid height, grid width, 4) RGBA array,
@@ -1508,14 +1530,14 @@ def project_image(image, sat_positions, projection, settings=None, png=False, co
         raise InvalidError("project_image: a uint8 array of (height, 2080) or (height, 2080, 4)")
     if not isinstance(projection, ProjectionSettings):
         raise InvalidError("projection must be a ProjectionSettings")
-    pos = np.ascontiguousarray(np.asarray(sat_positions, dtype=np.float64).reshape(-1, 2))
+    _keep, pos, npos = _track_arrays([sat_positions])
     cctx = (context or Context())._c()
     cms = (settings or projection.geometry or MapSettings())._c()
     cpr, cps = projection._c(), _CPngSettings(C.sizeof(_CPngSettings), 0)
     out, n = _u8p(), C.c_size_t()
     err = C.create_string_buffer(_ERRCAP)
     _check(lib().aptgpu_project_image(C.byref(cctx), x.ctypes.data_as(_u8p), x.shape[0], 4 if x.ndim == 3 else 1,
-                                      pos.ctypes.data_as(_f64p), len(pos), C.byref(cms), C.byref(cpr), 1 if png else 0,
+                                      pos[0], npos[0], C.byref(cms), C.byref(cpr), 1 if png else 0,
                                       C.byref(cps), C.byref(out), C.byref(n), err, _ERRCAP), err)
     data = _take(out, n.value, np.uint8)
     return data.tobytes() if png else data.reshape(projection.shape)
@@ -1565,7 +1587,7 @@ def composite_images(images, tracks, projection, blend=Composite.NADIR, settings
     if len(tracks) != k:
         raise InvalidError("composite: one track per image")
     xs = _composite_passes(images)
-    pos = [np.ascontiguousarray(np.asarray(t, dtype=np.float64).reshape(-1, 2)) for t in tracks]
+    keep_tracks, pos, npos = _track_arrays(tracks)
     maps, keep = _composite_maps(settings, projection, k)
     cctx = (context or Context())._c()
     cpr, cps = projection._c(), _CPngSettings(C.sizeof(_CPngSettings), 0)
@@ -1575,10 +1597,9 @@ def composite_images(images, tracks, projection, blend=Composite.NADIR, settings
     _check(lib().aptgpu_composite_images(
         C.byref(cctx), k, (_u8p * k)(*[x.ctypes.data_as(_u8p) for x in xs]),
         (C.c_uint32 * k)(*[x.shape[0] for x in xs]), (C.c_int32 * k)(*[4 if x.ndim == 3 else 1 for x in xs]),
-        (_f64p * k)(*[p.ctypes.data_as(_f64p) for p in pos]), (C.c_size_t * k)(*[len(p) for p in pos]), maps,
-        C.byref(cpr), C.byref(cco), 1 if png else 0, C.byref(cps), C.byref(out), C.byref(n),
+        pos, npos, maps, C.byref(cpr), C.byref(cco), 1 if png else 0, C.byref(cps), C.byref(out), C.byref(n),
         C.byref(cov) if return_coverage else None, err, _ERRCAP), err)
-    del keep
+    del keep, keep_tracks
     data = _take(out, n.value, np.uint8)
     data = data.tobytes() if png else data.reshape(projection.shape)
     if return_coverage:
@@ -1586,47 +1607,57 @@ def composite_images(images, tracks, projection, blend=Composite.NADIR, settings
     return data
 
 
-def _process_image_project(context, signal, contrast_adjustment, rotate, color, return_info, orbit, layers, png,
-                           projection):
-    if not isinstance(projection, ProjectionSettings):
-        raise InvalidError("projection must be a ProjectionSettings")
-    if color is not None and not isinstance(color, ColorSettings):
-        raise UnsupportedError("color must be a ColorSettings")
-    if orbit is None:
-        raise InvalidError("a projection needs the track: orbit = a MapOverlay, an OrbitSettings or the sat_positions")
-    cctx = (context or Context())._c()
-    x, xp = _as_f32(signal)
-    kind, p = Contrast._c(contrast_adjustment)
-    ccol = color._c() if color is not None else None
-    corb, keep, pos, lay, ms = None, None, None, None, projection.geometry
-    if isinstance(orbit, OrbitSettings):
-        corb, keep = orbit._c()
-        if orbit.draw_map is not None:
-            if not isinstance(layers, MapLayers):
-                raise InvalidError("OrbitSettings.draw_map needs layers=MapLayers")
-            layers._colors(orbit.draw_map)
-            lay, ms = layers, orbit.draw_map
-    elif isinstance(orbit, MapOverlay):
-        orbit.layers._colors(orbit.settings)
-        pos, lay, ms = orbit.sat_positions, orbit.layers, orbit.settings
-    else:
-        pos = np.ascontiguousarray(np.asarray(orbit, dtype=np.float64).reshape(-1, 2))
-    if pos is not None and len(pos) != x.size // PX_PER_ROW:
-        raise InvalidError(f"projection: {len(pos)} positions for {x.size // PX_PER_ROW} rows")
-    channels = 4 if color is not None or lay is not None else 1
-    cms = (ms or MapSettings())._c()
-    cpr, cps = projection._c(), _CPngSettings(C.sizeof(_CPngSettings), 0)
-    img, n, info = _u8p(), C.c_size_t(), ImageResult()
-    err = C.create_string_buffer(_ERRCAP)
-    _check(lib().aptgpu_process_image_project(
-        C.byref(cctx), xp, x.size, kind, p, int(rotate), C.byref(ccol) if ccol is not None else None, channels,
-        C.byref(cms), lay._p if lay is not None else None, pos.ctypes.data_as(_f64p) if pos is not None else None,
-        C.byref(corb) if corb is not None else None, C.byref(cpr), 1 if png else 0, C.byref(cps), C.byref(img),
-        C.byref(n), C.byref(info), err, _ERRCAP), err)
-    del keep
-    out = _take(img, n.value, np.uint8)
-    out = out.tobytes() if png else out.reshape(projection.shape)
-    return (out, info) if return_info else out
+class _ImageRequest:
+    """What one call of process() or of Plan.process_device_image asks of the image entry points of include/aptgpu.h,
+    turned into their arguments once.  The constructor takes what every entry point has (`head`); resolve() takes the
+    rest and leaves the track source as one of four: none, MapOverlays (positions and a drawn map), OrbitSettings (a
+    drawn map with draw_map) or, under a projection, plain sat_positions.  The two callers make the checks of their
+    own before, between and after the two; tests/test_image_request_py_cpu.py holds the order of all of them."""
+
+    def __init__(self, contrast, rotate, color, channels):
+        if color is not None and not isinstance(color, ColorSettings):
+            raise UnsupportedError("color must be a ColorSettings")
+        self.contrast, self.percent = Contrast._c(contrast)
+        self.rotate, self.channels = int(rotate), channels
+        self.color = color._c() if color is not None else None
+
+    def resolve(self, k, map, orbit, layers, png, grids):  # noqa: A002
+        """map: a MapOverlay or k of them or, under a projection, k sat_positions arrays; orbit: an OrbitSettings or k
+        of them; at most one of the two.  png: whether the PNG file is asked for; grids: k ProjectionSettings or None.
+        `keep` is what the pointers in the arguments point into."""
+        self.map = self.layers = self.positions = self.counts = self.orbits = self.cgrids = self.keep = None
+        if orbit is not None:
+            orbits = _one_per(orbit, OrbitSettings, k, "orbit", "an OrbitSettings", "recording")
+            if orbits and orbits[0].draw_map is not None:
+                if not isinstance(layers, MapLayers):
+                    raise InvalidError("OrbitSettings.draw_map needs layers=MapLayers")
+                self.map, self.layers = orbits[0].draw_map, layers
+            self.orbits, self.keep = _orbit_pointers(orbits)
+        elif map is not None:
+            tracks = map
+            if grids is None or isinstance(map, MapOverlay) or all(isinstance(m, MapOverlay) for m in map):
+                maps = _one_per(map, MapOverlay, k, "map", "a MapOverlay", "recording")
+                if any(m.layers is not maps[0].layers or vars(m.settings) != vars(maps[0].settings) for m in maps):
+                    raise InvalidError("map: every recording's MapOverlay must share settings and layers")
+                self.map, self.layers = maps[0].settings, maps[0].layers
+                tracks = [m.sat_positions for m in maps]
+            self.keep, self.positions, self.counts = _track_arrays(tracks)
+            if len(self.keep) != k:
+                raise InvalidError("map: one sat_positions array per recording")
+        if self.layers is not None:
+            self.layers._colors(self.map)
+        if self.channels is None:
+            self.channels = 4 if self.color is not None or self.layers is not None else 1
+        if grids is not None:  # (the geometry that places the swath is the drawn map's, else the first grid's)
+            self.map = self.map or grids[0].geometry or MapSettings()
+            self.cgrids = (_CProjectionSettings * k)(*[g._c() for g in grids])
+        self.cmap = self.map._c() if self.map is not None else None
+        self.cpng = _CPngSettings(C.sizeof(_CPngSettings), 0)
+        self.layers_p = self.layers._p if self.layers is not None else None
+        self.head = self.contrast, self.percent, self.rotate, _ref(self.color), int(self.channels)
+        # the entry point that serves the request, as what its name ends in
+        self.entry = "_project" if grids is not None else "_orbit" if orbit is not None else "_png" if png else \
+            "_map" if map is not None else ""
 
 
 class DespeckleSettings:
@@ -2995,23 +3026,10 @@ def process(context, signal, contrast_adjustment, rotate=Rotate.NO, color=None, 
             raise InvalidError("despeckle must be a DespeckleSettings")
         signal = _despeckle(signal, despeckle, context)
         return process(context, signal, contrast_adjustment, rotate, color, orbit, return_info, png, layers, projection)
-    if projection is not None:
-        return _process_image_project(context, signal, contrast_adjustment, rotate, color, return_info, orbit, layers,
-                                      png, projection)
-    if isinstance(orbit, OrbitSettings):
-        return _process_image_orbit(context, signal, contrast_adjustment, rotate, color, return_info, orbit, layers, png)
-    if png:
-        if orbit is not None and not isinstance(orbit, MapOverlay):
-            raise UnsupportedError("orbit: only a MapOverlay (the map overlay) is served on the GPU path")
-        return _process_image(context, signal, contrast_adjustment, rotate, color, return_info, orbit, png=True)
-    if isinstance(orbit, MapOverlay):
-        return _process_image(context, signal, contrast_adjustment, rotate, color, return_info, orbit)
-    if orbit is not None:
-        raise UnsupportedError("orbit: only a MapOverlay (the map overlay) is served on the GPU path")
-    if color is not None and not isinstance(color, ColorSettings):
-        raise UnsupportedError("color must be a ColorSettings")
-    if color is not None or contrast_adjustment in (Contrast.HISTOGRAM, Contrast.HISTOGRAM_FLOAT):
-        return _process_image(context, signal, contrast_adjustment, rotate, color, return_info)
+    if projection is not None or orbit is not None or png or color is not None or \
+            contrast_adjustment in (Contrast.HISTOGRAM, Contrast.HISTOGRAM_FLOAT):
+        return _process_image(context, signal, contrast_adjustment, rotate, color, return_info, orbit, None, png, layers,
+                              projection)
     cctx = (context or Context())._c()
     x, xp = _as_f32(signal)
     kind, p = Contrast._c(contrast_adjustment)
@@ -3023,73 +3041,43 @@ def process(context, signal, contrast_adjustment, rotate=Rotate.NO, color=None, 
     return (out, info) if return_info else out
 
 
-def _process_image(context, signal, contrast_adjustment, rotate, color, return_info, overlay=None, channels=None,
-                   png=False):
-    if color is not None and not isinstance(color, ColorSettings):
-        raise UnsupportedError("color must be a ColorSettings")
+def _process_image(context, signal, contrast_adjustment, rotate, color, return_info, orbit=None, channels=None,
+                   png=False, layers=None, projection=None):
+    """process() through the image entry points, rows and image on the host (channels: 1 or 4, process() leaves it
+    to the request)."""
+    if projection is not None and not isinstance(projection, ProjectionSettings):
+        raise InvalidError("projection must be a ProjectionSettings")
+    if projection is None and orbit is not None and not isinstance(orbit, (MapOverlay, OrbitSettings)):
+        raise UnsupportedError("orbit: only a MapOverlay (the map overlay) is served on the GPU path")
+    req = _ImageRequest(contrast_adjustment, rotate, color, channels)
+    if projection is not None and orbit is None:
+        raise InvalidError("a projection needs the track: orbit = a MapOverlay, an OrbitSettings or the sat_positions")
+    grids = [projection] if projection is not None else None
+    if isinstance(orbit, OrbitSettings):
+        req.resolve(1, None, orbit, layers, png, grids)
+    else:  # (nothing, a MapOverlay or, under a projection, the sat_positions)
+        req.resolve(1, orbit if orbit is None or isinstance(orbit, MapOverlay) else [orbit], None, layers, png, grids)
     cctx = (context or Context())._c()
     x, xp = _as_f32(signal)
-    kind, p = Contrast._c(contrast_adjustment)
-    if channels is None:
-        channels = 4 if color is not None or overlay is not None else 1
-    ccol = color._c() if color is not None else None
+    if req.counts is not None and req.counts[0] != x.size // PX_PER_ROW:  # (the plan leaves this to the record)
+        raise InvalidError(f"{'MapOverlay' if projection is None else 'projection'}: {req.counts[0]} positions for "
+                           f"{x.size // PX_PER_ROW} rows")
+    pos = req.positions[0] if req.positions is not None else None
+    orb = req.orbits[0] if req.orbits is not None else None
+    cmap, lay, output, cpng = _ref(req.cmap), req.layers_p, 1 if png else 0, C.byref(req.cpng)
+    tail = {"_project": (cmap, lay, pos, orb, req.cgrids, output, cpng), "_orbit": (orb, lay, output, cpng),
+            "_png": (cmap, lay, pos, cpng), "_map": (cmap, lay, pos), "": ()}[req.entry]
     img, n, info = _u8p(), C.c_size_t(), ImageResult()
     err = C.create_string_buffer(_ERRCAP)
-    if overlay is not None:
-        if len(overlay.sat_positions) != x.size // PX_PER_ROW:
-            raise InvalidError(f"MapOverlay: {len(overlay.sat_positions)} positions for {x.size // PX_PER_ROW} rows")
-        overlay.layers._colors(overlay.settings)
-    if png:
-        cms = overlay.settings._c() if overlay is not None else None
-        cps = _CPngSettings(C.sizeof(_CPngSettings), 0)
-        _check(lib().aptgpu_process_image_png(
-            C.byref(cctx), xp, x.size, kind, p, int(rotate), C.byref(ccol) if ccol is not None else None,
-            int(channels), C.byref(cms) if cms is not None else None, overlay.layers._p if overlay is not None else None,
-            overlay.sat_positions.ctypes.data_as(_f64p) if overlay is not None else None, C.byref(cps), C.byref(img),
-            C.byref(n), C.byref(info), err, _ERRCAP), err)
-        data = _take(img, n.value, np.uint8).tobytes()
-        return (data, info) if return_info else data
-    if overlay is not None:
-        cms = overlay.settings._c()
-        _check(lib().aptgpu_process_image_map(C.byref(cctx), xp, x.size, kind, p, int(rotate),
-                                              C.byref(ccol) if ccol is not None else None, int(channels),
-                                              C.byref(cms), overlay.layers._p,
-                                              overlay.sat_positions.ctypes.data_as(_f64p), C.byref(img), C.byref(n),
-                                              C.byref(info), err, _ERRCAP), err)
-    else:
-        _check(lib().aptgpu_process_image(C.byref(cctx), xp, x.size, kind, p, int(rotate),
-                                          C.byref(ccol) if ccol is not None else None, channels, C.byref(img),
-                                          C.byref(n), C.byref(info), err, _ERRCAP), err)
-    out = _take(img, n.value, np.uint8)
-    out = out.reshape(-1, PX_PER_ROW, 4) if channels == 4 else out.reshape(-1, PX_PER_ROW)
-    return (out, info) if return_info else out
-
-
-def _process_image_orbit(context, signal, contrast_adjustment, rotate, color, return_info, orbit, layers, png):
-    if color is not None and not isinstance(color, ColorSettings):
-        raise UnsupportedError("color must be a ColorSettings")
-    if orbit.draw_map is not None:
-        if not isinstance(layers, MapLayers):
-            raise InvalidError("OrbitSettings.draw_map needs layers=MapLayers")
-        layers._colors(orbit.draw_map)
-    cctx = (context or Context())._c()
-    x, xp = _as_f32(signal)
-    kind, p = Contrast._c(contrast_adjustment)
-    channels = 4 if color is not None or orbit.draw_map is not None else 1
-    ccol = color._c() if color is not None else None
-    corb, _keep = orbit._c()
-    cps = _CPngSettings(C.sizeof(_CPngSettings), 0)
-    img, n, info = _u8p(), C.c_size_t(), ImageResult()
-    err = C.create_string_buffer(_ERRCAP)
-    _check(lib().aptgpu_process_image_orbit(
-        C.byref(cctx), xp, x.size, kind, p, int(rotate), C.byref(ccol) if ccol is not None else None, channels,
-        C.byref(corb), layers._p if orbit.draw_map is not None else None, 1 if png else 0, C.byref(cps), C.byref(img),
-        C.byref(n), C.byref(info), err, _ERRCAP), err)
+    _check(getattr(lib(), "aptgpu_process_image" + req.entry)(
+        C.byref(cctx), xp, x.size, *req.head, *tail, C.byref(img), C.byref(n), C.byref(info), err, _ERRCAP), err)
     out = _take(img, n.value, np.uint8)
     if png:
         out = out.tobytes()
+    elif projection is not None:
+        out = out.reshape(projection.shape)
     else:
-        out = out.reshape(-1, PX_PER_ROW, 4) if channels == 4 else out.reshape(-1, PX_PER_ROW)
+        out = out.reshape(-1, PX_PER_ROW, 4) if req.channels == 4 else out.reshape(-1, PX_PER_ROW)
     return (out, info) if return_info else out
 
 
@@ -3306,13 +3294,10 @@ class Plan:
         _, _, _, cms, cs, keep = _geoloc_c(None, map_settings, settings)
         pos = cnt = orb = None
         if k and all(orbits):
-            cos_ = [t._c() for t in tracks_or_orbits]
-            orb = (C.POINTER(_COrbitSettings) * k)(*[C.pointer(c[0]) for c in cos_])
+            orb, cos_ = _orbit_pointers(tracks_or_orbits)
             keep = (keep, cos_)
         else:
-            tr = [np.ascontiguousarray(np.asarray(t, dtype=np.float64).reshape(-1, 2)) for t in tracks_or_orbits]
-            pos = (_f64p * k)(*[t.ctypes.data_as(_f64p) for t in tr])
-            cnt = (C.c_size_t * k)(*[t.shape[0] for t in tr])
+            tr, pos, cnt = _track_arrays(tracks_or_orbits)
             keep = (keep, tr)
 
         def arr(v):
@@ -3358,132 +3343,42 @@ class Plan:
         `map`'s (a MapOverlay: the map is drawn first), `orbit`'s, or map = a list of plain sat_positions arrays
         (no map).  A capacity that is too small is reported in image_results() (reason PROJECT_REASON_CAPACITY) and
         nothing is written; a position count that differs from the height as reason 7."""
-        if color is not None and not isinstance(color, ColorSettings):
-            raise UnsupportedError("color must be a ColorSettings")
+        req = _ImageRequest(contrast_adjustment, rotate, color, channels)
         k = len(d_rows)
+        grids, out = None, (None, None)
         if projection is not None:
-            return self._process_device_image_project(d_rows, rows_cap, contrast_adjustment, d_images, rotate, color,
-                                                      channels, map, png, orbit, layers, projection)
-        orbits = None
-        if orbit is not None:
-            if map is not None:
-                raise InvalidError("map and orbit exclude each other")
-            orbits = [orbit] * k if isinstance(orbit, OrbitSettings) else list(orbit)
-            if len(orbits) != k or not all(isinstance(o, OrbitSettings) for o in orbits):
-                raise InvalidError("orbit: an OrbitSettings or one per recording")
-        drawn = bool(orbits) and orbits[0].draw_map is not None
-        if channels is None:
-            channels = 4 if color is not None or map is not None or drawn else 1
-        kind, p = Contrast._c(contrast_adjustment)
-        ccol = color._c() if color is not None else None
+            grids, d_out, out_cap = projection
+            grids = [grids] * k if isinstance(grids, ProjectionSettings) else list(grids)
+            if len(grids) != k or len(d_out) != k or len(out_cap) != k or \
+                    not all(isinstance(g, ProjectionSettings) for g in grids):
+                raise InvalidError("projection: (settings, d_out, out_cap) with one entry per recording")
+            if (map is None) == (orbit is None):
+                raise InvalidError("a projection needs the track: exactly one of map and orbit")
+            out = (C.c_void_p * k)(*d_out), (C.c_size_t * k)(*[int(c) for c in out_cap])
+        elif map is not None and orbit is not None:
+            raise InvalidError("map and orbit exclude each other")
+        if projection is None and orbit is None:
+            self._png_arrays(png, k)  # (this form alone has always checked the pair before the map)
+        req.resolve(k, map, orbit, layers, png is not None, grids)
+        pngs = self._png_arrays(png, k)
+        cmap, lay, cpng, images = _ref(req.cmap), req.layers_p, C.byref(req.cpng), (C.c_void_p * k)(*d_images)
+        pos = req.positions, req.counts
+        tail = {"_project": (cmap, lay, *pos, req.orbits, images, req.cgrids, *out, cpng, *pngs),
+                "_orbit": (req.orbits, lay, images, cpng, *pngs), "_png": (cmap, lay, *pos, images, cpng, *pngs),
+                "_map": (cmap, lay, *pos, images), "": (images,)}[req.entry]
         err = C.create_string_buffer(_ERRCAP)
-        if orbits is not None:
-            if drawn:
-                if not isinstance(layers, MapLayers):
-                    raise InvalidError("OrbitSettings.draw_map needs layers=MapLayers")
-                layers._colors(orbits[0].draw_map)
-            cs = [o._c() for o in orbits]
-            ptrs = (C.POINTER(_COrbitSettings) * k)(*[C.pointer(c) for c, _ in cs])
-            cps = _CPngSettings(C.sizeof(_CPngSettings), 0)
-            d_png, png_cap = png if png is not None else (None, None)
-            if png is not None and (len(d_png) != k or len(png_cap) != k):
-                raise InvalidError("png: (d_png, png_cap) with one entry per recording")
-            _check(lib().aptgpu_plan_process_device_image_orbit(
-                self._p, k, (C.c_void_p * k)(*d_rows), (C.c_size_t * k)(*rows_cap), kind, p, int(rotate),
-                C.byref(ccol) if ccol is not None else None, int(channels), ptrs, layers._p if drawn else None,
-                (C.c_void_p * k)(*d_images), C.byref(cps), (C.c_void_p * k)(*d_png) if png is not None else None,
-                (C.c_size_t * k)(*[int(c) for c in png_cap]) if png is not None else None, err, _ERRCAP), err)
-            return
-        if png is not None:
-            d_png, png_cap = png
-            if len(d_png) != k or len(png_cap) != k:
-                raise InvalidError("png: (d_png, png_cap) with one entry per recording")
-            cms, layers, pos, npos = None, None, None, None
-            if map is not None:
-                maps = self._maps(map, k)
-                cms, layers = maps[0].settings._c(), maps[0].layers._p
-                pos = (_f64p * k)(*[m.sat_positions.ctypes.data_as(_f64p) for m in maps])
-                npos = (C.c_size_t * k)(*[len(m.sat_positions) for m in maps])
-            cps = _CPngSettings(C.sizeof(_CPngSettings), 0)
-            _check(lib().aptgpu_plan_process_device_image_png(
-                self._p, k, (C.c_void_p * k)(*d_rows), (C.c_size_t * k)(*rows_cap), kind, p, int(rotate),
-                C.byref(ccol) if ccol is not None else None, int(channels), C.byref(cms) if cms is not None else None,
-                layers, pos, npos, (C.c_void_p * k)(*d_images), C.byref(cps), (C.c_void_p * k)(*d_png),
-                (C.c_size_t * k)(*[int(c) for c in png_cap]), err, _ERRCAP), err)
-            return
-        if map is not None:
-            maps = [map] * k if isinstance(map, MapOverlay) else list(map)
-            if len(maps) != k or not all(isinstance(m, MapOverlay) for m in maps):
-                raise InvalidError("map: a MapOverlay or one per recording")
-            if any(m.layers is not maps[0].layers or vars(m.settings) != vars(maps[0].settings) for m in maps):
-                raise InvalidError("map: every recording's MapOverlay must share settings and layers")
-            maps[0].layers._colors(maps[0].settings)
-            cms = maps[0].settings._c()
-            pos = (_f64p * k)(*[m.sat_positions.ctypes.data_as(_f64p) for m in maps])
-            npos = (C.c_size_t * k)(*[len(m.sat_positions) for m in maps])
-            _check(lib().aptgpu_plan_process_device_image_map(
-                self._p, k, (C.c_void_p * k)(*d_rows), (C.c_size_t * k)(*rows_cap), kind, p, int(rotate),
-                C.byref(ccol) if ccol is not None else None, int(channels), C.byref(cms), maps[0].layers._p, pos, npos,
-                (C.c_void_p * k)(*d_images), err, _ERRCAP), err)
-            return
-        _check(lib().aptgpu_plan_process_device_image(self._p, k, (C.c_void_p * k)(*d_rows),
-                                                      (C.c_size_t * k)(*rows_cap), kind, p, int(rotate),
-                                                      C.byref(ccol) if ccol is not None else None, int(channels),
-                                                      (C.c_void_p * k)(*d_images), err, _ERRCAP), err)
+        _check(getattr(lib(), "aptgpu_plan_process_device_image" + req.entry)(
+            self._p, k, (C.c_void_p * k)(*d_rows), (C.c_size_t * k)(*rows_cap), *req.head, *tail, err, _ERRCAP), err)
 
-    def _process_device_image_project(self, d_rows, rows_cap, contrast_adjustment, d_images, rotate, color, channels,
-                                      map, png, orbit, layers, projection):  # noqa: A002
-        k = len(d_rows)
-        settings, d_out, out_cap = projection
-        settings = [settings] * k if isinstance(settings, ProjectionSettings) else list(settings)
-        if len(settings) != k or len(d_out) != k or len(out_cap) != k or \
-                not all(isinstance(q, ProjectionSettings) for q in settings):
-            raise InvalidError("projection: (settings, d_out, out_cap) with one entry per recording")
-        if (map is None) == (orbit is None):
-            raise InvalidError("a projection needs the track: exactly one of map and orbit")
-        ms, lay, pos, npos, ptrs, keep = settings[0].geometry, None, None, None, None, None
-        if orbit is not None:
-            orbits = [orbit] * k if isinstance(orbit, OrbitSettings) else list(orbit)
-            if len(orbits) != k or not all(isinstance(o, OrbitSettings) for o in orbits):
-                raise InvalidError("orbit: an OrbitSettings or one per recording")
-            if orbits[0].draw_map is not None:
-                if not isinstance(layers, MapLayers):
-                    raise InvalidError("OrbitSettings.draw_map needs layers=MapLayers")
-                layers._colors(orbits[0].draw_map)
-                lay, ms = layers, orbits[0].draw_map
-            keep = [o._c() for o in orbits]
-            ptrs = (C.POINTER(_COrbitSettings) * k)(*[C.pointer(c) for c, _ in keep])
-        else:
-            if isinstance(map, MapOverlay) or all(isinstance(m, MapOverlay) for m in map):
-                maps = self._maps(map, k)
-                lay, ms = maps[0].layers, maps[0].settings
-                tracks = [m.sat_positions for m in maps]
-            else:
-                tracks = [np.ascontiguousarray(np.asarray(t, dtype=np.float64).reshape(-1, 2)) for t in map]
-                if len(tracks) != k:
-                    raise InvalidError("map: one sat_positions array per recording")
-            pos = (_f64p * k)(*[t.ctypes.data_as(_f64p) for t in tracks])
-            npos = (C.c_size_t * k)(*[len(t) for t in tracks])
-            keep = tracks
-        if channels is None:
-            channels = 4 if color is not None or lay is not None else 1
-        kind, p = Contrast._c(contrast_adjustment)
-        ccol = color._c() if color is not None else None
-        cms = (ms or MapSettings())._c()
-        cpr = (_CProjectionSettings * k)(*[q._c() for q in settings])
-        cps = _CPngSettings(C.sizeof(_CPngSettings), 0)
-        d_png, png_cap = png if png is not None else (None, None)
-        if png is not None and (len(d_png) != k or len(png_cap) != k):
+    @staticmethod
+    def _png_arrays(png, k):
+        """process_device_image's png = (d_png, png_cap) as the two arrays; (None, None) without."""
+        if png is None:
+            return None, None
+        d_png, png_cap = png
+        if len(d_png) != k or len(png_cap) != k:
             raise InvalidError("png: (d_png, png_cap) with one entry per recording")
-        err = C.create_string_buffer(_ERRCAP)
-        _check(lib().aptgpu_plan_process_device_image_project(
-            self._p, k, (C.c_void_p * k)(*d_rows), (C.c_size_t * k)(*rows_cap), kind, p, int(rotate),
-            C.byref(ccol) if ccol is not None else None, int(channels), C.byref(cms),
-            lay._p if lay is not None else None, pos, npos, ptrs, (C.c_void_p * k)(*d_images), cpr,
-            (C.c_void_p * k)(*d_out), (C.c_size_t * k)(*[int(c) for c in out_cap]), C.byref(cps),
-            (C.c_void_p * k)(*d_png) if png is not None else None,
-            (C.c_size_t * k)(*[int(c) for c in png_cap]) if png is not None else None, err, _ERRCAP), err)
-        del keep
+        return (C.c_void_p * k)(*d_png), (C.c_size_t * k)(*[int(c) for c in png_cap])
 
     def composite_device_images(self, d_images: Sequence[int], heights: Sequence[int], channels: Sequence[int],
                                 projection, d_out: int, out_cap: int, tracks=None, orbit=None,
@@ -3505,17 +3400,11 @@ class Plan:
             raise InvalidError("a composite needs the tracks: exactly one of tracks and orbit")
         pos = npos = ptrs = keep = None
         if orbit is not None:
-            orbits = [orbit] * k if isinstance(orbit, OrbitSettings) else list(orbit)
-            if len(orbits) != k or not all(isinstance(o, OrbitSettings) for o in orbits):
-                raise InvalidError("orbit: an OrbitSettings or one per pass")
-            keep = [o._c() for o in orbits]
-            ptrs = (C.POINTER(_COrbitSettings) * k)(*[C.pointer(c) for c, _ in keep])
+            ptrs, keep = _orbit_pointers(_one_per(orbit, OrbitSettings, k, "orbit", "an OrbitSettings", "pass"))
         else:
-            keep = [np.ascontiguousarray(np.asarray(t, dtype=np.float64).reshape(-1, 2)) for t in tracks]
+            keep, pos, npos = _track_arrays(tracks)
             if len(keep) != k:
                 raise InvalidError("tracks: one sat_positions array per pass")
-            pos = (_f64p * k)(*[t.ctypes.data_as(_f64p) for t in keep])
-            npos = (C.c_size_t * k)(*[len(t) for t in keep])
         maps, keep_maps = _composite_maps(settings, projection, k)
         if settings is None and projection.geometry is None and orbit is not None:
             maps = None  # (each pass's geometry is then its orbit's draw_map, or 0, 1, 1)
@@ -3528,16 +3417,6 @@ class Plan:
             (C.c_int32 * k)(*[int(c) for c in channels]), pos, npos, ptrs, maps, C.byref(cpr), C.byref(cco),
             d_out, int(out_cap), d_coverage, C.byref(cps), d_png, int(png_cap), err, _ERRCAP), err)
         del keep, keep_maps
-
-    @staticmethod
-    def _maps(map, k):  # noqa: A002
-        maps = [map] * k if isinstance(map, MapOverlay) else list(map)
-        if len(maps) != k or not all(isinstance(m, MapOverlay) for m in maps):
-            raise InvalidError("map: a MapOverlay or one per recording")
-        if any(m.layers is not maps[0].layers or vars(m.settings) != vars(maps[0].settings) for m in maps):
-            raise InvalidError("map: every recording's MapOverlay must share settings and layers")
-        maps[0].layers._colors(maps[0].settings)
-        return maps
 
     def png_sizes(self, count=1) -> List[int]:
         """Lengths of the PNG files of the last process_device_image(..., png=...) call (waits for it).  Raises for a
