@@ -6,6 +6,7 @@
  *                   [--tle FILE --sat NAME (--start-ms N | --end-ms N)] [--rotate no|yes|orbit]
  *                   [--project equirect|mercator[:step_deg] [--grid DEG]] [--despeckle R[:T]] [--track=[W,LAMBDA[,LAG]]]
  *                   [--live SECONDS] [--iq FMT:FS:D[:SHIFT_HZ]] [--sun A|B:UNIX_MS[:BLACK] --track FILE]
+ *                   [--land-mask SHAPEFILE_DIR --track FILE]
  *
  * What `noaa-apt in.wav -o out.png` does (main.rs:91-110, noaa_apt.rs:114-235): load -> decode ->
  * contrast limits -> 8-bit image, written as a binary PGM, or with --png as the PNG file the GPU
@@ -48,6 +49,8 @@
  * --sun A|B:UNIX_MS[:BLACK] --track FILE: the rows go through aptgpu_geolocate first, which divides channel A's or B's
  * video by the cosine of the solar zenith angle at every pixel (capped at 80 degrees), for a pass that starts at
  * UNIX_MS; BLACK is the zero level in row units (default: wedge 9 of the telemetry, the zero-modulation wedge).
+ * --land-mask DIR --track FILE: instead of the image, the land / sea / lake mask of the swath (aptgpu_land_mask) from
+ * DIR/countries.shp and DIR/lakes.shp, as a 909-wide PGM of the classes 0 sea, 1 land, 2 lake, 255 invalid.
  * Plain C99, links only libaptgpu.so.
  */
 #include <stdio.h>
@@ -69,14 +72,15 @@ int main(int argc, char **argv)
                 "[--palette FILE] [--lab] [--map SHAPEFILE_DIR --track FILE [--fit]] [--png]\n"
                 "       [--tle FILE --sat NAME (--start-ms N | --end-ms N)] [--rotate no|yes|orbit]\n"
                 "       [--project equirect|mercator[:step_deg] [--grid DEG]] [--despeckle R[:T]] [--track=[W,LAMBDA[,LAG]]]\n"
-                "       [--live SECONDS] [--iq u8|s8|s16|f32:FS:D[:SHIFT_HZ] [--afc[=MAX_HZ]]] [--sun A|B:UNIX_MS[:BLACK] --track FILE]\n", argv[0]);
+                "       [--live SECONDS] [--iq u8|s8|s16|f32:FS:D[:SHIFT_HZ] [--afc[=MAX_HZ]]] [--sun A|B:UNIX_MS[:BLACK] --track FILE]\n"
+                "       [--land-mask SHAPEFILE_DIR --track FILE]\n", argv[0]);
         return 2;
     }
     int contrast = APTGPU_CONTRAST_PERCENT, sync = 1, lab = 0, png = 0, fit = 0;
     const char *palette_path = NULL, *map_dir = NULL, *track_path = NULL, *tle_path = NULL, *sat = NULL;
     int rotate = APTGPU_ROTATE_NO, ref_kind = -1;
     long long ref_ms = 0;
-    const char *project = NULL, *despeckle = NULL, *flywheel = NULL, *iq_spec = NULL, *sun = NULL;
+    const char *project = NULL, *despeckle = NULL, *flywheel = NULL, *iq_spec = NULL, *sun = NULL, *land_dir = NULL;
     double grid_deg = 0.0, live_seconds = 0.0, afc_max_hz = 15000.0;
     int afc = 0;
     for (int i = 3; i < argc; ++i) {
@@ -103,6 +107,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--live") && i + 1 < argc) live_seconds = atof(argv[++i]);
         else if (!strcmp(argv[i], "--iq") && i + 1 < argc) iq_spec = argv[++i];
         else if (!strcmp(argv[i], "--sun") && i + 1 < argc) sun = argv[++i];
+        else if (!strcmp(argv[i], "--land-mask") && i + 1 < argc) land_dir = argv[++i];
         else if (!strcmp(argv[i], "--afc")) afc = 1;
         else if (!strncmp(argv[i], "--afc=", 6)) afc = 1, afc_max_hz = atof(argv[i] + 6); /* (0 or no number: refused by the library) */
         else if (!strcmp(argv[i], "--rotate") && i + 1 < argc) {
@@ -415,6 +420,64 @@ int main(int argc, char **argv)
                 (unsigned long long)gr.height * 909ull);
         aptgpu_free(rows);
         rows = normalised;
+    }
+
+    if (land_dir) {
+        /* the land / sea / lake mask of the swath (aptgpu_land_mask) from DIR/countries.shp and DIR/lakes.shp, written as
+         * a 909-wide PGM of the classes 0 sea, 1 land, 2 lake, 255 invalid instead of the image */
+        const size_t height = n_rows_px / 2080;
+        int failed = 1;
+        double *track = malloc((height ? height : 1) * 2 * sizeof(double));
+        FILE *t = track_path ? fopen(track_path, "rb") : NULL;
+        aptgpu_map_layers *layers = NULL;
+        uint8_t *mask = NULL;
+        FILE *out = NULL;
+        if (!track || !t || fread(track, sizeof(double), 2 * height, t) != 2 * height || fgetc(t) != EOF) {
+            fprintf(stderr, "--land-mask DIR needs --track FILE with exactly %zu (lat, lon) f64 pairs\n", height);
+            goto land_done;
+        }
+        if (aptgpu_map_layers_create(&layers) != APTGPU_OK) goto land_done;
+        {
+            const char *files[2] = {"countries.shp", "lakes.shp"};
+            const int which[2] = {APTGPU_MAP_COUNTRIES, APTGPU_MAP_LAKES};
+            for (int k = 0; k < 2; k++) {
+                char path[4096];
+                double *xy = NULL;
+                uint32_t *parts = NULL;
+                size_t n_points = 0, n_parts = 0;
+                snprintf(path, sizeof path, "%s/%s", land_dir, files[k]);
+                rc = aptgpu_map_read_shapefile(path, 5, &xy, &n_points, &parts, &n_parts, err, sizeof err);
+                if (rc == APTGPU_OK) rc = aptgpu_map_layers_set(layers, which[k], xy, n_points, parts, n_parts, err, sizeof err);
+                aptgpu_free(xy);
+                aptgpu_free(parts);
+                if (rc != APTGPU_OK) { fprintf(stderr, "--land-mask: %s (%d): %s\n", path, rc, err); goto land_done; }
+            }
+        }
+        {
+            aptgpu_land_mask_result lr;
+            memset(&lr, 0, sizeof lr);
+            lr.struct_size = sizeof lr;
+            rc = aptgpu_land_mask(&ctx, height, track, height, NULL, NULL, layers, NULL, &mask, &lr, err, sizeof err);
+            if (rc != APTGPU_OK) { fprintf(stderr, "land mask failed (%d): %s\n", rc, err); goto land_done; }
+            fprintf(stderr, "land mask: %llu sea, %llu land, %llu lake, %llu invalid of %zu rows x 909\n",
+                    (unsigned long long)lr.n_sea, (unsigned long long)lr.n_land, (unsigned long long)lr.n_lake,
+                    (unsigned long long)lr.n_invalid, height);
+        }
+        out = fopen(argv[2], "wb");
+        if (!out) { perror(argv[2]); goto land_done; }
+        if (fprintf(out, "P5\n909 %zu\n255\n", height) < 0 || fwrite(mask, 1, height * 909, out) != height * 909) {
+            fprintf(stderr, "%s: short write\n", argv[2]);
+            goto land_done;
+        }
+        failed = 0;
+    land_done:
+        if (out && fclose(out) != 0 && !failed) { perror(argv[2]); failed = 1; }
+        if (t) fclose(t);
+        free(track);
+        aptgpu_map_layers_destroy(layers);
+        aptgpu_free(mask);
+        aptgpu_free(rows);
+        return failed;
     }
 
     uint8_t *image = NULL;

@@ -1181,6 +1181,106 @@ int aptgpu_fit_overlay_host(const uint8_t *image, size_t height, const double *s
 int aptgpu_fit_sample_points(const aptgpu_map_layers *layers, uint32_t layer_mask, double spacing_deg, double **xy,
                              size_t *n_points, char *err, size_t err_cap);
 
+/* ---- land / sea / lake mask of the swath, and map-coloured false colour ----
+ * Whether a point of the Earth is land, sea or lake, from the polygons of the layer set (countries.shp and lakes.shp,
+ * which the overlay only ever draws as outlines).  The reference has nothing like it, so the definition is this
+ * library's; tests/np_landmask_model.py states it in numpy.  Opt-in, a stage of its own; nothing else changes when it
+ * is not called.
+ *  - Classes, one uint8 per point: APTGPU_LAND_SEA 0, APTGPU_LAND_LAND 1, APTGPU_LAND_LAKE 2, APTGPU_LAND_INVALID 255: a
+ *    NaN lat or lon, which is what the geolocation stage returns beyond 60 degrees of arc.  A point is lake if `lake`,
+ *    else land if `land`, else sea: land = the crossing count against all rings of APTGPU_MAP_COUNTRIES is odd, lake =
+ *    the count against all rings of APTGPU_MAP_LAKES is odd.  Even-odd over the whole layer: holes and enclaves come
+ *    out right, shapes that overlap in sloppy data come out as their parity.  An absent layer counts 0.
+ *  - Edges: the consecutive vertex pairs of every part, and a closing edge from the last vertex to the first where the
+ *    two differ.  Coordinates are the layer's own f64 degrees (lon = x, lat = y), untouched.  A non-finite vertex is
+ *    APTGPU_ERR_INVALID ("land mask: a vertex of the layer set is not finite") when the table is built:
+ *    aptgpu_map_layers_set and the shapefile reader take such vertices as they come.
+ *  - Point: (lat, lon) in radians; py = lat * 57.29577951308232, px = lon * 57.29577951308232 (one f64 multiply each).
+ *  - Crossing rule, a ray going east; every operation is an f64 operation rounded on its own, never contracted:
+ *      straddle = (y1 > py) != (y2 > py)
+ *      d        = (x2 - x1) * (py - y1) - (px - x1) * (y2 - y1)
+ *      crossing = straddle && (y2 > y1 ? d > 0 : d < 0)
+ *    No division, no libm call, no epsilon.  The count is an integer: it does not depend on the order or grouping of
+ *    the edges, so any acceleration structure is exact.  A horizontal edge never straddles and a point on a vertex or on
+ *    an edge falls on the side the half-open rule gives it.
+ *  - Acceleration: n_bands latitude bands (default 720, in [1, 7200]),
+ *      band(y) = clamp((int) floor((y + 90.0) * (n_bands / 180.0)), 0, n_bands - 1),
+ *    an edge is listed in bands band(min(y1, y2)) .. band(max(y1, y2)), horizontal edges are dropped.  band() is
+ *    monotone, so the band of py lists every edge that can straddle py, each once; a point counts the edges of its own
+ *    band only.  The output does not depend on n_bands.
+ *  - Swath form: the points are those of the geolocation stage above (same track or orbit, same map settings), row r,
+ *    video column k at mask[r * 909 + k]; the lat / lon plane is never written.  Record reasons as there: 7, 10, 15, 16.
+ *    The host-array forms return APTGPU_ERR_INTERNAL with the record filled and no mask; the plan form writes 255 over
+ *    the rows and counts them invalid.
+ *  - The record counts the four classes and gives the table's size: non-horizontal edges per layer and the band entries
+ *    of both layers together. */
+#define APTGPU_LAND_SEA 0
+#define APTGPU_LAND_LAND 1
+#define APTGPU_LAND_LAKE 2
+#define APTGPU_LAND_INVALID 255
+typedef struct aptgpu_land_mask_settings {
+    uint32_t struct_size;  /* sizeof(aptgpu_land_mask_settings) */
+    uint32_t flags;        /* 0; any set bit is APTGPU_ERR_INVALID */
+    int32_t n_bands;       /* 1 .. 7200; the bindings default to 720 */
+    int32_t reserved;      /* 0 */
+} aptgpu_land_mask_settings;
+typedef struct aptgpu_land_mask_result {
+    uint32_t struct_size;  /* the caller's sizeof(aptgpu_land_mask_result) */
+    int32_t status;        /* APTGPU_OK or APTGPU_ERR_INTERNAL */
+    int32_t reason;        /* 0, 7, 10, 15, 16 */
+    uint32_t height;       /* whole rows (0 in the plane forms) */
+    uint64_t n_sea, n_land, n_lake, n_invalid;
+    uint32_t n_edges[2];   /* non-horizontal edges of countries, lakes */
+    uint64_t n_band_entries; /* records of the table, both layers */
+} aptgpu_land_mask_result;
+/* The swath form: height rows, exactly one of sat_positions (n_positions pairs) and orbit, map nullable (0, 1, 1),
+ * layers required with countries or lakes present, settings nullable (720 bands).  *mask: malloc'd, height * 909
+ * bytes (aptgpu_free); info nullable (its struct_size set by the caller).  Refused before a device is touched
+ * (APTGPU_ERR_INVALID): a null or empty layer set, a struct_size that is too small, a flag, n_bands out of range. */
+int aptgpu_land_mask(const aptgpu_context *ctx, size_t height, const double *sat_positions, size_t n_positions,
+                     const aptgpu_orbit_settings *orbit, const aptgpu_map_settings *map,
+                     const aptgpu_map_layers *layers, const aptgpu_land_mask_settings *settings, uint8_t **mask,
+                     aptgpu_land_mask_result *info, char *err, size_t err_cap);
+/* The same on the CPU, in plain C++ (no GPU needed). */
+int aptgpu_land_mask_host(size_t height, const double *sat_positions, size_t n_positions,
+                          const aptgpu_orbit_settings *orbit, const aptgpu_map_settings *map,
+                          const aptgpu_map_layers *layers, const aptgpu_land_mask_settings *settings, uint8_t **mask,
+                          aptgpu_land_mask_result *info, char *err, size_t err_cap);
+/* The plane form: n (lat, lon) pairs of f64 in radians, interleaved, of any shape (the plane of aptgpu_geolocate, the
+ * lat / lon of a map grid).  latlon null or not 8-byte aligned: APTGPU_ERR_INVALID.  *mask: n bytes. */
+int aptgpu_land_mask_plane(const aptgpu_context *ctx, const double *latlon, size_t n, const aptgpu_map_layers *layers,
+                           const aptgpu_land_mask_settings *settings, uint8_t **mask, aptgpu_land_mask_result *info,
+                           char *err, size_t err_cap);
+int aptgpu_land_mask_plane_host(const double *latlon, size_t n, const aptgpu_map_layers *layers,
+                                const aptgpu_land_mask_settings *settings, uint8_t **mask,
+                                aptgpu_land_mask_result *info, char *err, size_t err_cap);
+/* Device-resident, chained behind the last aptgpu_plan_decode_device call on each recording's stream (the height comes
+ * from the decode record on the device; with a rows_cap below it, rows_cap rows).  Tracks and orbits as
+ * aptgpu_plan_geolocate_device.  d_mask[i] holds rows_cap[i] * 909 bytes and may not overlap a rows buffer or another
+ * mask.  The table is built once per layer set and band count and uploaded once per slot.  Timer names:
+ * image_geoloc_track, image_geoloc_rows, image_land_mask. */
+int aptgpu_plan_land_mask_device(aptgpu_plan *plan, int count, const float *const *d_rows, const size_t *rows_cap,
+                                 const double *const *sat_positions, const size_t *n_positions,
+                                 const aptgpu_orbit_settings *const *orbit, const aptgpu_map_settings *map,
+                                 const aptgpu_map_layers *layers, const aptgpu_land_mask_settings *settings,
+                                 uint8_t *const *d_mask, char *err, size_t err_cap);
+/* Waits for the land mask stage of the last call and copies the records (each results[i].struct_size set). */
+int aptgpu_plan_land_mask_results(aptgpu_plan *plan, int count, aptgpu_land_mask_result *results);
+/* Map-coloured false colour: image is the un-rotated gray image of aptgpu_process_image (height rows of 2080 bytes),
+ * mask a swath mask of mask_height rows of 909 bytes (mask_height != height: APTGPU_ERR_INVALID), palettes three
+ * 256 x 256 x 3 RGB images for sea, land and lake, each of palette_bytes[k] bytes (anything but 196608:
+ * APTGPU_ERR_INVALID), tunes = {ch_a_tune_start, ch_a_tune_end, ch_b_tune_start, ch_b_tune_end}.  *rgba: malloc'd,
+ * height * 2080 * 4 bytes.  Every pixel is (v, v, v, 255) except channel A's video columns x in [86, 995): there
+ * c = mask[y * 909 + x - 86], and for c in {0, 1, 2} the pixel is palette_c[val_b][val_a] with alpha 255, (val_a, val_b)
+ * from tune_input_values (processing.rs:125-140) of the pixel and of its channel-B partner 1040 columns on, as in
+ * aptgpu_process_image's false colour; c == 255 stays gray.  Rotation is the caller's business, afterwards. */
+int aptgpu_false_color_masked(const aptgpu_context *ctx, const uint8_t *image, size_t height, const uint8_t *mask,
+                              size_t mask_height, const uint8_t *const *palettes, const size_t *palette_bytes,
+                              const float tunes[4], uint8_t **rgba, char *err, size_t err_cap);
+int aptgpu_false_color_masked_host(const uint8_t *image, size_t height, const uint8_t *mask, size_t mask_height,
+                                   const uint8_t *const *palettes, const size_t *palette_bytes, const float tunes[4],
+                                   uint8_t **rgba, char *err, size_t err_cap);
+
 /* ====================================================================== */
 /* 4b. FM demodulation of IQ recordings, in front of decode() */
 /* ====================================================================== */

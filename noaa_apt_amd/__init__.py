@@ -42,6 +42,9 @@ Names, argument meaning and error behaviour follow the reference:
     fit_overlay, fit_overlay_host, fit_overlay_device,     the reference's to-do list, docs/development.md:90: yaw, scales
     fit_sample_points, margin_track, FitSettings,          and the time offset fitted to the image's edges, DESIGN.md §26
     OverlayFit
+    land_mask, land_mask_plane (each with a _host form),   what every APT user knows from WXtoImg's map-coloured
+    false_color_masked, LandMaskSettings,                  enhancements: land, sea or lake per swath pixel from the layer
+    Plan.land_mask_device                                  set's polygons, and a palette per class, DESIGN.md §28
     fm_demodulate, fm_demodulate_host, fm_demodulate_wav,  FM demodulation of an IQ recording in front of decode()
     fm_design, load_iq, IqFormat, FmSettings,              (the reference takes audio only, docs/usage.md:87),
     FmDemodulator                                          DESIGN.md §20
@@ -80,6 +83,8 @@ from .api import (  # noqa: F401
     GEOLOC_PX, GEOLOC_REASON_HEIGHT, GEOLOC_REASON_DECODE,
     FitSettings, FitResult, FitRound, OverlayFit, fit_overlay, fit_overlay_host, fit_overlay_device, fit_sample_points,
     margin_track, FIT_REASON_NO_CANDIDATE, FIT_REASON_FLAT, FIT_SCORE_DTYPE,
+    LandMaskSettings, LandMaskResult, land_mask, land_mask_host, land_mask_plane, land_mask_plane_host,
+    false_color_masked, false_color_masked_host, LAND_SEA, LAND_LAND, LAND_LAKE, LAND_INVALID,
     IqFormat, FmSettings, FmInfo, FmDemodulator, fm_demodulate, fm_demodulate_host, fm_demodulate_wav, fm_design, load_iq,
     FM_SWAP_IQ, FM_MAX_BATCH,
     AfcSettings, AfcInfo, AfcTable, FmAfc, AFC_RECORD_DTYPE, fm_afc_design, fm_afc_sums, fm_afc_sums_host,

@@ -256,6 +256,19 @@ class GeolocResult(C.Structure):
                 ("n_outside", C.c_uint64), ("n_capped", C.c_uint64), ("cos_min", C.c_float), ("cos_max", C.c_float)]
 
 
+class _CLandMaskSettings(C.Structure):
+    """aptgpu_land_mask_settings"""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n_bands", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LandMaskResult(C.Structure):
+    """aptgpu_land_mask_result: the height (0 in the plane forms), the points of each class and the size of the
+    acceleration table (non-horizontal edges of countries and lakes, band entries of both)."""
+    _fields_ = [("struct_size", C.c_uint32), ("status", C.c_int32), ("reason", C.c_int32), ("height", C.c_uint32),
+                ("n_sea", C.c_uint64), ("n_land", C.c_uint64), ("n_lake", C.c_uint64), ("n_invalid", C.c_uint64),
+                ("n_edges", C.c_uint32 * 2), ("n_band_entries", C.c_uint64)]
+
+
 class _CFitSettings(C.Structure):
     """aptgpu_fit_settings"""
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("channel", C.c_int32), ("layer_mask", C.c_uint32),
@@ -572,6 +585,20 @@ def lib():
     L.aptgpu_fit_overlay_device.argtypes = [cp, vp, sz, vp, *fit]
     L.aptgpu_fit_overlay_host.argtypes = [_u8p, sz, *fit]
     L.aptgpu_fit_sample_points.argtypes = [vp, C.c_uint32, C.c_double, C.POINTER(_f64p), C.POINTER(sz), C.c_char_p, sz]
+    clm, rlm = C.POINTER(_CLandMaskSettings), C.POINTER(LandMaskResult)
+    land = (sz, _f64p, sz, C.POINTER(_COrbitSettings), C.POINTER(_CMapSettings), vp, clm, C.POINTER(_u8p), rlm,
+            C.c_char_p, sz)
+    L.aptgpu_land_mask.argtypes = [cp, *land]
+    L.aptgpu_land_mask_host.argtypes = [*land]
+    L.aptgpu_land_mask_plane.argtypes = [cp, vp, sz, vp, clm, C.POINTER(_u8p), rlm, C.c_char_p, sz]
+    L.aptgpu_land_mask_plane_host.argtypes = [vp, sz, vp, clm, C.POINTER(_u8p), rlm, C.c_char_p, sz]
+    L.aptgpu_plan_land_mask_device.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(sz), C.POINTER(_f64p), C.POINTER(sz),
+                                               C.POINTER(C.POINTER(_COrbitSettings)), C.POINTER(_CMapSettings), vp, clm,
+                                               C.POINTER(vp), C.c_char_p, sz]
+    L.aptgpu_plan_land_mask_results.argtypes = [vp, i32, rlm]
+    fcm = (_u8p, sz, _u8p, sz, C.POINTER(vp), C.POINTER(sz), _f32p, C.POINTER(_u8p), C.c_char_p, sz)
+    L.aptgpu_false_color_masked.argtypes = [cp, *fcm]
+    L.aptgpu_false_color_masked_host.argtypes = [*fcm]
     cfm = C.POINTER(_CFmSettings)
     fm_out = (C.POINTER(_f32p), C.POINTER(sz), _u32p, C.c_char_p, sz)
     L.aptgpu_fm_default_settings.argtypes = [cfm]
@@ -2277,6 +2304,152 @@ def normalize_sun(signal, track_or_orbit, channel, black=None, ref_time=None, ma
     return (rows, info) if return_info else rows
 
 
+LAND_SEA, LAND_LAND, LAND_LAKE, LAND_INVALID = 0, 1, 2, 255
+
+
+class LandMaskSettings:
+    """aptgpu_land_mask_settings.  n_bands: the latitude bands of the acceleration table, 1 .. 7200; the mask does not
+    depend on it."""
+
+    def __init__(self, n_bands=720, flags=0):
+        self.n_bands, self.flags = n_bands, flags
+
+    def _c(self, struct_size=None):
+        return _CLandMaskSettings(C.sizeof(_CLandMaskSettings) if struct_size is None else int(struct_size),
+                                  int(self.flags), int(self.n_bands), 0)
+
+
+def _land_c(layers, settings):
+    settings = settings if settings is not None else LandMaskSettings()
+    if not isinstance(settings, LandMaskSettings):
+        raise InvalidError("land mask: settings must be a LandMaskSettings")
+    if not isinstance(layers, MapLayers):
+        raise InvalidError("land mask: layers must be a MapLayers")
+    try:
+        return settings._c()
+    except (TypeError, ValueError, OverflowError) as e:
+        raise InvalidError(f"land mask: {e}") from None
+
+
+def _land_info():
+    info = LandMaskResult()
+    info.struct_size = C.sizeof(LandMaskResult)
+    return info
+
+
+def _land_call(fn, head, height_or_signal, track_or_orbit, layers, map_settings, settings):
+    if isinstance(height_or_signal, (int, np.integer)):
+        h = int(height_or_signal)
+    else:
+        h = np.asarray(height_or_signal).size // PX_PER_ROW
+    if h < 0:
+        raise InvalidError("land mask: the height is negative")
+    cs = _land_c(layers, settings)
+    if map_settings is not None and not isinstance(map_settings, MapSettings):
+        raise InvalidError("land mask: map_settings must be a MapSettings or None")
+    cms = map_settings._c() if map_settings is not None else None
+    pos, count, co, keep = None, 0, None, None
+    if isinstance(track_or_orbit, OrbitSettings):
+        c_orbit, keep = track_or_orbit._c()
+        co = C.byref(c_orbit)
+    elif track_or_orbit is not None:
+        keep = np.ascontiguousarray(np.asarray(track_or_orbit, dtype=np.float64).reshape(-1, 2))
+        pos, count = keep.ctypes.data_as(_f64p), keep.shape[0]
+    p_mask, info = _u8p(), _land_info()
+    err = C.create_string_buffer(_ERRCAP)
+    try:
+        _check(fn(*head, h, pos, count, co, C.byref(cms) if cms is not None else None, layers._p, C.byref(cs),
+                  C.byref(p_mask), C.byref(info), err, _ERRCAP), err)
+    except AptError as e:
+        e.info = info  # (the record of a failed call: status, reason, height)
+        raise
+    del keep
+    return _take(p_mask, h * GEOLOC_PX, np.uint8).reshape(h, GEOLOC_PX), info
+
+
+def land_mask(height_or_signal, track_or_orbit, layers, map_settings=None, settings=None, context=None):
+    """Whether every video pixel of the swath shows sea, land or a lake, on the GPU: the even-odd rule
+    against the polygons of the layer set's countries and lakes at the geolocation stage's points, which are computed
+    in the kernel (the lat / lon plane is never written).  height_or_signal: the number of rows, or the decoded rows.
+    track_or_orbit: the satellite's (lat, lon) in radians per row, or an OrbitSettings (SGP4 then runs on the GPU).
+    Returns (mask, info): the height x 909 uint8 classes LAND_SEA, LAND_LAND, LAND_LAKE, LAND_INVALID (beyond 60 degrees
+    of arc from the track's start) and the LandMaskResult.  A failed call (fewer than two rows, a track of another
+    length, SGP4) raises InternalError whose `info` attribute is the record."""
+    cctx = (context or Context())._c()
+    return _land_call(lib().aptgpu_land_mask, (C.byref(cctx),), height_or_signal, track_or_orbit, layers, map_settings,
+                      settings)
+
+
+def land_mask_host(height_or_signal, track_or_orbit, layers, map_settings=None, settings=None):
+    """land_mask() on the CPU, in plain C++ (no GPU needed): geolocate_host()'s points, the same source text per edge."""
+    return _land_call(lib().aptgpu_land_mask_host, (), height_or_signal, track_or_orbit, layers, map_settings, settings)
+
+
+def _land_plane_call(fn, head, latlon, layers, settings):
+    cs = _land_c(layers, settings)
+    ll = np.asarray(latlon)
+    if ll.dtype != np.float64 or not ll.flags.c_contiguous:
+        ll = np.ascontiguousarray(ll, dtype=np.float64)
+    if ll.ndim < 1 or ll.shape[-1] != 2:
+        raise InvalidError("land mask: the last axis of the plane holds (lat, lon)")
+    n = ll.size // 2
+    p_mask, info = _u8p(), _land_info()
+    err = C.create_string_buffer(_ERRCAP)
+    _check(fn(*head, C.c_void_p(ll.ctypes.data), n, layers._p, C.byref(cs), C.byref(p_mask), C.byref(info), err,
+              _ERRCAP), err)
+    return _take(p_mask, n, np.uint8).reshape(ll.shape[:-1]), info
+
+
+def land_mask_plane(latlon, layers, settings=None, context=None):
+    """The classes of arbitrary points, on the GPU: latlon is a (..., 2) float64 array of (lat, lon) in radians, such as
+    geolocate()'s plane or the lat / lon of a map grid; a NaN in either is LAND_INVALID.  Returns (mask, info), the mask
+    of latlon's shape without its last axis."""
+    cctx = (context or Context())._c()
+    return _land_plane_call(lib().aptgpu_land_mask_plane, (C.byref(cctx),), latlon, layers, settings)
+
+
+def land_mask_plane_host(latlon, layers, settings=None):
+    """land_mask_plane() on the CPU, in plain C++ (no GPU needed)."""
+    return _land_plane_call(lib().aptgpu_land_mask_plane_host, (), latlon, layers, settings)
+
+
+def _masked_color_call(fn, head, image, mask, palettes, tunes):
+    image = np.ascontiguousarray(image, dtype=np.uint8)
+    if image.ndim != 2 or image.shape[1] != PX_PER_ROW:
+        raise InvalidError("false_color_masked: the image is an unrotated (height, 2080) uint8 array")
+    mask = np.ascontiguousarray(mask, dtype=np.uint8)
+    if mask.ndim != 2 or mask.shape[1] != GEOLOC_PX:
+        raise InvalidError("false_color_masked: the mask is a (height, 909) uint8 array")
+    pals = [np.ascontiguousarray(p, dtype=np.uint8) for p in palettes]
+    if len(pals) != 3:
+        raise InvalidError("false_color_masked: three palettes (sea, land, lake)")
+    tn = np.ascontiguousarray(tunes, dtype=np.float32)
+    if tn.shape != (4,):
+        raise InvalidError("false_color_masked: tunes are (ch_a_start, ch_a_end, ch_b_start, ch_b_end)")
+    h = image.shape[0]
+    out = _u8p()
+    err = C.create_string_buffer(_ERRCAP)
+    _check(fn(*head, image.ctypes.data_as(_u8p), h, mask.ctypes.data_as(_u8p), mask.shape[0],
+              (C.c_void_p * 3)(*[p.ctypes.data for p in pals]), (C.c_size_t * 3)(*[p.nbytes for p in pals]),
+              tn.ctypes.data_as(_f32p), C.byref(out), err, _ERRCAP), err)
+    return _take(out, h * PX_PER_ROW * 4, np.uint8).reshape(h, PX_PER_ROW, 4)
+
+
+def false_color_masked(image, mask, palettes, tunes=(0.0, 0.0, 0.0, 0.0), context=None):
+    """Map-coloured false colour, on the GPU: the unrotated gray image of process(rotate=Rotate.NO),
+    (height, 2080) uint8, coloured over channel A's video columns by the palette of each pixel's class.  mask: the
+    (height, 909) mask of land_mask(); palettes: three (256, 256, 3) uint8 arrays indexed [b, a], for sea, land and
+    lake; tunes: ColorSettings' four tune values.  Returns (height, 2080, 4) RGBA; LAND_INVALID pixels and everything
+    outside the video columns stay gray.  Rotate afterwards if the pass needs it."""
+    cctx = (context or Context())._c()
+    return _masked_color_call(lib().aptgpu_false_color_masked, (C.byref(cctx),), image, mask, palettes, tunes)
+
+
+def false_color_masked_host(image, mask, palettes, tunes=(0.0, 0.0, 0.0, 0.0)):
+    """false_color_masked() on the CPU, in plain C++ (no GPU needed)."""
+    return _masked_color_call(lib().aptgpu_false_color_masked_host, (), image, mask, palettes, tunes)
+
+
 FIT_REASON_NO_CANDIDATE = 17
 FIT_REASON_FLAT = 18
 FIT_SCORE_DTYPE = np.dtype([("score", np.uint64), ("count", np.uint32), ("zero", np.uint32)])
@@ -3313,6 +3486,39 @@ class Plan:
         for r in arr:
             r.struct_size = C.sizeof(GeolocResult)
         _check(lib().aptgpu_plan_geoloc_results(self._p, count, arr))
+        return list(arr)
+
+    def land_mask_device(self, d_rows: Sequence[int], rows_cap: Sequence[int], tracks_or_orbits, layers,
+                         d_mask: Sequence[int], settings=None, map_settings=None):
+        """The land mask of the recordings of the last decode_device call, chained on the device behind their decode
+        (the height comes from the decode record).  tracks_or_orbits as geolocate_device().  d_mask[i] holds
+        rows_cap[i] * 909 bytes.  Records through land_mask_results()."""
+        k = len(d_rows)
+        if len(tracks_or_orbits) != k or len(d_mask) != k:
+            raise InvalidError("land mask: one track or orbit and one mask per recording")
+        orbits = [isinstance(t, OrbitSettings) for t in tracks_or_orbits]
+        if any(orbits) and not all(orbits):
+            raise InvalidError("land mask: tracks or orbits, not both")
+        cs = _land_c(layers, settings)
+        if map_settings is not None and not isinstance(map_settings, MapSettings):
+            raise InvalidError("land mask: map_settings must be a MapSettings or None")
+        cms = map_settings._c() if map_settings is not None else None
+        pos = cnt = orb = None
+        if k and all(orbits):
+            orb, keep = _orbit_pointers(tracks_or_orbits)
+        else:
+            keep, pos, cnt = _track_arrays(tracks_or_orbits)
+        err = C.create_string_buffer(_ERRCAP)
+        _check(lib().aptgpu_plan_land_mask_device(self._p, k, (C.c_void_p * k)(*d_rows), (C.c_size_t * k)(*rows_cap),
+                                                  pos, cnt, orb, C.byref(cms) if cms is not None else None, layers._p,
+                                                  C.byref(cs), (C.c_void_p * k)(*d_mask), err, _ERRCAP), err)
+        del keep
+
+    def land_mask_results(self, count=1) -> List["LandMaskResult"]:
+        arr = (LandMaskResult * count)()
+        for r in arr:
+            r.struct_size = C.sizeof(LandMaskResult)
+        _check(lib().aptgpu_plan_land_mask_results(self._p, count, arr))
         return list(arr)
 
     def thermal_results(self, count=1) -> List["ThermalResult"]:

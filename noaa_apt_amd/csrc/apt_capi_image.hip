@@ -232,13 +232,8 @@ void color_args(ImageRequest &q, int contrast, float percent, int rotate, const 
     }
     if (channels != 4) throw Error{ErrorKind::Invalid, "false colour needs channels = 4 (RGBA)"};
     // tune_input_values (processing.rs:126-140): the per-call part, f32 as the reference rounds it
-    const float factor = 0.3f;
-    const float s_a = color->ch_a_tune_start * factor, e_a = color->ch_a_tune_end * factor;
-    const float s_b = color->ch_b_tune_start * factor, e_b = color->ch_b_tune_end * factor;
-    q.tune.k_a = 1.f + e_a - s_a;
-    q.tune.o_a = s_a * 255.f;
-    q.tune.k_b = 1.f + e_b - s_b;
-    q.tune.o_b = s_b * 255.f;
+    q.tune = apt::gpu::color_tune_of(color->ch_a_tune_start, color->ch_a_tune_end, color->ch_b_tune_start,
+                                     color->ch_b_tune_end);
     q.colored = true;
     q.palette = color->palette_rgb;
 }

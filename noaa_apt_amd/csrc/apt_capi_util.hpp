@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <mutex>
 #include <new>
 #include <string>
 #include <type_traits>
@@ -18,6 +19,10 @@
 // the opaque layer-set handle of include/aptgpu.h (apt_capi_image.hip creates and fills it)
 struct aptgpu_map_layers {
     apt::map::Layers layers;
+    // the land mask's acceleration table of `layers` (apt_kernels_landmask.hpp), built on first use and again when the
+    // layers' generation or the band count change; type-erased so that only the land mask's unit needs its header
+    mutable std::shared_ptr<const void> land_table;
+    mutable std::mutex land_mutex;
 };
 
 namespace apt::capi {

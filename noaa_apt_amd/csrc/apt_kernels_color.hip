@@ -76,15 +76,7 @@ __device__ inline uint64_t rotate_src(uint64_t r, uint32_t c, uint64_t rows)
     return (rows - 1 - r) * kPx + base + (kW - 1 - (c - base));
 }
 
-// tune_input_values (processing.rs:126-140): `(in * k - o).clamp(0., 255.) as u32`; clamp keeps a
-// NaN and `as u32` makes it 0
-__device__ inline uint32_t tune(uint32_t in, float k, float o)
-{
-    const float t = static_cast<float>(in) * k - o;
-    if (t != t) return 0u;
-    const float c = t < 0.f ? 0.f : (t > 255.f ? 255.f : t);
-    return static_cast<uint32_t>(c);
-}
+// (tune_input_values, processing.rs:126-140: tune() of apt_color_tune.hpp)
 
 __device__ inline bool aligned16(const void *p)
 {

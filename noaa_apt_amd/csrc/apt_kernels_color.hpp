@@ -7,16 +7,11 @@
 // pixel count from the decode result record on the device when one is given.
 #pragma once
 
+#include "apt_color_tune.hpp"  // ColorTune, tune()
 #include "apt_kernels.hpp"
 #include "apt_lab.hpp"
 
 namespace apt::gpu {
-
-// The false colour tune of one channel (processing.rs:126-140) with the settings folded in on the
-// host: s' = start * 0.3f, e' = end * 0.3f, k = (1 + e') - s', o = s' * 255; out = in * k - o.
-struct ColorTune {
-    float k_a, o_a, k_b, o_b;
-};
 
 // Scratch of the colour stage: two 256-bin histograms (channel A, channel B), two 256-entry u8
 // equalisation tables, the palette as 65536 packed RGBA words (A = 255).  color_ws_init zeroes the

@@ -183,6 +183,7 @@ void launch_pixels(hipStream_t s, const GeolocLaunch &l, apt::map::Device &dev, 
 
 size_t geoloc_ws_bytes(size_t rows) { return kSunOffset + 3 * (rows ? rows : 1) * sizeof(double); }
 GeolocRecord *geoloc_ws_record(void *ws) { return &view(ws)->rec; }
+const apt::geoloc::Frame *geoloc_ws_frame(void *ws) { return &view(ws)->frame; }
 
 void geoloc_record_to_public(const GeolocRecord &r, aptgpu_geoloc_result *out)
 {

@@ -209,6 +209,8 @@ void geoloc_record_to_public(const GeolocRecord &r, aptgpu_geoloc_result *out);
 // them, the per-row sun vectors of `rows` rows.
 size_t geoloc_ws_bytes(size_t rows);
 GeolocRecord *geoloc_ws_record(void *ws);
+// the frame k_geoloc_rows wrote there (what a stage behind the track and row launches reads: apt_kernels_landmask.hpp)
+const apt::geoloc::Frame *geoloc_ws_frame(void *ws);
 
 // One recording's launches on s.  x (nullable unless out_rows), res, n, cap: as for the image stages (the sample count
 // comes from the decode record on the device when res is set; cap bounds it and sizes the launches; cap / 2080 rows

@@ -190,6 +190,7 @@ struct aptgpu_plan : apt::PlanDesign {
         apt::DeviceBuffer<char> thermal_ws;    // record, pixel parameters, telemetry record and row means of the thermal stage, on first use
         apt::DeviceBuffer<char> geoloc_ws;     // record, frame, height record and per-row sun vectors of the geolocation stage, on first use
         size_t geoloc_rows = 0;                // rows geoloc_ws has room for
+        std::shared_ptr<void> landmask;        // the land mask stage's table, record and scratch (apt_capi_landmask.hip), on first use
         apt::DeviceBuffer<char> track_ws;      // scores, back-pointers, position lists and record of the flywheel sync stage, on first use
         std::unique_ptr<apt::map::Device> map;  // the map overlay's layer set, lists and track, on first use
         std::unique_ptr<apt::project::Device> project;  // the reprojection's graticule, record and PNG scratch, on first use
